@@ -10,6 +10,7 @@ is fixed as N grows (weak scaling); value = cells filled by all ranks per second
     python bench.py --gpus 1 --steps 20 --warmup 3          # configs[1]: single discount a=0.5
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8   # one discount per GPU
     python bench.py --discounts-per-gpu 8                    # the batched mode (configs[2] shape)
+    python bench.py --steps 20 --dump-outputs bench_outputs  # + the last timed step's results as bench_outputs/*.npy
 
 One JSON line on stdout (rank 0):
   value / roofline   configs[1]; the roofline prices the fill kernel against HBM (8 B per stored cell,
@@ -446,6 +447,55 @@ def speedup_vs_n1(world: int, fill_ms: float, grid_ms: float, fresh_ms: float):
     return None
 
 
+DUMP_SEED = 20261015
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, T, probes):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files under `path` (64 MB at most).
+    Tables and S1 are this rank's; the probes are those of every rank (the gathered scalars).
+      S_probes.npy        (D_total,)     log S^N_{M/2}, one per discount of the grid
+      S1.npy              (D, N)         log S^n_1, n = 1..N (a fixed seeded sample of columns beyond 16 MB)
+      S_row_N.npy         (D, min(N-2, M-1))   the table's last row, m = 2.. (sampled likewise beyond 8 MB)
+      S_table_sample.npy  (D, K)         log S^n_m at K fixed seeded cells (n uniform in 3..N, m uniform in 2..min(n-1, M)),
+                                         the same cells for every discount, K = min(cells, 2^22 / D)
+    The sample depends on (N, M, D) alone, so two builds run with the same arguments dump the same cells."""
+    import torch
+
+    N, M, D = T.N, T.M, T.D
+    dev = T.tables.device
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def columns(width, limit_bytes):
+        keep = max(1, limit_bytes // (8 * D))
+        return None if width <= keep else np.sort(rng.choice(width, keep, replace=False))
+
+    def take(t2d, cols):
+        if cols is not None:
+            t2d = t2d.index_select(1, torch.from_numpy(cols.astype(np.int64)).to(dev))
+        return t2d.to(torch.float64).cpu().numpy()
+
+    out = {"S_probes": probes.reshape(-1).to(torch.float64).cpu().numpy()}
+    out["S1"] = take(T.S1[:, :N], columns(N, 16 << 20))
+    rowlen = min(N - 2, M - 1)
+    offN = T.rowoff(N)
+    assert offN + rowlen <= T.elems <= T.stride
+    out["S_row_N"] = take(T.tables[:, offN:offN + rowlen], columns(rowlen, 8 << 20))
+    k = int(min(T.cells, (1 << 22) // D))
+    n = rng.integers(3, N + 1, k)
+    m = 2 + (rng.random(k) * (np.minimum(n - 1, M) - 1)).astype(np.int64)
+    rowoff = np.array([T.rowoff(r) for r in range(3, N + 1)], dtype=np.int64)
+    idx = rowoff[n - 3] + (m - 2)
+    assert idx.min() >= 0 and idx.max() < T.elems  # valid cells only: never the rows' padding, never past the slab
+    out["S_table_sample"] = take(T.tables, idx)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+    return {"dir": path, "bytes": total, "arrays": {name: list(a.shape) for name, a in out.items()}}
+
+
 def launcher_command(gpus: int, argv, port: int):
     """the child that `python bench.py --gpus N` (no launcher in the environment) starts: one rank per GPU
     under torch.distributed.run on this node, rendezvous on 127.0.0.1 (the container's host name may not resolve)"""
@@ -485,7 +535,11 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the sweep (grid-evals/s) sections")
     ap.add_argument("--no-batch64", action="store_true", help="skip the 64-discount sharded batch")
     ap.add_argument("--batch-steps", type=int, default=50, help="timed steps of the 64-discount batch (scale_job)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` without a launcher starts its own N ranks: a FRESH child process
     # (python -m torch.distributed.run ... bench.py <the same arguments>), started before this process
@@ -563,6 +617,7 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     must_be_clean("timed steps", fb0)
+    dumped = dump_outputs(args.dump_outputs, T, gathered) if args.dump_outputs and rank == 0 else None
 
     # Kernel-only durations for the roofline: the same K steps once more, live, with a HIP
     # start/stop event pair on every fill launch.  Kept out of the timed region above because an
@@ -775,6 +830,8 @@ def main():
         vb = valu_busy("fill1" if Dl == 1 else "fill8", "k_fill_hb") if fname == "hb" else None
         if vb:
             out["roofline"].update(vb)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         extra = {}
         if batch64 is not None:
             out["scale_job"] = batch64

@@ -463,12 +463,36 @@ def g16_samplea_slice(R):
     dump("samplers_slice.json", out)
 
 
+def g17_ziggurat(R):
+    """the Gaussian ziggurat's three published 128-entry tables (lib/gslrandist.c: ytab, wtab as double, ktab as
+    unsigned long), read from the reference's source as text -- they are file-static, no entry point returns them.
+    The source tree is the one oracle/Makefile compiles: REF=<reference tree> python tests/golden/gen_golden.py g17"""
+    import re
+
+    ref = os.environ.get("REF")
+    if not ref:
+        sys.exit("g17: set REF to the reference source tree (oracle/Makefile's REF)")
+    with open(os.path.join(ref, "lib", "gslrandist.c")) as f:
+        src = f.read()
+
+    def table(name):
+        m = re.search(r"static const (?:double|unsigned long) " + name + r"\[128\] = \{(.*?)\};", src, re.S)
+        vals = [t.strip().rstrip("UL") for t in m.group(1).replace("\n", " ").split(",") if t.strip()]
+        assert len(vals) == 128, name
+        return vals
+
+    dump("ziggurat.json", {"ytab": [hx(float(t)) for t in table("ytab")],
+                           "wtab": [hx(float(t)) for t in table("wtab")],
+                           "ktab": [int(t) for t in table("ktab")]})
+
+
 def main():
     if not orc.have_ref():
         sys.exit("oracle/_ref/libstb_ref.so missing: run `make -C oracle` where /root/reference exists")
     R = orc.ref()
     gens = [g1_small_tables, g2_big_probes, g3_asympt, g4_extend, g5_aterms, g6_bterms,
-            g7_samplers, g8_arms, g9_slice, g10_sapprox, g11_uv, g12_rng, g13_grid_tables, g14_grid_aterms, g15_samplea2, g16_samplea_slice]
+            g7_samplers, g8_arms, g9_slice, g10_sapprox, g11_uv, g12_rng, g13_grid_tables, g14_grid_aterms, g15_samplea2, g16_samplea_slice,
+            g17_ziggurat]
     want = sys.argv[1:]
     for g in gens:
         if not want or g.__name__.split("_")[0] in want:

@@ -68,6 +68,63 @@ def test_under_a_launcher_the_world_size_must_match():
     assert r.returncode != 0 and "WORLD_SIZE=3" in (r.stderr + r.stdout)
 
 
+class _Tables:
+    """a host stand-in for capi.DeviceTables: every stored cell holds n * 100000 + m (+ 0.25 d), row padding is NaN"""
+
+    def __init__(self, N, M, D):
+        import numpy as np
+        import torch
+
+        from libstb_amd import capi
+
+        L = capi.lib()
+        self.N, self.M, self.D = N, M, D
+        self.cells, self.elems = int(L.stb_cells(N, M)), int(L.stb_elems(N, M))
+        self.stride = max(32, (self.elems + 31) // 32 * 32)
+        t = np.full((D, self.stride), np.nan)
+        for n in range(3, N + 1):
+            o = self.rowoff(n)
+            ln = min(n - 2, M - 1)
+            t[:, o:o + ln] = n * 100000.0 + np.arange(2, ln + 2) + 0.25 * np.arange(D)[:, None]
+        self.tables = torch.from_numpy(t)
+        self.S1 = torch.from_numpy(np.arange(D * N, dtype=np.float64).reshape(D, N))
+
+    def rowoff(self, n):
+        from libstb_amd import capi
+
+        return int(capi.lib().stb_rowoff(n, self.M))
+
+
+@pytest.mark.parametrize("N,M,D", [(300, 40, 1), (257, 300, 3)])
+def test_dump_outputs_reads_stored_cells_only_and_repeats(tmp_path, N, M, D):
+    """--dump-outputs: every sampled cell is a stored one (never padding), the same cells for every discount and run,
+    float64 files within the size limit"""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    probes = torch.arange(5, dtype=torch.float64)
+    got = []
+    for run in range(2):
+        info = b.dump_outputs(str(tmp_path / f"run{run}"), _Tables(N, M, D), probes)
+        arrs = {p.stem: np.load(p) for p in (tmp_path / f"run{run}").glob("*.npy")}
+        assert set(arrs) == set(info["arrays"]) == {"S_probes", "S1", "S_row_N", "S_table_sample"}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) == info["bytes"] <= b.DUMP_LIMIT_BYTES
+        got.append(arrs)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
+    s = got[0]["S_table_sample"]
+    assert s.shape == (D, min(int(_Tables(N, M, 1).cells), (1 << 22) // D)) and np.isfinite(s).all()
+    n, m = np.floor(s[0] / 100000.0), np.round(s[0] % 100000.0)
+    assert (n >= 3).all() and (n <= N).all() and (m >= 2).all() and (m <= np.minimum(n - 1, M)).all()
+    assert np.array_equal(s - s[:1], np.broadcast_to(0.25 * np.arange(D)[:, None], s.shape))
+    row = got[0]["S_row_N"]
+    assert np.array_equal(row[0], N * 100000.0 + np.arange(2, min(N - 1, M) + 1))
+    assert np.array_equal(got[0]["S1"], np.arange(D * N, dtype=np.float64).reshape(D, N))
+    assert np.array_equal(got[0]["S_probes"], np.arange(5.0))
+
+
 def test_speedup_fields_against_the_committed_one_gpu_line():
     b = _bench()
     s = b.speedup_vs_n1(8, 0.8, 0.4, 0.6)

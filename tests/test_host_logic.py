@@ -5,7 +5,6 @@ import ctypes as C
 import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -145,18 +144,14 @@ def test_variate_streams_match_reference_bitwise(golden_dir):
     assert [L.gsl_rng_beta(10.0, 500.0).hex() for _ in range(32)] == g["beta_10_500"]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/lib/gslrandist.c"), reason="reference tree absent")
-def test_ziggurat_tables_rebuilt_exactly():
-    """all 384 published table entries are reproduced from the level recursion (read as text)"""
+def test_ziggurat_tables_rebuilt_exactly(golden_dir):
+    """all 384 published table entries are reproduced from the level recursion (tests/golden/ziggurat.json: the
+    reference's tables as written in its source, gen_golden.py g17)"""
     L = capi.lib()
-    src = open("/root/reference/lib/gslrandist.c").read()
-
-    def table(name):
-        m = re.search(r"static const (?:double|unsigned long) " + name + r"\[128\] = \{(.*?)\};", src, re.S)
-        return [t.strip() for t in m.group(1).replace("\n", " ").split(",") if t.strip()]
-
+    z = load(golden_dir, "ziggurat.json")
     for which, name in ((0, "ytab"), (1, "wtab"), (2, "ktab")):
-        want = [float(t.rstrip("UL")) for t in table(name)]
+        want = [float(k) for k in z[name]] if name == "ktab" else [fh(v) for v in z[name]]
+        assert len(want) == 128, name
         got = [L.stb_zig_table(which, i) for i in range(128)]
         assert got == want, name
 
