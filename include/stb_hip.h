@@ -269,6 +269,52 @@ int stb_groups_shape(const stb_groups_t *g, int *I, uint64_t *G, unsigned *N, un
 int stb_groups_aterms_timed(stb_groups_t *g, const double *x_host, int D, double *out_host,
                             float *ms_fill, float *ms_sweep, float *ms_terms);
 
+/* ---- table counts: a collapsed Gibbs sweep over t (the step a Pitman-Yor sampler alternates with sampleb / samplea;
+ * reference test/check.c:868-935, SampleCT without its early stop).  Restaurant i owns pairs k = 0 .. K_i-1 in CSR order
+ * (n uint32, t uint16, base-measure weight h > 0, NULL: all 1), a total T_i = sum_k t_ik and a concentration b_i > -a;
+ * one discount 0 <= a < 1.  A sweep visits each restaurant's pairs in order and draws t_ik from its conditional given the
+ * rest, with T_ = T_i - t_ik:
+ *     log w(tau) = S_S(n, tau) + (tau-1) log h + sum_{s=T_+1}^{T_+tau-1} log(b_i + s a),   tau = 1 .. min(n, M)
+ * (S_S with stb_lookup_S's semantics), the smallest tau whose cumulative weight exceeds u W (weights scaled by
+ * exp(-max log w), W their sum); T_i is updated before the next pair.  n = 0 keeps t = 0, n = 1 gets t = 1.  With M < n
+ * the draw is from the conditional TRUNCATED at M: exact only when M >= the largest n.  The uniform of pair g (flat
+ * index) in sweep s is splitmix64's (libstb_amd/synth.py): key = mix(seed + (s+1) gamma), u = top 53 bits of
+ * mix(key + (g+1) gamma) / 2^53 -- the draws depend on (seed, sweep, g) alone.
+ * Raw layer: d_table / d_S1 one slab of stb_fill_S for `a` with bounds (N, M) (never read, and may be NULL, when no pair
+ * has min(n, M) >= 2); a pair with n > N lies outside the table and keeps its t, whatever M; d_koff[I+1] the CSR
+ * offsets; d_t and d_T are updated in place.  One sweep. */
+int stb_sample_tcounts(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a,
+                       const double *d_bpar, int I, const uint64_t *d_koff /* I+1 */, const uint32_t *d_n,
+                       uint16_t *d_t, uint32_t *d_T, const double *d_h /* NULL: 1 */,
+                       uint64_t seed, uint64_t sweep, void *stream);
+/* Object layer: owns the pairs, T, h, its own stream and its own S table (bounds: the largest n, M), filled by
+ * stb_fill_S for the current a and refilled only when a changes.  Inputs are checked (sum K = G; t = 0 exactly when
+ * n = 0, else 1 <= t <= min(n, M); h > 0 and finite; 0 <= a < 1; b_i > -a; M = 0 with a largest n above 65535 is
+ * refused, t being a uint16): a failure returns non-zero (NULL from create) with stb_last_error() set and leaves the
+ * state as it was.  Objects whose pairs all have n <= 1, or with M = 1, hold no table: every draw is t = 1.  Device
+ * rules as for group sets (stb_set_device).
+ *   stb_tcounts_sweep      sweeps sweep .. sweep+nsweeps-1, queued on the object's stream (bpar: host [I], copied
+ *                          before the call returns).  The call waits only when `a` differs from the last call's: the
+ *                          table is refilled and its fill checked (stb_fill_status) behind the sweeps already queued
+ *   stb_tcounts_get        waits, then t (G) and / or T (I) to the host (either may be NULL)
+ *   stb_tcounts_to_groups  pairs and T to a group set of the same shape on the same device, device to device: what
+ *                          stb_groups_update_pairs + stb_groups_update_restaurants do from the host.  Only I and
+ *                          G = sum K are checked (a set does not keep K; its evaluation reads flat pairs and per-
+ *                          restaurant T, as with stb_groups_update_pairs).  The set re-sorts its copy and rebuilds its
+ *                          cell lists on first need; its table bounds grow to at least (max n, min(max n, M)) -- what
+ *                          any t can need, so no count is read back; bpar (host [I]) replaces its concentrations, NULL
+ *                          keeps them.  Work queued on the set afterwards sees the new pairs; later sweeps wait for the
+ *                          copy.  Nothing waits on the host but for the set's own earlier work. */
+typedef struct stb_tcounts stb_tcounts_t;
+stb_tcounts_t *stb_tcounts_create(int I, const int *K, const uint32_t *nflat, const uint16_t *tflat,
+                                  const double *hflat, unsigned M /* 0: max n */);
+int stb_tcounts_set_h(stb_tcounts_t *s, const double *hflat);   /* NULL: all 1 */
+int stb_tcounts_sweep(stb_tcounts_t *s, double a, const double *bpar /* host [I] */,
+                      uint64_t seed, uint64_t sweep, int nsweeps);
+int stb_tcounts_get(stb_tcounts_t *s, uint16_t *t_out, uint32_t *T_out);
+int stb_tcounts_to_groups(stb_tcounts_t *s, stb_groups_t *g, const double *bpar /* NULL: keep */);
+void stb_tcounts_free(stb_tcounts_t *s);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

@@ -162,6 +162,13 @@ def lib() -> C.CDLL:
     sig("stb_groups_shape", i, [vp, c_int_p, C.POINTER(u64), C.POINTER(u), C.POINTER(u), c_int_p])
     sig("stb_sampler_cache_clear", None, [])
     sig("stb_groups_aterms_timed", i, [vp, c_double_p, i, c_double_p, c_float_p, c_float_p, c_float_p])
+    sig("stb_sample_tcounts", i, [vp, vp, u, u, d, vp, i, vp, vp, vp, vp, vp, u64, u64, vp])
+    sig("stb_tcounts_create", vp, [i, c_int_p, c_u32_p, c_u16_p, c_double_p, u])
+    sig("stb_tcounts_set_h", i, [vp, c_double_p])
+    sig("stb_tcounts_sweep", i, [vp, d, c_double_p, u64, u64, i])
+    sig("stb_tcounts_get", i, [vp, c_u16_p, c_u32_p])
+    sig("stb_tcounts_to_groups", i, [vp, vp, c_double_p])
+    sig("stb_tcounts_free", None, [vp])
     # optional entry points (present once the sampler host code is linked in)
     for name, res, args in (
         ("arms_simple", i, [i, c_double_p, c_double_p, LOGDENS, vp, i, c_double_p, c_double_p]),
@@ -429,6 +436,54 @@ class DeviceGroups:
         self.t = torch.as_tensor(g.t.view(np.int16), device=device)
         self.T = torch.as_tensor(g.T.view(np.int32), device=device)
         self.bpar = torch.as_tensor(g.bpar, device=device)
+
+
+class TableCounts:
+    """Table counts t of (n, t) pairs resampled on the device by collapsed Gibbs sweeps (stb_tcounts_*).  K, n, t
+    (and h, NULL: all 1) in the CSR layout of synth.Groups; M = 0 draws from the full conditional (the largest n)."""
+
+    def __init__(self, K, n, t, h=None, M: int = 0):
+        self.L = lib()
+        K = np.ascontiguousarray(K, dtype=np.int32)
+        n = np.ascontiguousarray(n, dtype=np.uint32)
+        t = np.ascontiguousarray(t, dtype=np.uint16)
+        self.I, self.G = int(K.shape[0]), int(n.shape[0])
+        hp = None if h is None else dp(np.ascontiguousarray(h, dtype=np.float64))
+        self.h = self.L.stb_tcounts_create(self.I, K.ctypes.data_as(c_int_p), n.ctypes.data_as(c_u32_p),
+                                           t.ctypes.data_as(c_u16_p), hp, M)
+        if not self.h:
+            raise StbError(last_error())
+
+    def set_h(self, h=None):
+        check(self.L.stb_tcounts_set_h(self.h, None if h is None else dp(np.ascontiguousarray(h, dtype=np.float64))))
+
+    def sweep(self, a, bpar, seed: int, sweep: int, nsweeps: int = 1):
+        """sweeps sweep .. sweep+nsweeps-1, queued (bpar: the I concentrations)"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        check(self.L.stb_tcounts_sweep(self.h, float(a), dp(bpar), seed, sweep, nsweeps))
+
+    def get(self):
+        """(t[G] uint16, T[I] uint32) after the queued sweeps"""
+        t = np.zeros(self.G, dtype=np.uint16)
+        T = np.zeros(self.I, dtype=np.uint32)
+        check(self.L.stb_tcounts_get(self.h, t.ctypes.data_as(c_u16_p), T.ctypes.data_as(c_u32_p)))
+        return t, T
+
+    def to_groups(self, groups, bpar=None):
+        """pairs and T to a group set (an stb_groups_create handle) of the same shape, device to device"""
+        bp = None if bpar is None else dp(np.ascontiguousarray(bpar, dtype=np.float64))
+        check(self.L.stb_tcounts_to_groups(self.h, groups, bp))
+
+    def free(self):
+        if self.h:
+            self.L.stb_tcounts_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def sweep(tabs: DeviceTables, dg: DeviceGroups, stream=None):
