@@ -90,6 +90,9 @@ void stb_extend_policy(unsigned usedN, unsigned usedM, unsigned maxN, unsigned m
 #define STB_FILL_HB 9          /* one launch: a spine that walks blocks of rows behind a halo, alone; tile workers convert and store */
 size_t stb_fill_workspace_bytes(unsigned N, unsigned M, int D);
 int stb_default_variant(void); /* STB_FILL_SCALED unless the environment says STB_FILL_VARIANT=1 */
+/* table_stride: elements from one table's slab to the next, which is also the room each slab has: at least
+ * stb_elems(N, M) (stb_velems(N, M) for V tables) whatever D, and an even number when D > 1; s1_stride at least N.
+ * Less is refused before anything is queued ("strides too small"), in every fill below. */
 int stb_fill_S(const double *a_host, int D, unsigned N, unsigned M, double *d_tables,
                uint64_t table_stride, double *d_S1, uint64_t s1_stride, void *d_ws, size_t ws_bytes,
                int variant, void *stream);

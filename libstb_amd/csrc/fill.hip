@@ -363,8 +363,9 @@ static int fill_common(const double *a_host, int D, unsigned N, unsigned M, doub
   if (!a_host || !d_tables || !d_ws || (!vtable && !d_S1)) return stb_fail("%s: null pointer", who);
   if (ws_bytes < fill_workspace_need(N, M, D))
     return stb_fail("%s: workspace %zu < %zu", who, ws_bytes, fill_workspace_need(N, M, D));
+  // (for every D: with one table the stride is the caller's slab size, and nothing else stops a fill past its end)
   const uint64_t need = vtable ? stb_vtable_elems(N, M) : stb_table_elems(N, M);
-  if (D > 1 && (table_stride < need || (!vtable && s1_stride < N))) return stb_fail("%s: strides too small", who);
+  if (table_stride < need || (!vtable && s1_stride < N)) return stb_fail("%s: strides too small", who);
   if (D > 1 && (table_stride & 1)) return stb_fail("%s: table stride must be even", who);
   for (int d = 0; d < D; d++)
     if (!(a_host[d] >= 0.0 && a_host[d] < 1.0)) return stb_fail("%s: discount %g outside [0,1)", who, a_host[d]);

@@ -528,17 +528,17 @@ static int build(stable_t *sp, double a, unsigned N, unsigned M) {
   stb_impl *im = sp->impl;
   if (sp->flags & S_STABLE) {
     int done = 0;
-    if (float_direct(sp, N, M, 0)) {
+    if (float_direct(sp, N, M, 0))
       /* all arithmetic in double (as lib/stable.c:389-449 does through its frontier vectors), the stored value
        * narrowed by the kernel that computed it: one pass, no double slab.  A fill that gave up waiting cannot be
        * repeated in this form: the old way below takes over (and only then gets its double slab). */
       done = !stb_fill_Sf(&a, 1, N, M, im->d_Sf, im->d_Sf_elems, im->d_S1, N, im->d_ws, im->ws_bytes, NULL) && !stb_fill_status();
-      if (!done) {
-        uint64_t el = stb_table_elems(N, M);
-        if (dev_grow(im, &im->d_S, &im->d_S_elems, el < 2 ? 2 : el)) return 1;
-      }
-    }
     if (!done) {
+      /* the double slab as these bounds need it: provision() sized it for the route of its own time, and the route
+       * changes under a table -- the shared-GPU mode turns the direct one off, and growth past STB_HB_MIN_N turns it
+       * on without a double slab for the new bounds (nothing when the slab is large enough already) */
+      uint64_t el = stb_table_elems(N, M);
+      if (dev_grow(im, &im->d_S, &im->d_S_elems, el < 2 ? 2 : el)) return 1;
       if (stb_fill_S(&a, 1, N, M, im->d_S, im->d_S_elems, im->d_S1, N, im->d_ws, im->ws_bytes,
                      stb_default_variant(), NULL))
         return 1;
@@ -551,15 +551,13 @@ static int build(stable_t *sp, double a, unsigned N, unsigned M) {
   }
   if (sp->flags & S_UVTABLE) {
     int done = 0;
-    if (float_direct(sp, N, M, 1)) {
+    if (float_direct(sp, N, M, 1))
       done = !stb_fill_Vf(&a, 1, N, M, im->d_Vf, im->d_Vf_elems, im->d_ws, im->ws_bytes, NULL) && !stb_fill_status();
-      if (!done) {
-        uint64_t el = stb_vtable_elems(N, M);
-        if (dev_grow(im, &im->d_V, &im->d_V_elems, el < 2 ? 2 : el)) return 1;
-      }
-    }
     if (!done) {
-      int rc = stb_fill_V(&a, 1, N, M, im->d_V, im->d_V_elems, im->d_ws, im->ws_bytes, NULL);
+      uint64_t el = stb_vtable_elems(N, M); /* (sized here, as the S slab above) */
+      int rc;
+      if (dev_grow(im, &im->d_V, &im->d_V_elems, el < 2 ? 2 : el)) return 1;
+      rc = stb_fill_V(&a, 1, N, M, im->d_V, im->d_V_elems, im->d_ws, im->ws_bytes, NULL);
       if (!rc) rc = stb_fill_status(); /* before anything reads it or a later fill reuses the workspace and its header */
       if (rc) {
         /* (the V table from the S recurrence's cells gave up waiting: the reference's own recurrence, which cannot) */
