@@ -318,6 +318,51 @@ int stb_tcounts_get(stb_tcounts_t *s, uint16_t *t_out, uint32_t *T_out);
 int stb_tcounts_to_groups(stb_tcounts_t *s, stb_groups_t *g, const double *bpar /* NULL: keep */);
 void stb_tcounts_free(stb_tcounts_t *s);
 
+/* ---- table indicators: the other t-sampler, one Gibbs step per customer (reference test/demo.c:405-436, SampleTI of
+ * test/check.c:843-866), with the exact prior ratio.  Pairs, h, T_i, b_i and a as for stb_tcounts above.  The customers of
+ * restaurant i are a sequence of its pair indices, cust[coff[i] .. coff[i+1]) (uint32, local k): pair k appears exactly
+ * n_ik times; cust == NULL is PAIR ORDER (pair 0 n_0 times, then pair 1, ...).  c = 0 .. C-1 is the flat customer index
+ * over all restaurants in CSR order.  A sweep visits each restaurant's customers in sequence; a visit to a customer of
+ * pair (n, t, h):
+ *   1. n <= 1, or n > N (outside the table, as in stb_sample_tcounts): nothing.
+ *   2. remove: if t > 1 and (double)(n-1) * u1 < (double)(t-1): t -= 1, T_i -= 1.  (Now t < n.)
+ *   3. odds = h * (b + (double)T_i * a) * (double)t / (double)(n - t) * V, evaluated left to right without contraction,
+ *      V = what stb_lookup_V returns for (n, t+1): 0 when t+1 > M, the draw truncated at M as in stb_tcounts.
+ *      With STB_TI_REF_ODDS the divisor is (double)(n - t + 1), the reference's factor (its chain
+ *      does not leave the PYP joint invariant; t / (n-t) is C(n-1, t-1) / C(n-1, t), the exact ratio).
+ *   4. add: p = odds / (odds + 1.0) (1 when odds is +inf); if u2 < p: t += 1, T_i += 1.
+ * Uniforms of sweep s: key = mix(seed + (s+1) gamma); u1 = top 53 bits of mix(key + (2c+1) gamma) / 2^53, u2 the same
+ * at 2c+2 (elements 2c and 2c+1 of libstb_amd/synth.py's unit(2C, key)).  The draws depend on (seed, sweep, c) alone,
+ * not on launch geometry or on the kernel form.  This stream coincides with stb_tcounts' for the same seed and sweep: a
+ * caller that alternates the two samplers gives them different seeds.
+ * Two kernels with the same arithmetic: one lane per restaurant (many short restaurants) and one wave per restaurant
+ * (few long ones); the form follows the number of restaurants, STB_TINDIC_FORM=lane|wave forces one.
+ * Raw layer: d_vtable a slab of stb_fill_V for `a` with bounds (N, M) (never read, and may be NULL, when M = 1 or no
+ * pair has 2 <= n <= N); d_koff[I+1] the pair offsets, d_coff[I+1] (uint64) the customer offsets -- the prefix sums of
+ * each restaurant's sum of n; d_cust NULL or every entry a pair of its restaurant; t and T updated in place.  One
+ * sweep. */
+#define STB_TI_REF_ODDS 1
+int stb_sample_tindic(const double *d_vtable, unsigned N, unsigned M, double a, const double *d_bpar, int I,
+                      const uint64_t *d_koff /* I+1 */, const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T,
+                      const double *d_h /* NULL: 1 */, const uint64_t *d_coff /* I+1 */, const uint32_t *d_cust /* NULL: pair order */,
+                      unsigned flags, uint64_t seed, uint64_t sweep, void *stream);
+/* Object layer, as stb_tcounts_*: owns the pairs, T, h, the customer order, its own stream and its own V table (bounds:
+ * the largest n, M), filled by stb_fill_V for the current a and refilled only when a changes.  Inputs are checked (t = 0
+ * exactly when n = 0, else 1 <= t <= min(n, M); h > 0 and finite; every cust entry < K_i and pair k visited exactly n_k
+ * times; known flag bits; 0 <= a < 1; b_i > -a; M = 0 with a largest n above 65535 is refused): a failure returns
+ * non-zero (NULL from create) with stb_last_error() set and leaves the state as it was.  Objects whose pairs all have
+ * n <= 1, or with M = 1, hold no table (no indicator is ever added).  _sweep, _get and _to_groups behave as
+ * stb_tcounts_sweep, _get and _to_groups. */
+typedef struct stb_tindic stb_tindic_t;
+stb_tindic_t *stb_tindic_create(int I, const int *K, const uint32_t *nflat, const uint16_t *tflat, const double *hflat,
+                                const uint32_t *cust /* NULL: pair order */, unsigned M /* 0: max n */, unsigned flags);
+int stb_tindic_set_h(stb_tindic_t *s, const double *hflat);   /* NULL: all 1 */
+int stb_tindic_sweep(stb_tindic_t *s, double a, const double *bpar /* host [I] */, uint64_t seed, uint64_t sweep,
+                     int nsweeps);
+int stb_tindic_get(stb_tindic_t *s, uint16_t *t_out, uint32_t *T_out);
+int stb_tindic_to_groups(stb_tindic_t *s, stb_groups_t *g, const double *bpar /* NULL: keep */);
+void stb_tindic_free(stb_tindic_t *s);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

@@ -169,6 +169,13 @@ def lib() -> C.CDLL:
     sig("stb_tcounts_get", i, [vp, c_u16_p, c_u32_p])
     sig("stb_tcounts_to_groups", i, [vp, vp, c_double_p])
     sig("stb_tcounts_free", None, [vp])
+    sig("stb_sample_tindic", i, [vp, u, u, d, vp, i, vp, vp, vp, vp, vp, vp, vp, u, u64, u64, vp])
+    sig("stb_tindic_create", vp, [i, c_int_p, c_u32_p, c_u16_p, c_double_p, c_u32_p, u, u])
+    sig("stb_tindic_set_h", i, [vp, c_double_p])
+    sig("stb_tindic_sweep", i, [vp, d, c_double_p, u64, u64, i])
+    sig("stb_tindic_get", i, [vp, c_u16_p, c_u32_p])
+    sig("stb_tindic_to_groups", i, [vp, vp, c_double_p])
+    sig("stb_tindic_free", None, [vp])
     # optional entry points (present once the sampler host code is linked in)
     for name, res, args in (
         ("arms_simple", i, [i, c_double_p, c_double_p, LOGDENS, vp, i, c_double_p, c_double_p]),
@@ -477,6 +484,70 @@ class TableCounts:
     def free(self):
         if self.h:
             self.L.stb_tcounts_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+TI_REF_ODDS = 1  # stb_tindic_create / stb_sample_tindic flag: the reference's factor t / (n-t+1)
+
+
+class TableIndicators:
+    """Table counts t of (n, t) pairs resampled on the device customer by customer with table indicators
+    (stb_tindic_*).  K, n, t, h as for TableCounts; cust: the customers of every restaurant as local pair indices, back to
+    back (None: pair order); M = 0 truncates at the largest n; flags TI_REF_ODDS."""
+
+    def __init__(self, K, n, t, h=None, cust=None, M: int = 0, flags: int = 0):
+        self.L = lib()
+        K = np.ascontiguousarray(K, dtype=np.int32)
+        n = np.ascontiguousarray(n, dtype=np.uint32)
+        t = np.ascontiguousarray(t, dtype=np.uint16)
+        self.I, self.G = int(K.shape[0]), int(n.shape[0])
+        self.h = None
+        if int(K.astype(np.int64).sum()) != self.G or t.shape[0] != self.G or (h is not None and len(h) != self.G):
+            raise StbError(f"TableIndicators: sum K = {int(K.astype(np.int64).sum())}, but {self.G} n, {t.shape[0]} t"
+                           + ("" if h is None else f", {len(h)} h"))
+        C_ = int(n.astype(np.int64).sum())
+        cp = None
+        if cust is not None:
+            cust = np.ascontiguousarray(cust, dtype=np.uint32)
+            if cust.shape[0] != C_:
+                raise StbError(f"TableIndicators: {cust.shape[0]} customers in cust, sum n = {C_}")
+            cp = cust.ctypes.data_as(c_u32_p)
+        self.C = C_
+        hp = None if h is None else dp(np.ascontiguousarray(h, dtype=np.float64))
+        self.h = self.L.stb_tindic_create(self.I, K.ctypes.data_as(c_int_p), n.ctypes.data_as(c_u32_p),
+                                          t.ctypes.data_as(c_u16_p), hp, cp, M, flags)
+        if not self.h:
+            raise StbError(last_error())
+
+    def set_h(self, h=None):
+        check(self.L.stb_tindic_set_h(self.h, None if h is None else dp(np.ascontiguousarray(h, dtype=np.float64))))
+
+    def sweep(self, a, bpar, seed: int, sweep: int, nsweeps: int = 1):
+        """sweeps sweep .. sweep+nsweeps-1, queued (bpar: the I concentrations)"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        check(self.L.stb_tindic_sweep(self.h, float(a), dp(bpar), seed, sweep, nsweeps))
+
+    def get(self):
+        """(t[G] uint16, T[I] uint32) after the queued sweeps"""
+        t = np.zeros(self.G, dtype=np.uint16)
+        T = np.zeros(self.I, dtype=np.uint32)
+        check(self.L.stb_tindic_get(self.h, t.ctypes.data_as(c_u16_p), T.ctypes.data_as(c_u32_p)))
+        return t, T
+
+    def to_groups(self, groups, bpar=None):
+        """pairs and T to a group set (an stb_groups_create handle) of the same shape, device to device"""
+        bp = None if bpar is None else dp(np.ascontiguousarray(bpar, dtype=np.float64))
+        check(self.L.stb_tindic_to_groups(self.h, groups, bp))
+
+    def free(self):
+        if self.h:
+            self.L.stb_tindic_free(self.h)
             self.h = None
 
     def __del__(self):

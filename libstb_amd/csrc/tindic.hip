@@ -1,0 +1,571 @@
+// tindic.hip -- the table-indicator step of a Pitman-Yor Gibbs sampler on the device: every customer's indicator
+// ("heads a table of its dish") is removed and drawn again given the rest of its restaurant (test/demo.c:405-436,
+// SampleTI of test/check.c:843-866), one customer after another.
+//
+//   k_tindic_lane   one lane per restaurant: many short restaurants
+//   k_tindic_wave   one wave per restaurant: few long ones (t in LDS, the next 64 customers' V cells prefetched)
+//
+// A visit to a customer of pair (n, t, h) of restaurant i (total T, concentration b, discount a):
+//   n <= 1 or n > N: nothing.  Remove: t > 1 and (n-1) u1 < t-1 -> t--, T--.  Then, with V = V^n_{t+1} (0 when t+1 > M)
+//     odds = h (b + T a) t / (n - t) V        (STB_TI_REF_ODDS: / (n - t + 1), the reference's factor)
+//   and t++, T++ when u2 < odds / (odds + 1).
+// Given one indicator held at 1 and the other n-1 uniform given t, the prior ratio of t+1 to t tables is
+// C(n-1, t-1) / C(n-1, t) = t / (n-t): with it the step leaves the PYP joint (b|a)_T prod_k S^{n_k}_{t_k,a} h_k^{t_k}
+// invariant; the reference's t / (n-t+1) does not.
+//
+// Both forms evaluate a visit with the same functions (ti_remove, ti_add; no contraction) on the same V cells, so
+// they give the same bits.  Uniforms are counter-based as in tcounts.hip: sweep s, flat customer index c,
+//     key_s = mix(seed + (s+1) gamma),  u1 = unit(mix(key_s + (2c+1) gamma)),  u2 = unit(mix(key_s + (2c+2) gamma))
+// so the draws depend on (seed, sweep, c) alone.  No workgroup waits for another.
+
+#include <algorithm>
+#include <vector>
+
+#include "stb_common.h"
+#include "groups.h"
+
+#define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
+#define STB_TI_REF_ODDS_FLAG 1u
+
+static constexpr uint64_t TI_GAMMA = 0x9E3779B97F4A7C15ull;
+
+__host__ __device__ static inline uint64_t ti_mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// element j of the sweep's stream: u1 of customer c is j = 2c+1, u2 is j = 2c+2
+__device__ __forceinline__ double ti_unit(uint64_t key, uint64_t j) {
+  return (double)(ti_mix64(key + j * TI_GAMMA) >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// V^n_m with stb_lookup_V's semantics for the cells a visit can address (2 <= n <= N): 0 outside 2 <= m <= min(n, M)
+__device__ __forceinline__ double ti_V(const double *vt, unsigned M, unsigned n, unsigned m) {
+  if (m < 2 || m > M || m > n) return 0.0;
+  return vt[stb_vrow_offset(n, M) + (m - 2)];
+}
+
+__device__ __forceinline__ bool ti_remove(unsigned n, unsigned t, double u1) {
+  return t > 1 && (double)(n - 1) * u1 < (double)(t - 1);
+}
+
+// t, T after the removal; t < n
+__device__ __forceinline__ bool ti_add(unsigned n, unsigned t, uint32_t T, double h, double a, double b, double V, double u2,
+                                       bool ref) {
+#pragma clang fp contract(off)
+  const double odds = h * (b + (double)T * a) * (double)t / (double)(ref ? n - t + 1 : n - t) * V;
+  const double p = isinf(odds) ? 1.0 : odds / (odds + 1.0);
+  return u2 < p;
+}
+
+// ---- lane form -------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(64) void k_tindic_lane(const double *vt, unsigned N, unsigned M, double a, const double *bpar,
+                                                    int I, const uint64_t *koff, const uint32_t *nv, uint16_t *tv,
+                                                    uint32_t *Tv, const double *hv, const uint64_t *coff,
+                                                    const uint32_t *cust, unsigned flags, uint64_t seed, uint64_t sweep0,
+                                                    int nsweeps) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= I) return;
+  const bool ref = (flags & STB_TI_REF_ODDS_FLAG) != 0;
+  const uint64_t k0 = koff[i], k1 = koff[i + 1], c0 = coff[i], c1 = coff[i + 1];
+  const double b = bpar[i];
+  uint32_t T = Tv[i];
+  for (int s = 0; s < nsweeps; s++) {
+    const uint64_t key = ti_mix64(seed + (sweep0 + (uint64_t)s + 1) * TI_GAMMA);
+    if (cust) {
+      for (uint64_t c = c0; c < c1; c++) {  // (t through global memory: this lane's own stores)
+        const uint64_t g = k0 + cust[c];
+        const unsigned n = nv[g];
+        if (n <= 1 || n > N) continue;
+        unsigned t = tv[g];
+        if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
+        const double h = hv ? hv[g] : 1.0;
+        if (ti_add(n, t, T, h, a, b, ti_V(vt, M, n, t + 1), ti_unit(key, 2 * c + 2), ref)) t++, T++;
+        tv[g] = (uint16_t)t;
+      }
+    } else {  // pair order: a pair's customers are consecutive, its t stays in a register
+      uint64_t c = c0;
+      for (uint64_t g = k0; g < k1; g++) {
+        const unsigned n = nv[g];
+        if (n <= 1 || n > N) {
+          c += n;
+          continue;
+        }
+        const double h = hv ? hv[g] : 1.0;
+        const unsigned t0 = tv[g];
+        unsigned t = t0;
+        for (unsigned r = 0; r < n; r++, c++) {
+          if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
+          if (ti_add(n, t, T, h, a, b, ti_V(vt, M, n, t + 1), ti_unit(key, 2 * c + 2), ref)) t++, T++;
+        }
+        if (t != t0) tv[g] = (uint16_t)t;
+      }
+    }
+  }
+  Tv[i] = T;
+}
+
+// ---- wave form -------------------------------------------------------------------------------------------------
+// Every lane walks the same chain on the same values (read with readlane), so each lane's own loads and stores are
+// all the ordering the chain needs; the per-lane work is the loads of the next 64 customers and their V cells.
+
+__device__ __forceinline__ unsigned ti_rl(unsigned v, unsigned j) {
+  return (unsigned)__builtin_amdgcn_readlane((int)v, (int)__builtin_amdgcn_readfirstlane((int)j));
+}
+__device__ __forceinline__ double ti_rld(double v, unsigned j) {
+  const int jj = __builtin_amdgcn_readfirstlane((int)j);
+  const uint64_t x = (uint64_t)__double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, jj);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), jj);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+__global__ __launch_bounds__(64) void k_tindic_wave(const double *vt, unsigned N, unsigned M, double a, const double *bpar,
+                                                    int I, const uint64_t *koff, const uint32_t *nv, uint16_t *tv,
+                                                    uint32_t *Tv, const double *hv, const uint64_t *coff,
+                                                    const uint32_t *cust, unsigned flags, uint64_t seed, uint64_t sweep0,
+                                                    int nsweeps, unsigned cap) {
+  extern __shared__ uint16_t lt[];  // [cap]: t of the restaurant's dishes, customer order with K_i <= cap
+  const int i = blockIdx.x;
+  if (i >= I) return;
+  const unsigned lane = threadIdx.x;
+  const bool ref = (flags & STB_TI_REF_ODDS_FLAG) != 0;
+  const uint64_t k0 = koff[i], k1 = koff[i + 1], c0 = coff[i], c1 = coff[i + 1];
+  const double b = bpar[i];
+  uint32_t T = Tv[i];
+  const bool inlds = cust && k1 - k0 <= cap;
+  if (inlds)
+    for (uint64_t k = lane; k < k1 - k0; k += 64) lt[k] = tv[k0 + k];
+  __syncthreads();
+  for (int s = 0; s < nsweeps; s++) {
+    const uint64_t key = ti_mix64(seed + (sweep0 + (uint64_t)s + 1) * TI_GAMMA);
+    if (cust) {
+      for (uint64_t cb = c0; cb < c1; cb += 64) {
+        const unsigned L = c1 - cb < 64 ? (unsigned)(c1 - cb) : 64u;
+        // this lane's customer of the chunk: its dish, n, h, and V(n, t0), V(n, t0+1) at the chunk's start t0 --
+        // the two cells the dish's first visit in the chunk can read
+        unsigned mk = 0, mn = 0, mt0 = 0;
+        double mh = 1.0, v0 = 0.0, v1 = 0.0;
+        if (lane < L) {
+          mk = cust[cb + lane];
+          const uint64_t g = k0 + mk;
+          mn = nv[g];
+          if (mn >= 2 && mn <= N) {
+            mh = hv ? hv[g] : 1.0;
+            mt0 = inlds ? lt[mk] : tv[g];
+            v0 = ti_V(vt, M, mn, mt0);
+            v1 = ti_V(vt, M, mn, mt0 + 1);
+          }
+        }
+        for (unsigned j = 0; j < L; j++) {
+          const unsigned n = ti_rl(mn, j);
+          if (n <= 1 || n > N) continue;
+          const unsigned k = ti_rl(mk, j), t0 = ti_rl(mt0, j);
+          const uint64_t c = cb + j;
+          unsigned t = inlds ? lt[k] : tv[k0 + k];
+          if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
+          const unsigned m = t + 1;
+          // (an earlier visit in this chunk may have moved the dish's t out of the prefetched pair: a direct load)
+          const double V = m == t0 ? ti_rld(v0, j) : (m == t0 + 1 ? ti_rld(v1, j) : ti_V(vt, M, n, m));
+          if (ti_add(n, t, T, ti_rld(mh, j), a, b, V, ti_unit(key, 2 * c + 2), ref)) t++, T++;
+          if (inlds) lt[k] = (uint16_t)t;  // (every lane stores the same value)
+          else tv[k0 + k] = (uint16_t)t;
+        }
+      }
+    } else {  // pair order: 64 pairs loaded at a time, a window of 64 cells of the row around t per pair
+      uint64_t c = c0;
+      for (uint64_t pb = k0; pb < k1; pb += 64) {
+        const unsigned P = k1 - pb < 64 ? (unsigned)(k1 - pb) : 64u;
+        unsigned mn = 0, mt = 0;
+        double mh = 1.0;
+        if (lane < P) {
+          mn = nv[pb + lane];
+          mt = tv[pb + lane];
+          mh = hv ? hv[pb + lane] : 1.0;
+        }
+        for (unsigned j = 0; j < P; j++) {
+          const unsigned n = ti_rl(mn, j);
+          if (n <= 1 || n > N) {
+            c += n;
+            continue;
+          }
+          const unsigned t0 = ti_rl(mt, j);
+          const double h = ti_rld(mh, j);
+          unsigned t = t0;
+          unsigned wb = t0 > 32 ? t0 - 32 : 0;  // the window holds m = wb .. wb+63
+          double win = ti_V(vt, M, n, wb + lane);
+          for (unsigned r = 0; r < n; r++, c++) {
+            if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
+            const unsigned m = t + 1;
+            if (m - wb >= 64u) {
+              wb = m > 32 ? m - 32 : 0;
+              win = ti_V(vt, M, n, wb + lane);
+            }
+            if (ti_add(n, t, T, h, a, b, ti_rld(win, m - wb), ti_unit(key, 2 * c + 2), ref)) t++, T++;
+          }
+          if (t != t0) tv[pb + j] = (uint16_t)t;
+        }
+      }
+    }
+  }
+  if (inlds) {
+    __syncthreads();
+    for (uint64_t k = lane; k < k1 - k0; k += 64) tv[k0 + k] = lt[k];
+  }
+  if (lane == 0) Tv[i] = T;
+}
+
+// ---- launch ------------------------------------------------------------------------------------------------------
+
+// the wave form below this many restaurants (MEASUREMENTS.md section T2), the lane form from it on;
+// STB_TINDIC_FORM=lane|wave forces one
+#define STB_TI_WAVE_BELOW 2048
+
+static int ti_form(int I) {
+  const char *e = getenv("STB_TINDIC_FORM");
+  if (e && !strcmp(e, "lane")) return 0;
+  if (e && !strcmp(e, "wave")) return 1;
+  return I < STB_TI_WAVE_BELOW ? 1 : 0;
+}
+
+// cap: dishes a wave keeps in LDS (the largest K_i when it is known and smaller than STB_TI_LDS_CAP)
+static int ti_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I, const uint64_t *d_koff,
+                     const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, const uint64_t *d_coff,
+                     const uint32_t *d_cust, unsigned flags, uint64_t seed, uint64_t sweep, int nsweeps, unsigned cap,
+                     hipStream_t st) {
+  if (I <= 0 || nsweeps <= 0) return 0;
+  if (ti_form(I) == 0) {
+    STB_LAUNCH(k_tindic_lane, dim3((unsigned)((I + 63) / 64)), dim3(64), st, d_vt, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T,
+               d_h, d_coff, d_cust, flags, seed, sweep, nsweeps);
+  } else {
+    if (cap > STB_TI_LDS_CAP) cap = STB_TI_LDS_CAP;
+    if (!d_cust) cap = 0;
+    STB_LAUNCH_SHM(k_tindic_wave, dim3((unsigned)I), dim3(64), sizeof(uint16_t) * (cap ? cap : 1), st, d_vt, N, M, a, d_bpar,
+                   I, d_koff, d_n, d_t, d_T, d_h, d_coff, d_cust, flags, seed, sweep, nsweeps, cap);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int stb_sample_tindic(const double *d_vtable, unsigned N, unsigned M, double a, const double *d_bpar, int I,
+                                 const uint64_t *d_koff, const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h,
+                                 const uint64_t *d_coff, const uint32_t *d_cust, unsigned flags, uint64_t seed, uint64_t sweep,
+                                 void *stream) {
+  STB_ENTRY;
+  if (!(a >= 0.0 && a < 1.0)) return stb_fail("stb_sample_tindic: discount a=%g outside [0, 1)", a);
+  if (N < 1 || M < 1) return stb_fail("stb_sample_tindic: table bounds N=%u M=%u", N, M);
+  if (M > 65535u) return stb_fail("stb_sample_tindic: M=%u (t is a uint16: at most 65535)", M);
+  if (flags & ~STB_TI_REF_ODDS_FLAG) return stb_fail("stb_sample_tindic: unknown flags 0x%x", flags);
+  if (I < 0) return stb_fail("stb_sample_tindic: I=%d", I);
+  return ti_launch(d_vtable, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h, d_coff, d_cust, flags, seed, sweep, 1,
+                   STB_TI_LDS_CAP, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the object: pairs, totals, weights, customer order, its own V table for the current discount, its own stream
+
+struct stb_tindic {
+  int dev;
+  int I;
+  uint64_t G, C;        // pairs, customers
+  unsigned N, M;        // table bounds: N = the largest n (at least 3), M = min(the column bound, N)
+  unsigned Mdraw;       // the column bound the draws are truncated at (what create was given, or the largest n)
+  unsigned maxn, maxK;
+  unsigned flags;
+  bool need_table;      // some visit can read a V cell (max n >= 2 and M >= 2); otherwise no indicator is ever added
+  uint64_t *d_koff, *d_coff;
+  uint32_t *d_n, *d_T;
+  uint32_t *d_cust;     // null: pair order
+  uint16_t *d_t;
+  double *d_h;          // null: every h is 1
+  double *d_bpar;
+  double *h_bpar[2];    // pinned staging of bpar, used in turn: a sweep does not wait for the one before it
+  hipEvent_t ev_bpar[2];  // the copy out of h_bpar[k] is through
+  int slot;
+  std::vector<double> last_bpar;  // what d_bpar holds (empty: nothing yet)
+  double *d_vt;
+  uint64_t vstride;
+  void *d_ws;
+  size_t ws_bytes;
+  double a_filled;      // the discount the table holds (NaN: none yet)
+  hipStream_t st;
+};
+
+static void ti_release(stb_tindic_t *s) {
+  void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  for (int k = 0; k < 2; k++) {
+    if (s->h_bpar[k]) (void)hipHostFree(s->h_bpar[k]);
+    if (s->ev_bpar[k]) (void)hipEventDestroy(s->ev_bpar[k]);
+  }
+  if (s->st) (void)hipStreamDestroy(s->st);
+  delete s;
+}
+
+static int ti_check_h(const double *h, uint64_t G, const char *who) {
+  for (uint64_t g = 0; g < G; g++)
+    if (!(h[g] > 0.0) || !std::isfinite(h[g])) return stb_fail("%s: h[%llu]=%g (must be > 0 and finite)", who, (unsigned long long)g, h[g]);
+  return 0;
+}
+
+static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, const uint16_t *tflat, const double *hflat,
+                                    const uint32_t *cust, unsigned M, unsigned flags) {
+  if (stb_device_count() < 1) {
+    stb_fail("stb_tindic_create: no HIP device (libstb_amd has no CPU path)");
+    return nullptr;
+  }
+  if (I < 1 || !K || !nflat || !tflat) {
+    stb_fail("stb_tindic_create: I=%d and K, n, t are required", I);
+    return nullptr;
+  }
+  if (flags & ~STB_TI_REF_ODDS_FLAG) {
+    stb_fail("stb_tindic_create: unknown flags 0x%x", flags);
+    return nullptr;
+  }
+  std::vector<uint64_t> koff((size_t)I + 1, 0), coff((size_t)I + 1, 0);
+  unsigned maxK = 0;
+  for (int i = 0; i < I; i++) {
+    if (K[i] < 0) {
+      stb_fail("stb_tindic_create: K[%d]=%d", i, K[i]);
+      return nullptr;
+    }
+    koff[i + 1] = koff[i] + (uint64_t)K[i];
+    maxK = (unsigned)K[i] > maxK ? (unsigned)K[i] : maxK;
+  }
+  const uint64_t G = koff[I];
+  unsigned maxn = 0;
+  for (uint64_t g = 0; g < G; g++) maxn = nflat[g] > maxn ? nflat[g] : maxn;
+  if (M == 0 && maxn > 65535u) {
+    stb_fail("stb_tindic_create: the largest n is %u; t is a uint16, so pass M <= 65535 (the draws are then truncated "
+             "at M)", maxn);
+    return nullptr;
+  }
+  if (M == 0) M = maxn > 0 ? maxn : 1;
+  if (M > 65535u) {
+    stb_fail("stb_tindic_create: M=%u (t is a uint16: at most 65535)", M);
+    return nullptr;
+  }
+  std::vector<uint32_t> T(I, 0);
+  for (int i = 0; i < I; i++) {
+    uint64_t ci = 0;
+    for (uint64_t g = koff[i]; g < koff[i + 1]; g++) {
+      const unsigned n = nflat[g], t = tflat[g], tm = n < M ? n : M;
+      if (n == 0 ? t != 0 : (t < 1 || t > tm)) {
+        stb_fail("stb_tindic_create: pair %llu has n=%u t=%u (t = 0 exactly when n = 0, else 1 <= t <= min(n, M=%u))",
+                 (unsigned long long)g, n, t, M);
+        return nullptr;
+      }
+      T[i] += t;
+      ci += n;
+    }
+    coff[i + 1] = coff[i] + ci;
+  }
+  const uint64_t C = coff[I];
+  if (hflat && ti_check_h(hflat, G, "stb_tindic_create")) return nullptr;
+  if (cust) {  // every restaurant's sequence visits pair k exactly n_k times
+    std::vector<uint64_t> seen(maxK ? maxK : 1);
+    for (int i = 0; i < I; i++) {
+      const unsigned Ki = (unsigned)K[i];
+      std::fill(seen.begin(), seen.begin() + Ki, 0);
+      for (uint64_t c = coff[i]; c < coff[i + 1]; c++) {
+        if (cust[c] >= Ki) {
+          stb_fail("stb_tindic_create: cust[%llu]=%u is not a pair of restaurant %d (K=%u)", (unsigned long long)c, cust[c], i, Ki);
+          return nullptr;
+        }
+        seen[cust[c]]++;
+      }
+      for (unsigned k = 0; k < Ki; k++)
+        if (seen[k] != nflat[koff[i] + k]) {
+          stb_fail("stb_tindic_create: restaurant %d visits pair %u %llu times; its n is %u", i, k,
+                   (unsigned long long)seen[k], nflat[koff[i] + k]);
+          return nullptr;
+        }
+    }
+  }
+  stb_tindic_t *s = new stb_tindic_t();
+  s->I = I;
+  s->G = G;
+  s->C = C;
+  s->maxn = maxn;
+  s->maxK = maxK;
+  s->flags = flags;
+  s->N = maxn < 3 ? 3 : maxn;
+  s->Mdraw = M;
+  s->need_table = maxn >= 2 && M >= 2;
+  // (the draws never address m > max n: a table of min(M, N) columns is the same table)
+  s->M = s->need_table ? (M < s->N ? M : s->N) : M;
+  s->a_filled = NAN;
+  const size_t Gs = G ? G : 1;
+  int rc = 0;
+  if (hipGetDevice(&s->dev) != hipSuccess || hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess ||
+      hipMalloc((void **)&s->d_koff, sizeof(uint64_t) * (I + 1)) != hipSuccess ||
+      hipMalloc((void **)&s->d_coff, sizeof(uint64_t) * (I + 1)) != hipSuccess ||
+      hipMalloc((void **)&s->d_n, sizeof(uint32_t) * Gs) != hipSuccess || hipMalloc((void **)&s->d_t, sizeof(uint16_t) * Gs) != hipSuccess ||
+      hipMalloc((void **)&s->d_T, sizeof(uint32_t) * I) != hipSuccess || hipMalloc((void **)&s->d_bpar, sizeof(double) * I) != hipSuccess ||
+      hipHostMalloc((void **)&s->h_bpar[0], sizeof(double) * I) != hipSuccess ||
+      hipHostMalloc((void **)&s->h_bpar[1], sizeof(double) * I) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_bpar[0], hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_bpar[1], hipEventDisableTiming) != hipSuccess ||
+      (hflat && hipMalloc((void **)&s->d_h, sizeof(double) * Gs) != hipSuccess) ||
+      (cust && hipMalloc((void **)&s->d_cust, sizeof(uint32_t) * (C ? C : 1)) != hipSuccess))
+    rc = stb_fail("stb_tindic_create: %s", hipGetErrorString(hipGetLastError()));
+  // (no table where no visit reads one: every pair has n <= 1, or M = 1)
+  s->vstride = s->need_table ? (stb_vtable_elems(s->N, s->M) + 31) & ~31ull : 0;
+  s->ws_bytes = s->need_table ? stb_fill_workspace_bytes(s->N, s->M, 1) : 0;
+  if (!rc && s->need_table && (hipMalloc((void **)&s->d_vt, sizeof(double) * s->vstride) != hipSuccess ||
+                               hipMalloc(&s->d_ws, s->ws_bytes ? s->ws_bytes : 1) != hipSuccess))
+    rc = stb_fail("stb_tindic_create: out of device memory for a %u x %u V table", s->N, s->M);
+  if (!rc && (hipMemcpy(s->d_koff, koff.data(), sizeof(uint64_t) * (I + 1), hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(s->d_coff, coff.data(), sizeof(uint64_t) * (I + 1), hipMemcpyHostToDevice) != hipSuccess ||
+              (G && hipMemcpy(s->d_n, nflat, sizeof(uint32_t) * G, hipMemcpyHostToDevice) != hipSuccess) ||
+              (G && hipMemcpy(s->d_t, tflat, sizeof(uint16_t) * G, hipMemcpyHostToDevice) != hipSuccess) ||
+              hipMemcpy(s->d_T, T.data(), sizeof(uint32_t) * I, hipMemcpyHostToDevice) != hipSuccess ||
+              (hflat && G && hipMemcpy(s->d_h, hflat, sizeof(double) * G, hipMemcpyHostToDevice) != hipSuccess) ||
+              (cust && C && hipMemcpy(s->d_cust, cust, sizeof(uint32_t) * C, hipMemcpyHostToDevice) != hipSuccess)))
+    rc = stb_fail("stb_tindic_create: %s", hipGetErrorString(hipGetLastError()));
+  if (rc) {
+    ti_release(s);
+    return nullptr;
+  }
+  return s;
+}
+
+// The object lives on the device stb_get_device() names, like a group set; every later call switches to it.
+extern "C" stb_tindic_t *stb_tindic_create(int I, const int *K, const uint32_t *nflat, const uint16_t *tflat, const double *hflat,
+                                           const uint32_t *cust, unsigned M, unsigned flags) {
+  STB_ENTRY;
+  const int prev = stb_device_enter(stb_get_device());
+  stb_tindic_t *s = ti_create_here(I, K, nflat, tflat, hflat, cust, M, flags);
+  stb_device_leave(prev);
+  return s;
+}
+
+extern "C" void stb_tindic_free(stb_tindic_t *s) {
+  STB_ENTRY;
+  if (!s) return;
+  const int prev = stb_device_enter(s->dev);
+  (void)hipStreamSynchronize(s->st);
+  ti_release(s);
+  stb_device_leave(prev);
+}
+
+extern "C" int stb_tindic_set_h(stb_tindic_t *s, const double *hflat) {
+  STB_ENTRY;
+  if (!s) return stb_fail("stb_tindic_set_h: null object");
+  if (hflat && ti_check_h(hflat, s->G, "stb_tindic_set_h")) return 1;
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (hipStreamSynchronize(s->st) != hipSuccess) rc = stb_fail("stb_tindic_set_h: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc && !hflat && s->d_h) {
+    (void)hipFree(s->d_h);
+    s->d_h = nullptr;
+  } else if (!rc && hflat && s->G) {
+    if (!s->d_h && hipMalloc((void **)&s->d_h, sizeof(double) * s->G) != hipSuccess) rc = stb_fail("stb_tindic_set_h: out of device memory");
+    if (!rc && hipMemcpy(s->d_h, hflat, sizeof(double) * s->G, hipMemcpyHostToDevice) != hipSuccess)
+      rc = stb_fail("stb_tindic_set_h: %s", hipGetErrorString(hipGetLastError()));
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_sweep(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, int nsweeps) {
+  STB_ENTRY;
+  if (!s) return stb_fail("stb_tindic_sweep: null object");
+  if (!(a >= 0.0 && a < 1.0)) return stb_fail("stb_tindic_sweep: discount a=%g outside [0, 1)", a);
+  if (!bpar) return stb_fail("stb_tindic_sweep: bpar is required");
+  if (nsweeps < 0) return stb_fail("stb_tindic_sweep: nsweeps=%d", nsweeps);
+  for (int i = 0; i < s->I; i++)
+    if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("stb_tindic_sweep: bpar[%d]=%g (must be > -a = %g)", i, bpar[i], -a);
+  if (nsweeps == 0) return 0;
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (s->need_table && !(a == s->a_filled)) {  // (refilled only when the discount changes; the refill is checked: a wait)
+    s->a_filled = NAN;
+    rc = stb_fill_V(&a, 1, s->N, s->M, s->d_vt, s->vstride, s->d_ws, s->ws_bytes, s->st);
+    if (!rc) rc = stb_fill_status();
+    if (!rc) s->a_filled = a;
+  }
+  // new concentrations through the staging buffer used two calls ago (its copy is long through); unchanged ones stay
+  const bool same_b = s->last_bpar.size() == (size_t)s->I && memcmp(s->last_bpar.data(), bpar, sizeof(double) * s->I) == 0;
+  if (!rc && !same_b) {
+    const int k = s->slot ^= 1;
+    s->last_bpar.clear();
+    if (hipEventSynchronize(s->ev_bpar[k]) != hipSuccess) rc = stb_fail("stb_tindic_sweep: %s", hipGetErrorString(hipGetLastError()));
+    if (!rc) {
+      memcpy(s->h_bpar[k], bpar, sizeof(double) * s->I);
+      if (hipMemcpyAsync(s->d_bpar, s->h_bpar[k], sizeof(double) * s->I, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+          hipEventRecord(s->ev_bpar[k], s->st) != hipSuccess)
+        rc = stb_fail("stb_tindic_sweep: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (!rc) s->last_bpar.assign(bpar, bpar + s->I);
+  }
+  if (!rc)
+    rc = ti_launch(s->d_vt, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T,
+                   s->d_h, s->d_coff, s->d_cust, s->flags, seed, sweep, nsweeps, s->maxK, s->st);
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_get(stb_tindic_t *s, uint16_t *t_out, uint32_t *T_out) {
+  STB_ENTRY;
+  if (!s) return stb_fail("stb_tindic_get: null object");
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if ((t_out && s->G && hipMemcpyAsync(t_out, s->d_t, sizeof(uint16_t) * s->G, hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
+      (T_out && hipMemcpyAsync(T_out, s->d_T, sizeof(uint32_t) * s->I, hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
+      hipStreamSynchronize(s->st) != hipSuccess)
+    rc = stb_fail("stb_tindic_get: %s", hipGetErrorString(hipGetLastError()));
+  stb_device_leave(prev);
+  return rc;
+}
+
+// the pairs and T to a group set of the same shape, device to device: what stb_tcounts_to_groups does
+extern "C" int stb_tindic_to_groups(stb_tindic_t *s, stb_groups_t *g, const double *bpar) {
+  STB_ENTRY;
+  if (!s || !g) return stb_fail("stb_tindic_to_groups: null object");
+  if (g->I != s->I || g->G != s->G)
+    return stb_fail("stb_tindic_to_groups: the group set has I=%d, G=%llu; the indicators I=%d, G=%llu", g->I,
+                    (unsigned long long)g->G, s->I, (unsigned long long)s->G);
+  if (g->dev != s->dev) return stb_fail("stb_tindic_to_groups: the group set is on device %d, the indicators on %d", g->dev, s->dev);
+  if (g->pending == 1) return stb_fail("stb_tindic_to_groups: an evaluation queued with stb_groups_aterms_async has not been waited for");
+  if (g->putting) return stb_fail("stb_tindic_to_groups: the group set is between stb_groups_pairs_begin and _commit");
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  // the bounds the new pairs can need, known without looking at them: n up to max n, t up to min(max n, M)
+  unsigned N = g->have_bounds ? g->N : 0, M = g->have_bounds ? g->M : 0;
+  if (N < s->maxn) N = s->maxn;
+  const unsigned tcap = s->maxn < s->Mdraw ? s->maxn : s->Mdraw;
+  if (M < tcap) M = tcap;
+  if (N < 1) N = 1;
+  if (M < 1) M = 1;
+  hipEvent_t ev = nullptr;
+  if (!rc && hipStreamSynchronize(g->st) != hipSuccess) rc = stb_fail("stb_tindic_to_groups: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc) rc = stb_groups_set_bounds(g, N, M);  // (re-sizes what depends on the bounds when they grow)
+  if (!rc && (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, s->st) != hipSuccess ||
+              hipStreamWaitEvent(g->st, ev, 0) != hipSuccess))
+    rc = stb_fail("stb_tindic_to_groups: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc && ((s->G && (hipMemcpyAsync(g->d_n, s->d_n, sizeof(uint32_t) * s->G, hipMemcpyDeviceToDevice, g->st) != hipSuccess ||
+                        hipMemcpyAsync(g->d_t, s->d_t, sizeof(uint16_t) * s->G, hipMemcpyDeviceToDevice, g->st) != hipSuccess)) ||
+              hipMemcpyAsync(g->d_T, s->d_T, sizeof(uint32_t) * s->I, hipMemcpyDeviceToDevice, g->st) != hipSuccess))
+    rc = stb_fail("stb_tindic_to_groups: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc && bpar) {
+    memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);  // (g->st was idle above: its staging area is free)
+    if (hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess)
+      rc = stb_fail("stb_tindic_to_groups: %s", hipGetErrorString(hipGetLastError()));
+  }
+  // later sweeps must not overwrite the pairs before the set has its copy
+  if (!rc && (hipEventRecord(ev, g->st) != hipSuccess || hipStreamWaitEvent(s->st, ev, 0) != hipSuccess))
+    rc = stb_fail("stb_tindic_to_groups: %s", hipGetErrorString(hipGetLastError()));
+  if (ev) (void)hipEventDestroy(ev);
+  if (!rc) {  // as stb_groups_pairs_commit: new pairs, cell lists rebuilt and the pairs sorted again on first need
+    stb_lists_drop(g, true);
+    g->sorted = 0;
+    g->have_pairs = 1;
+    g->reused = 1;
+  }
+  stb_device_leave(prev);
+  return rc;
+}
