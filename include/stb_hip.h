@@ -318,6 +318,40 @@ int stb_tcounts_get(stb_tcounts_t *s, uint16_t *t_out, uint32_t *T_out);
 int stb_tcounts_to_groups(stb_tcounts_t *s, stb_groups_t *g, const double *bpar /* NULL: keep */);
 void stb_tcounts_free(stb_tcounts_t *s);
 
+/* ---- windowed table counts: t drawn from a window around itself, O(W) a pair instead of O(min(n, M)) (reference
+ * test/check.c:905-935, SampleCTW, made exact).  Pairs, h, T_i, b_i, a and the weights w(tau) exactly as for
+ * stb_tcounts above (T_ = T_i - t).  With Mt = min(n, M), lo(x) = max(1, x - W), hi(x) = min(Mt, x + W),
+ * win(x) = [lo(x), hi(x)] and Z(x) = sum over win(x) of w, a sweep visits each restaurant's pairs in order:
+ *   1. n = 0 keeps t = 0.  n = 1, or Mt = 1, gives t = 1.  n > N (outside the table) keeps t.  (A raw-layer t outside
+ *      [1, Mt] is first clamped into it; T_ still uses the stored t.)
+ *   2. proposal: tau' = the smallest tau in win(t) whose cumulative weight (ascending tau, weights of win(t) scaled by
+ *      exp(-max log w over win(t))) exceeds u1 Z(t).
+ *   3. acceptance (the default, exact mode): if tau' != t, t = tau' iff u2 Z(tau') < Z(t), both sums scaled by
+ *      exp(-max log w over [lo(min(t, tau')), hi(max(t, tau'))]).  STB_TC_REF_WINDOW accepts every proposal: the
+ *      reference's chain in law.  Its normaliser Z(t) depends on the state, so that chain does not leave the PYP joint
+ *      invariant (deviation 11); with the test, pi(t) q(t -> tau') alpha = pi(t) pi(tau')
+ *      min(1/Z(t), 1/Z(tau')) is symmetric (|t - tau'| <= W either way) and the exact conditional is invariant.
+ *   4. T_i is updated before the next pair.
+ * log w is evaluated up to a constant per visit (the log terms summed outward from t on spans of up to 64 tau, from the
+ * span's start on longer ones): the draws agree with a replay in another summation order up to rounding.  W >= 1 is any
+ * unsigned value; windows are clipped to [1, Mt].  When W >= Mt - 1 for every pair the proposal is the full conditional
+ * and every proposal is accepted: the law of stb_tcounts_sweep, not its bits.  Uniforms of sweep s: key = mix(seed +
+ * (s+1) gamma); u1 = top 53 bits of mix(key + (2g+1) gamma) / 2^53, u2 the same at 2g+2 (g the flat pair index) --
+ * stb_tindic's convention on pairs, the same stream as stb_tcounts' and stb_tindic's for the same seed and sweep (a caller
+ * that alternates samplers gives them different seeds).  The draws depend on (seed, sweep, g) alone, not on launch
+ * geometry (STB_TCWIN_WAVES = 1, 2, 4 or 8 waves a workgroup, one restaurant a wave).
+ * Raw layer: the arguments of stb_sample_tcounts plus W and flags; M <= 65535.  W = 0 and unknown flag bits are refused.
+ * One sweep.  Object layer: stb_tcounts_sweep_window runs on an stb_tcounts_t with stb_tcounts_sweep's table (refilled
+ * only when a changes), staging, stream and input checks; full and windowed sweeps mix freely on one object, and
+ * _get / _to_groups see either.  A failure returns non-zero with stb_last_error() set and leaves the state as it was. */
+#define STB_TC_REF_WINDOW 1u
+int stb_sample_tcounts_window(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a,
+                              const double *d_bpar, int I, const uint64_t *d_koff /* I+1 */, const uint32_t *d_n,
+                              uint16_t *d_t, uint32_t *d_T, const double *d_h /* NULL: 1 */, unsigned W, unsigned flags,
+                              uint64_t seed, uint64_t sweep, void *stream);
+int stb_tcounts_sweep_window(stb_tcounts_t *s, double a, const double *bpar /* host [I] */, unsigned W, unsigned flags,
+                             uint64_t seed, uint64_t sweep, int nsweeps);
+
 /* ---- table indicators: the other t-sampler, one Gibbs step per customer (reference test/demo.c:405-436, SampleTI of
  * test/check.c:843-866), with the exact prior ratio.  Pairs, h, T_i, b_i and a as for stb_tcounts above.  The customers of
  * restaurant i are a sequence of its pair indices, cust[coff[i] .. coff[i+1]) (uint32, local k): pair k appears exactly

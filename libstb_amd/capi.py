@@ -169,6 +169,8 @@ def lib() -> C.CDLL:
     sig("stb_tcounts_get", i, [vp, c_u16_p, c_u32_p])
     sig("stb_tcounts_to_groups", i, [vp, vp, c_double_p])
     sig("stb_tcounts_free", None, [vp])
+    sig("stb_sample_tcounts_window", i, [vp, vp, u, u, d, vp, i, vp, vp, vp, vp, vp, u, u, u64, u64, vp])
+    sig("stb_tcounts_sweep_window", i, [vp, d, c_double_p, u, u, u64, u64, i])
     sig("stb_sample_tindic", i, [vp, u, u, d, vp, i, vp, vp, vp, vp, vp, vp, vp, u, u64, u64, vp])
     sig("stb_tindic_create", vp, [i, c_int_p, c_u32_p, c_u16_p, c_double_p, c_u32_p, u, u])
     sig("stb_tindic_set_h", i, [vp, c_double_p])
@@ -445,6 +447,9 @@ class DeviceGroups:
         self.bpar = torch.as_tensor(g.bpar, device=device)
 
 
+TC_REF_WINDOW = 1  # stb_tcounts_sweep_window / stb_sample_tcounts_window flag: the reference's chain
+
+
 class TableCounts:
     """Table counts t of (n, t) pairs resampled on the device by collapsed Gibbs sweeps (stb_tcounts_*).  K, n, t
     (and h, NULL: all 1) in the CSR layout of synth.Groups; M = 0 draws from the full conditional (the largest n)."""
@@ -469,6 +474,13 @@ class TableCounts:
         bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
         check(self.L.stb_tcounts_sweep(self.h, float(a), dp(bpar), seed, sweep, nsweeps))
 
+    def sweep_window(self, a, bpar, window: int, seed: int, sweep: int, nsweeps: int = 1, ref: bool = False):
+        """windowed sweeps sweep .. sweep+nsweeps-1, queued: t moves at most `window` a visit, by an exact
+        Metropolis-Hastings step (ref: the reference's chain, every proposal accepted)"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        check(self.L.stb_tcounts_sweep_window(self.h, float(a), dp(bpar), int(window), TC_REF_WINDOW if ref else 0, seed,
+                                              sweep, nsweeps))
+
     def get(self):
         """(t[G] uint16, T[I] uint32) after the queued sweeps"""
         t = np.zeros(self.G, dtype=np.uint16)
@@ -491,6 +503,17 @@ class TableCounts:
             self.free()
         except Exception:
             pass
+
+
+def sample_tcounts_window(tabs, a, bpar, koff, n, t, T, h, window: int, seed: int, sweep: int, ref: bool = False,
+                          stream=None):
+    """one windowed sweep (stb_sample_tcounts_window) on device arrays, t and T in place: tabs a DeviceTables filled for
+    `a` (its first slab and its bounds N, M are used), koff (int64 [I+1]), n (int32), t (int16), T (int32), bpar and h
+    (float64; h None: all 1) torch tensors on the device"""
+    check(lib().stb_sample_tcounts_window(tabs.tables.data_ptr(), tabs.S1.data_ptr(), tabs.N, tabs.M, float(a),
+                                          bpar.data_ptr(), int(koff.shape[0]) - 1, koff.data_ptr(), n.data_ptr(),
+                                          t.data_ptr(), T.data_ptr(), None if h is None else h.data_ptr(), int(window),
+                                          TC_REF_WINDOW if ref else 0, seed, sweep, stream_ptr(stream)))
 
 
 TI_REF_ODDS = 1  # stb_tindic_create / stb_sample_tindic flag: the reference's factor t / (n-t+1) (DESIGN.md section 6)

@@ -27,17 +27,10 @@
 
 #include "stb_common.h"
 #include "groups.h"
+#include "tcounts.h"
 
 #define STB_TC_CAP 4096      // tau values a workgroup keeps in LDS (32 KB); longer rows recompute
 #define STB_TC_MAXWAVES 16
-
-static constexpr uint64_t STB_GAMMA = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ static inline uint64_t stb_mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // ---- workgroup collectives (nw = waves of the workgroup; every thread gets the same bits) ----
 
@@ -95,14 +88,6 @@ __device__ __forceinline__ unsigned tc_min(unsigned v, int nw, tc_shared &sh) {
   for (int w = 1; w < nw; w++) m = min(m, sh.wmin[w]);
   __syncthreads();
   return m;
-}
-
-// S_S(n, tau) for 1 <= tau <= min(n, M): dev_S_S of sweep_terms.hip for the cells a draw can address
-// (n <= N: the kernel leaves pairs with n > N alone)
-__device__ __forceinline__ double tc_S(const double *row, const double *S1, unsigned n, unsigned tau) {
-  if (tau == n) return 0.0;
-  if (tau == 1) return S1[n - 1];
-  return row[tau - 2];
 }
 
 // one chunk of pass 1: log w at tau (-inf outside 1..tmax); *carry advances by the chunk's sum of log terms
@@ -163,7 +148,7 @@ __global__ __launch_bounds__(1024) void k_tcounts(const double *table, const dou
           c2 += tot;
           if (cached && tau <= tmax) lds[tau - 1] = c;
         }
-        const double u = (double)(stb_mix64(key + (g + 1) * STB_GAMMA) >> 11) * (1.0 / 9007199254740992.0);
+        const double u = tc_unit(key, g + 1);
         const double target = u * c2;
         // pass 3: the first tau with C(tau) > u W
         unsigned first = 0xffffffffu;
@@ -390,16 +375,20 @@ extern "C" int stb_tcounts_set_h(stb_tcounts_t *s, const double *hflat) {
   return rc;
 }
 
-extern "C" int stb_tcounts_sweep(stb_tcounts_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, int nsweeps) {
-  STB_ENTRY;
-  if (!s) return stb_fail("stb_tcounts_sweep: null object");
-  if (!(a >= 0.0 && a < 1.0)) return stb_fail("stb_tcounts_sweep: discount a=%g outside [0, 1)", a);
-  if (!bpar) return stb_fail("stb_tcounts_sweep: bpar is required");
-  if (nsweeps < 0) return stb_fail("stb_tcounts_sweep: nsweeps=%d", nsweeps);
+// what every sweep of the object checks before anything changes: a failure leaves the state as it was
+static int tc_check_sweep(stb_tcounts_t *s, double a, const double *bpar, int nsweeps, const char *who) {
+  if (!s) return stb_fail("%s: null object", who);
+  if (!(a >= 0.0 && a < 1.0)) return stb_fail("%s: discount a=%g outside [0, 1)", who, a);
+  if (!bpar) return stb_fail("%s: bpar is required", who);
+  if (nsweeps < 0) return stb_fail("%s: nsweeps=%d", who, nsweeps);
   for (int i = 0; i < s->I; i++)
-    if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("stb_tcounts_sweep: bpar[%d]=%g (must be > -a = %g)", i, bpar[i], -a);
-  if (nsweeps == 0) return 0;
-  const int prev = stb_device_enter(s->dev);
+    if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
+  return 0;
+}
+
+// what every sweep of the object needs queued before its kernel (on the object's device): the table for `a` and the
+// concentrations bpar on the device
+static int tc_stage(stb_tcounts_t *s, double a, const double *bpar, const char *who) {
   int rc = 0;
   if (s->need_table && !(a == s->a_filled)) {  // (refilled only when the discount changes; the refill is checked: a wait)
     s->a_filled = NAN;
@@ -412,18 +401,44 @@ extern "C" int stb_tcounts_sweep(stb_tcounts_t *s, double a, const double *bpar,
   if (!rc && !same_b) {
     const int k = s->slot ^= 1;
     s->last_bpar.clear();
-    if (hipEventSynchronize(s->ev_bpar[k]) != hipSuccess) rc = stb_fail("stb_tcounts_sweep: %s", hipGetErrorString(hipGetLastError()));
+    if (hipEventSynchronize(s->ev_bpar[k]) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
     if (!rc) {
       memcpy(s->h_bpar[k], bpar, sizeof(double) * s->I);
       if (hipMemcpyAsync(s->d_bpar, s->h_bpar[k], sizeof(double) * s->I, hipMemcpyHostToDevice, s->st) != hipSuccess ||
           hipEventRecord(s->ev_bpar[k], s->st) != hipSuccess)
-        rc = stb_fail("stb_tcounts_sweep: %s", hipGetErrorString(hipGetLastError()));
+        rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
     }
     if (!rc) s->last_bpar.assign(bpar, bpar + s->I);
   }
+  return rc;
+}
+
+extern "C" int stb_tcounts_sweep(stb_tcounts_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, int nsweeps) {
+  STB_ENTRY;
+  if (tc_check_sweep(s, a, bpar, nsweeps, "stb_tcounts_sweep")) return 1;
+  if (nsweeps == 0) return 0;
+  const int prev = stb_device_enter(s->dev);
+  int rc = tc_stage(s, a, bpar, "stb_tcounts_sweep");
   if (!rc)
     rc = tc_launch(s->d_table, s->d_S1, s->N, s->M, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, seed, sweep,
                    nsweeps, s->maxn < s->M ? s->maxn : s->M, s->st);
+  stb_device_leave(prev);
+  return rc;
+}
+
+// the windowed sweep (tcwin.hip) on the same object: the same table, concentrations, stream and checks
+extern "C" int stb_tcounts_sweep_window(stb_tcounts_t *s, double a, const double *bpar, unsigned W, unsigned flags,
+                                        uint64_t seed, uint64_t sweep, int nsweeps) {
+  STB_ENTRY;
+  if (W == 0) return stb_fail("stb_tcounts_sweep_window: window W=0 (must be >= 1)");
+  if (flags & ~STB_TC_REF_WINDOW_FLAG) return stb_fail("stb_tcounts_sweep_window: unknown flags 0x%x", flags);
+  if (tc_check_sweep(s, a, bpar, nsweeps, "stb_tcounts_sweep_window")) return 1;
+  if (nsweeps == 0) return 0;
+  const int prev = stb_device_enter(s->dev);
+  int rc = tc_stage(s, a, bpar, "stb_tcounts_sweep_window");
+  if (!rc)
+    rc = stb_tcw_launch(s->d_table, s->d_S1, s->N, s->M, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, W,
+                        flags, seed, sweep, nsweeps, s->st);
   stb_device_leave(prev);
   return rc;
 }
