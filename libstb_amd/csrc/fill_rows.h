@@ -58,10 +58,11 @@ __device__ __forceinline__ double ld_logadd(double V, double lp) {
   }
   return hi + log(1.0 + exp(lo - hi));
 }
-// lib/stable.c:384-385: logadd(log(N-M*a-1.0) + S[N-1][M], S[N-1][M-1])
+// lib/stable.c:384-385: logadd(log(N-M*a-1.0) + S[N-1][M], S[N-1][M-1]); column 1 is the running sum of
+// log((N-1) - a) of lib/stable.c:337-348, integer N-1 formed first (near a = 1, (N - a) - 1.0 loses ~N/(1-a) units)
 __device__ __forceinline__ double ld_cell(int n, int c, double a, double up, double left) {
 #pragma clang fp contract(off)
-  const double coef = ((double)n - (double)c * a) - 1.0;
+  const double coef = (c == 1) ? (double)(n - 1) - a : ((double)n - (double)c * a) - 1.0;
   return ld_logadd(log(coef) + up, left);
 }
 
