@@ -406,6 +406,50 @@ typedef struct stb_hist stb_hist_t;
 stb_hist_t *stb_hist_create(const uint32_t *cnt, unsigned S, int I, const uint32_t *T, const double *bpar);
 int stb_hist_aterms2(stb_hist_t *h, const double *x_host, int D, double *out_host);
 void stb_hist_free(stb_hist_t *h);
+/* A histogram the device fills (stb_sample_partition, stb_tcounts_partition):
+ *   stb_hist_create_empty   S sizes, I restaurants on the current device; counts 0, T 0, bpar 1
+ *   stb_hist_restaurants    T[I], bpar[I] from the host, after the histogram's queued work
+ *   stb_hist_counts_device  its device counts cnt[S] and its stream (hipStream_t as void*): work that writes the counts
+ *                           is queued there (or ordered before the histogram's next call by the caller)
+ *   stb_hist_get            waits for its stream, then cnt[S] to the host
+ * stb_hist_aterms2 on a histogram the device filled returns what stb_hist_create returns on the same counts, T and bpar
+ * uploaded from the host: the same buffers, the same kernels. */
+stb_hist_t *stb_hist_create_empty(unsigned S, int I);
+int stb_hist_restaurants(stb_hist_t *h, const uint32_t *T, const double *bpar);
+uint32_t *stb_hist_counts_device(stb_hist_t *h, unsigned *S, void **stream);
+int stb_hist_get(stb_hist_t *h, uint32_t *cnt_out);
+
+/* ---- table-size partitions: stage 1 of the S-free discount step, on the device (partition.hip) ----
+ * For every pair (n, t), how the n customers split over the t tables, drawn exactly: in rounds r = 0 .. t-2, with M = t-1-r
+ * tables to open after this one and N customers unplaced, the next table's size l = 1 .. N-M with probability
+ *     C(N-1, l-1) (1-a)_{l-1} S^{N-l}_M / S^N_{M+1}
+ * (S with stb_lookup_S's semantics); the last table takes the N left.  Each round draws the smallest l whose cumulative
+ * weight exceeds u W (W the round's total, the arithmetic written out in partition.hip's header) with a fresh uniform:
+ * key = mix(seed + (sweep+1) gamma), u = element g 65536 + r + 1 of that stream (splitmix64, libstb_amd/synth.py) --
+ * the draws depend on (seed, sweep, g, r) alone.  STB_PT_REF_WALK draws with lib/samplea.c:295-320's walk instead (the
+ * drop-in samplea2's, one uniform a pair, r = 0's; it does not sample this law: DESIGN.md section 6, deviation 12).
+ * The counts: cnt[s], s = 2 .. S-1, tables of s customers (stb_hist's layout); cnt[1] singleton tables (aterms2 ignores
+ * them); cnt[0] pairs left out.  n = 0 and t = n count nothing; t = 1 counts one table of n (reading no table); left out:
+ * t = 0, t > n, n >= S, and 1 < t < n with n > N or t > M.  cnt is zeroed and filled on `stream`.  d_sizes / d_soff
+ * (both or neither; d_soff G+1 offsets): pair g's t sizes in draw order at d_sizes + d_soff[g], the remainder last
+ * (t = 1: n; t = n: n ones), when its slot holds at least t entries; pairs left out get none.
+ * Raw layer: d_table / d_S1 one slab of stb_fill_S for `a` with bounds (N, M) (not read, and may be NULL, when no pair
+ * has 1 < t < n).  Object layer: stb_tcounts_partition on the object's pairs, table (refilled when a changes) and
+ * stream, queued behind its sweeps; fills h's counts, copies T (device to device) and bpar (host [I]) to h; nothing comes
+ * back to the host, and h's later calls wait for it.  Refused, with the state as it was: a outside [0, 1), bad bpar (as
+ * stb_tcounts_sweep), a histogram on another device, with another I, or with S <= the largest n, and pairs holding 2^32
+ * or more customers. */
+#define STB_PT_REF_WALK 1u
+int stb_sample_partition(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, uint64_t G,
+                         const uint32_t *d_n, const uint16_t *d_t, uint32_t *d_cnt, unsigned S,
+                         uint16_t *d_sizes, const uint64_t *d_soff /* both NULL: histogram only */, unsigned flags,
+                         uint64_t seed, uint64_t sweep, void *stream);
+int stb_tcounts_partition(stb_tcounts_t *s, double a, stb_hist_t *h, const double *bpar /* host [I] */, uint64_t seed,
+                          uint64_t sweep);
+/* stage 2 on a histogram: samplea2's bracket around a and its ARMS or slice draw (STB_SAMPLER as for samplea2) from
+ * aterms2 on h, with the caller's rng (an rngp_t, include/srng.h); the drop-in samplea2 runs this same code.  h must
+ * hold the partition drawn at `a`, and its T and bpar. */
+double stb_samplea2_hist(double a, stb_hist_t *h, void *rng, int loops, int verbose);
 /* the table sizes the most recent samplea2() sampled, in the reference's layout (ALData.m,
  * lib/samplea.c:283-320): returns the number of entries and, through m, the array (uint16) */
 size_t stb_samplea2_partition(const uint16_t **m);

@@ -178,6 +178,12 @@ def lib() -> C.CDLL:
     sig("stb_tindic_get", i, [vp, c_u16_p, c_u32_p])
     sig("stb_tindic_to_groups", i, [vp, vp, c_double_p])
     sig("stb_tindic_free", None, [vp])
+    sig("stb_sample_partition", i, [vp, vp, u, u, d, u64, vp, vp, vp, u, vp, vp, u, u64, u64, vp])
+    sig("stb_tcounts_partition", i, [vp, d, vp, c_double_p, u64, u64])
+    sig("stb_hist_create_empty", vp, [u, i])
+    sig("stb_hist_restaurants", i, [vp, c_u32_p, c_double_p])
+    sig("stb_hist_counts_device", vp, [vp, C.POINTER(u), C.POINTER(vp)])
+    sig("stb_hist_get", i, [vp, c_u32_p])
     # optional entry points (present once the sampler host code is linked in)
     for name, res, args in (
         ("arms_simple", i, [i, c_double_p, c_double_p, LOGDENS, vp, i, c_double_p, c_double_p]),
@@ -193,6 +199,7 @@ def lib() -> C.CDLL:
         ("stb_hist_create", vp, [c_u32_p, u, i, c_u32_p, c_double_p]),
         ("stb_hist_aterms2", i, [vp, c_double_p, i, c_double_p]),
         ("stb_hist_free", None, [vp]),
+        ("stb_samplea2_hist", d, [d, vp, vp, i, i]),
         ("S_approx", d, [i, i, C.c_float]),
         ("S_approx_da", d, [i, i, C.c_float]),
         ("digammaRN", d, [d]),
@@ -493,6 +500,12 @@ class TableCounts:
         bp = None if bpar is None else dp(np.ascontiguousarray(bpar, dtype=np.float64))
         check(self.L.stb_tcounts_to_groups(self.h, groups, bp))
 
+    def partition(self, a, hist, bpar, seed: int, sweep: int):
+        """stage 1 of the S-free discount step on the current pairs, queued: the table-size histogram into `hist` (a
+        Histogram with I restaurants and S > the largest n), with T and bpar (stb_tcounts_partition)"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        check(self.L.stb_tcounts_partition(self.h, float(a), hist.h, dp(bpar), seed, sweep))
+
     def free(self):
         if self.h:
             self.L.stb_tcounts_free(self.h)
@@ -514,6 +527,81 @@ def sample_tcounts_window(tabs, a, bpar, koff, n, t, T, h, window: int, seed: in
                                           bpar.data_ptr(), int(koff.shape[0]) - 1, koff.data_ptr(), n.data_ptr(),
                                           t.data_ptr(), T.data_ptr(), None if h is None else h.data_ptr(), int(window),
                                           TC_REF_WINDOW if ref else 0, seed, sweep, stream_ptr(stream)))
+
+
+PT_REF_WALK = 1  # stb_sample_partition flag: lib/samplea.c's walk, as the drop-in samplea2
+
+
+class Histogram:
+    """A table-size histogram on the device (stb_hist_t): cnt[S] (cnt[s], s >= 2, tables of s customers; cnt[1]
+    singletons; cnt[0] pairs left out) with the I restaurants' T and bpar, as aterms2 reads it.  From host counts
+    (stb_hist_create) or empty, for a partition call to fill (stb_hist_create_empty)."""
+
+    def __init__(self, S: int, I: int, cnt=None, T=None, bpar=None):
+        self.L = lib()
+        self.S, self.I = int(S), int(I)
+        if cnt is None:
+            self.h = self.L.stb_hist_create_empty(self.S, self.I)
+        else:
+            cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+            T = np.ascontiguousarray(T, dtype=np.uint32)
+            bpar = np.ascontiguousarray(bpar, dtype=np.float64)
+            assert cnt.shape[0] == self.S and T.shape[0] == self.I and bpar.shape[0] == self.I
+            self.h = self.L.stb_hist_create(cnt.ctypes.data_as(c_u32_p), self.S, self.I, T.ctypes.data_as(c_u32_p), dp(bpar))
+        if not self.h:
+            raise StbError(last_error())
+
+    def restaurants(self, T, bpar):
+        T = np.ascontiguousarray(T, dtype=np.uint32)
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        check(self.L.stb_hist_restaurants(self.h, T.ctypes.data_as(c_u32_p), dp(bpar)))
+
+    def device_counts(self):
+        """(device address of cnt[S], the histogram's stream as an int)"""
+        S, st = C.c_uint(0), C.c_void_p()
+        p = self.L.stb_hist_counts_device(self.h, C.byref(S), C.byref(st))
+        if not p:
+            raise StbError(last_error())
+        return p, st.value
+
+    def counts(self):
+        """cnt[S] uint32, after the work queued on the histogram"""
+        out = np.zeros(self.S, dtype=np.uint32)
+        check(self.L.stb_hist_get(self.h, out.ctypes.data_as(c_u32_p)))
+        return out
+
+    def aterms2(self, xs):
+        """aterms2 at the discounts xs (at most 64 a call; stb_hist_aterms2)"""
+        xs = np.ascontiguousarray(np.atleast_1d(np.asarray(xs, dtype=np.float64)))
+        out = np.zeros(xs.shape[0])
+        check(self.L.stb_hist_aterms2(self.h, dp(xs), int(xs.shape[0]), dp(out)))
+        return out
+
+    def free(self):
+        if self.h:
+            self.L.stb_hist_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def sample_partition(tabs, a, n, t, S: int, seed: int, sweep: int, sizes=None, soff=None, ref: bool = False, cnt=None,
+                     stream=None):
+    """one partition draw (stb_sample_partition) on device arrays: tabs a DeviceTables filled for `a` (its first slab
+    and its bounds N, M), n (int32) and t (int16) torch tensors on the device; sizes (int16) and soff (int64 [G+1]) both
+    or neither.  Returns cnt (int32 [S] torch tensor on the device, zeroed and filled on `stream`)."""
+    torch = _torch()
+    if cnt is None:
+        cnt = torch.empty(S, dtype=torch.int32, device=n.device)
+    check(lib().stb_sample_partition(tabs.tables.data_ptr(), tabs.S1.data_ptr(), tabs.N, tabs.M, float(a),
+                                     int(n.shape[0]), n.data_ptr(), t.data_ptr(), cnt.data_ptr(), int(S),
+                                     None if sizes is None else sizes.data_ptr(), None if soff is None else soff.data_ptr(),
+                                     PT_REF_WALK if ref else 0, seed, sweep, stream_ptr(stream)))
+    return cnt
 
 
 TI_REF_ODDS = 1  # stb_tindic_create / stb_sample_tindic flag: the reference's factor t / (n-t+1) (DESIGN.md section 6)

@@ -69,18 +69,11 @@ size_t stb_samplea2_partition(const stcnt_int **m) {
   return last_m_count;
 }
 
-double samplea2(double mya, stable_t *S, int I, int *K, scnt_int *T, scnt_int **n, stcnt_int **t,
-                void (*getval)(scnt_int *n, stcnt_int *t, unsigned i, unsigned k), double *bpar, rngp_t rng,
-                int loops, int verbose) {
+/* stage 2 (lib/samplea.c:257-270, 322-338): the bracket around a, then ARMS or the slice sampler on aterms2 */
+double stb_samplea2_hist(double mya, stb_hist_t *h, rngp_t rng, int loops, int verbose) {
   double inita[3] = {A_MIN, 1, A_MAX};
   a2_posterior ap;
-  uint32_t *cnt;
-  stcnt_int *mp;
-  size_t n_m = 0;
-  unsigned maxn = 2;
-  int i, k;
 
-  /* lib/samplea.c:257-270 */
   inita[1] = mya;
   if (fabs(inita[1] - A_MAX) / A_MAX < 0.00001) inita[1] = A_MAX * 0.999 + A_MIN * 0.001;
   if (fabs(inita[1] - A_MIN) / A_MIN < 0.00001) inita[1] = A_MIN * 0.999 + A_MAX * 0.001;
@@ -88,6 +81,35 @@ double samplea2(double mya, stable_t *S, int I, int *K, scnt_int *T, scnt_int **
   if (inita[1] - SQUEEZEA > A_MIN) inita[0] = inita[1] - SQUEEZEA;
   if (inita[1] + SQUEEZEA < A_MAX) inita[2] = inita[1] + SQUEEZEA;
 #endif
+  ap.verbose = verbose;
+  ap.dev = h;
+  stb_trace_reset();
+  if (!use_slice2()) {
+    int code = arms_simple(3, inita, inita + 2, aterms2, &ap, 0, inita + 1, &mya); /* lib/samplea.c:325 (with the data) */
+    stb_trace_code(code);
+    if (mya < inita[0] || mya > inita[2]) {
+      fprintf(stderr, "Arms_simple(apar) returned value out of bounds\n");
+      exit(1);
+    }
+  } else {
+    inita[1] = A_MAX; /* lib/samplea.c:332 */
+    if (SliceSimple(&mya, aterms2, inita, rng, loops, &ap)) {
+      fprintf(stderr, "SliceSimple error\n");
+      exit(1);
+    }
+  }
+  return mya;
+}
+
+double samplea2(double mya, stable_t *S, int I, int *K, scnt_int *T, scnt_int **n, stcnt_int **t,
+                void (*getval)(scnt_int *n, stcnt_int *t, unsigned i, unsigned k), double *bpar, rngp_t rng,
+                int loops, int verbose) {
+  stb_hist_t *h;
+  uint32_t *cnt;
+  stcnt_int *mp;
+  size_t n_m = 0;
+  unsigned maxn = 2;
+  int i, k;
 
   /* lib/samplea.c:283-288: space for the table sizes */
   for (i = 0; i < I; i++)
@@ -155,28 +177,13 @@ double samplea2(double mya, stable_t *S, int I, int *K, scnt_int *T, scnt_int **
       }
     }
 
-  ap.verbose = verbose;
-  ap.dev = stb_hist_create(cnt, maxn + 1, I, T, bpar);
+  h = stb_hist_create(cnt, maxn + 1, I, T, bpar);
   free(cnt);
-  if (!ap.dev) {
+  if (!h) {
     fprintf(stderr, "Out of memory for samplea() (%s)\n", stb_last_error());
     exit(1);
   }
-  stb_trace_reset();
-  if (!use_slice2()) {
-    int code = arms_simple(3, inita, inita + 2, aterms2, &ap, 0, inita + 1, &mya); /* lib/samplea.c:325 (with the data) */
-    stb_trace_code(code);
-    if (mya < inita[0] || mya > inita[2]) {
-      fprintf(stderr, "Arms_simple(apar) returned value out of bounds\n");
-      exit(1);
-    }
-  } else {
-    inita[1] = A_MAX; /* lib/samplea.c:332 */
-    if (SliceSimple(&mya, aterms2, inita, rng, loops, &ap)) {
-      fprintf(stderr, "SliceSimple error\n");
-      exit(1);
-    }
-  }
-  stb_hist_free(ap.dev);
+  mya = stb_samplea2_hist(mya, h, rng, loops, verbose);
+  stb_hist_free(h);
   return mya;
 }

@@ -7,7 +7,10 @@
 //       k_to_float        S_FLOAT storage: narrow a slab                     lib/stable.h:31-33
 // Sums are double-double per thread, then a fixed-shape tree: the same bits on every run.
 
+#include <vector>
+
 #include "stb_common.h"
+#include "tcounts.h"
 
 // ------------------------------------------------------------------------------------------------
 // S_FLOAT storage: narrow a slab
@@ -598,15 +601,14 @@ extern "C" void stb_hist_free(stb_hist_t *h) {
   free(h);
 }
 
-extern "C" stb_hist_t *stb_hist_create(const uint32_t *cnt, unsigned S, int I, const uint32_t *T, const double *bpar) {
-  STB_ENTRY;
+// the buffers and stream of a histogram of S sizes for I restaurants, nothing uploaded (the current device's)
+static stb_hist_t *hist_alloc(unsigned S, int I, const char *who) {
   if (stb_device_count() < 1) {
-    stb_fail("stb_hist_create: no HIP device (libstb_amd has no CPU path)");
+    stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
     return nullptr;
   }
   stb_hist_t *h = (stb_hist_t *)calloc(1, sizeof(*h));
   if (!h) return nullptr;
-  const int prev = stb_device_enter(stb_get_device());
   bool ok = hipGetDevice(&h->dev) == hipSuccess;
   h->S = S;
   h->I = I;
@@ -621,19 +623,107 @@ extern "C" stb_hist_t *stb_hist_create(const uint32_t *cnt, unsigned S, int I, c
   ok = ok && stb_pool_malloc((void **)&h->d_out, sizeof(double) * 2 * STB_TERMS_DMAX) == hipSuccess;
   ok = ok && stb_pool_malloc(&h->d_ws, h->ws_bytes) == hipSuccess;
   ok = ok && stb_pool_malloc((void **)&h->d_partial, sizeof(dd_t) * STB_TERMS_DMAX * h->nb) == hipSuccess;
+  if (!ok) {
+    const hipError_t e = hipGetLastError();
+    stb_fail("%s: %s", who, e != hipSuccess ? hipGetErrorString(e) : "out of memory");
+    stb_hist_free(h);
+    return nullptr;
+  }
+  return h;
+}
+
+extern "C" stb_hist_t *stb_hist_create(const uint32_t *cnt, unsigned S, int I, const uint32_t *T, const double *bpar) {
+  STB_ENTRY;
+  const int prev = stb_device_enter(stb_get_device());
+  stb_hist_t *h = hist_alloc(S, I, "stb_hist_create");
+  bool ok = h != nullptr;
   if (ok && S) ok = hipMemcpy(h->d_cnt, cnt, sizeof(uint32_t) * S, hipMemcpyHostToDevice) == hipSuccess;
   if (ok && I > 0)
     ok = hipMemcpy(h->d_T, T, sizeof(uint32_t) * I, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(h->d_bpar, bpar, sizeof(double) * I, hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    const hipError_t e = hipGetLastError();
-    stb_fail("stb_hist_create: %s", e != hipSuccess ? hipGetErrorString(e) : "out of memory");
-    stb_device_leave(prev);
+  if (h && !ok) {
+    stb_fail("stb_hist_create: %s", hipGetErrorString(hipGetLastError()));
     stb_hist_free(h);
-    return nullptr;
+    h = nullptr;
   }
   stb_device_leave(prev);
   return h;
+}
+
+// a histogram whose counts a partition call fills on the device: counts 0, T 0, bpar 1 until set
+extern "C" stb_hist_t *stb_hist_create_empty(unsigned S, int I) {
+  STB_ENTRY;
+  if (S < 2 || I < 0) {
+    stb_fail("stb_hist_create_empty: S=%u I=%d (S >= 2, I >= 0)", S, I);
+    return nullptr;
+  }
+  const int prev = stb_device_enter(stb_get_device());
+  stb_hist_t *h = hist_alloc(S, I, "stb_hist_create_empty");
+  bool ok = h != nullptr;
+  if (ok) {
+    std::vector<double> ones((size_t)(I > 0 ? I : 1), 1.0);
+    ok = hipMemset(h->d_cnt, 0, sizeof(uint32_t) * S) == hipSuccess &&
+         hipMemset(h->d_T, 0, sizeof(uint32_t) * (I > 0 ? I : 1)) == hipSuccess &&
+         hipMemcpy(h->d_bpar, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+      stb_fail("stb_hist_create_empty: %s", hipGetErrorString(hipGetLastError()));
+      stb_hist_free(h);
+      h = nullptr;
+    }
+  }
+  stb_device_leave(prev);
+  return h;
+}
+
+// new per-restaurant totals and concentrations (host [I]), after the histogram's queued work
+extern "C" int stb_hist_restaurants(stb_hist_t *h, const uint32_t *T, const double *bpar) {
+  STB_ENTRY;
+  if (!h) return stb_fail("stb_hist_restaurants: null histogram");
+  if (h->I > 0 && (!T || !bpar)) return stb_fail("stb_hist_restaurants: T and bpar are required");
+  const int prev = stb_device_enter(h->dev);
+  int rc = 0;
+  if (hipStreamSynchronize(h->st) != hipSuccess ||
+      (h->I > 0 && (hipMemcpy(h->d_T, T, sizeof(uint32_t) * h->I, hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(h->d_bpar, bpar, sizeof(double) * h->I, hipMemcpyHostToDevice) != hipSuccess)))
+    rc = stb_fail("stb_hist_restaurants: %s", hipGetErrorString(hipGetLastError()));
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" uint32_t *stb_hist_counts_device(stb_hist_t *h, unsigned *S, void **stream) {
+  STB_ENTRY;
+  if (!h) {
+    stb_fail("stb_hist_counts_device: null histogram");
+    return nullptr;
+  }
+  if (S) *S = h->S;
+  if (stream) *stream = (void *)h->st;
+  return h->d_cnt;
+}
+
+extern "C" int stb_hist_get(stb_hist_t *h, uint32_t *cnt_out) {
+  STB_ENTRY;
+  if (!h || !cnt_out) return stb_fail("stb_hist_get: null histogram or output");
+  const int prev = stb_device_enter(h->dev);
+  int rc = 0;
+  if (hipMemcpyAsync(cnt_out, h->d_cnt, sizeof(uint32_t) * h->S, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+      hipStreamSynchronize(h->st) != hipSuccess)
+    rc = stb_fail("stb_hist_get: %s", hipGetErrorString(hipGetLastError()));
+  stb_device_leave(prev);
+  return rc;
+}
+
+int stb_hist_view_of(stb_hist_t *h, stb_hist_view *v) {
+  if (!h) return stb_fail("null histogram");
+  v->dev = h->dev;
+  v->I = h->I;
+  v->S = h->S;
+  v->d_cnt = h->d_cnt;
+  v->d_T = h->d_T;
+  v->d_bpar = h->d_bpar;
+  v->st = h->st;
+  return 0;
 }
 
 // out_host[d] = aterms2(x_d): restaurant terms + sum over table sizes of count * log rising factorial

@@ -31,3 +31,22 @@ __device__ __forceinline__ double tc_S(const double *row, const double *S1, unsi
 int stb_tcw_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
                    const uint64_t *d_koff, const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, unsigned W,
                    unsigned flags, uint64_t seed, uint64_t sweep, int nsweeps, hipStream_t st);
+
+#define STB_PT_REF_WALK_FLAG 1u
+
+// the partition draw (partition.hip, include/stb_hip.h stb_sample_partition): zeroes cnt[S] on st, then fills it
+int stb_pt_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, uint64_t G,
+                  const uint32_t *d_n, const uint16_t *d_t, uint32_t *d_cnt, unsigned S, uint16_t *d_sizes,
+                  const uint64_t *d_soff, unsigned flags, uint64_t seed, uint64_t sweep, hipStream_t st);
+// the checks of the raw call that the object's call shares (0, or 1 with stb_last_error() set)
+int stb_pt_check(double a, unsigned N, unsigned M, uint64_t G, unsigned S, unsigned flags, const char *who);
+
+// what the object layer needs of a histogram (sweep_terms.hip)
+struct stb_hist_view {
+  int dev, I;
+  unsigned S;
+  uint32_t *d_cnt, *d_T;
+  double *d_bpar;
+  hipStream_t st;
+};
+int stb_hist_view_of(stb_hist_t *h, stb_hist_view *v);

@@ -219,6 +219,7 @@ struct stb_tcounts {
   uint64_t G;
   unsigned N, M;        // table bounds: N = the largest n (at least 3), M = the column bound the draws are truncated at
   unsigned maxn;
+  uint64_t sumn;        // sum of n over the pairs (the partition's histogram bins are uint32)
   bool need_table;      // some pair can have 2 or more tables (min(max n, M) >= 2); otherwise every draw is t = 1
   uint64_t *d_koff;
   uint32_t *d_n, *d_T;
@@ -302,6 +303,7 @@ static stb_tcounts_t *tc_create_here(int I, const int *K, const uint32_t *nflat,
   s->I = I;
   s->G = G;
   s->maxn = maxn;
+  for (uint64_t g = 0; g < G; g++) s->sumn += nflat[g];
   s->N = maxn < 3 ? 3 : maxn;
   s->M = M;
   s->a_filled = NAN;
@@ -501,6 +503,40 @@ extern "C" int stb_tcounts_to_groups(stb_tcounts_t *s, stb_groups_t *g, const do
     g->have_pairs = 1;
     g->reused = 1;  // (as stb_groups_update_restaurants marks: a set that serves sweep after sweep)
   }
+  stb_device_leave(prev);
+  return rc;
+}
+
+// stage 1 of the S-free discount step (partition.hip) on the object's pairs: the table-size histogram into h, T and bpar
+// to h, all on the device, queued behind the object's earlier work; h's later work waits for it
+extern "C" int stb_tcounts_partition(stb_tcounts_t *s, double a, stb_hist_t *h, const double *bpar, uint64_t seed,
+                                     uint64_t sweep) {
+  STB_ENTRY;
+  const char *who = "stb_tcounts_partition";
+  if (tc_check_sweep(s, a, bpar, 0, who)) return 1;
+  stb_hist_view v;
+  if (!h || stb_hist_view_of(h, &v)) return stb_fail("%s: null histogram", who);
+  if (v.dev != s->dev) return stb_fail("%s: the histogram is on device %d, the counts on %d", who, v.dev, s->dev);
+  if (v.I != s->I) return stb_fail("%s: the histogram has I=%d, the counts I=%d", who, v.I, s->I);
+  if (v.S <= s->maxn) return stb_fail("%s: histogram length S=%u (must exceed the largest n, %u)", who, v.S, s->maxn);
+  if (s->sumn >= (1ull << 32))
+    return stb_fail("%s: the pairs hold %llu customers (the bins are uint32: fewer than 2^32)", who,
+                    (unsigned long long)s->sumn);
+  if (stb_pt_check(a, s->N, s->M, s->G, v.S, 0u, who)) return 1;
+  const int prev = stb_device_enter(s->dev);
+  int rc = tc_stage(s, a, bpar, who);
+  hipEvent_t ev = nullptr;
+  if (!rc && (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, v.st) != hipSuccess ||
+              hipStreamWaitEvent(s->st, ev, 0) != hipSuccess))
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc)
+    rc = stb_pt_launch(s->d_table, s->d_S1, s->N, s->M, a, s->G, s->d_n, s->d_t, v.d_cnt, v.S, nullptr, nullptr, 0u, seed,
+                       sweep, s->st);
+  if (!rc && (hipMemcpyAsync(v.d_T, s->d_T, sizeof(uint32_t) * s->I, hipMemcpyDeviceToDevice, s->st) != hipSuccess ||
+              hipMemcpyAsync(v.d_bpar, s->d_bpar, sizeof(double) * s->I, hipMemcpyDeviceToDevice, s->st) != hipSuccess ||
+              hipEventRecord(ev, s->st) != hipSuccess || hipStreamWaitEvent(v.st, ev, 0) != hipSuccess))
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (ev) (void)hipEventDestroy(ev);
   stb_device_leave(prev);
   return rc;
 }
