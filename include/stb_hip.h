@@ -268,6 +268,13 @@ unsigned stb_groups_fallbacks(void);
 int stb_grid_shape(unsigned N, unsigned M, int D, int *C_out, int *G_out, int *K_out);
 /* what the set was created with (any pointer may be NULL) */
 int stb_groups_shape(const stb_groups_t *g, int *I, uint64_t *G, unsigned *N, unsigned *M, int *Dmax);
+/* which form the set's most recent evaluation was prepared in (any pointer may be NULL): fused 1 when the sums are taken
+ * inside the fill, 0 for stored tables and the gather; which the list layout -- 0 chain, 1 checkpointed, 2 halo-block, 3 / 4 / 5
+ * the grid form with 2 / 4 / 8 columns a lane; sparse 1 for cell lists, 0 for the count slab (chain form only); C, R the
+ * columns per lane and rows per block the lists taken were built for (0, 0 for the forms without strips).  It reads the set
+ * and changes nothing; an evaluation that gave up on a wait and was redone through stored tables still reports the form
+ * it was prepared in, and stb_groups_fallbacks counts it.  Diagnostics. */
+int stb_groups_last_form(const stb_groups_t *g, int *fused, int *which, int *sparse, int *C, int *R);
 /* pieces of the same evaluation, for timing: ms of device time per stage (may be NULL) */
 int stb_groups_aterms_timed(stb_groups_t *g, const double *x_host, int D, double *out_host,
                             float *ms_fill, float *ms_sweep, float *ms_terms);

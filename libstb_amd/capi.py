@@ -62,7 +62,9 @@ def lib() -> C.CDLL:
               "stb_groups_update_pairs", "stb_groups_fallbacks", "stb_grid_shape", "stb_bterms_update",
               # ... and in round 6
               "stb_table_probe", "stb_slow_launches", "stb_shared_gpu_mode", "stb_set_shared_gpu", "stb_note_launch_span",
-              "stb_lookup_V", "stb_lookup_U", "stb_lookup_UV", "stb_groups_aterms_multi", "stb_groups_create_node"}
+              "stb_lookup_V", "stb_lookup_U", "stb_lookup_UV", "stb_groups_aterms_multi", "stb_groups_create_node",
+              # ... and the diagnostics of the truth tests at working shapes
+              "stb_groups_last_form"}
 
     def sig(name, res, args):
         try:
@@ -160,6 +162,7 @@ def lib() -> C.CDLL:
     sig("stb_groups_fallbacks", C.c_uint, [])
     sig("stb_grid_shape", i, [u, u, i, c_int_p, c_int_p, c_int_p])
     sig("stb_groups_shape", i, [vp, c_int_p, C.POINTER(u64), C.POINTER(u), C.POINTER(u), c_int_p])
+    sig("stb_groups_last_form", i, [vp, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p])
     sig("stb_sampler_cache_clear", None, [])
     sig("stb_groups_aterms_timed", i, [vp, c_double_p, i, c_double_p, c_float_p, c_float_p, c_float_p])
     sig("stb_sample_tcounts", i, [vp, vp, u, u, d, vp, i, vp, vp, vp, vp, vp, u64, u64, vp])

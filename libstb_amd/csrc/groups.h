@@ -78,6 +78,7 @@ struct stb_groups {
   hipEvent_t ev_dep;
   int pending, pend_D, pend_fuse, pend_v;
   int sel_which;  // the list layout aterms_prepare chose for a fused evaluation in the halo-block form
+  int last_fused, last_C, last_R;  // what aterms_prepare decided last: fused or not, the strip shape of the lists taken (stb_groups_last_form)
   double *pend_out;
   double pend_x[STB_TERMS_DMAX];
   last_fill pend_fill;

@@ -1235,6 +1235,10 @@ static int aterms_prepare(stb_groups_t *g, int D, bool allow_fuse, bool *fuse_ou
   bool fuse2 = fuse;
   if (fuse && g->sparse && !g->lists_ready[which]) fuse2 = false;  // (no list in this layout: stored tables + gather)
   g->sel_which = which;
+  // (diagnostics, stb_groups_last_form: the strip shape the lists of this layout were built for)
+  g->last_fused = fuse2 ? 1 : 0;
+  g->last_C = !fuse2 || which < 2 ? 0 : (which == 2 ? g->hb_sum_C : stb_which_C(which));
+  g->last_R = !fuse2 || which < 2 ? 0 : g->list_R[which];
   *fuse_out = fuse2;
   *v_out = !fuse2 ? v : (which >= 2 ? STB_FILL_HB : (which ? STB_FILL_CK : STB_FILL_CHAIN));
   return 0;
@@ -1435,6 +1439,16 @@ extern "C" int stb_groups_update_restaurants(stb_groups_t *g, const uint32_t *T,
   }
   stb_device_leave(prev_dev);
   return rc;
+}
+
+extern "C" int stb_groups_last_form(const stb_groups_t *g, int *fused, int *which, int *sparse, int *C_out, int *R_out) {
+  if (!g) return 1;
+  if (fused) *fused = g->last_fused;
+  if (which) *which = g->sel_which;
+  if (sparse) *sparse = g->sparse;
+  if (C_out) *C_out = g->last_C;
+  if (R_out) *R_out = g->last_R;
+  return 0;
 }
 
 extern "C" int stb_groups_shape(const stb_groups_t *g, int *I, uint64_t *G, unsigned *N, unsigned *M, int *Dmax) {

@@ -294,6 +294,51 @@ def bterms(x: float, Q: float, shape: float, T, apar: float):
     return float(val), term_bar(terms, args)
 
 
+def aterms2(x: float, cnt, T, bpar):
+    """stb_hist_aterms2's value from the exact double x: the restaurant terms + sum over sizes s >= 2 of
+    cnt[s] (loggamma(s - x) - loggamma(1 - x)), at 40 digits (returned as a long double), and its bar.
+
+    The bar follows gcache_term's own operations (sweep_terms.hip), j = s - 1, u = 2^-53:
+      * par = 1.0 - x is formed once on the host with one rounding, |d par| <= u/2 (par <= 1), exact for x >= 1/2.  The
+        term's slope in par is psi(j + par) - psi(par) = sum_{i<j} 1/(par + i): d par moves the term by at most
+        (u/2) sum_i 1/(par + i) -- taken as zero for x >= 1/2, where par is exact, so no 1/par enters for small par.
+      * j <= 3: log(par (par+1) .. (par+j-1)) -- j-1 sums and j-1 products, each one relative rounding u, which move the
+        log by u each: 2 (j-1) u; the log itself to 2 ulp of its value (what the HIP math library states for double log
+        is 1 ulp): + 2 u |y|.
+      * j >= 4: lgamma((double)j + par) - lgpar.  Both lgammas (the device's, and the host's for lgpar) at the stated
+        L = 4 ulp of their values; the argument j + par is formed with one rounding, which moves lgamma by at most
+        u |z psi(z)| (_slope); the subtraction rounds once, u |y|.
+      * times the count -- exact as a double below 2^53 -- with one rounding of the product, u |c y|; the sums run in
+        double-double (dd_add: no first-order term); the final hi + lo and the addition of the restaurant terms round
+        once each: 2 u |total|; 16 u absolute.
+    The restaurant terms carry term_bar as everywhere."""
+    mp = _mp()
+    xm = mp.mpf(float(x))
+    par = 1.0 - float(x)
+    dpar = 0.0 if float(x) >= 0.5 else U / 2
+    lg1 = mp.loggamma(1 - xm)
+    val, b = mp.mpf(0), 0.0
+    for Ti, bi in zip(np.asarray(T, dtype=np.int64), np.asarray(bpar, dtype=np.float64)):
+        v, tb = restaurant_term(x, int(Ti), float(bi))
+        val += mp.mpf(v)
+        b += tb
+    cnt = np.asarray(cnt)
+    for s in np.nonzero(cnt[2:])[0] + 2:
+        c, j = int(cnt[s]), int(s) - 1
+        lgz = mp.loggamma(int(s) - xm)
+        y = lgz - lg1
+        ya = abs(float(y))
+        if j <= 3:
+            e = 2.0 * (j - 1) * U + 2.0 * U * ya
+        else:
+            e = U * (L_LGAMMA * (abs(float(lgz)) + abs(float(lg1))) + float(_slope(j + par)) + ya)
+        e += dpar * float(mp.digamma(j + par) - mp.digamma(par))
+        val += c * y
+        b += c * e + U * c * ya
+    hi = float(val)
+    return LD(hi) + LD(float(val - hi)), b + U * (2.0 * abs(hi) + 16.0)
+
+
 def term_bar(terms, args):
     """8 u times the magnitudes of the terms, + 2 u |z psi(z)| for each lgamma argument z (z = b/x and T + z are formed
     with one rounding each: the argument's error times lgamma's slope), + 16 u"""

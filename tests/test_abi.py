@@ -38,7 +38,7 @@ def test_every_declared_symbol_is_exported():
                  "yaps_message", "yaps_quit", "yaps_sysquit", "yaps_yapper", "S_approx", "S_approx_da",
                  "gsl_rng_gamma", "gsl_rng_beta", "gsl_rng_gaussian_ziggurat",
                  "stb_fill_S", "stb_fill_V", "stb_sweep_S", "stb_restaurant_terms", "stb_bterms",
-                 "stb_lookup_S", "stb_groups_create", "stb_groups_aterms"):
+                 "stb_lookup_S", "stb_groups_create", "stb_groups_aterms", "stb_groups_last_form"):
         assert must in want, f"{must} not declared in include/"
     missing = [n for n in sorted(want) if not hasattr(L, n)]
     assert not missing, f"declared but not exported: {missing}"

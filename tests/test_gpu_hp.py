@@ -9,6 +9,8 @@ import pytest
 
 import hp_oracle as hp
 import orc
+from hp_pairs import (FORMS, XS, Counters, _aterms, _check_sums, _create, _note, aterms_truth, check_form, expected_form,
+                      grid_geometry, hb_geometry, targeted_pairs, walk_geometry)
 from libstb_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -27,11 +29,6 @@ def truth(a, N, M, want_v=False):
     if key not in _truth:
         _truth[key] = hp.tables(list(key[0]), N, M, want_v)
     return _truth[key]
-
-
-def _note(form, a, ratio):
-    """print a worst error / bar (the MEASUREMENTS table is read from these lines)"""
-    print(f"{form} a={a!r}: worst error / bar {ratio:.3g}")
 
 
 def check_S(form, T, a, N, M):
@@ -255,184 +252,27 @@ def test_V_reference_recurrence_against_the_truth(N, exact):
 # ------------------------------------------------------------------------------------------------ aterms sums
 
 NP = 1500
-XS = np.concatenate([[0.01, 0.5, 0.999, 0.99999, 0.37, 0.98, 3 * 2.0 ** -30], synth.discount_grid(64)])[:64]
 
 
-def _period_rows(N):
-    """fill.hip stb_period_rows: the renormalisation period, which caps a block"""
-    bits = 1
-    while (1 << bits) < N:
-        bits += 1
-    return max(1, 1450 // (2 * bits + 1))
-
-
-_MHL = {1: 32, 2: 25, 3: 17, 4: 13}   # fill_hb.hip hb_mhl: halo lanes at most
-
-
-def hb_geometry(N, C):
-    """(R, UC, HC) of the halo-block forms (fill_hb.hip hb_geometry) with C columns a lane: blocks of R rows (the state
-    before block b is row 1 + b R), strip j's own columns from 2 + j UC, its halo the HC columns left of them"""
-    R = min(48, _period_rows(N), (_MHL[C] - 1) * C) // 8 * 8
-    if C == 3:
-        R = R // 24 * 24
-    HL = R // C
-    return R, (64 - HL) * C, HL * C
-
-
-def grid_geometry(N, C):
-    """(R, UC, HC) of the grid form (grid_hb.hip stb_grid_geometry) with C columns a lane"""
-    R = min(48, _period_rows(N)) // 8 * 8
-    HL = R // C
-    return R, (64 - HL) * C, HL * C
-
-
-def walk_geometry(N, M):
-    """every geometry the summing forms take at N x M: the halo-block form with 2, 3, 4 columns a lane (STB_HB_DOT_C, or
-    stb_hb_sum_C's choice) and the grid form with 2, 4, 8 (STB_GRID_C, or stb_grid_shape's choice); the mirrored
-    formulas are checked against what the library reports (stb_fill_tuning's blocks and strips, stb_grid_shape)"""
+@pytest.fixture(scope="module")
+def shared_rule_off():
+    """the automatic shared-GPU rule pinned off (a slow launch on a busy machine would send every later evaluation through
+    stored tables, silently), and restored"""
     L = capi.lib()
-    Cw, Rw = C.c_int(), C.c_int()
-    assert L.stb_fill_tuning(N, M, 1, C.byref(Cw), C.byref(Rw), None) == 6
-    assert (Rw.value, Cw.value) in {hb_geometry(N, c)[:2] for c in (1, 2, 4)}, (Rw.value, Cw.value)
-    geoms = {hb_geometry(N, c) for c in (2, 3, 4)} | {grid_geometry(N, c) for c in (2, 4, 8)}
-    groups = {8}                                        # HB_DOT_GR: the summing form's groups of staged rows
-    for D in (29, 64):
-        gc, gg, gk = C.c_int(), C.c_int(), C.c_int()
-        assert L.stb_grid_shape(N, M, D, C.byref(gc), C.byref(gg), C.byref(gk)) == 0
-        assert grid_geometry(N, gc.value) in geoms
-        groups |= {gg.value, gk.value}
-    return sorted(geoms), sorted(groups)
-
-
-def targeted_pairs(N, M, seed=7):
-    """(n, t) pairs on the cells where fused walks go wrong, for every geometry of walk_geometry: on every row, the columns
-    either side of every strip start 2 + j UC and of its halo edge 2 + j UC - HC; whole rows 1 + b R and 2 + b R either
-    side of every block boundary; 16 columns of the rows either side of every group / staged-row boundary inside a block;
-    column 1 and the first cell (3, 2); next to the diagonal; the last row (whole) and column; t = n; one cell carrying a
-    huge count"""
-    rng = np.random.default_rng(seed)
-    geoms, groups = walk_geometry(N, M)
-    cm = min(N - 1, M)
-    edges = set()
-    for R, UC, HC in geoms:
-        for c in range(2, cm + 1, UC):
-            edges |= {c - 1, c, c - HC - 1, c - HC}
-    edges = np.array(sorted(e for e in edges if 2 <= e <= cm))
-    block_rows, group_rows = set(), set()
-    for R, _, _ in geoms:
-        for b in range(0, N // R + 1):
-            block_rows |= {1 + b * R, 2 + b * R}
-            for g in groups:
-                for i in range(1, R // g + 1):
-                    group_rows |= {1 + b * R + i * g, 2 + b * R + i * g}
-    ns, ts = [], []
-
-    def add(n, t):
-        t = np.atleast_1d(t)
-        ns.append(np.full(t.shape[0], n))
-        ts.append(t)
-
-    for n in range(3, N + 1):
-        add(n, edges[edges <= min(n - 1, M)])             # strip and halo edges, every row
-    for n in sorted(r for r in block_rows if 3 <= r <= N):
-        add(n, np.arange(1, min(n - 1, M) + 1))           # block boundaries: whole rows
-    for n in sorted(r for r in group_rows - block_rows if 3 <= r <= N):
-        k = min(n - 1, M) - 1
-        add(n, rng.choice(np.arange(2, min(n - 1, M) + 1), size=min(16, k), replace=False))
-    add(2, 1)
-    for n in range(2, N + 1, 37):
-        add(n, 1)                                         # column 1
-    add(3, 2)
-    for n in range(3, N + 1, 11):
-        add(n, [n - 1, min(n, M)])                        # next to the diagonal; the diagonal (log 1) or the last column
-    add(N, np.arange(1, min(N, M) + 1))                   # the last row, whole
-    add(N // 2, np.full(3000, 7))                         # one cell carrying a huge count
-    n = np.concatenate(ns).astype(np.uint32)
-    t = np.concatenate(ts).astype(np.uint16)
-    I = 37
-    K = np.full(I, len(n) // I, dtype=np.int32)
-    K[-1] += len(n) - int(K.sum())
-    order = rng.permutation(len(n))
-    n, t = n[order].copy(), t[order].copy()
-    T = np.add.reduceat(t.astype(np.uint64), np.r_[0, np.cumsum(K)[:-1]]).astype(np.uint32)
-    bpar = np.linspace(0.3, 40.0, I)
-    return K, n, t, T, bpar
-
-
-_aterms_truth = {}
-
-
-def aterms_truth(K, n, t, T, bpar, x, N, M):
-    """per discount: (the true sum, its bar) -- sum of per-pair bars + restaurant-term bars + 4 u |sum|"""
-    key = (n.tobytes(), t.tobytes(), tuple(x), N, M)
-    if key in _aterms_truth:
-        return _aterms_truth[key]
-    x = np.asarray(x, dtype=np.float64)
-    D = len(x)
-    keep = n > 1
-    order = np.argsort(n[keep], kind="stable")
-    nn, tt = n[keep][order].astype(np.int64), t[keep][order].astype(np.int64)
-    starts = np.searchsorted(nn, np.arange(N + 2))
-    pair_sum = np.zeros(D, dtype=hp.LD)
-    pair_bar = np.zeros(D)
-    slope = hp.K1 + hp.K2 / (1.0 - x)
-    for r, v, e in hp.rows(x, N, M):
-        lo, hi = starts[r], starts[r + 1]
-        if lo == hi:
-            continue
-        y = hp.logs(v, e)[:, tt[lo:hi]]                   # (D, pairs of this row); t = n: log 1 = 0
-        k = hi - lo
-        pair_sum += y.sum(axis=1)
-        pair_bar += U * (slope * r * k + 4.0 * np.abs(y.astype(np.float64)).sum(axis=1) + 16.0 * k)
-    out = []
-    for d in range(D):
-        s, bsum = hp.LD(0), 0.0
-        for i in range(len(K)):
-            val, b = hp.restaurant_term(x[d], int(T[i]), float(bpar[i]))
-            s += hp.LD(val)
-            bsum += b
-        tot = s + pair_sum[d]
-        out.append((tot, float(pair_bar[d]) + bsum + 4 * U * abs(float(tot))))
-    _aterms_truth[key] = out
-    return out
-
-
-FORMS = [("fused", {}, (1, 3, 8, 16, 29, 64)),
-         ("hb2", {"STB_HB_DOT_C": "2"}, (1, 3)), ("hb3", {"STB_HB_DOT_C": "3"}, (8,)), ("hb4", {"STB_HB_DOT_C": "4"}, (16,)),
-         ("chain", {"STB_ATERMS_HB": "0"}, (3, 8)),
-         ("grid2", {"STB_ATERMS_GRID": "1", "STB_GRID_C": "2"}, (3,)), ("grid4", {"STB_ATERMS_GRID": "1", "STB_GRID_C": "4"}, (8, 29)),
-         ("grid4jobs", {"STB_ATERMS_GRID": "1", "STB_GRID_C": "4", "STB_GRID_HELP_NW": "1"}, (64,)),
-         ("grid8", {"STB_ATERMS_GRID": "1", "STB_GRID_C": "8"}, (16,)),
-         ("dense", {"STB_ATERMS_SPARSE": "0"}, (3,)),
-         ("tables", {"STB_ATERMS_FUSED": "0"}, (8, 64))]
-
-
-def _create(L, K, n, t, T, bpar, N, M, D):
-    h = L.stb_groups_create(len(K), orc.i32p(K), orc.u32p(T), orc.u32p(n), orc.u16p(t), orc.dp(bpar), N, M, D)
-    assert h, capi.last_error()
-    return h
-
-
-def _aterms(L, h, x, tables=False):
-    out = np.zeros(len(x))
-    f = L.stb_groups_aterms_tables if tables else L.stb_groups_aterms
-    capi.check(f(h, capi.dp(np.ascontiguousarray(x)), len(x), capi.dp(out)))
-    return out
-
-
-def _check_sums(form, got, want):
-    for d, (g, (tv, b)) in enumerate(zip(got, want)):
-        e = abs(float(hp.LD(g) - tv))
-        _note(f"aterms-{form}", d, e / b)
-        assert e <= b, (form, d, g, float(tv), e, b)
+    L.stb_set_shared_gpu(0)
+    try:
+        yield L
+    finally:
+        L.stb_set_shared_gpu(-1)
 
 
 @pytest.mark.parametrize("name,env,Ds", FORMS, ids=[f[0] for f in FORMS])
-def test_aterms_forms_against_the_truth(monkeypatch, name, env, Ds):
-    """each fused / grid / two-pass form, forced through its switch, on the targeted pairs"""
+def test_aterms_forms_against_the_truth(monkeypatch, shared_rule_off, name, env, Ds):
+    """each fused / grid / two-pass form, forced through its switch, on the targeted pairs; the form the library reports
+    (stb_groups_last_form) is the one the case names, its strips the mirrored geometry, and no evaluation fell back"""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    L = capi.lib()
+    L = shared_rule_off
     geoms, _ = walk_geometry(NP, NP)
     if "STB_GRID_C" in env:                              # the form's own strips are among those the pairs straddle
         gc = C.c_int()
@@ -440,13 +280,17 @@ def test_aterms_forms_against_the_truth(monkeypatch, name, env, Ds):
         assert grid_geometry(NP, gc.value) in geoms
     if "STB_HB_DOT_C" in env:
         assert hb_geometry(NP, int(env["STB_HB_DOT_C"])) in geoms
-    K, n, t, T, bpar = targeted_pairs(NP, NP)
-    want = aterms_truth(K, n, t, T, bpar, XS, NP, NP)
+    K, n, t, T, bpar, cls = targeted_pairs(NP, NP)
+    want = aterms_truth(K, n, t, T, bpar, XS, NP, NP, cls)
+    watch = Counters(L)
     h = _create(L, K, n, t, T, bpar, NP, NP, max(Ds))
     try:
         for D in Ds:
             _check_sums(name, _aterms(L, h, XS[:D]), want[:D])
+            check_form(L, h, f"{name}-D{D}", expected_form(name, env, NP), NP)
         _check_sums(name + "-tables", _aterms(L, h, XS[:max(Ds)], tables=True), want[:max(Ds)])
+        check_form(L, h, name + "-tables", expected_form("tables", {}, NP), NP)
+        watch.check(name)
     finally:
         L.stb_groups_free(h)
 
@@ -455,8 +299,8 @@ def test_aterms_on_pairs_made_new_and_log_zero():
     """a kept set given new pairs through stb_groups_pairs_begin / _put / _commit (the slab-built lists) against the truth
     of the new pairs; a pair outside the support (t > n) gives -inf"""
     L = capi.lib()
-    K, n, t, T, bpar = targeted_pairs(NP, NP)
-    K2, n2, t2, T2, bpar2 = targeted_pairs(NP, NP, seed=99)
+    K, n, t, T, bpar, _ = targeted_pairs(NP, NP)
+    K2, n2, t2, T2, bpar2, _ = targeted_pairs(NP, NP, seed=99)
     assert np.array_equal(K, K2)
     x = XS[:8]
     h = _create(L, K, n, t, T, bpar, NP, NP, len(x))
