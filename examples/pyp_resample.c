@@ -13,10 +13,13 @@
  *   5. with -G k as well: the same grid sharded over k group sets, set s on GPU s % (number of GPUs), driven by
  *      THIS one host thread (stb_set_device + stb_groups_aterms_async on every set, then stb_groups_wait on
  *      every set: INTEGRATION.md section 5, pattern (a)) -- the discount axis of SURVEY 8e without MPI.
+ *   6. with -d steps 2 and 3 run on the device from resident counts: stb_tindic_sweep -> stb_tindic_sampleb ->
+ *      stb_tindic_to_groups + stb_groups_samplea; no pair and no per-restaurant array crosses to the host inside the loop
+ *      (the indicator step then uses the exact prior ratio t/(n-t), see stb_hip.h, and counter-based uniforms).
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d]
  */
 #include <math.h>
 #include <stdio.h>
@@ -32,10 +35,10 @@
 #define DISHES 50
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:d")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -44,6 +47,7 @@ int main(int argc, char **argv) {
     else if (c == 'g') grid = atoi(optarg);
     else if (c == 'G') nsets = atoi(optarg);
     else if (c == 's') seed = atol(optarg);
+    else if (c == 'd') ondev = 1;
     else return 2;
   }
   srand48(seed);
@@ -95,10 +99,53 @@ int main(int argc, char **argv) {
   double a = 0.3, b = 5.0, asum = 0, bsum = 0;
   int kept = 0;
   unsigned maxt = maxn < 400 ? maxn : 400;
-  stable_t *S = S_make(maxn, maxt, maxn, maxn, a, S_STABLE | S_UVTABLE);
-  if (!S) yaps_quit("S_make failed: %s\n", stb_last_error());
+  stable_t *S = ondev ? NULL : S_make(maxn, maxt, maxn, maxn, a, S_STABLE | S_UVTABLE);
+  if (!S && !ondev) yaps_quit("S_make failed: %s\n", stb_last_error());
   double *bvec = malloc(sizeof(double) * J);
-  for (it = 0; it < cycles; it++) {
+  if (ondev) {
+    /* ---- 6. the same loop from device-resident counts: the pairs go to the device once, t and T come back once ---- */
+    size_t G = (size_t)J * DISHES, g = 0, cc;
+    scnt_int *nf = malloc(sizeof(*nf) * G), *cust = malloc(sizeof(*cust) * (size_t)J * ncust);
+    stcnt_int *tf = malloc(sizeof(*tf) * G);
+    double *hf = malloc(sizeof(double) * G);
+    for (j = 0; j < J; j++)
+      for (i = 0; i < DISHES; i++, g++) {
+        nf[g] = n[j][i];
+        tf[g] = t[j][i];
+        hf[g] = 1.0 / DISHES;
+      }
+    for (cc = 0; cc < (size_t)J * ncust; cc++) cust[cc] = (scnt_int)dish_of[cc]; /* (K = DISHES: the dish is the local pair) */
+    stb_tindic_t *ti = stb_tindic_create(J, K, nf, tf, hf, cust, maxn > 65535 ? 65535 : 0, 0);
+    stb_groups_t *gs = stb_groups_create(J, K, NULL, NULL, NULL, NULL, 0, 0, 3);
+    if (!ti || !gs) yaps_quit("device loop: %s\n", stb_last_error());
+    for (j = 0; j < J; j++) bvec[j] = b;
+    for (it = 0; it < cycles; it++) {
+      if (stb_tindic_sweep(ti, a, bvec, (uint64_t)seed, (uint64_t)it, 1)) yaps_quit("stb_tindic_sweep: %s\n", stb_last_error());
+      if (it % 3 == 2) {
+        b = stb_tindic_sampleb(ti, b, 1.1, 20.0, a, 0, 1, 0, (uint64_t)seed + 1, (uint64_t)it);
+        if (b != b) yaps_quit("stb_tindic_sampleb: %s\n", stb_last_error());
+        for (j = 0; j < J; j++) bvec[j] = b;
+        if (stb_tindic_to_groups(ti, gs, bvec)) yaps_quit("stb_tindic_to_groups: %s\n", stb_last_error());
+        a = stb_groups_samplea(gs, a, 0, 1, 0);
+        if (a != a) yaps_quit("stb_groups_samplea: %s\n", stb_last_error());
+        if (it >= cycles / 2) {
+          asum += a;
+          bsum += b;
+          kept++;
+        }
+      }
+    }
+    if (stb_tindic_get(ti, tf, T)) yaps_quit("stb_tindic_get: %s\n", stb_last_error());
+    for (j = 0, g = 0; j < J; j++)
+      for (i = 0; i < DISHES; i++, g++) t[j][i] = tf[g];
+    stb_groups_free(gs);
+    stb_tindic_free(ti);
+    free(nf);
+    free(tf);
+    free(hf);
+    free(cust);
+  }
+  for (it = 0; it < cycles && !ondev; it++) {
     for (j = 0; j < J; j++) {
       int cst;
       for (cst = 0; cst < ncust; cst++) {
@@ -188,6 +235,6 @@ int main(int argc, char **argv) {
     free(nf);
     free(tf);
   }
-  S_free(S);
+  if (S) S_free(S);
   return 0;
 }

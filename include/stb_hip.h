@@ -196,6 +196,36 @@ stb_bctx_t *stb_bterms_create(const uint32_t *T, int I);
 int stb_bterms_update(stb_bctx_t *c, const uint32_t *T, int I); /* new totals, I <= the I it was created with; else non-zero */
 int stb_bterms_eval(stb_bctx_t *c, const double *x_host, int J, double Q, double shape, double apar, double *out_host);
 void stb_bterms_free(stb_bctx_t *c);
+/* borrowed-T mode: a context over totals that already live on the device.  Evaluations read d_T in place (nothing is
+ * copied) and are queued on `stream` (a hipStream_t, or NULL) behind whatever it holds.  c = NULL makes a context; a
+ * context made here before is pointed at the new array and keeps its buffers when they fit.  NULL on failure (c is then
+ * freed).  stb_bterms_update refuses such a context; stb_bterms_free leaves d_T alone. */
+stb_bctx_t *stb_bterms_borrow(stb_bctx_t *c, const uint32_t *d_T, int I, void *stream);
+
+/* ---- the concentration step from device-resident counts (hyperq.hip; reference lib/sampleb.c:79-159) ----
+ * stb_sample_logq: for every restaurant with N_i > 0 customers an auxiliary q_i ~ Beta(b, N_i) is drawn on the device
+ * and L_i = -log q_i formed in the log domain (q itself is never formed, so it cannot underflow at b = B_MIN, where the
+ * reference exits with "Illegal q"); *Q_host = 1/scale + sum_i L_i, the Q of lib/sampleb.c:90-99.  d_N[I] customers
+ * per restaurant; d_L (NULL, or I doubles) receives L_i (0 where N_i = 0).  One launch and one wait.  b > 0, scale > 0.
+ * Uniforms: key = mix(seed + (sweep+1) gamma); restaurant i owns key_i = mix(key + (i+1) gamma); its k-th uniform is the
+ * top 53 bits m of mix(key_i + k gamma) as m / 2^53, with 2^-54 in place of m = 0 (the open interval).  The Gamma
+ * variates are Marsaglia-Tsang's with Box-Muller's cosine member, in the order hyperq.hip's header writes out
+ * (tests/hq_oracle.py replays it); the draws depend on (seed, sweep, i) alone and Q's bits do not depend on launch
+ * geometry (STB_HYPERQ_WAVES = 1, 2, 4 or 8 waves a workgroup).  The rejection loop is bounded (64 attempts a variate,
+ * acceptance above 0.95 each): running out fails the call with a message.
+ * stb_sampleb_device: sampleb with that Q and with bterms evaluated over d_T where it lives.  a = 0: the Gamma (or, above
+ * 400, Gaussian) draw of lib/sampleb.c:101-118 with the caller's rng, sum T from a device reduction.  Otherwise ARMS
+ * (libc rand()) or the slice sampler per STB_SAMPLER, with sampleb's bracket, B_MIN / B_MAX clamps and trace
+ * (stb_sampler_trace_*).  Work is queued on `stream`; the call waits for Q and for each evaluation.
+ * stb_tcounts_sampleb / stb_tindic_sampleb: the same on an object's counts, queued behind its sweeps on its stream;
+ * nothing is read back but Q and the evaluations, and t and T are not written.
+ * Failures -- a null object, a outside [0, 1), b_in <= -a or not finite (and b_in <= 0: no Beta draw exists), scale <= 0,
+ * a rejection loop that ran out -- return NaN with stb_last_error() set; unlike the drop-in sampleb they never exit. */
+int stb_sample_logq(double b, double scale, int I, const uint32_t *d_N, double *d_L, double *Q_host,
+                    uint64_t seed, uint64_t sweep, void *stream);
+double stb_sampleb_device(double b_in, int I, double shape, double scale, const uint32_t *d_N, const uint32_t *d_T,
+                          double a, void *rng, int loops, int verbose, uint64_t seed, uint64_t sweep, void *stream);
+double stb_sampleb_last_Q(void);          /* the Q of this thread's last device b step, for tests */
 
 /* ---- device-resident group set + grid evaluation (host-friendly wrappers over the above) ----
  * stb_groups_t owns device copies of the flat (n,t) pairs and the per-restaurant T, bpar, plus
@@ -235,6 +265,12 @@ int stb_groups_aterms_device(stb_groups_t *g, const double *x_host, int D, doubl
 /* the same values through stored tables and the sorted gather whatever D is (stb_groups_aterms sums
  * inside the fill when D >= 2, which needs a set-up pass over the pairs on first use) */
 int stb_groups_aterms_tables(stb_groups_t *g, const double *x_host, int D, double *out_host);
+/* samplea's draw on a set that already holds the pairs, T and bpar (stb_groups_create, stb_groups_pairs_*,
+ * stb_tcounts_to_groups, stb_tindic_to_groups): the bracket of lib/samplea.c:161-177 around a, the three abscissae ARMS
+ * asks for first in one batched evaluation, ARMS (libc rand()) or the slice sampler (the caller's rng) per STB_SAMPLER,
+ * and the trace; the drop-in samplea() runs this same code on its kept set.  The set needs Dmax >= 3.  Returns the new
+ * discount, or NaN with stb_last_error() set (a null set, a outside (0, 1), a failed evaluation): it never exits. */
+double stb_groups_samplea(stb_groups_t *g, double a, void *rng, int loops, int verbose);
 /* new per-restaurant totals T[I] and concentrations bpar[I] for the same pairs */
 int stb_groups_update_restaurants(stb_groups_t *g, const uint32_t *T, const double *bpar);
 /* NEW PAIRS for a set of the same shape (I restaurants, G = sum K pairs): what a caller whose counts change between
@@ -323,6 +359,9 @@ int stb_tcounts_sweep(stb_tcounts_t *s, double a, const double *bpar /* host [I]
                       uint64_t seed, uint64_t sweep, int nsweeps);
 int stb_tcounts_get(stb_tcounts_t *s, uint16_t *t_out, uint32_t *T_out);
 int stb_tcounts_to_groups(stb_tcounts_t *s, stb_groups_t *g, const double *bpar /* NULL: keep */);
+/* the concentration step on the object's counts (see stb_sampleb_device): N_i is built once at create */
+double stb_tcounts_sampleb(stb_tcounts_t *s, double b_in, double shape, double scale, double a, void *rng,
+                           int loops, int verbose, uint64_t seed, uint64_t sweep);
 void stb_tcounts_free(stb_tcounts_t *s);
 
 /* ---- windowed table counts: t drawn from a window around itself, O(W) a pair instead of O(min(n, M)) (reference
@@ -402,6 +441,8 @@ int stb_tindic_sweep(stb_tindic_t *s, double a, const double *bpar /* host [I] *
                      int nsweeps);
 int stb_tindic_get(stb_tindic_t *s, uint16_t *t_out, uint32_t *T_out);
 int stb_tindic_to_groups(stb_tindic_t *s, stb_groups_t *g, const double *bpar /* NULL: keep */);
+double stb_tindic_sampleb(stb_tindic_t *s, double b_in, double shape, double scale, double a, void *rng,
+                          int loops, int verbose, uint64_t seed, uint64_t sweep);
 void stb_tindic_free(stb_tindic_t *s);
 
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----

@@ -187,6 +187,13 @@ def lib() -> C.CDLL:
     sig("stb_hist_restaurants", i, [vp, c_u32_p, c_double_p])
     sig("stb_hist_counts_device", vp, [vp, C.POINTER(u), C.POINTER(vp)])
     sig("stb_hist_get", i, [vp, c_u32_p])
+    sig("stb_bterms_borrow", vp, [vp, vp, i, vp])
+    sig("stb_sample_logq", i, [d, d, i, vp, vp, c_double_p, u64, u64, vp])
+    sig("stb_sampleb_device", d, [d, i, d, d, vp, vp, d, vp, i, i, u64, u64, vp])
+    sig("stb_tcounts_sampleb", d, [vp, d, d, d, d, vp, i, i, u64, u64])
+    sig("stb_tindic_sampleb", d, [vp, d, d, d, d, vp, i, i, u64, u64])
+    sig("stb_sampleb_last_Q", d, [])
+    sig("stb_groups_samplea", d, [vp, d, vp, i, i])
     # optional entry points (present once the sampler host code is linked in)
     for name, res, args in (
         ("arms_simple", i, [i, c_double_p, c_double_p, LOGDENS, vp, i, c_double_p, c_double_p]),
@@ -503,6 +510,15 @@ class TableCounts:
         bp = None if bpar is None else dp(np.ascontiguousarray(bpar, dtype=np.float64))
         check(self.L.stb_tcounts_to_groups(self.h, groups, bp))
 
+    def sampleb(self, b, shape, scale, a, seed: int, sweep: int, loops: int = 1, verbose: int = 0):
+        """one concentration step on the current counts, behind the queued sweeps (stb_tcounts_sampleb): Q is drawn on the
+        device from (seed, sweep), b by ARMS / the slice sampler (a > 0) or the Gamma draw (a = 0).  NaN -> StbError"""
+        r = float(self.L.stb_tcounts_sampleb(self.h, float(b), float(shape), float(scale), float(a), None, loops, verbose,
+                                            seed, sweep))
+        if r != r:
+            raise StbError(last_error())
+        return r
+
     def partition(self, a, hist, bpar, seed: int, sweep: int):
         """stage 1 of the S-free discount step on the current pairs, queued: the table-size histogram into `hist` (a
         Histogram with I restaurants and S > the largest n), with T and bpar (stb_tcounts_partition)"""
@@ -530,6 +546,47 @@ def sample_tcounts_window(tabs, a, bpar, koff, n, t, T, h, window: int, seed: in
                                           bpar.data_ptr(), int(koff.shape[0]) - 1, koff.data_ptr(), n.data_ptr(),
                                           t.data_ptr(), T.data_ptr(), None if h is None else h.data_ptr(), int(window),
                                           TC_REF_WINDOW if ref else 0, seed, sweep, stream_ptr(stream)))
+
+
+def sample_logq(b, scale, N, seed: int, sweep: int, want_L: bool = True, stream=None):
+    """stb_sample_logq on a device tensor N (int32 holding uint32 counts): (Q, L) with L a float64 device tensor of
+    -log q_i (None when want_L is false)"""
+    torch = _torch()
+    I = int(N.shape[0])
+    Lt = torch.empty(I, dtype=torch.float64, device=N.device) if want_L else None
+    Q = C.c_double(0.0)
+    check(lib().stb_sample_logq(float(b), float(scale), I, N.data_ptr() if I else None, Lt.data_ptr() if want_L and I else None,
+                                C.byref(Q), seed, sweep, stream_ptr(stream)))
+    return Q.value, Lt
+
+
+def sampleb_device(b, shape, scale, N, T, a, seed: int, sweep: int, loops: int = 1, verbose: int = 0, stream=None):
+    """stb_sampleb_device on device tensors N, T (int32 holding uint32 counts).  NaN -> StbError"""
+    r = float(lib().stb_sampleb_device(float(b), int(N.shape[0]), float(shape), float(scale), N.data_ptr(), T.data_ptr(),
+                                       float(a), None, loops, verbose, seed, sweep, stream_ptr(stream)))
+    if r != r:
+        raise StbError(last_error())
+    return r
+
+
+def groups_samplea(groups, a, loops: int = 1, verbose: int = 0):
+    """stb_groups_samplea on a group-set handle (stb_groups_create): the new discount.  NaN -> StbError"""
+    r = float(lib().stb_groups_samplea(groups, float(a), None, loops, verbose))
+    if r != r:
+        raise StbError(last_error())
+    return r
+
+
+def sampler_trace():
+    """the (x, y) evaluations of this process's most recent sampler call, and ARMS' return code"""
+    L = lib()
+    xs, ys = [], []
+    x, y = C.c_double(), C.c_double()
+    for k in range(L.stb_sampler_trace_count()):
+        L.stb_sampler_trace_get(k, C.byref(x), C.byref(y))
+        xs.append(x.value)
+        ys.append(y.value)
+    return np.array(xs), np.array(ys), int(L.stb_sampler_trace_code())
 
 
 PT_REF_WALK = 1  # stb_sample_partition flag: lib/samplea.c's walk, as the drop-in samplea2 (DESIGN.md section 6)
@@ -658,6 +715,15 @@ class TableIndicators:
         """pairs and T to a group set (an stb_groups_create handle) of the same shape, device to device"""
         bp = None if bpar is None else dp(np.ascontiguousarray(bpar, dtype=np.float64))
         check(self.L.stb_tindic_to_groups(self.h, groups, bp))
+
+    def sampleb(self, b, shape, scale, a, seed: int, sweep: int, loops: int = 1, verbose: int = 0):
+        """one concentration step on the current counts, behind the queued sweeps (stb_tindic_sampleb): Q is drawn on the
+        device from (seed, sweep), b by ARMS / the slice sampler (a > 0) or the Gamma draw (a = 0).  NaN -> StbError"""
+        r = float(self.L.stb_tindic_sampleb(self.h, float(b), float(shape), float(scale), float(a), None, loops, verbose,
+                                            seed, sweep))
+        if r != r:
+            raise StbError(last_error())
+        return r
 
     def free(self):
         if self.h:

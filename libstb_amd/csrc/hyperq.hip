@@ -1,0 +1,295 @@
+// hyperq.hip -- the auxiliary variables of the concentration step on the device (reference lib/sampleb.c:90-99): for
+// every restaurant i with N_i > 0 customers, q_i ~ Beta(b, N_i), L_i = -log q_i, and Q = 1/scale + sum_i L_i.
+//
+//   k_logq      one lane per restaurant, grid-strided over blocks of 256 restaurants; the block sums and Q
+//   k_sum_u32   sum of T over the restaurants (the a = 0 branch's Gamma shape)
+//   k_segsum    customers per restaurant from the pairs (stb_tcounts' N, built once)
+//
+// Uniforms (counter-based, the convention of tcounts.hip): key = mix(seed + (sweep+1) gamma); restaurant i owns the
+// substream key_i = mix(key + (i+1) gamma); its k-th uniform, k = 1, 2, ..., is m 2^-53 with m the top 53 bits of
+// mix(key_i + k gamma), and 2^-54 in place of m = 0: always inside the open interval (0, 1), so every log is finite.
+// They are consumed in the order written below; the draws depend on (seed, sweep, i) alone.
+//
+// log of a Gamma(alpha) variate, alpha >= 1 (Marsaglia & Tsang 2000): d = alpha - 1/3, c = 1 / sqrt(9 d); an attempt
+// takes u1, u2, the normal x = sqrt(-2 log u1) cos(2 pi u2) (Box-Muller's cosine member; the sine member is not used),
+// w = 1 + c x; w <= 0 ends the attempt; else v = w w w, a third uniform u, and the attempt is accepted when
+//     log u < ((x x / 2 + d) - d v) + d log v          (evaluated as written, no contraction)
+// with log G = log d + log v.  For alpha < 1 the boost in the log domain: log G = log G' + log(u') / alpha with
+// G' ~ Gamma(alpha + 1) as above and one more uniform u' after it.  At most HQ_CAP attempts a variate (acceptance is
+// above 0.95 an attempt): a lane that runs out sets the error word, writes NaN and goes on; the call then fails.
+// A restaurant draws log G_b (shape b) first, then log G_N (shape N_i); with D = log G_N - log G_b
+//     L_i = log1p(exp D)  (D <= 0),   D + log1p(exp(-D))  (D > 0)
+// which is -log(G_b / (G_b + G_N)) without ever forming q: q underflows for small b where L_i stays an ordinary number.
+//
+// Q does not depend on launch geometry: the L of restaurants 256 c .. 256 c + 255 (0 beyond I) are summed in one fixed
+// tree (four quarters per lane, then the shuffle tree of a 64-lane wave), and the last workgroup to finish -- a ticket --
+// adds the block sums in a fixed order as well (lane l the blocks l, l + 64, ... in double-double, then the same tree)
+// to 1/scale.  Q and the error word go to pinned host memory from the kernel: one launch, one wait, no copy.
+// STB_HYPERQ_WAVES = 1, 2, 4 or 8 waves a workgroup (default 4); the bits are the same for each.
+//
+// What sets the pace: FP64 transcendentals.  A restaurant costs two variates, each attempt five of them (log u1, cos,
+// sqrt, log v, log u) plus log d, and exp / log1p at the end -- about 14 calls of 40 to 100 FP64 instructions, against
+// 4 bytes read and 8 written.  Lanes diverge only in the attempt loop (a wave repeats while any lane rejects: with
+// acceptance above 0.95, 64 lanes need two rounds more often than not and almost never four) and between b < 1 and
+// b >= 1, which is uniform over the launch.
+
+#include "stb_common.h"
+#include "tcounts.h"
+#include "hyperq.h"
+
+#define HQ_CHUNK 256
+#define HQ_CAP 64
+#define HQ_MAXTHREADS 512
+
+__device__ __forceinline__ double hq_unit(uint64_t key, uint64_t k) {
+  const uint64_t m = stb_mix64(key + k * STB_GAMMA) >> 11;
+  return m ? (double)m * (1.0 / 9007199254740992.0) : (1.0 / 18014398509481984.0);
+}
+
+// log of a Gamma(alpha) variate, alpha >= 1; k counts the uniforms taken from the substream
+__device__ __forceinline__ double hq_log_gamma_ge1(double alpha, uint64_t key, uint64_t &k, bool &bad) {
+#pragma clang fp contract(off)
+  const double d = alpha - 1.0 / 3.0;
+  const double c = 1.0 / sqrt(9.0 * d);
+  for (int it = 0; it < HQ_CAP; it++) {
+    const double u1 = hq_unit(key, ++k);
+    const double u2 = hq_unit(key, ++k);
+    const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+    const double w = 1.0 + c * x;
+    if (!(w > 0.0)) continue;
+    const double v = w * w * w;
+    const double u = hq_unit(key, ++k);
+    const double lv = log(v);
+    if (log(u) < ((0.5 * (x * x) + d) - d * v) + d * lv) return log(d) + lv;
+  }
+  bad = true;
+  return NAN;
+}
+
+__device__ __forceinline__ double hq_log_gamma(double alpha, uint64_t key, uint64_t &k, bool &bad) {
+#pragma clang fp contract(off)
+  if (alpha >= 1.0) return hq_log_gamma_ge1(alpha, key, k, bad);
+  const double lg = hq_log_gamma_ge1(alpha + 1.0, key, k, bad);
+  const double u = hq_unit(key, ++k);
+  return lg + log(u) / alpha;
+}
+
+__device__ __forceinline__ double hq_draw_L(double b, double Ni, uint64_t key, uint64_t i, bool &bad) {
+#pragma clang fp contract(off)
+  const uint64_t ki = stb_mix64(key + (i + 1) * STB_GAMMA);
+  uint64_t k = 0;
+  const double lgb = hq_log_gamma(b, ki, k, bad);
+  const double lgn = hq_log_gamma(Ni, ki, k, bad);
+  const double D = lgn - lgb;
+  return D > 0.0 ? D + log1p(exp(-D)) : log1p(exp(D));
+}
+
+// ctl[0] ticket, ctl[1] error word (both zeroed on the stream ahead of the launch); host_out[0] = Q, host_out[1] = error
+__global__ __launch_bounds__(HQ_MAXTHREADS) void k_logq(double b, double inv_scale, uint64_t I, const uint32_t *Nv,
+                                                        const uint64_t *coff, double *Lout, uint64_t key, double *partial,
+                                                        unsigned nchunks, unsigned *ctl, double *host_out) {
+  __shared__ double sL[HQ_MAXTHREADS];
+  __shared__ unsigned s_last;
+  const unsigned nthr = blockDim.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned span = nthr > HQ_CHUNK ? nthr : HQ_CHUNK;  // restaurants a workgroup takes per step
+  const unsigned cps = span / HQ_CHUNK;                     // ... which are this many blocks of 256
+  const unsigned nsteps = (nchunks + cps - 1) / cps;
+  bool bad = false;
+  for (unsigned s = blockIdx.x; s < nsteps; s += gridDim.x) {
+    const uint64_t base = (uint64_t)s * span;
+    for (unsigned o = threadIdx.x; o < span; o += nthr) {
+      const uint64_t i = base + o;
+      double L = 0.0;
+      if (i < I) {
+        const uint64_t Ni = Nv ? (uint64_t)Nv[i] : coff[i + 1] - coff[i];
+        if (Ni > 0) L = hq_draw_L(b, (double)Ni, key, i, bad);
+        if (Lout) Lout[i] = L;
+      }
+      sL[o] = L;
+    }
+    __syncthreads();
+    if (wave < cps) {  // (cps <= the number of waves: 1 up to four waves, 2 with eight)
+      const double *p = sL + wave * HQ_CHUNK;
+      double v = (p[lane] + p[lane + 64]) + (p[lane + 128] + p[lane + 192]);
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+      const unsigned c = s * cps + wave;
+      if (lane == 0 && c < nchunks) partial[c] = v;
+    }
+    __syncthreads();
+  }
+  if (bad) __hip_atomic_fetch_or(&ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // the block sums are published by an agent-scope release ahead of the ticket; the last workgroup acquires and sums
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = __hip_atomic_fetch_add(&ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
+    if (s_last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!s_last || wave != 0) return;
+  dd_t acc{0.0, 0.0};
+  for (unsigned c = lane; c < nchunks; c += 64) dd_add(acc, partial[c]);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    dd_t o;
+    o.hi = __shfl_down(acc.hi, off, 64);
+    o.lo = __shfl_down(acc.lo, off, 64);
+    dd_merge(acc, o);
+  }
+  if (lane == 0) {
+    dd_add(acc, inv_scale);
+    host_out[0] = acc.hi + acc.lo;
+    host_out[1] = (double)__hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_sum_u32(const uint32_t *T, uint64_t I, unsigned long long *host_out) {
+  __shared__ unsigned long long sw[4];
+  unsigned long long v = 0;  // (integers: exact in any order)
+  for (uint64_t i = threadIdx.x; i < I; i += 256) v += T[i];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) *host_out = sw[0] + sw[1] + sw[2] + sw[3];
+}
+
+__global__ __launch_bounds__(256) void k_segsum(const uint64_t *koff, const uint32_t *n, int I, uint32_t *Nout) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= I) return;
+  uint32_t v = 0;
+  for (uint64_t g = koff[i]; g < koff[i + 1]; g++) v += n[g];
+  Nout[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// per calling thread: the block sums, the ticket and error words, and the pinned words the kernels answer in.  A call
+// waits for its answer before it returns, so one set per thread is never in use twice.
+
+struct hq_ctx {
+  int dev = -1;
+  double *d_partial = nullptr;
+  size_t cap = 0;  // block sums d_partial holds
+  unsigned *d_ctl = nullptr;
+  double *h_out = nullptr, *h_out_dev = nullptr;  // [0] Q, [1] error word, [2] (as uint64) sum of T
+};
+static thread_local hq_ctx hq;
+
+static void hq_drop() {
+  if (hq.dev < 0) return;
+  const int prev = stb_device_enter(hq.dev);
+  if (hq.d_partial) stb_pool_free(hq.d_partial);
+  if (hq.d_ctl) stb_pool_free(hq.d_ctl);
+  if (hq.h_out) stb_pool_free(hq.h_out);
+  stb_device_leave(prev);
+  hq = hq_ctx();
+}
+
+extern "C" void stb_hq_release(void) {
+  STB_ENTRY;
+  hq_drop();
+}
+
+// the calling thread's set on the current device, with room for nchunks block sums
+static int hq_ready(size_t nchunks) {
+  int dev = -1;
+  HIPCHK(hipGetDevice(&dev));
+  if (hq.dev >= 0 && hq.dev != dev) hq_drop();
+  if (hq.dev < 0) {
+    hq.dev = dev;
+    if (stb_pool_malloc((void **)&hq.d_ctl, 256) != hipSuccess || stb_pool_malloc((void **)&hq.h_out, 256, 1) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&hq.h_out_dev, hq.h_out, 0) != hipSuccess) {
+      hq_drop();
+      return stb_fail("stb_sample_logq: out of memory for the result words");
+    }
+  }
+  if (nchunks > hq.cap) {
+    if (hq.d_partial) stb_pool_free(hq.d_partial);
+    hq.d_partial = nullptr;
+    hq.cap = 0;
+    const size_t want = nchunks < 4096 ? 4096 : nchunks;
+    if (stb_pool_malloc((void **)&hq.d_partial, sizeof(double) * want) != hipSuccess)
+      return stb_fail("stb_sample_logq: out of device memory for %zu block sums", want);
+    hq.cap = want;
+  }
+  return 0;
+}
+
+static int hq_waves(void) {
+  const int v = stb_env_int("STB_HYPERQ_WAVES", 4);
+  return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
+}
+
+extern "C" int stb_hq_logq(double b, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff, double *d_L,
+                           double *Q_host, uint64_t seed, uint64_t sweep, void *stream) {
+  STB_ENTRY;
+  if (!(b > 0.0) || !std::isfinite(b)) return stb_fail("stb_sample_logq: b=%g (a Beta(b, N) draw needs b > 0, finite)", b);
+  if (!(scale > 0.0) || !std::isfinite(scale)) return stb_fail("stb_sample_logq: scale=%g (must be > 0, finite)", scale);
+  if (I < 0) return stb_fail("stb_sample_logq: I=%d", I);
+  if (!Q_host) return stb_fail("stb_sample_logq: Q_host is required");
+  if (I > 0 && !d_N == !d_coff) return stb_fail("stb_sample_logq: the customers per restaurant are required");
+  if (I == 0) {
+    *Q_host = 1.0 / scale;
+    return 0;
+  }
+  if (stb_device_count() < 1) return stb_fail("stb_sample_logq: no HIP device (libstb_amd has no CPU path)");
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nchunks = (unsigned)(((uint64_t)I + HQ_CHUNK - 1) / HQ_CHUNK);
+  if (hq_ready(nchunks)) return 1;
+  const int nthr = 64 * hq_waves();
+  const unsigned cps = nthr > HQ_CHUNK ? nthr / HQ_CHUNK : 1;
+  const unsigned nsteps = (nchunks + cps - 1) / cps;
+  unsigned grid = 4u * (unsigned)stb_cu_count();
+  if (grid < 1) grid = 1;
+  if (grid > nsteps) grid = nsteps;
+  const uint64_t key = stb_mix64(seed + (sweep + 1) * STB_GAMMA);
+  HIPCHK(hipMemsetAsync(hq.d_ctl, 0, 2 * sizeof(unsigned), st));
+  STB_LAUNCH(k_logq, dim3(grid), dim3(nthr), st, b, 1.0 / scale, (uint64_t)I, d_N, d_coff, d_L, key, hq.d_partial, nchunks,
+             hq.d_ctl, hq.h_out_dev);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  const double Q = ((volatile double *)hq.h_out)[0], err = ((volatile double *)hq.h_out)[1];
+  if (err != 0.0)
+    return stb_fail("stb_sample_logq: a Gamma draw was not accepted within %d attempts (b=%g, seed=%llu, sweep=%llu)", HQ_CAP, b,
+                    (unsigned long long)seed, (unsigned long long)sweep);
+  *Q_host = Q;
+  return 0;
+}
+
+extern "C" int stb_sample_logq(double b, double scale, int I, const uint32_t *d_N, double *d_L, double *Q_host, uint64_t seed,
+                               uint64_t sweep, void *stream) {
+  if (I > 0 && !d_N) return stb_fail("stb_sample_logq: d_N is required");
+  return stb_hq_logq(b, scale, I, d_N, nullptr, d_L, Q_host, seed, sweep, stream);
+}
+
+extern "C" int stb_hq_sum_u32(const uint32_t *d_T, int I, uint64_t *sum_host, void *stream) {
+  STB_ENTRY;
+  if (I < 0 || !sum_host || (I > 0 && !d_T)) return stb_fail("stb_sampleb_device: I=%d and T are required", I);
+  if (I == 0) {
+    *sum_host = 0;
+    return 0;
+  }
+  if (hq_ready(0)) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long *out_dev = (unsigned long long *)(hq.h_out_dev + 2);
+  STB_LAUNCH(k_sum_u32, dim3(1), dim3(256), st, d_T, (uint64_t)I, out_dev);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  *sum_host = *(volatile unsigned long long *)(hq.h_out + 2);
+  return 0;
+}
+
+extern "C" int stb_hq_segsum(const uint64_t *d_koff, const uint32_t *d_n, int I, uint32_t *d_N, void *stream) {
+  if (I <= 0) return 0;
+  STB_LAUNCH(k_segsum, dim3((unsigned)((I + 255) / 256)), dim3(256), (hipStream_t)stream, d_koff, d_n, I, d_N);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int stb_fail_msg(const char *msg) { return stb_fail("%s", msg); }

@@ -19,6 +19,7 @@
 #include "../../include/psample.h"
 #include "../../include/stb_hip.h"
 #include "sampler_trace.h"
+#include "hyperq.h"
 
 #define NPRE 3 /* abscissae ARMS is known to ask for first (lib/arms.c:117-119) */
 
@@ -31,6 +32,8 @@ typedef struct {
   /* values evaluated ahead of time, served when ARMS asks for exactly these abscissae */
   int npre;
   double xpre[NPRE], ypre[NPRE];
+  /* stb_groups_samplea never exits: a failed evaluation is remembered and the call returns NaN */
+  int noexit, failed;
 } a_posterior;
 
 static double aterms(double x, void *vp) {
@@ -47,7 +50,12 @@ static double aterms(double x, void *vp) {
       stb_trace_add(x, ap->ypre[i]);
       return ap->ypre[i];
     }
+  if (ap->failed) return 0.0;
   if (stb_groups_aterms(ap->dev, &x, 1, &val)) {
+    if (ap->noexit) {
+      ap->failed = 1;
+      return 0.0;
+    }
     fprintf(stderr, "aterms(): device evaluation failed: %s\n", stb_last_error());
     exit(1);
   }
@@ -188,10 +196,115 @@ static int use_slice(void) {
 #endif
 }
 
+/* lib/samplea.c:161-177: start point nudged off the ends, move limited to +-SQUEEZEA */
+static void a_bracket(double mya, double inita[3]) {
+  inita[0] = A_MIN;
+  inita[1] = mya;
+  inita[2] = A_MAX;
+  if (fabs(inita[1] - A_MAX) / A_MAX < 0.00001) inita[1] = A_MAX * 0.999 + A_MIN * 0.001;
+  if (fabs(inita[1] - A_MIN) / A_MIN < 0.00001) inita[1] = A_MIN * 0.999 + A_MAX * 0.001;
+#ifdef SQUEEZEA
+  if (inita[1] - SQUEEZEA > A_MIN) inita[0] = inita[1] - SQUEEZEA;
+  if (inita[1] + SQUEEZEA < A_MAX) inita[2] = inita[1] + SQUEEZEA;
+#endif
+}
+/* ARMS starts from three abscissae it fixes before any evaluation (lib/arms.c:117-119, the same expression here, so
+ * the same bits): they are evaluated in ONE batched device call */
+static void a_first_abscissae(const double inita[3], double xspec[NPRE]) {
+  int i;
+  for (i = 0; i < NPRE; i++) xspec[i] = inita[0] + (i + 1.0) * (inita[2] - inita[0]) / (NPRE + 1.0);
+}
+
+/* The draw on a set that holds the pairs, T and bpar (lib/samplea.c:186-240 after the scan of the counts): the bracket, the
+ * three abscissae ARMS asks for first in one batched evaluation (y3_ready: the caller has them already, queued ahead of
+ * time), ARMS or the slice sampler, the trace.  ap carries the set, verbose, maxt and noexit. */
+static double a_draw(double mya, a_posterior *ap, const double *y3_ready, rngp_t rng, int loops) {
+  double inita[3], xspec[NPRE];
+  const int slice = use_slice();
+  int i;
+  a_bracket(mya, inita);
+  a_first_abscissae(inita, xspec);
+  ap->npre = 0;
+  ap->failed = 0;
+  if (!slice) {
+    double y3[NPRE];
+    if (y3_ready) {
+      for (i = 0; i < NPRE; i++) y3[i] = y3_ready[i];
+    } else if (stb_groups_aterms(ap->dev, xspec, NPRE, y3)) {
+      if (ap->noexit) return NAN;
+      fprintf(stderr, "aterms(): device evaluation failed: %s\n", stb_last_error());
+      exit(1);
+    }
+    for (i = 0; i < NPRE; i++) {
+      ap->xpre[i] = xspec[i];
+      ap->ypre[i] = y3[i];
+    }
+    ap->npre = NPRE;
+  }
+
+  stb_trace_reset();
+  if (!slice) {
+    int code = arms_simple(3, inita, inita + 2, aterms, ap, 0, inita + 1, &mya); /* :210 */
+    stb_trace_code(code);
+    if (ap->failed) return NAN;
+    if (mya < inita[0] || mya > inita[2]) {
+      if (ap->noexit) {
+        stb_fail_msg("stb_groups_samplea: arms_simple returned a value out of bounds");
+        return NAN;
+      }
+      fprintf(stderr, "Arms_simple(apar) returned value out of bounds\n");
+      exit(1);
+    }
+  } else {
+    inita[1] = A_MAX; /* lib/samplea.c:217: the slice bracket is [lower, A_MAX] */
+    if (SliceSimple(&mya, aterms, inita, rng, loops, ap)) {
+      if (ap->noexit) {
+        if (!ap->failed) stb_fail_msg("stb_groups_samplea: SliceSimple error");
+        return NAN;
+      }
+      fprintf(stderr, "SliceSimple error\n");
+      exit(1);
+    }
+    if (ap->failed) return NAN;
+  }
+  return mya;
+}
+
+/* include/stb_hip.h: samplea's draw for a caller whose pairs are on the device already (stb_tcounts_to_groups,
+ * stb_tindic_to_groups, or a set made from host pairs).  Never exits: NaN with stb_last_error() set. */
+double stb_groups_samplea(stb_groups_t *g, double a, void *rng, int loops, int verbose) {
+  a_posterior ap;
+  unsigned N = 0, M = 0;
+  int Dmax = 0;
+  char msg[160];
+  if (!g || stb_groups_shape(g, NULL, NULL, &N, &M, &Dmax)) {
+    stb_fail_msg("stb_groups_samplea: null group set");
+    return NAN;
+  }
+  if (!(a > 0.0 && a < 1.0)) { /* (aterms has log(x) and b/x: the discount must be positive, as in samplea) */
+    snprintf(msg, sizeof(msg), "stb_groups_samplea: discount a=%g outside (0, 1)", a);
+    stb_fail_msg(msg);
+    return NAN;
+  }
+  if (N < 1 || M < 1 || Dmax < NPRE) {
+    snprintf(msg, sizeof(msg), "stb_groups_samplea: the set has bounds N=%u M=%u and Dmax=%d (needs pairs, bounds and Dmax >= %d)",
+             N, M, Dmax, NPRE);
+    stb_fail_msg(msg);
+    return NAN;
+  }
+  memset(&ap, 0, sizeof(ap));
+  ap.dev = g;
+  ap.verbose = verbose;
+  ap.maxn = (int)N;
+  ap.maxt = (int)M;
+  ap.noexit = 1;
+  return a_draw(a, &ap, NULL, rng, loops);
+}
+
 double samplea(double mya, int I, int *K, scnt_int *T, scnt_int **n, stcnt_int **t,
                void (*getval)(scnt_int *n, stcnt_int *t, unsigned i, unsigned k), double *bpar,
                rngp_t rng, int loops, int verbose) {
-  double inita[3] = {A_MIN, 1, A_MAX};
+  double inita[3];
   a_posterior ap;
   scnt_int *nflat = NULL;
   stcnt_int *tflat = NULL;
@@ -202,17 +315,9 @@ double samplea(double mya, int I, int *K, scnt_int *T, scnt_int **n, stcnt_int *
   int i, k, cache, spec = 0, hit = 0;
   const int slice = use_slice();
 
-  /* lib/samplea.c:161-177: start point nudged off the ends, move limited to +-SQUEEZEA */
-  inita[1] = mya;
-  if (fabs(inita[1] - A_MAX) / A_MAX < 0.00001) inita[1] = A_MAX * 0.999 + A_MIN * 0.001;
-  if (fabs(inita[1] - A_MIN) / A_MIN < 0.00001) inita[1] = A_MIN * 0.999 + A_MAX * 0.001;
-#ifdef SQUEEZEA
-  if (inita[1] - SQUEEZEA > A_MIN) inita[0] = inita[1] - SQUEEZEA;
-  if (inita[1] + SQUEEZEA < A_MAX) inita[2] = inita[1] + SQUEEZEA;
-#endif
-  /* ARMS starts from three abscissae it fixes before any evaluation (lib/arms.c:117-119, the same expression here, so
-   * the same bits): they are evaluated in ONE batched device call */
-  for (i = 0; i < NPRE; i++) xspec[i] = inita[0] + (i + 1.0) * (inita[2] - inita[0]) / (NPRE + 1.0);
+  memset(&ap, 0, sizeof(ap));
+  a_bracket(mya, inita);
+  a_first_abscissae(inita, xspec);
 
   for (i = 0; i < I; i++) G += (size_t)(K[i] > 0 ? K[i] : 0);
   ap.verbose = verbose;
@@ -320,42 +425,11 @@ double samplea(double mya, int I, int *K, scnt_int *T, scnt_int **n, stcnt_int *
   }
   ap.keep = 1;
   ap.reused = hit;
-  ap.npre = 0;
-  if (!slice) {
-    double y3[NPRE];
-    int bad;
-    if (spec) {
-      bad = stb_groups_wait(ap.dev);
-      for (i = 0; i < NPRE; i++) y3[i] = yspec[i];
-    } else {
-      bad = stb_groups_aterms(ap.dev, xspec, NPRE, y3);
-    }
-    if (bad) {
-      fprintf(stderr, "aterms(): device evaluation failed: %s\n", stb_last_error());
-      exit(1);
-    }
-    for (i = 0; i < NPRE; i++) {
-      ap.xpre[i] = xspec[i];
-      ap.ypre[i] = y3[i];
-    }
-    ap.npre = NPRE;
+  if (spec && stb_groups_wait(ap.dev)) { /* (the three starting values were queued ahead of the fingerprint) */
+    fprintf(stderr, "aterms(): device evaluation failed: %s\n", stb_last_error());
+    exit(1);
   }
-
-  stb_trace_reset();
-  if (!slice) {
-    int code = arms_simple(3, inita, inita + 2, aterms, &ap, 0, inita + 1, &mya); /* :210 */
-    stb_trace_code(code);
-    if (mya < inita[0] || mya > inita[2]) {
-      fprintf(stderr, "Arms_simple(apar) returned value out of bounds\n");
-      exit(1);
-    }
-  } else {
-    inita[1] = A_MAX; /* lib/samplea.c:217: the slice bracket is [lower, A_MAX] */
-    if (SliceSimple(&mya, aterms, inita, rng, loops, &ap)) {
-      fprintf(stderr, "SliceSimple error\n");
-      exit(1);
-    }
-  }
+  mya = a_draw(mya, &ap, spec ? yspec : NULL, rng, loops);
   /* (the set stays with the thread, as a container; stb_sampler_cache_clear releases it) */
   return mya;
 }

@@ -399,14 +399,17 @@ struct stb_bctx {
   void *d_ws;
   size_t ws_bytes;
   hipStream_t st;
+  bool borrowed;  // d_T and st are the caller's (stb_bterms_borrow): read where they live, never copied, never freed here
 };
 
 extern "C" void stb_bterms_free(stb_bctx_t *c) {
   STB_ENTRY;
   if (!c) return;
   const int prev = stb_device_enter(c->dev);
-  (void)hipStreamSynchronize(c->st);
-  stb_pool_free(c->d_T);
+  if (!c->borrowed) {
+    (void)hipStreamSynchronize(c->st);
+    stb_pool_free(c->d_T);
+  }
   stb_pool_free(c->d_out);
   stb_pool_free(c->d_ws);
   stb_pool_free(c->h_out);
@@ -453,6 +456,7 @@ extern "C" stb_bctx_t *stb_bterms_create(const uint32_t *T, int I) {
 extern "C" int stb_bterms_update(stb_bctx_t *c, const uint32_t *T, int I) {
   STB_ENTRY;
   if (!c) return stb_fail("stb_bterms_update: null context");
+  if (c->borrowed) return stb_fail("stb_bterms_update: the context borrows its T (stb_bterms_borrow)");
   if (I < 0 || (uint64_t)I > c->cap) return 1;
   const int prev = stb_device_enter(c->dev);
   int rc = 0;
@@ -462,6 +466,53 @@ extern "C" int stb_bterms_update(stb_bctx_t *c, const uint32_t *T, int I) {
     rc = stb_fail("stb_bterms_update: %s", hipGetErrorString(hipGetLastError()));
   stb_device_leave(prev);
   return rc;
+}
+
+// A context over totals that already live on the device: evaluations read d_T in place, queued on `stream` behind
+// whatever it holds.  c = NULL makes one; otherwise c (made here before) is pointed at the new array, its buffers kept
+// when they are large enough.  NULL on failure (c is then freed).
+extern "C" stb_bctx_t *stb_bterms_borrow(stb_bctx_t *c, const uint32_t *d_T, int I, void *stream) {
+  STB_ENTRY;
+  if (c && !c->borrowed) {
+    stb_fail("stb_bterms_borrow: the context owns its T");
+    return nullptr;
+  }
+  if (I < 0 || (I > 0 && !d_T)) {
+    stb_fail("stb_bterms_borrow: I=%d and d_T are required", I);
+    if (c) stb_bterms_free(c);
+    return nullptr;
+  }
+  int dev = -1;
+  if (stb_device_count() < 1 || hipGetDevice(&dev) != hipSuccess) {
+    stb_fail("stb_bterms_borrow: no HIP device (libstb_amd has no CPU path)");
+    if (c) stb_bterms_free(c);
+    return nullptr;
+  }
+  if (c && (c->dev != dev || (uint64_t)I > c->cap)) {
+    stb_bterms_free(c);
+    c = nullptr;
+  }
+  if (!c) {
+    c = (stb_bctx_t *)calloc(1, sizeof(*c));
+    if (!c) return nullptr;
+    c->borrowed = true;
+    c->dev = dev;
+    c->cap = (uint64_t)I;
+    c->ws_bytes = stb_terms_workspace_bytes(c->cap, STB_TERMS_DMAX);
+    bool ok = stb_pool_malloc((void **)&c->d_out, sizeof(double) * STB_TERMS_DMAX) == hipSuccess;
+    ok = ok && stb_pool_malloc(&c->d_ws, c->ws_bytes) == hipSuccess;
+    ok = ok && stb_pool_malloc((void **)&c->h_out, sizeof(double) * (STB_TERMS_DMAX + 8), 1) == hipSuccess;
+    ok = ok && hipHostGetDevicePointer((void **)&c->h_out_dev, c->h_out, 0) == hipSuccess;
+    if (!ok) {
+      stb_fail("stb_bterms_borrow: out of memory");
+      stb_bterms_free(c);
+      return nullptr;
+    }
+  }
+  c->I = (uint64_t)I;
+  c->d_T = const_cast<uint32_t *>(d_T);
+  c->st = (hipStream_t)stream;
+  return c;
 }
 
 // out_host[j] = bterms(x_j) (lib/sampleb.c:33-41), j < J <= 64; blocks until the values are there

@@ -28,6 +28,7 @@
 #include "stb_common.h"
 #include "groups.h"
 #include "tcounts.h"
+#include "hyperq.h"
 
 #define STB_TC_CAP 4096      // tau values a workgroup keeps in LDS (32 KB); longer rows recompute
 #define STB_TC_MAXWAVES 16
@@ -223,6 +224,7 @@ struct stb_tcounts {
   bool need_table;      // some pair can have 2 or more tables (min(max n, M) >= 2); otherwise every draw is t = 1
   uint64_t *d_koff;
   uint32_t *d_n, *d_T;
+  uint32_t *d_N;        // customers per restaurant (the sum of n over its pairs), built once at create: sampleb's N
   uint16_t *d_t;
   double *d_h;          // null: every h is 1
   double *d_bpar;
@@ -239,7 +241,7 @@ struct stb_tcounts {
 };
 
 static void tc_release(stb_tcounts_t *s) {
-  void *dev[] = {s->d_koff, s->d_n, s->d_T, s->d_t, s->d_h, s->d_bpar, s->d_table, s->d_S1, s->d_ws};
+  void *dev[] = {s->d_koff, s->d_n, s->d_T, s->d_N, s->d_t, s->d_h, s->d_bpar, s->d_table, s->d_S1, s->d_ws};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   for (int k = 0; k < 2; k++) {
@@ -304,6 +306,15 @@ static stb_tcounts_t *tc_create_here(int I, const int *K, const uint32_t *nflat,
   s->G = G;
   s->maxn = maxn;
   for (uint64_t g = 0; g < G; g++) s->sumn += nflat[g];
+  for (int i = 0; i < I; i++) {  // (N_i is a uint32, as sampleb's N[])
+    uint64_t ni = 0;
+    for (uint64_t g = koff[i]; g < koff[i + 1]; g++) ni += nflat[g];
+    if (ni >= (1ull << 32)) {
+      stb_fail("stb_tcounts_create: restaurant %d holds %llu customers (fewer than 2^32)", i, (unsigned long long)ni);
+      delete s;
+      return nullptr;
+    }
+  }
   s->N = maxn < 3 ? 3 : maxn;
   s->M = M;
   s->a_filled = NAN;
@@ -314,6 +325,7 @@ static stb_tcounts_t *tc_create_here(int I, const int *K, const uint32_t *nflat,
       hipMalloc((void **)&s->d_koff, sizeof(uint64_t) * (I + 1)) != hipSuccess ||
       hipMalloc((void **)&s->d_n, sizeof(uint32_t) * Gs) != hipSuccess || hipMalloc((void **)&s->d_t, sizeof(uint16_t) * Gs) != hipSuccess ||
       hipMalloc((void **)&s->d_T, sizeof(uint32_t) * I) != hipSuccess || hipMalloc((void **)&s->d_bpar, sizeof(double) * I) != hipSuccess ||
+      hipMalloc((void **)&s->d_N, sizeof(uint32_t) * I) != hipSuccess ||
       hipHostMalloc((void **)&s->h_bpar[0], sizeof(double) * I) != hipSuccess ||
       hipHostMalloc((void **)&s->h_bpar[1], sizeof(double) * I) != hipSuccess ||
       hipEventCreateWithFlags(&s->ev_bpar[0], hipEventDisableTiming) != hipSuccess ||
@@ -332,6 +344,9 @@ static stb_tcounts_t *tc_create_here(int I, const int *K, const uint32_t *nflat,
               hipMemcpy(s->d_T, T.data(), sizeof(uint32_t) * I, hipMemcpyHostToDevice) != hipSuccess ||
               (hflat && G && hipMemcpy(s->d_h, hflat, sizeof(double) * G, hipMemcpyHostToDevice) != hipSuccess)))
     rc = stb_fail("stb_tcounts_create: %s", hipGetErrorString(hipGetLastError()));
+  // customers per restaurant: a segmented sum of n over the pair offsets, once (the b step reads it: stb_tcounts_sampleb)
+  if (!rc) rc = stb_hq_segsum(s->d_koff, s->d_n, I, s->d_N, s->st);
+  if (!rc && hipStreamSynchronize(s->st) != hipSuccess) rc = stb_fail("stb_tcounts_create: %s", hipGetErrorString(hipGetLastError()));
   if (rc) {
     tc_release(s);
     return nullptr;
@@ -539,4 +554,20 @@ extern "C" int stb_tcounts_partition(stb_tcounts_t *s, double a, stb_hist_t *h, 
   if (ev) (void)hipEventDestroy(ev);
   stb_device_leave(prev);
   return rc;
+}
+
+// the concentration step on the object's counts (hyperq.hip, sampleb.c): Q from N on the device, T read in place, queued
+// behind the object's sweeps; the call waits for Q and for the sampler's evaluations only.  t and T are not written.
+extern "C" double stb_tcounts_sampleb(stb_tcounts_t *s, double b_in, double shape, double scale, double a, void *rng, int loops,
+                                      int verbose, uint64_t seed, uint64_t sweep) {
+  // (no rand() guard across the call: ARMS draws from the caller's rand() stream, as in sampleb)
+  if (!s) {
+    stb_fail("stb_tcounts_sampleb: null object");
+    return NAN;
+  }
+  const int prev = stb_device_enter(s->dev);
+  const double b = stb_sampleb_device_ex(b_in, s->I, shape, scale, s->d_N, nullptr, s->d_T, a, rng, loops, verbose, seed, sweep,
+                                         s->st, "stb_tcounts_sampleb");
+  stb_device_leave(prev);
+  return b;
 }

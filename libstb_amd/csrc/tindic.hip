@@ -23,6 +23,7 @@
 
 #include "stb_common.h"
 #include "groups.h"
+#include "hyperq.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
 #define STB_TI_REF_ODDS_FLAG 1u
@@ -568,4 +569,19 @@ extern "C" int stb_tindic_to_groups(stb_tindic_t *s, stb_groups_t *g, const doub
   }
   stb_device_leave(prev);
   return rc;
+}
+
+// the concentration step on the object's counts, as stb_tcounts_sampleb: N_i is the customer offsets' difference
+extern "C" double stb_tindic_sampleb(stb_tindic_t *s, double b_in, double shape, double scale, double a, void *rng, int loops,
+                                     int verbose, uint64_t seed, uint64_t sweep) {
+  // (no rand() guard across the call: ARMS draws from the caller's rand() stream, as in sampleb)
+  if (!s) {
+    stb_fail("stb_tindic_sampleb: null object");
+    return NAN;
+  }
+  const int prev = stb_device_enter(s->dev);
+  const double b = stb_sampleb_device_ex(b_in, s->I, shape, scale, nullptr, s->d_coff, s->d_T, a, rng, loops, verbose, seed,
+                                         sweep, s->st, "stb_tindic_sampleb");
+  stb_device_leave(prev);
+  return b;
 }
