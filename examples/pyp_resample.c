@@ -16,10 +16,12 @@
  *   6. with -d steps 2 and 3 run on the device from resident counts: stb_tindic_sweep -> stb_tindic_sampleb ->
  *      stb_tindic_to_groups + stb_groups_samplea; no pair and no per-restaurant array crosses to the host inside the loop
  *      (the indicator step then uses the exact prior ratio t/(n-t), see stb_hip.h, and counter-based uniforms).
+ *   7. with -j the device loop draws a and b JOINTLY instead: stb_tindic_sweep -> stb_tindic_samplejoint, an exact
+ *      independence Metropolis-Hastings step from nested grids on [0.02, 0.97] x [0.05, 500] (stb_hip.h).
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j]
  */
 #include <math.h>
 #include <stdio.h>
@@ -35,10 +37,10 @@
 #define DISHES 50
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:d")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:dj")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -48,6 +50,7 @@ int main(int argc, char **argv) {
     else if (c == 'G') nsets = atoi(optarg);
     else if (c == 's') seed = atol(optarg);
     else if (c == 'd') ondev = 1;
+    else if (c == 'j') ondev = joint = 1;
     else return 2;
   }
   srand48(seed);
@@ -116,12 +119,25 @@ int main(int argc, char **argv) {
       }
     for (cc = 0; cc < (size_t)J * ncust; cc++) cust[cc] = (scnt_int)dish_of[cc]; /* (K = DISHES: the dish is the local pair) */
     stb_tindic_t *ti = stb_tindic_create(J, K, nf, tf, hf, cust, maxn > 65535 ? 65535 : 0, 0);
-    stb_groups_t *gs = stb_groups_create(J, K, NULL, NULL, NULL, NULL, 0, 0, 3);
+    stb_groups_t *gs = stb_groups_create(J, K, NULL, NULL, NULL, NULL, 0, 0, joint ? 25 : 3);
+    int accepted = 0, steps = 0;
     if (!ti || !gs) yaps_quit("device loop: %s\n", stb_last_error());
     for (j = 0; j < J; j++) bvec[j] = b;
     for (it = 0; it < cycles; it++) {
       if (stb_tindic_sweep(ti, a, bvec, (uint64_t)seed, (uint64_t)it, 1)) yaps_quit("stb_tindic_sweep: %s\n", stb_last_error());
-      if (it % 3 == 2) {
+      if (it % 3 == 2 && joint) {
+        stb_joint_opts_t jo = {0.02, 0.97, 0.05, 500.0, 24, 24, 1.1, 20.0, (uint64_t)seed + 1, (uint64_t)it, 0};
+        stb_joint_info_t ji;
+        if (stb_tindic_samplejoint(ti, gs, &jo, a, b, &a, &b, &ji)) yaps_quit("stb_tindic_samplejoint: %s\n", stb_last_error());
+        accepted += ji.accepted;
+        steps++;
+        for (j = 0; j < J; j++) bvec[j] = b;
+        if (it >= cycles / 2) {
+          asum += a;
+          bsum += b;
+          kept++;
+        }
+      } else if (it % 3 == 2) {
         b = stb_tindic_sampleb(ti, b, 1.1, 20.0, a, 0, 1, 0, (uint64_t)seed + 1, (uint64_t)it);
         if (b != b) yaps_quit("stb_tindic_sampleb: %s\n", stb_last_error());
         for (j = 0; j < J; j++) bvec[j] = b;
@@ -136,6 +152,7 @@ int main(int argc, char **argv) {
       }
     }
     if (stb_tindic_get(ti, tf, T)) yaps_quit("stb_tindic_get: %s\n", stb_last_error());
+    if (joint) printf("joint steps: %d of %d proposals accepted, last a=%.4f b=%.3f\n", accepted, steps, a, b);
     for (j = 0, g = 0; j < J; j++)
       for (i = 0; i < DISHES; i++, g++) t[j][i] = tf[g];
     stb_groups_free(gs);

@@ -227,6 +227,65 @@ double stb_sampleb_device(double b_in, int I, double shape, double scale, const 
                           double a, void *rng, int loops, int verbose, uint64_t seed, uint64_t sweep, void *stream);
 double stb_sampleb_last_Q(void);          /* the Q of this thread's last device b step, for tests */
 
+/* ---- the joint step for discount and concentration from device-resident counts (hyperj.hip; an additive algorithm,
+ * not the reference's: DESIGN.md section 6, deviation 14) ----
+ * All restaurants share one discount a and one concentration b (test/demo.c's model).  With beta = log b the target is
+ *     L(a, beta) = W(a) + R(a, b) + (shape - 1) beta - b / scale + beta           on [a_lo, a_hi] x [b_lo, b_hi]
+ *     W(a)    = sum over pairs with n > 1 of S_S_a(n, t)                          (stb_groups_ssum)
+ *     R(a, b) = sum_i [ T_i log a + lgamma(T_i + b/a) - lgamma(b/a) - lgamma(b + N_i) + lgamma(b) ]   (0 where N_i = 0)
+ * -- a flat prior on a, sampleb's Gamma(shape, scale) on b, the Jacobian of b -> beta.
+ * stb_joint_terms: d_out[d J + j] = R(a_d, b_j) for a grid of D x J (1 <= D, J <= 64) from d_T[I], d_N[I] (uint32, device),
+ * queued on `stream`; one launch, FP64.  The bits do not depend on launch geometry (STB_HYPERJ_WAVES = 1, 2, 4 or 8 waves
+ * a workgroup); the association is written out in hyperj.hip's header.  One stream at a time per calling thread.
+ * stb_groups_samplejoint: one independence Metropolis-Hastings step that leaves exp(L) on the rectangle invariant.  Up to
+ * five nested stages; stage s lays D x J cells (uniform in a and in beta) over its rectangle, evaluates L at the cell
+ * midpoints (one batched stb_groups_ssum of D + 1 discounts -- the current a rides along -- and one stb_joint_terms launch),
+ * weights w = exp(max(L - max, -60)), and takes as its box the bounding box of the cells with L >= max - 40, padded by one
+ * cell and clipped; while the box spans at most half of the cells on either axis (and s < 5) the next stage repeats on the
+ * box.  The proposal is q = sum_s eps_s q_s (eps_s = 1/64 for every stage but the last, which takes the rest), q_s
+ * piecewise constant over stage s's cells: the stage from u5, the cell by inverse CDF of the weights in d-major order from
+ * u1, the point uniform in the cell from u2, u3; accepted iff log u4 < [L(x') - L(x)] + [log q(x) - log q(x')], with L
+ * evaluated at the two points themselves.  u_k = element k of the stream of key = mix(seed + (sweep+1) gamma)
+ * (libstb_amd/synth.py's unit(., key)).  The rectangle must not depend on the state.  S + 1 waits for S stages.
+ * The set needs Dmax >= D + 1 and holds the pairs and T (stb_tcounts_to_groups ...).  Its bpar are NOT read -- b is the
+ * argument, and after an accepted move the set's copy is stale until the caller sets it again; they are only a consistency
+ * token for the model of one shared b: a set whose bpar were last set to unequal values is refused, one whose bpar were
+ * never set is accepted.  Failures -- a null set, a bad rectangle (A_MIN <= a_lo < a_hi <= A_MAX,
+ * B_MIN <= b_lo < b_hi <= B_MAX of include/psample.h), a state outside it, Dmax too small, unequal bpar, a non-finite L at
+ * the current state or a NaN / +inf on a grid -- return non-zero with stb_last_error() set and leave *a_out, *b_out alone.
+ * stb_tcounts_samplejoint / stb_tindic_samplejoint: the same on an object's counts: stb_*_to_groups(s, g, NULL) first, then
+ * the step with the object's N, queued behind its sweeps; nothing per restaurant crosses to the host, t and T are not
+ * written. */
+#define STB_JOINT_KEEP_L 1u   /* info->L receives every stage's D J values of L (for tests) */
+typedef struct stb_joint_opts {
+  double a_lo, a_hi, b_lo, b_hi;   /* the rectangle, in a and b */
+  int D, J;                        /* cells per stage; 0: 24.  D <= 63, J <= 64 */
+  double shape, scale;             /* the Gamma prior of b, as sampleb's */
+  uint64_t seed, sweep;
+  unsigned flags;
+} stb_joint_opts_t;
+typedef struct stb_joint_info {
+  int stages, accepted, evals;     /* stages taken, 1 if x' was accepted, batched pair-sum evaluations (stages + 1) */
+  int stage_pick;                  /* the stage x' was drawn from, 1-based */
+  double log_alpha;
+  double rect[4];                  /* the last stage's rectangle: a_lo, a_hi, beta_lo, beta_hi */
+  double a_prop, b_prop, L_cur, L_prop;
+  int cell[5];                     /* per stage the cell u1 picks, d J + j */
+  int box[5][4];                   /* per stage its box: d lo, d hi, j lo, j hi (cells, inclusive) */
+  const double *L;                 /* STB_JOINT_KEEP_L: [stages][D J], valid until this thread's next step */
+} stb_joint_info_t;
+struct stb_groups;
+struct stb_tcounts;
+struct stb_tindic;
+int stb_joint_terms(const double *a_host, int D, const double *b_host, int J, const uint32_t *d_T, const uint32_t *d_N,
+                    uint64_t I, double *d_out, void *stream);
+int stb_groups_samplejoint(struct stb_groups *g, const uint32_t *d_N, const stb_joint_opts_t *opts, double a_in, double b_in,
+                           double *a_out, double *b_out, stb_joint_info_t *info);
+int stb_tcounts_samplejoint(struct stb_tcounts *s, struct stb_groups *g, const stb_joint_opts_t *opts, double a_in, double b_in,
+                            double *a_out, double *b_out, stb_joint_info_t *info);
+int stb_tindic_samplejoint(struct stb_tindic *s, struct stb_groups *g, const stb_joint_opts_t *opts, double a_in, double b_in,
+                           double *a_out, double *b_out, stb_joint_info_t *info);
+
 /* ---- device-resident group set + grid evaluation (host-friendly wrappers over the above) ----
  * stb_groups_t owns device copies of the flat (n,t) pairs and the per-restaurant T, bpar, plus
  * the scratch needed to evaluate aterms on up to Dmax discounts with table bounds (N,M). */
@@ -262,6 +321,11 @@ int stb_groups_create_node(int ndev, int I, const int *K, const uint32_t *T, con
  * stb_groups_wait(g) must still follow, before the values are trusted: it reports a table walk that gave up waiting
  * for a neighbour, in which case it re-evaluates through stored tables and rewrites d_out. */
 int stb_groups_aterms_device(stb_groups_t *g, const double *x_host, int D, double *d_out, void *stream);
+/* the pair sum alone: out[d] = W(x_d) = sum over pairs with n > 1 of S_S_{x_d}(n, t), without the restaurant terms.  It
+ * goes through exactly the forms stb_groups_aterms_device takes (same lists, same fallbacks); _device queues like
+ * stb_groups_aterms_device and stb_groups_wait(g) must follow; stb_groups_ssum blocks and writes out_host[0..D). */
+int stb_groups_ssum_device(stb_groups_t *g, const double *x_host, int D, double *d_out, void *stream);
+int stb_groups_ssum(stb_groups_t *g, const double *x_host, int D, double *out_host);
 /* the same values through stored tables and the sorted gather whatever D is (stb_groups_aterms sums
  * inside the fill when D >= 2, which needs a set-up pass over the pairs on first use) */
 int stb_groups_aterms_tables(stb_groups_t *g, const double *x_host, int D, double *out_host);

@@ -39,6 +39,24 @@ class StbError(RuntimeError):
     pass
 
 
+JOINT_KEEP_L = 1  # stb_joint_opts_t flag: every stage's L values come back in the info (tests)
+
+
+class JointOpts(C.Structure):
+    """stb_joint_opts_t (include/stb_hip.h)"""
+    _fields_ = [("a_lo", C.c_double), ("a_hi", C.c_double), ("b_lo", C.c_double), ("b_hi", C.c_double),
+                ("D", C.c_int), ("J", C.c_int), ("shape", C.c_double), ("scale", C.c_double),
+                ("seed", C.c_uint64), ("sweep", C.c_uint64), ("flags", C.c_uint)]
+
+
+class JointInfo(C.Structure):
+    """stb_joint_info_t (include/stb_hip.h)"""
+    _fields_ = [("stages", C.c_int), ("accepted", C.c_int), ("evals", C.c_int), ("stage_pick", C.c_int),
+                ("log_alpha", C.c_double), ("rect", C.c_double * 4), ("a_prop", C.c_double), ("b_prop", C.c_double),
+                ("L_cur", C.c_double), ("L_prop", C.c_double), ("cell", C.c_int * 5), ("box", (C.c_int * 4) * 5),
+                ("L", c_double_p)]
+
+
 @lru_cache(maxsize=None)
 def lib() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
@@ -194,6 +212,13 @@ def lib() -> C.CDLL:
     sig("stb_tindic_sampleb", d, [vp, d, d, d, d, vp, i, i, u64, u64])
     sig("stb_sampleb_last_Q", d, [])
     sig("stb_groups_samplea", d, [vp, d, vp, i, i])
+    sig("stb_groups_ssum", i, [vp, c_double_p, i, c_double_p])
+    sig("stb_groups_ssum_device", i, [vp, c_double_p, i, vp, vp])
+    sig("stb_joint_terms", i, [c_double_p, i, c_double_p, i, vp, vp, u64, vp, vp])
+    jo, ji = C.POINTER(JointOpts), C.POINTER(JointInfo)
+    sig("stb_groups_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
+    sig("stb_tcounts_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
+    sig("stb_tindic_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
     # optional entry points (present once the sampler host code is linked in)
     for name, res, args in (
         ("arms_simple", i, [i, c_double_p, c_double_p, LOGDENS, vp, i, c_double_p, c_double_p]),
@@ -519,6 +544,13 @@ class TableCounts:
             raise StbError(last_error())
         return r
 
+    def samplejoint(self, groups, rect, a, b, shape, scale, seed: int, sweep: int, D: int = 0, J: int = 0,
+                    keep_L: bool = False):
+        """one joint step for (a, b) on the current counts through the group set `groups`, behind the queued sweeps
+        (stb_tcounts_samplejoint); see groups_samplejoint"""
+        return _joint_call(self.L.stb_tcounts_samplejoint, (self.h, groups), rect, a, b, shape, scale, seed, sweep, D, J,
+                           keep_L)
+
     def partition(self, a, hist, bpar, seed: int, sweep: int):
         """stage 1 of the S-free discount step on the current pairs, queued: the table-size histogram into `hist` (a
         Histogram with I restaurants and S > the largest n), with T and bpar (stb_tcounts_partition)"""
@@ -575,6 +607,51 @@ def groups_samplea(groups, a, loops: int = 1, verbose: int = 0):
     if r != r:
         raise StbError(last_error())
     return r
+
+
+def groups_ssum(groups, x):
+    """stb_groups_ssum on a group-set handle: W(x_d), the pair sum without the restaurant terms"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros(x.shape[0], dtype=np.float64)
+    check(lib().stb_groups_ssum(groups, dp(x), int(x.shape[0]), dp(out)))
+    return out
+
+
+def joint_terms(a, b, T, N, stream=None):
+    """stb_joint_terms on device tensors T, N (int32 holding uint32 counts): R[d, j] as a float64 device tensor"""
+    torch = _torch()
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    I = int(T.shape[0])
+    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float64, device=T.device)
+    check(lib().stb_joint_terms(dp(a), int(a.shape[0]), dp(b), int(b.shape[0]), T.data_ptr() if I else None,
+                                N.data_ptr() if I else None, I, out.data_ptr(), stream_ptr(stream)))
+    return out
+
+
+def _joint_call(fn, head, rect, a, b, shape, scale, seed, sweep, D, J, keep_L):
+    o = JointOpts(float(rect[0]), float(rect[1]), float(rect[2]), float(rect[3]), int(D), int(J), float(shape),
+                  float(scale), int(seed), int(sweep), JOINT_KEEP_L if keep_L else 0)
+    info = JointInfo()
+    ao, bo = C.c_double(float(a)), C.c_double(float(b))
+    check(fn(*head, C.byref(o), float(a), float(b), C.byref(ao), C.byref(bo), C.byref(info)))
+    res = {"a": ao.value, "b": bo.value, "stages": info.stages, "accepted": bool(info.accepted), "evals": info.evals,
+           "stage_pick": info.stage_pick, "log_alpha": info.log_alpha, "rect": tuple(info.rect),
+           "a_prop": info.a_prop, "b_prop": info.b_prop, "L_cur": info.L_cur, "L_prop": info.L_prop,
+           "cell": [info.cell[s] for s in range(info.stages)],
+           "box": [tuple(info.box[s]) for s in range(info.stages)]}
+    if keep_L:
+        DJ = (int(D) or 24) * (int(J) or 24)
+        res["L"] = np.ctypeslib.as_array(info.L, shape=(info.stages * DJ,)).reshape(info.stages, DJ).copy()
+    return res
+
+
+def groups_samplejoint(groups, N, rect, a, b, shape, scale, seed: int, sweep: int, D: int = 0, J: int = 0,
+                       keep_L: bool = False):
+    """stb_groups_samplejoint on a group-set handle and a device tensor N (int32 holding uint32 counts); rect =
+    (a_lo, a_hi, b_lo, b_hi).  A dict with the new a, b and the step's diagnostics"""
+    return _joint_call(lib().stb_groups_samplejoint, (groups, None if N is None else N.data_ptr()), rect, a, b, shape,
+                       scale, seed, sweep, D, J, keep_L)
 
 
 def sampler_trace():
@@ -724,6 +801,13 @@ class TableIndicators:
         if r != r:
             raise StbError(last_error())
         return r
+
+    def samplejoint(self, groups, rect, a, b, shape, scale, seed: int, sweep: int, D: int = 0, J: int = 0,
+                    keep_L: bool = False):
+        """one joint step for (a, b) on the current counts through the group set `groups`, behind the queued sweeps
+        (stb_tindic_samplejoint); see groups_samplejoint"""
+        return _joint_call(self.L.stb_tindic_samplejoint, (self.h, groups), rect, a, b, shape, scale, seed, sweep, D, J,
+                           keep_L)
 
     def free(self):
         if self.h:

@@ -77,6 +77,7 @@ struct stb_groups {
   hipEvent_t ev_done;
   hipEvent_t ev_dep;
   int pending, pend_D, pend_fuse, pend_v;
+  int pend_ssum;               // the queued evaluation is the pair sum alone (stb_groups_ssum): no restaurant terms
   int sel_which;  // the list layout aterms_prepare chose for a fused evaluation in the halo-block form
   int last_fused, last_C, last_R;  // what aterms_prepare decided last: fused or not, the strip shape of the lists taken (stb_groups_last_form)
   double *pend_out;

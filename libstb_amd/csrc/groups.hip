@@ -265,6 +265,7 @@ static stb_groups_t *groups_create_here(int I, const int *K, const uint32_t *T, 
   GCHK(stb_pool_malloc((void **)&g->d_bpar, sizeof(double) * (I > 0 ? I : 1)));
   GCHK(stb_pool_malloc((void **)&g->h_T, sizeof(uint32_t) * (I > 0 ? I : 1), 1));
   GCHK(stb_pool_malloc((void **)&g->h_bpar, sizeof(double) * (I > 0 ? I : 1), 1));
+  for (int i = 0; i < (I > 0 ? I : 1); i++) g->h_bpar[i] = NAN;  // (no concentrations yet: the joint step refuses such a set)
   GCHK(stb_pool_malloc((void **)&g->d_out, sizeof(double) * 2 * Dmax));
   GCHK(stb_pool_malloc((void **)&g->h_out, sizeof(double) * (2 * Dmax + 4), 1));
   GCHK(hipHostGetDevicePointer((void **)&g->h_out_dev, g->h_out, 0));
@@ -968,7 +969,7 @@ static int groups_fused_setup(stb_groups_t *g) {
 static std::atomic<unsigned> g_fused_giveups{0};
 extern "C" unsigned stb_groups_fallbacks(void) { return g_fused_giveups.load(); }
 
-static int aterms_issue_lean(stb_groups_t *g, const double *x_host, int D, double *out_host, int which, bool timed) {
+static int aterms_issue_lean(stb_groups_t *g, const double *x_host, int D, double *out_host, int which, bool timed, bool ssum) {
   g->pending = 0;
   char *ws0 = (char *)g->d_ws_fill;
   double *a_dev = (double *)ws0;
@@ -977,7 +978,10 @@ static int aterms_issue_lean(stb_groups_t *g, const double *x_host, int D, doubl
   if (timed) HIPCHK(hipEventRecord(g->ev[0], g->st));
   const dd_t *tpart = nullptr;
   int nbt = 0;
-  if (stb_restaurant_partials(x_host, D, g->d_T, g->d_bpar, (uint64_t)g->I, g->d_ws_terms, g->ws_terms, a_dev, &tpart, &nbt, g->st))
+  // (the pair sum alone: the same launch over no restaurants -- one empty partial per abscissa, and 0 + dots is dots;
+  // the abscissae still travel with it)
+  g->pend_ssum = ssum ? 1 : 0;
+  if (stb_restaurant_partials(x_host, D, g->d_T, g->d_bpar, g->pend_ssum ? 0 : (uint64_t)g->I, g->d_ws_terms, g->ws_terms, a_dev, &tpart, &nbt, g->st))
     return 1;
   dot_request req;
   req.item_ptr = g->d_item_ptr[which];
@@ -1042,10 +1046,11 @@ static int aterms_issue_lean(stb_groups_t *g, const double *x_host, int D, doubl
   return 0;
 }
 
-static int aterms_issue(stb_groups_t *g, const double *x_host, int D, double *out_host, bool fuse, int v, bool timed = true) {
+static int aterms_issue(stb_groups_t *g, const double *x_host, int D, double *out_host, bool fuse, int v, bool timed, bool ssum) {
   if (fuse && v == STB_FILL_HB && g->sparse && g->sel_which >= 2)
-    return aterms_issue_lean(g, x_host, D, out_host, g->sel_which, timed);
+    return aterms_issue_lean(g, x_host, D, out_host, g->sel_which, timed, ssum);
   g->pend_lean = 0;
+  g->pend_ssum = ssum ? 1 : 0;
   g->ws_zero = 0;  // (this flow's fills zero and use the workspace themselves)
   if (ensure_tables(g)) return 1;
   if (!fuse && stb_groups_sort_pairs(g)) return 1;  // (the gather's sum is then independent of the caller's order)
@@ -1092,8 +1097,8 @@ static int aterms_issue(stb_groups_t *g, const double *x_host, int D, double *ou
       return 1;
   }
   HIPCHK(hipEventRecord(g->ev[2], g->st));
-  if (stb_restaurant_terms(x_host, D, g->d_T, g->d_bpar, (uint64_t)g->I, g->d_out + g->Dmax,
-                           g->d_ws_terms, g->ws_terms, g->st))
+  if (!g->pend_ssum && stb_restaurant_terms(x_host, D, g->d_T, g->d_bpar, (uint64_t)g->I, g->d_out + g->Dmax,
+                                            g->d_ws_terms, g->ws_terms, g->st))
     return 1;
   HIPCHK(hipEventRecord(g->ev[3], g->st));
   HIPCHK(hipMemcpyAsync(g->h_out, g->d_out, sizeof(double) * 2 * g->Dmax, hipMemcpyDeviceToHost, g->st));
@@ -1150,7 +1155,7 @@ static int aterms_finish(stb_groups_t *g, float *ms_fill, float *ms_sweep, float
     HIPCHK(hipMemcpyAsync(g->h_out, g->d_out, sizeof(double) * g->Dmax, hipMemcpyDeviceToHost, g->st));
     HIPCHK(hipStreamSynchronize(g->st));
   }
-  for (int d = 0; d < D; d++) g->pend_out[d] = g->h_out[g->Dmax + d] + g->h_out[d];
+  for (int d = 0; d < D; d++) g->pend_out[d] = g->pend_ssum ? g->h_out[d] : g->h_out[g->Dmax + d] + g->h_out[d];
   if (ms_fill) HIPCHK(hipEventElapsedTime(ms_fill, g->ev[0], g->ev[1]));
   if (ms_sweep) HIPCHK(hipEventElapsedTime(ms_sweep, g->ev[1], g->ev[2]));
   if (ms_terms) HIPCHK(hipEventElapsedTime(ms_terms, g->ev[2], g->ev[3]));
@@ -1158,8 +1163,8 @@ static int aterms_finish(stb_groups_t *g, float *ms_fill, float *ms_sweep, float
 }
 
 static int aterms_once(stb_groups_t *g, const double *x_host, int D, double *out_host, bool fuse, int v,
-                       float *ms_fill, float *ms_sweep, float *ms_terms) {
-  if (aterms_issue(g, x_host, D, out_host, fuse, v, ms_fill || ms_sweep || ms_terms)) return 1;
+                       float *ms_fill, float *ms_sweep, float *ms_terms, bool ssum = false) {
+  if (aterms_issue(g, x_host, D, out_host, fuse, v, ms_fill || ms_sweep || ms_terms, ssum)) return 1;
   return aterms_finish(g, ms_fill, ms_sweep, ms_terms);
 }
 
@@ -1245,15 +1250,15 @@ static int aterms_prepare(stb_groups_t *g, int D, bool allow_fuse, bool *fuse_ou
 }
 
 static int groups_aterms(stb_groups_t *g, const double *x_host, int D, double *out_host, bool allow_fuse, float *ms_fill,
-                         float *ms_sweep, float *ms_terms) {
+                         float *ms_sweep, float *ms_terms, bool ssum = false) {
   if (!g) return stb_fail("stb_groups_aterms: null group set");
   const int prev_dev = stb_device_enter(g->dev);
   bool fuse = false;
   int v = 0;
   int rc = aterms_prepare(g, D, allow_fuse, &fuse, &v);
-  if (!rc) rc = aterms_once(g, x_host, D, out_host, fuse, v, ms_fill, ms_sweep, ms_terms);
+  if (!rc) rc = aterms_once(g, x_host, D, out_host, fuse, v, ms_fill, ms_sweep, ms_terms, ssum);
   if (rc == 2)  // no waits between workgroups in this form
-    rc = aterms_once(g, x_host, D, out_host, false, STB_FILL_PC, ms_fill, ms_sweep, ms_terms) ? 1 : 0;
+    rc = aterms_once(g, x_host, D, out_host, false, STB_FILL_PC, ms_fill, ms_sweep, ms_terms, ssum) ? 1 : 0;
   stb_device_leave(prev_dev);
   return rc;
 }
@@ -1274,7 +1279,7 @@ extern "C" int stb_groups_aterms_async(stb_groups_t *g, const double *x_host, in
     if (hipEventRecord(g->ev_dep, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(g->st, g->ev_dep, 0) != hipSuccess)
       rc = stb_fail("stb_groups_aterms_async: %s", hipGetErrorString(hipGetLastError()));
   }
-  if (!rc) rc = aterms_issue(g, x_host, D, out_host, fuse, v, false);
+  if (!rc) rc = aterms_issue(g, x_host, D, out_host, fuse, v, false, false);
   stb_device_leave(prev_dev);
   return rc;
 }
@@ -1296,7 +1301,8 @@ extern "C" int stb_groups_wait(stb_groups_t *g) {
   g->pend_user = nullptr;
   int rc = aterms_finish(g, nullptr, nullptr, nullptr);
   const bool redo = rc == 2;
-  if (rc == 2) rc = aterms_once(g, x, D, out, false, STB_FILL_PC, nullptr, nullptr, nullptr) ? 1 : 0;
+  const bool ssum = g->pend_ssum != 0;  // (the repeat is the same kind of evaluation)
+  if (rc == 2) rc = aterms_once(g, x, D, out, false, STB_FILL_PC, nullptr, nullptr, nullptr, ssum) ? 1 : 0;
   // (stb_groups_aterms_device: only the lean flow's last launch writes the caller's device buffer itself)
   if (!rc && user && (redo || !lean)) {
     if (hipMemcpyAsync(user, out, sizeof(double) * D, hipMemcpyHostToDevice, g->st) != hipSuccess || hipStreamSynchronize(g->st) != hipSuccess)
@@ -1312,20 +1318,19 @@ extern "C" int stb_groups_wait(stb_groups_t *g) {
 // for the values, so work queued on it afterwards sees them.  stb_groups_wait(g) must still be called -- before the
 // values are trusted: it reports a walk that gave up waiting, and then re-evaluates through stored tables and rewrites
 // d_out.
-extern "C" int stb_groups_aterms_device(stb_groups_t *g, const double *x_host, int D, double *d_out, void *stream) {
-  STB_ENTRY;
-  if (!g || !d_out) return stb_fail("stb_groups_aterms_device: null argument");
+static int groups_eval_device(stb_groups_t *g, const double *x_host, int D, double *d_out, void *stream, bool ssum, const char *who) {
+  if (!g || !d_out) return stb_fail("%s: null argument", who);
   const int prev_dev = stb_device_enter(g->dev);
   bool fuse = false;
   int v = 0;
   int rc = aterms_prepare(g, D, true, &fuse, &v);
   if (!rc && stream) {
     if (hipEventRecord(g->ev_dep, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(g->st, g->ev_dep, 0) != hipSuccess)
-      rc = stb_fail("stb_groups_aterms_device: %s", hipGetErrorString(hipGetLastError()));
+      rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
   }
   if (!rc) {
     g->pend_user = d_out;
-    rc = aterms_issue(g, x_host, D, g->pend_host, fuse, v, false);
+    rc = aterms_issue(g, x_host, D, g->pend_host, fuse, v, false, ssum);
     if (rc) g->pend_user = nullptr;
   }
   if (!rc && !g->pend_lean) {
@@ -1333,15 +1338,33 @@ extern "C" int stb_groups_aterms_device(stb_groups_t *g, const double *x_host, i
     // copied, on the set's stream; the wait that must follow has nothing left to do)
     g->pend_user = nullptr;
     rc = aterms_finish(g, nullptr, nullptr, nullptr);
-    if (rc == 2) rc = aterms_once(g, x_host, D, g->pend_host, false, STB_FILL_PC, nullptr, nullptr, nullptr) ? 1 : 0;
+    if (rc == 2) rc = aterms_once(g, x_host, D, g->pend_host, false, STB_FILL_PC, nullptr, nullptr, nullptr, ssum) ? 1 : 0;
     if (!rc && hipMemcpyAsync(d_out, g->pend_host, sizeof(double) * D, hipMemcpyHostToDevice, g->st) != hipSuccess)
-      rc = stb_fail("stb_groups_aterms_device: %s", hipGetErrorString(hipGetLastError()));
+      rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
     if (!rc) g->pending = 2;
   }
   if (!rc && (hipEventRecord(g->ev_done, g->st) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, g->ev_done, 0) != hipSuccess))
-    rc = stb_fail("stb_groups_aterms_device: %s", hipGetErrorString(hipGetLastError()));
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
   stb_device_leave(prev_dev);
   return rc;
+}
+
+extern "C" int stb_groups_aterms_device(stb_groups_t *g, const double *x_host, int D, double *d_out, void *stream) {
+  STB_ENTRY;
+  return groups_eval_device(g, x_host, D, d_out, stream, false, "stb_groups_aterms_device");
+}
+
+// The pair sum alone, W(x_d) = sum over pairs with n > 1 of S_S_{x_d}(n, t): the evaluation above without its restaurant
+// terms -- same choice of form, same lists, same fallbacks (what the joint step of hyperj.hip adds its own R(a, b) to).
+extern "C" int stb_groups_ssum_device(stb_groups_t *g, const double *x_host, int D, double *d_out, void *stream) {
+  STB_ENTRY;
+  return groups_eval_device(g, x_host, D, d_out, stream, true, "stb_groups_ssum_device");
+}
+
+extern "C" int stb_groups_ssum(stb_groups_t *g, const double *x_host, int D, double *out_host) {
+  STB_ENTRY;
+  if (!g) return stb_fail("stb_groups_ssum: null group set");
+  return groups_aterms(g, x_host, D, out_host, true, nullptr, nullptr, nullptr, true);
 }
 
 extern "C" int stb_groups_aterms_timed(stb_groups_t *g, const double *x_host, int D, double *out_host, float *ms_fill,

@@ -19,6 +19,7 @@
 #include "../../include/stb_hip.h"
 #include "sampler_trace.h"
 #include "hyperq.h"
+#include "hyperj.h"
 
 #define NPRE 3 /* abscissae ARMS is known to ask for first (lib/arms.c:117-119) */
 
@@ -65,6 +66,7 @@ void stb_sampleb_cache_clear(void) {
   if (kept_bdev) stb_bterms_free(kept_bdev);
   kept_bdev = NULL;
   stb_hq_release();
+  stb_hj_release();
 }
 
 static int use_slice(void) {

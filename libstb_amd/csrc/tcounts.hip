@@ -29,6 +29,7 @@
 #include "groups.h"
 #include "tcounts.h"
 #include "hyperq.h"
+#include "hyperj.h"
 
 #define STB_TC_CAP 4096      // tau values a workgroup keeps in LDS (32 KB); longer rows recompute
 #define STB_TC_MAXWAVES 16
@@ -570,4 +571,13 @@ extern "C" double stb_tcounts_sampleb(stb_tcounts_t *s, double b_in, double shap
                                          s->st, "stb_tcounts_sampleb");
   stb_device_leave(prev);
   return b;
+}
+
+// the joint step for a and b on the object's counts (hyperj.hip): the pairs and T to the set, device to device, then the
+// step with the object's N, queued behind its sweeps.  Nothing per restaurant crosses to the host; t and T are not written.
+extern "C" int stb_tcounts_samplejoint(stb_tcounts_t *s, stb_groups_t *g, const stb_joint_opts_t *opts, double a_in, double b_in,
+                                   double *a_out, double *b_out, stb_joint_info_t *info) {
+  if (!s || !g) return stb_fail("stb_tcounts_samplejoint: null object");
+  if (stb_tcounts_to_groups(s, g, nullptr)) return 1;
+  return stb_hj_samplejoint(g, s->d_N, nullptr, opts, a_in, b_in, a_out, b_out, info, "stb_tcounts_samplejoint");
 }

@@ -24,6 +24,7 @@
 #include "stb_common.h"
 #include "groups.h"
 #include "hyperq.h"
+#include "hyperj.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
 #define STB_TI_REF_ODDS_FLAG 1u
@@ -584,4 +585,13 @@ extern "C" double stb_tindic_sampleb(stb_tindic_t *s, double b_in, double shape,
                                          sweep, s->st, "stb_tindic_sampleb");
   stb_device_leave(prev);
   return b;
+}
+
+// the joint step for a and b on the object's counts (hyperj.hip): the pairs and T to the set, device to device, then the
+// step with the object's N, queued behind its sweeps.  Nothing per restaurant crosses to the host; t and T are not written.
+extern "C" int stb_tindic_samplejoint(stb_tindic_t *s, stb_groups_t *g, const stb_joint_opts_t *opts, double a_in, double b_in,
+                                   double *a_out, double *b_out, stb_joint_info_t *info) {
+  if (!s || !g) return stb_fail("stb_tindic_samplejoint: null object");
+  if (stb_tindic_to_groups(s, g, nullptr)) return 1;
+  return stb_hj_samplejoint(g, nullptr, s->d_coff, opts, a_in, b_in, a_out, b_out, info, "stb_tindic_samplejoint");
 }

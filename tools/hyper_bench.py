@@ -9,6 +9,10 @@ S1000 = 1000 x 50 x 200; a = 0.5, b = 10, h = 1/50, shuffled customer order), th
   device   (i)   b step: stb_tindic_sampleb
            (ii)  a step: stb_tindic_to_groups + stb_groups_samplea
            (iii) stb_tindic_sweep + (i) + (ii)
+           (iv)  joint step: stb_tindic_samplejoint on [0.02, 0.97] x [0.05, 500], 24 x 24 cells (hyperj.hip), a set of its
+                 own with Dmax = 25; and stb_tindic_sweep + (iv).  Over --joint-iters (50) iterations of sweep + joint, the
+                 state moving with the draws: stages taken and acceptance rate.  k_joint_terms alone (device events around
+                 stb_joint_terms) at 24 x 24 and 64 x 64.
   host     (i)   stb_tindic_get + sampleb(N, T)          (the parent's path: Beta draws on one core, T copied back up)
            (ii)  stb_tindic_get + samplea(ragged n, t)   (the pairs down and up again)
            (iii) stb_tindic_sweep + get + sampleb + samplea
@@ -48,7 +52,7 @@ def stats(v):
     return {"median_ms": float(np.median(v)), "min_ms": float(min(v)), "max_ms": float(max(v))}
 
 
-def run(name, reps, warmup, a=0.5, b=10.0, shape=1.1, scale=20.0):
+def run(name, reps, warmup, a=0.5, b=10.0, shape=1.1, scale=20.0, joint_iters=50):
     import torch
 
     I, K, per = time_tindic.shape(name)
@@ -59,6 +63,10 @@ def run(name, reps, warmup, a=0.5, b=10.0, shape=1.1, scale=20.0):
     ti = capi.TableIndicators(Kv, n, t, h, cust)
     gs = L.stb_groups_create(I, Kv.ctypes.data_as(capi.c_int_p), None, None, None, None, 0, 0, 3)
     assert gs, capi.last_error()
+    gj = L.stb_groups_create(I, Kv.ctypes.data_as(capi.c_int_p), None, None, None, None, 0, 0, 25)
+    assert gj, capi.last_error()
+    rect = (0.02, 0.97, 0.05, 500.0)
+    joint_info = {}
     Nh = np.full(I, per, dtype=np.uint32)
     bvec = np.full(I, b)
     koff = np.concatenate([[0], np.cumsum(Kv)]).astype(np.uint64)
@@ -84,6 +92,11 @@ def run(name, reps, warmup, a=0.5, b=10.0, shape=1.1, scale=20.0):
         ti.to_groups(gs, bvec)
         return capi.groups_samplea(gs, a)
 
+    def dev_joint():
+        r = ti.samplejoint(gj, rect, a, b, shape, scale, seed=99, sweep=sweep_no[0])
+        joint_info.update(stages=r["stages"], evals=r["evals"])
+        return r
+
     def host_b(apar=a):
         get()
         return L.sampleb(b, I, shape, scale, Nh.ctypes.data_as(u32p), Th.ctypes.data_as(u32p), apar, None, 1, 0)
@@ -97,6 +110,7 @@ def run(name, reps, warmup, a=0.5, b=10.0, shape=1.1, scale=20.0):
         "device_b": dev_b, "host_b": host_b, "device_a": dev_a, "host_a": host_a,
         "device_iter": lambda: (sweep(), dev_b(), dev_a()), "host_iter": lambda: (sweep(), host_b(), host_a()),
         "host_beta_loop": lambda: host_b(0.0),
+        "device_joint": dev_joint, "device_iter_joint": lambda: (sweep(), dev_joint()),
     }
     ms = {k: [] for k in cases}
     evals = {}
@@ -126,13 +140,43 @@ def run(name, reps, warmup, a=0.5, b=10.0, shape=1.1, scale=20.0):
         if r >= warmup:
             qdev.append(e0.elapsed_time(e1))
             qwall.append(dt)
-    res = {"shape": name, "I": I, "K": K, "customers_per_restaurant": per, "G": G, "a": a, "b": b, "reps": reps, "warmup": warmup,
+    # k_joint_terms alone
+    Td = torch.as_tensor(Th.view(np.int32), device="cuda")
+    get()
+    Td.copy_(torch.as_tensor(Th.view(np.int32)))
+    jt = {}
+    for dj in (24, 64):
+        av = 0.02 + 0.95 * (np.arange(dj) + 0.5) / dj
+        bv = np.exp(np.log(0.05) + np.log(1e4) * (np.arange(dj) + 0.5) / dj)
+        v = []
+        for r in range(warmup + reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            capi.joint_terms(av, bv, Td, Nd, stream=torch.cuda.current_stream())
+            e1.record()
+            torch.cuda.synchronize()
+            if r >= warmup:
+                v.append(e0.elapsed_time(e1))
+        jt["%dx%d" % (dj, dj)] = stats(v)
+    # a chain of sweep + joint: stages and acceptance with the state moving
+    ca, cb, acc, stg = a, b, 0, []
+    for it in range(joint_iters):
+        ti.sweep(ca, np.full(I, cb), 2026, it, 1)
+        r = ti.samplejoint(gj, rect, ca, cb, shape, scale, seed=2027, sweep=it)
+        ca, cb = r["a"], r["b"]
+        acc += r["accepted"]
+        stg.append(r["stages"])
+    res = {"shape": name, "joint_terms_device": jt, "joint_stages": joint_info,
+           "joint_chain": {"iterations": joint_iters, "accepted": acc, "stages_min": int(min(stg)), "stages_max": int(max(stg)),
+                           "stages_mean": float(np.mean(stg)), "a_last": ca, "b_last": cb}, "I": I, "K": K, "customers_per_restaurant": per, "G": G, "a": a, "b": b, "reps": reps, "warmup": warmup,
            "evaluations": evals, "q_kernel_device": stats(qdev), "q_call_wall": stats(qwall)}
     for k in cases:
         res[k] = stats(ms[k])
     res["device_b_round_trips_ms"] = res["device_b"]["median_ms"] - res["q_call_wall"]["median_ms"]
     ti.free()
     L.stb_groups_free(gs)
+    L.stb_groups_free(gj)
     L.stb_sampler_cache_clear()
     return res
 
@@ -142,11 +186,12 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--shapes", default="A,S1000")
+    ap.add_argument("--joint-iters", type=int, default=50)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     out = []
     for name in args.shapes.split(","):
-        r = run(name, args.reps, args.warmup)
+        r = run(name, args.reps, args.warmup, joint_iters=args.joint_iters)
         out.append(r)
         print(json.dumps(r), flush=True)
     if args.out:
