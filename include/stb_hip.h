@@ -177,6 +177,36 @@ int stb_sweep_S(const double *d_tables, uint64_t table_stride, const double *d_S
                 const uint16_t *d_t, uint64_t G, double *d_out, void *d_ws, size_t ws_bytes,
                 void *stream);
 
+/* ---- the slope of log S in the discount (fill_da.hip; additive: the reference's only derivative, S_approx_da of
+ * lib/sapprox.c:76-114, covers m <= 4 and is wrong at m = 4 -- DESIGN.md section 6) ----
+ * g(n, m) = d log S^n_{m,a} / da = -E / S with E^n_m = (n-1-m a) E^{n-1}_m + m S^{n-1}_m + E^{n-1}_{m-1}, E^1_1 = 0, walked
+ * next to S by the producer/consumer form (no waits between workgroups); one FP64 division a cell.
+ * stb_fill_dS: D slabs of g in exactly the S table's layout (stb_elems / stb_rowoff) and D vectors
+ * dS1[n-1] = d log S^n_1 / da = -sum_{k=1}^{n-1} 1 / (k - a) (a fixed summation order).  d_tables / d_S1: both NULL, or D
+ * slabs and vectors that receive log S as well, the bits of stb_fill_S(..., STB_FILL_PC).  Strides, bounds and discounts
+ * as for stb_fill_S (a = 0 allowed), refused the same way before anything is queued; D <= 64, N < 2^27.  The bits do not
+ * depend on D (they do on STB_FILL_P / STB_FILL_R, which move where a coefficient is formed anew, as in stb_fill_S).
+ * stb_lookup_dS: S_S's cases -- n == m: 0; m == 1: dS1; inside the bounds: the slab; where S_S is log 0 (m == 0, n < m,
+ * beyond the bounds): NaN, the slope of -inf.
+ * stb_sweep_dS: out[d] = sum over pairs with n > 1 of g_d(n, t), stb_sweep_S's gather and order on the g slabs (its
+ * workspace: stb_sweep_workspace_bytes); a set with a log-0 pair gives NaN for that discount.
+ * stb_restaurant_terms_da: out[d] = sum_i [T_i / x_d - (b_i / x_d^2) (psi(T_i + b_i/x_d) - psi(b_i/x_d))], the derivative
+ * of stb_restaurant_terms in x (workspace: stb_terms_workspace_bytes). */
+size_t stb_fill_dS_workspace_bytes(unsigned N, unsigned M, int D);
+int stb_fill_dS(const double *a_host, int D, unsigned N, unsigned M, double *d_gtables, uint64_t gtable_stride,
+                double *d_dS1, uint64_t ds1_stride, double *d_tables /* or NULL */, uint64_t table_stride,
+                double *d_S1 /* or NULL */, uint64_t s1_stride, void *d_ws, size_t ws_bytes, void *stream);
+/* the fill's constants, for tests that sit on its boundaries (any pointer may be NULL): rows per launch, owned and halo
+ * columns of a column block, rows between two barriers, rows of a renormalisation period at N rows */
+void stb_fill_dS_geometry(unsigned N, int *rows_per_launch, int *owned_cols, int *halo_cols, int *trip_rows, int *period_rows);
+int stb_lookup_dS(const double *d_gtable, const double *d_dS1, unsigned N, unsigned M, const uint32_t *d_n,
+                  const uint32_t *d_m, uint64_t G, double *d_out, void *stream);
+int stb_sweep_dS(const double *d_gtables, uint64_t gtable_stride, const double *d_dS1, uint64_t ds1_stride, int D,
+                 unsigned N, unsigned M, const uint32_t *d_n, const uint16_t *d_t, uint64_t G, double *d_out, void *d_ws,
+                 size_t ws_bytes, void *stream);
+int stb_restaurant_terms_da(const double *x_host, int D, const uint32_t *d_T, const double *d_bpar, uint64_t I,
+                            double *d_out, void *d_ws, size_t ws_bytes, void *stream);
+
 /* ---- K4: per-restaurant terms.
  * restaurant: out[d] = sum_i T_i*log(x_d) + lgamma(T_i + b_i/x_d) - lgamma(b_i/x_d)  (samplea.c:65-67)
  * bterms:     out[j] = -Q*x_j + (shape-1)*log(x_j) + sum_i (lgamma(T_i + x_j/apar) - lgamma(x_j/apar))
@@ -335,6 +365,28 @@ int stb_groups_aterms_tables(stb_groups_t *g, const double *x_host, int D, doubl
  * and the trace; the drop-in samplea() runs this same code on its kept set.  The set needs Dmax >= 3.  Returns the new
  * discount, or NaN with stb_last_error() set (a null set, a outside (0, 1), a failed evaluation): it never exits. */
 double stb_groups_samplea(stb_groups_t *g, double a, void *rng, int loops, int verbose);
+/* ---- gradient and mode of aterms in the discount (groups_da.hip) ----
+ * stb_groups_aterms_grad: val_out[d] = what stb_groups_aterms returns for the same call, bit for bit; grad_out[d] =
+ * d aterms / dx at x_d = stb_restaurant_terms_da + stb_sweep_dS over the set's pairs, from g tables private to the set
+ * (asked for on first need, sized by the set's bounds).  0 < x_d < 1, D <= Dmax; a set without pairs is refused; a log-0
+ * pair makes the gradient NaN (the value is -inf).  Non-zero return: stb_last_error() is set and nothing is written.
+ * stb_groups_modea: the maximum of aterms on [a_lo, a_hi] -- under samplea's flat prior the posterior mode of the
+ * discount.  k = min(Dmax, 8) gradients a round in ONE stb_groups_aterms_grad call: round 1 at k equally spaced points
+ * that include both bounds (gradient at a_lo <= 0: a_hat = a_lo, at_bound -1; at a_hi >= 0: a_hat = a_hi, at_bound +1),
+ * later rounds at k equally spaced interior points of the bracket; the bracket becomes the leftmost pair of neighbours
+ * with gradients (> 0, <= 0); rounds end at width <= tol, at rounds_max, or when the bracket no longer narrows.  a_hat is
+ * one secant step inside the last bracket.  A last call evaluates a_hat - delta, a_hat, a_hat + delta (delta: the last
+ * bracket's width -- tol at a bound -- cut to half the distance from a_hat to 0 and to 1): *curv = (g(a_hat + delta) -
+ * g(a_hat - delta)) / (2 delta) (may be NULL).  Host C, deterministic, no random numbers.  Needs Dmax >= 3,
+ * 0 < a_lo < a_hi < 1, tol > 0, rounds_max >= 1; refusals and failures (a NaN gradient) leave the outputs untouched. */
+typedef struct stb_modea_info {
+  int rounds, evals, at_bound;     /* bracketing rounds, gradient evaluations in all (the last three included), -1 / 0 / +1 */
+  double lo, hi, g_lo, g_hi;       /* the last bracket and the gradients at its ends (lo == hi at a bound) */
+  double grad, delta;              /* the gradient at a_hat, the step of the curvature's difference */
+} stb_modea_info_t;
+int stb_groups_aterms_grad(stb_groups_t *g, const double *x_host, int D, double *val_out, double *grad_out);
+int stb_groups_modea(stb_groups_t *g, double a_lo, double a_hi, double tol, int rounds_max, double *a_hat, double *curv,
+                     stb_modea_info_t *info);
 /* new per-restaurant totals T[I] and concentrations bpar[I] for the same pairs */
 int stb_groups_update_restaurants(stb_groups_t *g, const uint32_t *T, const double *bpar);
 /* NEW PAIRS for a set of the same shape (I restaurants, G = sum K pairs): what a caller whose counts change between

@@ -49,6 +49,12 @@ class JointOpts(C.Structure):
                 ("seed", C.c_uint64), ("sweep", C.c_uint64), ("flags", C.c_uint)]
 
 
+class ModeaInfo(C.Structure):
+    """stb_modea_info_t (include/stb_hip.h)"""
+    _fields_ = [("rounds", C.c_int), ("evals", C.c_int), ("at_bound", C.c_int), ("lo", C.c_double), ("hi", C.c_double),
+                ("g_lo", C.c_double), ("g_hi", C.c_double), ("grad", C.c_double), ("delta", C.c_double)]
+
+
 class JointInfo(C.Structure):
     """stb_joint_info_t (include/stb_hip.h)"""
     _fields_ = [("stages", C.c_int), ("accepted", C.c_int), ("evals", C.c_int), ("stage_pick", C.c_int),
@@ -219,6 +225,15 @@ def lib() -> C.CDLL:
     sig("stb_groups_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
     sig("stb_tcounts_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
     sig("stb_tindic_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
+    # ---- the slope of log S in the discount
+    sig("stb_fill_dS_workspace_bytes", sz, [u, u, i])
+    sig("stb_fill_dS", i, [c_double_p, i, u, u, vp, u64, vp, u64, vp, u64, vp, u64, vp, sz, vp])
+    sig("stb_fill_dS_geometry", None, [u, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p])
+    sig("stb_lookup_dS", i, [vp, vp, u, u, vp, vp, u64, vp, vp])
+    sig("stb_sweep_dS", i, [vp, u64, vp, u64, i, u, u, vp, vp, u64, vp, vp, sz, vp])
+    sig("stb_restaurant_terms_da", i, [c_double_p, i, vp, vp, u64, vp, vp, sz, vp])
+    sig("stb_groups_aterms_grad", i, [vp, c_double_p, i, c_double_p, c_double_p])
+    sig("stb_groups_modea", i, [vp, d, d, d, i, c_double_p, c_double_p, C.POINTER(ModeaInfo)])
     # optional entry points (present once the sampler host code is linked in)
     for name, res, args in (
         ("arms_simple", i, [i, c_double_p, c_double_p, LOGDENS, vp, i, c_double_p, c_double_p]),
@@ -414,6 +429,54 @@ class DeviceTables:
         check(self.L.stb_lookup_S(self.tables[d].data_ptr(), self.S1[d].data_ptr(), self.N, self.M,
                                   n.data_ptr(), m.data_ptr(), n.shape[0], out.data_ptr(),
                                   stream_ptr(stream)))
+        return out.cpu().numpy()
+
+
+class DeviceSlopeTables:
+    """D tables of g = d log S / da and their dS1 vectors (stb_fill_dS); with_S: the log S slabs of the same call too"""
+
+    def __init__(self, N: int, M: int, D: int = 1, device="cuda", with_S: bool = False):
+        torch = _torch()
+        self.L = lib()
+        self.N, self.M, self.D = N, M, D
+        self.cells = int(self.L.stb_cells(N, M))
+        self.elems = int(self.L.stb_elems(N, M))
+        self.stride = max(32, (self.elems + 31) // 32 * 32)
+        self.g = torch.full((D, self.stride), float("nan"), dtype=torch.float64, device=device)
+        self.dS1 = torch.empty((D, N), dtype=torch.float64, device=device)
+        self.tables = torch.empty((D, self.stride), dtype=torch.float64, device=device) if with_S else None
+        self.S1 = torch.empty((D, N), dtype=torch.float64, device=device) if with_S else None
+        self.ws_bytes = int(self.L.stb_fill_dS_workspace_bytes(N, M, D))
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+
+    def fill(self, a, stream=None):
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(a, dtype=np.float64)))
+        assert a.shape[0] == self.D
+        self.a = a
+        check(self.L.stb_fill_dS(dp(a), self.D, self.N, self.M, self.g.data_ptr(), self.stride, self.dS1.data_ptr(), self.N,
+                                 self.tables.data_ptr() if self.tables is not None else None, self.stride,
+                                 self.S1.data_ptr() if self.S1 is not None else None, self.N,
+                                 self.ws.data_ptr(), self.ws_bytes, stream_ptr(stream)))
+
+    def packed_host(self, d=0, which="g"):
+        """the slab without row padding, in the packed order of the truth (numpy)"""
+        t = (self.g if which == "g" else self.tables)[d].cpu().numpy()
+        out = np.empty(self.cells, dtype=np.float64)
+        pos = 0
+        for n in range(3, self.N + 1):
+            ln = min(n - 2, self.M - 1)
+            o = int(self.L.stb_rowoff(n, self.M))
+            out[pos:pos + ln] = t[o:o + ln]
+            pos += ln
+        return out
+
+    def lookup(self, n, m, d=0, stream=None):
+        torch = _torch()
+        n = torch.as_tensor(np.asarray(n, dtype=np.uint32).view(np.int32), device=self.g.device)
+        m = torch.as_tensor(np.asarray(m, dtype=np.uint32).view(np.int32), device=self.g.device)
+        out = torch.empty(n.shape[0], dtype=torch.float64, device=self.g.device)
+        check(self.L.stb_lookup_dS(self.g[d].data_ptr(), self.dS1[d].data_ptr(), self.N, self.M, n.data_ptr(), m.data_ptr(),
+                                   n.shape[0], out.data_ptr(), stream_ptr(stream)))
         return out.cpu().numpy()
 
 
@@ -615,6 +678,23 @@ def groups_ssum(groups, x):
     out = np.zeros(x.shape[0], dtype=np.float64)
     check(lib().stb_groups_ssum(groups, dp(x), int(x.shape[0]), dp(out)))
     return out
+
+
+def groups_aterms_grad(groups, x):
+    """stb_groups_aterms_grad on a group-set handle: (aterms(x_d), d aterms / dx at x_d)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    val = np.zeros(x.shape[0], dtype=np.float64)
+    grad = np.zeros(x.shape[0], dtype=np.float64)
+    check(lib().stb_groups_aterms_grad(groups, dp(x), int(x.shape[0]), dp(val), dp(grad)))
+    return val, grad
+
+
+def groups_modea(groups, a_lo, a_hi, tol=1e-9, rounds_max=32):
+    """stb_groups_modea on a group-set handle: (a_hat, curvature, ModeaInfo)"""
+    a_hat, curv, info = C.c_double(float("nan")), C.c_double(float("nan")), ModeaInfo()
+    check(lib().stb_groups_modea(groups, float(a_lo), float(a_hi), float(tol), int(rounds_max), C.byref(a_hat), C.byref(curv),
+                                 C.byref(info)))
+    return a_hat.value, curv.value, info
 
 
 def joint_terms(a, b, T, N, stream=None):

@@ -111,6 +111,13 @@ struct stb_groups {
   size_t ent_cap[STB_NLISTS];  // entries the list buffers of a layout hold (0: sized exactly by the sort-based builder)
   size_t dense_cap[STB_NLISTS];
   unsigned *d_tnw[STB_NLISTS], *d_toff[STB_NLISTS];  // [3] .. [5]: words per group and first word of every tile (the dense layout), kept
+  // ---- the gradient in the discount (groups_da.hip): Dmax tables of g = d log S / da and their dS1 vectors, private to the
+  // set, asked for when the first stb_groups_aterms_grad comes and sized by the bounds they were made for (da_N, da_M)
+  double *d_gtab, *d_dS1g, *d_gout;  // d_gout: [2][Dmax] pair sums, restaurant terms
+  void *d_ws_da, *d_ws_dasweep;
+  size_t ws_da, ws_dasweep;
+  uint64_t da_stride, da_G;
+  unsigned da_N, da_M;
 };
 
 // the list layout of the grid form with C columns per lane, and back; a position is row << stb_pos_bits(C) | element of the wave

@@ -76,7 +76,8 @@ extern "C" void stb_groups_free(stb_groups_t *g) {
   if (!g) return;
   const int prev_dev = stb_device_enter(g->dev);
   std::vector<void *> ptrs = {g->d_n, g->d_T, g->d_t, g->d_bpar, g->d_tables, g->d_S1, g->d_out, g->d_ws_fill, g->d_ws_sweep, g->d_ws_terms,
-                              g->d_cnt, g->d_n2, g->d_t2, g->d_dotp, g->d_slab, g->d_icnt, g->d_ninf, g->d_scan_tmp};
+                              g->d_cnt, g->d_n2, g->d_t2, g->d_dotp, g->d_slab, g->d_icnt, g->d_ninf, g->d_scan_tmp,
+                              g->d_gtab, g->d_dS1g, g->d_gout, g->d_ws_da, g->d_ws_dasweep};
   for (int w = 0; w < STB_NLISTS; w++)
     for (void *q : {(void *)g->d_item_ptr[w], (void *)g->d_ent_pos[w], (void *)g->d_ent_cnt[w], (void *)g->d_tile_off[w], (void *)g->d_dense[w],
                     (void *)g->d_tinfo[w], (void *)g->d_jobs[w], (void *)g->d_tjob[w], (void *)g->d_tnw[w], (void *)g->d_toff[w]})

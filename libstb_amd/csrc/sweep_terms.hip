@@ -807,3 +807,147 @@ extern "C" int stb_hist_aterms2(stb_hist_t *h, const double *x_host, int D, doub
   stb_device_leave(prev);
   return rc;
 }
+
+// ------------------------------------------------------------------------------------------------
+// the slope of log S in the discount: look-ups, the gather-sum and the restaurant terms' derivative
+// (tables of g = d log S / da and the dS1 vector from stb_fill_dS, fill_da.hip)
+
+// S_S's cases (dev_S_S); where S_S is log 0 the slope is not a number
+__global__ void k_lookup_dS(const double *gtable, const double *dS1, unsigned N, unsigned M, const uint32_t *n, const uint32_t *m, uint64_t G,
+                            double *out) {
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  for (; g < G; g += step) {
+    const unsigned nn = n[g], mm = m[g];
+    double r;
+    if (nn == mm) r = 0.0;
+    else if (mm == 1) r = (nn >= 1 && nn <= N) ? dS1[nn - 1] : nan;
+    else if (nn < mm || mm == 0 || mm > M || nn > N) r = nan;
+    else r = gtable[stb_row_offset(nn, M) + (mm - 2)];
+    out[g] = r;
+  }
+}
+
+extern "C" int stb_lookup_dS(const double *d_gtable, const double *d_dS1, unsigned N, unsigned M, const uint32_t *d_n, const uint32_t *d_m,
+                             uint64_t G, double *d_out, void *stream) {
+  STB_ENTRY;
+  if (G == 0) return 0;
+  if (!d_gtable || !d_dS1 || !d_n || !d_m || !d_out) return stb_fail("stb_lookup_dS: null pointer");
+  uint64_t blocks = (G + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k_lookup_dS, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_gtable, d_dS1, N, M, d_n, d_m, G, d_out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// The gather-sum is k_sweep_partial itself on the g slab and dS1: the same cases, the same fixed order.  A pair whose S_S
+// is log 0 enters it as -inf; every g is finite, so a sum of -inf says exactly "a log-0 pair", and becomes NaN here.
+__global__ void k_inf_to_nan(double *out, int D) {
+  const int d = threadIdx.x;
+  if (d < D && isinf(out[d])) out[d] = __longlong_as_double(0x7ff8000000000000ll);
+}
+
+extern "C" int stb_sweep_dS(const double *d_gtables, uint64_t gtable_stride, const double *d_dS1, uint64_t ds1_stride, int D, unsigned N,
+                            unsigned M, const uint32_t *d_n, const uint16_t *d_t, uint64_t G, double *d_out, void *d_ws, size_t ws_bytes,
+                            void *stream) {
+  STB_ENTRY;
+  hipStream_t st = (hipStream_t)stream;
+  if (D < 1 || D > STB_TERMS_DMAX) return stb_fail("stb_sweep_dS: D=%d (1..%d)", D, STB_TERMS_DMAX);
+  if (!d_out || (G && (!d_gtables || !d_dS1 || !d_n || !d_t || !d_ws))) return stb_fail("stb_sweep_dS: null pointer");
+  if (ws_bytes < stb_sweep_workspace_bytes(G, D)) return stb_fail("stb_sweep_dS: workspace too small");
+  const int nb = sweep_blocks(G);
+  if (nb == 0) {
+    HIPCHK(hipMemsetAsync(d_out, 0, sizeof(double) * D, st));
+    return 0;
+  }
+  dd_t *partial = (dd_t *)d_ws;
+  dim3 grid(nb, (D + STB_SWEEP_DT - 1) / STB_SWEEP_DT);
+  hipLaunchKernelGGL(k_sweep_partial, grid, dim3(256), 0, st, d_gtables, gtable_stride, d_dS1, ds1_stride, D, N, M, d_n, d_t, G, partial, nb);
+  hipLaunchKernelGGL(k_reduce_final, dim3(D), dim3(256), 0, st, partial, nb, d_out, (const double *)nullptr);
+  hipLaunchKernelGGL(k_inf_to_nan, dim3(1), dim3(64), 0, st, d_out, D);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// d/dx of the restaurant terms: sum_i [T_i / x - (b_i / x^2) (psi(T_i + z_i) - psi(z_i))], z_i = b_i / x.
+// psi(T + z) - psi(z), T >= 1:
+//  * T <= STB_PSI_CUT (64): the finite sum sum_{k=0}^{T-1} 1 / (z + k), ascending k from 0: T divisions, T additions.
+//  * beyond: with s = max(0, ceil(16 - z)) (so z + s >= 16; T + z > 64 already) and
+//        A(y) = -1/(2y) - 1/(12 y^2) + 1/(120 y^4) - 1/(252 y^6) + 1/(240 y^8) - 1/(132 y^10) + 691/(32760 y^12),
+//    psi(y) = log y + A(y) - R(y), 0 < R(y) < 1 / (12 y^14) <= 1.2e-18 at y >= 16 (the series alternates: the truncation
+//    error is below the first term left out), the difference is
+//        log1p((T - s) / (z + s)) + (A(T + z) - A(z + s)) + sum_{k=0}^{s-1} 1 / (z + k)
+//    -- the two logs as ONE log1p, so no cancellation between them; truncation error below 2.4e-18 absolute.
+// Fixed reduction order (k_terms_partial's chunks, block_reduce_dd, k_reduce_final), no contraction.
+#define STB_PSI_CUT 64
+__device__ __forceinline__ double psi_tail(double y) {
+#pragma clang fp contract(off)
+  const double r = 1.0 / y, r2 = r * r;
+  double p = 691.0 / 32760.0;
+  p = p * r2 - 1.0 / 132.0;
+  p = p * r2 + 1.0 / 240.0;
+  p = p * r2 - 1.0 / 252.0;
+  p = p * r2 + 1.0 / 120.0;
+  p = p * r2 - 1.0 / 12.0;
+  return p * r2 - 0.5 * r;
+}
+__device__ __forceinline__ double psi_diff(unsigned T, double z) {
+#pragma clang fp contract(off)
+  if (T == 0) return 0.0;
+  if (T <= STB_PSI_CUT) {
+    double acc = 0.0;
+    for (unsigned k = 0; k < T; k++) acc += 1.0 / (z + (double)k);
+    return acc;
+  }
+  const int s = z >= 16.0 ? 0 : (int)ceil(16.0 - z);
+  double acc = 0.0;
+  for (int k = 0; k < s; k++) acc += 1.0 / (z + (double)k);
+  const double y0 = z + (double)s, y1 = (double)T + z;
+  const double L = log1p(((double)T - (double)s) / y0);
+  return (L + (psi_tail(y1) - psi_tail(y0))) + acc;
+}
+
+__global__ __launch_bounds__(256) void k_terms_da_partial(terms_args A, const uint32_t *T, const double *bpar, uint64_t I, dd_t *partial, int nb) {
+#pragma clang fp contract(off)
+  __shared__ dd_t lds[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * STB_TERMS_CHUNK;
+  const uint64_t i1 = (i0 + STB_TERMS_CHUNK < I) ? i0 + STB_TERMS_CHUNK : I;
+  const int d = blockIdx.y;
+  const double x = A.x[d], x2 = x * x;
+  dd_t acc{0.0, 0.0};
+  for (uint64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+    const unsigned Ti = T[i];
+    const double b = bpar[i];
+    const double term = (double)Ti / x - (b / x2) * psi_diff(Ti, b / x);
+    dd_add(acc, term);
+  }
+  dd_t r = block_reduce_dd(acc, lds);
+  if (threadIdx.x == 0) partial[(size_t)d * nb + blockIdx.x] = r;
+}
+
+extern "C" int stb_restaurant_terms_da(const double *x_host, int D, const uint32_t *d_T, const double *d_bpar, uint64_t I, double *d_out,
+                                       void *d_ws, size_t ws_bytes, void *stream) {
+  STB_ENTRY;
+  hipStream_t st = (hipStream_t)stream;
+  if (D < 1 || D > STB_TERMS_DMAX) return stb_fail("stb_restaurant_terms_da: D=%d (max %d)", D, STB_TERMS_DMAX);
+  if (!x_host || !d_out || !d_ws || (I && (!d_T || !d_bpar))) return stb_fail("stb_restaurant_terms_da: null pointer");
+  if (ws_bytes < stb_terms_workspace_bytes(I, D)) return stb_fail("stb_restaurant_terms_da: workspace too small");
+  terms_args A;
+  memset(&A, 0, sizeof(A));
+  A.D = D;
+  for (int d = 0; d < D; d++) {
+    if (!(x_host[d] > 0)) return stb_fail("stb_restaurant_terms_da: x=%g", x_host[d]);
+    A.x[d] = x_host[d];
+  }
+  const int nb = terms_blocks(I);
+  if (nb == 0) {
+    HIPCHK(hipMemsetAsync(d_out, 0, sizeof(double) * D, st));
+    return 0;
+  }
+  dd_t *partial = (dd_t *)((char *)d_ws + stb_align_up((size_t)D * sizeof(double), 256));
+  hipLaunchKernelGGL(k_terms_da_partial, dim3(nb, D), dim3(256), 0, st, A, d_T, d_bpar, I, partial, nb);
+  hipLaunchKernelGGL(k_reduce_final, dim3(D), dim3(256), 0, st, partial, nb, d_out, (const double *)nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
