@@ -18,10 +18,12 @@
  *      (the indicator step then uses the exact prior ratio t/(n-t), see stb_hip.h, and counter-based uniforms).
  *   7. with -j the device loop draws a and b JOINTLY instead: stb_tindic_sweep -> stb_tindic_samplejoint, an exact
  *      independence Metropolis-Hastings step from nested grids on [0.02, 0.97] x [0.05, 500] (stb_hip.h).
+ *   8. with -L the device loop (-d or -j) prints the log joint probability of the state after every iteration
+ *      (stb_tindic_logjoint, the table-indicator representation): one launch on the resident counts, 64 bytes back.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L]
  */
 #include <math.h>
 #include <stdio.h>
@@ -37,10 +39,10 @@
 #define DISHES 50
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:dj")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djL")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -51,6 +53,7 @@ int main(int argc, char **argv) {
     else if (c == 's') seed = atol(optarg);
     else if (c == 'd') ondev = 1;
     else if (c == 'j') ondev = joint = 1;
+    else if (c == 'L') showlj = 1;
     else return 2;
   }
   srand48(seed);
@@ -149,6 +152,13 @@ int main(int argc, char **argv) {
           bsum += b;
           kept++;
         }
+      }
+      if (showlj) {
+        double lj;
+        stb_logjoint_info_t li;
+        if (stb_tindic_logjoint(ti, a, bvec, STB_LJ_INDICATORS, &lj, NULL, &li)) yaps_quit("stb_tindic_logjoint: %s\n", stb_last_error());
+        printf("iteration %d: log joint %.6f (pairs %.6f, base %.6f, restaurants %.6f, indicators %.6f) a=%.4f b=%.3f\n", it, lj,
+               li.pairs, li.base, li.restaurants, li.binom, a, b);
       }
     }
     if (stb_tindic_get(ti, tf, T)) yaps_quit("stb_tindic_get: %s\n", stb_last_error());

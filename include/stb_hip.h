@@ -561,6 +561,61 @@ double stb_tindic_sampleb(stb_tindic_t *s, double b_in, double shape, double sca
                           int loops, int verbose, uint64_t seed, uint64_t sweep);
 void stb_tindic_free(stb_tindic_t *s);
 
+/* ---- the log joint probability of a sampler state (logjoint.hip): what a Gibbs chain is watched by, what runs are
+ * compared on, what annealed and bridge estimates of the evidence feed on.  Pairs, h, b_i and a as for stb_tcounts above;
+ * T_i = sum_k t_ik, N_i = sum_k n_ik:
+ *     log p(n, t | a, b, h) = sum_i L_i,     L_i = P_i + H_i + R_i
+ *     P_i = sum_k S_S_a(n_ik, t_ik)            pairs with n >= 1 (stb_lookup_S's semantics; n = 0, t = 0 contributes 0)
+ *     H_i = sum_k t_ik log h_ik                0 when h is NULL
+ *     R_i = log (b_i|a)_{T_i} - log (b_i)_{N_i}
+ *         = T_i log a + [lgamma(T_i + b_i/a) - lgamma(b_i/a)] - [lgamma(b_i + N_i) - lgamma(b_i)]      a > 0
+ *         = T_i log b_i - [lgamma(b_i + N_i) - lgamma(b_i)]                                             a = 0
+ *         = 0                                                                                           N_i = 0
+ * This is the table-count representation, the law stb_sample_tcounts draws from: changing one pair's t from tau to tau'
+ * changes the sum by log w(tau') - log w(tau), w as written there.  With STB_LJ_INDICATORS every pair with n >= 1 also
+ * contributes -log C(n - 1, t - 1): the table-indicator representation, one indicator of a pair held at 1 and the other
+ * n - 1 uniform given t, whose Gibbs step is stb_sample_tindic with the exact ratio t / (n - t) = C(n-1, t-1) / C(n-1, t)
+ * (with C(n, t) the ratio would be (t + 1) / (n - t), which is not that step's).  lgamma is log |Gamma|: for -a < b_i < 0 (allowed when a > 0) Gamma(b_i/a) and Gamma(b_i) are both
+ * negative, Gamma(T_i + b_i/a) and Gamma(b_i + N_i) both positive (b_i + N_i and b_i lie on opposite sides of zero exactly
+ * when T_i + b_i/a and b_i/a do, and for b_i > -a > -1, N_i >= 1 no second sign change can happen), so the signs cancel and
+ * the difference of the log |Gamma| values is the logarithm of a positive quotient.  b_i = 0 (a > 0) takes the limit.
+ * One pass over the pairs, one table gather a pair; every sum in a fixed association (logjoint.hip's header; DESIGN.md
+ * section 6), so the bits of every output depend on neither grid nor workgroup size (STB_LOGJOINT_WAVES = 1, 2, 4 or 8).
+ *   impossible  pairs whose S_S is log 0 (t = 0 with n > 0, or t > n) or whose h is not positive and finite: the
+ *               restaurant's L_i, the component (pairs, or base for h) and the total are -inf.  No NaN is ever produced
+ *               (for b_i > -a, which the raw layer trusts as the sweeps do).
+ *   outside     pairs the table cannot answer (n > N, or 1 < t < n with t > M or with no table): left out of the sums, as
+ *               stb_sample_partition's cnt[0].  They still count in T_i and N_i.
+ *   t_mismatch  restaurants with d_T[i] != sum_k t_ik (d_T given): a free check of the sweeps' invariant.  The kernel's
+ *               own integer sum is the one used.
+ * Raw layer: d_table / d_S1 one slab of stb_fill_S for `a` with bounds (N, M); either may be NULL when no pair has
+ * min(n, M) >= 2 (stb_sample_tcounts' rule), and S^n_1 is then evaluated as the fill does, lgamma(n - a) - lgamma(1 - a).
+ * d_Li: NULL, or I doubles on the device.  One launch, one wait; *total_host and *info (may be NULL) arrive through
+ * pinned memory, as stb_sample_logq's Q.  I = 0 gives 0.  Refused before anything is queued, with stb_last_error() set: a
+ * outside [0, 1), unknown flag bits, a null koff, n or t, I < 0.
+ * Object layer: queued behind the object's sweeps on its stream; bpar (host [I]) is checked as by _sweep; neither t nor
+ * T is written and a failure leaves the state as it was; Li_host (may be NULL) receives the I values L_i.
+ * stb_tcounts_logjoint reads the object's S table, refilled when `a` differs from the table's, as in _sweep.
+ * stb_tindic_logjoint needs an S slab of its own, the object holding only a V table: same bounds as the V table, taken
+ * from the library's buffer cache on first use, filled by stb_fill_S and checked (stb_fill_status), refilled only when `a`
+ * changes, given back when the object is freed.  It costs what the V table costs once more -- 8 stb_elems(N, M) bytes
+ * plus 8 N for S^n_1 and the fill's workspace (stb_fill_workspace_bytes(N, M, 1)): 0.7 MB at max n = 200, M = 200.
+ * Objects without a table (all n <= 1, or M = 1) work and read none. */
+#define STB_LJ_INDICATORS 1u
+typedef struct stb_logjoint_info {
+  double pairs, base, restaurants, binom;      /* sum P_i, sum H_i, sum R_i, -sum log C(n-1, t-1) (0 without the flag); total = their sum */
+  uint64_t outside, impossible, t_mismatch;
+} stb_logjoint_info_t;
+int stb_logjoint(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a,
+                 const double *d_bpar, int I, const uint64_t *d_koff, const uint32_t *d_n,
+                 const uint16_t *d_t, const uint32_t *d_T /* or NULL */, const double *d_h /* or NULL */,
+                 unsigned flags, double *d_Li /* NULL, or I doubles */, double *total_host,
+                 stb_logjoint_info_t *info /* or NULL */, void *stream);
+int stb_tcounts_logjoint(stb_tcounts_t *s, double a, const double *bpar, unsigned flags, double *total, double *Li_host,
+                         stb_logjoint_info_t *info);
+int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total, double *Li_host,
+                        stb_logjoint_info_t *info);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

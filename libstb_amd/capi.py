@@ -55,6 +55,15 @@ class ModeaInfo(C.Structure):
                 ("g_lo", C.c_double), ("g_hi", C.c_double), ("grad", C.c_double), ("delta", C.c_double)]
 
 
+LJ_INDICATORS = 1  # stb_logjoint flag: the table-indicator representation (every pair also contributes -log C(n-1, t-1))
+
+
+class LogJointInfo(C.Structure):
+    """stb_logjoint_info_t (include/stb_hip.h)"""
+    _fields_ = [("pairs", C.c_double), ("base", C.c_double), ("restaurants", C.c_double), ("binom", C.c_double),
+                ("outside", C.c_uint64), ("impossible", C.c_uint64), ("t_mismatch", C.c_uint64)]
+
+
 class JointInfo(C.Structure):
     """stb_joint_info_t (include/stb_hip.h)"""
     _fields_ = [("stages", C.c_int), ("accepted", C.c_int), ("evals", C.c_int), ("stage_pick", C.c_int),
@@ -225,6 +234,11 @@ def lib() -> C.CDLL:
     sig("stb_groups_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
     sig("stb_tcounts_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
     sig("stb_tindic_samplejoint", i, [vp, vp, jo, d, d, c_double_p, c_double_p, ji])
+    # ---- the log joint of a sampler state
+    lji = C.POINTER(LogJointInfo)
+    sig("stb_logjoint", i, [vp, vp, u, u, d, vp, i, vp, vp, vp, vp, vp, u, vp, c_double_p, lji, vp])
+    sig("stb_tcounts_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
+    sig("stb_tindic_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
     # ---- the slope of log S in the discount
     sig("stb_fill_dS_workspace_bytes", sz, [u, u, i])
     sig("stb_fill_dS", i, [c_double_p, i, u, u, vp, u64, vp, u64, vp, u64, vp, u64, vp, sz, vp])
@@ -614,6 +628,16 @@ class TableCounts:
         return _joint_call(self.L.stb_tcounts_samplejoint, (self.h, groups), rect, a, b, shape, scale, seed, sweep, D, J,
                            keep_L)
 
+    def logjoint(self, a, bpar, indicators: bool = False, want_Li: bool = True):
+        """(total, L_i[I] or None, LogJointInfo): the log joint probability of the current state, behind the queued sweeps
+        (stb_tcounts_logjoint); indicators: the table-indicator representation"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        Li = np.zeros(self.I, dtype=np.float64) if want_Li else None
+        tot, info = C.c_double(0.0), LogJointInfo()
+        check(self.L.stb_tcounts_logjoint(self.h, float(a), dp(bpar), LJ_INDICATORS if indicators else 0, C.byref(tot),
+              None if Li is None else dp(Li), C.byref(info)))
+        return tot.value, Li, info
+
     def partition(self, a, hist, bpar, seed: int, sweep: int):
         """stage 1 of the S-free discount step on the current pairs, queued: the table-size histogram into `hist` (a
         Histogram with I restaurants and S > the largest n), with T and bpar (stb_tcounts_partition)"""
@@ -641,6 +665,28 @@ def sample_tcounts_window(tabs, a, bpar, koff, n, t, T, h, window: int, seed: in
                                           bpar.data_ptr(), int(koff.shape[0]) - 1, koff.data_ptr(), n.data_ptr(),
                                           t.data_ptr(), T.data_ptr(), None if h is None else h.data_ptr(), int(window),
                                           TC_REF_WINDOW if ref else 0, seed, sweep, stream_ptr(stream)))
+
+
+def logjoint(tabs, a, bpar, koff, n, t, T=None, h=None, indicators: bool = False, want_Li: bool = True, stream=None,
+             flags=None):
+    """stb_logjoint on device arrays: tabs a DeviceTables filled for `a` (its first slab and its bounds N, M are used), a
+    pair (N, M) of bounds alone (no table: no pair may need one), koff (int64 [I+1]), n (int32), t (int16), T (int32, or
+    None), bpar and h (float64; h None: all 1) torch tensors on the device.  Returns (total, L_i as a float64 device
+    tensor or None, LogJointInfo)."""
+    torch = _torch()
+    I = int(koff.shape[0]) - 1
+    if isinstance(tabs, tuple):
+        tp, sp, N, M = None, None, int(tabs[0]), int(tabs[1])
+    else:
+        tp, sp, N, M = tabs.tables.data_ptr(), tabs.S1.data_ptr(), tabs.N, tabs.M
+    Li = torch.empty(max(I, 1), dtype=torch.float64, device=koff.device)[:I] if want_Li else None
+    tot, info = C.c_double(0.0), LogJointInfo()
+    fl = (LJ_INDICATORS if indicators else 0) if flags is None else int(flags)
+    check(lib().stb_logjoint(tp, sp, N, M, float(a), None if bpar is None else bpar.data_ptr(), I, koff.data_ptr(),
+                             n.data_ptr(), t.data_ptr(), None if T is None else T.data_ptr(),
+                             None if h is None else h.data_ptr(), fl, None if Li is None else Li.data_ptr(), C.byref(tot),
+                             C.byref(info), stream_ptr(stream)))
+    return tot.value, Li, info
 
 
 def sample_logq(b, scale, N, seed: int, sweep: int, want_L: bool = True, stream=None):
@@ -888,6 +934,16 @@ class TableIndicators:
         (stb_tindic_samplejoint); see groups_samplejoint"""
         return _joint_call(self.L.stb_tindic_samplejoint, (self.h, groups), rect, a, b, shape, scale, seed, sweep, D, J,
                            keep_L)
+
+    def logjoint(self, a, bpar, indicators: bool = False, want_Li: bool = True):
+        """(total, L_i[I] or None, LogJointInfo): the log joint probability of the current state, behind the queued sweeps
+        (stb_tindic_logjoint); indicators: the table-indicator representation"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        Li = np.zeros(self.I, dtype=np.float64) if want_Li else None
+        tot, info = C.c_double(0.0), LogJointInfo()
+        check(self.L.stb_tindic_logjoint(self.h, float(a), dp(bpar), LJ_INDICATORS if indicators else 0, C.byref(tot),
+              None if Li is None else dp(Li), C.byref(info)))
+        return tot.value, Li, info
 
     def free(self):
         if self.h:

@@ -1,0 +1,26 @@
+/* logjoint.h -- private: what the object layers (tcounts.hip, tindic.hip) and the samplers' cache need of
+ * logjoint.hip, beyond include/stb_hip.h. */
+#ifndef STB_LOGJOINT_H
+#define STB_LOGJOINT_H
+#include <stdint.h>
+#include "../../include/stb_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* frees the calling thread's block sums, counters and result words (stb_sampler_cache_clear) */
+void stb_lj_release(void);
+#ifdef __cplusplus
+}
+#endif
+
+#if defined(__HIPCC__)
+/* the checks stb_logjoint and the objects' calls share (0, or 1 with stb_last_error() set) */
+int stb_lj_check(double a, unsigned flags, int I, const char *who);
+/* the launch on st, the copy of d_Li to Li_host (when both are given) and the wait; arguments checked by the caller */
+int stb_lj_run(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
+               const uint64_t *d_koff, const uint32_t *d_n, const uint16_t *d_t, const uint32_t *d_T, const double *d_h,
+               unsigned flags, double *d_Li, double *Li_host, double *total_host, stb_logjoint_info_t *info, hipStream_t st,
+               const char *who);
+#endif
+#endif

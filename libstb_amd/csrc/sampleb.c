@@ -20,6 +20,7 @@
 #include "sampler_trace.h"
 #include "hyperq.h"
 #include "hyperj.h"
+#include "logjoint.h"
 
 #define NPRE 3 /* abscissae ARMS is known to ask for first (lib/arms.c:117-119) */
 
@@ -67,6 +68,7 @@ void stb_sampleb_cache_clear(void) {
   kept_bdev = NULL;
   stb_hq_release();
   stb_hj_release();
+  stb_lj_release();
 }
 
 static int use_slice(void) {

@@ -30,6 +30,7 @@
 #include "tcounts.h"
 #include "hyperq.h"
 #include "hyperj.h"
+#include "logjoint.h"
 
 #define STB_TC_CAP 4096      // tau values a workgroup keeps in LDS (32 KB); longer rows recompute
 #define STB_TC_MAXWAVES 16
@@ -580,4 +581,30 @@ extern "C" int stb_tcounts_samplejoint(stb_tcounts_t *s, stb_groups_t *g, const 
   if (!s || !g) return stb_fail("stb_tcounts_samplejoint: null object");
   if (stb_tcounts_to_groups(s, g, nullptr)) return 1;
   return stb_hj_samplejoint(g, s->d_N, nullptr, opts, a_in, b_in, a_out, b_out, info, "stb_tcounts_samplejoint");
+}
+
+// the log joint of the object's state (logjoint.hip) from its own S table, queued behind its sweeps; t and T are not
+// written.  Objects without a table read none: S^n_1 (M = 1) is evaluated in place, as the fill would.
+extern "C" int stb_tcounts_logjoint(stb_tcounts_t *s, double a, const double *bpar, unsigned flags, double *total,
+                                    double *Li_host, stb_logjoint_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tcounts_logjoint";
+  if (!s) return stb_fail("%s: null object", who);
+  if (stb_lj_check(a, flags, s->I, who)) return 1;
+  if (!total) return stb_fail("%s: total is required", who);
+  if (tc_check_sweep(s, a, bpar, 0, who)) return 1;
+  const int prev = stb_device_enter(s->dev);
+  int rc = tc_stage(s, a, bpar, who);
+  double *d_Li = nullptr;
+  if (!rc && Li_host && stb_pool_malloc((void **)&d_Li, sizeof(double) * (size_t)s->I) != hipSuccess)
+    rc = stb_fail("%s: out of device memory for %d values", who, s->I);
+  if (!rc)
+    rc = stb_lj_run(s->d_table, s->d_S1, s->N, s->M, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, flags, d_Li,
+                    Li_host, total, info, s->st, who);
+  if (d_Li) {
+    if (rc) (void)hipStreamSynchronize(s->st);  // (the cache may hand the buffer on at once)
+    stb_pool_free(d_Li);
+  }
+  stb_device_leave(prev);
+  return rc;
 }

@@ -25,6 +25,7 @@
 #include "groups.h"
 #include "hyperq.h"
 #include "hyperj.h"
+#include "logjoint.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
 #define STB_TI_REF_ODDS_FLAG 1u
@@ -292,10 +293,19 @@ struct stb_tindic {
   void *d_ws;
   size_t ws_bytes;
   double a_filled;      // the discount the table holds (NaN: none yet)
+  // the S slab of stb_tindic_logjoint (bounds N, M as the V table's): from the buffer cache on first use
+  double *d_stab, *d_sS1;
+  uint64_t sstride;
+  void *d_sws;
+  size_t sws_bytes;
+  double a_sfilled;     // the discount the S slab holds (NaN: none yet)
   hipStream_t st;
 };
 
 static void ti_release(stb_tindic_t *s) {
+  void *pooled[] = {s->d_stab, s->d_sS1, s->d_sws};
+  for (void *p : pooled)
+    if (p) stb_pool_free(p);
   void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws};
   for (void *p : dev)
     if (p) (void)hipFree(p);
@@ -400,6 +410,7 @@ static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, 
   // (the draws never address m > max n: a table of min(M, N) columns is the same table)
   s->M = s->need_table ? (M < s->N ? M : s->N) : M;
   s->a_filled = NAN;
+  s->a_sfilled = NAN;
   const size_t Gs = G ? G : 1;
   int rc = 0;
   if (hipGetDevice(&s->dev) != hipSuccess || hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess ||
@@ -473,6 +484,25 @@ extern "C" int stb_tindic_set_h(stb_tindic_t *s, const double *hflat) {
   return rc;
 }
 
+// new concentrations through the staging buffer used two calls ago (its copy is long through); unchanged ones stay
+static int ti_stage_bpar(stb_tindic_t *s, const double *bpar, const char *who) {
+  int rc = 0;
+  const bool same_b = s->last_bpar.size() == (size_t)s->I && memcmp(s->last_bpar.data(), bpar, sizeof(double) * s->I) == 0;
+  if (!same_b) {
+    const int k = s->slot ^= 1;
+    s->last_bpar.clear();
+    if (hipEventSynchronize(s->ev_bpar[k]) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    if (!rc) {
+      memcpy(s->h_bpar[k], bpar, sizeof(double) * s->I);
+      if (hipMemcpyAsync(s->d_bpar, s->h_bpar[k], sizeof(double) * s->I, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+          hipEventRecord(s->ev_bpar[k], s->st) != hipSuccess)
+        rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    }
+    if (!rc) s->last_bpar.assign(bpar, bpar + s->I);
+  }
+  return rc;
+}
+
 extern "C" int stb_tindic_sweep(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, int nsweeps) {
   STB_ENTRY;
   if (!s) return stb_fail("stb_tindic_sweep: null object");
@@ -490,20 +520,7 @@ extern "C" int stb_tindic_sweep(stb_tindic_t *s, double a, const double *bpar, u
     if (!rc) rc = stb_fill_status();
     if (!rc) s->a_filled = a;
   }
-  // new concentrations through the staging buffer used two calls ago (its copy is long through); unchanged ones stay
-  const bool same_b = s->last_bpar.size() == (size_t)s->I && memcmp(s->last_bpar.data(), bpar, sizeof(double) * s->I) == 0;
-  if (!rc && !same_b) {
-    const int k = s->slot ^= 1;
-    s->last_bpar.clear();
-    if (hipEventSynchronize(s->ev_bpar[k]) != hipSuccess) rc = stb_fail("stb_tindic_sweep: %s", hipGetErrorString(hipGetLastError()));
-    if (!rc) {
-      memcpy(s->h_bpar[k], bpar, sizeof(double) * s->I);
-      if (hipMemcpyAsync(s->d_bpar, s->h_bpar[k], sizeof(double) * s->I, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-          hipEventRecord(s->ev_bpar[k], s->st) != hipSuccess)
-        rc = stb_fail("stb_tindic_sweep: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (!rc) s->last_bpar.assign(bpar, bpar + s->I);
-  }
+  if (!rc) rc = ti_stage_bpar(s, bpar, "stb_tindic_sweep");
   if (!rc)
     rc = ti_launch(s->d_vt, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T,
                    s->d_h, s->d_coff, s->d_cust, s->flags, seed, sweep, nsweeps, s->maxK, s->st);
@@ -594,4 +611,55 @@ extern "C" int stb_tindic_samplejoint(stb_tindic_t *s, stb_groups_t *g, const st
   if (!s || !g) return stb_fail("stb_tindic_samplejoint: null object");
   if (stb_tindic_to_groups(s, g, nullptr)) return 1;
   return stb_hj_samplejoint(g, nullptr, s->d_coff, opts, a_in, b_in, a_out, b_out, info, "stb_tindic_samplejoint");
+}
+
+// the log joint of the object's state (logjoint.hip), queued behind its sweeps; t and T are not written.  The S cells come
+// from a slab of the object's own with the V table's bounds: taken from the buffer cache on first use, refilled only when
+// the discount changes, given back by stb_tindic_free.
+extern "C" int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total, double *Li_host,
+                                   stb_logjoint_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_logjoint";
+  if (!s) return stb_fail("%s: null object", who);
+  if (stb_lj_check(a, flags, s->I, who)) return 1;
+  if (!bpar) return stb_fail("%s: bpar is required", who);
+  if (!total) return stb_fail("%s: total is required", who);
+  for (int i = 0; i < s->I; i++)
+    if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (s->need_table && !s->d_stab) {
+    s->sstride = (stb_table_elems(s->N, s->M) + 31) & ~31ull;
+    s->sws_bytes = stb_fill_workspace_bytes(s->N, s->M, 1);
+    if (stb_pool_malloc((void **)&s->d_stab, sizeof(double) * s->sstride) != hipSuccess ||
+        stb_pool_malloc((void **)&s->d_sS1, sizeof(double) * s->N) != hipSuccess ||
+        stb_pool_malloc(&s->d_sws, s->sws_bytes ? s->sws_bytes : 1) != hipSuccess) {
+      void *pooled[] = {s->d_stab, s->d_sS1, s->d_sws};
+      for (void *p : pooled)
+        if (p) stb_pool_free(p);
+      s->d_stab = s->d_sS1 = nullptr;
+      s->d_sws = nullptr;
+      rc = stb_fail("%s: out of device memory for a %u x %u S table", who, s->N, s->M);
+    }
+    s->a_sfilled = NAN;
+  }
+  if (!rc && s->need_table && !(a == s->a_sfilled)) {
+    s->a_sfilled = NAN;
+    rc = stb_fill_S(&a, 1, s->N, s->M, s->d_stab, s->sstride, s->d_sS1, s->N, s->d_sws, s->sws_bytes, stb_default_variant(), s->st);
+    if (!rc) rc = stb_fill_status();
+    if (!rc) s->a_sfilled = a;
+  }
+  if (!rc) rc = ti_stage_bpar(s, bpar, who);
+  double *d_Li = nullptr;
+  if (!rc && Li_host && stb_pool_malloc((void **)&d_Li, sizeof(double) * (size_t)s->I) != hipSuccess)
+    rc = stb_fail("%s: out of device memory for %d values", who, s->I);
+  if (!rc)
+    rc = stb_lj_run(s->d_stab, s->d_sS1, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t,
+                    s->d_T, s->d_h, flags, d_Li, Li_host, total, info, s->st, who);
+  if (d_Li) {
+    if (rc) (void)hipStreamSynchronize(s->st);  // (the cache may hand the buffer on at once)
+    stb_pool_free(d_Li);
+  }
+  stb_device_leave(prev);
+  return rc;
 }

@@ -1,0 +1,353 @@
+"""The log joint probability of a sampler state on the device (stb_logjoint, stb_tcounts_logjoint, stb_tindic_logjoint;
+libstb_amd/csrc/logjoint.hip) against the high-precision truth and the bar of tests/lj_oracle.py -- derived there from
+the kernel's own operations --, across launch geometries, on inputs built to trigger every counter, on the two objects,
+and with refused arguments.  Shapes: tables N = 48 with M = 48 and M = 7; restaurants of 0, 1, 63, 64, 65 and 129 pairs
+(the chunk edges) and sets of 1, 255, 256, 257 and 513 restaurants (the block edges)."""
+import ctypes as C
+import math
+import os
+from functools import lru_cache
+
+import numpy as np
+import pytest
+
+import hj_oracle as hj
+import lj_oracle as lj
+import orc
+from libstb_amd import capi
+
+pytestmark = pytest.mark.gpu
+N48 = 48
+A_ALL = [0.0, 0.125, 0.5, 0.9]
+K_EDGES = [0, 1, 63, 64, 65, 129]
+
+
+def dev(a, dtype):
+    import torch
+
+    a = np.ascontiguousarray(a, dtype=dtype)
+    view = {np.uint32: np.int32, np.uint16: np.int16, np.uint64: np.int64}.get(dtype)
+    return torch.as_tensor(a.view(view) if view else a, device="cuda")
+
+
+class waves:
+    """STB_LOGJOINT_WAVES for the calls inside"""
+
+    def __init__(self, v):
+        self.v = v
+
+    def __enter__(self):
+        self.old = os.environ.get("STB_LOGJOINT_WAVES")
+        os.environ["STB_LOGJOINT_WAVES"] = str(self.v)
+
+    def __exit__(self, *a):
+        if self.old is None:
+            os.environ.pop("STB_LOGJOINT_WAVES", None)
+        else:
+            os.environ["STB_LOGJOINT_WAVES"] = self.old
+
+
+def b_values(I, a):
+    """b_i over 1e-3, 1, 1e3 -- and -0.25 at a = 0.5"""
+    vals = [1e-3, 1.0, 1e3] + ([-0.25] if a == 0.5 else [])
+    return np.array([vals[i % len(vals)] for i in range(I)])
+
+
+def make_state(K, M, seed):
+    """a valid state on the CSR shape K: n = 0 (t = 0), n = 1, t = 1, t = n and the interior all occur; n <= 48 and
+    t <= min(n, M) or t = n"""
+    rng = np.random.default_rng(seed)
+    K = np.asarray(K, dtype=np.int32)
+    G = int(K.sum())
+    n = rng.integers(0, N48 + 1, size=G).astype(np.uint32)
+    kind = rng.integers(0, 5, size=G)
+    tm = np.minimum(n, M)
+    t = np.where(n > 0, 1 + np.floor(rng.random(G) * tm), 0).astype(np.int64)
+    t = np.where((kind == 0) & (n > 0), 1, t)
+    t = np.where((kind == 1) & (n > 0), n, t)
+    n = np.where(kind == 2, 1, n).astype(np.uint32)
+    t = np.where(kind == 2, 1, t).astype(np.uint16)
+    h = 0.05 + 0.95 * rng.random(G)
+    h[::7] = 1.0
+    return K, n, t, h
+
+
+@lru_cache(maxsize=None)
+def device_tables(a, M):
+    tabs = capi.DeviceTables(N48, M)
+    tabs.fill(a)
+    tabs.status()
+    return tabs
+
+
+@lru_cache(maxsize=None)
+def truth_tables(a, M):
+    return lj.Tables(a, N48, M)
+
+
+def run_raw(tabs, a, bpar, K, n, t, h, indicators=False, T=None, want_Li=True, flags=None):
+    import torch
+
+    koff = np.concatenate([[0], np.cumsum(K)]).astype(np.uint64)
+    tot, Li, info = capi.logjoint(tabs, a, dev(bpar, np.float64), dev(koff, np.uint64), dev(n if len(n) else [0], np.uint32),
+                                  dev(t if len(t) else [0], np.uint16), None if T is None else dev(T, np.uint32),
+                                  None if h is None else dev(h if len(h) else [1.0], np.float64), indicators, want_Li,
+                                  flags=flags)
+    torch.cuda.synchronize()
+    return tot, None if Li is None else Li.cpu().numpy(), info
+
+
+def check_against(tr, tot, Li, info, indicators, what):
+    print(what, "total", tot, "truth", tr["total"][0], "bar", tr["total"][1])
+    assert not np.isnan(Li).any() and not math.isnan(tot)
+    for i in range(len(Li)):
+        assert lj.within(float(Li[i]), float(tr["Li"][i]), float(tr["Li_bar"][i])), (what, i, Li[i], tr["Li"][i], tr["Li_bar"][i])
+    for name in ("pairs", "base", "restaurants", "binom"):
+        got = getattr(info, name)
+        want, bar = tr[name]
+        print(what, name, got, want, bar)
+        assert not math.isnan(got)
+        assert lj.within(got, want, bar), (what, name, got, want, bar)
+    if not indicators:
+        assert info.binom == 0.0
+    assert lj.within(tot, tr["total"][0], tr["total"][1]), (what, tot, tr["total"])
+    assert info.outside == tr["outside"] and info.impossible == tr["impossible"]
+
+
+# ---- the chunk edges, every discount, both tables, both flag values, with and without h
+
+@pytest.mark.parametrize("with_h", [False, True])
+@pytest.mark.parametrize("indicators", [False, True])
+@pytest.mark.parametrize("M", [48, 7])
+@pytest.mark.parametrize("a", A_ALL)
+def test_chunk_edges_against_the_truth(a, M, indicators, with_h):
+    K, n, t, h = make_state(K_EDGES, M, seed=101 + M)
+    h = h if with_h else None
+    bpar = b_values(len(K), a)
+    tr = lj.truth(K, n, t, h, a, bpar, truth_tables(a, M), indicators)
+    tot, Li, info = run_raw(device_tables(a, M), a, bpar, K, n, t, h, indicators, T=tr["T"])
+    check_against(tr, tot, Li, info, indicators, f"a={a} M={M} ind={indicators} h={with_h}")
+    assert info.outside == 0 and info.impossible == 0 and info.t_mismatch == 0
+    assert Li[0] == 0.0  # (a restaurant without pairs)
+
+
+# ---- the block edges, restaurants without customers among them
+
+def block_state(I, M, seed):
+    rng = np.random.default_rng(seed)
+    K = rng.integers(0, 4, size=I).astype(np.int32)
+    K, n, t, h = make_state(K, M, seed + 1)
+    koff = np.concatenate([[0], np.cumsum(K)])
+    for i in range(0, I, 5):  # restaurants whose pairs all have n = 0: N_i = 0 with K_i > 0
+        n[koff[i]:koff[i + 1]] = 0
+        t[koff[i]:koff[i + 1]] = 0
+    return K, n, t, h
+
+
+@pytest.mark.parametrize("I", [1, 255, 256, 257, 513])
+@pytest.mark.parametrize("a,M,indicators,with_h", [(0.5, 48, True, True), (0.0, 7, False, False)])
+def test_block_edges_against_the_truth(I, a, M, indicators, with_h):
+    K, n, t, h = block_state(I, M, seed=7 * I + M)
+    h = h if with_h else None
+    bpar = b_values(I, a)
+    tr = lj.truth(K, n, t, h, a, bpar, truth_tables(a, M), indicators)
+    assert I < 5 or (tr["Nc"] == 0).sum() >= I // 5
+    tot, Li, info = run_raw(device_tables(a, M), a, bpar, K, n, t, h, indicators, T=tr["T"])
+    check_against(tr, tot, Li, info, indicators, f"I={I} a={a} M={M}")
+    assert info.outside == 0 and info.impossible == 0 and info.t_mismatch == 0
+    assert (Li[tr["Nc"] == 0] == 0.0).all()
+
+
+# ---- launch geometry
+
+@pytest.mark.parametrize("shape", ["chunks", "blocks"])
+def test_the_same_bits_for_every_workgroup_size(shape):
+    a, M = 0.5, 7
+    K, n, t, h = make_state(K_EDGES, M, 5) if shape == "chunks" else block_state(513, M, 6)
+    bpar = b_values(len(K), a)
+    ref = None
+    for wv in (1, 2, 4, 8, 0):
+        with waves(wv):
+            tot, Li, info = run_raw(device_tables(a, M), a, bpar, K, n, t, h, True)
+        got = (np.float64(tot).tobytes(), Li.tobytes(), bytes(info))
+        ref = got if ref is None else ref
+        assert got == ref, wv
+    # the total does not depend on whether the L_i are asked for
+    tot2, none, info2 = run_raw(device_tables(a, M), a, bpar, K, n, t, h, True, want_Li=False)
+    assert none is None and (np.float64(tot2).tobytes(), bytes(info2)) == (ref[0], ref[2])
+
+
+# ---- the counters
+
+def test_counters_are_exact_and_impossible_pairs_give_minus_infinity():
+    a, M = 0.5, 7
+    K = np.array([4, 5, 3, 2, 70], dtype=np.int32)
+    n = np.concatenate([[60, 60, 20, 5], [5, 5, 0, 9, 9], [6, 6, 6], [12, 12], np.full(70, 10)]).astype(np.uint32)
+    t = np.concatenate([[3, 60, 10, 2], [0, 6, 2, 9, 1], [2, 3, 1], [8, 3], np.full(70, 3)]).astype(np.uint16)
+    h = np.ones(len(n))
+    h[9:12] = [0.0, -1.0, math.inf]
+    h[14 + 69] = math.nan
+    bpar = np.array([1.0, 2.0, 0.5, 3.0, 1e3])
+    tr = lj.truth(K, n, t, h, a, bpar, truth_tables(a, M), True)
+    # outside: n = 60 twice, t = 10 > M, t = 8 > M; impossible: t = 0, t = 6 > n = 5, n = 0 with t = 2, four bad h
+    assert tr["outside"] == 4 and tr["impossible"] == 7
+    T = tr["T"].copy()
+    T[0] += 1
+    T[3] -= 1
+    tot, Li, info = run_raw(device_tables(a, M), a, bpar, K, n, t, h, True, T=T)
+    assert (info.outside, info.impossible, info.t_mismatch) == (4, 7, 2)
+    assert not np.isnan(Li).any()
+    assert list(np.isneginf(Li)) == [False, True, True, False, True]
+    assert tot == -math.inf and info.pairs == -math.inf and info.base == -math.inf
+    assert math.isfinite(info.restaurants) and math.isfinite(info.binom)
+    for i in (0, 3):  # the kernel's own sum of t is the one used
+        assert lj.within(float(Li[i]), float(tr["Li"][i]), float(tr["Li_bar"][i]))
+    assert lj.within(info.restaurants, *tr["restaurants"])
+    # without d_T nothing is compared
+    _, _, info = run_raw(device_tables(a, M), a, bpar, K, n, t, h, False)
+    assert info.t_mismatch == 0 and info.binom == 0.0
+
+
+def test_without_a_table_and_at_b_zero():
+    # no slab and no S1 vector: pairs with n <= 1, and M = 1 with larger n (S^n_1 evaluated in place)
+    a = 0.5
+    K = np.array([3, 2, 0, 4], dtype=np.int32)
+    n = np.array([1, 0, 1, 1, 1, 30, 2, 48, 1], dtype=np.uint32)
+    t = np.array([1, 0, 1, 1, 1, 1, 1, 1, 1], dtype=np.uint16)
+    h = np.linspace(0.2, 1.0, len(n))
+    bpar = np.array([1.0, -0.25, 5.0, 0.0])  # (b = 0 takes the limit)
+    tabs = lj.Tables(a, N48, 1, with_table=False)
+    for ind in (False, True):
+        tr = lj.truth(K, n, t, h, a, bpar, tabs, ind)
+        tot, Li, info = run_raw((N48, 1), a, bpar, K, n, t, h, ind, T=tr["T"])
+        check_against(tr, tot, Li, info, ind, "no table")
+        assert info.outside == 0 and info.t_mismatch == 0 and math.isfinite(tot)
+    # an interior pair cannot be answered without a table
+    n2, t2 = n.copy(), t.copy()
+    n2[5], t2[5] = 30, 4
+    _, _, info = run_raw((N48, 48), a, bpar, K, n2, t2, h)
+    assert info.outside == 1
+
+
+# ---- the objects
+
+def object_state(M):
+    rng = np.random.default_rng(31)
+    K = np.concatenate([[0, 1, 65], rng.integers(1, 12, size=37)]).astype(np.int32)
+    return make_state(K, M, 32)
+
+
+@pytest.mark.parametrize("kind", ["tcounts", "tindic"])
+def test_objects_equal_the_raw_call_and_leave_the_state_alone(kind):
+    L = capi.lib()
+    M = N48
+    K, n, t, h = object_state(M)
+    t = np.where(n > 0, np.minimum(t, n), 0).astype(np.uint16)
+    I = len(K)
+    a, b = 0.5, 2.0
+    bpar = np.full(I, b)
+    obj = capi.TableCounts(K, n, t, h) if kind == "tcounts" else capi.TableIndicators(K, n, t, h)
+    g = L.stb_groups_create(I, orc.i32p(K), None, None, None, None, 0, 0, 2)
+    assert g, capi.last_error()
+    try:
+        obj.sweep(a, bpar, 77, 0, 3)
+        for ind in (False, True):
+            tot, Li, info = obj.logjoint(a, bpar, ind)
+            t_now, T_now = obj.get()
+            Nobj = max(int(n.max()), 3)
+            tabs = capi.DeviceTables(Nobj, min(M, Nobj) if kind == "tindic" else int(n.max()))
+            tabs.fill(a)
+            tabs.status()
+            tot_r, Li_r, info_r = run_raw(tabs, a, bpar, K, n, t_now, h, ind, T=T_now)
+            assert np.float64(tot).tobytes() == np.float64(tot_r).tobytes()
+            assert Li.tobytes() == Li_r.tobytes() and bytes(info) == bytes(info_r)
+            assert info.t_mismatch == 0 and info.outside == 0 and info.impossible == 0
+            # against the truth as well
+            tr = lj.truth(K, n, t_now, h, a, bpar, lj.Tables(a, Nobj, tabs.M), ind)
+            check_against(tr, tot, Li, info, ind, kind)
+            # the state is unchanged
+            t2, T2 = obj.get()
+            assert np.array_equal(t2, t_now) and np.array_equal(T2, T_now)
+        # the pair sum and the restaurant terms the library already had, within the two sides' bars
+        obj.to_groups(g, bpar)
+        W = capi.groups_ssum(g, [a])[0]
+        _, wbar = hj.W_truth_bar([a], n, t_now)
+        assert abs(info.pairs - W) <= tr["pairs"][1] + wbar[0], (info.pairs, W)
+        Ncust = tr["Nc"]
+        R = float(capi.joint_terms([a], [b], dev(T_now, np.uint32), dev(Ncust, np.uint32)).cpu().numpy()[0, 0])
+        _, rbar = hj.R_points_truth([a], [b], T_now, Ncust)
+        assert abs(info.restaurants - R) <= tr["restaurants"][1] + rbar[0], (info.restaurants, R)
+        # a second call at a new discount refills the table
+        a2 = 0.125
+        tot2, Li2, info2 = obj.logjoint(a2, bpar, True)
+        tr2 = lj.truth(K, n, t_now, h, a2, bpar, lj.Tables(a2, Nobj, tabs.M), True)
+        check_against(tr2, tot2, Li2, info2, True, kind + " refilled")
+        assert tot2 != tot
+        # ... and back, with Li_host NULL
+        tot3, none, info3 = obj.logjoint(a, bpar, True, want_Li=False)
+        assert none is None and tot3 == tot and bytes(info3) == bytes(info)
+        # refused: the state stays as it was
+        for bad in (lambda: obj.logjoint(1.0, bpar), lambda: obj.logjoint(-0.1, bpar),
+                    lambda: obj.logjoint(a, np.full(I, -0.6)), lambda: obj.logjoint(a, np.full(I, math.nan))):
+            with pytest.raises(capi.StbError):
+                bad()
+        fn = L.stb_tcounts_logjoint if kind == "tcounts" else L.stb_tindic_logjoint
+        tt, inf = C.c_double(1.5), capi.LogJointInfo()
+        assert fn(obj.h, a, capi.dp(bpar), 2, C.byref(tt), None, C.byref(inf)) != 0 and b"flags" in L.stb_last_error()
+        assert fn(obj.h, a, None, 0, C.byref(tt), None, C.byref(inf)) != 0
+        assert fn(None, a, capi.dp(bpar), 0, C.byref(tt), None, C.byref(inf)) != 0
+        assert tt.value == 1.5
+        t4, T4 = obj.get()
+        assert np.array_equal(t4, t_now) and np.array_equal(T4, T_now)
+        tot5, _, _ = obj.logjoint(a, bpar, True)
+        assert tot5 == tot
+    finally:
+        obj.free()
+        L.stb_groups_free(g)
+        L.stb_sampler_cache_clear()
+
+
+@pytest.mark.parametrize("kind", ["tcounts", "tindic"])
+def test_objects_without_a_table_read_none(kind):
+    # every n <= 1; and M = 1 with larger n: every t is 1, S^n_1 is evaluated in place
+    a, bpar = 0.9, np.array([1.0, 1e-3, 1e3])
+    K = np.array([2, 3, 1], dtype=np.int32)
+    for n, M in ((np.array([1, 0, 1, 1, 0, 1], dtype=np.uint32), 0), (np.array([5, 0, 48, 2, 1, 17], dtype=np.uint32), 1)):
+        t = (n > 0).astype(np.uint16)
+        obj = capi.TableCounts(K, n, t, None, M) if kind == "tcounts" else capi.TableIndicators(K, n, t, None, None, M)
+        try:
+            obj.sweep(a, bpar, 3, 0, 2)
+            tot, Li, info = obj.logjoint(a, bpar, True)
+            tr = lj.truth(K, n, t, None, a, bpar, lj.Tables(a, N48, 1, with_table=False), True)
+            check_against(tr, tot, Li, info, True, f"{kind} M={M}")
+            assert info.t_mismatch == 0 and info.outside == 0
+        finally:
+            obj.free()
+
+
+# ---- refusals of the raw call
+
+def test_the_raw_call_refuses_before_anything_is_queued():
+    import torch
+
+    L = capi.lib()
+    a, M = 0.5, 7
+    K, n, t, h = make_state([3, 2], M, 1)
+    tabs = device_tables(a, M)
+    koff = dev(np.array([0, 3, 5]), np.uint64)
+    nd, td, bd = dev(n, np.uint32), dev(t, np.uint16), dev([1.0, 2.0], np.float64)
+    tot, info = C.c_double(2.5), capi.LogJointInfo()
+
+    def call(a=a, flags=0, koff=koff.data_ptr(), nn=nd.data_ptr(), tt=td.data_ptr(), I=2):
+        return L.stb_logjoint(tabs.tables.data_ptr(), tabs.S1.data_ptr(), N48, M, a, bd.data_ptr(), I, koff, nn, tt, None, None,
+                              flags, None, C.byref(tot), C.byref(info), None)
+
+    for kw, word in (({"a": 1.0}, b"discount"), ({"a": -0.5}, b"discount"), ({"a": math.nan}, b"discount"),
+                     ({"flags": 2}, b"flags"), ({"flags": 0x80000001}, b"flags"), ({"koff": None}, b"required"),
+                     ({"nn": None}, b"required"), ({"tt": None}, b"required"), ({"I": -1}, b"I=-1")):
+        assert call(**kw) != 0, kw
+        assert word in L.stb_last_error(), (kw, L.stb_last_error())
+        assert tot.value == 2.5
+    assert call(I=0) == 0 and tot.value == 0.0 and info.pairs == 0.0 and info.outside == 0
+    assert call() == 0 and math.isfinite(tot.value)
+    torch.cuda.synchronize()
