@@ -616,6 +616,28 @@ int stb_tcounts_logjoint(stb_tcounts_t *s, double a, const double *bpar, unsigne
 int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total, double *Li_host,
                         stb_logjoint_info_t *info);
 
+/* ---- the launch geometry of the ticket reductions (for tests) ----
+ * stb_sample_logq (k_logq), stb_joint_terms (k_joint_terms) and stb_logjoint (k_logjoint) share one design: workgroups take
+ * steps of `chunks` blocks of 256 restaurants grid-stride in x -- step blockIdx.x, then + grid_x, ... -- (k_joint_terms
+ * also the b_j grid-stride in y), write block sums to a per-thread buffer, and the last workgroup to take a ticket adds the
+ * blocks in order.  stb_reduce_geometry says what a call on I >= 1 restaurants (and, for STB_GEOM_JOINT_TERMS, a D x J
+ * grid) launches on the current device: it is computed by the function the three launch sites compute their launch
+ * from, so it cannot drift from them.  waves = 1, 2, 4 or 8 waves a workgroup; 0: what the call itself would take now
+ * (STB_HYPERQ_WAVES / STB_HYPERJ_WAVES / STB_LOGJOINT_WAVES, else the default).  need / cap0: what the call needs of the
+ * buffer of block sums and what the buffer holds when first allocated -- in block sums, and for STB_GEOM_JOINT_TERMS in
+ * doubles (a block sum is D J of them); a call with need > cap0 replaces the buffer.  No device work.  Returns 0, or
+ * non-zero with stb_last_error() set for an unknown `which`, waves, I = 0 or a grid outside 1..64. */
+#define STB_GEOM_LOGQ 0
+#define STB_GEOM_JOINT_TERMS 1
+#define STB_GEOM_LOGJOINT 2
+typedef struct stb_reduce_geom {
+  unsigned grid_x, grid_y;   /* workgroups */
+  unsigned steps, chunks;    /* steps in all, blocks of 256 restaurants a step */
+  unsigned blocks, waves;    /* blocks of 256 restaurants in all, waves a workgroup */
+  uint64_t need, cap0;
+} stb_reduce_geom_t;
+int stb_reduce_geometry(int which, uint64_t I, int D, int J, int waves, stb_reduce_geom_t *out);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

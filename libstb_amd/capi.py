@@ -64,6 +64,15 @@ class LogJointInfo(C.Structure):
                 ("outside", C.c_uint64), ("impossible", C.c_uint64), ("t_mismatch", C.c_uint64)]
 
 
+GEOM_LOGQ, GEOM_JOINT_TERMS, GEOM_LOGJOINT = 0, 1, 2  # stb_reduce_geometry's `which`
+
+
+class ReduceGeom(C.Structure):
+    """stb_reduce_geom_t (include/stb_hip.h)"""
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("steps", C.c_uint), ("chunks", C.c_uint),
+                ("blocks", C.c_uint), ("waves", C.c_uint), ("need", C.c_uint64), ("cap0", C.c_uint64)]
+
+
 class JointInfo(C.Structure):
     """stb_joint_info_t (include/stb_hip.h)"""
     _fields_ = [("stages", C.c_int), ("accepted", C.c_int), ("evals", C.c_int), ("stage_pick", C.c_int),
@@ -239,6 +248,10 @@ def lib() -> C.CDLL:
     sig("stb_logjoint", i, [vp, vp, u, u, d, vp, i, vp, vp, vp, vp, vp, u, vp, c_double_p, lji, vp])
     sig("stb_tcounts_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
     sig("stb_tindic_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
+    sig("stb_reduce_geometry", i, [i, u64, i, i, i, C.POINTER(ReduceGeom)])
+    # (private entry points: the customers per restaurant as d_N or as d_coff prefix sums, for tests)
+    sig("stb_hq_logq", i, [d, d, i, vp, vp, vp, c_double_p, u64, u64, vp])
+    sig("stb_hj_joint_terms", i, [c_double_p, i, c_double_p, i, vp, vp, vp, u64, vp, vp])
     # ---- the slope of log S in the discount
     sig("stb_fill_dS_workspace_bytes", sz, [u, u, i])
     sig("stb_fill_dS", i, [c_double_p, i, u, u, vp, u64, vp, u64, vp, u64, vp, u64, vp, sz, vp])
@@ -689,10 +702,25 @@ def logjoint(tabs, a, bpar, koff, n, t, T=None, h=None, indicators: bool = False
     return tot.value, Li, info
 
 
-def sample_logq(b, scale, N, seed: int, sweep: int, want_L: bool = True, stream=None):
+def reduce_geometry(which: int, I: int, D: int = 1, J: int = 1, waves: int = 0) -> ReduceGeom:
+    """stb_reduce_geometry: what stb_sample_logq (GEOM_LOGQ), stb_joint_terms on a D x J grid (GEOM_JOINT_TERMS) or
+    stb_logjoint (GEOM_LOGJOINT) launches for I restaurants on the current device; waves 0: what the call would take now"""
+    g = ReduceGeom()
+    check(lib().stb_reduce_geometry(int(which), int(I), int(D), int(J), int(waves), C.byref(g)))
+    return g
+
+
+def sample_logq(b, scale, N, seed: int, sweep: int, want_L: bool = True, stream=None, coff=None):
     """stb_sample_logq on a device tensor N (int32 holding uint32 counts): (Q, L) with L a float64 device tensor of
-    -log q_i (None when want_L is false)"""
+    -log q_i (None when want_L is false).  coff (int64 [I+1] prefix sums of the customers, N None): the objects' route"""
     torch = _torch()
+    if coff is not None:
+        I = int(coff.shape[0]) - 1
+        Lt = torch.empty(I, dtype=torch.float64, device=coff.device) if want_L else None
+        Q = C.c_double(0.0)
+        check(lib().stb_hq_logq(float(b), float(scale), I, None, coff.data_ptr(), Lt.data_ptr() if want_L and I else None,
+                                C.byref(Q), seed, sweep, stream_ptr(stream)))
+        return Q.value, Lt
     I = int(N.shape[0])
     Lt = torch.empty(I, dtype=torch.float64, device=N.device) if want_L else None
     Q = C.c_double(0.0)
@@ -743,13 +771,18 @@ def groups_modea(groups, a_lo, a_hi, tol=1e-9, rounds_max=32):
     return a_hat.value, curv.value, info
 
 
-def joint_terms(a, b, T, N, stream=None):
-    """stb_joint_terms on device tensors T, N (int32 holding uint32 counts): R[d, j] as a float64 device tensor"""
+def joint_terms(a, b, T, N, stream=None, coff=None):
+    """stb_joint_terms on device tensors T, N (int32 holding uint32 counts): R[d, j] as a float64 device tensor.
+    coff (int64 [I+1] prefix sums of the customers, N None): the objects' route"""
     torch = _torch()
     a = np.ascontiguousarray(a, dtype=np.float64)
     b = np.ascontiguousarray(b, dtype=np.float64)
     I = int(T.shape[0])
     out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float64, device=T.device)
+    if coff is not None:
+        check(lib().stb_hj_joint_terms(dp(a), int(a.shape[0]), dp(b), int(b.shape[0]), T.data_ptr(), None, coff.data_ptr(), I,
+                                       out.data_ptr(), stream_ptr(stream)))
+        return out
     check(lib().stb_joint_terms(dp(a), int(a.shape[0]), dp(b), int(b.shape[0]), T.data_ptr() if I else None,
                                 N.data_ptr() if I else None, I, out.data_ptr(), stream_ptr(stream)))
     return out

@@ -31,11 +31,12 @@
 #include "groups.h"
 #include "tcounts.h"
 #include "hyperj.h"
+#include "ticket_geom.h"
 #include "../../include/psample.h"
 
 #include <vector>
 
-#define HJ_CHUNK 256
+#define HJ_CHUNK STB_TG_BLOCK  // (one constant for the kernel, the launch and stb_reduce_geometry)
 #define HJ_CT 4
 #define HJ_MAXTHREADS 512
 #define HJ_DMAX 64
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(HJ_MAXTHREADS) void k_joint_terms(hj_args A, uint64
   __shared__ unsigned s_last;
   const unsigned nthr = blockDim.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = nthr >> 6;
   const unsigned span = nthr * RPT;       // restaurants a workgroup takes per step: 256, or 512 with eight waves
-  const unsigned cps = span / HJ_CHUNK;   // ... which are this many blocks of 256
+  const unsigned cps = stb_tg_cps(nthr);  // ... which are this many blocks of 256 (the launch pairs RPT with nthr so)
   const unsigned nsteps = (nchunks + cps - 1) / cps;
   const int D = A.D, J = A.J, DJ = D * J;
   for (unsigned s = blockIdx.x; s < nsteps; s += gridDim.x) {
@@ -321,17 +322,12 @@ static int hj_ready(size_t partials, bool stages) {
     if (hj.d_partial) stb_pool_free(hj.d_partial);
     hj.d_partial = nullptr;
     hj.cap = 0;
-    const size_t want = partials < 65536 ? 65536 : partials;
+    const size_t want = partials < STB_TG_CAP0_HJ ? STB_TG_CAP0_HJ : partials;
     if (stb_pool_malloc((void **)&hj.d_partial, sizeof(double) * want) != hipSuccess)
       return stb_fail("stb_joint_terms: out of device memory for %zu block sums", want);
     hj.cap = want;
   }
   return 0;
-}
-
-static int hj_waves(void) {
-  const int v = stb_env_int("STB_HYPERJ_WAVES", 4);
-  return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
 }
 
 // R over the grid, queued on st; N given either way (d_N uint32, or d_coff uint64 prefix sums)
@@ -360,17 +356,11 @@ static int hj_terms(const double *a, int D, const double *b, int J, const uint32
   if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
   const uint64_t nch64 = (I + HJ_CHUNK - 1) / HJ_CHUNK;
   if (nch64 * (uint64_t)(D * J) > (1ull << 28)) return stb_fail("%s: %llu restaurants x %d cells: more block sums than 2 GB hold", who, (unsigned long long)I, D * J);
-  const unsigned nchunks = (unsigned)nch64;
-  if (hj_ready((size_t)nchunks * D * J, false)) return 1;
-  const int nw = hj_waves(), nthr = 64 * nw;
-  const unsigned cps = nthr > HJ_CHUNK ? nthr / HJ_CHUNK : 1;
-  const unsigned nsteps = (nchunks + cps - 1) / cps;
-  unsigned want = 4u * (unsigned)stb_cu_count();
-  if (want < 1) want = 1;
-  unsigned gx = nsteps < want ? nsteps : want;
-  unsigned gy = want / gx;
-  if (gy < 1) gy = 1;
-  if (gy > (unsigned)J) gy = (unsigned)J;
+  stb_tgeom tg;
+  if (stb_ticket_geom(STB_GEOM_JOINT_TERMS, I, D, J, 0, &tg)) return stb_fail("%s: no launch geometry for I=%llu", who, (unsigned long long)I);
+  if (hj_ready(tg.need, false)) return 1;
+  const unsigned nchunks = tg.nblk, gx = tg.gx, gy = tg.gy;
+  const int nw = (int)tg.waves, nthr = 64 * nw;
   HIPCHK(hipMemsetAsync(hj.d_ctl, 0, sizeof(unsigned), st));
   if (nw == 1)
     STB_LAUNCH(k_joint_terms<4>, dim3(gx, gy), dim3(nthr), st, A, I, d_T, d_N, d_coff, hj.d_partial, nchunks, hj.d_ctl, d_out);
@@ -386,6 +376,13 @@ extern "C" int stb_joint_terms(const double *a_host, int D, const double *b_host
                                uint64_t I, double *d_out, void *stream) {
   STB_ENTRY;
   return hj_terms(a_host, D, b_host, J, d_T, d_N, nullptr, I, d_out, (hipStream_t)stream, "stb_joint_terms");
+}
+
+// stb_joint_terms with the customers per restaurant given either way (hyperj.h)
+extern "C" int stb_hj_joint_terms(const double *a_host, int D, const double *b_host, int J, const uint32_t *d_T, const uint32_t *d_N,
+                                  const uint64_t *d_coff, uint64_t I, double *d_out, void *stream) {
+  STB_ENTRY;
+  return hj_terms(a_host, D, b_host, J, d_T, d_N, d_coff, I, d_out, (hipStream_t)stream, "stb_joint_terms");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -36,8 +36,9 @@
 #include "stb_common.h"
 #include "tcounts.h"
 #include "hyperq.h"
+#include "ticket_geom.h"
 
-#define HQ_CHUNK 256
+#define HQ_CHUNK STB_TG_BLOCK  // (one constant for the kernel, the launch and stb_reduce_geometry)
 #define HQ_CAP 64
 #define HQ_MAXTHREADS 512
 
@@ -91,8 +92,8 @@ __global__ __launch_bounds__(HQ_MAXTHREADS) void k_logq(double b, double inv_sca
   __shared__ double sL[HQ_MAXTHREADS];
   __shared__ unsigned s_last;
   const unsigned nthr = blockDim.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned span = nthr > HQ_CHUNK ? nthr : HQ_CHUNK;  // restaurants a workgroup takes per step
-  const unsigned cps = span / HQ_CHUNK;                     // ... which are this many blocks of 256
+  const unsigned cps = stb_tg_cps(nthr);   // blocks of 256 a workgroup takes per step
+  const unsigned span = cps * HQ_CHUNK;    // ... which are this many restaurants
   const unsigned nsteps = (nchunks + cps - 1) / cps;
   bool bad = false;
   for (unsigned s = blockIdx.x; s < nsteps; s += gridDim.x) {
@@ -213,17 +214,12 @@ static int hq_ready(size_t nchunks) {
     if (hq.d_partial) stb_pool_free(hq.d_partial);
     hq.d_partial = nullptr;
     hq.cap = 0;
-    const size_t want = nchunks < 4096 ? 4096 : nchunks;
+    const size_t want = nchunks < STB_TG_CAP0_BLOCKS ? STB_TG_CAP0_BLOCKS : nchunks;
     if (stb_pool_malloc((void **)&hq.d_partial, sizeof(double) * want) != hipSuccess)
       return stb_fail("stb_sample_logq: out of device memory for %zu block sums", want);
     hq.cap = want;
   }
   return 0;
-}
-
-static int hq_waves(void) {
-  const int v = stb_env_int("STB_HYPERQ_WAVES", 4);
-  return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
 }
 
 extern "C" int stb_hq_logq(double b, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff, double *d_L,
@@ -240,14 +236,11 @@ extern "C" int stb_hq_logq(double b, double scale, int I, const uint32_t *d_N, c
   }
   if (stb_device_count() < 1) return stb_fail("stb_sample_logq: no HIP device (libstb_amd has no CPU path)");
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nchunks = (unsigned)(((uint64_t)I + HQ_CHUNK - 1) / HQ_CHUNK);
-  if (hq_ready(nchunks)) return 1;
-  const int nthr = 64 * hq_waves();
-  const unsigned cps = nthr > HQ_CHUNK ? nthr / HQ_CHUNK : 1;
-  const unsigned nsteps = (nchunks + cps - 1) / cps;
-  unsigned grid = 4u * (unsigned)stb_cu_count();
-  if (grid < 1) grid = 1;
-  if (grid > nsteps) grid = nsteps;
+  stb_tgeom tg;
+  if (stb_ticket_geom(STB_GEOM_LOGQ, (uint64_t)I, 0, 0, 0, &tg)) return stb_fail("stb_sample_logq: no launch geometry for I=%d", I);
+  if (hq_ready(tg.need)) return 1;
+  const unsigned nchunks = tg.nblk, grid = tg.gx;
+  const int nthr = 64 * (int)tg.waves;
   const uint64_t key = stb_mix64(seed + (sweep + 1) * STB_GAMMA);
   HIPCHK(hipMemsetAsync(hq.d_ctl, 0, 2 * sizeof(unsigned), st));
   STB_LAUNCH(k_logq, dim3(grid), dim3(nthr), st, b, 1.0 / scale, (uint64_t)I, d_N, d_coff, d_L, key, hq.d_partial, nchunks,

@@ -60,8 +60,9 @@
 #include "stb_common.h"
 #include "tcounts.h"
 #include "logjoint.h"
+#include "ticket_geom.h"
 
-#define LJ_BLOCK 256
+#define LJ_BLOCK STB_TG_BLOCK  // (one constant for the kernel, the launch and stb_reduce_geometry)
 #define LJ_MAXTHREADS 512
 #define LJ_STAGE 1024  // block sums (x 4 components) the last workgroup stages in LDS at a time
 
@@ -303,7 +304,7 @@ static int lj_ready(size_t nblk) {
     if (lj.d_partial) stb_pool_free(lj.d_partial);
     lj.d_partial = nullptr;
     lj.cap = 0;
-    const size_t want = nblk < 4096 ? 4096 : nblk;
+    const size_t want = nblk < STB_TG_CAP0_BLOCKS ? STB_TG_CAP0_BLOCKS : nblk;
     if (stb_pool_malloc((void **)&lj.d_partial, sizeof(double) * 4 * want) != hipSuccess)
       return stb_fail("stb_logjoint: out of device memory for %zu block sums", want);
     lj.cap = want;
@@ -329,13 +330,11 @@ int stb_lj_run(const double *d_table, const double *d_S1, unsigned N, unsigned M
     return 0;
   }
   if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
-  const unsigned nblk = (unsigned)(((uint64_t)I + LJ_BLOCK - 1) / LJ_BLOCK);
-  if (lj_ready(nblk)) return 1;
-  const int cus = stb_cu_count();
-  int nw = stb_env_int("STB_LOGJOINT_WAVES", 0);
-  if (!(nw == 1 || nw == 2 || nw == 4 || nw == 8)) nw = nblk < 2u * (unsigned)(cus > 0 ? cus : 1) ? 8 : 4;
-  unsigned grid = 4u * (unsigned)(cus > 0 ? cus : 1);
-  if (grid > nblk) grid = nblk;
+  stb_tgeom tg;
+  if (stb_ticket_geom(STB_GEOM_LOGJOINT, (uint64_t)I, 0, 0, 0, &tg)) return stb_fail("%s: no launch geometry for I=%d", who, I);
+  if (lj_ready(tg.need)) return 1;
+  const unsigned nblk = tg.nblk, grid = tg.gx;
+  const int nw = (int)tg.waves;
   HIPCHK(hipMemsetAsync(lj.d_ctl, 0, 64, st));
   STB_LAUNCH(k_logjoint, dim3(grid), dim3(64 * nw), st, d_table, d_S1, N, M, a, a > 0.0 ? log(a) : 0.0, d_bpar, (uint64_t)I,
              d_koff, d_n, d_t, d_T, d_h, flags, d_Li, lj.d_partial, nblk, lj.d_ctl, lj.h_out_dev);
@@ -354,6 +353,27 @@ int stb_lj_run(const double *d_table, const double *d_S1, unsigned N, unsigned M
     info->impossible = hc[1];
     info->t_mismatch = hc[2];
   }
+  return 0;
+}
+
+extern "C" int stb_reduce_geometry(int which, uint64_t I, int D, int J, int waves, stb_reduce_geom_t *out) {
+  STB_ENTRY;
+  if (!out) return stb_fail("stb_reduce_geometry: null argument");
+  if (which == STB_GEOM_JOINT_TERMS && (D < 1 || J < 1 || D > 64 || J > 64))
+    return stb_fail("stb_reduce_geometry: a grid of %d x %d (1..64 each way)", D, J);
+  if (stb_device_count() < 1) return stb_fail("stb_reduce_geometry: no HIP device (libstb_amd has no CPU path)");
+  stb_tgeom tg;
+  if (stb_ticket_geom(which, I, D, J, waves, &tg))
+    return stb_fail("stb_reduce_geometry: which=%d, I=%llu, waves=%d (which 0..2, I >= 1, waves 0, 1, 2, 4 or 8)", which,
+                    (unsigned long long)I, waves);
+  out->grid_x = tg.gx;
+  out->grid_y = tg.gy;
+  out->steps = tg.steps;
+  out->chunks = tg.cps;
+  out->blocks = tg.nblk;
+  out->waves = tg.waves;
+  out->need = tg.need;
+  out->cap0 = tg.cap0;
   return 0;
 }
 

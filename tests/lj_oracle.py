@@ -141,12 +141,9 @@ def restaurant_term(a: float, b: float, T: int, N: int):
     return t1 - (t4 - t5), hp.term_bar([t1, t4, t5], [bm + N, bm])
 
 
-def truth(K, n, t, h, a: float, bpar, tabs: Tables, indicators: bool = False):
-    """the truth and the bars of every output of stb_logjoint on the CSR state (K, n, t, h or None).  A dict:
-      Li, Li_bar [I] (doubles; -inf where the restaurant holds an impossible pair), T, Nc [I] (the integer sums),
-      P_ld, P_bar [I]: P_i summed in long double and the sum of its cells' bars,
-      pairs, base, restaurants, binom, total: (value, bar) each (value -inf as the kernel defines it),
-      outside, impossible: counts."""
+def per_restaurant(K, n, t, h, a: float, bpar, tabs: Tables, indicators: bool = False):
+    """what truth() sums, restaurant by restaurant: a dict of Li, Li_bar, T, Nc, P_ld, P_bar [I] as truth() returns them and
+    comp, cbar [I][4] (P, H, R, B as mpf; their bars), out, imp_p, imp_h [I] (the restaurant's counts)"""
     mp = hp._mp()
     K = np.asarray(K, dtype=np.int64)
     I = K.shape[0]
@@ -155,14 +152,11 @@ def truth(K, n, t, h, a: float, bpar, tabs: Tables, indicators: bool = False):
     Li, Li_bar = np.zeros(I), np.zeros(I)
     Ts, Ns = np.zeros(I, dtype=np.int64), np.zeros(I, dtype=np.int64)
     P_ld, P_bar = np.zeros(I, dtype=LD), np.zeros(I)   # P_i in long double, and the sum of its cells' bars
-    tot = [mp.mpf(0)] * 4          # P, H, R, B
-    tot_bar = [0.0] * 4            # the per-restaurant bars
-    tot_abs = [0.0] * 4            # sum_i |value_i|: the block tree
-    outside = imp_p = imp_h = 0
+    comps, cbars = [], []
+    counts = np.zeros((3, I), dtype=np.int64)           # outside, impossible (S), impossible (h)
     for i in range(I):
         comp = [mp.mpf(0)] * 4
         cbar = [0.0] * 4
-        bad = False
         for j0 in range(koff[i], koff[i + 1], 64):
             mags = [0.0, 0.0, 0.0]
             for g in range(j0, min(j0 + 64, koff[i + 1])):
@@ -172,13 +166,11 @@ def truth(K, n, t, h, a: float, bpar, tabs: Tables, indicators: bool = False):
                 Ns[i] += ng
                 kind = classify(ng, tg, hg, tabs)
                 if kind == "imp_p":
-                    imp_p += 1
-                    bad = True
+                    counts[1, i] += 1
                 elif kind == "imp_h":
-                    imp_h += 1
-                    bad = True
+                    counts[2, i] += 1
                 elif kind == "out":
-                    outside += 1
+                    counts[0, i] += 1
                 elif kind == "in":
                     vals, bars = pair_terms(ng, tg, hg, tabs, indicators)
                     P_ld[i] += tabs.cell(ng, tg)[0]
@@ -191,13 +183,38 @@ def truth(K, n, t, h, a: float, bpar, tabs: Tables, indicators: bool = False):
                 cbar[slot] += 6.0 * U * mags[c]
         comp[2], cbar[2] = restaurant_term(a, float(bpar[i]), int(Ts[i]), int(Ns[i]))
         absum = sum(abs(float(x)) for x in comp)
+        bad = counts[1, i] + counts[2, i] > 0
         Li[i] = NEG_INF if bad else float(comp[0] + comp[1] + comp[2] + comp[3])
         Li_bar[i] = sum(cbar) + U * (2.0 * absum + 16.0)
+        comps.append(comp)
+        cbars.append(cbar)
+    return {"Li": Li, "Li_bar": Li_bar, "T": Ts, "Nc": Ns, "P_ld": P_ld, "P_bar": P_bar, "comp": comps, "cbar": cbars,
+            "out": counts[0], "imp_p": counts[1], "imp_h": counts[2]}
+
+
+def tiled(per, mult=None):
+    """the totals, their bars and the counts of a state in which restaurant i of `per` (per_restaurant's dict) occurs
+    mult[i] times (None: once): sums over the types of multiplicity x value, bars sums of multiplicity x the type's bar --
+    every per-restaurant term of the bar is linear in the restaurants, the block tree's 8 u sum_i |value_i| included; the
+    double-double terms 2 u |total| + 16 u are taken once, on the tiled totals.  Returns truth()'s dict (Li, Li_bar, T,
+    Nc, P_ld, P_bar stay per type)."""
+    mp = hp._mp()
+    I = len(per["comp"])
+    mult = np.ones(I, dtype=np.int64) if mult is None else np.asarray(mult, dtype=np.int64)
+    assert mult.shape == (I,) and (mult >= 0).all()
+    tot = [mp.mpf(0)] * 4          # P, H, R, B
+    tot_bar = [0.0] * 4            # the per-restaurant bars
+    tot_abs = [0.0] * 4            # sum_i |value_i|: the block tree
+    for i in range(I):
+        m = int(mult[i])
+        comp, cbar = per["comp"][i], per["cbar"][i]
         for c in range(4):
-            tot[c] += comp[c]
-            tot_bar[c] += cbar[c] + U * abs(float(comp[c]))   # (hi + lo of the restaurant's sum, where it has one)
-            tot_abs[c] += abs(float(comp[c]))
-    out = {"Li": Li, "Li_bar": Li_bar, "T": Ts, "Nc": Ns, "P_ld": P_ld, "P_bar": P_bar, "outside": outside, "impossible": imp_p + imp_h}
+            tot[c] += m * comp[c]
+            tot_bar[c] += m * (cbar[c] + U * abs(float(comp[c])))   # (hi + lo of the restaurant's sum, where it has one)
+            tot_abs[c] += m * abs(float(comp[c]))
+    outside, imp_p, imp_h = (int((mult * per[k]).sum()) for k in ("out", "imp_p", "imp_h"))
+    out = {k: per[k] for k in ("Li", "Li_bar", "T", "Nc", "P_ld", "P_bar")}
+    out.update({"outside": outside, "impossible": imp_p + imp_h})
     inner = [tot_bar[c] + 8.0 * U * tot_abs[c] for c in range(4)]
     for c, name in enumerate(("pairs", "base", "restaurants", "binom")):
         v = float(tot[c])
@@ -208,6 +225,16 @@ def truth(K, n, t, h, a: float, bpar, tabs: Tables, indicators: bool = False):
     out["total"] = (NEG_INF if imp_p or imp_h else float(total), sum(inner) + U * (2.0 * abs(float(total)) + 16.0))
     out["total_mp"] = total
     return out
+
+
+def truth(K, n, t, h, a: float, bpar, tabs: Tables, indicators: bool = False, mult=None):
+    """the truth and the bars of every output of stb_logjoint on the CSR state (K, n, t, h or None); mult (None: all 1):
+    restaurant i stands for mult[i] restaurants with its pairs and its b_i (tiled()).  A dict:
+      Li, Li_bar [I] (doubles; -inf where the restaurant holds an impossible pair), T, Nc [I] (the integer sums),
+      P_ld, P_bar [I]: P_i summed in long double and the sum of its cells' bars,
+      pairs, base, restaurants, binom, total: (value, bar) each (value -inf as the kernel defines it),
+      outside, impossible: counts."""
+    return tiled(per_restaurant(K, n, t, h, a, bpar, tabs, indicators), mult)
 
 
 def within(got, want, bar) -> bool:

@@ -1,5 +1,6 @@
 """The joint (a, b) step on the device (libstb_amd/csrc/hyperj.hip; DESIGN.md section 6, deviation 14): k_joint_terms
-against the high-precision truth and across launch geometries, the pair sum alone (stb_groups_ssum), the step against
+against the high-precision truth and across launch geometries -- also past one trip per workgroup in x and in j, on sizes
+taken from stb_reduce_geometry --, the pair sum alone (stb_groups_ssum), the step against
 the replay of tests/hj_oracle.py run on the device's own L values, the object wrappers, the refusals, and
 examples/pyp_resample -j.
 
@@ -17,6 +18,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from devarr import dev_coff, dev_u32
 import hj_oracle as hj
 import hp_oracle as hp
 import hp_pairs as hpp
@@ -27,12 +29,6 @@ from libstb_amd import capi, synth
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53
-
-
-def dev_u32(a):
-    import torch
-
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32), device="cuda")
 
 
 class waves:
@@ -117,6 +113,120 @@ def test_joint_terms_has_the_same_bits_for_every_geometry():
             got = capi.joint_terms(A64[ia], B64[ib], Td, Nd).cpu().numpy()
         ref = got if ref is None else ref
         assert np.array_equal(got, ref), wv
+
+
+# ---- k_joint_terms past one trip per workgroup, in x (blocks of restaurants) and in y (the b_j)
+
+HJ_CASES = ["ragged j", "J1", "x trip 3 x 2", "x trip 24 x 24", "x trip 64 x 64", "two x trips 1 x 1"]
+
+
+def hj_geom(I, DJ, wv=0):
+    return capi.reduce_geometry(capi.GEOM_JOINT_TERMS, I, DJ[0], DJ[1], wv)
+
+
+def hj_width():
+    """the workgroups of a launch with more steps than the device takes at once"""
+    return hj_geom(1 << 30, (1, 1)).grid_x
+
+
+def hj_case(label, wv=0):
+    """(I, (D, J)) and the case's premise, asserted through the query -- every size from the device at hand"""
+    W = hj_width()
+    if label == "ragged j":   # 17 blocks: the workgroups left over for j do not divide the 64 b_j evenly
+        I, DJ = 4352, (64, 64)
+        g = hj_geom(I, DJ)
+        assert g.grid_x == 17 and g.grid_y == W // 17 and g.grid_y < 64 and 64 % g.grid_y != 0, (g.grid_x, g.grid_y)
+    elif label == "J1":   # MEASUREMENTS section J1's shape: several j trips a workgroup
+        I, DJ = 10 ** 5, (24, 24)
+        g = hj_geom(I, DJ)
+        assert g.blocks == 391 and g.grid_x == g.steps and 2 * g.grid_y <= 24, (g.grid_x, g.grid_y)
+    else:
+        DJ = {"x trip 3 x 2": (3, 2), "x trip 24 x 24": (24, 24), "x trip 64 x 64": (64, 64), "two x trips 1 x 1": (1, 1)}[label]
+        span = 256 * hj_geom(1, DJ, wv).chunks
+        if label.startswith("two"):
+            I = 2 * span * W + 513
+            g = hj_geom(I, DJ, wv)
+            assert g.grid_x == W and g.steps > 2 * g.grid_x and g.grid_y == 1
+        else:   # a second x trip for one workgroup, and every j in one workgroup
+            I = span * W + 1
+            g = hj_geom(I, DJ, wv)
+            assert g.grid_x == W and g.steps == g.grid_x + 1 and g.grid_y == 1
+    return I, DJ
+
+
+def tiled_counts(I):
+    reps = -(-I // len(TYPES))
+    return np.tile([k[0] for k in TYPES], reps)[:I], np.tile([k[1] for k in TYPES], reps)[:I]
+
+
+def tiled_truth(I, DJ):
+    """the truth and the bar of R for restaurant i of type TYPES[i mod 10]: multiplicity x the type's"""
+    ia, ib = SUB[DJ]
+    tt = type_truth()
+    val = np.zeros((len(ia), len(ib)), dtype=hp.LD)
+    bar = np.zeros((len(ia), len(ib)))
+    for k, kind in enumerate(TYPES):
+        cnt = I // len(TYPES) + (k < I % len(TYPES))
+        v, e = tt[kind]
+        val += hp.LD(cnt) * v[np.ix_(ia, ib)]
+        bar += cnt * e[np.ix_(ia, ib)]
+    return val, bar + 4.0 * U * np.abs(val.astype(np.float64))
+
+
+def check_tiled(got, I, DJ, what):
+    val, bar = tiled_truth(I, DJ)
+    err = np.abs((got.astype(hp.LD) - val).astype(np.float64))
+    print("%s, I=%d, %d x %d: worst error / bar %.3g (worst error %.3e)" % (what, I, DJ[0], DJ[1], float((err / bar).max()), float(err.max())))
+    assert np.isfinite(got).all() and (err <= bar).all()
+
+
+@pytest.mark.parametrize("label", HJ_CASES)
+def test_joint_terms_past_one_trip_against_the_truth(label):
+    I, DJ = hj_case(label)
+    ia, ib = SUB[DJ]
+    T, N = tiled_counts(I)
+    Td = dev_u32(T)
+    got = capi.joint_terms(A64[ia], B64[ib], Td, dev_u32(N)).cpu().numpy()
+    check_tiled(got, I, DJ, label)
+    # N as prefix sums (the objects' route) gives the same bits
+    got2 = capi.joint_terms(A64[ia], B64[ib], Td, None, coff=dev_coff(N)).cpu().numpy()
+    assert np.array_equal(got2, got)
+
+
+def test_joint_terms_past_one_trip_has_the_same_bits_for_every_geometry():
+    """24 x 24 at the size where a workgroup of eight waves makes a second x trip: every workgroup size makes one"""
+    DJ = (24, 24)
+    I, _ = hj_case("x trip 24 x 24", wv=8)
+    ia, ib = SUB[DJ]
+    T, N = tiled_counts(I)
+    Td, Nd = dev_u32(T), dev_u32(N)
+    ref = None
+    for wv in (1, 2, 4, 8, 4):
+        g = hj_geom(I, DJ, wv)
+        assert g.steps > g.grid_x and g.grid_y == 1 and g.chunks == (2 if wv == 8 else 1)
+        with waves(wv):
+            assert hj_geom(I, DJ).waves == wv
+            got = capi.joint_terms(A64[ia], B64[ib], Td, Nd).cpu().numpy()
+        if ref is None:
+            ref = got
+            check_tiled(got, I, DJ, "x trip at eight waves")
+        assert np.array_equal(got, ref), wv
+
+
+def test_joint_terms_outgrows_its_block_sums_and_is_called_again():
+    DJ = (24, 24)
+    ia, ib = SUB[DJ]
+    small, big = 2049, hj_case("J1")[0]
+    gs, gb = hj_geom(small, DJ), hj_geom(big, DJ)
+    assert gs.need <= gs.cap0 < gb.need
+    capi.lib().stb_sampler_cache_clear()   # (this thread's buffer of block sums: the next call allocates cap0 afresh)
+    out = []
+    for I in (small, big, small, big):
+        T, N = tiled_counts(I)
+        out.append(capi.joint_terms(A64[ia], B64[ib], dev_u32(T), dev_u32(N)).cpu().numpy())
+    check_tiled(out[0], small, DJ, "before the larger call")
+    check_tiled(out[1], big, DJ, "the larger call")
+    assert np.array_equal(out[2], out[0]) and np.array_equal(out[3], out[1])
 
 
 # ---- stb_groups_ssum

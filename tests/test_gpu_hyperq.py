@@ -1,5 +1,6 @@
 """The hyper-parameter half of the Gibbs loop from device-resident counts: stb_sample_logq (hyperq.hip) against its
-numpy replay and its law, Q's reduction, the b step on the tcounts / tindic objects, stb_groups_samplea on sets the
+numpy replay and its law, Q's reduction -- also past one trip per workgroup and past the block sums first allocated, on
+sizes taken from stb_reduce_geometry --, the b step on the tcounts / tindic objects, stb_groups_samplea on sets the
 device filled, the refusals, and examples/pyp_resample -d."""
 import ctypes as C
 import math
@@ -10,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from devarr import dev_coff, dev_u32
 import hq_oracle as hq
 import orc
 from libstb_amd import capi, synth
@@ -17,12 +19,6 @@ from libstb_amd import capi, synth
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53
-
-
-def dev_u32(a):
-    import torch
-
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32), device="cuda")
 
 
 class waves:
@@ -94,6 +90,121 @@ def test_Q_without_restaurants_is_one_over_scale():
     assert Q == 0.25
     Q, Lt = capi.sample_logq(1.0, 4.0, dev_u32(np.zeros(300)), seed=1, sweep=0)
     assert Q == 0.25 and (Lt.cpu().numpy() == 0).all()
+
+
+# ---- past one trip per workgroup
+
+HQ_CASES = ["second trip, four waves", "second trip, eight waves", "third trip, four waves", "third trip, eight waves",
+            "odd chunks, eight waves"]
+
+
+def hq_geom(I, wv=0):
+    return capi.reduce_geometry(capi.GEOM_LOGQ, I, waves=wv)
+
+
+def hq_case(label):
+    """I and the case's premise, asserted through the query -- every size from the device at hand"""
+    wv = 8 if "eight" in label else 4
+    W = hq_geom(1 << 30, wv).grid_x
+    span = 256 * hq_geom(1, wv).chunks
+    assert span == (512 if wv == 8 else 256)
+    if label.startswith("second"):
+        I = span * W + 1
+        g = hq_geom(I, wv)
+        assert g.grid_x == W and g.steps == g.grid_x + 1
+    elif label.startswith("third"):
+        I = 2 * span * W + 257 + 64
+        g = hq_geom(I, wv)
+        assert g.grid_x == W and g.steps > 2 * g.grid_x and g.blocks == 2 * g.chunks * W + 2
+    else:   # the last step of a workgroup of eight waves holds one block, not two
+        I = 2 * span * W + 64
+        g = hq_geom(I, wv)
+        assert g.chunks == 2 and g.blocks % 2 == 1 and g.steps > 2 * g.grid_x
+    return I
+
+
+def trip_windows(I):
+    """the first 512 restaurants, the 512 either side of every trip boundary (at four and at eight waves), the last 512"""
+    starts = {0, max(I - 512, 0)}
+    for wv in (4, 8):
+        g = hq_geom(I, wv)
+        trip = g.grid_x * g.chunks * 256
+        starts |= {k - 512 for k in range(trip, I, trip)}
+        assert g.steps <= g.grid_x or any(k for k in range(trip, I, trip))
+    return sorted(starts)
+
+
+def check_L_on_windows(L, N, b, seed, sweep, what):
+    """test_L_equals_the_replay's criterion on the windows: outside 1e-12 at most one restaurant in 10^5, rounded down --
+    none, the windows holding fewer than 10^5"""
+    I = len(N)
+    nout = ntot = 0
+    for w0 in trip_windows(I):
+        w1 = min(w0 + 1024, I) if 0 < w0 < I - 512 else min(w0 + 512, I)
+        want = hq.replay_L(b, N[w0:w1], seed=seed, sweep=sweep, first=w0)
+        got = L[w0:w1]
+        assert (got[N[w0:w1] == 0] == 0).all() and np.isfinite(got).all() and (got[N[w0:w1] > 0] > 0).all()
+        out = np.abs(got - want) > 1e-12 * np.maximum(1.0, want)
+        nout += int(out.sum())
+        ntot += w1 - w0
+    print("%s: %d of %d restaurants on the windows outside 1e-12" % (what, nout, ntot))
+    assert ntot >= 1024 and nout <= ntot // 10 ** 5
+
+
+def all_geometries(I, N, b, scale, seed, sweep):
+    """(Q, L) for 1, 2, 4, 8 waves and again 4: the same bits each time; and with the customers as prefix sums"""
+    Nd = dev_u32(N)
+    Q0 = L0 = None
+    for wv in (1, 2, 4, 8, 4):
+        with waves(wv):
+            assert hq_geom(I).waves == wv
+            Q, Lt = capi.sample_logq(b, scale, Nd, seed=seed, sweep=sweep)
+        L = Lt.cpu().numpy()
+        if L0 is None:
+            Q0, L0 = Q, L
+        assert np.array_equal(L, L0) and Q == Q0, (wv, Q.hex(), Q0.hex())
+    Q2, none = capi.sample_logq(b, scale, Nd, seed=seed, sweep=sweep, want_L=False)
+    assert none is None and Q2 == Q0
+    Q3, Lt = capi.sample_logq(b, scale, None, seed=seed, sweep=sweep, coff=dev_coff(N))
+    assert Q3 == Q0 and np.array_equal(Lt.cpu().numpy(), L0)
+    return Q0, L0
+
+
+def check_Q(Q, L, I, scale, what):
+    want = 1.0 / scale + math.fsum(L)
+    print("%s I=%d: Q=%.17g, |Q - fsum| = %.3e (bar %.3e)" % (what, I, Q, abs(Q - want), 4 * U * I * abs(Q)))
+    assert abs(Q - want) <= 4 * U * I * abs(Q)
+
+
+@pytest.mark.parametrize("label", HQ_CASES)
+def test_L_and_Q_past_one_trip_per_workgroup(label):
+    I = hq_case(label)
+    N = hq.mixed_restaurants(I)
+    b, scale = 0.7, 20.0
+    Q, L = all_geometries(I, N, b, scale, seed=4711, sweep=3)
+    check_L_on_windows(L, N, b, 4711, 3, label)
+    assert (L[N == 0] == 0).all() and np.isfinite(L).all() and (L[N > 0] > 0).all()
+    check_Q(Q, L, I, scale, label)
+
+
+def test_a_call_that_outgrows_the_block_sums_and_the_calls_after_it():
+    cap0 = int(hq_geom(1).cap0)
+    big, small = cap0 * 256 + 1, 1000
+    gb, gs = hq_geom(big), hq_geom(small)
+    assert gb.need == gb.cap0 + 1 and gs.need <= gs.cap0
+    b, scale = 0.7, 20.0
+    Nb, Ns = hq.mixed_restaurants(big), hq.mixed_restaurants(small)
+    capi.lib().stb_sampler_cache_clear()   # (this thread's buffer of block sums: the next call allocates cap0 afresh)
+    Qs, Lts = capi.sample_logq(b, scale, dev_u32(Ns), seed=31, sweep=2)
+    Ls = Lts.cpu().numpy()
+    Q, L = all_geometries(big, Nb, b, scale, seed=31, sweep=2)   # replaces the buffer
+    check_L_on_windows(L, Nb, b, 31, 2, "regrow")
+    check_Q(Q, L, big, scale, "regrow")
+    Qs2, Lts2 = capi.sample_logq(b, scale, dev_u32(Ns), seed=31, sweep=2)   # a smaller call in the larger buffer
+    assert Qs2 == Qs and np.array_equal(Lts2.cpu().numpy(), Ls)
+    check_Q(Qs, Ls, small, scale, "after the larger call")
+    Q2, Lt2 = capi.sample_logq(b, scale, dev_u32(Nb), seed=31, sweep=2)    # ... and the large one again
+    assert Q2 == Q and np.array_equal(Lt2.cpu().numpy(), L)
 
 
 # ---- law

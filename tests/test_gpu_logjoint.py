@@ -2,7 +2,9 @@
 libstb_amd/csrc/logjoint.hip) against the high-precision truth and the bar of tests/lj_oracle.py -- derived there from
 the kernel's own operations --, across launch geometries, on inputs built to trigger every counter, on the two objects,
 and with refused arguments.  Shapes: tables N = 48 with M = 48 and M = 7; restaurants of 0, 1, 63, 64, 65 and 129 pairs
-(the chunk edges) and sets of 1, 255, 256, 257 and 513 restaurants (the block edges)."""
+(the chunk edges) and sets of 1, 255, 256, 257 and 513 restaurants (the block edges); tiled states of 1031 types past one
+trip per workgroup, past the 1024 block sums the last workgroup stages at a time and past the block sums first
+allocated, every size taken from stb_reduce_geometry."""
 import ctypes as C
 import math
 import os
@@ -323,6 +325,280 @@ def test_objects_without_a_table_read_none(kind):
             assert info.t_mismatch == 0 and info.outside == 0
         finally:
             obj.free()
+
+
+# ---- past one trip per workgroup: tiled states, restaurant i of type i mod P_TYPES (the truth once per type)
+
+P_TYPES = 1031  # prime: no two blocks a workgroup takes hold the same restaurants in the same slots
+CONFIGS = [(0.5, 7, True, True), (0.0, 48, False, False)]  # (a, M, indicators, with h)
+LJ_CASES = ["tail", "two trips", "stage 1024", "stage 1025", "stage 2049"]
+
+
+def lj_geom(I, wv=0):
+    return capi.reduce_geometry(capi.GEOM_LOGJOINT, I, waves=wv)
+
+
+def lj_width():
+    """the workgroups of a launch with more blocks than the device takes at once"""
+    return lj_geom(1 << 30).grid_x
+
+
+def lj_case(label):
+    """(I, its premise, asserted through the query) -- every size from the geometry of the device at hand"""
+    W = lj_width()
+    if label == "tail":  # one workgroup takes a one-restaurant tail block after a full one
+        I = W * 256 + 1
+        g = lj_geom(I)
+        assert (g.grid_x, g.steps, g.blocks) == (W, W + 1, W + 1) and g.chunks == 1
+    elif label == "two trips":  # two or three trips a workgroup, the last block of 129 restaurants
+        I = (2 * W + 2) * 256 + 129
+        g = lj_geom(I)
+        assert g.grid_x == W and g.steps == 2 * g.grid_x + 3
+    elif label == "regrow":  # one block sum more than the buffer first allocated holds
+        I = int(lj_geom(1).cap0) * 256 + 1
+        g = lj_geom(I)
+        assert g.need == g.cap0 + 1 and g.need == g.blocks
+    else:  # the edges of the last workgroup's staging loop (LJ_STAGE = 1024 block sums a round)
+        nblk = int(label.split()[1])
+        I = {1024: 1024 * 256, 1025: 1024 * 256 + 1, 2049: 2048 * 256 + 77}[nblk]
+        assert lj_geom(I).blocks == nblk
+    return I
+
+
+def type_state(M, seed):
+    """P_TYPES restaurants of 0 .. 3 pairs, four of 65 and 129, every fifth without customers (block_state's kinds)"""
+    rng = np.random.default_rng(seed)
+    K = rng.integers(0, 4, size=P_TYPES).astype(np.int32)
+    K[[11, 401, 777, 1029]] = [65, 129, 65, 129]
+    K, n, t, h = make_state(K, M, seed + 1)
+    koff = np.concatenate([[0], np.cumsum(K)])
+    for i in range(0, P_TYPES, 5):
+        n[koff[i]:koff[i + 1]] = 0
+        t[koff[i]:koff[i + 1]] = 0
+    return K, n, t, h
+
+
+def type_mult(I, first=0):
+    """how often each type occurs among I restaurants, restaurant i of type (first + i) mod P_TYPES"""
+    return np.roll(I // P_TYPES + (np.arange(P_TYPES) < I % P_TYPES), first)
+
+
+def first_for(I, last_type=1029):
+    """the type to start the tiling at for the last of I restaurants to be of `last_type` (129 pairs): a one-restaurant tail
+    block then weighs in every sum"""
+    return (last_type - (I - 1)) % P_TYPES
+
+
+class Tiled:
+    """the types tiled to I restaurants, restaurant i of type (first + i) mod P_TYPES, on the device once"""
+
+    def __init__(self, K, n, t, h, bpar, T, I, first=0):
+        assert 0 <= first < P_TYPES
+        reps = -(-I // P_TYPES) + 1
+        self.I, self.reps, self.first = I, reps, first
+        kofft = np.concatenate([[0], np.cumsum(np.tile(K, reps), dtype=np.int64)])
+        g0, g1 = int(kofft[first]), int(kofft[first + I])
+        self.koff = dev((kofft[first:first + I + 1] - g0).astype(np.uint64), np.uint64)
+        self.n, self.t = dev(np.tile(n, reps)[g0:g1], np.uint32), dev(np.tile(t, reps)[g0:g1], np.uint16)
+        self.h = None if h is None else dev(np.tile(h, reps)[g0:g1], np.float64)
+        self.b = dev(self.tile(bpar), np.float64)
+        self.T = dev(self.tile(T), np.uint32)
+
+    def run(self, tabs, a, indicators, want_Li=True):
+        import torch
+
+        tot, Li, info = capi.logjoint(tabs, a, self.b, self.koff, self.n, self.t, self.T, self.h, indicators, want_Li)
+        torch.cuda.synchronize()
+        return tot, None if Li is None else Li.cpu().numpy(), info
+
+    def tile(self, x):
+        return np.tile(x, self.reps)[self.first:self.first + self.I]
+
+
+@lru_cache(maxsize=None)
+def clean_types(cfg):
+    """the types of a configuration, their per-type truth, and the device's L_i of the P_TYPES alone -- held to the truth"""
+    a, M, indicators, with_h = CONFIGS[cfg]
+    K, n, t, h = type_state(M, seed=900 + cfg)
+    h = h if with_h else None
+    bpar = b_values(P_TYPES, a)
+    assert set(K) >= {0, 1, 2, 3, 65, 129} and (a != 0.5 or (bpar < 0).any())
+    per = lj.per_restaurant(K, n, t, h, a, bpar, truth_tables(a, M), indicators)
+    assert (per["Nc"] == 0).sum() >= P_TYPES // 5
+    tr = lj.tiled(per)
+    tot, Li, info = run_raw(device_tables(a, M), a, bpar, K, n, t, h, indicators, T=tr["T"])
+    check_against(tr, tot, Li, info, indicators, f"types a={a} M={M}")
+    assert info.outside == 0 and info.impossible == 0 and info.t_mismatch == 0
+    return (K, n, t, h, bpar), per, Li
+
+
+def check_totals(tr, tot, info, what):
+    """the four components and the total within the bar of the tiled truth"""
+    worst = 0.0
+    for name, got in (("pairs", info.pairs), ("base", info.base), ("restaurants", info.restaurants), ("binom", info.binom),
+                      ("total", tot)):
+        want, bar = tr[name]
+        ratio = 0.0 if got == want else abs(got - want) / bar if bar > 0 else math.inf
+        worst = max(worst, ratio)
+        print("%s %s: %.17g, truth %.17g, bar %.3e, error / bar %.3g" % (what, name, got, want, bar, ratio))
+        assert not math.isnan(got) and lj.within(got, want, bar), (what, name, got, want, bar)
+    print("%s: worst error / bar %.3g" % (what, worst))
+
+
+def same_bits_for_every_workgroup_size(tl, tabs, a, indicators, ref):
+    for wv in (1, 2, 4, 8, 0):
+        with waves(wv):
+            tot, Li, info = tl.run(tabs, a, indicators)
+        assert (np.float64(tot).tobytes(), Li.tobytes(), bytes(info)) == ref, wv
+    tot, none, info = tl.run(tabs, a, indicators, want_Li=False)
+    assert none is None and (np.float64(tot).tobytes(), bytes(info)) == (ref[0], ref[2])
+
+
+@pytest.mark.parametrize("cfg", [0, 1])
+@pytest.mark.parametrize("label", LJ_CASES)
+def test_tiled_states_past_one_trip_per_workgroup(label, cfg):
+    a, M, indicators, with_h = CONFIGS[cfg]
+    I = lj_case(label)
+    same = [x for x in LJ_CASES[:LJ_CASES.index(label)] if lj_case(x) == I]
+    if same:   # the same restaurants as an earlier case on this device, which ran the checks; both premises hold
+        print("%s: I=%d is the case %r on this device, nothing more is run here" % (label, I, same[0]))
+        return
+    (K, n, t, h, bpar), per, Li_types = clean_types(cfg)
+    first = first_for(I) if I % 256 == 1 else 0   # (a tail block of one restaurant: one with 129 pairs)
+    tl = Tiled(K, n, t, h, bpar, per["T"], I, first)
+    tabs = device_tables(a, M)
+    tot, Li, info = tl.run(tabs, a, indicators)
+    # (i) every restaurant has the bits of its type
+    assert np.array_equal(Li.view(np.uint64), tl.tile(Li_types.view(np.uint64)))
+    assert I % 256 != 1 or (K[(first + I - 1) % P_TYPES] == 129 and Li[-1] != 0.0)
+    # (ii) the sums against the tiled truth
+    check_totals(lj.tiled(per, type_mult(I, first)), tot, info, f"{label} I={I} a={a} M={M}")
+    assert info.outside == 0 and info.impossible == 0 and info.t_mismatch == 0
+    if not indicators:
+        assert info.binom == 0.0
+    # (iii) the same bytes for every workgroup size, and without the L_i
+    same_bits_for_every_workgroup_size(tl, tabs, a, indicators, (np.float64(tot).tobytes(), Li.tobytes(), bytes(info)))
+
+
+@pytest.mark.parametrize("cfg", [0, 1])
+def test_a_call_that_outgrows_the_block_sums_and_the_calls_after_it(cfg):
+    a, M, indicators, with_h = CONFIGS[cfg]
+    I = lj_case("regrow")
+    (K, n, t, h, bpar), per, Li_types = clean_types(cfg)
+    tabs = device_tables(a, M)
+    capi.lib().stb_sampler_cache_clear()  # (this thread's buffer of block sums: the next call allocates cap0 afresh)
+    small = Tiled(K, n, t, h, bpar, per["T"], 257)
+    tot_s, Li_s, info_s = small.run(tabs, a, indicators)
+    check_totals(lj.tiled(per, type_mult(257)), tot_s, info_s, f"I=257 a={a} M={M}")
+    first = first_for(I)
+    big = Tiled(K, n, t, h, bpar, per["T"], I, first)
+    tot, Li, info = big.run(tabs, a, indicators)   # replaces the buffer
+    assert np.array_equal(Li.view(np.uint64), big.tile(Li_types.view(np.uint64))) and Li[-1] != 0.0
+    check_totals(lj.tiled(per, type_mult(I, first)), tot, info, f"regrow I={I} a={a} M={M}")
+    assert info.outside == 0 and info.impossible == 0 and info.t_mismatch == 0
+    ref = (np.float64(tot).tobytes(), Li.tobytes(), bytes(info))
+    tot2, Li2, info2 = small.run(tabs, a, indicators)   # a smaller call in the larger buffer
+    assert (np.float64(tot2).tobytes(), Li2.tobytes(), bytes(info2)) == (np.float64(tot_s).tobytes(), Li_s.tobytes(), bytes(info_s))
+    same_bits_for_every_workgroup_size(big, tabs, a, indicators, ref)   # ... and the first call again
+
+
+def test_counters_accumulate_over_a_workgroups_trips():
+    """types with impossible pairs, outside pairs and d_T off by one among the clean ones: the counts are the sums of
+    multiplicity x the type's, the sums -inf and never NaN, and a clean type keeps its bits (no flag left from a trip)"""
+    a, M, indicators = 0.5, 7, True
+    (K, n, t, h, bpar), _, Li_clean = clean_types(0)
+    n, t, h = n.copy(), t.copy(), h.copy()
+    koff = np.concatenate([[0], np.cumsum(K)])
+    have = [i for i in range(P_TYPES) if K[i] >= 1]
+    kinds = ["t > n", "t = 0 < n", "h = 0", "h < 0", "n > N", "t > M"]
+    changed = {}
+    for j, i in enumerate(have[3::9][:60]):
+        g = koff[i] + (K[i] - 1) * (j % 2)   # the type's first pair, or its last
+        kind = kinds[j % len(kinds)]
+        n[g], t[g], h[g] = {"t > n": (5, 6, 1.0), "t = 0 < n": (9, 0, 0.5), "h = 0": (6, 2, 0.0), "h < 0": (4, 4, -1.0),
+                            "n > N": (60, 3, 0.5), "t > M": (20, 10, 0.5)}[kind]
+        changed[i] = kind
+    per = lj.per_restaurant(K, n, t, h, a, bpar, truth_tables(a, M), indicators)
+    off = np.zeros(P_TYPES, dtype=np.int64)   # d_T off by one, on types with and without pairs, clean and not
+    off[2::50] = 1
+    off[27::50] = -1
+    off[min(changed)] = 1
+    off[per["T"] + off < 0] = 1
+    clean = np.array([i not in changed for i in range(P_TYPES)])
+    assert (off[clean] != 0).sum() >= 10 and (off[~clean] != 0).sum() >= 1 and (K[off != 0] == 0).any()
+    # the types alone, held to the truth
+    tr1 = lj.tiled(per)
+    assert tr1["outside"] == 20 and tr1["impossible"] == 40
+    tot1, Li_types, info1 = run_raw(device_tables(a, M), a, bpar, K, n, t, h, indicators, T=per["T"] + off)
+    check_against(tr1, tot1, Li_types, info1, indicators, "counter types")
+    assert info1.t_mismatch == (off != 0).sum()
+    imp = (per["imp_p"] + per["imp_h"]) > 0
+    assert np.array_equal(np.isneginf(Li_types), imp) and np.isfinite(Li_types[~imp]).all()
+    assert np.array_equal(Li_types[clean].view(np.uint64), Li_clean[clean].view(np.uint64))
+    # tiled past two trips a workgroup
+    I = lj_case("two trips")
+    mult = type_mult(I)
+    tr = lj.tiled(per, mult)
+    tl = Tiled(K, n, t, h, bpar, per["T"] + off, I)
+    ref = None
+    for wv in (0, 1, 8):
+        with waves(wv):
+            tot, Li, info = tl.run(device_tables(a, M), a, indicators)
+        assert info.outside == tr["outside"] == int((mult * per["out"]).sum()) and info.outside >= 20 * (I // P_TYPES)
+        assert info.impossible == tr["impossible"] and info.t_mismatch == int((mult * (off != 0)).sum())
+        assert not np.isnan(Li).any() and not any(math.isnan(x) for x in (tot, info.pairs, info.base, info.restaurants, info.binom))
+        assert tot == -math.inf and info.pairs == -math.inf and info.base == -math.inf
+        assert lj.within(info.restaurants, *tr["restaurants"]) and lj.within(info.binom, *tr["binom"])
+        assert np.array_equal(Li.view(np.uint64), tl.tile(Li_types.view(np.uint64)))
+        got = (Li.tobytes(), bytes(info))
+        ref = got if ref is None else ref
+        assert got == ref, wv
+    assert np.isfinite(Li[tl.tile(~imp)]).all()
+
+
+@pytest.mark.parametrize("kind", ["tcounts", "tindic"])
+def test_objects_at_a_second_trip_equal_the_raw_calls(kind):
+    """an object of gx * 256 + 1 restaurants (K_i <= 1, n <= 3: nothing to sweep): its log joint has the bits of the raw call,
+    and its b step's Q -- the customers as d_coff prefix sums for stb_tindic -- the bits of stb_sample_logq on d_N"""
+    L = capi.lib()
+    I = lj_case("tail")
+    rng = np.random.default_rng(77)
+    K = (rng.random(I) < 0.8).astype(np.int32)
+    G = int(K.sum())
+    n = rng.integers(1, 4, size=G).astype(np.uint32)
+    t = (1 + np.floor(rng.random(G) * n)).astype(np.uint16)
+    h = 0.05 + 0.95 * rng.random(G)
+    assert n.max() == 3 and (t <= n).all() and (t == 2).any() and (K == 0).any()
+    a, b = 0.5, 2.0
+    bpar = np.full(I, b)
+    koff = np.concatenate([[0], np.cumsum(K)])
+    Ncust = np.zeros(I, dtype=np.int64)
+    Ncust[K > 0] = n
+    Tsum = np.zeros(I, dtype=np.int64)
+    Tsum[K > 0] = t
+    obj = capi.TableCounts(K, n, t, h) if kind == "tcounts" else capi.TableIndicators(K, n, t, h)
+    try:
+        tabs = capi.DeviceTables(3, 3)
+        tabs.fill(a)
+        tabs.status()
+        for ind in (False, True):
+            tot, Li, info = obj.logjoint(a, bpar, ind)
+            tot_r, Li_r, info_r = run_raw(tabs, a, bpar, K, n, t, h, ind, T=Tsum)
+            assert np.float64(tot).tobytes() == np.float64(tot_r).tobytes()
+            assert Li.tobytes() == Li_r.tobytes() and bytes(info) == bytes(info_r)
+            assert info.t_mismatch == 0 and info.outside == 0 and info.impossible == 0 and math.isfinite(tot)
+        t2, T2 = obj.get()
+        assert np.array_equal(t2, t) and np.array_equal(T2, Tsum)
+        # the b step's Q
+        assert capi.reduce_geometry(capi.GEOM_LOGQ, I).steps > capi.reduce_geometry(capi.GEOM_LOGQ, I).grid_x
+        orc.seed_libc(3, 4)
+        bn = obj.sampleb(b, 1.1, 20.0, a, seed=515, sweep=6)
+        Q = L.stb_sampleb_last_Q()
+        Qr, _ = capi.sample_logq(b, 20.0, dev(Ncust, np.uint32), seed=515, sweep=6, want_L=False)
+        assert 0.01 <= bn <= 2000 and Q == Qr and math.isfinite(Q) and Q > 1 / 20.0
+    finally:
+        obj.free()
+        L.stb_sampler_cache_clear()
 
 
 # ---- refusals of the raw call

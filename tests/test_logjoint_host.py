@@ -154,3 +154,29 @@ def test_impossible_and_outside_pairs_are_classified_as_the_kernel_does():
     assert tr["Li"][0] == -math.inf and tr["Li"][1] == -math.inf and tr["total"][0] == -math.inf
     assert tr["pairs"][0] == -math.inf and tr["base"][0] == -math.inf and math.isfinite(tr["restaurants"][0])
     assert list(tr["T"]) == [25, 3] and list(tr["Nc"]) == [39, 8]
+
+
+def test_a_tiled_truth_equals_the_truth_of_the_state_written_out():
+    """truth(mult=...) -- what the device's sums over 10^6 restaurants are held to -- against the same restaurants one by one"""
+    a, M = 0.5, 7
+    K, n, t, h = state(11, 7, 5, N48, M)
+    n[5], t[5] = 60, 3      # outside
+    n[9], t[9] = 4, 5       # impossible
+    bpar = np.array([1e-3, 1.0, 1e3, -0.25, 2.0, 0.5, 7.0])
+    tabs = lj.Tables(a, N48, M)
+    mult = np.array([3, 0, 1, 4, 2, 1, 5])
+    tiled = lj.truth(K, n, t, h, a, bpar, tabs, True, mult=mult)
+    koff = np.concatenate([[0], np.cumsum(K)])
+    idx = np.repeat(np.arange(len(K)), mult)
+    pick = np.concatenate([np.arange(koff[i], koff[i + 1]) for i in idx]).astype(np.int64)
+    full = lj.truth(K[idx], n[pick], t[pick], h[pick], a, bpar[idx], tabs, True)
+    assert tiled["outside"] == full["outside"] and tiled["impossible"] == full["impossible"]
+    assert tiled["outside"] + tiled["impossible"] > 0
+    for name in ("pairs", "base", "restaurants", "binom", "total"):
+        (v1, b1), (v2, b2) = tiled[name], full[name]
+        assert (v1 == v2 or abs(v1 - v2) <= 4 * U * abs(v2)) and abs(b1 - b2) <= 1e-12 * b2, (name, tiled[name], full[name])
+    assert abs(float(tiled["total_mp"] - full["total_mp"])) <= 1e-25 * abs(float(full["total_mp"]))
+    # and without multiplicities nothing changed
+    one = lj.truth(K, n, t, h, a, bpar, tabs, True, mult=np.ones(len(K), dtype=np.int64))
+    ref = lj.truth(K, n, t, h, a, bpar, tabs, True)
+    assert all(one[k] == ref[k] for k in ("pairs", "base", "restaurants", "binom", "total", "outside", "impossible"))
