@@ -20,10 +20,13 @@
  *      independence Metropolis-Hastings step from nested grids on [0.02, 0.97] x [0.05, 500] (stb_hip.h).
  *   8. with -L the device loop (-d or -j) prints the log joint probability of the state after every iteration
  *      (stb_tindic_logjoint, the table-indicator representation): one launch on the resident counts, 64 bytes back.
+ *   9. with -z the device loop also moves the data: before each indicator sweep every customer leaves its dish and is
+ *      seated again at any dish of its restaurant (stb_tindic_sweep_dishes), under a likelihood with two synthetic
+ *      classes (even customers favour even dishes, odd customers odd ones); n changes on the device and comes back once.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z]
  */
 #include <math.h>
 #include <stdio.h>
@@ -39,10 +42,10 @@
 #define DISHES 50
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djL")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLz")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -54,6 +57,7 @@ int main(int argc, char **argv) {
     else if (c == 'd') ondev = 1;
     else if (c == 'j') ondev = joint = 1;
     else if (c == 'L') showlj = 1;
+    else if (c == 'z') ondev = dishes = 1;
     else return 2;
   }
   srand48(seed);
@@ -121,12 +125,26 @@ int main(int argc, char **argv) {
         hf[g] = 1.0 / DISHES;
       }
     for (cc = 0; cc < (size_t)J * ncust; cc++) cust[cc] = (scnt_int)dish_of[cc]; /* (K = DISHES: the dish is the local pair) */
-    stb_tindic_t *ti = stb_tindic_create(J, K, nf, tf, hf, cust, maxn > 65535 ? 65535 : 0, 0);
+    stb_tindic_t *ti = stb_tindic_create(J, K, nf, tf, hf, cust, maxn > 65535 || (dishes && ncust > 65535) ? 65535 : 0, 0);
     stb_groups_t *gs = stb_groups_create(J, K, NULL, NULL, NULL, NULL, 0, 0, joint ? 25 : 3);
     int accepted = 0, steps = 0;
     if (!ti || !gs) yaps_quit("device loop: %s\n", stb_last_error());
     for (j = 0; j < J; j++) bvec[j] = b;
+    unsigned long long stuck = 0;
+    if (dishes) { /* two classes by the customer's parity; a class likes the dishes of its parity twice as much */
+      scnt_int *cls = malloc(sizeof(*cls) * (size_t)J * ncust);
+      double lik[2 * DISHES];
+      for (cc = 0; cc < (size_t)J * ncust; cc++) cls[cc] = (scnt_int)(cc & 1);
+      for (i = 0; i < 2 * DISHES; i++) lik[i] = ((i % DISHES) & 1) == i / DISHES ? 1.0 : 0.5;
+      if (stb_tindic_set_classes(ti, cls, 2) || stb_tindic_set_lik(ti, lik, 2, DISHES)) yaps_quit("dishes: %s\n", stb_last_error());
+      free(cls);
+    }
     for (it = 0; it < cycles; it++) {
+      if (dishes) {
+        stb_tdish_info_t di;
+        if (stb_tindic_sweep_dishes(ti, a, bvec, (uint64_t)seed + 2, (uint64_t)it, 1, &di)) yaps_quit("stb_tindic_sweep_dishes: %s\n", stb_last_error());
+        stuck += di.stuck + di.skipped;
+      }
       if (stb_tindic_sweep(ti, a, bvec, (uint64_t)seed, (uint64_t)it, 1)) yaps_quit("stb_tindic_sweep: %s\n", stb_last_error());
       if (it % 3 == 2 && joint) {
         stb_joint_opts_t jo = {0.02, 0.97, 0.05, 500.0, 24, 24, 1.1, 20.0, (uint64_t)seed + 1, (uint64_t)it, 0};
@@ -165,6 +183,18 @@ int main(int argc, char **argv) {
     if (joint) printf("joint steps: %d of %d proposals accepted, last a=%.4f b=%.3f\n", accepted, steps, a, b);
     for (j = 0, g = 0; j < J; j++)
       for (i = 0; i < DISHES; i++, g++) t[j][i] = tf[g];
+    if (dishes) { /* the customers moved: n comes back too */
+      unsigned long long moved = 0;
+      if (stb_tindic_get_state(ti, nf, cust)) yaps_quit("stb_tindic_get_state: %s\n", stb_last_error());
+      for (j = 0, g = 0; j < J; j++)
+        for (i = 0; i < DISHES; i++, g++) {
+          n[j][i] = nf[g];
+          if (nf[g] >= maxn) maxn = nf[g] + 1;
+        }
+      for (cc = 0; cc < (size_t)J * ncust; cc++) moved += cust[cc] != (scnt_int)dish_of[cc];
+      printf("dish sweeps: %llu of %llu customers ended at another dish, %llu visits found none\n", moved,
+             (unsigned long long)J * ncust, stuck);
+    }
     stb_groups_free(gs);
     stb_tindic_free(ti);
     free(nf);

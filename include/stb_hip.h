@@ -561,6 +561,77 @@ double stb_tindic_sampleb(stb_tindic_t *s, double b_in, double shape, double sca
                           int loops, int verbose, uint64_t seed, uint64_t sweep);
 void stb_tindic_free(stb_tindic_t *s);
 
+/* ---- dishes: the step that moves data.  Every customer leaves its dish and is seated again, at any dish of its
+ * restaurant, under a likelihood that is a fixed table during the sweep; restaurants stay independent and the sweep is
+ * exact.  The reference has no such step (test/demo.c:405-434 re-seats a customer in its own dish):
+ * like stb_tcounts_partition this is additive.  Pairs, h, T_i, b_i, a, cust / coff and the V slab as for stb_sample_tindic;
+ * cust is required and is written.  cls[c] (uint32, flat customer index c) is the customer's likelihood class, lik a device
+ * matrix of rows x stride doubles, row-major, finite and >= 0: L_k = lik[cls[c] * stride + k] for local pair k.  lik == NULL:
+ * every L is 1 and cls is not read.  A visit to customer c, now at pair k0 = cust[c]:
+ *   1. remove.  (n, t) of k0: n >= 2: if t > 1 and (double)(n-1) * u1 < (double)(t-1): t -= 1, T_i -= 1 (the indicator
+ *      sweep's removal); then n -= 1.  n == 1: (n, t) = (0, 0), T_i -= 1.
+ *   2. weights.  g = b + (double)T_i * a.  Every pair k with (n, t, h): z_k = L_k * (A_k + g * B_k), where
+ *        n = 0:   A = 0, B = h
+ *        n >= 1:  U = t == 1 ? n - a : (n - t * a) + 1 / V^n_t                  (S^{n+1}_t / S^n_t)
+ *                 A = U * (n - t + 1) / n
+ *                 R = t + 1 > M ? 0 : (t == n ? 1 : (n - (t+1) * a) * V^n_{t+1} + 1)     (S^{n+1}_{t+1} / S^n_t)
+ *                 B = h * t * R / n
+ *      n, t, n - t + 1 and t + 1 converted to double first; FP64, evaluated left to right as written (g * B is one product,
+ *      then the sum, then the product with L), no contraction.  t/n and (n-t+1)/n are the binomial ratios of the
+ *      held-first indicator representation (C(n-1, t-1) against C(n, t) and C(n, t-1)); z_k is the total weight of seating
+ *      c at k, at a new table or an old one.  A_k and B_k depend on the pair's own (n, t, h) alone.
+ *   3. choose.  Cumulative sums of z in this association: dishes in blocks of 64 (dish k in block k / 64, lane k % 64,
+ *      lanes past K_i holding 0); inside a block the inclusive Kogge-Stone scan x_l <- x_l + x_{l-d} (l >= d, all lanes at
+ *      once) for d = 1, 2, 4, 8, 16, 32; cum_k = base_j + scan_k with base_0 = 0 and base_{j+1} = cum of block j's lane
+ *      63.  Z = the last base.  If Z is not positive and finite the customer goes back to k0 with the (n, t, T_i) it had
+ *      and counts as stuck.  Otherwise thr = u3 * Z and k* is the smallest k with z_k > 0 and cum_k > thr, or, if there is
+ *      none, the largest k with z_k > 0.
+ *   4. seat.  n_{k*} = 0: (n, t) = (1, 1), T_i += 1.  Otherwise n += 1 and the indicator sweep's step 3-4 on (n, t), with
+ *      V^n_{t+1} and u2 and the exact ratio, decides t += 1, T_i += 1.  cust[c] = k*.
+ * u1 and u2 are stb_sample_tindic's (elements 2c+1, 2c+2 of the sweep's stream), u3 is element 2C+1+c, C = coff[I] the
+ * number of customers: the draws depend on (seed, sweep, c, C) alone, not on launch geometry or kernel form.  A visit
+ * where only k0 has positive weight (K_i = 1, a one-hot likelihood row) equals stb_sample_tindic's bit for bit.
+ * One wave per restaurant, lanes over dishes; K_i <= 64 everywhere: n, t, h, A, B in registers, else in LDS.
+ * Raw layer: n, t, T and cust updated in place; d_info NULL or two uint64 the call ADDS to: skipped, stuck.  A restaurant
+ * with N_i = coff[i+1] - coff[i] > N, K_i > STB_TD_MAXK, or (with a likelihood) K_i > stride is left untouched and counts
+ * in skipped (K_i lives on the device: the call cannot refuse it); a class >= rows makes every L 0.  Refused before
+ * anything is queued: a outside [0, 1), bounds as stb_sample_tindic, a null d_cust or other required array, a likelihood
+ * without d_cls or with rows or stride 0.  One sweep. */
+#define STB_TD_MAXK 1024
+typedef struct stb_tdish_info {
+  uint64_t skipped, stuck; /* restaurants left untouched; visits that found no dish of positive finite weight */
+} stb_tdish_info_t;
+int stb_sample_tdishes(const double *d_vtable, unsigned N, unsigned M, double a, const double *d_bpar, int I,
+                       const uint64_t *d_koff /* I+1 */, uint32_t *d_n, uint16_t *d_t, uint32_t *d_T,
+                       const double *d_h /* NULL: 1 */, const uint64_t *d_coff /* I+1 */, uint32_t *d_cust,
+                       const uint32_t *d_cls, const double *d_lik /* NULL: 1 */, unsigned rows, unsigned stride,
+                       uint64_t seed, uint64_t sweep, uint64_t *d_info /* NULL, or {skipped, stuck} */, void *stream);
+/* Object layer, on an stb_tindic_t; dish sweeps, indicator sweeps, _sampleb, _samplejoint, _logjoint and _to_groups mix
+ * freely on one object.
+ *   stb_tindic_set_classes  cls[C] from the host, every entry < rows (NULL: none)
+ *   stb_tindic_set_lik      rows x stride doubles from the host, finite and >= 0, stride >= the largest K_i; a NULL
+ *                           matrix with rows = 0 removes the likelihood, with rows > 0 holds all ones (for device writers)
+ *   stb_tindic_lik_device   the device matrix, its shape and the object's stream (hipStream_t as void*): work that writes
+ *                           it is queued there, or ordered before the next dish sweep by the caller; NULL when none is set
+ *   stb_tindic_sweep_dishes sweeps sweep .. sweep+nsweeps-1, queued in one launch; *info (may be NULL: then no wait)
+ *                           receives the call's counts.  With a likelihood, classes must be set, with rows <= the matrix's.
+ *   stb_tindic_get_state    n[G] and cust[C] to the host (either may be NULL), after the queued sweeps
+ *   stb_tindic_class_counts customers per (class, dish): cnt[rows x stride] uint32, rows as given to _set_classes, stride
+ *                           the matrix's, or the largest K_i when none is set
+ * The first dish sweep materialises pair order if the object was created without cust, and grows the object's bounds to
+ * what moving customers can reach: N = max(3, max_i N_i), the truncation M as given at create (0: max_i N_i).  The V table
+ * is reallocated and refilled (checked with stb_fill_status as in _sweep), the log joint's S slab is given back and taken
+ * again at the new bounds on its next use, and the largest n the object vouches for becomes max_i N_i, so _to_groups
+ * still needs no read-back.  Refused, the state left as it was: objects created with STB_TI_REF_ODDS; some K_i >
+ * STB_TD_MAXK; M = 0 at create with some N_i > 65535; a, bpar as for _sweep; the checks above. */
+int stb_tindic_set_classes(stb_tindic_t *s, const uint32_t *cls_host, unsigned rows);
+int stb_tindic_set_lik(stb_tindic_t *s, const double *lik_host, unsigned rows, unsigned stride);
+double *stb_tindic_lik_device(stb_tindic_t *s, unsigned *rows, unsigned *stride, void **stream);
+int stb_tindic_sweep_dishes(stb_tindic_t *s, double a, const double *bpar /* host [I] */, uint64_t seed, uint64_t sweep,
+                            int nsweeps, stb_tdish_info_t *info /* or NULL */);
+int stb_tindic_get_state(stb_tindic_t *s, uint32_t *n_out, uint32_t *cust_out);
+int stb_tindic_class_counts(stb_tindic_t *s, uint32_t *cnt_out);
+
 /* ---- the log joint probability of a sampler state (logjoint.hip): what a Gibbs chain is watched by, what runs are
  * compared on, what annealed and bridge estimates of the evidence feed on.  Pairs, h, b_i and a as for stb_tcounts above;
  * T_i = sum_k t_ik, N_i = sum_k n_ik:

@@ -64,6 +64,11 @@ class LogJointInfo(C.Structure):
                 ("outside", C.c_uint64), ("impossible", C.c_uint64), ("t_mismatch", C.c_uint64)]
 
 
+class TDishInfo(C.Structure):
+    """stb_tdish_info_t (include/stb_hip.h)"""
+    _fields_ = [("skipped", C.c_uint64), ("stuck", C.c_uint64)]
+
+
 GEOM_LOGQ, GEOM_JOINT_TERMS, GEOM_LOGJOINT = 0, 1, 2  # stb_reduce_geometry's `which`
 
 
@@ -223,6 +228,13 @@ def lib() -> C.CDLL:
     sig("stb_tindic_get", i, [vp, c_u16_p, c_u32_p])
     sig("stb_tindic_to_groups", i, [vp, vp, c_double_p])
     sig("stb_tindic_free", None, [vp])
+    sig("stb_sample_tdishes", i, [vp, u, u, d, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, u, u, u64, u64, vp, vp])
+    sig("stb_tindic_set_classes", i, [vp, c_u32_p, u])
+    sig("stb_tindic_set_lik", i, [vp, c_double_p, u, u])
+    sig("stb_tindic_lik_device", vp, [vp, C.POINTER(u), C.POINTER(u), C.POINTER(vp)])
+    sig("stb_tindic_sweep_dishes", i, [vp, d, c_double_p, u64, u64, i, C.POINTER(TDishInfo)])
+    sig("stb_tindic_get_state", i, [vp, c_u32_p, c_u32_p])
+    sig("stb_tindic_class_counts", i, [vp, c_u32_p])
     sig("stb_sample_partition", i, [vp, vp, u, u, d, u64, vp, vp, vp, u, vp, vp, u, u64, u64, vp])
     sig("stb_tcounts_partition", i, [vp, d, vp, c_double_p, u64, u64])
     sig("stb_hist_create_empty", vp, [u, i])
@@ -900,6 +912,7 @@ def sample_partition(tabs, a, n, t, S: int, seed: int, sweep: int, sizes=None, s
     return cnt
 
 
+TD_MAXK = 1024  # STB_TD_MAXK: dishes a restaurant may have under stb_tindic_sweep_dishes / stb_sample_tdishes
 TI_REF_ODDS = 1  # stb_tindic_create / stb_sample_tindic flag: the reference's factor t / (n-t+1)
 
 
@@ -915,6 +928,7 @@ class TableIndicators:
         t = np.ascontiguousarray(t, dtype=np.uint16)
         self.I, self.G = int(K.shape[0]), int(n.shape[0])
         self.h = None
+        self.maxK = int(K.max()) if self.I else 0
         if int(K.astype(np.int64).sum()) != self.G or t.shape[0] != self.G or (h is not None and len(h) != self.G):
             raise StbError(f"TableIndicators: sum K = {int(K.astype(np.int64).sum())}, but {self.G} n, {t.shape[0]} t"
                            + ("" if h is None else f", {len(h)} h"))
@@ -977,6 +991,62 @@ class TableIndicators:
         check(self.L.stb_tindic_logjoint(self.h, float(a), dp(bpar), LJ_INDICATORS if indicators else 0, C.byref(tot),
               None if Li is None else dp(Li), C.byref(info)))
         return tot.value, Li, info
+
+    # ---- dishes: customers move between the pairs of their restaurant (stb_tindic_sweep_dishes)
+
+    def set_classes(self, cls, rows: int):
+        """cls[C]: every customer's likelihood class, < rows (None: none)"""
+        if cls is None:
+            check(self.L.stb_tindic_set_classes(self.h, None, 0))
+            self.rows = 0
+            return
+        cls = np.ascontiguousarray(cls, dtype=np.uint32)
+        if cls.shape[0] != self.C:
+            raise StbError(f"TableIndicators.set_classes: {cls.shape[0]} classes, {self.C} customers")
+        check(self.L.stb_tindic_set_classes(self.h, cls.ctypes.data_as(c_u32_p), rows))
+        self.rows = int(rows)
+
+    def set_lik(self, lik=None, rows: int = 0, stride: int = 0):
+        """lik: a (rows, stride) matrix of likelihoods, finite and >= 0, stride >= the largest K; None with rows = 0
+        removes it, None with a shape holds all ones (for device writers: lik_device)"""
+        if lik is None:
+            check(self.L.stb_tindic_set_lik(self.h, None, rows, stride))
+        else:
+            lik = np.ascontiguousarray(lik, dtype=np.float64)
+            if lik.ndim != 2:
+                raise StbError("TableIndicators.set_lik: lik must be a (rows, stride) matrix")
+            rows, stride = lik.shape
+            check(self.L.stb_tindic_set_lik(self.h, dp(lik), rows, stride))
+        self.stride = int(stride) if rows else 0
+
+    def lik_device(self):
+        """(device pointer or None, rows, stride, stream) of the likelihood matrix"""
+        r, st, q = C.c_uint(0), C.c_uint(0), C.c_void_p(None)
+        p = self.L.stb_tindic_lik_device(self.h, C.byref(r), C.byref(st), C.byref(q))
+        return p, r.value, st.value, q.value
+
+    def sweep_dishes(self, a, bpar, seed: int, sweep: int, nsweeps: int = 1):
+        """dish sweeps sweep .. sweep+nsweeps-1; returns TDishInfo (skipped, stuck) of the call, after a wait"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        info = TDishInfo()
+        check(self.L.stb_tindic_sweep_dishes(self.h, float(a), dp(bpar), seed, sweep, nsweeps, C.byref(info)))
+        return info
+
+    def get_state(self):
+        """(n[G] uint32, cust[C] uint32) after the queued sweeps"""
+        n = np.zeros(self.G, dtype=np.uint32)
+        cust = np.zeros(self.C, dtype=np.uint32)
+        check(self.L.stb_tindic_get_state(self.h, n.ctypes.data_as(c_u32_p), cust.ctypes.data_as(c_u32_p)))
+        return n, cust
+
+    def class_counts(self):
+        """customers per (class, dish): uint32 (rows, stride), stride the likelihood's or the largest K"""
+        stride = getattr(self, "stride", 0) or max(self.maxK, 1)
+        cnt = np.zeros((getattr(self, "rows", 0), stride), dtype=np.uint32)
+        if cnt.size == 0:
+            raise StbError("TableIndicators.class_counts: classes are not set")
+        check(self.L.stb_tindic_class_counts(self.h, cnt.ctypes.data_as(c_u32_p)))
+        return cnt
 
     def free(self):
         if self.h:

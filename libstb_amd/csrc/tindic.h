@@ -1,0 +1,66 @@
+// tindic.h -- what tindic.hip (the indicator sweep) and tdish.hip (the dish sweep) share: the counter-based uniforms, the V
+// cell look-up, the two decisions of a visit, and the wave's readlane helpers.  Both kernels evaluate a visit with these
+// functions, so a dish visit whose customer stays in its dish gives the indicator visit's bits.
+#ifndef STB_TINDIC_H
+#define STB_TINDIC_H
+
+#include "stb_common.h"
+
+#define STB_TI_REF_ODDS_FLAG 1u
+
+static constexpr uint64_t TI_GAMMA = 0x9E3779B97F4A7C15ull;
+
+__host__ __device__ static inline uint64_t ti_mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// element j of the sweep's stream: u1 of customer c is j = 2c+1, u2 is j = 2c+2
+__device__ __forceinline__ double ti_unit(uint64_t key, uint64_t j) {
+  return (double)(ti_mix64(key + j * TI_GAMMA) >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// V^n_m with stb_lookup_V's semantics for the cells a visit can address (2 <= n <= N): 0 outside 2 <= m <= min(n, M)
+__device__ __forceinline__ double ti_V(const double *vt, unsigned M, unsigned n, unsigned m) {
+  if (m < 2 || m > M || m > n) return 0.0;
+  return vt[stb_vrow_offset(n, M) + (m - 2)];
+}
+
+__device__ __forceinline__ bool ti_remove(unsigned n, unsigned t, double u1) {
+  return t > 1 && (double)(n - 1) * u1 < (double)(t - 1);
+}
+
+// t, T after the removal; t < n
+__device__ __forceinline__ bool ti_add(unsigned n, unsigned t, uint32_t T, double h, double a, double b, double V, double u2,
+                                       bool ref) {
+#pragma clang fp contract(off)
+  const double odds = h * (b + (double)T * a) * (double)t / (double)(ref ? n - t + 1 : n - t) * V;
+  const double p = isinf(odds) ? 1.0 : odds / (odds + 1.0);
+  return u2 < p;
+}
+
+// ---- readlane helpers: every lane of a wave walks the same chain on the same values ----
+
+__device__ __forceinline__ unsigned ti_rl(unsigned v, unsigned j) {
+  return (unsigned)__builtin_amdgcn_readlane((int)v, (int)__builtin_amdgcn_readfirstlane((int)j));
+}
+__device__ __forceinline__ double ti_rld(double v, unsigned j) {
+  const int jj = __builtin_amdgcn_readfirstlane((int)j);
+  const uint64_t x = (uint64_t)__double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, jj);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), jj);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// the dish sweep's launch (tdish.hip): nsweeps sweeps from `sweep` on, cap = dishes a wave holds (the largest K_i, at most
+// STB_TD_MAXK); d_info: two uint64 (skipped, stuck), added to
+int stb_td_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I, const uint64_t *d_koff,
+                  uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, const uint64_t *d_coff, uint32_t *d_cust,
+                  const uint32_t *d_cls, const double *d_lik, unsigned rows, unsigned stride, uint64_t seed, uint64_t sweep,
+                  int nsweeps, unsigned cap, unsigned long long *d_info, hipStream_t st);
+// customers per (class, dish): cnt[rows x stride] += 1 at (cls[c], cust[c]) for c < C
+int stb_td_class_counts(const uint32_t *d_cust, const uint32_t *d_cls, uint64_t C, unsigned rows, unsigned stride,
+                        uint32_t *d_cnt, hipStream_t st);
+
+#endif

@@ -26,42 +26,9 @@
 #include "hyperq.h"
 #include "hyperj.h"
 #include "logjoint.h"
+#include "tindic.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
-#define STB_TI_REF_ODDS_FLAG 1u
-
-static constexpr uint64_t TI_GAMMA = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ static inline uint64_t ti_mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// element j of the sweep's stream: u1 of customer c is j = 2c+1, u2 is j = 2c+2
-__device__ __forceinline__ double ti_unit(uint64_t key, uint64_t j) {
-  return (double)(ti_mix64(key + j * TI_GAMMA) >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// V^n_m with stb_lookup_V's semantics for the cells a visit can address (2 <= n <= N): 0 outside 2 <= m <= min(n, M)
-__device__ __forceinline__ double ti_V(const double *vt, unsigned M, unsigned n, unsigned m) {
-  if (m < 2 || m > M || m > n) return 0.0;
-  return vt[stb_vrow_offset(n, M) + (m - 2)];
-}
-
-__device__ __forceinline__ bool ti_remove(unsigned n, unsigned t, double u1) {
-  return t > 1 && (double)(n - 1) * u1 < (double)(t - 1);
-}
-
-// t, T after the removal; t < n
-__device__ __forceinline__ bool ti_add(unsigned n, unsigned t, uint32_t T, double h, double a, double b, double V, double u2,
-                                       bool ref) {
-#pragma clang fp contract(off)
-  const double odds = h * (b + (double)T * a) * (double)t / (double)(ref ? n - t + 1 : n - t) * V;
-  const double p = isinf(odds) ? 1.0 : odds / (odds + 1.0);
-  return u2 < p;
-}
-
 // ---- lane form -------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(64) void k_tindic_lane(const double *vt, unsigned N, unsigned M, double a, const double *bpar,
@@ -113,17 +80,6 @@ __global__ __launch_bounds__(64) void k_tindic_lane(const double *vt, unsigned N
 // ---- wave form -------------------------------------------------------------------------------------------------
 // Every lane walks the same chain on the same values (read with readlane), so each lane's own loads and stores are
 // all the ordering the chain needs; the per-lane work is the loads of the next 64 customers and their V cells.
-
-__device__ __forceinline__ unsigned ti_rl(unsigned v, unsigned j) {
-  return (unsigned)__builtin_amdgcn_readlane((int)v, (int)__builtin_amdgcn_readfirstlane((int)j));
-}
-__device__ __forceinline__ double ti_rld(double v, unsigned j) {
-  const int jj = __builtin_amdgcn_readfirstlane((int)j);
-  const uint64_t x = (uint64_t)__double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, jj);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), jj);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
 
 __global__ __launch_bounds__(64) void k_tindic_wave(const double *vt, unsigned N, unsigned M, double a, const double *bpar,
                                                     int I, const uint64_t *koff, const uint32_t *nv, uint16_t *tv,
@@ -277,6 +233,15 @@ struct stb_tindic {
   unsigned Mdraw;       // the column bound the draws are truncated at (what create was given, or the largest n)
   unsigned maxn, maxK;
   unsigned flags;
+  // the dish sweep (tdish.hip)
+  unsigned Mgiven;      // the column bound create was given (0: the largest n)
+  uint64_t maxNi;       // the largest restaurant's customers: what one pair's n can reach
+  bool dish_ready;      // pair order materialised, bounds grown to maxNi
+  uint32_t *d_cls;      // [C] likelihood classes (null: none set)
+  unsigned cls_rows;
+  double *d_lik;        // [lik_rows x lik_stride] (null: every L is 1)
+  unsigned lik_rows, lik_stride;
+  unsigned long long *d_info, *h_info;  // {skipped, stuck} on the device, and pinned
   bool need_table;      // some visit can read a V cell (max n >= 2 and M >= 2); otherwise no indicator is ever added
   uint64_t *d_koff, *d_coff;
   uint32_t *d_n, *d_T;
@@ -306,9 +271,11 @@ static void ti_release(stb_tindic_t *s) {
   void *pooled[] = {s->d_stab, s->d_sS1, s->d_sws};
   for (void *p : pooled)
     if (p) stb_pool_free(p);
-  void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws};
+  void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws,
+                 s->d_cls, s->d_lik, s->d_info};
   for (void *p : dev)
     if (p) (void)hipFree(p);
+  if (s->h_info) (void)hipHostFree(s->h_info);
   for (int k = 0; k < 2; k++) {
     if (s->h_bpar[k]) (void)hipHostFree(s->h_bpar[k]);
     if (s->ev_bpar[k]) (void)hipEventDestroy(s->ev_bpar[k]);
@@ -355,11 +322,13 @@ static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, 
              "at M)", maxn);
     return nullptr;
   }
+  const unsigned Mgiven = M;
   if (M == 0) M = maxn > 0 ? maxn : 1;
   if (M > 65535u) {
     stb_fail("stb_tindic_create: M=%u (t is a uint16: at most 65535)", M);
     return nullptr;
   }
+  uint64_t maxNi = 0;
   std::vector<uint32_t> T(I, 0);
   for (int i = 0; i < I; i++) {
     uint64_t ci = 0;
@@ -374,6 +343,7 @@ static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, 
       ci += n;
     }
     coff[i + 1] = coff[i] + ci;
+    maxNi = ci > maxNi ? ci : maxNi;
   }
   const uint64_t C = coff[I];
   if (hflat && ti_check_h(hflat, G, "stb_tindic_create")) return nullptr;
@@ -404,6 +374,8 @@ static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, 
   s->maxn = maxn;
   s->maxK = maxK;
   s->flags = flags;
+  s->Mgiven = Mgiven;
+  s->maxNi = maxNi;
   s->N = maxn < 3 ? 3 : maxn;
   s->Mdraw = M;
   s->need_table = maxn >= 2 && M >= 2;
@@ -659,6 +631,254 @@ extern "C" int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar
   if (d_Li) {
     if (rc) (void)hipStreamSynchronize(s->st);  // (the cache may hand the buffer on at once)
     stb_pool_free(d_Li);
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// dishes on the object (the kernel is tdish.hip's)
+
+// pair order written out: the dish sweep writes a customer's dish, so it needs the sequence
+static int ti_materialise_cust(stb_tindic_t *s, const char *who) {
+  if (s->d_cust) return 0;
+  std::vector<uint32_t> n(s->G ? s->G : 1), cust(s->C ? s->C : 1);
+  std::vector<uint64_t> koff((size_t)s->I + 1);
+  if (hipStreamSynchronize(s->st) != hipSuccess ||
+      (s->G && hipMemcpy(n.data(), s->d_n, sizeof(uint32_t) * s->G, hipMemcpyDeviceToHost) != hipSuccess) ||
+      hipMemcpy(koff.data(), s->d_koff, sizeof(uint64_t) * (s->I + 1), hipMemcpyDeviceToHost) != hipSuccess)
+    return stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  uint64_t c = 0;
+  for (int i = 0; i < s->I; i++)
+    for (uint64_t g = koff[i]; g < koff[i + 1]; g++)
+      for (uint32_t r = 0; r < n[g]; r++) cust[c++] = (uint32_t)(g - koff[i]);
+  uint32_t *d = nullptr;
+  if (hipMalloc((void **)&d, sizeof(uint32_t) * (s->C ? s->C : 1)) != hipSuccess)
+    return stb_fail("%s: out of device memory for %llu customers", who, (unsigned long long)s->C);
+  if (s->C && hipMemcpy(d, cust.data(), sizeof(uint32_t) * s->C, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  }
+  s->d_cust = d;
+  return 0;
+}
+
+// first dish sweep: the customer sequence, the counters, and bounds that hold whatever moving customers can reach
+static int ti_dish_prepare(stb_tindic_t *s, const char *who) {
+  if (s->dish_ready) return 0;
+  if (s->Mgiven == 0 && s->maxNi > 65535u)
+    return stb_fail("%s: a restaurant has %llu customers and the object was created with M = 0; t is a uint16, so create "
+                    "it with M <= 65535", who, (unsigned long long)s->maxNi);
+  if (s->maxNi > 0x7fffffffull) return stb_fail("%s: a restaurant has %llu customers", who, (unsigned long long)s->maxNi);
+  if (ti_materialise_cust(s, who)) return 1;
+  if (!s->d_info && hipMalloc((void **)&s->d_info, 2 * sizeof(unsigned long long)) != hipSuccess)
+    return stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!s->h_info && hipHostMalloc((void **)&s->h_info, 2 * sizeof(unsigned long long)) != hipSuccess)
+    return stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  const unsigned maxn = (unsigned)s->maxNi;
+  const unsigned N = maxn < 3 ? 3 : maxn;
+  const unsigned Mdraw = s->Mgiven ? s->Mgiven : (maxn > 0 ? maxn : 1);
+  const bool need = maxn >= 2 && Mdraw >= 2;
+  const unsigned M = need ? (Mdraw < N ? Mdraw : N) : Mdraw;
+  if (need && (!s->d_vt || N != s->N || M != s->M)) {
+    const uint64_t vstride = (stb_vtable_elems(N, M) + 31) & ~31ull;
+    const size_t ws_bytes = stb_fill_workspace_bytes(N, M, 1);
+    double *vt = nullptr;
+    void *ws = nullptr;
+    if (hipMalloc((void **)&vt, sizeof(double) * vstride) != hipSuccess || hipMalloc(&ws, ws_bytes ? ws_bytes : 1) != hipSuccess) {
+      if (vt) (void)hipFree(vt);
+      return stb_fail("%s: out of device memory for a %u x %u V table", who, N, M);
+    }
+    if (hipStreamSynchronize(s->st) != hipSuccess) {  // (queued sweeps read the table that goes)
+      (void)hipFree(vt);
+      (void)hipFree(ws);
+      return stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    }
+    if (s->d_vt) (void)hipFree(s->d_vt);
+    if (s->d_ws) (void)hipFree(s->d_ws);
+    s->d_vt = vt;
+    s->d_ws = ws;
+    s->vstride = vstride;
+    s->ws_bytes = ws_bytes;
+    s->a_filled = NAN;
+  }
+  if (N != s->N || M != s->M || need != s->need_table) {  // the S slab follows on the log joint's next use
+    (void)hipStreamSynchronize(s->st);
+    void *pooled[] = {s->d_stab, s->d_sS1, s->d_sws};
+    for (void *p : pooled)
+      if (p) stb_pool_free(p);
+    s->d_stab = s->d_sS1 = nullptr;
+    s->d_sws = nullptr;
+    s->a_sfilled = NAN;
+  }
+  s->N = N;
+  s->M = M;
+  s->Mdraw = Mdraw;
+  s->need_table = need;
+  s->maxn = maxn;
+  s->dish_ready = true;
+  return 0;
+}
+
+extern "C" int stb_tindic_set_classes(stb_tindic_t *s, const uint32_t *cls_host, unsigned rows) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_classes";
+  if (!s) return stb_fail("%s: null object", who);
+  if (cls_host) {
+    if (rows < 1) return stb_fail("%s: rows=%u", who, rows);
+    for (uint64_t c = 0; c < s->C; c++)
+      if (cls_host[c] >= rows) return stb_fail("%s: cls[%llu]=%u (must be < rows = %u)", who, (unsigned long long)c, cls_host[c], rows);
+  }
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (hipStreamSynchronize(s->st) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc && !cls_host) {
+    if (s->d_cls) (void)hipFree(s->d_cls);
+    s->d_cls = nullptr;
+    s->cls_rows = 0;
+  } else if (!rc) {
+    if (!s->d_cls && hipMalloc((void **)&s->d_cls, sizeof(uint32_t) * (s->C ? s->C : 1)) != hipSuccess)
+      rc = stb_fail("%s: out of device memory", who);
+    if (!rc && s->C && hipMemcpy(s->d_cls, cls_host, sizeof(uint32_t) * s->C, hipMemcpyHostToDevice) != hipSuccess)
+      rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    if (!rc) s->cls_rows = rows;
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_set_lik(stb_tindic_t *s, const double *lik_host, unsigned rows, unsigned stride) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_lik";
+  if (!s) return stb_fail("%s: null object", who);
+  const bool drop = !lik_host && rows == 0;
+  if (!drop) {
+    if (rows < 1) return stb_fail("%s: rows=%u", who, rows);
+    if (stride < s->maxK || stride < 1)
+      return stb_fail("%s: stride=%u; the largest restaurant has K=%u dishes", who, stride, s->maxK);
+    if (lik_host)
+      for (uint64_t j = 0; j < (uint64_t)rows * stride; j++)
+        if (!(lik_host[j] >= 0.0) || !std::isfinite(lik_host[j]))
+          return stb_fail("%s: lik[%llu]=%g (must be finite and >= 0)", who, (unsigned long long)j, lik_host[j]);
+  }
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (hipStreamSynchronize(s->st) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc && drop) {
+    if (s->d_lik) (void)hipFree(s->d_lik);
+    s->d_lik = nullptr;
+    s->lik_rows = s->lik_stride = 0;
+  } else if (!rc) {
+    const size_t cells = (size_t)rows * stride;
+    double *d = nullptr;
+    std::vector<double> ones;
+    if (!lik_host) ones.assign(cells, 1.0);
+    if (hipMalloc((void **)&d, sizeof(double) * cells) != hipSuccess) rc = stb_fail("%s: out of device memory", who);
+    if (!rc && hipMemcpy(d, lik_host ? lik_host : ones.data(), sizeof(double) * cells, hipMemcpyHostToDevice) != hipSuccess) {
+      rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+      (void)hipFree(d);
+    }
+    if (!rc) {
+      if (s->d_lik) (void)hipFree(s->d_lik);
+      s->d_lik = d;
+      s->lik_rows = rows;
+      s->lik_stride = stride;
+    }
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" double *stb_tindic_lik_device(stb_tindic_t *s, unsigned *rows, unsigned *stride, void **stream) {
+  if (!s) {
+    stb_fail("stb_tindic_lik_device: null object");
+    return nullptr;
+  }
+  if (rows) *rows = s->lik_rows;
+  if (stride) *stride = s->lik_stride;
+  if (stream) *stream = (void *)s->st;
+  return s->d_lik;
+}
+
+extern "C" int stb_tindic_sweep_dishes(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, int nsweeps,
+                                       stb_tdish_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sweep_dishes";
+  if (!s) return stb_fail("%s: null object", who);
+  if (s->flags & STB_TI_REF_ODDS_FLAG)
+    return stb_fail("%s: the object was created with STB_TI_REF_ODDS; the dish sweep has the exact ratio only", who);
+  if (!(a >= 0.0 && a < 1.0)) return stb_fail("%s: discount a=%g outside [0, 1)", who, a);
+  if (!bpar) return stb_fail("%s: bpar is required", who);
+  if (nsweeps < 0) return stb_fail("%s: nsweeps=%d", who, nsweeps);
+  for (int i = 0; i < s->I; i++)
+    if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
+  if (s->maxK > STB_TD_MAXK)
+    return stb_fail("%s: a restaurant has K=%u dishes; the sweep holds at most STB_TD_MAXK = %d", who, s->maxK, STB_TD_MAXK);
+  if (s->d_lik && (!s->d_cls || s->cls_rows > s->lik_rows))
+    return stb_fail("%s: the likelihood has %u rows; classes %s", who, s->lik_rows,
+                    s->d_cls ? "were set with more" : "are not set (stb_tindic_set_classes)");
+  if (info) info->skipped = info->stuck = 0;
+  if (nsweeps == 0) return 0;
+  const int prev = stb_device_enter(s->dev);
+  int rc = ti_dish_prepare(s, who);
+  if (!rc && s->need_table && !(a == s->a_filled)) {
+    s->a_filled = NAN;
+    rc = stb_fill_V(&a, 1, s->N, s->M, s->d_vt, s->vstride, s->d_ws, s->ws_bytes, s->st);
+    if (!rc) rc = stb_fill_status();
+    if (!rc) s->a_filled = a;
+  }
+  if (!rc) rc = ti_stage_bpar(s, bpar, who);
+  if (!rc && hipMemsetAsync(s->d_info, 0, 2 * sizeof(unsigned long long), s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc)
+    rc = stb_td_launch(s->d_vt, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T,
+                       s->d_h, s->d_coff, s->d_cust, s->d_cls, s->d_lik, s->lik_rows, s->lik_stride, seed, sweep, nsweeps,
+                       s->maxK, s->d_info, s->st);
+  if (!rc && info) {
+    if (hipMemcpyAsync(s->h_info, s->d_info, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+        hipStreamSynchronize(s->st) != hipSuccess)
+      rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    if (!rc) {
+      info->skipped = s->h_info[0];
+      info->stuck = s->h_info[1];
+    }
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_get_state(stb_tindic_t *s, uint32_t *n_out, uint32_t *cust_out) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_get_state";
+  if (!s) return stb_fail("%s: null object", who);
+  const int prev = stb_device_enter(s->dev);
+  int rc = cust_out ? ti_materialise_cust(s, who) : 0;
+  if (!rc && ((n_out && s->G && hipMemcpyAsync(n_out, s->d_n, sizeof(uint32_t) * s->G, hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
+              (cust_out && s->C && hipMemcpyAsync(cust_out, s->d_cust, sizeof(uint32_t) * s->C, hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
+              hipStreamSynchronize(s->st) != hipSuccess))
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_class_counts(stb_tindic_t *s, uint32_t *cnt_out) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_class_counts";
+  if (!s || !cnt_out) return stb_fail("%s: null %s", who, s ? "cnt_out" : "object");
+  if (!s->d_cls) return stb_fail("%s: classes are not set (stb_tindic_set_classes)", who);
+  const unsigned rows = s->cls_rows, stride = s->d_lik ? s->lik_stride : (s->maxK ? s->maxK : 1);
+  const size_t bytes = sizeof(uint32_t) * (size_t)rows * stride;
+  const int prev = stb_device_enter(s->dev);
+  int rc = ti_materialise_cust(s, who);
+  uint32_t *d_cnt = nullptr;
+  if (!rc && stb_pool_malloc((void **)&d_cnt, bytes) != hipSuccess) rc = stb_fail("%s: out of device memory", who);
+  if (!rc && hipMemsetAsync(d_cnt, 0, bytes, s->st) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc) rc = stb_td_class_counts(s->d_cust, s->d_cls, s->C, rows, stride, d_cnt, s->st);
+  if (!rc && hipMemcpyAsync(cnt_out, d_cnt, bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (d_cnt) {
+    if (hipStreamSynchronize(s->st) != hipSuccess && !rc) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    stb_pool_free(d_cnt);
   }
   stb_device_leave(prev);
   return rc;
