@@ -23,10 +23,14 @@
  *   9. with -z the device loop also moves the data: before each indicator sweep every customer leaves its dish and is
  *      seated again at any dish of its restaurant (stb_tindic_sweep_dishes), under a likelihood with two synthetic
  *      classes (even customers favour even dishes, odd customers odd ones); n changes on the device and comes back once.
+ *  10. with -w (needs -d -z) the likelihood and the base weights are parameters of the chain too: after each dish sweep every
+ *      dish's class distribution is drawn from its Dirichlet(0.5) posterior given the (class, dish) counts and h from its
+ *      Dirichlet(1) posterior given the table counts (stb_tindic_sample_lik, stb_tindic_sample_h), on the device; with -L
+ *      the line gains the data term (stb_tindic_loglik) and the complete-data log joint.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w]
  */
 #include <math.h>
 #include <stdio.h>
@@ -42,10 +46,10 @@
 #define DISHES 50
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, explicit_d = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLz")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzw")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -54,11 +58,16 @@ int main(int argc, char **argv) {
     else if (c == 'g') grid = atoi(optarg);
     else if (c == 'G') nsets = atoi(optarg);
     else if (c == 's') seed = atol(optarg);
-    else if (c == 'd') ondev = 1;
+    else if (c == 'd') ondev = explicit_d = 1;
     else if (c == 'j') ondev = joint = 1;
     else if (c == 'L') showlj = 1;
     else if (c == 'z') ondev = dishes = 1;
+    else if (c == 'w') redraw = 1;
     else return 2;
+  }
+  if (redraw && !(explicit_d && dishes)) {
+    fprintf(stderr, "pyp_resample: -w needs -d -z\n");
+    return 2;
   }
   srand48(seed);
   srand((unsigned)seed);
@@ -144,6 +153,10 @@ int main(int argc, char **argv) {
         stb_tdish_info_t di;
         if (stb_tindic_sweep_dishes(ti, a, bvec, (uint64_t)seed + 2, (uint64_t)it, 1, &di)) yaps_quit("stb_tindic_sweep_dishes: %s\n", stb_last_error());
         stuck += di.stuck + di.skipped;
+        /* the uncollapsed step: seeds of their own, so neither shares a stream with a sweep or with the other */
+        if (redraw && (stb_tindic_sample_lik(ti, NULL, 0.5, (uint64_t)seed + 3, (uint64_t)it) ||
+                       stb_tindic_sample_h(ti, NULL, 1.0, (uint64_t)seed + 4, (uint64_t)it)))
+          yaps_quit("stb_tindic_sample_lik / _sample_h: %s\n", stb_last_error());
       }
       if (stb_tindic_sweep(ti, a, bvec, (uint64_t)seed, (uint64_t)it, 1)) yaps_quit("stb_tindic_sweep: %s\n", stb_last_error());
       if (it % 3 == 2 && joint) {
@@ -175,8 +188,14 @@ int main(int argc, char **argv) {
         double lj;
         stb_logjoint_info_t li;
         if (stb_tindic_logjoint(ti, a, bvec, STB_LJ_INDICATORS, &lj, NULL, &li)) yaps_quit("stb_tindic_logjoint: %s\n", stb_last_error());
-        printf("iteration %d: log joint %.6f (pairs %.6f, base %.6f, restaurants %.6f, indicators %.6f) a=%.4f b=%.3f\n", it, lj,
-               li.pairs, li.base, li.restaurants, li.binom, a, b);
+        if (redraw) {
+          double dt;
+          if (stb_tindic_loglik(ti, &dt, NULL)) yaps_quit("stb_tindic_loglik: %s\n", stb_last_error());
+          printf("iteration %d: log joint %.6f (pairs %.6f, base %.6f, restaurants %.6f, indicators %.6f) data %.6f complete %.6f "
+                 "a=%.4f b=%.3f\n", it, lj, li.pairs, li.base, li.restaurants, li.binom, dt, lj + dt, a, b);
+        } else
+          printf("iteration %d: log joint %.6f (pairs %.6f, base %.6f, restaurants %.6f, indicators %.6f) a=%.4f b=%.3f\n", it, lj,
+                 li.pairs, li.base, li.restaurants, li.binom, a, b);
       }
     }
     if (stb_tindic_get(ti, tf, T)) yaps_quit("stb_tindic_get: %s\n", stb_last_error());

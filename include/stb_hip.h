@@ -632,6 +632,66 @@ int stb_tindic_sweep_dishes(stb_tindic_t *s, double a, const double *bpar /* hos
 int stb_tindic_get_state(stb_tindic_t *s, uint32_t *n_out, uint32_t *cust_out);
 int stb_tindic_class_counts(stb_tindic_t *s, uint32_t *cnt_out);
 
+/* ---- the likelihood and the base weights, drawn on the device (tlik.hip; additive: the reference has no such step) ----
+ * The dish sweep is exact because the likelihood is a fixed table while it runs.  The step that completes the chain is the
+ * uncollapsed one: with a Dirichlet(beta) prior on every dish's distribution over classes, the distribution of dish k given
+ * the customers is Dirichlet(beta_w + cnt_wk), cnt_wk the customers of class w at dish k, independently over dishes; drawing
+ * it and sweeping the dishes under it is a Gibbs sampler on (likelihood, seating).  The same holds for
+ * the base weights: every table draws its dish from h, so h enters the joint as prod_k h_k^{c_k}, c_k the tables serving
+ * dish k -- the H term of stb_logjoint -- and with a Dirichlet(gamma) prior h | t is Dirichlet(gamma_k + c_k).
+ * stb_sample_lik: d_cnt and d_lik are rows x stride, row-major (class w, dish k at w * stride + k; uint32 and double).  For
+ * every cell lg_wk = log G, G ~ Gamma(beta_w + cnt_wk) (beta_w = beta_host[w], or beta0 when beta_host is NULL), by
+ * stb_sample_logq's recipe unchanged: Marsaglia-Tsang with Box-Muller's cosine member, the log-domain boost for a shape
+ * below 1, at most 64 attempts a variate (libstb_amd/csrc/gamma_dev.h writes it out; tests/tl_oracle.py replays it).
+ * Uniforms: key = mix(seed + (sweep+1) gamma); cell e = w * stride + k owns key_e = mix(key + (e+1) gamma) and takes its
+ * elements 1, 2, ... (m / 2^53 of the top 53 bits, 2^-54 in place of 0) in the recipe's order: the draws depend on
+ * (seed, sweep, e) alone.  Every column is then normalised in the log domain in this association, FP64, no contraction:
+ *     M_k = max over all w of lg_wk;  e_wk = exp(lg_wk - M_k);
+ *     rows in chunks of 256 (chunk j = rows 256 j .. 256 j + 255); a chunk's sum adds its e_wk one after another in row
+ *     order, starting from the chunk's first; Z_k adds the chunk sums one after another in chunk order;
+ *     lik[w * stride + k] = e_wk / Z_k.
+ * A column sums to 1 within 2 u rows (u = 2^-53); rows = 1 gives exactly 1.0.  A cell whose e_wk underflows is 0 (a dish
+ * sweep gives such a class no weight at that dish; it happens for beta far below 1 only).  The bits do not depend on launch
+ * geometry (STB_TLIK_WAVES = 1, 2, 4 or 8 waves a workgroup).  Five launches and one wait, for the error word; d_lik is
+ * scratch between them.  Refused before anything is queued, with stb_last_error() set: a null array, rows or stride 0, a
+ * beta that is not positive and finite.  A rejection loop that runs out, or a column whose Z_k is not positive and finite
+ * (every lg_wk -inf: beta below 1e-300), fails the call after the wait; d_lik is then undefined.
+ * stb_lik_loglik: the data term log p(classes | dishes, lik) = sum_wk cnt_wk log lik_wk.  x_wk = (double)cnt * log(lik)
+ * where cnt > 0 and 0 where cnt = 0; a column's sum by the chunk association above (a chunk's x in row order, then the
+ * chunks in order), then the columns one after another in k order.  A cell with cnt > 0 and lik = 0 counts in
+ * *impossible_host (may be NULL) and makes the total -inf; a finite matrix >= 0 never gives a NaN.  Two launches; the
+ * answer arrives through pinned memory: one wait.
+ * Object layer, queued on the object's stream behind its sweeps; t, T, n and cust are not written and nothing per class,
+ * dish or restaurant crosses to the host.
+ *   stb_tindic_sample_lik  counts (class, dish) on the device over the matrix's shape and draws all of its rows x stride
+ *                          cells into it (beta_host: the matrix's rows values, or NULL).  Classes and a matrix must be set,
+ *                          the classes' rows <= the matrix's (stb_tindic_set_lik(s, NULL, rows, stride) makes one); rows
+ *                          past the classes' and columns past the largest K_i have zero counts: drawn from the prior.
+ *   stb_tindic_sample_h    dish k is local pair k of every restaurant, the dish sweep's convention.  c_k = sum of t_ik over
+ *                          the restaurants with K_i > k; for k < Kmax = max_i K_i (1 <= Kmax <= STB_TD_MAXK) lg_k = log of a
+ *                          Gamma(gamma_k + c_k) variate as above with e = k (gamma_host: Kmax values, or NULL for gamma0);
+ *                          M = max lg_k, e_k = exp(lg_k - M), Z = the e_k added one after another in k order, h_k = e_k / Z,
+ *                          written to every pair (i, k): it replaces the object's h, later sweeps and log joints see it.
+ *                          The weights are one distribution over Kmax dishes; a restaurant with K_i < Kmax sees its first
+ *                          K_i.  Equal seeds give _sample_lik and _sample_h one stream: give them different seeds.
+ *   stb_tindic_loglik      the data term of the current state under the object's matrix; with stb_tindic_logjoint's total
+ *                          it is the complete-data log joint log p(classes, n, t | a, b, h, lik)
+ *   stb_tindic_get_h       the object's h[G] to the host (1 everywhere when none is set), after the queued work
+ * Refused before anything is queued, the state as it was: a null object (or total / h_out); no classes or no matrix, or
+ * classes with more rows than the matrix; a beta or gamma that is not positive and finite; for _sample_h an object created
+ * with STB_TI_REF_ODDS, or Kmax outside 1 .. STB_TD_MAXK.  A draw that fails after its wait (above) leaves the matrix, or
+ * h, undefined: stb_tindic_sweep_dishes (and, for the matrix, _loglik) is then refused until a _sample_lik / _sample_h
+ * that succeeds, or a stb_tindic_set_lik / _set_h. */
+int stb_sample_lik(const uint32_t *d_cnt, unsigned rows, unsigned stride, const double *beta_host /* rows, or NULL */,
+                   double beta0, double *d_lik, uint64_t seed, uint64_t sweep, void *stream);
+int stb_lik_loglik(const uint32_t *d_cnt, const double *d_lik, unsigned rows, unsigned stride, double *total_host,
+                   uint64_t *impossible_host /* or NULL */, void *stream);
+int stb_tindic_sample_lik(stb_tindic_t *s, const double *beta_host, double beta0, uint64_t seed, uint64_t sweep);
+int stb_tindic_sample_h(stb_tindic_t *s, const double *gamma_host /* Kmax, or NULL */, double gamma0, uint64_t seed,
+                        uint64_t sweep);
+int stb_tindic_loglik(stb_tindic_t *s, double *total, uint64_t *impossible /* or NULL */);
+int stb_tindic_get_h(stb_tindic_t *s, double *h_out);
+
 /* ---- the log joint probability of a sampler state (logjoint.hip): what a Gibbs chain is watched by, what runs are
  * compared on, what annealed and bridge estimates of the evidence feed on.  Pairs, h, b_i and a as for stb_tcounts above;
  * T_i = sum_k t_ik, N_i = sum_k n_ik:

@@ -235,6 +235,13 @@ def lib() -> C.CDLL:
     sig("stb_tindic_sweep_dishes", i, [vp, d, c_double_p, u64, u64, i, C.POINTER(TDishInfo)])
     sig("stb_tindic_get_state", i, [vp, c_u32_p, c_u32_p])
     sig("stb_tindic_class_counts", i, [vp, c_u32_p])
+    # ---- the likelihood and the base weights drawn on the device, the data term
+    sig("stb_sample_lik", i, [vp, u, u, c_double_p, d, vp, u64, u64, vp])
+    sig("stb_lik_loglik", i, [vp, vp, u, u, c_double_p, C.POINTER(u64), vp])
+    sig("stb_tindic_sample_lik", i, [vp, c_double_p, d, u64, u64])
+    sig("stb_tindic_sample_h", i, [vp, c_double_p, d, u64, u64])
+    sig("stb_tindic_loglik", i, [vp, c_double_p, C.POINTER(u64)])
+    sig("stb_tindic_get_h", i, [vp, c_double_p])
     sig("stb_sample_partition", i, [vp, vp, u, u, d, u64, vp, vp, vp, u, vp, vp, u, u64, u64, vp])
     sig("stb_tcounts_partition", i, [vp, d, vp, c_double_p, u64, u64])
     sig("stb_hist_create_empty", vp, [u, i])
@@ -741,6 +748,37 @@ def sample_logq(b, scale, N, seed: int, sweep: int, want_L: bool = True, stream=
     return Q.value, Lt
 
 
+def _prior(v, n: int):
+    """a Dirichlet parameter, a scalar for every entry or n values, as (the host vector to keep alive or None, its pointer or
+    None, the scalar)"""
+    if np.ndim(v) == 0:
+        return None, None, float(v)
+    vec = np.ascontiguousarray(v, dtype=np.float64)
+    if vec.shape != (n,):
+        raise StbError(f"expected a scalar or {n} values, got shape {vec.shape}")
+    return vec, dp(vec), 0.0
+
+
+def sample_lik(cnt, beta, seed: int, sweep: int, out=None, stream=None):
+    """stb_sample_lik on a device tensor cnt (int32 holding uint32 counts, (rows, stride)): a float64 device tensor of the
+    same shape whose column k is a draw from Dirichlet(beta_w + cnt[w, k]); beta a scalar or rows values"""
+    torch = _torch()
+    rows, stride = int(cnt.shape[0]), int(cnt.shape[1])
+    lik = torch.empty((rows, stride), dtype=torch.float64, device=cnt.device) if out is None else out
+    keep, bp, b0 = _prior(beta, rows)
+    check(lib().stb_sample_lik(cnt.data_ptr(), rows, stride, bp, b0, lik.data_ptr(), seed, sweep, stream_ptr(stream)))
+    return lik
+
+
+def lik_loglik(cnt, lik, stream=None):
+    """stb_lik_loglik on device tensors cnt (int32 holding uint32) and lik (float64), both (rows, stride):
+    (sum cnt log lik, cells with a count and no likelihood)"""
+    rows, stride = int(cnt.shape[0]), int(cnt.shape[1])
+    tot, imp = C.c_double(0.0), C.c_uint64(0)
+    check(lib().stb_lik_loglik(cnt.data_ptr(), lik.data_ptr(), rows, stride, C.byref(tot), C.byref(imp), stream_ptr(stream)))
+    return tot.value, imp.value
+
+
 def sampleb_device(b, shape, scale, N, T, a, seed: int, sweep: int, loops: int = 1, verbose: int = 0, stream=None):
     """stb_sampleb_device on device tensors N, T (int32 holding uint32 counts).  NaN -> StbError"""
     r = float(lib().stb_sampleb_device(float(b), int(N.shape[0]), float(shape), float(scale), N.data_ptr(), T.data_ptr(),
@@ -1047,6 +1085,32 @@ class TableIndicators:
             raise StbError("TableIndicators.class_counts: classes are not set")
         check(self.L.stb_tindic_class_counts(self.h, cnt.ctypes.data_as(c_u32_p)))
         return cnt
+
+    # ---- the likelihood and the base weights drawn on the device (stb_tindic_sample_lik / _sample_h / _loglik)
+
+    def sample_lik(self, beta, seed: int, sweep: int):
+        """the matrix drawn again: column k from Dirichlet(beta_w + customers of class w at dish k), behind the queued
+        sweeps; beta a scalar or one value per row of the matrix.  Classes and a matrix must be set"""
+        keep, bp, b0 = _prior(beta, self.lik_device()[1])
+        check(self.L.stb_tindic_sample_lik(self.h, bp, b0, seed, sweep))
+
+    def sample_h(self, gamma, seed: int, sweep: int):
+        """the base weights drawn again: h from Dirichlet(gamma_k + tables of dish k), the same for every restaurant;
+        gamma a scalar or one value per dish (the largest K).  Give it another seed than sample_lik"""
+        keep, gp, g0 = _prior(gamma, self.maxK)
+        check(self.L.stb_tindic_sample_h(self.h, gp, g0, seed, sweep))
+
+    def loglik(self):
+        """(sum over customers of log lik[class, dish], cells with customers and no likelihood) of the current state"""
+        tot, imp = C.c_double(0.0), C.c_uint64(0)
+        check(self.L.stb_tindic_loglik(self.h, C.byref(tot), C.byref(imp)))
+        return tot.value, imp.value
+
+    def get_h(self):
+        """h[G] float64 (1 everywhere when none is set), after the queued work"""
+        h = np.zeros(self.G, dtype=np.float64)
+        check(self.L.stb_tindic_get_h(self.h, dp(h)))
+        return h
 
     def free(self):
         if self.h:

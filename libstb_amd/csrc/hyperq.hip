@@ -36,44 +36,11 @@
 #include "stb_common.h"
 #include "tcounts.h"
 #include "hyperq.h"
+#include "gamma_dev.h"  // hq_unit, hq_log_gamma, HQ_CAP
 #include "ticket_geom.h"
 
 #define HQ_CHUNK STB_TG_BLOCK  // (one constant for the kernel, the launch and stb_reduce_geometry)
-#define HQ_CAP 64
 #define HQ_MAXTHREADS 512
-
-__device__ __forceinline__ double hq_unit(uint64_t key, uint64_t k) {
-  const uint64_t m = stb_mix64(key + k * STB_GAMMA) >> 11;
-  return m ? (double)m * (1.0 / 9007199254740992.0) : (1.0 / 18014398509481984.0);
-}
-
-// log of a Gamma(alpha) variate, alpha >= 1; k counts the uniforms taken from the substream
-__device__ __forceinline__ double hq_log_gamma_ge1(double alpha, uint64_t key, uint64_t &k, bool &bad) {
-#pragma clang fp contract(off)
-  const double d = alpha - 1.0 / 3.0;
-  const double c = 1.0 / sqrt(9.0 * d);
-  for (int it = 0; it < HQ_CAP; it++) {
-    const double u1 = hq_unit(key, ++k);
-    const double u2 = hq_unit(key, ++k);
-    const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-    const double w = 1.0 + c * x;
-    if (!(w > 0.0)) continue;
-    const double v = w * w * w;
-    const double u = hq_unit(key, ++k);
-    const double lv = log(v);
-    if (log(u) < ((0.5 * (x * x) + d) - d * v) + d * lv) return log(d) + lv;
-  }
-  bad = true;
-  return NAN;
-}
-
-__device__ __forceinline__ double hq_log_gamma(double alpha, uint64_t key, uint64_t &k, bool &bad) {
-#pragma clang fp contract(off)
-  if (alpha >= 1.0) return hq_log_gamma_ge1(alpha, key, k, bad);
-  const double lg = hq_log_gamma_ge1(alpha + 1.0, key, k, bad);
-  const double u = hq_unit(key, ++k);
-  return lg + log(u) / alpha;
-}
 
 __device__ __forceinline__ double hq_draw_L(double b, double Ni, uint64_t key, uint64_t i, bool &bad) {
 #pragma clang fp contract(off)

@@ -27,6 +27,7 @@
 #include "hyperj.h"
 #include "logjoint.h"
 #include "tindic.h"
+#include "tlik.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
 // ---- lane form -------------------------------------------------------------------------------------------------
@@ -241,6 +242,7 @@ struct stb_tindic {
   unsigned cls_rows;
   double *d_lik;        // [lik_rows x lik_stride] (null: every L is 1)
   unsigned lik_rows, lik_stride;
+  bool lik_bad, h_bad;  // a draw of stb_tindic_sample_lik / _sample_h failed: the matrix / h is undefined, dish sweeps are refused
   unsigned long long *d_info, *h_info;  // {skipped, stuck} on the device, and pinned
   bool need_table;      // some visit can read a V cell (max n >= 2 and M >= 2); otherwise no indicator is ever added
   uint64_t *d_koff, *d_coff;
@@ -452,6 +454,7 @@ extern "C" int stb_tindic_set_h(stb_tindic_t *s, const double *hflat) {
     if (!rc && hipMemcpy(s->d_h, hflat, sizeof(double) * s->G, hipMemcpyHostToDevice) != hipSuccess)
       rc = stb_fail("stb_tindic_set_h: %s", hipGetErrorString(hipGetLastError()));
   }
+  if (!rc) s->h_bad = false;
   stb_device_leave(prev);
   return rc;
 }
@@ -768,6 +771,7 @@ extern "C" int stb_tindic_set_lik(stb_tindic_t *s, const double *lik_host, unsig
     if (s->d_lik) (void)hipFree(s->d_lik);
     s->d_lik = nullptr;
     s->lik_rows = s->lik_stride = 0;
+    s->lik_bad = false;
   } else if (!rc) {
     const size_t cells = (size_t)rows * stride;
     double *d = nullptr;
@@ -783,6 +787,7 @@ extern "C" int stb_tindic_set_lik(stb_tindic_t *s, const double *lik_host, unsig
       s->d_lik = d;
       s->lik_rows = rows;
       s->lik_stride = stride;
+      s->lik_bad = false;
     }
   }
   stb_device_leave(prev);
@@ -817,6 +822,9 @@ extern "C" int stb_tindic_sweep_dishes(stb_tindic_t *s, double a, const double *
   if (s->d_lik && (!s->d_cls || s->cls_rows > s->lik_rows))
     return stb_fail("%s: the likelihood has %u rows; classes %s", who, s->lik_rows,
                     s->d_cls ? "were set with more" : "are not set (stb_tindic_set_classes)");
+  if ((s->d_lik && s->lik_bad) || s->h_bad)
+    return stb_fail("%s: the last stb_tindic_sample_%s failed and left %s undefined; draw again or set it", who,
+                    s->h_bad ? "h" : "lik", s->h_bad ? "h" : "the likelihood");
   if (info) info->skipped = info->stuck = 0;
   if (nsweeps == 0) return 0;
   const int prev = stb_device_enter(s->dev);
@@ -880,6 +888,115 @@ extern "C" int stb_tindic_class_counts(stb_tindic_t *s, uint32_t *cnt_out) {
     if (hipStreamSynchronize(s->st) != hipSuccess && !rc) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
     stb_pool_free(d_cnt);
   }
+  stb_device_leave(prev);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the likelihood and the base weights drawn on the device, and the data term (the kernels are tlik.hip's)
+
+// what _sample_lik and _loglik ask of the object before anything is queued
+static int ti_lik_ready(stb_tindic_t *s, const char *who) {
+  if (!s->d_cls) return stb_fail("%s: classes are not set (stb_tindic_set_classes)", who);
+  if (!s->d_lik) return stb_fail("%s: no likelihood matrix is set (stb_tindic_set_lik; a NULL matrix with a shape makes one)", who);
+  if (s->cls_rows > s->lik_rows)
+    return stb_fail("%s: the likelihood has %u rows; classes were set with %u", who, s->lik_rows, s->cls_rows);
+  return 0;
+}
+
+// customers per (class, dish) over the matrix's shape, into a buffer from the cache, queued on the object's stream
+static int ti_count_classes(stb_tindic_t *s, uint32_t **d_cnt, const char *who) {
+  const size_t bytes = sizeof(uint32_t) * (size_t)s->lik_rows * s->lik_stride;
+  if (ti_materialise_cust(s, who)) return 1;
+  if (stb_pool_malloc((void **)d_cnt, bytes) != hipSuccess) return stb_fail("%s: out of device memory for the counts", who);
+  if (hipMemsetAsync(*d_cnt, 0, bytes, s->st) != hipSuccess) return stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  return stb_td_class_counts(s->d_cust, s->d_cls, s->C, s->lik_rows, s->lik_stride, *d_cnt, s->st);
+}
+
+extern "C" int stb_tindic_sample_lik(stb_tindic_t *s, const double *beta_host, double beta0, uint64_t seed, uint64_t sweep) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sample_lik";
+  if (!s) return stb_fail("%s: null object", who);
+  if (ti_lik_ready(s, who)) return 1;
+  if (stb_tl_check_prior(beta_host, s->lik_rows, beta0, "beta", who)) return 1;
+  const int prev = stb_device_enter(s->dev);
+  uint32_t *d_cnt = nullptr;
+  int rc = ti_count_classes(s, &d_cnt, who);
+  if (!rc) {
+    bool touched = false;
+    rc = stb_tl_sample_lik(d_cnt, s->lik_rows, s->lik_stride, beta_host, beta0, s->d_lik, seed, sweep, s->st, who, &touched);
+    if (touched) s->lik_bad = rc != 0;  // (a call that failed before its first launch left the matrix as it was)
+  }
+  if (d_cnt) {
+    if (rc) (void)hipStreamSynchronize(s->st);  // (the cache may hand the buffer on at once)
+    stb_pool_free(d_cnt);
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_loglik(stb_tindic_t *s, double *total, uint64_t *impossible) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_loglik";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!total) return stb_fail("%s: total is required", who);
+  if (ti_lik_ready(s, who)) return 1;
+  if (s->lik_bad) return stb_fail("%s: the last stb_tindic_sample_lik failed and left the likelihood undefined", who);
+  const int prev = stb_device_enter(s->dev);
+  uint32_t *d_cnt = nullptr;
+  int rc = ti_count_classes(s, &d_cnt, who);
+  if (!rc) rc = stb_tl_loglik(d_cnt, s->d_lik, s->lik_rows, s->lik_stride, total, impossible, s->st, who);
+  if (d_cnt) {
+    if (rc) (void)hipStreamSynchronize(s->st);
+    stb_pool_free(d_cnt);
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_sample_h(stb_tindic_t *s, const double *gamma_host, double gamma0, uint64_t seed, uint64_t sweep) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sample_h";
+  if (!s) return stb_fail("%s: null object", who);
+  if (s->flags & STB_TI_REF_ODDS_FLAG)
+    return stb_fail("%s: the object was created with STB_TI_REF_ODDS; its sweeps do not leave the law h is drawn under", who);
+  if (s->maxK < 1 || s->maxK > STB_TD_MAXK)
+    return stb_fail("%s: the largest restaurant has K=%u dishes (1 to STB_TD_MAXK = %d)", who, s->maxK, STB_TD_MAXK);
+  if (stb_tl_check_prior(gamma_host, s->maxK, gamma0, "gamma", who)) return 1;
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  double *d_h = s->d_h;  // an object without h gets one only if the draw is queued
+  if (!d_h && hipMalloc((void **)&d_h, sizeof(double) * (s->G ? s->G : 1)) != hipSuccess) {
+    d_h = nullptr;
+    rc = stb_fail("%s: out of device memory", who);
+  }
+  if (!rc) {
+    bool touched = false;
+    rc = stb_tl_sample_h(s->I, s->d_koff, s->d_t, s->maxK, gamma_host, gamma0, d_h, seed, sweep, s->st, who, &touched);
+    if (touched) {
+      s->d_h = d_h;
+      s->h_bad = rc != 0;
+    } else if (d_h != s->d_h) {
+      (void)hipFree(d_h);  // (nothing was queued: the object keeps the h it had)
+    }
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_get_h(stb_tindic_t *s, double *h_out) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_get_h";
+  if (!s || !h_out) return stb_fail("%s: null %s", who, s ? "h_out" : "object");
+  if (!s->d_h) {
+    for (uint64_t g = 0; g < s->G; g++) h_out[g] = 1.0;
+    return 0;
+  }
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if ((s->G && hipMemcpyAsync(h_out, s->d_h, sizeof(double) * s->G, hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
+      hipStreamSynchronize(s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
   stb_device_leave(prev);
   return rc;
 }
