@@ -27,10 +27,14 @@
  *      dish's class distribution is drawn from its Dirichlet(0.5) posterior given the (class, dish) counts and h from its
  *      Dirichlet(1) posterior given the table counts (stb_tindic_sample_lik, stb_tindic_sample_h), on the device; with -L
  *      the line gains the data term (stb_tindic_loglik) and the complete-data log joint.
+ *  11. with -P (needs -d -z) every restaurant gets NCUST / 5 held-out customers of the same two synthetic classes; each
+ *      iteration's line carries their log likelihood under the state's predictive dish proportions and the running
+ *      estimate sum_c log((1/S) sum_s p_c) over the iterations so far (stb_tindic_heldout), and the per-customer
+ *      perplexity is printed at the end.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P]
  */
 #include <math.h>
 #include <stdio.h>
@@ -46,10 +50,10 @@
 #define DISHES 50
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, explicit_d = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzw")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwP")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -63,10 +67,15 @@ int main(int argc, char **argv) {
     else if (c == 'L') showlj = 1;
     else if (c == 'z') ondev = dishes = 1;
     else if (c == 'w') redraw = 1;
+    else if (c == 'P') predict = 1;
     else return 2;
   }
   if (redraw && !(explicit_d && dishes)) {
     fprintf(stderr, "pyp_resample: -w needs -d -z\n");
+    return 2;
+  }
+  if (predict && !(explicit_d && dishes)) {
+    fprintf(stderr, "pyp_resample: -P needs -d -z\n");
     return 2;
   }
   srand48(seed);
@@ -148,6 +157,19 @@ int main(int argc, char **argv) {
       if (stb_tindic_set_classes(ti, cls, 2) || stb_tindic_set_lik(ti, lik, 2, DISHES)) yaps_quit("dishes: %s\n", stb_last_error());
       free(cls);
     }
+    double ho_avg = 0.0;
+    uint64_t ho_n = 0;
+    if (predict) { /* ncust / 5 held-out customers a restaurant, the classes by parity as above */
+      const uint64_t per = (uint64_t)ncust / 5;
+      uint64_t *hoff = malloc(sizeof(*hoff) * ((size_t)J + 1));
+      scnt_int *hcls = malloc(sizeof(*hcls) * ((size_t)J * per + 1));
+      ho_n = (uint64_t)J * per;
+      for (j = 0; j <= J; j++) hoff[j] = (uint64_t)j * per;
+      for (cc = 0; cc < ho_n; cc++) hcls[cc] = (scnt_int)(cc & 1);
+      if (stb_tindic_set_heldout(ti, hoff, hcls)) yaps_quit("held-out customers: %s\n", stb_last_error());
+      free(hoff);
+      free(hcls);
+    }
     for (it = 0; it < cycles; it++) {
       if (dishes) {
         stb_tdish_info_t di;
@@ -192,13 +214,23 @@ int main(int argc, char **argv) {
           double dt;
           if (stb_tindic_loglik(ti, &dt, NULL)) yaps_quit("stb_tindic_loglik: %s\n", stb_last_error());
           printf("iteration %d: log joint %.6f (pairs %.6f, base %.6f, restaurants %.6f, indicators %.6f) data %.6f complete %.6f "
-                 "a=%.4f b=%.3f\n", it, lj, li.pairs, li.base, li.restaurants, li.binom, dt, lj + dt, a, b);
+                 "a=%.4f b=%.3f%s", it, lj, li.pairs, li.base, li.restaurants, li.binom, dt, lj + dt, a, b, predict ? "" : "\n");
         } else
-          printf("iteration %d: log joint %.6f (pairs %.6f, base %.6f, restaurants %.6f, indicators %.6f) a=%.4f b=%.3f\n", it, lj,
-                 li.pairs, li.base, li.restaurants, li.binom, a, b);
+          printf("iteration %d: log joint %.6f (pairs %.6f, base %.6f, restaurants %.6f, indicators %.6f) a=%.4f b=%.3f%s", it, lj,
+                 li.pairs, li.base, li.restaurants, li.binom, a, b, predict ? "" : "\n");
+      }
+      if (predict) {
+        double ho;
+        if (stb_tindic_heldout(ti, a, bvec, 0, &ho, NULL, NULL) || stb_tindic_heldout(ti, a, bvec, STB_PR_ACCUMULATE, &ho_avg, NULL, NULL))
+          yaps_quit("stb_tindic_heldout: %s\n", stb_last_error());
+        if (showlj) printf(" heldout %.6f avg %.6f\n", ho, ho_avg);
+        else printf("iteration %d: heldout %.6f avg %.6f\n", it, ho, ho_avg);
       }
     }
     if (stb_tindic_get(ti, tf, T)) yaps_quit("stb_tindic_get: %s\n", stb_last_error());
+    if (predict && ho_n && cycles > 0)
+      printf("held-out: %llu customers, log likelihood %.6f averaged over %d states, perplexity %.6f\n", (unsigned long long)ho_n,
+             ho_avg, cycles, exp(-ho_avg / (double)ho_n));
     if (joint) printf("joint steps: %d of %d proposals accepted, last a=%.4f b=%.3f\n", accepted, steps, a, b);
     for (j = 0, g = 0; j < J; j++)
       for (i = 0; i < DISHES; i++, g++) t[j][i] = tf[g];

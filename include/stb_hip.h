@@ -769,6 +769,90 @@ typedef struct stb_reduce_geom {
 } stb_reduce_geom_t;
 int stb_reduce_geometry(int which, uint64_t I, int D, int J, int waves, stb_reduce_geom_t *out);
 
+/* ---- what a state predicts: dish proportions and held-out customers (predict.hip) ----
+ * Pairs (n_k, t_k, h_k), k < K_i, b_i and a as for stb_sample_tdish; T_i = sum_k t_k, N_i = sum_k n_k.  Given the seating,
+ * the next customer of restaurant i sits at an existing table of dish k with weight n_k - t_k a and opens a new table
+ * serving k with weight (b_i + T_i a) h_k; the sizes of the tables do not enter.  So
+ *     theta_ik = ((n_k - t_k a) + g_i h_k) / (b_i + N_i),     g_i = b_i + T_i a
+ *     p_c      = sum_k theta_ik lik[cls_c stride + k]         a held-out customer c of restaurant i
+ * the state's exact one-step predictive: with S^{n+1}_{t'} = (n - t' a) S^n_{t'} + S^n_{t'-1},
+ * p(n + e_k, t) + p(n + e_k, t + e_k) = p(n, t) theta_k(t) term by term, and summing over t gives
+ * E_{t|n}[theta_k] = p(n + e_k) / p(n).  No Stirling table is read.  sum_k theta_ik = 1 exactly when the restaurant's
+ * h sums to 1 -- after stb_tindic_sample_h that is every restaurant with K_i = Kmax; otherwise theta is the
+ * sub-probability on the listed dishes, and p_c the probability that the customer is of class cls_c AND eats a listed dish.
+ * The estimate of a held-out set's log likelihood over S states of a chain is sum_c log((1/S) sum_s p_c^(s)), not the
+ * mean of the states' logs: STB_PR_ACCUMULATE adds a state's p_c into the caller's p, stb_heldout_loglik divides by S.
+ *
+ * stb_predict_dishes (k_predict), one wave a restaurant.  The arithmetic is part of the contract (FP64, no contraction;
+ * tests/pr_oracle.py replays it):
+ *   T_i and N_i are the kernel's own uint64 sums over the restaurant's pairs (no d_T is read).
+ *   T = (double)T_i, N = (double)N_i, n = (double)n_k, t = (double)t_k, b = d_bpar[i], h = d_h[pair] (1.0 without d_h):
+ *       g = b + T * a        den = b + N        x = n - t * a        theta = (x + g * h) / den
+ *   each one product, then one sum, left to right as written, then the one division.  N_i = 0: theta = h, no division.
+ *   L_k = d_lik[cls * stride + k]; 0.0 when cls >= rows; 1.0 without d_lik.  q_k = theta_k * L_k.
+ *   Dishes are taken in blocks of 64, lane l the dish 64 j + l of block j (+0.0 past K_i); a block is summed by the
+ *   64-lane shuffle tree of stb_logjoint, v += shfl_down(v, o), o = 32, 16, .. 1, lane 0 taken: s_j.  p_c = s_0, then
+ *   p_c = p_c + s_j for j = 1, 2, .. in plain doubles.
+ *   theta: d_theta NULL, or I rows of tstride doubles; columns K_i .. tstride-1 are written 0.
+ *   p: d_p[c], c the flat held-out index -- CSR over d_hoff[I + 1], classes d_hcls[d_hoff[I]]; d_hoff NULL: no held-out
+ *   customers.  With STB_PR_ACCUMULATE d_p[c] = d_p[c] + p_c (one lane owns a customer: S calls give the bits of the S
+ *   values added in call order), else d_p[c] = p_c.
+ *   skipped  a restaurant with K_i > STB_TD_MAXK, K_i > stride (with a matrix) or K_i > tstride (with d_theta): its
+ *            theta row is 0, its customers' p is 0 when overwriting and left alone when accumulating; *d_skipped (NULL,
+ *            or one uint64 on the device) is increased by their number.
+ * The bits depend on neither grid nor workgroup size (STB_PREDICT_WAVES = 1, 2, 4 or 8 waves a workgroup; default 4),
+ * nor on which restaurants share a call: K_i <= 64 keeps theta in registers and K_i > 64 in LDS, chosen per restaurant,
+ * the arithmetic the same.  No wait: the call returns when the launch is queued.
+ *
+ * stb_heldout_loglik (k_heldout_sum): x_c = log(d_p[c] / (double)samples).  A customer whose d_p[c] / samples is not a
+ * positive finite number (0, negative, inf, NaN, or a quotient that underflows to 0) is impossible: it adds +0.0 to the
+ * sums and is counted; its restaurant's H_i and the total are -inf.  No NaN is ever produced.  Per restaurant the x_c are
+ * taken in chunks of 64 in CSR order through the same tree (+0.0 past the end), the chunk sums added in order in
+ * double-double, H_i = hi + lo (d_Hi: NULL, or I doubles on the device).  Over restaurants: stb_logjoint's association,
+ * geometry and ticket (blocks of 256 in the one fixed tree, block sums added in block order in double-double by the last
+ * workgroup; stb_reduce_geometry(STB_GEOM_LOGJOINT, I, 0, 0, waves) is the launch, waves STB_PREDICT_WAVES where it is
+ * set, else stb_logjoint's choice).  One launch, one wait; *total_host and *info arrive through pinned memory.  info:
+ * impossible customers, customers = d_hoff[I] - d_hoff[0], skipped = 0 (the object layer puts k_predict's count there).
+ * I = 0 or no customers gives 0.
+ * Both calls refuse before anything is queued, with stb_last_error() set: a outside [0, 1), a null required array (koff,
+ * n, t, bpar; p, hoff and total_host for the sum), d_hoff without d_hcls and d_p, a matrix with rows or stride 0, d_theta
+ * with tstride 0, samples 0, unknown flag bits, I < 0.
+ *
+ * Object layer, on an stb_tindic_t: queued on the object's stream behind its sweeps; none of it writes n, t, T, cust, h
+ * or the matrix; a and bpar are arguments, as for _sweep and _logjoint.
+ *   stb_tindic_set_heldout    hoff[I + 1] (hoff[0] = 0, non-decreasing) and the classes hcls[hoff[I]] from the host,
+ *                             every class < the matrix's rows when a matrix is set (checked again at use).  Allocates
+ *                             the accumulator p[hoff[I]], zeroes it and sets the sample count to 0.  hoff NULL removes
+ *                             the held-out customers.
+ *   stb_tindic_predict        theta to the host, I x tstride, tstride >= the largest K_i
+ *   stb_tindic_heldout        without flags: the current state's sum_c log p_c through a scratch p; the accumulator is
+ *                             left alone.  With STB_PR_ACCUMULATE: adds the state's p_c into the accumulator, counts the
+ *                             sample (S), and returns the running estimate sum_c log(acc_c / S).  Hi_host (or NULL)
+ *                             receives the I values H_i.
+ *   stb_tindic_heldout_reset  zeroes the accumulator and S
+ *   stb_tindic_heldout_get    the accumulator (p_out: hoff[I] doubles, or NULL) and S (or NULL) to the host
+ * Refused, the state and the accumulator as they were: no held-out set (_heldout, _heldout_reset, _heldout_get); a, bpar
+ * as _sweep refuses them; h left undefined by a failed stb_tindic_sample_h, or (_heldout) the matrix by a failed
+ * _sample_lik; a held-out class >= the matrix's rows; some K_i > STB_TD_MAXK; tstride below the largest K_i. */
+#define STB_PR_ACCUMULATE 1u
+typedef struct stb_predict_info { uint64_t skipped, impossible, customers; } stb_predict_info_t;
+int stb_predict_dishes(double a, const double *d_bpar, int I, const uint64_t *d_koff, const uint32_t *d_n,
+                       const uint16_t *d_t, const double *d_h /* NULL: 1 */,
+                       double *d_theta /* NULL, or I x tstride */, unsigned tstride,
+                       const uint64_t *d_hoff /* I+1, or NULL: no held-out customers */, const uint32_t *d_hcls,
+                       const double *d_lik /* NULL: 1 */, unsigned rows, unsigned stride,
+                       double *d_p, unsigned flags, uint64_t *d_skipped /* NULL, or one uint64 the call adds to */,
+                       void *stream);
+int stb_heldout_loglik(const double *d_p, const uint64_t *d_hoff, int I, unsigned samples,
+                       double *d_Hi /* NULL, or I */, double *total_host, stb_predict_info_t *info /* or NULL */,
+                       void *stream);
+int stb_tindic_set_heldout(stb_tindic_t *s, const uint64_t *hoff_host /* I+1, or NULL */, const uint32_t *hcls_host);
+int stb_tindic_predict(stb_tindic_t *s, double a, const double *bpar, double *theta_host, unsigned tstride);
+int stb_tindic_heldout(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total,
+                       double *Hi_host /* or NULL */, stb_predict_info_t *info /* or NULL */);
+int stb_tindic_heldout_reset(stb_tindic_t *s);
+int stb_tindic_heldout_get(stb_tindic_t *s, double *p_out /* or NULL */, unsigned *samples /* or NULL */);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

@@ -69,6 +69,14 @@ class TDishInfo(C.Structure):
     _fields_ = [("skipped", C.c_uint64), ("stuck", C.c_uint64)]
 
 
+PR_ACCUMULATE = 1  # stb_predict_dishes / stb_tindic_heldout flag: add the state's p into the accumulator
+
+
+class PredictInfo(C.Structure):
+    """stb_predict_info_t (include/stb_hip.h)"""
+    _fields_ = [("skipped", C.c_uint64), ("impossible", C.c_uint64), ("customers", C.c_uint64)]
+
+
 GEOM_LOGQ, GEOM_JOINT_TERMS, GEOM_LOGJOINT = 0, 1, 2  # stb_reduce_geometry's `which`
 
 
@@ -268,6 +276,15 @@ def lib() -> C.CDLL:
     sig("stb_tcounts_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
     sig("stb_tindic_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
     sig("stb_reduce_geometry", i, [i, u64, i, i, i, C.POINTER(ReduceGeom)])
+    # ---- what a state predicts: dish proportions and held-out customers
+    pri = C.POINTER(PredictInfo)
+    sig("stb_predict_dishes", i, [d, vp, i, vp, vp, vp, vp, vp, u, vp, vp, vp, u, u, vp, u, vp, vp])
+    sig("stb_heldout_loglik", i, [vp, vp, i, u, vp, c_double_p, pri, vp])
+    sig("stb_tindic_set_heldout", i, [vp, C.POINTER(u64), c_u32_p])
+    sig("stb_tindic_predict", i, [vp, d, c_double_p, c_double_p, u])
+    sig("stb_tindic_heldout", i, [vp, d, c_double_p, u, c_double_p, c_double_p, pri])
+    sig("stb_tindic_heldout_reset", i, [vp])
+    sig("stb_tindic_heldout_get", i, [vp, c_double_p, C.POINTER(u)])
     # (private entry points: the customers per restaurant as d_N or as d_coff prefix sums, for tests)
     sig("stb_hq_logq", i, [d, d, i, vp, vp, vp, c_double_p, u64, u64, vp])
     sig("stb_hj_joint_terms", i, [c_double_p, i, c_double_p, i, vp, vp, vp, u64, vp, vp])
@@ -721,6 +738,41 @@ def logjoint(tabs, a, bpar, koff, n, t, T=None, h=None, indicators: bool = False
     return tot.value, Li, info
 
 
+def predict_dishes(a, bpar, koff, n, t, h=None, tstride: int = 0, hoff=None, hcls=None, lik=None, p=None,
+                   accumulate: bool = False, skipped=None, stream=None, flags=None):
+    """stb_predict_dishes on device arrays: koff (int64 [I+1]), n (int32), t (int16), bpar and h (float64; h None: all 1),
+    hoff (int64 [I+1], or None: no held-out customers), hcls (int32 holding uint32 classes), lik (float64 (rows, stride), or
+    None: all 1) torch tensors on the device.  tstride > 0: theta comes back as a float64 (I, tstride) device tensor.  p: a
+    float64 device tensor of hoff[I] values the call overwrites or (accumulate) adds to; None with hoff: a new one (zeros
+    when accumulating).  skipped: None, or an int64 device tensor of one element the call adds to.  Queued, no wait.
+    Returns (theta or None, p or None)."""
+    torch = _torch()
+    I = int(koff.shape[0]) - 1
+    theta = torch.empty((max(I, 1), tstride), dtype=torch.float64, device=koff.device)[:I] if tstride > 0 else None
+    if hoff is not None and p is None:
+        Hc = int(hoff[-1].item())
+        p = torch.zeros(max(Hc, 1), dtype=torch.float64, device=koff.device)[:Hc]
+    rows, stride = (int(lik.shape[0]), int(lik.shape[1])) if lik is not None else (0, 0)
+    fl = (PR_ACCUMULATE if accumulate else 0) if flags is None else int(flags)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    check(lib().stb_predict_dishes(float(a), ptr(bpar), I, koff.data_ptr(), n.data_ptr(), t.data_ptr(), ptr(h), ptr(theta),
+                                   int(tstride), ptr(hoff), ptr(hcls), ptr(lik), rows, stride, ptr(p), fl, ptr(skipped),
+                                   stream_ptr(stream)))
+    return theta, p
+
+
+def heldout_loglik(p, hoff, samples: int = 1, want_Hi: bool = True, stream=None):
+    """stb_heldout_loglik on device tensors p (float64 [hoff[I]]) and hoff (int64 [I+1]): (sum_c log(p_c / samples), H_i as
+    a float64 device tensor or None, PredictInfo), after one wait"""
+    torch = _torch()
+    I = int(hoff.shape[0]) - 1
+    Hi = torch.empty(max(I, 1), dtype=torch.float64, device=hoff.device)[:I] if want_Hi else None
+    tot, info = C.c_double(0.0), PredictInfo()
+    check(lib().stb_heldout_loglik(p.data_ptr(), hoff.data_ptr(), I, int(samples), None if Hi is None else Hi.data_ptr(),
+                                   C.byref(tot), C.byref(info), stream_ptr(stream)))
+    return tot.value, Hi, info
+
+
 def reduce_geometry(which: int, I: int, D: int = 1, J: int = 1, waves: int = 0) -> ReduceGeom:
     """stb_reduce_geometry: what stb_sample_logq (GEOM_LOGQ), stb_joint_terms on a D x J grid (GEOM_JOINT_TERMS) or
     stb_logjoint (GEOM_LOGJOINT) launches for I restaurants on the current device; waves 0: what the call would take now"""
@@ -1111,6 +1163,54 @@ class TableIndicators:
         h = np.zeros(self.G, dtype=np.float64)
         check(self.L.stb_tindic_get_h(self.h, dp(h)))
         return h
+
+    # ---- what the state predicts (stb_tindic_predict / _set_heldout / _heldout)
+
+    def set_heldout(self, hoff=None, hcls=None):
+        """the held-out customers of every restaurant: hoff[I+1] prefix sums and their classes hcls[hoff[I]]; None removes
+        them.  Zeroes the accumulator and the sample count"""
+        if hoff is None:
+            check(self.L.stb_tindic_set_heldout(self.h, None, None))
+            self.Hc = 0
+            return
+        hoff = np.ascontiguousarray(hoff, dtype=np.uint64)
+        hcls = np.ascontiguousarray([] if hcls is None else hcls, dtype=np.uint32)
+        if hoff.shape != (self.I + 1,) or hcls.shape[0] != int(hoff[-1]):
+            raise StbError(f"TableIndicators.set_heldout: {hoff.shape[0]} offsets for {self.I} restaurants, "
+                           f"{hcls.shape[0]} classes for {int(hoff[-1])} customers")
+        check(self.L.stb_tindic_set_heldout(self.h, hoff.ctypes.data_as(C.POINTER(C.c_uint64)), hcls.ctypes.data_as(c_u32_p)))
+        self.Hc = int(hoff[-1])
+
+    def predict(self, a, bpar, tstride: int = 0):
+        """theta (I, tstride) float64: every restaurant's predictive dish proportions in the current state (columns past
+        K_i are 0); tstride 0: the largest K"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        tstride = int(tstride) or max(self.maxK, 1)
+        theta = np.zeros((self.I, tstride), dtype=np.float64)
+        check(self.L.stb_tindic_predict(self.h, float(a), dp(bpar), dp(theta), tstride))
+        return theta
+
+    def heldout(self, a, bpar, accumulate: bool = False, want_Hi: bool = True, flags=None):
+        """(total, H_i[I] or None, PredictInfo): the held-out customers' log likelihood -- the current state's sum_c log p_c,
+        or with accumulate the running estimate sum_c log(acc_c / S) after this state's p_c went into the accumulator"""
+        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        Hi = np.zeros(self.I, dtype=np.float64) if want_Hi else None
+        tot, info = C.c_double(0.0), PredictInfo()
+        fl = (PR_ACCUMULATE if accumulate else 0) if flags is None else int(flags)
+        check(self.L.stb_tindic_heldout(self.h, float(a), dp(bpar), fl, C.byref(tot), None if Hi is None else dp(Hi),
+                                        C.byref(info)))
+        return tot.value, Hi, info
+
+    def heldout_reset(self):
+        """zeroes the accumulator and the sample count"""
+        check(self.L.stb_tindic_heldout_reset(self.h))
+
+    def heldout_get(self):
+        """(the accumulator p[Hc] float64, the states accumulated)"""
+        S = C.c_uint(0)
+        p = np.zeros(getattr(self, "Hc", 0), dtype=np.float64)
+        check(self.L.stb_tindic_heldout_get(self.h, dp(p) if p.size else None, C.byref(S)))
+        return p, S.value
 
     def free(self):
         if self.h:

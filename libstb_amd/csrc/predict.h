@@ -1,0 +1,30 @@
+/* predict.h -- private: what the object layer (tindic.hip) and the samplers' cache need of predict.hip, beyond
+ * include/stb_hip.h. */
+#ifndef STB_PREDICT_H
+#define STB_PREDICT_H
+#include <stdint.h>
+#include "../../include/stb_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* frees the calling thread's block sums, counters and result words (stb_sampler_cache_clear) */
+void stb_pr_release(void);
+#ifdef __cplusplus
+}
+#endif
+
+#if defined(__HIPCC__)
+/* the checks stb_predict_dishes and the object's calls share (0, or 1 with stb_last_error() set) */
+int stb_pr_check(double a, unsigned flags, int I, const char *who);
+/* k_predict on st, no wait; arguments checked by the caller */
+int stb_pr_predict(double a, const double *d_bpar, int I, const uint64_t *d_koff, const uint32_t *d_n, const uint16_t *d_t,
+                   const double *d_h, double *d_theta, unsigned tstride, const uint64_t *d_hoff, const uint32_t *d_hcls,
+                   const double *d_lik, unsigned rows, unsigned stride, double *d_p, unsigned flags, uint64_t *d_skipped,
+                   hipStream_t st, const char *who);
+/* k_heldout_sum on st, the copy of d_Hi to Hi_host (when both are given) and the wait; d_skipped (or NULL: 0) is a
+ * device word whose value goes into info->skipped */
+int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned samples, double *d_Hi, double *Hi_host,
+                   double *total_host, stb_predict_info_t *info, const uint64_t *d_skipped, hipStream_t st, const char *who);
+#endif
+#endif

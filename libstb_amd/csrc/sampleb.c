@@ -21,6 +21,7 @@
 #include "hyperq.h"
 #include "hyperj.h"
 #include "logjoint.h"
+#include "predict.h"
 
 #define NPRE 3 /* abscissae ARMS is known to ask for first (lib/arms.c:117-119) */
 
@@ -69,6 +70,7 @@ void stb_sampleb_cache_clear(void) {
   stb_hq_release();
   stb_hj_release();
   stb_lj_release();
+  stb_pr_release();
 }
 
 static int use_slice(void) {

@@ -28,6 +28,7 @@
 #include "logjoint.h"
 #include "tindic.h"
 #include "tlik.h"
+#include "predict.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
 // ---- lane form -------------------------------------------------------------------------------------------------
@@ -266,6 +267,13 @@ struct stb_tindic {
   void *d_sws;
   size_t sws_bytes;
   double a_sfilled;     // the discount the S slab holds (NaN: none yet)
+  // held-out customers (predict.hip): CSR over the restaurants, their classes, and the accumulator of p over states
+  uint64_t *d_hoff;     // [I + 1] (null: no held-out set)
+  uint32_t *d_hcls;     // [Hc]
+  double *d_pacc;       // [Hc] sum over the accumulated states of p_c
+  uint64_t Hc;
+  unsigned hcls_max;    // the largest held-out class (0 when Hc = 0)
+  unsigned hsamples;    // states accumulated
   hipStream_t st;
 };
 
@@ -274,7 +282,7 @@ static void ti_release(stb_tindic_t *s) {
   for (void *p : pooled)
     if (p) stb_pool_free(p);
   void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws,
-                 s->d_cls, s->d_lik, s->d_info};
+                 s->d_cls, s->d_lik, s->d_info, s->d_hoff, s->d_hcls, s->d_pacc};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (s->h_info) (void)hipHostFree(s->h_info);
@@ -997,6 +1005,171 @@ extern "C" int stb_tindic_get_h(stb_tindic_t *s, double *h_out) {
   if ((s->G && hipMemcpyAsync(h_out, s->d_h, sizeof(double) * s->G, hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
       hipStreamSynchronize(s->st) != hipSuccess)
     rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  stb_device_leave(prev);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// what the state predicts: dish proportions and held-out customers (the kernels are predict.hip's)
+
+extern "C" int stb_tindic_set_heldout(stb_tindic_t *s, const uint64_t *hoff_host, const uint32_t *hcls_host) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_heldout";
+  if (!s) return stb_fail("%s: null object", who);
+  uint64_t Hc = 0;
+  unsigned cmax = 0;
+  if (hoff_host) {
+    if (hoff_host[0] != 0) return stb_fail("%s: hoff[0]=%llu (must be 0)", who, (unsigned long long)hoff_host[0]);
+    for (int i = 0; i < s->I; i++)
+      if (hoff_host[i + 1] < hoff_host[i]) return stb_fail("%s: hoff[%d] < hoff[%d]", who, i + 1, i);
+    Hc = hoff_host[s->I];
+    if (Hc && !hcls_host) return stb_fail("%s: the held-out classes are required", who);
+    for (uint64_t c = 0; c < Hc; c++) {
+      if (s->d_lik && hcls_host[c] >= s->lik_rows)
+        return stb_fail("%s: hcls[%llu]=%u (the likelihood has %u rows)", who, (unsigned long long)c, hcls_host[c], s->lik_rows);
+      cmax = hcls_host[c] > cmax ? hcls_host[c] : cmax;
+    }
+  }
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  uint64_t *d_hoff = nullptr;
+  uint32_t *d_hcls = nullptr;
+  double *d_pacc = nullptr;
+  if (hipStreamSynchronize(s->st) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc && hoff_host) {
+    const size_t Hs = Hc ? Hc : 1;
+    if (hipMalloc((void **)&d_hoff, sizeof(uint64_t) * ((size_t)s->I + 1)) != hipSuccess ||
+        hipMalloc((void **)&d_hcls, sizeof(uint32_t) * Hs) != hipSuccess || hipMalloc((void **)&d_pacc, sizeof(double) * Hs) != hipSuccess)
+      rc = stb_fail("%s: out of device memory for %llu held-out customers", who, (unsigned long long)Hc);
+    if (!rc && (hipMemcpy(d_hoff, hoff_host, sizeof(uint64_t) * ((size_t)s->I + 1), hipMemcpyHostToDevice) != hipSuccess ||
+                (Hc && hipMemcpy(d_hcls, hcls_host, sizeof(uint32_t) * Hc, hipMemcpyHostToDevice) != hipSuccess) ||
+                hipMemset(d_pacc, 0, sizeof(double) * Hs) != hipSuccess))
+      rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  }
+  if (rc) {  // the set the object had stays
+    void *fresh[] = {d_hoff, d_hcls, d_pacc};
+    for (void *p : fresh)
+      if (p) (void)hipFree(p);
+  } else {
+    void *old[] = {s->d_hoff, s->d_hcls, s->d_pacc};
+    for (void *p : old)
+      if (p) (void)hipFree(p);
+    s->d_hoff = d_hoff;
+    s->d_hcls = d_hcls;
+    s->d_pacc = d_pacc;
+    s->Hc = Hc;
+    s->hcls_max = cmax;
+    s->hsamples = 0;
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+// what _predict and _heldout ask of the object and of (a, bpar) before anything is queued
+static int ti_pr_ready(stb_tindic_t *s, double a, const double *bpar, unsigned flags, bool heldout, const char *who) {
+  if (stb_pr_check(a, flags, s->I, who)) return 1;
+  if (!bpar) return stb_fail("%s: bpar is required", who);
+  for (int i = 0; i < s->I; i++)
+    if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
+  if (s->maxK > STB_TD_MAXK)
+    return stb_fail("%s: a restaurant has K=%u dishes; the kernel holds at most STB_TD_MAXK = %d", who, s->maxK, STB_TD_MAXK);
+  if (s->h_bad) return stb_fail("%s: the last stb_tindic_sample_h failed and left h undefined; draw again or set it", who);
+  if (heldout) {
+    if (!s->d_hoff) return stb_fail("%s: no held-out customers are set (stb_tindic_set_heldout)", who);
+    if (s->d_lik && s->lik_bad)
+      return stb_fail("%s: the last stb_tindic_sample_lik failed and left the likelihood undefined; draw again or set it", who);
+    if (s->d_lik && s->Hc && s->hcls_max >= s->lik_rows)
+      return stb_fail("%s: a held-out customer has class %u; the likelihood has %u rows", who, s->hcls_max, s->lik_rows);
+  }
+  return 0;
+}
+
+extern "C" int stb_tindic_predict(stb_tindic_t *s, double a, const double *bpar, double *theta_host, unsigned tstride) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_predict";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!theta_host) return stb_fail("%s: theta_host is required", who);
+  if (ti_pr_ready(s, a, bpar, 0, false, who)) return 1;
+  if (tstride < s->maxK || tstride < 1) return stb_fail("%s: tstride=%u; the largest restaurant has K=%u dishes", who, tstride, s->maxK);
+  const int prev = stb_device_enter(s->dev);
+  const size_t bytes = sizeof(double) * (size_t)s->I * tstride;
+  double *d_theta = nullptr;
+  int rc = ti_stage_bpar(s, bpar, who);
+  if (!rc && stb_pool_malloc((void **)&d_theta, bytes) != hipSuccess) rc = stb_fail("%s: out of device memory for %d x %u values", who, s->I, tstride);
+  if (!rc)
+    rc = stb_pr_predict(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_h, d_theta, tstride, nullptr, nullptr, nullptr, 0, 0,
+                        nullptr, 0, nullptr, s->st, who);
+  if (!rc && hipMemcpyAsync(theta_host, d_theta, bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (d_theta) {
+    if (hipStreamSynchronize(s->st) != hipSuccess && !rc) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    stb_pool_free(d_theta);
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_heldout(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total, double *Hi_host,
+                                  stb_predict_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_heldout";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!total) return stb_fail("%s: total is required", who);
+  if (ti_pr_ready(s, a, bpar, flags, true, who)) return 1;
+  const bool accumulate = (flags & STB_PR_ACCUMULATE) != 0;
+  if (accumulate && s->hsamples == 0xffffffffu) return stb_fail("%s: the sample count is full (stb_tindic_heldout_reset)", who);
+  const int prev = stb_device_enter(s->dev);
+  double *d_p = nullptr, *d_Hi = nullptr;
+  uint64_t *d_skip = nullptr;
+  int rc = ti_stage_bpar(s, bpar, who);
+  if (!rc && ((!accumulate && stb_pool_malloc((void **)&d_p, sizeof(double) * (s->Hc ? s->Hc : 1)) != hipSuccess) ||
+              (Hi_host && stb_pool_malloc((void **)&d_Hi, sizeof(double) * (size_t)s->I) != hipSuccess) ||
+              stb_pool_malloc((void **)&d_skip, sizeof(uint64_t)) != hipSuccess))
+    rc = stb_fail("%s: out of device memory for %llu held-out customers", who, (unsigned long long)s->Hc);
+  if (!rc && hipMemsetAsync(d_skip, 0, sizeof(uint64_t), s->st) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  bool queued = false;
+  if (!rc) {
+    rc = stb_pr_predict(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_h, nullptr, 0, s->d_hoff, s->d_hcls, s->d_lik,
+                        s->lik_rows, s->lik_stride, accumulate ? s->d_pacc : d_p, flags, d_skip, s->st, who);
+    queued = !rc;
+    if (!rc && accumulate) s->hsamples++;
+  }
+  if (!rc)
+    rc = stb_pr_heldout(accumulate ? s->d_pacc : d_p, s->d_hoff, s->I, accumulate ? s->hsamples : 1u, d_Hi, Hi_host, total, info,
+                        d_skip, s->st, who);
+  if (queued && rc) (void)hipStreamSynchronize(s->st);  // (the cache may hand the buffers on at once)
+  void *pooled[] = {d_p, d_Hi, d_skip};
+  for (void *p : pooled)
+    if (p) stb_pool_free(p);
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_heldout_reset(stb_tindic_t *s) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_heldout_reset";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!s->d_hoff) return stb_fail("%s: no held-out customers are set (stb_tindic_set_heldout)", who);
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (hipMemsetAsync(s->d_pacc, 0, sizeof(double) * (s->Hc ? s->Hc : 1), s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc) s->hsamples = 0;
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_heldout_get(stb_tindic_t *s, double *p_out, unsigned *samples) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_heldout_get";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!s->d_hoff) return stb_fail("%s: no held-out customers are set (stb_tindic_set_heldout)", who);
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if ((p_out && s->Hc && hipMemcpyAsync(p_out, s->d_pacc, sizeof(double) * s->Hc, hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
+      hipStreamSynchronize(s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc && samples) *samples = s->hsamples;
   stb_device_leave(prev);
   return rc;
 }
