@@ -31,10 +31,15 @@
  *      iteration's line carries their log likelihood under the state's predictive dish proportions and the running
  *      estimate sum_c log((1/S) sum_s p_c) over the iterations so far (stb_tindic_heldout), and the per-customer
  *      perplexity is printed at the end.
+ *  12. with -B (needs -d) every restaurant has a concentration of its own: after each sweep all of them are redrawn on the
+ *      device in one exact step (stb_tindic_sampleb_groups, Teh's auxiliary variables), every later call reads them where
+ *      they live (STB_BPAR_RESIDENT), and the discount step runs on them: stb_tindic_to_groups(..., STB_BPAR_RESIDENT) +
+ *      stb_groups_samplea.  Each iteration's line ends with min, median and max of b_i from one read-back.  -B with -j is
+ *      refused: the joint step models one shared b.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B]
  */
 #include <math.h>
 #include <stdio.h>
@@ -49,11 +54,16 @@
 
 #define DISHES 50
 
+static int cmp_double(const void *x, const void *y) {
+  const double a = *(const double *)x, b = *(const double *)y;
+  return a < b ? -1 : a > b;
+}
+
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwP")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPB")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -68,6 +78,7 @@ int main(int argc, char **argv) {
     else if (c == 'z') ondev = dishes = 1;
     else if (c == 'w') redraw = 1;
     else if (c == 'P') predict = 1;
+    else if (c == 'B') pergroup = 1;
     else return 2;
   }
   if (redraw && !(explicit_d && dishes)) {
@@ -76,6 +87,10 @@ int main(int argc, char **argv) {
   }
   if (predict && !(explicit_d && dishes)) {
     fprintf(stderr, "pyp_resample: -P needs -d -z\n");
+    return 2;
+  }
+  if (pergroup && (!explicit_d || joint)) {
+    fprintf(stderr, joint ? "pyp_resample: -B with -j is refused: the joint step models one shared b\n" : "pyp_resample: -B needs -d\n");
     return 2;
   }
   srand48(seed);
@@ -148,6 +163,10 @@ int main(int argc, char **argv) {
     int accepted = 0, steps = 0;
     if (!ti || !gs) yaps_quit("device loop: %s\n", stb_last_error());
     for (j = 0; j < J; j++) bvec[j] = b;
+    /* -B: the concentrations live on the device from here on; every call below reads them there */
+    const double *bp = pergroup ? STB_BPAR_RESIDENT : bvec;
+    double *bsort = malloc(sizeof(double) * J);
+    if (pergroup && stb_tindic_set_bpar(ti, bvec)) yaps_quit("stb_tindic_set_bpar: %s\n", stb_last_error());
     unsigned long long stuck = 0;
     if (dishes) { /* two classes by the customer's parity; a class likes the dishes of its parity twice as much */
       scnt_int *cls = malloc(sizeof(*cls) * (size_t)J * ncust);
@@ -173,15 +192,24 @@ int main(int argc, char **argv) {
     for (it = 0; it < cycles; it++) {
       if (dishes) {
         stb_tdish_info_t di;
-        if (stb_tindic_sweep_dishes(ti, a, bvec, (uint64_t)seed + 2, (uint64_t)it, 1, &di)) yaps_quit("stb_tindic_sweep_dishes: %s\n", stb_last_error());
+        if (stb_tindic_sweep_dishes(ti, a, bp, (uint64_t)seed + 2, (uint64_t)it, 1, &di)) yaps_quit("stb_tindic_sweep_dishes: %s\n", stb_last_error());
         stuck += di.stuck + di.skipped;
         /* the uncollapsed step: seeds of their own, so neither shares a stream with a sweep or with the other */
         if (redraw && (stb_tindic_sample_lik(ti, NULL, 0.5, (uint64_t)seed + 3, (uint64_t)it) ||
                        stb_tindic_sample_h(ti, NULL, 1.0, (uint64_t)seed + 4, (uint64_t)it)))
           yaps_quit("stb_tindic_sample_lik / _sample_h: %s\n", stb_last_error());
       }
-      if (stb_tindic_sweep(ti, a, bvec, (uint64_t)seed, (uint64_t)it, 1)) yaps_quit("stb_tindic_sweep: %s\n", stb_last_error());
-      if (it % 3 == 2 && joint) {
+      if (stb_tindic_sweep(ti, a, bp, (uint64_t)seed, (uint64_t)it, 1)) yaps_quit("stb_tindic_sweep: %s\n", stb_last_error());
+      if (pergroup) {
+        stb_bgroups_info_t bi;
+        if (stb_tindic_sampleb_groups(ti, a, 1.1, 20.0, (uint64_t)seed + 1, (uint64_t)it, NULL, &bi))
+          yaps_quit("stb_tindic_sampleb_groups: %s\n", stb_last_error());
+        if (it % 3 == 2) {
+          if (stb_tindic_to_groups(ti, gs, STB_BPAR_RESIDENT)) yaps_quit("stb_tindic_to_groups: %s\n", stb_last_error());
+          a = stb_groups_samplea(gs, a, 0, 1, 0);
+          if (a != a) yaps_quit("stb_groups_samplea: %s\n", stb_last_error());
+        }
+      } else if (it % 3 == 2 && joint) {
         stb_joint_opts_t jo = {0.02, 0.97, 0.05, 500.0, 24, 24, 1.1, 20.0, (uint64_t)seed + 1, (uint64_t)it, 0};
         stb_joint_info_t ji;
         if (stb_tindic_samplejoint(ti, gs, &jo, a, b, &a, &b, &ji)) yaps_quit("stb_tindic_samplejoint: %s\n", stb_last_error());
@@ -209,7 +237,7 @@ int main(int argc, char **argv) {
       if (showlj) {
         double lj;
         stb_logjoint_info_t li;
-        if (stb_tindic_logjoint(ti, a, bvec, STB_LJ_INDICATORS, &lj, NULL, &li)) yaps_quit("stb_tindic_logjoint: %s\n", stb_last_error());
+        if (stb_tindic_logjoint(ti, a, bp, STB_LJ_INDICATORS, &lj, NULL, &li)) yaps_quit("stb_tindic_logjoint: %s\n", stb_last_error());
         if (redraw) {
           double dt;
           if (stb_tindic_loglik(ti, &dt, NULL)) yaps_quit("stb_tindic_loglik: %s\n", stb_last_error());
@@ -221,10 +249,22 @@ int main(int argc, char **argv) {
       }
       if (predict) {
         double ho;
-        if (stb_tindic_heldout(ti, a, bvec, 0, &ho, NULL, NULL) || stb_tindic_heldout(ti, a, bvec, STB_PR_ACCUMULATE, &ho_avg, NULL, NULL))
+        if (stb_tindic_heldout(ti, a, bp, 0, &ho, NULL, NULL) || stb_tindic_heldout(ti, a, bp, STB_PR_ACCUMULATE, &ho_avg, NULL, NULL))
           yaps_quit("stb_tindic_heldout: %s\n", stb_last_error());
         if (showlj) printf(" heldout %.6f avg %.6f\n", ho, ho_avg);
         else printf("iteration %d: heldout %.6f avg %.6f\n", it, ho, ho_avg);
+      }
+      if (pergroup) { /* the iteration's one read-back: the J concentrations */
+        if (stb_tindic_get_bpar(ti, bvec)) yaps_quit("stb_tindic_get_bpar: %s\n", stb_last_error());
+        memcpy(bsort, bvec, sizeof(double) * J);
+        qsort(bsort, J, sizeof(double), cmp_double);
+        b = bsort[J / 2];
+        printf("iteration %d: a=%.4f b_i min %.6g median %.6g max %.6g\n", it, a, bsort[0], b, bsort[J - 1]);
+        if (it % 3 == 2 && it >= cycles / 2) {
+          asum += a;
+          bsum += b;
+          kept++;
+        }
       }
     }
     if (stb_tindic_get(ti, tf, T)) yaps_quit("stb_tindic_get: %s\n", stb_last_error());
@@ -252,6 +292,7 @@ int main(int argc, char **argv) {
     free(tf);
     free(hf);
     free(cust);
+    free(bsort);
   }
   for (it = 0; it < cycles && !ondev; it++) {
     for (j = 0; j < J; j++) {

@@ -257,6 +257,69 @@ double stb_sampleb_device(double b_in, int I, double shape, double scale, const 
                           double a, void *rng, int loops, int verbose, uint64_t seed, uint64_t sweep, void *stream);
 double stb_sampleb_last_Q(void);          /* the Q of this thread's last device b step, for tests */
 
+/* ---- one concentration per group of restaurants, drawn on the device (hyperb.hip; an additive algorithm, Teh's
+ * auxiliary-variable scheme: DESIGN.md section 6) ----
+ * The restaurants 0 .. I-1 are partitioned into G contiguous ranges d_goff[G+1] (uint64, 0 = goff[0] <= ... <= goff[G]
+ * = I, empty ranges allowed; NULL: every restaurant its own group, G = I).  Group g shares one concentration b > 0 with
+ * the prior Gamma(shape, scale); d_bpar[I] holds it once per restaurant (every layer's bpar).  With the discount a in
+ * [0, 1), T_i tables and N_i customers (d_N[I] uint32, or d_coff[I+1] uint64 prefix sums; exactly one of the two):
+ *     q_i | b ~ Beta(b, N_i) for N_i > 0, L_i = -log q_i;   y_ik | b ~ Bernoulli(b / (b + k a)), k = 1 .. T_i - 1,
+ *     Y_i = [T_i >= 1] + sum_k y_ik;   b_g | q, y ~ Gamma(shape + sum_{i in g} Y_i, rate = 1/scale + sum_{i in g} L_i).
+ * These are the exact conditionals of an augmented joint whose marginal is p(b | .) ~ b^(shape-1) e^(-b/scale) prod_i
+ * (b|a)_{T_i} Gamma(b) / Gamma(b + N_i): the step leaves it invariant, with no ARMS, no lgamma and no host in the loop.
+ * a = 0: every y is 1 and the step is the Gamma draw of lib/sampleb.c:101-118.  A restaurant without customers adds
+ * nothing; a group without customers draws from the prior.
+ * d_bpar is read (b_i, from the restaurant's own entry) and, on success, overwritten with b_g for i in g; d_bgrp (G, or
+ * NULL) receives b_g; d_L (I doubles) receives L_i (0 where N_i = 0), d_Y (I uint32, or NULL) Y_i.
+ * Streams: key = mix(seed + (sweep+1) gamma); restaurant i owns key_i = mix(key + (i+1) gamma).  L_i is stb_sample_logq's
+ * draw on key_i with b_i: with every b_i equal, d_L is that call's, to the bit.  The y take the substream mix(key_i ^
+ * 0x59B1D5A7C3E9F24D): y_ik = [u_k (b + k a) < b] in doubles as written (no contraction), u_k its element k (the open
+ * interval), so they do not depend on how many uniforms the Beta draw took.  Group g's variate is the log-Gamma variate
+ * of stb_sample_logq with shape + sum Y on the substream mix(key' + (g+1) gamma), key' = mix(key ^ 0x6A09E667F3BCC909),
+ * and b_g = exp(log G - log rate).
+ * Associations: sum Y is a sum of integers.  sum L is taken relative to the group's first restaurant: blocks of 256
+ * restaurants, inside a block stb_sample_logq's tree (four quarters per lane, then the shuffle tree of a 64-lane wave),
+ * the block sums lane-strided in double-double, merged by the same tree, 1/scale added last -- one group of equal b has
+ * stb_sample_logq's Q as its rate.  No bit depends on STB_HYPERB_WAVES (1, 2, 4 or 8 waves a workgroup), on
+ * STB_HYPERB_FORM (lane | wave: how a restaurant's y are spread over lanes; by default a wave takes the restaurants with
+ * more than 257 tables) or on whether ranges of one restaurant each or NULL are passed.
+ * Three kernels queued on `stream`, one wait; the counts and, for G = 1, b come back in pinned words (info).
+ * Refusals return non-zero with stb_last_error() set and nothing written to d_bpar or d_bgrp: a outside [0, 1), shape
+ * <= 0, scale <= 0, both or neither of d_N and d_coff, and a raised error word (info->error_word: 1 a rejection loop
+ * ran out, 2 a b_i is not a positive finite double, 4 a b_i differs from its group's first restaurant's, 8 bad ranges;
+ * info->bad_restaurants counts the restaurants of 1, 2 and 4).  A group whose draw is not a positive finite double
+ * keeps its b and is counted in info->kept_groups; the call succeeds. */
+struct stb_tcounts;
+struct stb_tindic;
+typedef struct stb_bgroups_info {
+  uint64_t bad_restaurants, kept_groups;
+  unsigned error_word, reserved;
+  double b;                 /* G = 1: the new b; otherwise NaN */
+} stb_bgroups_info_t;
+int stb_sample_bgroups(double a, double shape, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff,
+                       const uint32_t *d_T, int G, const uint64_t *d_goff /* NULL: every restaurant its own group, G = I */,
+                       double *d_bpar /* in: current, out: new */, double *d_bgrp /* G, or NULL */, double *d_L,
+                       uint32_t *d_Y /* or NULL */, uint64_t seed, uint64_t sweep, void *stream, stb_bgroups_info_t *info);
+/* On the objects (their declarations follow below): stb_*_set_bpar uploads I concentrations, stb_*_get_bpar reads back what
+ * the object holds (after the queued work), stb_*_set_bgroups sets the ranges (goff_host[G+1], kept on the device with
+ * the object; NULL: every restaurant its own group -- the state of a new object).  stb_*_sampleb_groups runs the step
+ * behind the object's queued sweeps on its own T, customers and concentrations; bgrp_host (G, or NULL) receives b_g.
+ * STB_BPAR_RESIDENT in place of a host bpar[I] means "what the object holds": no upload, and in place of the host-side
+ * range check the object's lower bound of what it holds (the smallest value of the last upload; positive after a step,
+ * which only ever writes positive finite values) must exceed -a; it fails while the object holds none.  Every object
+ * entry point that takes bpar accepts it; stb_*_to_groups with it copies device to device into the set. */
+#define STB_BPAR_RESIDENT ((const double *)(uintptr_t)8)
+int stb_tcounts_set_bpar(struct stb_tcounts *s, const double *bpar /* host [I] */);
+int stb_tcounts_get_bpar(struct stb_tcounts *s, double *bpar_out /* host [I] */);
+int stb_tcounts_set_bgroups(struct stb_tcounts *s, int G, const uint64_t *goff_host /* G+1, or NULL: per restaurant */);
+int stb_tcounts_sampleb_groups(struct stb_tcounts *s, double a, double shape, double scale, uint64_t seed, uint64_t sweep,
+                               double *bgrp_host /* G, or NULL */, stb_bgroups_info_t *info);
+int stb_tindic_set_bpar(struct stb_tindic *s, const double *bpar /* host [I] */);
+int stb_tindic_get_bpar(struct stb_tindic *s, double *bpar_out /* host [I] */);
+int stb_tindic_set_bgroups(struct stb_tindic *s, int G, const uint64_t *goff_host /* G+1, or NULL: per restaurant */);
+int stb_tindic_sampleb_groups(struct stb_tindic *s, double a, double shape, double scale, uint64_t seed, uint64_t sweep,
+                              double *bgrp_host /* G, or NULL */, stb_bgroups_info_t *info);
+
 /* ---- the joint step for discount and concentration from device-resident counts (hyperj.hip; an additive algorithm,
  * not the reference's: DESIGN.md section 6, deviation 14) ----
  * All restaurants share one discount a and one concentration b (test/demo.c's model).  With beta = log b the target is

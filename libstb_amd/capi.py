@@ -86,6 +86,12 @@ class ReduceGeom(C.Structure):
                 ("blocks", C.c_uint), ("waves", C.c_uint), ("need", C.c_uint64), ("cap0", C.c_uint64)]
 
 
+class BGroupsInfo(C.Structure):
+    """stb_bgroups_info_t (include/stb_hip.h)"""
+    _fields_ = [("bad_restaurants", C.c_uint64), ("kept_groups", C.c_uint64), ("error_word", C.c_uint),
+                ("reserved", C.c_uint), ("b", C.c_double)]
+
+
 class JointInfo(C.Structure):
     """stb_joint_info_t (include/stb_hip.h)"""
     _fields_ = [("stages", C.c_int), ("accepted", C.c_int), ("evals", C.c_int), ("stage_pick", C.c_int),
@@ -262,6 +268,15 @@ def lib() -> C.CDLL:
     sig("stb_tcounts_sampleb", d, [vp, d, d, d, d, vp, i, i, u64, u64])
     sig("stb_tindic_sampleb", d, [vp, d, d, d, d, vp, i, i, u64, u64])
     sig("stb_sampleb_last_Q", d, [])
+    # ---- one concentration per group of restaurants, drawn on the device
+    bgi = C.POINTER(BGroupsInfo)
+    sig("stb_sample_bgroups", i, [d, d, d, i, vp, vp, vp, i, vp, vp, vp, vp, vp, u64, u64, vp, bgi])
+    sig("stb_hb_bgroups", i, [d, d, d, i, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, u64, u64, vp, bgi, C.c_char_p])
+    for obj in ("tcounts", "tindic"):
+        sig("stb_%s_set_bpar" % obj, i, [vp, c_double_p])
+        sig("stb_%s_get_bpar" % obj, i, [vp, c_double_p])
+        sig("stb_%s_set_bgroups" % obj, i, [vp, i, C.POINTER(u64)])
+        sig("stb_%s_sampleb_groups" % obj, i, [vp, d, d, d, u64, u64, c_double_p, bgi])
     sig("stb_groups_samplea", d, [vp, d, vp, i, i])
     sig("stb_groups_ssum", i, [vp, c_double_p, i, c_double_p])
     sig("stb_groups_ssum_device", i, [vp, c_double_p, i, vp, vp])
@@ -346,7 +361,24 @@ def check(rc: int) -> None:
         raise StbError(last_error())
 
 
+class _Resident:
+    def __repr__(self):
+        return "BPAR_RESIDENT"
+
+
+BPAR_RESIDENT = _Resident()  # STB_BPAR_RESIDENT: in place of a host bpar, "the concentrations the object holds"
+
+
+def _bpar(bpar, I: int):
+    """the I concentrations of an object call as a host vector (a scalar is broadcast), or the sentinel as it is"""
+    if bpar is BPAR_RESIDENT:
+        return bpar
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (I,)))
+
+
 def dp(a: np.ndarray):
+    if a is BPAR_RESIDENT:
+        return C.cast(8, c_double_p)
     assert a.dtype == np.float64 and a.flags.c_contiguous
     return a.ctypes.data_as(c_double_p)
 
@@ -618,9 +650,50 @@ class DeviceGroups:
 TC_REF_WINDOW = 1  # stb_tcounts_sweep_window / stb_sample_tcounts_window flag: the reference's chain
 
 
-class TableCounts:
+class _BGroupsMixin:
+    """the per-group concentration step on an object (stb_*_set_bpar, _get_bpar, _set_bgroups, _sampleb_groups)"""
+
+    def _hb(self, name):
+        return getattr(self.L, "stb_%s_%s" % (self._hb_prefix, name))
+
+    def set_bpar(self, bpar):
+        check(self._hb("set_bpar")(self.h, dp(_bpar(bpar, self.I))))
+
+    def get_bpar(self):
+        out = np.zeros(self.I, dtype=np.float64)
+        check(self._hb("get_bpar")(self.h, dp(out)))
+        return out
+
+    def set_bgroups(self, goff=None):
+        """contiguous ranges goff[G+1] of restaurants that share a concentration (None: every restaurant its own)"""
+        if goff is None:
+            check(self._hb("set_bgroups")(self.h, 0, None))
+            self.nbgroups = self.I
+            return
+        goff = np.ascontiguousarray(goff, dtype=np.uint64)
+        check(self._hb("set_bgroups")(self.h, int(goff.shape[0]) - 1, goff.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self.nbgroups = int(goff.shape[0]) - 1
+
+    def sampleb_groups(self, a, shape, scale, seed: int, sweep: int, want_bgrp: bool = True):
+        """one exact step for every group's concentration on the current counts, behind the queued sweeps: (b_g [G] or
+        None, BGroupsInfo).  The new concentrations stay on the device: pass BPAR_RESIDENT where a call takes bpar"""
+        G = getattr(self, "nbgroups", self.I)
+        bgrp = np.zeros(G, dtype=np.float64) if want_bgrp else None
+        info = BGroupsInfo()
+        rc = self._hb("sampleb_groups")(self.h, float(a), float(shape), float(scale), seed, sweep,
+                                        None if bgrp is None else dp(bgrp), C.byref(info))
+        if rc:
+            err = StbError(last_error())
+            err.info = info
+            raise err
+        return bgrp, info
+
+
+class TableCounts(_BGroupsMixin):
     """Table counts t of (n, t) pairs resampled on the device by collapsed Gibbs sweeps (stb_tcounts_*).  K, n, t
     (and h, NULL: all 1) in the CSR layout of synth.Groups; M = 0 draws from the full conditional (the largest n)."""
+
+    _hb_prefix = "tcounts"
 
     def __init__(self, K, n, t, h=None, M: int = 0):
         self.L = lib()
@@ -639,13 +712,13 @@ class TableCounts:
 
     def sweep(self, a, bpar, seed: int, sweep: int, nsweeps: int = 1):
         """sweeps sweep .. sweep+nsweeps-1, queued (bpar: the I concentrations)"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         check(self.L.stb_tcounts_sweep(self.h, float(a), dp(bpar), seed, sweep, nsweeps))
 
     def sweep_window(self, a, bpar, window: int, seed: int, sweep: int, nsweeps: int = 1, ref: bool = False):
         """windowed sweeps sweep .. sweep+nsweeps-1, queued: t moves at most `window` a visit, by an exact
         Metropolis-Hastings step (ref: the reference's chain, every proposal accepted)"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         check(self.L.stb_tcounts_sweep_window(self.h, float(a), dp(bpar), int(window), TC_REF_WINDOW if ref else 0, seed,
                                               sweep, nsweeps))
 
@@ -658,7 +731,7 @@ class TableCounts:
 
     def to_groups(self, groups, bpar=None):
         """pairs and T to a group set (an stb_groups_create handle) of the same shape, device to device"""
-        bp = None if bpar is None else dp(np.ascontiguousarray(bpar, dtype=np.float64))
+        bp = None if bpar is None else dp(_bpar(bpar, self.I))
         check(self.L.stb_tcounts_to_groups(self.h, groups, bp))
 
     def sampleb(self, b, shape, scale, a, seed: int, sweep: int, loops: int = 1, verbose: int = 0):
@@ -680,7 +753,7 @@ class TableCounts:
     def logjoint(self, a, bpar, indicators: bool = False, want_Li: bool = True):
         """(total, L_i[I] or None, LogJointInfo): the log joint probability of the current state, behind the queued sweeps
         (stb_tcounts_logjoint); indicators: the table-indicator representation"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         Li = np.zeros(self.I, dtype=np.float64) if want_Li else None
         tot, info = C.c_double(0.0), LogJointInfo()
         check(self.L.stb_tcounts_logjoint(self.h, float(a), dp(bpar), LJ_INDICATORS if indicators else 0, C.byref(tot),
@@ -690,7 +763,7 @@ class TableCounts:
     def partition(self, a, hist, bpar, seed: int, sweep: int):
         """stage 1 of the S-free discount step on the current pairs, queued: the table-size histogram into `hist` (a
         Histogram with I restaurants and S > the largest n), with T and bpar (stb_tcounts_partition)"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         check(self.L.stb_tcounts_partition(self.h, float(a), hist.h, dp(bpar), seed, sweep))
 
     def free(self):
@@ -798,6 +871,35 @@ def sample_logq(b, scale, N, seed: int, sweep: int, want_L: bool = True, stream=
     check(lib().stb_sample_logq(float(b), float(scale), I, N.data_ptr() if I else None, Lt.data_ptr() if want_L and I else None,
                                 C.byref(Q), seed, sweep, stream_ptr(stream)))
     return Q.value, Lt
+
+
+def sample_bgroups(a, shape, scale, T, bpar, seed: int, sweep: int, N=None, coff=None, goff=None, want_Y: bool = True,
+                   want_rate: bool = False, stream=None):
+    """stb_sample_bgroups on device tensors: T, N (int32 holding uint32 counts; or coff, int64 [I+1] prefix sums of the
+    customers), bpar (float64 [I], overwritten with the new concentrations), goff (int64 [G+1] ranges; None: every
+    restaurant its own group).  Returns (bgrp [G], L [I], Y [I] int32 or None, rate [G] or None, BGroupsInfo); want_rate
+    goes through the private entry point that also writes every group's 1/scale + sum L"""
+    torch = _torch()
+    I = int(T.shape[0])
+    G = I if goff is None else int(goff.shape[0]) - 1
+    dev = bpar.device
+    bgrp = torch.empty(G, dtype=torch.float64, device=dev)
+    Lt = torch.empty(I, dtype=torch.float64, device=dev)
+    Yt = torch.empty(I, dtype=torch.int32, device=dev) if want_Y else None
+    rate = torch.empty(G, dtype=torch.float64, device=dev) if want_rate else None
+    info = BGroupsInfo()
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    head = (float(a), float(shape), float(scale), I, ptr(N), ptr(coff) if coff is not None else None, ptr(T), G,
+            None if goff is None else goff.data_ptr(), ptr(bpar), ptr(bgrp), ptr(Lt), ptr(Yt))
+    if want_rate:
+        rc = lib().stb_hb_bgroups(*head, ptr(rate), seed, sweep, stream_ptr(stream), C.byref(info), b"stb_sample_bgroups")
+    else:
+        rc = lib().stb_sample_bgroups(*head, seed, sweep, stream_ptr(stream), C.byref(info))
+    if rc:
+        err = StbError(last_error())
+        err.info = info
+        raise err
+    return bgrp, Lt, Yt, rate, info
 
 
 def _prior(v, n: int):
@@ -1006,10 +1108,12 @@ TD_MAXK = 1024  # STB_TD_MAXK: dishes a restaurant may have under stb_tindic_swe
 TI_REF_ODDS = 1  # stb_tindic_create / stb_sample_tindic flag: the reference's factor t / (n-t+1)
 
 
-class TableIndicators:
+class TableIndicators(_BGroupsMixin):
     """Table counts t of (n, t) pairs resampled on the device customer by customer with table indicators
     (stb_tindic_*).  K, n, t, h as for TableCounts; cust: the customers of every restaurant as local pair indices, back to
     back (None: pair order); M = 0 truncates at the largest n; flags TI_REF_ODDS."""
+
+    _hb_prefix = "tindic"
 
     def __init__(self, K, n, t, h=None, cust=None, M: int = 0, flags: int = 0):
         self.L = lib()
@@ -1041,7 +1145,7 @@ class TableIndicators:
 
     def sweep(self, a, bpar, seed: int, sweep: int, nsweeps: int = 1):
         """sweeps sweep .. sweep+nsweeps-1, queued (bpar: the I concentrations)"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         check(self.L.stb_tindic_sweep(self.h, float(a), dp(bpar), seed, sweep, nsweeps))
 
     def get(self):
@@ -1053,7 +1157,7 @@ class TableIndicators:
 
     def to_groups(self, groups, bpar=None):
         """pairs and T to a group set (an stb_groups_create handle) of the same shape, device to device"""
-        bp = None if bpar is None else dp(np.ascontiguousarray(bpar, dtype=np.float64))
+        bp = None if bpar is None else dp(_bpar(bpar, self.I))
         check(self.L.stb_tindic_to_groups(self.h, groups, bp))
 
     def sampleb(self, b, shape, scale, a, seed: int, sweep: int, loops: int = 1, verbose: int = 0):
@@ -1075,7 +1179,7 @@ class TableIndicators:
     def logjoint(self, a, bpar, indicators: bool = False, want_Li: bool = True):
         """(total, L_i[I] or None, LogJointInfo): the log joint probability of the current state, behind the queued sweeps
         (stb_tindic_logjoint); indicators: the table-indicator representation"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         Li = np.zeros(self.I, dtype=np.float64) if want_Li else None
         tot, info = C.c_double(0.0), LogJointInfo()
         check(self.L.stb_tindic_logjoint(self.h, float(a), dp(bpar), LJ_INDICATORS if indicators else 0, C.byref(tot),
@@ -1117,7 +1221,7 @@ class TableIndicators:
 
     def sweep_dishes(self, a, bpar, seed: int, sweep: int, nsweeps: int = 1):
         """dish sweeps sweep .. sweep+nsweeps-1; returns TDishInfo (skipped, stuck) of the call, after a wait"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         info = TDishInfo()
         check(self.L.stb_tindic_sweep_dishes(self.h, float(a), dp(bpar), seed, sweep, nsweeps, C.byref(info)))
         return info
@@ -1184,7 +1288,7 @@ class TableIndicators:
     def predict(self, a, bpar, tstride: int = 0):
         """theta (I, tstride) float64: every restaurant's predictive dish proportions in the current state (columns past
         K_i are 0); tstride 0: the largest K"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         tstride = int(tstride) or max(self.maxK, 1)
         theta = np.zeros((self.I, tstride), dtype=np.float64)
         check(self.L.stb_tindic_predict(self.h, float(a), dp(bpar), dp(theta), tstride))
@@ -1193,7 +1297,7 @@ class TableIndicators:
     def heldout(self, a, bpar, accumulate: bool = False, want_Hi: bool = True, flags=None):
         """(total, H_i[I] or None, PredictInfo): the held-out customers' log likelihood -- the current state's sum_c log p_c,
         or with accumulate the running estimate sum_c log(acc_c / S) after this state's p_c went into the accumulator"""
-        bpar = np.ascontiguousarray(np.broadcast_to(np.asarray(bpar, dtype=np.float64), (self.I,)))
+        bpar = _bpar(bpar, self.I)
         Hi = np.zeros(self.I, dtype=np.float64) if want_Hi else None
         tot, info = C.c_double(0.0), PredictInfo()
         fl = (PR_ACCUMULATE if accumulate else 0) if flags is None else int(flags)

@@ -53,6 +53,19 @@ __device__ __forceinline__ double hq_log_gamma(double alpha, uint64_t key, uint6
   const double u = hq_unit(key, ++k);
   return lg + log(u) / alpha;
 }
+
+// L = -log q, q ~ Beta(b, Ni), for restaurant i of the sweep `key` (hyperq.hip's header: log G_b first, then log G_N, from
+// the restaurant's substream key_i = mix(key + (i+1) gamma)); shared by hyperq.hip and hyperb.hip, so the two draw the
+// same bits
+__device__ __forceinline__ double hq_draw_L(double b, double Ni, uint64_t key, uint64_t i, bool &bad) {
+#pragma clang fp contract(off)
+  const uint64_t ki = stb_mix64(key + (i + 1) * STB_GAMMA);
+  uint64_t k = 0;
+  const double lgb = hq_log_gamma(b, ki, k, bad);
+  const double lgn = hq_log_gamma(Ni, ki, k, bad);
+  const double D = lgn - lgb;
+  return D > 0.0 ? D + log1p(exp(-D)) : log1p(exp(D));
+}
 #endif  // __HIPCC__
 
 #endif

@@ -36,21 +36,11 @@
 #include "stb_common.h"
 #include "tcounts.h"
 #include "hyperq.h"
-#include "gamma_dev.h"  // hq_unit, hq_log_gamma, HQ_CAP
+#include "gamma_dev.h"  // hq_unit, hq_log_gamma, hq_draw_L, HQ_CAP
 #include "ticket_geom.h"
 
 #define HQ_CHUNK STB_TG_BLOCK  // (one constant for the kernel, the launch and stb_reduce_geometry)
 #define HQ_MAXTHREADS 512
-
-__device__ __forceinline__ double hq_draw_L(double b, double Ni, uint64_t key, uint64_t i, bool &bad) {
-#pragma clang fp contract(off)
-  const uint64_t ki = stb_mix64(key + (i + 1) * STB_GAMMA);
-  uint64_t k = 0;
-  const double lgb = hq_log_gamma(b, ki, k, bad);
-  const double lgn = hq_log_gamma(Ni, ki, k, bad);
-  const double D = lgn - lgb;
-  return D > 0.0 ? D + log1p(exp(-D)) : log1p(exp(D));
-}
 
 // ctl[0] ticket, ctl[1] error word (both zeroed on the stream ahead of the launch); host_out[0] = Q, host_out[1] = error
 __global__ __launch_bounds__(HQ_MAXTHREADS) void k_logq(double b, double inv_scale, uint64_t I, const uint32_t *Nv,

@@ -19,6 +19,7 @@
 #include "../../include/stb_hip.h"
 #include "sampler_trace.h"
 #include "hyperq.h"
+#include "hyperb.h"
 #include "hyperj.h"
 #include "logjoint.h"
 #include "predict.h"
@@ -68,6 +69,7 @@ void stb_sampleb_cache_clear(void) {
   if (kept_bdev) stb_bterms_free(kept_bdev);
   kept_bdev = NULL;
   stb_hq_release();
+  stb_hb_release();
   stb_hj_release();
   stb_lj_release();
   stb_pr_release();

@@ -29,6 +29,7 @@
 #include "groups.h"
 #include "tcounts.h"
 #include "hyperq.h"
+#include "hyperb.h"
 #include "hyperj.h"
 #include "logjoint.h"
 
@@ -233,7 +234,8 @@ struct stb_tcounts {
   double *h_bpar[2];    // pinned staging of bpar, used in turn: a sweep does not wait for the one before it
   hipEvent_t ev_bpar[2];  // the copy out of h_bpar[k] is through
   int slot;
-  std::vector<double> last_bpar;  // what d_bpar holds (empty: nothing yet)
+  std::vector<double> last_bpar;  // what d_bpar holds (empty: nothing yet, or a device step wrote it)
+  stb_hb_obj hb;        // the per-group concentration step (hyperb.hip): ranges, L, Y, and whether d_bpar holds anything
   double *d_table, *d_S1;
   uint64_t tstride;
   void *d_ws;
@@ -243,6 +245,7 @@ struct stb_tcounts {
 };
 
 static void tc_release(stb_tcounts_t *s) {
+  stb_hb_obj_release(&s->hb);
   void *dev[] = {s->d_koff, s->d_n, s->d_T, s->d_N, s->d_t, s->d_h, s->d_bpar, s->d_table, s->d_S1, s->d_ws};
   for (void *p : dev)
     if (p) (void)hipFree(p);
@@ -400,9 +403,31 @@ static int tc_check_sweep(stb_tcounts_t *s, double a, const double *bpar, int ns
   if (!(a >= 0.0 && a < 1.0)) return stb_fail("%s: discount a=%g outside [0, 1)", who, a);
   if (!bpar) return stb_fail("%s: bpar is required", who);
   if (nsweeps < 0) return stb_fail("%s: nsweeps=%d", who, nsweeps);
+  if (bpar == STB_BPAR_RESIDENT) return stb_hb_obj_resident(&s->hb, a, who);  // (what the object holds, by its lower bound)
   for (int i = 0; i < s->I; i++)
     if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
   return 0;
+}
+
+// new concentrations through the staging buffer used two calls ago (its copy is long through); unchanged ones stay
+static int tc_stage_bpar(stb_tcounts_t *s, const double *bpar, const char *who) {
+  int rc = 0;
+  if (bpar == STB_BPAR_RESIDENT) return rc;  // (tc_check_sweep saw that the object holds some)
+  const bool same_b = s->last_bpar.size() == (size_t)s->I && memcmp(s->last_bpar.data(), bpar, sizeof(double) * s->I) == 0;
+  if (!same_b) {
+    const int k = s->slot ^= 1;
+    s->last_bpar.clear();
+    if (hipEventSynchronize(s->ev_bpar[k]) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    if (!rc) {
+      memcpy(s->h_bpar[k], bpar, sizeof(double) * s->I);
+      if (hipMemcpyAsync(s->d_bpar, s->h_bpar[k], sizeof(double) * s->I, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+          hipEventRecord(s->ev_bpar[k], s->st) != hipSuccess)
+        rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    }
+    if (!rc) s->last_bpar.assign(bpar, bpar + s->I);
+    if (!rc) stb_hb_obj_uploaded(&s->hb, bpar, s->I);
+  }
+  return rc;
 }
 
 // what every sweep of the object needs queued before its kernel (on the object's device): the table for `a` and the
@@ -415,20 +440,57 @@ static int tc_stage(stb_tcounts_t *s, double a, const double *bpar, const char *
     if (!rc) rc = stb_fill_status();
     if (!rc) s->a_filled = a;
   }
-  // new concentrations through the staging buffer used two calls ago (its copy is long through); unchanged ones stay
-  const bool same_b = s->last_bpar.size() == (size_t)s->I && memcmp(s->last_bpar.data(), bpar, sizeof(double) * s->I) == 0;
-  if (!rc && !same_b) {
-    const int k = s->slot ^= 1;
-    s->last_bpar.clear();
-    if (hipEventSynchronize(s->ev_bpar[k]) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
-    if (!rc) {
-      memcpy(s->h_bpar[k], bpar, sizeof(double) * s->I);
-      if (hipMemcpyAsync(s->d_bpar, s->h_bpar[k], sizeof(double) * s->I, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-          hipEventRecord(s->ev_bpar[k], s->st) != hipSuccess)
-        rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
-    }
-    if (!rc) s->last_bpar.assign(bpar, bpar + s->I);
-  }
+  if (!rc) rc = tc_stage_bpar(s, bpar, who);
+  return rc;
+}
+
+extern "C" int stb_tcounts_set_bpar(stb_tcounts_t *s, const double *bpar) {
+  STB_ENTRY;
+  const char *who = "stb_tcounts_set_bpar";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!bpar || bpar == STB_BPAR_RESIDENT) return stb_fail("%s: bpar (host, I values) is required", who);
+  for (int i = 0; i < s->I; i++)
+    if (!std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be finite)", who, i, bpar[i]);
+  const int prev = stb_device_enter(s->dev);
+  const int rc = tc_stage_bpar(s, bpar, who);
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tcounts_get_bpar(stb_tcounts_t *s, double *bpar_out) {
+  STB_ENTRY;
+  const char *who = "stb_tcounts_get_bpar";
+  if (!s || !bpar_out) return stb_fail("%s: null %s", who, s ? "output" : "object");
+  if (!s->hb.resident) return stb_fail("%s: the object holds no concentrations yet", who);
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (hipMemcpyAsync(bpar_out, s->d_bpar, sizeof(double) * s->I, hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+      hipStreamSynchronize(s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tcounts_set_bgroups(stb_tcounts_t *s, int G, const uint64_t *goff_host) {
+  STB_ENTRY;
+  if (!s) return stb_fail("stb_tcounts_set_bgroups: null object");
+  const int prev = stb_device_enter(s->dev);
+  const int rc = stb_hb_obj_set_groups(&s->hb, s->I, G, goff_host, s->st, "stb_tcounts_set_bgroups");
+  stb_device_leave(prev);
+  return rc;
+}
+
+// the per-group concentration step (hyperb.hip) on the object's T, N and concentrations, queued behind its sweeps.  The
+// step writes d_bpar: the host copy that spares an upload no longer describes it
+extern "C" int stb_tcounts_sampleb_groups(stb_tcounts_t *s, double a, double shape, double scale, uint64_t seed, uint64_t sweep,
+                                          double *bgrp_host, stb_bgroups_info_t *info) {
+  STB_ENTRY;
+  if (!s) return stb_fail("stb_tcounts_sampleb_groups: null object");
+  const int prev = stb_device_enter(s->dev);
+  const int rc = stb_hb_obj_step(&s->hb, a, shape, scale, s->I, s->d_N, nullptr, s->d_T, s->d_bpar, seed, sweep, s->st, bgrp_host,
+                                 info, "stb_tcounts_sampleb_groups");
+  if (s->hb.resident) s->last_bpar.clear();
+  stb_device_leave(prev);
   return rc;
 }
 
@@ -486,6 +548,8 @@ extern "C" int stb_tcounts_to_groups(stb_tcounts_t *s, stb_groups_t *g, const do
   if (g->dev != s->dev) return stb_fail("stb_tcounts_to_groups: the group set is on device %d, the counts on %d", g->dev, s->dev);
   if (g->pending == 1) return stb_fail("stb_tcounts_to_groups: an evaluation queued with stb_groups_aterms_async has not been waited for");
   if (g->putting) return stb_fail("stb_tcounts_to_groups: the group set is between stb_groups_pairs_begin and _commit");
+  if (bpar == STB_BPAR_RESIDENT && !s->hb.resident)
+    return stb_fail("stb_tcounts_to_groups: STB_BPAR_RESIDENT, but the object holds no concentrations yet");
   const int prev = stb_device_enter(s->dev);
   int rc = 0;
   // the bounds the new pairs can need, known without looking at them: n up to max n, t up to min(max n, M)
@@ -505,7 +569,11 @@ extern "C" int stb_tcounts_to_groups(stb_tcounts_t *s, stb_groups_t *g, const do
                         hipMemcpyAsync(g->d_t, s->d_t, sizeof(uint16_t) * s->G, hipMemcpyDeviceToDevice, g->st) != hipSuccess)) ||
               hipMemcpyAsync(g->d_T, s->d_T, sizeof(uint32_t) * s->I, hipMemcpyDeviceToDevice, g->st) != hipSuccess))
     rc = stb_fail("stb_tcounts_to_groups: %s", hipGetErrorString(hipGetLastError()));
-  if (!rc && bpar) {
+  if (!rc && bpar == STB_BPAR_RESIDENT) {  // (g->st waits for the object's stream above)
+    for (int i = 0; i < g->I; i++) g->h_bpar[i] = NAN;  // (the host's copy no longer says what the set holds)
+    if (hipMemcpyAsync(g->d_bpar, s->d_bpar, sizeof(double) * g->I, hipMemcpyDeviceToDevice, g->st) != hipSuccess)
+      rc = stb_fail("stb_tcounts_to_groups: %s", hipGetErrorString(hipGetLastError()));
+  } else if (!rc && bpar) {
     memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);  // (g->st was idle above: its staging area is free)
     if (hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess)
       rc = stb_fail("stb_tcounts_to_groups: %s", hipGetErrorString(hipGetLastError()));

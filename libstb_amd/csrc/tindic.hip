@@ -24,6 +24,7 @@
 #include "stb_common.h"
 #include "groups.h"
 #include "hyperq.h"
+#include "hyperb.h"
 #include "hyperj.h"
 #include "logjoint.h"
 #include "tindic.h"
@@ -255,7 +256,8 @@ struct stb_tindic {
   double *h_bpar[2];    // pinned staging of bpar, used in turn: a sweep does not wait for the one before it
   hipEvent_t ev_bpar[2];  // the copy out of h_bpar[k] is through
   int slot;
-  std::vector<double> last_bpar;  // what d_bpar holds (empty: nothing yet)
+  std::vector<double> last_bpar;  // what d_bpar holds (empty: nothing yet, or a device step wrote it)
+  stb_hb_obj hb;        // the per-group concentration step (hyperb.hip): ranges, L, Y, and whether d_bpar holds anything
   double *d_vt;
   uint64_t vstride;
   void *d_ws;
@@ -278,6 +280,7 @@ struct stb_tindic {
 };
 
 static void ti_release(stb_tindic_t *s) {
+  stb_hb_obj_release(&s->hb);
   void *pooled[] = {s->d_stab, s->d_sS1, s->d_sws};
   for (void *p : pooled)
     if (p) stb_pool_free(p);
@@ -470,6 +473,8 @@ extern "C" int stb_tindic_set_h(stb_tindic_t *s, const double *hflat) {
 // new concentrations through the staging buffer used two calls ago (its copy is long through); unchanged ones stay
 static int ti_stage_bpar(stb_tindic_t *s, const double *bpar, const char *who) {
   int rc = 0;
+  if (bpar == STB_BPAR_RESIDENT)  // what the object holds: nothing to upload
+    return s->hb.resident ? 0 : stb_fail("%s: STB_BPAR_RESIDENT, but the object holds no concentrations yet", who);
   const bool same_b = s->last_bpar.size() == (size_t)s->I && memcmp(s->last_bpar.data(), bpar, sizeof(double) * s->I) == 0;
   if (!same_b) {
     const int k = s->slot ^= 1;
@@ -482,7 +487,58 @@ static int ti_stage_bpar(stb_tindic_t *s, const double *bpar, const char *who) {
         rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
     }
     if (!rc) s->last_bpar.assign(bpar, bpar + s->I);
+    if (!rc) stb_hb_obj_uploaded(&s->hb, bpar, s->I);
   }
+  return rc;
+}
+
+extern "C" int stb_tindic_set_bpar(stb_tindic_t *s, const double *bpar) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_bpar";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!bpar || bpar == STB_BPAR_RESIDENT) return stb_fail("%s: bpar (host, I values) is required", who);
+  for (int i = 0; i < s->I; i++)
+    if (!std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be finite)", who, i, bpar[i]);
+  const int prev = stb_device_enter(s->dev);
+  const int rc = ti_stage_bpar(s, bpar, who);
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_get_bpar(stb_tindic_t *s, double *bpar_out) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_get_bpar";
+  if (!s || !bpar_out) return stb_fail("%s: null %s", who, s ? "output" : "object");
+  if (!s->hb.resident) return stb_fail("%s: the object holds no concentrations yet", who);
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (hipMemcpyAsync(bpar_out, s->d_bpar, sizeof(double) * s->I, hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+      hipStreamSynchronize(s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_set_bgroups(stb_tindic_t *s, int G, const uint64_t *goff_host) {
+  STB_ENTRY;
+  if (!s) return stb_fail("stb_tindic_set_bgroups: null object");
+  const int prev = stb_device_enter(s->dev);
+  const int rc = stb_hb_obj_set_groups(&s->hb, s->I, G, goff_host, s->st, "stb_tindic_set_bgroups");
+  stb_device_leave(prev);
+  return rc;
+}
+
+// the per-group concentration step (hyperb.hip) on the object's T, customer offsets and concentrations, queued behind its
+// sweeps.  The step writes d_bpar: the host copy that spares an upload no longer describes it
+extern "C" int stb_tindic_sampleb_groups(stb_tindic_t *s, double a, double shape, double scale, uint64_t seed, uint64_t sweep,
+                                         double *bgrp_host, stb_bgroups_info_t *info) {
+  STB_ENTRY;
+  if (!s) return stb_fail("stb_tindic_sampleb_groups: null object");
+  const int prev = stb_device_enter(s->dev);
+  const int rc = stb_hb_obj_step(&s->hb, a, shape, scale, s->I, nullptr, s->d_coff, s->d_T, s->d_bpar, seed, sweep, s->st,
+                                 bgrp_host, info, "stb_tindic_sampleb_groups");
+  if (s->hb.resident) s->last_bpar.clear();
+  stb_device_leave(prev);
   return rc;
 }
 
@@ -492,7 +548,8 @@ extern "C" int stb_tindic_sweep(stb_tindic_t *s, double a, const double *bpar, u
   if (!(a >= 0.0 && a < 1.0)) return stb_fail("stb_tindic_sweep: discount a=%g outside [0, 1)", a);
   if (!bpar) return stb_fail("stb_tindic_sweep: bpar is required");
   if (nsweeps < 0) return stb_fail("stb_tindic_sweep: nsweeps=%d", nsweeps);
-  for (int i = 0; i < s->I; i++)
+  if (bpar == STB_BPAR_RESIDENT && stb_hb_obj_resident(&s->hb, a, "stb_tindic_sweep")) return 1;
+  for (int i = 0; bpar != STB_BPAR_RESIDENT && i < s->I; i++)
     if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("stb_tindic_sweep: bpar[%d]=%g (must be > -a = %g)", i, bpar[i], -a);
   if (nsweeps == 0) return 0;
   const int prev = stb_device_enter(s->dev);
@@ -534,6 +591,8 @@ extern "C" int stb_tindic_to_groups(stb_tindic_t *s, stb_groups_t *g, const doub
   if (g->dev != s->dev) return stb_fail("stb_tindic_to_groups: the group set is on device %d, the indicators on %d", g->dev, s->dev);
   if (g->pending == 1) return stb_fail("stb_tindic_to_groups: an evaluation queued with stb_groups_aterms_async has not been waited for");
   if (g->putting) return stb_fail("stb_tindic_to_groups: the group set is between stb_groups_pairs_begin and _commit");
+  if (bpar == STB_BPAR_RESIDENT && !s->hb.resident)
+    return stb_fail("stb_tindic_to_groups: STB_BPAR_RESIDENT, but the object holds no concentrations yet");
   const int prev = stb_device_enter(s->dev);
   int rc = 0;
   // the bounds the new pairs can need, known without looking at them: n up to max n, t up to min(max n, M)
@@ -553,7 +612,11 @@ extern "C" int stb_tindic_to_groups(stb_tindic_t *s, stb_groups_t *g, const doub
                         hipMemcpyAsync(g->d_t, s->d_t, sizeof(uint16_t) * s->G, hipMemcpyDeviceToDevice, g->st) != hipSuccess)) ||
               hipMemcpyAsync(g->d_T, s->d_T, sizeof(uint32_t) * s->I, hipMemcpyDeviceToDevice, g->st) != hipSuccess))
     rc = stb_fail("stb_tindic_to_groups: %s", hipGetErrorString(hipGetLastError()));
-  if (!rc && bpar) {
+  if (!rc && bpar == STB_BPAR_RESIDENT) {  // (g->st waits for the object's stream above)
+    for (int i = 0; i < g->I; i++) g->h_bpar[i] = NAN;  // (the host's copy no longer says what the set holds)
+    if (hipMemcpyAsync(g->d_bpar, s->d_bpar, sizeof(double) * g->I, hipMemcpyDeviceToDevice, g->st) != hipSuccess)
+      rc = stb_fail("stb_tindic_to_groups: %s", hipGetErrorString(hipGetLastError()));
+  } else if (!rc && bpar) {
     memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);  // (g->st was idle above: its staging area is free)
     if (hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess)
       rc = stb_fail("stb_tindic_to_groups: %s", hipGetErrorString(hipGetLastError()));
@@ -607,7 +670,8 @@ extern "C" int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar
   if (stb_lj_check(a, flags, s->I, who)) return 1;
   if (!bpar) return stb_fail("%s: bpar is required", who);
   if (!total) return stb_fail("%s: total is required", who);
-  for (int i = 0; i < s->I; i++)
+  if (bpar == STB_BPAR_RESIDENT && stb_hb_obj_resident(&s->hb, a, who)) return 1;
+  for (int i = 0; bpar != STB_BPAR_RESIDENT && i < s->I; i++)
     if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
   const int prev = stb_device_enter(s->dev);
   int rc = 0;
@@ -823,7 +887,8 @@ extern "C" int stb_tindic_sweep_dishes(stb_tindic_t *s, double a, const double *
   if (!(a >= 0.0 && a < 1.0)) return stb_fail("%s: discount a=%g outside [0, 1)", who, a);
   if (!bpar) return stb_fail("%s: bpar is required", who);
   if (nsweeps < 0) return stb_fail("%s: nsweeps=%d", who, nsweeps);
-  for (int i = 0; i < s->I; i++)
+  if (bpar == STB_BPAR_RESIDENT && stb_hb_obj_resident(&s->hb, a, who)) return 1;
+  for (int i = 0; bpar != STB_BPAR_RESIDENT && i < s->I; i++)
     if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
   if (s->maxK > STB_TD_MAXK)
     return stb_fail("%s: a restaurant has K=%u dishes; the sweep holds at most STB_TD_MAXK = %d", who, s->maxK, STB_TD_MAXK);
@@ -1069,7 +1134,8 @@ extern "C" int stb_tindic_set_heldout(stb_tindic_t *s, const uint64_t *hoff_host
 static int ti_pr_ready(stb_tindic_t *s, double a, const double *bpar, unsigned flags, bool heldout, const char *who) {
   if (stb_pr_check(a, flags, s->I, who)) return 1;
   if (!bpar) return stb_fail("%s: bpar is required", who);
-  for (int i = 0; i < s->I; i++)
+  if (bpar == STB_BPAR_RESIDENT && stb_hb_obj_resident(&s->hb, a, who)) return 1;
+  for (int i = 0; bpar != STB_BPAR_RESIDENT && i < s->I; i++)
     if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
   if (s->maxK > STB_TD_MAXK)
     return stb_fail("%s: a restaurant has K=%u dishes; the kernel holds at most STB_TD_MAXK = %d", who, s->maxK, STB_TD_MAXK);
