@@ -36,10 +36,14 @@
  *      they live (STB_BPAR_RESIDENT), and the discount step runs on them: stb_tindic_to_groups(..., STB_BPAR_RESIDENT) +
  *      stb_groups_samplea.  Each iteration's line ends with min, median and max of b_i from one read-back.  -B with -j is
  *      refused: the joint step models one shared b.
+ *  13. with -H G (needs -d -z -w) the base weights are hierarchical: the restaurants are cut into G equal contiguous ranges,
+ *      each with weights of its own under a shared root, and stb_tindic_sample_hgroups takes stb_tindic_sample_h's place
+ *      (auxiliary tables, the root, the concentration alpha from a Gamma(1.1, 20) prior, then every group's h, one call);
+ *      each iteration prints alpha and the largest |sum_k h_gk - 1| over the restaurants from one read-back of h.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4]
  */
 #include <math.h>
 #include <stdio.h>
@@ -60,10 +64,10 @@ static int cmp_double(const void *x, const void *y) {
 }
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPB")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -79,10 +83,15 @@ int main(int argc, char **argv) {
     else if (c == 'w') redraw = 1;
     else if (c == 'P') predict = 1;
     else if (c == 'B') pergroup = 1;
+    else if (c == 'H') hgroups = atoi(optarg);
     else return 2;
   }
   if (redraw && !(explicit_d && dishes)) {
     fprintf(stderr, "pyp_resample: -w needs -d -z\n");
+    return 2;
+  }
+  if (hgroups < 0 || (hgroups && !(explicit_d && dishes && redraw))) {
+    fprintf(stderr, "pyp_resample: -H G needs G >= 1 and -d -z -w\n");
     return 2;
   }
   if (predict && !(explicit_d && dishes)) {
@@ -189,14 +198,36 @@ int main(int argc, char **argv) {
       free(hoff);
       free(hcls);
     }
+    double *hflat = NULL;
+    if (hgroups) { /* hgroups equal contiguous ranges of restaurants, each with base weights of its own */
+      uint64_t *hgoff = malloc(sizeof(*hgoff) * ((size_t)hgroups + 1));
+      for (j = 0; j <= hgroups; j++) hgoff[j] = (uint64_t)j * (uint64_t)J / (uint64_t)hgroups;
+      if (stb_tindic_set_hgroups(ti, hgroups, hgoff)) yaps_quit("stb_tindic_set_hgroups: %s\n", stb_last_error());
+      free(hgoff);
+      hflat = malloc(sizeof(double) * (size_t)J * DISHES);
+    }
     for (it = 0; it < cycles; it++) {
       if (dishes) {
         stb_tdish_info_t di;
         if (stb_tindic_sweep_dishes(ti, a, bp, (uint64_t)seed + 2, (uint64_t)it, 1, &di)) yaps_quit("stb_tindic_sweep_dishes: %s\n", stb_last_error());
         stuck += di.stuck + di.skipped;
         /* the uncollapsed step: seeds of their own, so neither shares a stream with a sweep or with the other */
-        if (redraw && (stb_tindic_sample_lik(ti, NULL, 0.5, (uint64_t)seed + 3, (uint64_t)it) ||
-                       stb_tindic_sample_h(ti, NULL, 1.0, (uint64_t)seed + 4, (uint64_t)it)))
+        if (redraw && hgroups) { /* alpha: 5 to start with, then what the step before left on the device */
+          stb_hgroups_opts_t ho = {it == 0 ? 5.0 : 0.0, 1.0, 1.1, 20.0, NULL, STB_HG_SAMPLE_ALPHA, 0};
+          stb_hgroups_info_t hi;
+          double worst = 0.0;
+          if (stb_tindic_sample_lik(ti, NULL, 0.5, (uint64_t)seed + 3, (uint64_t)it) ||
+              stb_tindic_sample_hgroups(ti, &ho, (uint64_t)seed + 4, (uint64_t)it, &hi) || stb_tindic_get_h(ti, hflat))
+            yaps_quit("stb_tindic_sample_lik / _sample_hgroups: %s\n", stb_last_error());
+          for (j = 0; j < J; j++) {
+            double sum = 0.0;
+            for (i = 0; i < DISHES; i++) sum += hflat[(size_t)j * DISHES + i];
+            if (fabs(sum - 1.0) > worst) worst = fabs(sum - 1.0);
+          }
+          printf("iteration %d: base weights in %d groups, alpha %.6f, %llu tables, %llu auxiliary, largest |sum h - 1| %.3g\n", it,
+                 hgroups, hi.alpha, (unsigned long long)hi.tables, (unsigned long long)hi.aux_tables, worst);
+        } else if (redraw && (stb_tindic_sample_lik(ti, NULL, 0.5, (uint64_t)seed + 3, (uint64_t)it) ||
+                              stb_tindic_sample_h(ti, NULL, 1.0, (uint64_t)seed + 4, (uint64_t)it)))
           yaps_quit("stb_tindic_sample_lik / _sample_h: %s\n", stb_last_error());
       }
       if (stb_tindic_sweep(ti, a, bp, (uint64_t)seed, (uint64_t)it, 1)) yaps_quit("stb_tindic_sweep: %s\n", stb_last_error());
@@ -288,6 +319,7 @@ int main(int argc, char **argv) {
     }
     stb_groups_free(gs);
     stb_tindic_free(ti);
+    free(hflat);
     free(nf);
     free(tf);
     free(hf);

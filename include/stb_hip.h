@@ -755,6 +755,84 @@ int stb_tindic_sample_h(stb_tindic_t *s, const double *gamma_host /* Kmax, or NU
 int stb_tindic_loglik(stb_tindic_t *s, double *total, uint64_t *impossible /* or NULL */);
 int stb_tindic_get_h(stb_tindic_t *s, double *h_out);
 
+/* ---- base weights per group of restaurants under a shared root (hgroups.hip; additive: the reference has no such step) ----
+ * stb_tindic_sample_h draws one h for every restaurant.  Here restaurants 0 .. I-1 are cut into G contiguous ranges
+ * goff[G+1] (stb_sample_bgroups' convention: 0 = goff[0] <= ... <= goff[G] = I, empty ranges allowed; d_goff NULL: every
+ * restaurant its own group, G = I), each range with weights of its own that share strength through a root (the HDP / HPYP
+ * structure):
+ *     r ~ Dirichlet(gamma_1 .. gamma_Kmax);   h_g | r ~ Dirichlet(alpha r_1, .., alpha r_Kmax), alpha > 0;
+ *     every table of a restaurant of group g draws its dish from h_g.
+ * Dish k is local pair k of every restaurant and Kmax = max_i K_i <= STB_TD_MAXK, as for _sample_h.  c_gk = sum of t_ik over
+ * the restaurants i of group g with K_i > k.  One call is one exact Gibbs step, in this order -- r and alpha are updated with
+ * h integrated out, then h is drawn from its full conditional:
+ *   1. c_gk (integers), C_g = sum_k c_gk.
+ *   2. auxiliary tables from the Antoniak law: w = alpha * r_k (one FP64 product), then
+ *        m_gk = [c_gk >= 1] + sum_{j=1}^{c_gk - 1} [u_j * (w + (double)j) < w]      (doubles as written, no contraction)
+ *      M_g = sum_k m_gk, s_k = sum_g m_gk.
+ *   3. r' ~ Dirichlet(gamma_k + s_k) (gamma_host: Kmax values, or NULL for gamma0), written over d_root.  Skipped with
+ *      STB_HG_KEEP_ROOT (gamma is then not read).
+ *   4. with STB_HG_SAMPLE_ALPHA: q_g ~ Beta(alpha, C_g) (C_g > 0), alpha' ~ Gamma(shape + sum_g M_g, rate = 1/scale + sum_g
+ *      -log q_g): exactly stb_sample_bgroups with a = 0, I = G "restaurants" of N = C_g customers and T = M_g tables, one
+ *      group {0, G}, every b = alpha, and seed ^ 0xA54FF53A5F1D36F1 (same sweep).  alpha' stays in a device word and feeds
+ *      step 5 without passing through the host.  Without the flag alpha' = alpha and shape, scale are not read.
+ *   5. h_g ~ Dirichlet(alpha' r'_k + c_gk) for every group (empty ranges too: a draw from the prior), written to every pair
+ *      (i, k) with i in g and k < K_i, to d_hgrp[g * Kmax + k] when given; d_c and d_m receive c_gk and m_gk when given.
+ * Uniforms: key = mix(seed + (sweep+1) gamma), the constant and mix of stb_sample_lik.  Cell e = g * Kmax + k (uint64) owns
+ * key_e = mix(key + (e+1) gamma); its group variate takes key_e's elements 1, 2, ... by the log-Gamma recipe above, exactly
+ * as _sample_h does with e = k; its u_j are element j of the substream mix(key_e ^ 0x59B1D5A7C3E9F24D) (stb_sample_bgroups'
+ * y substream and open-interval unit).  Root cell k owns mix(key_R + (k+1) gamma), key_R = mix(key ^ 0x6A09E667F3BCC909).
+ * Every draw depends on (seed, sweep, e) alone.  Each Dirichlet (the root, every group row) is normalised as _sample_h's:
+ * shape_k = alpha' * r'_k + (double)c_gk (the root: gamma_k + (double)s_k), lg_k the log-Gamma variate, M = max lg_k,
+ * e_k = exp(lg_k - M), Z the e_k added one after another in k order, h_k = e_k / Z; a row sums to 1 within 2 u Kmax.  So
+ * with STB_HG_KEEP_ROOT, G = 1, alpha = 1 and d_root = gamma the call gives _sample_h(gamma)'s bits.  No bit depends on the
+ * launch geometry (STB_HGROUPS_WAVES = 1, 2, 4 or 8 waves a workgroup) or on who takes a cell's Bernoulli draws
+ * (STB_HGROUPS_FORM = lane | wave; default: a wave takes the cells with c_gk > 257).  tests/hh_oracle.py replays the step.
+ * d_root (Kmax doubles, in: r, out: r') need only be positive and finite; it need not sum to 1.  All launches are queued
+ * back to back on the stream; one wait, for the error and info words (with d_goff given, the raw call first reads the G + 1
+ * offsets back to check them).  info (may be NULL): alpha' (alpha without the flag), tables = sum_g C_g, aux_tables =
+ * sum_g M_g, the error word.
+ * Refused before anything is queued, with stb_last_error() set and nothing written: a null d_koff, d_t, d_root, d_h or opts;
+ * I < 1; Kmax outside 1 .. STB_TD_MAXK; G < 1, G != I without ranges, ranges that are not 0 = goff[0] <= ... <= goff[G] = I;
+ * unknown flags; alpha, gamma (unless STB_HG_KEEP_ROOT) or shape, scale (with STB_HG_SAMPLE_ALPHA) not positive and finite.
+ * Fails after the wait, error word: 1 a rejection loop ran out, 2 a Z is not positive and finite, 4 a shape
+ * alpha r_k + c_gk is not positive and finite, 8 a group's C_g is above 2^32 - 1; or the concentration's draw was not a
+ * positive finite double.  The outputs are then undefined.
+ * Object layer, queued on the object's stream behind its sweeps; ranges, root and alpha live with the object:
+ *   stb_tindic_set_hgroups     the ranges (goff_host[G+1], checked as above; NULL: every restaurant its own group, the
+ *                              state of a new object)
+ *   stb_tindic_set_hroot       the root, Kmax positive finite values (NULL: 1/Kmax each, the state of a new object)
+ *   stb_tindic_get_hroot       the root to the host, after the queued work
+ *   stb_tindic_sample_hgroups  the step on the object's t.  opts->alpha > 0: the concentration of this step; opts->alpha = 0:
+ *                              the one the last successful step left (info->alpha), refused when there is none.  It
+ *                              replaces the object's h (one is made when it had none) and root; stb_tindic_set_h,
+ *                              _sample_h, the sweeps, _logjoint, _predict and _heldout simply see the per-group h.
+ * Refused, the object's h, root, ranges and alpha as they were: the refusals above, a null object, an object created with
+ * STB_TI_REF_ODDS, the largest K_i outside 1 .. STB_TD_MAXK.  A step that fails after its wait leaves h and the root
+ * undefined: stb_tindic_sweep_dishes is then refused until a _sample_hgroups / _sample_h that succeeds or a _set_h, as
+ * after a failed _sample_h; give the root again with _set_hroot. */
+#define STB_HG_KEEP_ROOT 1u
+#define STB_HG_SAMPLE_ALPHA 2u
+typedef struct stb_hgroups_opts {
+  double alpha, gamma0, shape, scale;
+  const double *gamma_host; /* Kmax, or NULL for gamma0 */
+  unsigned flags, reserved;
+} stb_hgroups_opts_t;
+typedef struct stb_hgroups_info {
+  double alpha;
+  uint64_t tables, aux_tables;
+  unsigned error_word, reserved;
+} stb_hgroups_info_t;
+int stb_sample_hgroups(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
+                       const stb_hgroups_opts_t *opts, double *d_root /* Kmax: in r, out r' */, double *d_h /* pairs, out */,
+                       double *d_hgrp /* G x Kmax or NULL */, uint32_t *d_c /* G x Kmax or NULL */,
+                       uint32_t *d_m /* G x Kmax or NULL */, uint64_t seed, uint64_t sweep, void *stream,
+                       stb_hgroups_info_t *info);
+int stb_tindic_set_hgroups(stb_tindic_t *s, int G, const uint64_t *goff_host /* G + 1, or NULL */);
+int stb_tindic_set_hroot(stb_tindic_t *s, const double *root_host /* Kmax, or NULL */);
+int stb_tindic_get_hroot(stb_tindic_t *s, double *root_out /* Kmax */);
+int stb_tindic_sample_hgroups(stb_tindic_t *s, const stb_hgroups_opts_t *opts, uint64_t seed, uint64_t sweep,
+                              stb_hgroups_info_t *info);
+
 /* ---- the log joint probability of a sampler state (logjoint.hip): what a Gibbs chain is watched by, what runs are
  * compared on, what annealed and bridge estimates of the evidence feed on.  Pairs, h, b_i and a as for stb_tcounts above;
  * T_i = sum_k t_ik, N_i = sum_k n_ik:

@@ -92,6 +92,22 @@ class BGroupsInfo(C.Structure):
                 ("reserved", C.c_uint), ("b", C.c_double)]
 
 
+HG_KEEP_ROOT = 1      # stb_hgroups_opts_t flags (include/stb_hip.h)
+HG_SAMPLE_ALPHA = 2
+
+
+class HGroupsOpts(C.Structure):
+    """stb_hgroups_opts_t (include/stb_hip.h)"""
+    _fields_ = [("alpha", C.c_double), ("gamma0", C.c_double), ("shape", C.c_double), ("scale", C.c_double),
+                ("gamma_host", c_double_p), ("flags", C.c_uint), ("reserved", C.c_uint)]
+
+
+class HGroupsInfo(C.Structure):
+    """stb_hgroups_info_t (include/stb_hip.h)"""
+    _fields_ = [("alpha", C.c_double), ("tables", C.c_uint64), ("aux_tables", C.c_uint64), ("error_word", C.c_uint),
+                ("reserved", C.c_uint)]
+
+
 class JointInfo(C.Structure):
     """stb_joint_info_t (include/stb_hip.h)"""
     _fields_ = [("stages", C.c_int), ("accepted", C.c_int), ("evals", C.c_int), ("stage_pick", C.c_int),
@@ -256,6 +272,13 @@ def lib() -> C.CDLL:
     sig("stb_tindic_sample_h", i, [vp, c_double_p, d, u64, u64])
     sig("stb_tindic_loglik", i, [vp, c_double_p, C.POINTER(u64)])
     sig("stb_tindic_get_h", i, [vp, c_double_p])
+    # ---- base weights per group of restaurants under a shared root
+    hgo, hgi = C.POINTER(HGroupsOpts), C.POINTER(HGroupsInfo)
+    sig("stb_sample_hgroups", i, [i, vp, vp, u, i, vp, hgo, vp, vp, vp, vp, vp, u64, u64, vp, hgi])
+    sig("stb_tindic_set_hgroups", i, [vp, i, C.POINTER(u64)])
+    sig("stb_tindic_set_hroot", i, [vp, c_double_p])
+    sig("stb_tindic_get_hroot", i, [vp, c_double_p])
+    sig("stb_tindic_sample_hgroups", i, [vp, hgo, u64, u64, hgi])
     sig("stb_sample_partition", i, [vp, vp, u, u, d, u64, vp, vp, vp, u, vp, vp, u, u64, u64, vp])
     sig("stb_tcounts_partition", i, [vp, d, vp, c_double_p, u64, u64])
     sig("stb_hist_create_empty", vp, [u, i])
@@ -902,6 +925,37 @@ def sample_bgroups(a, shape, scale, T, bpar, seed: int, sweep: int, N=None, coff
     return bgrp, Lt, Yt, rate, info
 
 
+def hgroups_opts(alpha, gamma=1.0, shape=1.0, scale=1.0, flags: int = 0, Kmax: int = 0):
+    """(the host vector to keep alive or None, HGroupsOpts): gamma a scalar or Kmax values"""
+    keep, gp, g0 = _prior(gamma, Kmax)
+    return keep, HGroupsOpts(float(alpha), g0, float(shape), float(scale), gp, int(flags), 0)
+
+
+def sample_hgroups(koff, t, Kmax: int, root, alpha, gamma, seed: int, sweep: int, goff=None, flags: int = 0, shape=1.0,
+                   scale=1.0, want=("hgrp", "c", "m"), stream=None):
+    """stb_sample_hgroups on device tensors: koff (int64 [I+1] prefix sums of K_i), t (int16 holding the uint16 table
+    counts of the pairs), root (float64 [Kmax], overwritten with r'), goff (int64 [G+1] ranges; None: every restaurant its
+    own group).  Returns (h [pairs], dict with whichever of hgrp (float64), c, m (int32 holding uint32) `want` names, each
+    (G, Kmax), HGroupsInfo)"""
+    torch = _torch()
+    I = int(koff.shape[0]) - 1
+    G = I if goff is None else int(goff.shape[0]) - 1
+    dev = root.device
+    h = torch.empty(int(t.shape[0]), dtype=torch.float64, device=dev)
+    out = {n: torch.empty((G, Kmax), dtype=torch.float64 if n == "hgrp" else torch.int32, device=dev) for n in want}
+    keep, opts = hgroups_opts(alpha, gamma, shape, scale, flags, Kmax)
+    info = HGroupsInfo()
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    rc = lib().stb_sample_hgroups(I, ptr(koff), ptr(t), Kmax, G, None if goff is None else goff.data_ptr(), C.byref(opts),
+                                  ptr(root), ptr(h), ptr(out.get("hgrp")), ptr(out.get("c")), ptr(out.get("m")), seed, sweep,
+                                  stream_ptr(stream), C.byref(info))
+    if rc:
+        err = StbError(last_error())
+        err.info = info
+        raise err
+    return h, out, info
+
+
 def _prior(v, n: int):
     """a Dirichlet parameter, a scalar for every entry or n values, as (the host vector to keep alive or None, its pointer or
     None, the scalar)"""
@@ -1255,6 +1309,44 @@ class TableIndicators(_BGroupsMixin):
         gamma a scalar or one value per dish (the largest K).  Give it another seed than sample_lik"""
         keep, gp, g0 = _prior(gamma, self.maxK)
         check(self.L.stb_tindic_sample_h(self.h, gp, g0, seed, sweep))
+
+    # ---- base weights per group of restaurants under a shared root (stb_tindic_set_hgroups / _set_hroot / _sample_hgroups)
+
+    def set_hgroups(self, goff=None):
+        """the contiguous ranges of restaurants that share base weights: goff[G+1] (None: every restaurant its own group)"""
+        if goff is None:
+            check(self.L.stb_tindic_set_hgroups(self.h, 0, None))
+            return
+        goff = np.ascontiguousarray(goff, dtype=np.uint64)
+        check(self.L.stb_tindic_set_hgroups(self.h, int(goff.shape[0]) - 1, goff.ctypes.data_as(C.POINTER(C.c_uint64))))
+
+    def set_hroot(self, root=None):
+        """the root of the groups' base weights: the largest K positive values (None: equal weights)"""
+        if root is None:
+            check(self.L.stb_tindic_set_hroot(self.h, None))
+            return
+        root = np.ascontiguousarray(root, dtype=np.float64)
+        if root.shape != (self.maxK,):
+            raise StbError(f"expected {self.maxK} values, got shape {root.shape}")
+        check(self.L.stb_tindic_set_hroot(self.h, dp(root)))
+
+    def get_hroot(self):
+        root = np.zeros(self.maxK, dtype=np.float64)
+        check(self.L.stb_tindic_get_hroot(self.h, dp(root)))
+        return root
+
+    def sample_hgroups(self, alpha, gamma=1.0, seed: int = 0, sweep: int = 0, flags: int = 0, shape=1.0, scale=1.0):
+        """one step of the grouped base weights: auxiliary tables, the root from Dirichlet(gamma + their sums), with
+        HG_SAMPLE_ALPHA the concentration, then every group's h; alpha = 0 takes the concentration the last step left.
+        Returns HGroupsInfo (alpha, tables, aux_tables).  Give it another seed than sample_lik"""
+        keep, opts = hgroups_opts(alpha, gamma, shape, scale, flags, self.maxK)
+        info = HGroupsInfo()
+        rc = self.L.stb_tindic_sample_hgroups(self.h, C.byref(opts), seed, sweep, C.byref(info))
+        if rc:
+            err = StbError(last_error())
+            err.info = info
+            raise err
+        return info
 
     def loglik(self):
         """(sum over customers of log lik[class, dish], cells with customers and no likelihood) of the current state"""

@@ -1,0 +1,19 @@
+// hgroups.h -- private: what the object layer (tindic.hip) needs of hgroups.hip beyond include/stb_hip.h.
+#ifndef STB_HGROUPS_H
+#define STB_HGROUPS_H
+
+#include "stb_common.h"
+#include "../../include/stb_hip.h"
+
+// opts' alpha, gamma, flags and (with STB_HG_SAMPLE_ALPHA) prior positive and finite, Kmax inside 1 .. STB_TD_MAXK; 0, or 1
+// with stb_last_error() set
+int stb_hg_check_opts(const stb_hgroups_opts_t *opts, unsigned Kmax, const char *who);
+// stb_sample_hgroups behind its checks: the caller has checked the arrays, Kmax, opts (stb_hg_check_opts) and the ranges
+// (d_goff: 0 = goff[0] <= ... <= goff[G] = I, or null with G = I).  Queues every launch on st, waits once, fills *info.
+// *touched (may be null) is set once the first launch that writes d_root / d_h is queued: a call that fails with it unset
+// has left them as they were
+int stb_hg_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
+                  const stb_hgroups_opts_t *opts, double *d_root, double *d_h, double *d_hgrp, uint32_t *d_c, uint32_t *d_m,
+                  uint64_t seed, uint64_t sweep, hipStream_t st, stb_hgroups_info_t *info, const char *who, bool *touched);
+
+#endif

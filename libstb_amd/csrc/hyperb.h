@@ -12,6 +12,14 @@ extern "C" {
 int stb_hb_bgroups(double a, double shape, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff, const uint32_t *d_T,
                    int G, const uint64_t *d_goff, double *d_bpar, double *d_bgrp, double *d_L, uint32_t *d_Y, double *d_rate,
                    uint64_t seed, uint64_t sweep, void *stream, stb_bgroups_info_t *info, const char *who);
+/* the same step in two halves, for a caller that queues it among launches of its own and waits once (hgroups.hip):
+ * _queue checks the arguments and queues the launches on `stream` (customers as d_N; no d_bgrp, no d_rate) without waiting;
+ * _answer reads the pinned words of the calling thread's last _queue once that stream has been waited for, fills *info and
+ * fails as stb_hb_bgroups does.  Between the two the thread makes no other stb_hb_* call */
+int stb_hb_bgroups_queue(double a, double shape, double scale, int I, const uint32_t *d_N, const uint32_t *d_T, int G,
+                         const uint64_t *d_goff, double *d_bpar, double *d_L, uint32_t *d_Y, uint64_t seed, uint64_t sweep,
+                         void *stream, const char *who);
+int stb_hb_bgroups_answer(int G, stb_bgroups_info_t *info, const char *who);
 /* frees the calling thread's words and scratch (stb_sampler_cache_clear) */
 void stb_hb_release(void);
 #ifdef __cplusplus

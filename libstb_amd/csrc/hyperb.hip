@@ -9,7 +9,9 @@
 //   k_hb_group_wg    pass 2 over ranges: a workgroup per group sums L and Y, draws b_g, scatters it
 //   k_hb_group_lane  pass 2 without ranges (every restaurant its own group): a lane per group
 //   k_hb_finish      the counts, the error word and (one group) b to pinned words
-// All three are queued back to back on the caller's stream; the call waits once, for the pinned words.
+// All three are queued back to back on the caller's stream; the call waits once, for the pinned words.  The two halves
+// are also entries of their own (hyperb.h: stb_hb_bgroups_queue, _answer) for a caller that queues the step among
+// launches of its own and waits once for all of them (hgroups.hip).
 //
 // Streams: key = mix(seed + (sweep+1) gamma); restaurant i owns key_i = mix(key + (i+1) gamma).  L_i is hq_draw_L
 // (gamma_dev.h) on key_i unchanged: with every b_i equal it is stb_sample_logq's L to the bit.  The y take the substream
@@ -279,11 +281,12 @@ static int hb_ready(size_t nY, const char *who) {
   return 0;
 }
 
-extern "C" int stb_hb_bgroups(double a, double shape, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff,
-                              const uint32_t *d_T, int G, const uint64_t *d_goff, double *d_bpar, double *d_bgrp, double *d_L,
-                              uint32_t *d_Y, double *d_rate, uint64_t seed, uint64_t sweep, void *stream,
-                              stb_bgroups_info_t *info, const char *who) {
-  STB_ENTRY;
+// the checks and the launches of a step, nothing waited for: *queued says whether hb_answer has words to read
+static int hb_queue(double a, double shape, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff,
+                    const uint32_t *d_T, int G, const uint64_t *d_goff, double *d_bpar, double *d_bgrp, double *d_L,
+                    uint32_t *d_Y, double *d_rate, uint64_t seed, uint64_t sweep, void *stream, stb_bgroups_info_t *info,
+                    const char *who, bool *queued) {
+  *queued = false;
   if (info) {
     info->bad_restaurants = info->kept_groups = 0;
     info->error_word = 0;
@@ -323,7 +326,12 @@ extern "C" int stb_hb_bgroups(double a, double shape, double scale, int I, const
                (const double *)d_L, (const uint32_t *)d_Y, d_bpar, d_bgrp, d_rate, keyG, hb.d_ctl);
   STB_LAUNCH(k_hb_finish, dim3(1), dim3(1), st, (const unsigned *)hb.d_ctl, hb.h_out_dev);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
+  *queued = true;
+  return 0;
+}
+
+// the pinned words of the step hb_queue queued last on this thread, once its stream has been waited for
+static int hb_answer(int G, stb_bgroups_info_t *info, const char *who) {
   const volatile unsigned long long *h = hb.h_out;
   const unsigned err = (unsigned)h[0];
   if (info) {
@@ -341,6 +349,39 @@ extern "C" int stb_hb_bgroups(double a, double shape, double scale, int I, const
     memcpy(&info->b, &bits, sizeof(double));
   }
   return 0;
+}
+
+extern "C" int stb_hb_bgroups(double a, double shape, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff,
+                              const uint32_t *d_T, int G, const uint64_t *d_goff, double *d_bpar, double *d_bgrp, double *d_L,
+                              uint32_t *d_Y, double *d_rate, uint64_t seed, uint64_t sweep, void *stream,
+                              stb_bgroups_info_t *info, const char *who) {
+  STB_ENTRY;
+  bool queued = false;
+  if (hb_queue(a, shape, scale, I, d_N, d_coff, d_T, G, d_goff, d_bpar, d_bgrp, d_L, d_Y, d_rate, seed, sweep, stream, info, who,
+               &queued))
+    return 1;
+  if (!queued) return 0;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  return hb_answer(G, info, who);
+}
+
+extern "C" int stb_hb_bgroups_queue(double a, double shape, double scale, int I, const uint32_t *d_N, const uint32_t *d_T, int G,
+                                    const uint64_t *d_goff, double *d_bpar, double *d_L, uint32_t *d_Y, uint64_t seed,
+                                    uint64_t sweep, void *stream, const char *who) {
+  STB_ENTRY;
+  bool queued = false;
+  return hb_queue(a, shape, scale, I, d_N, nullptr, d_T, G, d_goff, d_bpar, nullptr, d_L, d_Y, nullptr, seed, sweep, stream,
+                  nullptr, who, &queued);
+}
+
+extern "C" int stb_hb_bgroups_answer(int G, stb_bgroups_info_t *info, const char *who) {
+  STB_ENTRY;
+  if (info) {
+    info->bad_restaurants = info->kept_groups = 0;
+    info->error_word = 0;
+    info->b = NAN;
+  }
+  return hb_answer(G, info, who);
 }
 
 extern "C" int stb_sample_bgroups(double a, double shape, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff,

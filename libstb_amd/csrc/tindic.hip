@@ -30,6 +30,7 @@
 #include "tindic.h"
 #include "tlik.h"
 #include "predict.h"
+#include "hgroups.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
 // ---- lane form -------------------------------------------------------------------------------------------------
@@ -258,6 +259,11 @@ struct stb_tindic {
   int slot;
   std::vector<double> last_bpar;  // what d_bpar holds (empty: nothing yet, or a device step wrote it)
   stb_hb_obj hb;        // the per-group concentration step (hyperb.hip): ranges, L, Y, and whether d_bpar holds anything
+  // the per-group base weights (hgroups.hip): the ranges, the root and the concentration live with the object
+  int hg_G;             // ranges (0: every restaurant its own group)
+  uint64_t *d_hgoff;    // [hg_G + 1], or null
+  double *d_hroot;      // [maxK] (null: 1/maxK each)
+  double hg_alpha;      // what the last successful step left (NaN: none yet)
   double *d_vt;
   uint64_t vstride;
   void *d_ws;
@@ -285,7 +291,7 @@ static void ti_release(stb_tindic_t *s) {
   for (void *p : pooled)
     if (p) stb_pool_free(p);
   void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws,
-                 s->d_cls, s->d_lik, s->d_info, s->d_hoff, s->d_hcls, s->d_pacc};
+                 s->d_cls, s->d_lik, s->d_info, s->d_hoff, s->d_hcls, s->d_pacc, s->d_hgoff, s->d_hroot};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (s->h_info) (void)hipHostFree(s->h_info);
@@ -396,6 +402,7 @@ static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, 
   s->M = s->need_table ? (M < s->N ? M : s->N) : M;
   s->a_filled = NAN;
   s->a_sfilled = NAN;
+  s->hg_alpha = NAN;
   const size_t Gs = G ? G : 1;
   int rc = 0;
   if (hipGetDevice(&s->dev) != hipSuccess || hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess ||
@@ -1049,6 +1056,139 @@ extern "C" int stb_tindic_sample_h(stb_tindic_t *s, const double *gamma_host, do
     if (touched) {
       s->d_h = d_h;
       s->h_bad = rc != 0;
+    } else if (d_h != s->d_h) {
+      (void)hipFree(d_h);  // (nothing was queued: the object keeps the h it had)
+    }
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+// ---- base weights per group under a shared root (hgroups.hip)
+
+extern "C" int stb_tindic_set_hgroups(stb_tindic_t *s, int G, const uint64_t *goff_host) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_hgroups";
+  if (!s) return stb_fail("%s: null object", who);
+  if (goff_host) {
+    if (G < 1) return stb_fail("%s: G=%d", who, G);
+    if (goff_host[0] != 0 || goff_host[G] != (uint64_t)s->I)
+      return stb_fail("%s: the ranges run from %llu to %llu; the object has I=%d restaurants", who,
+                      (unsigned long long)goff_host[0], (unsigned long long)goff_host[G], s->I);
+    for (int g = 0; g < G; g++)
+      if (goff_host[g] > goff_host[g + 1]) return stb_fail("%s: goff[%d] > goff[%d]", who, g, g + 1);
+  }
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  uint64_t *d_new = nullptr;  // the new ranges first: a call that fails leaves the object with the ranges it had
+  if (goff_host && hipMalloc((void **)&d_new, sizeof(uint64_t) * ((size_t)G + 1)) != hipSuccess)
+    rc = stb_fail("%s: out of device memory for %d ranges", who, G);
+  if (!rc && goff_host && hipMemcpy(d_new, goff_host, sizeof(uint64_t) * ((size_t)G + 1), hipMemcpyHostToDevice) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (!rc && hipStreamSynchronize(s->st) != hipSuccess) rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  if (rc) {
+    if (d_new) (void)hipFree(d_new);
+  } else {
+    if (s->d_hgoff) (void)hipFree(s->d_hgoff);
+    s->d_hgoff = d_new;
+    s->hg_G = goff_host ? G : 0;
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+// the object's root on the device, made (1/maxK each) when it has none
+static int ti_hroot(stb_tindic_t *s, const double *root_host, const char *who) {
+  const unsigned K = s->maxK;
+  std::vector<double> flat;
+  if (!root_host) {
+    flat.assign(K, 1.0 / (double)K);
+    root_host = flat.data();
+  }
+  double *d_new = s->d_hroot;
+  if (!d_new && hipMalloc((void **)&d_new, sizeof(double) * K) != hipSuccess) return stb_fail("%s: out of device memory", who);
+  if (hipStreamSynchronize(s->st) != hipSuccess || hipMemcpy(d_new, root_host, sizeof(double) * K, hipMemcpyHostToDevice) != hipSuccess) {
+    if (d_new != s->d_hroot) (void)hipFree(d_new);
+    return stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  }
+  s->d_hroot = d_new;
+  return 0;
+}
+
+static int ti_hg_maxk(const stb_tindic_t *s, const char *who) {
+  if (s->maxK < 1 || s->maxK > STB_TD_MAXK)
+    return stb_fail("%s: the largest restaurant has K=%u dishes (1 to STB_TD_MAXK = %d)", who, s->maxK, STB_TD_MAXK);
+  return 0;
+}
+
+extern "C" int stb_tindic_set_hroot(stb_tindic_t *s, const double *root_host) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_hroot";
+  if (!s) return stb_fail("%s: null object", who);
+  if (ti_hg_maxk(s, who)) return 1;
+  if (root_host && stb_tl_check_prior(root_host, s->maxK, 0.0, "root", who)) return 1;
+  const int prev = stb_device_enter(s->dev);
+  const int rc = ti_hroot(s, root_host, who);
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_get_hroot(stb_tindic_t *s, double *root_out) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_get_hroot";
+  if (!s || !root_out) return stb_fail("%s: null %s", who, s ? "root_out" : "object");
+  if (ti_hg_maxk(s, who)) return 1;
+  if (!s->d_hroot) {
+    for (unsigned k = 0; k < s->maxK; k++) root_out[k] = 1.0 / (double)s->maxK;
+    return 0;
+  }
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (hipMemcpyAsync(root_out, s->d_hroot, sizeof(double) * s->maxK, hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+      hipStreamSynchronize(s->st) != hipSuccess)
+    rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_sample_hgroups(stb_tindic_t *s, const stb_hgroups_opts_t *opts, uint64_t seed, uint64_t sweep,
+                                         stb_hgroups_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sample_hgroups";
+  if (info) {
+    info->alpha = NAN;
+    info->tables = info->aux_tables = 0;
+    info->error_word = info->reserved = 0;
+  }
+  if (!s) return stb_fail("%s: null object", who);
+  if (!opts) return stb_fail("%s: opts is required", who);
+  if (s->flags & STB_TI_REF_ODDS_FLAG)
+    return stb_fail("%s: the object was created with STB_TI_REF_ODDS; its sweeps do not leave the law h is drawn under", who);
+  if (ti_hg_maxk(s, who)) return 1;
+  stb_hgroups_opts_t o = *opts;
+  if (o.alpha == 0.0) {
+    if (!(s->hg_alpha == s->hg_alpha)) return stb_fail("%s: alpha=0 asks for the object's concentration, and it has none yet", who);
+    o.alpha = s->hg_alpha;
+  }
+  if (stb_hg_check_opts(&o, s->maxK, who)) return 1;
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  if (!s->d_hroot) rc = ti_hroot(s, nullptr, who);
+  double *d_h = s->d_h;  // an object without h gets one only if the draw is queued
+  if (!rc && !d_h && hipMalloc((void **)&d_h, sizeof(double) * (s->G ? s->G : 1)) != hipSuccess) {
+    d_h = nullptr;
+    rc = stb_fail("%s: out of device memory", who);
+  }
+  if (!rc) {
+    bool touched = false;
+    stb_hgroups_info_t mine;
+    if (!info) info = &mine;
+    rc = stb_hg_sample(s->I, s->d_koff, s->d_t, s->maxK, s->d_hgoff ? s->hg_G : s->I, s->d_hgoff, &o, s->d_hroot, d_h, nullptr,
+                       nullptr, nullptr, seed, sweep, s->st, info, who, &touched);
+    if (touched) {
+      s->d_h = d_h;
+      s->h_bad = rc != 0;
+      if (!rc) s->hg_alpha = info->alpha;
     } else if (d_h != s->d_h) {
       (void)hipFree(d_h);  // (nothing was queued: the object keeps the h it had)
     }
