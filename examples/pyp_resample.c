@@ -40,10 +40,14 @@
  *      each with weights of its own under a shared root, and stb_tindic_sample_hgroups takes stb_tindic_sample_h's place
  *      (auxiliary tables, the root, the concentration alpha from a Gamma(1.1, 20) prior, then every group's h, one call);
  *      each iteration prints alpha and the largest |sum_k h_gk - 1| over the restaurants from one read-back of h.
+ *  14. with -C (needs -d -z -w) every iteration also prints the collapsed log joint (stb_tindic_logjoint_collapsed): the base
+ *      weights and every dish's class distribution summed out, so the figure is finite however small the drawn weights
+ *      are and comparable between runs.  With -H it is the grouped model's, with log p(root | gamma = 1) and the
+ *      concentration the step left; without, the flat model's with gamma = 1.  beta = 0.5 as the draws'.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C]
  */
 #include <math.h>
 #include <stdio.h>
@@ -64,10 +68,10 @@ static int cmp_double(const void *x, const void *y) {
 }
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:C")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -84,7 +88,12 @@ int main(int argc, char **argv) {
     else if (c == 'P') predict = 1;
     else if (c == 'B') pergroup = 1;
     else if (c == 'H') hgroups = atoi(optarg);
+    else if (c == 'C') collapsed = 1;
     else return 2;
+  }
+  if (collapsed && !(explicit_d && dishes && redraw)) {
+    fprintf(stderr, "pyp_resample: -C needs -d -z -w\n");
+    return 2;
   }
   if (redraw && !(explicit_d && dishes)) {
     fprintf(stderr, "pyp_resample: -w needs -d -z\n");
@@ -284,6 +293,16 @@ int main(int argc, char **argv) {
           yaps_quit("stb_tindic_heldout: %s\n", stb_last_error());
         if (showlj) printf(" heldout %.6f avg %.6f\n", ho, ho_avg);
         else printf("iteration %d: heldout %.6f avg %.6f\n", it, ho, ho_avg);
+      }
+      if (collapsed) { /* h and the likelihood summed out: alpha 0 is the concentration the -H step left on the object */
+        stb_cj_opts_t co = {0.0, 1.0, 0.5, NULL, NULL};
+        stb_cj_info_t ci;
+        double cj;
+        if (stb_tindic_logjoint_collapsed(ti, a, bp, STB_CJ_INDICATORS | STB_CJ_DATA | (hgroups ? STB_CJ_ROOT : STB_CJ_FLAT), &co,
+                                          &cj, &ci))
+          yaps_quit("stb_tindic_logjoint_collapsed: %s\n", stb_last_error());
+        printf("iteration %d: collapsed log joint %.6f (pairs %.6f, restaurants %.6f, indicators %.6f, tables %.6f, data %.6f, "
+               "root %.6f)\n", it, cj, ci.pairs, ci.restaurants, ci.binom, ci.tables, ci.data, ci.root);
       }
       if (pergroup) { /* the iteration's one read-back: the J concentrations */
         if (stb_tindic_get_bpar(ti, bvec)) yaps_quit("stb_tindic_get_bpar: %s\n", stb_last_error());

@@ -888,6 +888,88 @@ int stb_tcounts_logjoint(stb_tcounts_t *s, double a, const double *bpar, unsigne
 int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total, double *Li_host,
                         stb_logjoint_info_t *info);
 
+/* ---- the log marginal of multinomials under a Dirichlet prior, from a count matrix on the device (dirmult.hip) ----
+ * For a multinomial with counts c_j, weights w_j, W = sum_j w_j and C = sum_j c_j:
+ *     log ml = [lgamma(W) - lgamma(W + C)] + sum_j [lgamma(w_j + c_j) - lgamma(w_j)]
+ * d_cnt is rows x stride uint32, its first cols columns the matrix.  STB_DM_ROWS: every row is a multinomial over its cols
+ * cells, d_w holds cols weights; STB_DM_COLUMNS: every column is a multinomial over its rows cells, d_w holds rows weights.
+ * Operation by operation (FP64, no contraction; dirmult.hip's header has the associations, DESIGN.md section 6 the bar):
+ *     s = d_scale ? *d_scale (a device word) : scale;  w_j = s * d_w[j], one product (s = 1.0 changes no bit); d_w NULL:
+ *     every w is s * w0
+ *     rise(x, m) = log(x + 0.0) + log(x + 1.0) + ... + log(x + (double)(m - 1)), added in that order
+ *     cell term   c = 0: exactly 0.0, nothing evaluated; 1 <= c <= 8: rise(w, c); c > 8: lgamma(w + (double)c) - lgamma(w)
+ *     W           d_w NULL: (double)ncat * (s * w0); else the categories in chunks of 256, a chunk by a fixed tree, the
+ *                 chunk sums in order in double-double
+ *     normaliser  C = 0: 0.0; 1 <= C <= 8: -rise(W, C); else lgamma(W) - lgamma(W + (double)C).  C is a uint64
+ *     a multinomial's value = its cells' sum + its normaliser (d_each: NULL, or one double a multinomial on the device)
+ * Every sum has a fixed association, so no bit depends on the launch geometry (STB_DIRMULT_WAVES = 1, 2, 4 or 8 waves a
+ * workgroup).  info (may be NULL): cells and norms are the two sums over all multinomials, the total their merged sum.
+ *   zero_weight  cells with w = 0 and c = 0: they contribute 0 (an underflowed root coordinate)
+ *   impossible   cells with w = 0 and c > 0: that multinomial's value, `cells` and the total are -inf
+ *   error_word   1: a weight or the device's scale is negative, NaN or infinite; 2: W is not positive and finite.  The call
+ *                then fails after its wait with the outputs undefined.  No input >= 0 and finite ever gives a NaN.
+ * Two launches (the weights; the matrix, whose last workgroup to take a ticket adds the parts: nobody waits), one wait;
+ * *total_host and *info arrive through pinned words.  rows = 0 gives 0.  Refused before anything is queued, with
+ * stb_last_error() set and the outputs untouched: a null d_cnt or total_host; cols = 0 or cols > stride; neither or both
+ * orientation flags, or unknown flags; w0 (d_w NULL) or scale (d_scale NULL) not positive and finite. */
+#define STB_DM_ROWS    1u
+#define STB_DM_COLUMNS 2u
+typedef struct stb_dirmult_info {
+  double cells, norms;              /* sum of the cell terms, sum of the normalisers; total = their sum */
+  uint64_t nonzero, count;          /* cells with c > 0; sum of all c */
+  uint64_t zero_weight, impossible; /* cells with w = 0 and c = 0 (contribute 0); cells with w = 0 and c > 0 */
+  unsigned error_word, reserved;
+} stb_dirmult_info_t;
+int stb_dirmult_logml(const uint32_t *d_cnt, uint64_t rows, unsigned cols, unsigned stride, unsigned flags,
+                      const double *d_w /* or NULL: every weight w0 */, double w0, double scale,
+                      const double *d_scale /* or NULL; a device word that replaces `scale` */,
+                      double *d_each /* NULL, or one double per multinomial */, double *total_host,
+                      stb_dirmult_info_t *info /* or NULL */, void *stream);
+
+/* ---- the collapsed log joint of a table-indicator object: base weights and class distributions summed out ----
+ *     total = pairs + restaurants + binom     stb_tindic_logjoint's components with h absent, bit for bit
+ *           + tables = sum_g log ml(c_g. ; alpha r)   STB_DM_ROWS on c_gk, the tables of group g that serve dish k, counted
+ *                                                     by stb_sample_hgroups' own kernel over the object's ranges (none:
+ *                                                     every restaurant its own group); weights the object's root (none:
+ *                                                     1 / Kmax each) scaled by alpha.  STB_CJ_FLAT: one group over all
+ *                                                     restaurants, weights gamma, scale 1 -- the model of _sample_h
+ *           + data   = sum_k log ml(cnt_.k ; beta)    STB_CJ_DATA: STB_DM_COLUMNS on the (class, dish) counts over the
+ *                                                     matrix's shape, the counts _sample_lik takes
+ *           + root   = lgamma(sum gamma) - sum lgamma(gamma_k) + sum (gamma_k - 1) log(r_k / R)      STB_CJ_ROOT; R = sum r_k
+ *                                                     in k order; cells with r_k = 0 are left out of the last sum and
+ *                                                     counted in root_left_out (one workgroup; dirmult.hip, k_dm_root)
+ * added in that order in plain doubles: -inf when any component is impossible, never NaN.  h and the matrix's values are
+ * not read: the quantity is finite wherever the state is possible, however small alpha r_k or beta are.  The Gamma
+ * hyper-priors of alpha and b are closed-form scalars the caller adds.  opts: alpha > 0, or 0 for the one the last
+ * successful _sample_hgroups left (not read with STB_CJ_FLAT); gamma (read with STB_CJ_FLAT or STB_CJ_ROOT) and beta
+ * (read with STB_CJ_DATA) as a host vector or, when that is NULL, one value for every cell.  Everything is queued on the
+ * object's stream behind its sweeps; nothing per restaurant, group, dish or class crosses to the host; t, T, n, cust, h,
+ * the root and the matrix are not written.  The count matrices come from the buffer cache and go back: G Kmax uint32 --
+ * what _sample_hgroups takes for its c -- and the matrix's shape in uint32.
+ * Refused, with the state, *total and *info as they were: a null object, opts or total; unknown flags; STB_CJ_ROOT with STB_CJ_FLAT; alpha = 0
+ * while the object holds none, alpha not positive and finite; gamma or beta (when read) not positive and finite;
+ * STB_CJ_DATA without classes or a matrix shape, or with more class rows than the matrix has; an object created with
+ * STB_TI_REF_ODDS; the largest K_i outside 1 .. STB_TD_MAXK; a and bpar as _logjoint checks them (STB_BPAR_RESIDENT is
+ * accepted). */
+#define STB_CJ_INDICATORS 1u   /* as STB_LJ_INDICATORS */
+#define STB_CJ_FLAT       2u   /* the model of _sample_h: one multinomial over all restaurants, w = gamma */
+#define STB_CJ_DATA       4u   /* add the classes' term (classes and a matrix shape must be set) */
+#define STB_CJ_ROOT       8u   /* add log p(r | gamma) (not with STB_CJ_FLAT) */
+typedef struct stb_cj_opts {
+  double alpha;                       /* > 0, or 0: the one the last successful _sample_hgroups left */
+  double gamma0, beta0;
+  const double *gamma_host /* Kmax or NULL */, *beta_host /* the matrix's rows or NULL */;
+} stb_cj_opts_t;
+typedef struct stb_cj_info {
+  double pairs, restaurants, binom;   /* stb_tindic_logjoint's, with h absent */
+  double tables, data, root;          /* the two integrated terms; log p(r | gamma) */
+  stb_logjoint_info_t lj;
+  stb_dirmult_info_t dm_tables, dm_data;
+  uint64_t root_left_out;
+} stb_cj_info_t;
+int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const double *bpar, unsigned flags,
+                                  const stb_cj_opts_t *opts, double *total, stb_cj_info_t *info /* or NULL */);
+
 /* ---- the launch geometry of the ticket reductions (for tests) ----
  * stb_sample_logq (k_logq), stb_joint_terms (k_joint_terms) and stb_logjoint (k_logjoint) share one design: workgroups take
  * steps of `chunks` blocks of 256 restaurants grid-stride in x -- step blockIdx.x, then + grid_x, ... -- (k_joint_terms

@@ -108,6 +108,31 @@ class HGroupsInfo(C.Structure):
                 ("reserved", C.c_uint)]
 
 
+DM_ROWS, DM_COLUMNS = 1, 2  # stb_dirmult_logml's orientation: a multinomial a row / a column
+
+
+class DirMultInfo(C.Structure):
+    """stb_dirmult_info_t (include/stb_hip.h)"""
+    _fields_ = [("cells", C.c_double), ("norms", C.c_double), ("nonzero", C.c_uint64), ("count", C.c_uint64),
+                ("zero_weight", C.c_uint64), ("impossible", C.c_uint64), ("error_word", C.c_uint), ("reserved", C.c_uint)]
+
+
+CJ_INDICATORS, CJ_FLAT, CJ_DATA, CJ_ROOT = 1, 2, 4, 8  # stb_tindic_logjoint_collapsed's flags
+
+
+class CJOpts(C.Structure):
+    """stb_cj_opts_t (include/stb_hip.h)"""
+    _fields_ = [("alpha", C.c_double), ("gamma0", C.c_double), ("beta0", C.c_double), ("gamma_host", c_double_p),
+                ("beta_host", c_double_p)]
+
+
+class CJInfo(C.Structure):
+    """stb_cj_info_t (include/stb_hip.h)"""
+    _fields_ = [("pairs", C.c_double), ("restaurants", C.c_double), ("binom", C.c_double), ("tables", C.c_double),
+                ("data", C.c_double), ("root", C.c_double), ("lj", LogJointInfo), ("dm_tables", DirMultInfo),
+                ("dm_data", DirMultInfo), ("root_left_out", C.c_uint64)]
+
+
 class JointInfo(C.Structure):
     """stb_joint_info_t (include/stb_hip.h)"""
     _fields_ = [("stages", C.c_int), ("accepted", C.c_int), ("evals", C.c_int), ("stage_pick", C.c_int),
@@ -313,6 +338,8 @@ def lib() -> C.CDLL:
     sig("stb_logjoint", i, [vp, vp, u, u, d, vp, i, vp, vp, vp, vp, vp, u, vp, c_double_p, lji, vp])
     sig("stb_tcounts_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
     sig("stb_tindic_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
+    sig("stb_dirmult_logml", i, [vp, u64, u, u, u, vp, d, d, vp, vp, c_double_p, C.POINTER(DirMultInfo), vp])
+    sig("stb_tindic_logjoint_collapsed", i, [vp, d, c_double_p, u, C.POINTER(CJOpts), c_double_p, C.POINTER(CJInfo)])
     sig("stb_reduce_geometry", i, [i, u64, i, i, i, C.POINTER(ReduceGeom)])
     # ---- what a state predicts: dish proportions and held-out customers
     pri = C.POINTER(PredictInfo)
@@ -987,6 +1014,31 @@ def lik_loglik(cnt, lik, stream=None):
     return tot.value, imp.value
 
 
+def dirmult_logml(cnt, w, orientation: int = DM_ROWS, cols: int = 0, scale=1.0, want_each: bool = True, stream=None):
+    """stb_dirmult_logml on a device tensor cnt (int32 holding uint32 counts, (rows, stride); cols = 0: stride columns):
+    the log marginal of its rows (DM_ROWS) or columns (DM_COLUMNS) as multinomials under a Dirichlet prior.  w: a float64
+    device tensor of weights (one per column / per row) or a scalar for all of them; scale: a float, or a float64 device
+    tensor of one element.  Returns (total, one value per multinomial as a device tensor or None, DirMultInfo); a call that
+    fails raises StbError with .info set"""
+    torch = _torch()
+    rows, stride = int(cnt.shape[0]), int(cnt.shape[1])
+    cols = int(cols) if cols else stride
+    n_each = rows if orientation == DM_ROWS else cols
+    each = torch.empty(max(n_each, 1), dtype=torch.float64, device=cnt.device) if want_each else None
+    wvec = None if np.ndim(w) == 0 and not hasattr(w, "data_ptr") else w
+    svec = scale if hasattr(scale, "data_ptr") else None
+    tot, info = C.c_double(0.0), DirMultInfo()
+    rc = lib().stb_dirmult_logml(cnt.data_ptr(), rows, cols, stride, int(orientation),
+                                 None if wvec is None else wvec.data_ptr(), 0.0 if wvec is not None else float(w),
+                                 0.0 if svec is not None else float(scale), None if svec is None else svec.data_ptr(),
+                                 None if each is None else each.data_ptr(), C.byref(tot), C.byref(info), stream_ptr(stream))
+    if rc:
+        err = StbError(last_error())
+        err.info = info
+        raise err
+    return tot.value, (None if each is None else each[:n_each]), info
+
+
 def sampleb_device(b, shape, scale, N, T, a, seed: int, sweep: int, loops: int = 1, verbose: int = 0, stream=None):
     """stb_sampleb_device on device tensors N, T (int32 holding uint32 counts).  NaN -> StbError"""
     r = float(lib().stb_sampleb_device(float(b), int(N.shape[0]), float(shape), float(scale), N.data_ptr(), T.data_ptr(),
@@ -1239,6 +1291,20 @@ class TableIndicators(_BGroupsMixin):
         check(self.L.stb_tindic_logjoint(self.h, float(a), dp(bpar), LJ_INDICATORS if indicators else 0, C.byref(tot),
               None if Li is None else dp(Li), C.byref(info)))
         return tot.value, Li, info
+
+    def logjoint_collapsed(self, a, bpar, alpha=0.0, gamma=1.0, beta=1.0, flags: int = 0):
+        """(total, CJInfo): the log joint of the current state with the groups' base weights (and, with CJ_DATA, the dishes'
+        class distributions) summed out, behind the queued sweeps (stb_tindic_logjoint_collapsed).  alpha = 0: the
+        concentration the last sample_hgroups left; gamma (CJ_FLAT, CJ_ROOT) a scalar or one value per dish; beta (CJ_DATA) a
+        scalar or one value per row of the matrix"""
+        bpar = _bpar(bpar, self.I)
+        keep_g, gp, g0 = _prior(gamma, self.maxK)
+        keep_b, bp, b0 = _prior(beta, self.lik_device()[1]) if np.ndim(beta) else (None, None, float(beta))
+        opts = CJOpts(float(alpha), g0, b0, gp, bp)
+        tot, info = C.c_double(0.0), CJInfo()
+        check(self.L.stb_tindic_logjoint_collapsed(self.h, float(a), dp(bpar), int(flags), C.byref(opts), C.byref(tot),
+                                                   C.byref(info)))
+        return tot.value, info
 
     # ---- dishes: customers move between the pairs of their restaurant (stb_tindic_sweep_dishes)
 

@@ -15,5 +15,9 @@ int stb_hg_check_opts(const stb_hgroups_opts_t *opts, unsigned Kmax, const char 
 int stb_hg_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
                   const stb_hgroups_opts_t *opts, double *d_root, double *d_h, double *d_hgrp, uint32_t *d_c, uint32_t *d_m,
                   uint64_t seed, uint64_t sweep, hipStream_t st, stb_hgroups_info_t *info, const char *who, bool *touched);
+// the step's first launch alone: c_gk (d_c[G Kmax]) and C_g (d_Cg[G]) are added to -- the caller zeroes them on st first --
+// by k_hg_count with the geometry stb_hg_sample gives it.  d_goff null: G = I.  Queued on st; no wait
+int stb_hg_count_queue(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
+                       uint32_t *d_c, unsigned long long *d_Cg, hipStream_t st);
 
 #endif

@@ -382,7 +382,7 @@ int stb_hg_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned K
   const uint64_t cap_rows = (uint64_t)32 * cus;
   const unsigned gx_rows = (unsigned)(Gs < cap_rows ? Gs : cap_rows);
   if (parts > 1) HIPCHK(hipMemsetAsync(m, 0, 4 * cells, st));
-  STB_LAUNCH(k_hg_count, dim3(gx_rest), dim3(64 * nw), st, (uint64_t)I, d_koff, d_t, Kmax, (uint64_t)G, d_goff, c, Cg);
+  if (stb_hg_count_queue(I, d_koff, d_t, Kmax, G, d_goff, c, Cg, st)) return 1;
   STB_LAUNCH(k_hg_aux, dim3(cb, gy_aux), dim3(64 * nw), st, Kmax, (uint64_t)G, (const uint32_t *)c, (const double *)d_root,
              opts->alpha, key, twave, parts, m, Mg, s);
   if (touched) *touched = true;
@@ -421,6 +421,18 @@ int stb_hg_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned K
     if (stb_hb_bgroups_answer(1, &bi, who)) return 1;
     if (bi.kept_groups) return stb_fail("%s: the concentration's draw is not a positive finite double; the outputs are undefined", who);
   }
+  return 0;
+}
+
+// k_hg_count as stb_hg_sample launches it, for a caller that wants the counts alone (the collapsed log joint, tindic.hip)
+int stb_hg_count_queue(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
+                       uint32_t *d_c, unsigned long long *d_Cg, hipStream_t st) {
+  const int nwi = stb_env_int("STB_HGROUPS_WAVES", 4);
+  const unsigned nw = nwi == 1 || nwi == 2 || nwi == 4 || nwi == 8 ? (unsigned)nwi : 4u;
+  const uint64_t runs = ((uint64_t)I + HG_RUN - 1) / HG_RUN;
+  STB_LAUNCH(k_hg_count, dim3((unsigned)((runs + nw - 1) / nw)), dim3(64 * nw), st, (uint64_t)I, d_koff, d_t, Kmax, (uint64_t)G,
+             d_goff, d_c, d_Cg);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 

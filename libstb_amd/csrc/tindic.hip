@@ -31,6 +31,7 @@
 #include "tlik.h"
 #include "predict.h"
 #include "hgroups.h"
+#include "dirmult.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
 // ---- lane form -------------------------------------------------------------------------------------------------
@@ -669,11 +670,9 @@ extern "C" int stb_tindic_samplejoint(stb_tindic_t *s, stb_groups_t *g, const st
 // the log joint of the object's state (logjoint.hip), queued behind its sweeps; t and T are not written.  The S cells come
 // from a slab of the object's own with the V table's bounds: taken from the buffer cache on first use, refilled only when
 // the discount changes, given back by stb_tindic_free.
-extern "C" int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total, double *Li_host,
-                                   stb_logjoint_info_t *info) {
-  STB_ENTRY;
-  const char *who = "stb_tindic_logjoint";
-  if (!s) return stb_fail("%s: null object", who);
+// (with_h false: h is left out -- the collapsed joint's base, stb_tindic_logjoint_collapsed)
+static int ti_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned flags, bool with_h, double *total, double *Li_host,
+                       stb_logjoint_info_t *info, const char *who) {
   if (stb_lj_check(a, flags, s->I, who)) return 1;
   if (!bpar) return stb_fail("%s: bpar is required", who);
   if (!total) return stb_fail("%s: total is required", who);
@@ -709,13 +708,21 @@ extern "C" int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar
     rc = stb_fail("%s: out of device memory for %d values", who, s->I);
   if (!rc)
     rc = stb_lj_run(s->d_stab, s->d_sS1, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t,
-                    s->d_T, s->d_h, flags, d_Li, Li_host, total, info, s->st, who);
+                    s->d_T, with_h ? s->d_h : nullptr, flags, d_Li, Li_host, total, info, s->st, who);
   if (d_Li) {
     if (rc) (void)hipStreamSynchronize(s->st);  // (the cache may hand the buffer on at once)
     stb_pool_free(d_Li);
   }
   stb_device_leave(prev);
   return rc;
+}
+
+extern "C" int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total, double *Li_host,
+                                   stb_logjoint_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_logjoint";
+  if (!s) return stb_fail("%s: null object", who);
+  return ti_logjoint(s, a, bpar, flags, true, total, Li_host, info, who);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1212,6 +1219,123 @@ extern "C" int stb_tindic_get_h(stb_tindic_t *s, double *h_out) {
     rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
   stb_device_leave(prev);
   return rc;
+}
+
+// ---- the collapsed log joint: base weights and class distributions summed out (dirmult.hip)
+
+// what the call takes from the buffer cache, given back behind its waits
+struct ti_cj_scratch {
+  void *d = nullptr, *h = nullptr, *h_dev = nullptr, *stage = nullptr;
+  uint32_t *d_cls_cnt = nullptr;
+  hipStream_t st = nullptr;
+  ~ti_cj_scratch() {
+    (void)hipStreamSynchronize(st);  // (the cache may hand the buffers on at once)
+    void *pooled[] = {d, h, stage, d_cls_cnt};
+    for (void *p : pooled)
+      if (p) stb_pool_free(p);
+  }
+};
+
+extern "C" int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const double *bpar, unsigned flags,
+                                             const stb_cj_opts_t *opts, double *total, stb_cj_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_logjoint_collapsed";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!opts) return stb_fail("%s: opts is required", who);
+  if (!total) return stb_fail("%s: total is required", who);
+  if (flags & ~(STB_CJ_INDICATORS | STB_CJ_FLAT | STB_CJ_DATA | STB_CJ_ROOT)) return stb_fail("%s: unknown flags 0x%x", who, flags);
+  const bool flat = (flags & STB_CJ_FLAT) != 0, want_data = (flags & STB_CJ_DATA) != 0, want_root = (flags & STB_CJ_ROOT) != 0;
+  if (flat && want_root) return stb_fail("%s: STB_CJ_ROOT with STB_CJ_FLAT (the flat model has no root)", who);
+  if (s->flags & STB_TI_REF_ODDS_FLAG)
+    return stb_fail("%s: the object was created with STB_TI_REF_ODDS; its sweeps do not leave the law this is the joint of", who);
+  if (ti_hg_maxk(s, who)) return 1;
+  double alpha = 1.0;
+  if (!flat) {
+    alpha = opts->alpha;
+    if (alpha == 0.0) {
+      if (!(s->hg_alpha == s->hg_alpha)) return stb_fail("%s: alpha=0 asks for the object's concentration, and it has none yet", who);
+      alpha = s->hg_alpha;
+    }
+    if (!(alpha > 0.0) || !std::isfinite(alpha)) return stb_fail("%s: alpha=%g (must be > 0 and finite)", who, alpha);
+  }
+  const bool read_gamma = flat || want_root;
+  if (read_gamma && stb_tl_check_prior(opts->gamma_host, s->maxK, opts->gamma0, "gamma", who)) return 1;
+  if (want_data) {
+    if (ti_lik_ready(s, who)) return 1;
+    if (stb_tl_check_prior(opts->beta_host, s->lik_rows, opts->beta0, "beta", who)) return 1;
+  }
+  const unsigned Kmax = s->maxK;
+  const bool gvec = read_gamma && opts->gamma_host, bvec = want_data && opts->beta_host;
+  // the base: a and bpar are checked there, before anything is queued and before *info is written
+  double base = 0.0;
+  stb_logjoint_info_t lj;
+  if (ti_logjoint(s, a, bpar, (flags & STB_CJ_INDICATORS) ? STB_LJ_INDICATORS : 0u, false, &base, nullptr, &lj, who)) return 1;
+  stb_cj_info_t mine;
+  if (!info) info = &mine;
+  memset(info, 0, sizeof(*info));
+  info->lj = lj;
+  info->pairs = info->lj.pairs;
+  info->restaurants = info->lj.restaurants;
+  info->binom = info->lj.binom;
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  {
+    const int G = flat ? 1 : (s->d_hgoff ? s->hg_G : s->I);
+    const size_t Gs = (size_t)G, cells = Gs * Kmax;
+    // scratch.  Zeroed: c[G Kmax], Cg[G].  Then the flat model's one range, gamma[Kmax], beta[rows], the root's two words
+    const size_t up = 255, o_Cg = (4 * cells + up) & ~up, o_go = o_Cg + ((8 * Gs + up) & ~up), o_gam = o_go + 256,
+                 o_beta = o_gam + (gvec ? (8 * (size_t)Kmax + up) & ~up : 0),
+                 o_root = o_beta + (bvec ? (8 * (size_t)s->lik_rows + up) & ~up : 0), bytes = o_root + 256;
+    const size_t stage_bytes = 16 + (gvec ? 8 * (size_t)Kmax : 0) + (bvec ? 8 * (size_t)s->lik_rows : 0);
+    ti_cj_scratch sc;
+    sc.st = s->st;
+    if (stb_pool_malloc(&sc.d, bytes) != hipSuccess || stb_pool_malloc(&sc.h, 256, 1) != hipSuccess ||
+        hipHostGetDevicePointer(&sc.h_dev, sc.h, 0) != hipSuccess || stb_pool_malloc(&sc.stage, stage_bytes, 1) != hipSuccess)
+      rc = stb_fail("%s: out of memory for %zu bytes of scratch", who, bytes);
+    char *d = (char *)sc.d;
+    uint32_t *c = (uint32_t *)d;
+    unsigned long long *Cg = (unsigned long long *)(d + o_Cg);
+    uint64_t *goff1 = (uint64_t *)(d + o_go);
+    double *d_gam = gvec ? (double *)(d + o_gam) : nullptr, *d_beta = bvec ? (double *)(d + o_beta) : nullptr;
+    if (!rc) {  // the host's vectors and the flat range, through one pinned block
+      char *stg = (char *)sc.stage;
+      ((uint64_t *)stg)[0] = 0;
+      ((uint64_t *)stg)[1] = (uint64_t)s->I;
+      if (gvec) memcpy(stg + 16, opts->gamma_host, 8 * (size_t)Kmax);
+      if (bvec) memcpy(stg + 16 + (gvec ? 8 * (size_t)Kmax : 0), opts->beta_host, 8 * (size_t)s->lik_rows);
+      if (hipMemsetAsync(d, 0, o_go, s->st) != hipSuccess ||
+          hipMemcpyAsync(goff1, stg, 16, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+          (gvec && hipMemcpyAsync(d_gam, stg + 16, 8 * (size_t)Kmax, hipMemcpyHostToDevice, s->st) != hipSuccess) ||
+          (bvec && hipMemcpyAsync(d_beta, stg + 16 + (gvec ? 8 * (size_t)Kmax : 0), 8 * (size_t)s->lik_rows, hipMemcpyHostToDevice,
+                                  s->st) != hipSuccess))
+        rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+    }
+    volatile double *h_root = (volatile double *)sc.h;
+    if (!rc && want_root) rc = stb_dm_root_queue(Kmax, s->d_hroot, d_gam, opts->gamma0, (double *)sc.h_dev, s->st);
+    if (!rc)
+      rc = stb_hg_count_queue(s->I, s->d_koff, s->d_t, Kmax, G, flat ? goff1 : s->d_hgoff, c, Cg, s->st);
+    if (!rc) {
+      // flat: w = gamma, scale 1; grouped: w = the root (none: 1 / Kmax each), scale alpha
+      const double *d_w = flat ? d_gam : s->d_hroot;
+      const double w0 = flat ? opts->gamma0 : 1.0 / (double)Kmax;
+      rc = stb_dm_run(c, (uint64_t)G, Kmax, Kmax, STB_DM_ROWS, d_w, w0, alpha, nullptr, nullptr, &info->tables, &info->dm_tables,
+                      s->st, who);
+    }
+    if (!rc && want_root) {  // (the wait above covered the root's launch)
+      info->root = h_root[0];
+      info->root_left_out = ((volatile unsigned long long *)sc.h)[1];
+    }
+    if (!rc && want_data) {
+      rc = ti_count_classes(s, &sc.d_cls_cnt, who);
+      if (!rc)
+        rc = stb_dm_run(sc.d_cls_cnt, (uint64_t)s->lik_rows, s->lik_stride, s->lik_stride, STB_DM_COLUMNS, d_beta, opts->beta0, 1.0,
+                        nullptr, nullptr, &info->data, &info->dm_data, s->st, who);
+    }
+  }
+  stb_device_leave(prev);
+  if (rc) return rc;
+  *total = ((base + info->tables) + info->data) + info->root;
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
