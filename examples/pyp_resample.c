@@ -44,10 +44,15 @@
  *      weights and every dish's class distribution summed out, so the figure is finite however small the drawn weights
  *      are and comparable between runs.  With -H it is the grouped model's, with log p(root | gamma = 1) and the
  *      concentration the step left; without, the flat model's with gamma = 1.  beta = 0.5 as the draws'.
+ *  15. with -K (needs -d -z -w) the two Dirichlet concentrations are no longer constants: after every dish sweep beta, the
+ *      prior of every dish's class distribution, is drawn from its conditional given the (class, dish) counts under a
+ *      Gamma(1.1, 1) prior (stb_tindic_sample_beta) and feeds that iteration's stb_tindic_sample_lik and -C; without -H
+ *      gamma, the prior of the flat base weights, is drawn too, under Gamma(1.1, 10) (stb_tindic_sample_gamma), and feeds
+ *      stb_tindic_sample_h and -C.  Each iteration prints the drawn values.  (Under -H the root's gamma stays 1.)
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K]
  */
 #include <math.h>
 #include <stdio.h>
@@ -68,10 +73,10 @@ static int cmp_double(const void *x, const void *y) {
 }
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, c, j, i, it;
-  double a0 = 0.5, b0 = 10.0;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, c, j, i, it;
+  double a0 = 0.5, b0 = 10.0, beta = 0.5, gam = 1.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:C")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CK")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -89,10 +94,15 @@ int main(int argc, char **argv) {
     else if (c == 'B') pergroup = 1;
     else if (c == 'H') hgroups = atoi(optarg);
     else if (c == 'C') collapsed = 1;
+    else if (c == 'K') drawconc = 1;
     else return 2;
   }
   if (collapsed && !(explicit_d && dishes && redraw)) {
     fprintf(stderr, "pyp_resample: -C needs -d -z -w\n");
+    return 2;
+  }
+  if (drawconc && !(explicit_d && dishes && redraw)) {
+    fprintf(stderr, "pyp_resample: -K needs -d -z -w\n");
     return 2;
   }
   if (redraw && !(explicit_d && dishes)) {
@@ -220,12 +230,27 @@ int main(int argc, char **argv) {
         stb_tdish_info_t di;
         if (stb_tindic_sweep_dishes(ti, a, bp, (uint64_t)seed + 2, (uint64_t)it, 1, &di)) yaps_quit("stb_tindic_sweep_dishes: %s\n", stb_last_error());
         stuck += di.stuck + di.skipped;
+        if (drawconc) { /* the concentrations first, given the counts the sweep left: seeds of their own again */
+          stb_dirconc_info_t ki;
+          if (stb_tindic_sample_beta(ti, NULL, beta, 1.1, 1.0, (uint64_t)seed + 5, (uint64_t)it, &ki))
+            yaps_quit("stb_tindic_sample_beta: %s\n", stb_last_error());
+          beta = ki.s;
+          printf("iteration %d: beta %.6f from %llu customers, %llu auxiliary\n", it, beta, (unsigned long long)ki.count,
+                 (unsigned long long)ki.aux_tables);
+          if (!hgroups) {
+            if (stb_tindic_sample_gamma(ti, NULL, gam, 1.1, 10.0, (uint64_t)seed + 6, (uint64_t)it, &ki))
+              yaps_quit("stb_tindic_sample_gamma: %s\n", stb_last_error());
+            gam = ki.s;
+            printf("iteration %d: gamma %.6f from %llu tables, %llu auxiliary\n", it, gam, (unsigned long long)ki.count,
+                   (unsigned long long)ki.aux_tables);
+          }
+        }
         /* the uncollapsed step: seeds of their own, so neither shares a stream with a sweep or with the other */
         if (redraw && hgroups) { /* alpha: 5 to start with, then what the step before left on the device */
           stb_hgroups_opts_t ho = {it == 0 ? 5.0 : 0.0, 1.0, 1.1, 20.0, NULL, STB_HG_SAMPLE_ALPHA, 0};
           stb_hgroups_info_t hi;
           double worst = 0.0;
-          if (stb_tindic_sample_lik(ti, NULL, 0.5, (uint64_t)seed + 3, (uint64_t)it) ||
+          if (stb_tindic_sample_lik(ti, NULL, beta, (uint64_t)seed + 3, (uint64_t)it) ||
               stb_tindic_sample_hgroups(ti, &ho, (uint64_t)seed + 4, (uint64_t)it, &hi) || stb_tindic_get_h(ti, hflat))
             yaps_quit("stb_tindic_sample_lik / _sample_hgroups: %s\n", stb_last_error());
           for (j = 0; j < J; j++) {
@@ -235,8 +260,8 @@ int main(int argc, char **argv) {
           }
           printf("iteration %d: base weights in %d groups, alpha %.6f, %llu tables, %llu auxiliary, largest |sum h - 1| %.3g\n", it,
                  hgroups, hi.alpha, (unsigned long long)hi.tables, (unsigned long long)hi.aux_tables, worst);
-        } else if (redraw && (stb_tindic_sample_lik(ti, NULL, 0.5, (uint64_t)seed + 3, (uint64_t)it) ||
-                              stb_tindic_sample_h(ti, NULL, 1.0, (uint64_t)seed + 4, (uint64_t)it)))
+        } else if (redraw && (stb_tindic_sample_lik(ti, NULL, beta, (uint64_t)seed + 3, (uint64_t)it) ||
+                              stb_tindic_sample_h(ti, NULL, gam, (uint64_t)seed + 4, (uint64_t)it)))
           yaps_quit("stb_tindic_sample_lik / _sample_h: %s\n", stb_last_error());
       }
       if (stb_tindic_sweep(ti, a, bp, (uint64_t)seed, (uint64_t)it, 1)) yaps_quit("stb_tindic_sweep: %s\n", stb_last_error());
@@ -295,7 +320,7 @@ int main(int argc, char **argv) {
         else printf("iteration %d: heldout %.6f avg %.6f\n", it, ho, ho_avg);
       }
       if (collapsed) { /* h and the likelihood summed out: alpha 0 is the concentration the -H step left on the object */
-        stb_cj_opts_t co = {0.0, 1.0, 0.5, NULL, NULL};
+        stb_cj_opts_t co = {0.0, hgroups ? 1.0 : gam, beta, NULL, NULL};
         stb_cj_info_t ci;
         double cj;
         if (stb_tindic_logjoint_collapsed(ti, a, bp, STB_CJ_INDICATORS | STB_CJ_DATA | (hgroups ? STB_CJ_ROOT : STB_CJ_FLAT), &co,

@@ -970,6 +970,65 @@ typedef struct stb_cj_info {
 int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const double *bpar, unsigned flags,
                                   const stb_cj_opts_t *opts, double *total, stb_cj_info_t *info /* or NULL */);
 
+/* ---- the scale of Dirichlet weights shared by many multinomials, drawn on the device (dirconc.hip) ----
+ * The two Dirichlet hyper-parameters the calls above take from the host -- beta of every dish's class distribution
+ * (stb_sample_lik, STB_CJ_DATA) and gamma of the flat base weights (_sample_h, STB_CJ_FLAT) -- and the alpha of base
+ * weights under a root are all the scale s of weights w_j = s * v_j that many multinomials share.  With the prior
+ * s ~ Gamma(shape, scale) (stb_sample_bgroups' convention: mean shape * scale), V = sum_j v_j, counts c_mu,j and
+ * n_mu = sum_j c_mu,j:
+ *     p(s | c) ~ p(s) prod_mu Gamma(sV) / Gamma(sV + n_mu) prod_j Gamma(s v_j + c_mu,j) / Gamma(s v_j)
+ * d_cnt, rows, cols, stride, flags, d_w and w0 are stb_dirmult_logml's: STB_DM_ROWS a multinomial a row over cols
+ * categories (d_w: cols values), STB_DM_COLUMNS a multinomial a column over rows categories (d_w: rows values); d_w NULL:
+ * every v is w0.  One call is one exact Gibbs step (FP64, no contraction; DESIGN.md section 6 derives it):
+ *   1. n_mu (uint64).  V: stb_dirmult_logml's W with scale 1 -- d_w NULL: (double)ncat * w0; else chunks of 256 by the fixed
+ *      tree, the chunk sums in order in double-double.  A total n_mu above 2^32 - 1 sets error bit 8, and step 2 then
+ *      makes no draw at all: the call fails within milliseconds.
+ *   2. auxiliary tables: w = s * v_j (one product), m_mu,j = [c >= 1] + sum_{i=1}^{c-1} [u_i * (w + (double)i) < w]
+ *      (stb_sample_hgroups' step 2 unchanged); M_mu = sum_j m_mu,j.  Integers: no bit depends on the launch geometry.
+ *   3. B = s * V, scale_B = scale * V (one product each; s ~ Gamma(shape, scale) <=> sV ~ Gamma(shape, scale V)); then
+ *      exactly stb_sample_bgroups with a = 0, a "restaurant" per multinomial (N = n_mu, T = M_mu), one group {0,
+ *      #multinomials}, every b = B, 1/scale = 1.0 / scale_B and seed ^ 0xA54FF53A5F1D36F1 (same sweep), as
+ *      stb_sample_hgroups' step 4; s' = B' / V, one division.
+ * Uniforms: key = mix(seed + (sweep+1) gamma).  Cell e = mu * cols + j for rows (stb_sample_hgroups' g * Kmax + k), j * stride
+ * + mu for columns (stb_sample_lik's w * stride + k); u_i is element i of mix(mix(key + (e+1) gamma) ^ 0x59B1D5A7C3E9F24D).
+ * So STB_DM_ROWS on stb_sample_hgroups' c_gk with v = r, s = alpha gives that call's m and, when r sums to exactly 1.0, its
+ * alpha' to the bit.  No bit of any output depends on STB_DIRCONC_WAVES = 1, 2, 4 or 8 waves a workgroup or on who takes a
+ * cell's draws (STB_DIRCONC_FORM = lane | wave; default: its wave takes a cell with c > 257).  tests/dc_oracle.py replays it.
+ * info (required): s = s'; count = sum n; aux_tables = sum M; nonempty = multinomials with n > 0; zero_weight = cells with
+ * v = 0 and c = 0, which contribute nothing; the error word.  d_m (NULL, or rows x stride uint32: m at the matrix's own
+ * index, 0 in the padding) and d_M (NULL, or one uint32 a multinomial).  All launches are queued back to back on the
+ * stream; one wait, for the pinned words.  A multinomial without counts contributes nothing.
+ * Refused before anything is queued, with stb_last_error() set and the outputs untouched: a null d_cnt or info; cols = 0 or
+ * cols > stride; neither or both orientation flags, or unknown flags; w0 (d_w NULL), s, shape or scale not positive and
+ * finite; rows = 0; more multinomials than an int holds.
+ * Fails after the wait, error word: 1 a v is negative, NaN or infinite; 2 V is not positive and finite; 4 a cell with
+ * v = 0 holds a count; 8 a total above 2^32 - 1; or stb_sample_bgroups' own failures, or an s' that is not a positive
+ * finite double.  info->s is then NaN and d_m, d_M undefined.
+ * Object layer, queued on the object's stream behind its sweeps; t, T, n, cust, h, the root and the matrix are not written:
+ *   stb_tindic_sample_beta   STB_DM_COLUMNS on the (class, dish) counts over the matrix's shape (what _sample_lik takes):
+ *                            beta_w = s * base_w, base_host the matrix's rows values or NULL for 1 each.  A dish without
+ *                            customers contributes nothing.  Refused as _sample_lik refuses (a null object, no classes, no
+ *                            matrix, more class rows than the matrix has, base not positive and finite), and as above
+ *   stb_tindic_sample_gamma  the flat model of _sample_h: STB_DM_ROWS on the one row c_k = sum_i t_ik (stb_sample_hgroups'
+ *                            counting kernel over one range), gamma_k = s * base_k, base_host Kmax values or NULL for 1
+ *                            each.  Refused as _sample_h refuses (STB_TI_REF_ODDS, Kmax outside 1 .. STB_TD_MAXK), and as above
+ * The caller passes s' (times its base) on to _sample_lik, _sample_h and stb_cj_opts_t. */
+typedef struct stb_dirconc_info {
+  double s;                      /* s' (NaN after a failure) */
+  uint64_t count, aux_tables;    /* sum n_mu, sum M_mu */
+  uint64_t nonempty;             /* multinomials with n_mu > 0 */
+  uint64_t zero_weight;          /* cells with v = 0 and c = 0 */
+  unsigned error_word, reserved;
+} stb_dirconc_info_t;
+int stb_sample_dirconc(const uint32_t *d_cnt, uint64_t rows, unsigned cols, unsigned stride, unsigned flags,
+                       const double *d_w /* or NULL: every v is w0 */, double w0, double s, double shape, double scale,
+                       uint32_t *d_m /* rows x stride or NULL */, uint32_t *d_M /* one a multinomial or NULL */, uint64_t seed,
+                       uint64_t sweep, void *stream, stb_dirconc_info_t *info);
+int stb_tindic_sample_beta(stb_tindic_t *s, const double *base_host /* the matrix's rows, or NULL: 1 each */, double s_in,
+                           double shape, double scale, uint64_t seed, uint64_t sweep, stb_dirconc_info_t *info);
+int stb_tindic_sample_gamma(stb_tindic_t *s, const double *base_host /* Kmax, or NULL: 1 each */, double s_in, double shape,
+                            double scale, uint64_t seed, uint64_t sweep, stb_dirconc_info_t *info);
+
 /* ---- the launch geometry of the ticket reductions (for tests) ----
  * stb_sample_logq (k_logq), stb_joint_terms (k_joint_terms) and stb_logjoint (k_logjoint) share one design: workgroups take
  * steps of `chunks` blocks of 256 restaurants grid-stride in x -- step blockIdx.x, then + grid_x, ... -- (k_joint_terms

@@ -117,6 +117,12 @@ class DirMultInfo(C.Structure):
                 ("zero_weight", C.c_uint64), ("impossible", C.c_uint64), ("error_word", C.c_uint), ("reserved", C.c_uint)]
 
 
+class DirConcInfo(C.Structure):
+    """stb_dirconc_info_t (include/stb_hip.h)"""
+    _fields_ = [("s", C.c_double), ("count", C.c_uint64), ("aux_tables", C.c_uint64), ("nonempty", C.c_uint64),
+                ("zero_weight", C.c_uint64), ("error_word", C.c_uint), ("reserved", C.c_uint)]
+
+
 CJ_INDICATORS, CJ_FLAT, CJ_DATA, CJ_ROOT = 1, 2, 4, 8  # stb_tindic_logjoint_collapsed's flags
 
 
@@ -340,6 +346,10 @@ def lib() -> C.CDLL:
     sig("stb_tindic_logjoint", i, [vp, d, c_double_p, u, c_double_p, c_double_p, lji])
     sig("stb_dirmult_logml", i, [vp, u64, u, u, u, vp, d, d, vp, vp, c_double_p, C.POINTER(DirMultInfo), vp])
     sig("stb_tindic_logjoint_collapsed", i, [vp, d, c_double_p, u, C.POINTER(CJOpts), c_double_p, C.POINTER(CJInfo)])
+    dci = C.POINTER(DirConcInfo)
+    sig("stb_sample_dirconc", i, [vp, u64, u, u, u, vp, d, d, d, d, vp, vp, u64, u64, vp, dci])
+    sig("stb_tindic_sample_beta", i, [vp, c_double_p, d, d, d, u64, u64, dci])
+    sig("stb_tindic_sample_gamma", i, [vp, c_double_p, d, d, d, u64, u64, dci])
     sig("stb_reduce_geometry", i, [i, u64, i, i, i, C.POINTER(ReduceGeom)])
     # ---- what a state predicts: dish proportions and held-out customers
     pri = C.POINTER(PredictInfo)
@@ -1039,6 +1049,38 @@ def dirmult_logml(cnt, w, orientation: int = DM_ROWS, cols: int = 0, scale=1.0, 
     return tot.value, (None if each is None else each[:n_each]), info
 
 
+def sample_dirconc(cnt, v, s, shape, scale, seed: int, sweep: int, orientation: int = DM_ROWS, cols: int = 0,
+                   want=("m", "M"), stream=None):
+    """stb_sample_dirconc on a device tensor cnt (int32 holding uint32 counts, (rows, stride); cols = 0: stride columns):
+    one exact Gibbs step of the scale s of the Dirichlet weights s * v its rows (DM_ROWS) or columns (DM_COLUMNS) share
+    as multinomials, under the prior Gamma(shape, scale).  v: a float64 device tensor (one value per column / per row) or
+    a scalar for all.  Returns (s', dict with whichever of m ((rows, stride)) and M (one per multinomial) `want` names,
+    int32 holding uint32, DirConcInfo); a call that fails raises StbError with .info set"""
+    torch = _torch()
+    rows, stride = int(cnt.shape[0]), int(cnt.shape[1])
+    cols = int(cols) if cols else stride
+    nm = rows if orientation == DM_ROWS else cols
+    out = {}
+    if "m" in want:
+        out["m"] = torch.empty((rows, stride), dtype=torch.int32, device=cnt.device)
+    if "M" in want:
+        out["M"] = torch.empty(max(nm, 1), dtype=torch.int32, device=cnt.device)[:nm]
+    vvec = None if np.ndim(v) == 0 and not hasattr(v, "data_ptr") else v
+    ncat = cols if orientation == DM_ROWS else rows
+    if vvec is not None and (vvec.dtype != torch.float64 or vvec.numel() != ncat):
+        raise StbError(f"sample_dirconc: v must be a scalar or {ncat} float64 values on the device")
+    info = DirConcInfo()
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    rc = lib().stb_sample_dirconc(ptr(cnt), rows, cols, stride, int(orientation), None if vvec is None else vvec.data_ptr(),
+                                  0.0 if vvec is not None else float(v), float(s), float(shape), float(scale), ptr(out.get("m")),
+                                  ptr(out.get("M")), seed, sweep, stream_ptr(stream), C.byref(info))
+    if rc:
+        err = StbError(last_error())
+        err.info = info
+        raise err
+    return info.s, out, info
+
+
 def sampleb_device(b, shape, scale, N, T, a, seed: int, sweep: int, loops: int = 1, verbose: int = 0, stream=None):
     """stb_sampleb_device on device tensors N, T (int32 holding uint32 counts).  NaN -> StbError"""
     r = float(lib().stb_sampleb_device(float(b), int(N.shape[0]), float(shape), float(scale), N.data_ptr(), T.data_ptr(),
@@ -1375,6 +1417,28 @@ class TableIndicators(_BGroupsMixin):
         gamma a scalar or one value per dish (the largest K).  Give it another seed than sample_lik"""
         keep, gp, g0 = _prior(gamma, self.maxK)
         check(self.L.stb_tindic_sample_h(self.h, gp, g0, seed, sweep))
+
+    def _sample_conc(self, fn, base, n, s, shape, scale, seed, sweep):
+        keep, bp, _ = _prior(base, n) if base is not None and np.ndim(base) else (None, None, 1.0)
+        info = DirConcInfo()
+        rc = fn(self.h, bp, float(s), float(shape), float(scale), seed, sweep, C.byref(info))
+        if rc:
+            err = StbError(last_error())
+            err.info = info
+            raise err
+        return info
+
+    def sample_beta(self, s, shape, scale, seed: int, sweep: int, base=None):
+        """one exact Gibbs step of the scale of the class distributions' prior beta_w = s * base_w (base: one value per
+        row of the matrix, None: 1 each) under s ~ Gamma(shape, scale), from the (class, dish) counts, behind the queued
+        sweeps (stb_tindic_sample_beta).  Writes nothing of the state; returns DirConcInfo, .s the new scale"""
+        n = self.lik_device()[1] if base is not None and np.ndim(base) else 0
+        return self._sample_conc(self.L.stb_tindic_sample_beta, base, n, s, shape, scale, seed, sweep)
+
+    def sample_gamma(self, s, shape, scale, seed: int, sweep: int, base=None):
+        """the same for the flat base weights' prior gamma_k = s * base_k (base: one value per dish, None: 1 each), from
+        the tables of every dish over all restaurants (stb_tindic_sample_gamma)"""
+        return self._sample_conc(self.L.stb_tindic_sample_gamma, base, self.maxK, s, shape, scale, seed, sweep)
 
     # ---- base weights per group of restaurants under a shared root (stb_tindic_set_hgroups / _set_hroot / _sample_hgroups)
 

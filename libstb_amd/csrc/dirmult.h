@@ -15,5 +15,12 @@ int stb_dm_run(const uint32_t *d_cnt, uint64_t rows, unsigned cols, unsigned str
 // log p(r | gamma) of a root of K <= STB_TD_MAXK cells (d_root NULL: 1 / K each; d_gamma NULL: gamma0 each), queued on st:
 // out_dev[0] the value, out_dev[1] (as uint64) the cells with r_k = 0, which are left out.  No wait
 int stb_dm_root_queue(unsigned K, const double *d_root, const double *d_gamma, double gamma0, double *out_dev, hipStream_t st);
+// k_dm_weights alone with scale 1, queued on st, for a caller that needs the weights' total in dirmult's association
+// (dirconc.hip): ctl is 256 bytes the caller zeroed on st.  Behind the launch its u32 word STB_DM_CTL_ERR holds the error
+// bits (1: a weight is negative, NaN or infinite; 2: the total is not positive and finite) and its doubles STB_DM_CTL_W,
+// STB_DM_CTL_W + 1 the total W and lgamma(W).  No wait
+#define STB_DM_CTL_ERR 16
+#define STB_DM_CTL_W 16
+int stb_dm_weights_queue(const double *d_w, uint64_t ncat, double w0, unsigned *ctl, hipStream_t st);
 
 #endif

@@ -626,6 +626,14 @@ int stb_dm_run(const uint32_t *d_cnt, uint64_t rows, unsigned cols, unsigned str
   return 0;
 }
 
+static_assert(STB_DM_CTL_ERR == DM_CTL_ERR && STB_DM_CTL_W == DM_CTL_W, "dirmult.h describes k_dm_weights' words");
+
+int stb_dm_weights_queue(const double *d_w, uint64_t ncat, double w0, unsigned *ctl, hipStream_t st) {
+  STB_LAUNCH(k_dm_weights, dim3(1), dim3(DM_BLOCK), st, d_w, ncat, w0, 1.0, (const double *)nullptr, ctl);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int stb_dm_root_queue(unsigned K, const double *d_root, const double *d_gamma, double gamma0, double *out_dev, hipStream_t st) {
   const unsigned nw = dm_waves(), cb = (K + 63) / 64;
   STB_LAUNCH(k_dm_root, dim3(1), dim3(64 * (nw < cb ? nw : cb)), st, K, d_root, d_gamma, gamma0, out_dev);

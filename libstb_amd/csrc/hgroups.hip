@@ -41,14 +41,12 @@
 #include "gamma_dev.h"
 #include "hyperb.h"
 #include "hgroups.h"
+#include "hg_cell.h"  // HG_SALT_Y, HG_SALT_A, HG_TWAVE, hg_y, hg_cell: the cell's draw, shared with dirconc.hip
 
 #pragma clang fp contract(off)
 
-#define HG_SALT_Y 0x59B1D5A7C3E9F24Dull  // a cell's Bernoulli substream: mix(key_e ^ HG_SALT_Y)
 #define HG_SALT_R 0x6A09E667F3BCC909ull  // the root's key: mix(key ^ HG_SALT_R)
-#define HG_SALT_A 0xA54FF53A5F1D36F1ull  // the concentration step's seed: seed ^ HG_SALT_A
 #define HG_MAXTHREADS 512
-#define HG_TWAVE 256u  // a cell with more Bernoulli draws than this goes to its wave
 #define HG_RUN 32u     // restaurants a wave counts (or scatters) in a row
 #define HG_KREG (STB_TD_MAXK / 64)
 #define HG_ERR_CAP 1u
@@ -118,11 +116,6 @@ __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_count(uint64_t I, const ui
   hg_flush(acc, tot, g, Kmax, lane, c, Cg);
 }
 
-__device__ __forceinline__ unsigned hg_y(double w, uint64_t ky, uint64_t j) {
-#pragma clang fp contract(off)
-  return hq_unit(ky, j) * (w + (double)j) < w ? 1u : 0u;
-}
-
 // workgroup (x, y): the columns 64 x .. 64 x + 63; its wave v the rows y nw + v, then + gridDim.y nw, ...
 __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_aux(unsigned Kmax, uint64_t G, const uint32_t *c, const double *root,
                                                           double alpha, uint64_t key, unsigned twave, unsigned parts,
@@ -140,23 +133,7 @@ __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_aux(unsigned Kmax, uint64_
     const uint64_t e = g * Kmax + k;
     const unsigned cc = live ? c[e] : 0u;
     const uint64_t ky = stb_mix64(stb_mix64(key + (e + 1) * STB_GAMMA) ^ HG_SALT_Y);
-    unsigned mm = p == 0 && cc >= 1 ? 1u : 0u;
-    const bool big = cc >= 2 && cc - 1 > twave;
-    if (p == 0 && cc >= 2 && !big)
-      for (uint64_t j = 1; j < cc; j++) mm += hg_y(w, ky, j);
-    unsigned long long todo = __ballot(big);
-    while (todo) {  // (uniform over the wave) the cell of lane src, its draws strided over the lanes
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const unsigned cs = __shfl(cc, src, 64);
-      const double ws = __shfl(w, src, 64);
-      const uint64_t kys = (uint64_t)__shfl((unsigned long long)ky, src, 64);
-      unsigned cnt = 0;
-      for (uint64_t j = 1 + 64ull * p + lane; j < cs; j += 64ull * parts) cnt += hg_y(ws, kys, j);
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-      if ((int)lane == src) mm += cnt;
-    }
+    const unsigned mm = hg_cell(cc, w, ky, p, parts, twave, lane);
     if (live) {
       if (parts == 1) m[e] = mm;
       else if (mm) atomicAdd(&m[e], mm);

@@ -20,6 +20,11 @@ int stb_hb_bgroups_queue(double a, double shape, double scale, int I, const uint
                          const uint64_t *d_goff, double *d_bpar, double *d_L, uint32_t *d_Y, uint64_t seed, uint64_t sweep,
                          void *stream, const char *who);
 int stb_hb_bgroups_answer(int G, stb_bgroups_info_t *info, const char *who);
+/* _queue with a = 0 over ranges whose prior's 1/scale is a device word that an earlier launch on `stream` leaves
+ * (dirconc.hip: the scale is a product with a sum formed on the device); every other operation, stream and bit is _queue's */
+int stb_hb_bgroups_queue_dscale(const double *d_inv_scale, double shape, int I, const uint32_t *d_N, const uint32_t *d_T, int G,
+                                const uint64_t *d_goff, double *d_bpar, double *d_L, uint32_t *d_Y, uint64_t seed, uint64_t sweep,
+                                void *stream, const char *who);
 /* frees the calling thread's words and scratch (stb_sampler_cache_clear) */
 void stb_hb_release(void);
 #ifdef __cplusplus

@@ -11,7 +11,8 @@
 //   k_hb_finish      the counts, the error word and (one group) b to pinned words
 // All three are queued back to back on the caller's stream; the call waits once, for the pinned words.  The two halves
 // are also entries of their own (hyperb.h: stb_hb_bgroups_queue, _answer) for a caller that queues the step among
-// launches of its own and waits once for all of them (hgroups.hip).
+// launches of its own and waits once for all of them (hgroups.hip); _queue_dscale is _queue with the prior's 1/scale read
+// from a device word an earlier launch left (dirconc.hip), pass 2 over ranges being the one kernel that reads it.
 //
 // Streams: key = mix(seed + (sweep+1) gamma); restaurant i owns key_i = mix(key + (i+1) gamma).  L_i is hq_draw_L
 // (gamma_dev.h) on key_i unchanged: with every b_i equal it is stb_sample_logq's L to the bit.  The y take the substream
@@ -139,7 +140,9 @@ __device__ __forceinline__ double hb_draw_b(dd_t acc, double inv_scale, double s
   return bad ? NAN : exp(lg - log(rate));
 }
 
-__global__ __launch_bounds__(HB_MAXTHREADS) void k_hb_group_wg(double inv_scale, double shape, const uint64_t *goff,
+// d_inv_scale (may be null): a device word an earlier launch on the stream left, read in place of inv_scale
+__global__ __launch_bounds__(HB_MAXTHREADS) void k_hb_group_wg(double inv_scale, const double *d_inv_scale, double shape,
+                                                               const uint64_t *goff,
                                                                const double *Lv, const uint32_t *Yv, double *bpar,
                                                                double *bgrp, double *rate_out, uint64_t keyG, unsigned *ctl) {
   __shared__ double sblk[HB_ROUND];
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(HB_MAXTHREADS) void k_hb_group_wg(double inv_scale,
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double b = hb_draw_b(acc, inv_scale, shape, s_y, keyG, g, rate_out ? rate_out + g : nullptr);
+    double b = hb_draw_b(acc, d_inv_scale ? *d_inv_scale : inv_scale, shape, s_y, keyG, g, rate_out ? rate_out + g : nullptr);
     bool keep = !(b > 0.0) || !isfinite(b);
     if (keep) {
       atomicAdd(&ctl[2], 1u);
@@ -285,7 +288,7 @@ static int hb_ready(size_t nY, const char *who) {
 static int hb_queue(double a, double shape, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff,
                     const uint32_t *d_T, int G, const uint64_t *d_goff, double *d_bpar, double *d_bgrp, double *d_L,
                     uint32_t *d_Y, double *d_rate, uint64_t seed, uint64_t sweep, void *stream, stb_bgroups_info_t *info,
-                    const char *who, bool *queued) {
+                    const char *who, bool *queued, const double *d_inv_scale = nullptr) {
   *queued = false;
   if (info) {
     info->bad_restaurants = info->kept_groups = 0;
@@ -319,7 +322,7 @@ static int hb_queue(double a, double shape, double scale, int I, const uint32_t 
   STB_LAUNCH(k_hb_rest, dim3((unsigned)((cover + nthr - 1) / nthr)), dim3(nthr), st, a, (uint64_t)I, d_N, d_coff, d_T, (uint64_t)G,
              d_goff, (const double *)d_bpar, d_L, d_Y, key, twave, hb.d_ctl);
   if (d_goff)
-    STB_LAUNCH(k_hb_group_wg, dim3((unsigned)G), dim3(nthr2), st, 1.0 / scale, shape, d_goff, (const double *)d_L,
+    STB_LAUNCH(k_hb_group_wg, dim3((unsigned)G), dim3(nthr2), st, 1.0 / scale, d_inv_scale, shape, d_goff, (const double *)d_L,
                (const uint32_t *)d_Y, d_bpar, d_bgrp, d_rate, keyG, hb.d_ctl);
   else
     STB_LAUNCH(k_hb_group_lane, dim3((unsigned)((G + 255) / 256)), dim3(256), st, 1.0 / scale, shape, (uint64_t)G,
@@ -372,6 +375,16 @@ extern "C" int stb_hb_bgroups_queue(double a, double shape, double scale, int I,
   bool queued = false;
   return hb_queue(a, shape, scale, I, d_N, nullptr, d_T, G, d_goff, d_bpar, nullptr, d_L, d_Y, nullptr, seed, sweep, stream,
                   nullptr, who, &queued);
+}
+
+extern "C" int stb_hb_bgroups_queue_dscale(const double *d_inv_scale, double shape, int I, const uint32_t *d_N,
+                                           const uint32_t *d_T, int G, const uint64_t *d_goff, double *d_bpar, double *d_L,
+                                           uint32_t *d_Y, uint64_t seed, uint64_t sweep, void *stream, const char *who) {
+  STB_ENTRY;
+  bool queued = false;
+  if (!d_inv_scale || !d_goff) return stb_fail("%s: the device's 1/scale and the ranges are required", who);
+  return hb_queue(0.0, shape, 1.0, I, d_N, nullptr, d_T, G, d_goff, d_bpar, nullptr, d_L, d_Y, nullptr, seed, sweep, stream, nullptr,
+                  who, &queued, d_inv_scale);
 }
 
 extern "C" int stb_hb_bgroups_answer(int G, stb_bgroups_info_t *info, const char *who) {

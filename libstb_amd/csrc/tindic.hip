@@ -32,6 +32,7 @@
 #include "predict.h"
 #include "hgroups.h"
 #include "dirmult.h"
+#include "dirconc.h"
 
 #define STB_TI_LDS_CAP 4096  // dishes whose t a wave keeps in LDS (8 KB); restaurants with more keep t in global memory
 // ---- lane form -------------------------------------------------------------------------------------------------
@@ -1336,6 +1337,105 @@ extern "C" int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const do
   if (rc) return rc;
   *total = ((base + info->tables) + info->data) + info->root;
   return 0;
+}
+
+// ---- the Dirichlet concentrations beta and gamma drawn on the device (dirconc.hip)
+
+// the checks both draws make of their own arguments, after the object's
+static int ti_dc_args(const double *base_host, uint64_t len, double s_in, double shape, double scale, const stb_dirconc_info_t *info,
+                      const char *who) {
+  if (!info) return stb_fail("%s: info is required", who);
+  if (stb_tl_check_prior(base_host, len, 1.0, "base", who)) return 1;
+  if (!(s_in > 0.0) || !std::isfinite(s_in)) return stb_fail("%s: s_in=%g (must be > 0 and finite)", who, s_in);
+  if (!(shape > 0.0) || !std::isfinite(shape)) return stb_fail("%s: shape=%g (must be > 0 and finite)", who, shape);
+  if (!(scale > 0.0) || !std::isfinite(scale)) return stb_fail("%s: scale=%g (must be > 0 and finite)", who, scale);
+  return 0;
+}
+
+// what the two draws take from the buffer cache, given back behind their waits
+struct ti_dc_scratch {
+  void *d = nullptr, *stage = nullptr;
+  uint32_t *d_cls_cnt = nullptr;
+  hipStream_t st = nullptr;
+  ~ti_dc_scratch() {
+    (void)hipStreamSynchronize(st);  // (the cache may hand the buffers on at once)
+    void *pooled[] = {d, stage, d_cls_cnt};
+    for (void *p : pooled)
+      if (p) stb_pool_free(p);
+  }
+};
+
+// head bytes of device scratch and, behind them, base_host[len] on the device (*d_base; null without a base), staged
+// through a pinned block that holds `head_host` (head bytes, may be null) in front of it
+static int ti_dc_stage(ti_dc_scratch &sc, size_t head, const void *head_host, const double *base_host, size_t len, double **d_base,
+                       const char *who) {
+  const size_t vec = base_host ? 8 * len : 0;
+  if (stb_pool_malloc(&sc.d, head + vec + 256) != hipSuccess || stb_pool_malloc(&sc.stage, head + vec + 256, 1) != hipSuccess)
+    return stb_fail("%s: out of memory for %zu bytes of scratch", who, head + vec + 256);
+  *d_base = base_host ? (double *)((char *)sc.d + head) : nullptr;
+  if (head_host) memcpy(sc.stage, head_host, head);
+  if (base_host) memcpy((char *)sc.stage + head, base_host, vec);
+  if ((head_host && hipMemcpyAsync(sc.d, sc.stage, head, hipMemcpyHostToDevice, sc.st) != hipSuccess) ||
+      (base_host && hipMemcpyAsync(*d_base, (char *)sc.stage + head, vec, hipMemcpyHostToDevice, sc.st) != hipSuccess))
+    return stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+extern "C" int stb_tindic_sample_beta(stb_tindic_t *s, const double *base_host, double s_in, double shape, double scale,
+                                      uint64_t seed, uint64_t sweep, stb_dirconc_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sample_beta";
+  if (!s) return stb_fail("%s: null object", who);
+  if (ti_lik_ready(s, who)) return 1;
+  if (ti_dc_args(base_host, s->lik_rows, s_in, shape, scale, info, who)) return 1;
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  {
+    ti_dc_scratch sc;
+    sc.st = s->st;
+    double *d_base = nullptr;
+    rc = ti_dc_stage(sc, 0, nullptr, base_host, s->lik_rows, &d_base, who);
+    if (!rc) rc = ti_count_classes(s, &sc.d_cls_cnt, who);
+    if (!rc)
+      rc = stb_dc_run(sc.d_cls_cnt, s->lik_rows, s->lik_stride, s->lik_stride, STB_DM_COLUMNS, d_base, 1.0, s_in, shape, scale, nullptr,
+                      nullptr, seed, sweep, s->st, info, who);
+  }
+  stb_device_leave(prev);
+  return rc;
+}
+
+extern "C" int stb_tindic_sample_gamma(stb_tindic_t *s, const double *base_host, double s_in, double shape, double scale,
+                                       uint64_t seed, uint64_t sweep, stb_dirconc_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sample_gamma";
+  if (!s) return stb_fail("%s: null object", who);
+  if (s->flags & STB_TI_REF_ODDS_FLAG)
+    return stb_fail("%s: the object was created with STB_TI_REF_ODDS; its sweeps do not leave the law gamma is drawn under", who);
+  if (ti_hg_maxk(s, who)) return 1;
+  if (ti_dc_args(base_host, s->maxK, s_in, shape, scale, info, who)) return 1;
+  const unsigned Kmax = s->maxK;
+  const int prev = stb_device_enter(s->dev);
+  int rc = 0;
+  {
+    // device scratch: the one range {0, I} (256 bytes), c[Kmax], C (256 bytes), then the base
+    const size_t o_c = 256, o_C = o_c + ((4 * (size_t)Kmax + 255) & ~(size_t)255), head = o_C + 256;
+    ti_dc_scratch sc;
+    sc.st = s->st;
+    double *d_base = nullptr;
+    const uint64_t range[2] = {0, (uint64_t)s->I};
+    std::vector<char> head_host(head, 0);  // (the counts start at zero)
+    memcpy(head_host.data(), range, sizeof(range));
+    rc = ti_dc_stage(sc, head, head_host.data(), base_host, Kmax, &d_base, who);
+    char *d = (char *)sc.d;
+    if (!rc)
+      rc = stb_hg_count_queue(s->I, s->d_koff, s->d_t, Kmax, 1, (const uint64_t *)d, (uint32_t *)(d + o_c),
+                              (unsigned long long *)(d + o_C), s->st);
+    if (!rc)
+      rc = stb_dc_run((const uint32_t *)(d + o_c), 1, Kmax, Kmax, STB_DM_ROWS, d_base, 1.0, s_in, shape, scale, nullptr, nullptr, seed,
+                      sweep, s->st, info, who);
+  }
+  stb_device_leave(prev);
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
