@@ -1,4 +1,4 @@
-// dirconc.h -- private: what the object layer (tindic.hip) needs of dirconc.hip beyond include/stb_hip.h.
+// dirconc.h -- private: what the object layer (tindic_obj.hip) needs of dirconc.hip beyond include/stb_hip.h.
 #ifndef STB_DIRCONC_H
 #define STB_DIRCONC_H
 

@@ -1,4 +1,4 @@
-// dirmult.h -- private: what the object layer (tindic.hip) needs of dirmult.hip beyond include/stb_hip.h.
+// dirmult.h -- private: what the object layer (tindic_obj.hip) needs of dirmult.hip beyond include/stb_hip.h.
 #ifndef STB_DIRMULT_H
 #define STB_DIRMULT_H
 

@@ -6,7 +6,7 @@
 // STB_DM_COLUMNS: every column is a multinomial over its rows cells and the weights run along the rows.  Either way all
 // the multinomials share one weight vector, so W is formed once.  It is the term a collapsed log joint integrates a
 // Dirichlet-distributed vector out with: the groups' base weights over the table counts c_gk (rows), the dishes' class
-// distributions over the (class, dish) counts (columns) -- stb_tindic_logjoint_collapsed (tindic.hip).
+// distributions over the (class, dish) counts (columns) -- stb_tindic_logjoint_collapsed (tindic_obj.hip).
 //
 //   k_dm_weights   one workgroup: W, lgamma(W) and the checks of the weights
 //   k_dm_rows      rows orientation: a workgroup takes blocks of 256 rows grid-stride, a wave one row of the block at a

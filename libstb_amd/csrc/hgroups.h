@@ -1,4 +1,4 @@
-// hgroups.h -- private: what the object layer (tindic.hip) needs of hgroups.hip beyond include/stb_hip.h.
+// hgroups.h -- private: what the object layer (tindic_obj.hip) needs of hgroups.hip beyond include/stb_hip.h.
 #ifndef STB_HGROUPS_H
 #define STB_HGROUPS_H
 

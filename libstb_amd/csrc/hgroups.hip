@@ -401,7 +401,7 @@ int stb_hg_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned K
   return 0;
 }
 
-// k_hg_count as stb_hg_sample launches it, for a caller that wants the counts alone (the collapsed log joint, tindic.hip)
+// k_hg_count as stb_hg_sample launches it, for a caller that wants the counts alone (the collapsed log joint, tindic_obj.hip)
 int stb_hg_count_queue(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
                        uint32_t *d_c, unsigned long long *d_Cg, hipStream_t st) {
   const int nwi = stb_env_int("STB_HGROUPS_WAVES", 4);

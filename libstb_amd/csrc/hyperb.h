@@ -1,4 +1,4 @@
-/* hyperb.h -- private: what the object layers (tcounts.hip, tindic.hip) and the tests need of hyperb.hip beyond
+/* hyperb.h -- private: what the object layers (tcounts.hip, tindic_obj.hip) and the tests need of hyperb.hip beyond
  * include/stb_hip.h. */
 #ifndef STB_HYPERB_H
 #define STB_HYPERB_H

@@ -1,4 +1,4 @@
-/* predict.h -- private: what the object layer (tindic.hip) and the samplers' cache need of predict.hip, beyond
+/* predict.h -- private: what the object layer (tindic_obj.hip) and the samplers' cache need of predict.hip, beyond
  * include/stb_hip.h. */
 #ifndef STB_PREDICT_H
 #define STB_PREDICT_H

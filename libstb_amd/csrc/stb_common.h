@@ -58,6 +58,16 @@ struct stb_rand_guard {
 };
 #define STB_ENTRY stb_rand_guard stb_rand_guard_
 
+// dev current from here to the end of the block (stb_device_enter / stb_device_leave as a scope).  Declare it before any
+// owner of device memory in the same block: that one then goes first, while dev is still current.
+struct stb_device_scope {
+  const int prev;
+  explicit stb_device_scope(int dev) : prev(stb_device_enter(dev)) {}
+  ~stb_device_scope() { stb_device_leave(prev); }
+  stb_device_scope(const stb_device_scope &) = delete;
+  stb_device_scope &operator=(const stb_device_scope &) = delete;
+};
+
 // buffer cache (abi.hip): kind 0 device memory, 1 pinned host memory
 hipError_t stb_pool_malloc(void **out, size_t bytes, int kind = 0);
 bool stb_pool_free(void *p);  // false if p did not come from the cache

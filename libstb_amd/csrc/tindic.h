@@ -1,4 +1,4 @@
-// tindic.h -- what tindic.hip (the indicator sweep) and tdish.hip (the dish sweep) share: the counter-based uniforms, the V
+// tindic.h -- what tindic.hip (the indicator sweep), tdish.hip (the dish sweep) and tindic_obj.hip (the object) share: the counter-based uniforms, the V
 // cell look-up, the two decisions of a visit, and the wave's readlane helpers.  Both kernels evaluate a visit with these
 // functions, so a dish visit whose customer stays in its dish gives the indicator visit's bits.
 #ifndef STB_TINDIC_H
@@ -53,6 +53,11 @@ __device__ __forceinline__ double ti_rld(double v, unsigned j) {
   return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
+// the indicator sweep's launch (tindic.hip): nsweeps sweeps from `sweep` on, cap = dishes a wave keeps in LDS
+int stb_ti_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I, const uint64_t *d_koff,
+                  const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, const uint64_t *d_coff,
+                  const uint32_t *d_cust, unsigned flags, uint64_t seed, uint64_t sweep, int nsweeps, unsigned cap,
+                  hipStream_t st);
 // the dish sweep's launch (tdish.hip): nsweeps sweeps from `sweep` on, cap = dishes a wave holds (the largest K_i, at most
 // STB_TD_MAXK); d_info: two uint64 (skipped, stuck), added to
 int stb_td_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I, const uint64_t *d_koff,

@@ -1,4 +1,4 @@
-// tlik.h -- private: what the object layer (tindic.hip) needs of tlik.hip beyond include/stb_hip.h.  Each call queues its
+// tlik.h -- private: what the object layer (tindic_obj.hip) needs of tlik.hip beyond include/stb_hip.h.  Each call queues its
 // launches on st, waits once and returns 0, or 1 with stb_last_error() set; the arguments are checked by the caller.
 #ifndef STB_TLIK_H
 #define STB_TLIK_H

@@ -327,6 +327,35 @@ def test_objects_without_a_table_read_none(kind):
             obj.free()
 
 
+def test_the_indicator_objects_slab_follows_the_discount():
+    # one object asked at a = 0.3, 0.6 and 0.3 again: every answer is a fresh object's at that discount, bit for bit --
+    # the S slab is refilled when the discount changes, neither kept stale nor taken for another discount's
+    K = np.array([2, 3], dtype=np.int32)
+    n = np.array([6, 1, 4, 2, 5], dtype=np.uint32)
+    t = np.array([2, 1, 3, 1, 2], dtype=np.uint16)
+    h = np.array([0.5, 1.25, 2.0, 0.75, 1.5])
+    bpar = np.array([1.5, 0.25])
+
+    def ask(obj, a):
+        tot, Li, info = obj.logjoint(a, bpar, True)
+        return np.float64(tot).tobytes(), Li.tobytes(), bytes(info)
+
+    one = capi.TableIndicators(K, n, t, h)
+    try:
+        seen = []
+        for a in (0.3, 0.6, 0.3):
+            fresh = capi.TableIndicators(K, n, t, h)
+            try:
+                want = ask(fresh, a)
+            finally:
+                fresh.free()
+            seen.append(ask(one, a))
+            assert seen[-1] == want, a
+        assert seen[0] != seen[1] and seen[0] == seen[2]
+    finally:
+        one.free()
+
+
 # ---- past one trip per workgroup: tiled states, restaurant i of type i mod P_TYPES (the truth once per type)
 
 P_TYPES = 1031  # prime: no two blocks a workgroup takes hold the same restaurants in the same slots

@@ -293,6 +293,28 @@ def test_queued_sweeps_equal_single_calls():
         r.free()
 
 
+def test_dish_sweeps_follow_the_discount():
+    # three dish sweeps at a = 0.2, 0.7 and 0.2 again: each reads the V table of its own discount
+    rng = np.random.default_rng(93)
+    K, n, t, h = random_state(rng, [6] * 50, 30)
+    cust = shuffled_order(rng, K, n)
+    cls = rng.integers(0, 2, size=len(cust)).astype(np.uint32)
+    lik = random_lik(rng, 2, 6)
+    bpar = np.full(50, 3.0)
+    tabs = {a: grown_vtab(a, max_Ni(K, n)) for a in (0.2, 0.7)}
+    ti = capi.TableIndicators(K, n, t, h, cust)
+    try:
+        ti.set_classes(cls, 2)
+        ti.set_lik(lik)
+        for s, a in enumerate((0.2, 0.7, 0.2)):
+            vt, N, M = tabs[a]
+            ti.sweep_dishes(a, bpar, 94, s)
+            n, t, T, cust, _, _ = tdo.sweep(K, n, t, h, a, bpar, vt, N, M, 94, s, cust, cls, lik)
+            assert_state(fetch(ti), (n, t, T, cust))
+    finally:
+        ti.free()
+
+
 def test_dish_and_indicator_sweeps_alternate():
     rng = np.random.default_rng(101)
     K, n, t, h = random_state(rng, [5, 9, 70, 3], 8)

@@ -12,6 +12,7 @@ import pytest
 
 import hq_oracle as hqo
 import lj_oracle as lj
+import ti_oracle as tio
 import tl_oracle as tlo
 from libstb_amd import capi
 
@@ -405,6 +406,32 @@ def test_refusals_leave_the_state():
         ti.free()
         bare.free()
         odd.free()
+
+
+def test_a_refused_draw_leaves_an_object_without_h():
+    c = tlo.H_CASE
+    K, n, t = np.array(c["K"], dtype=np.int32), np.array(c["n"], dtype=np.uint32), np.array(c["t"], dtype=np.uint16)
+    a, bpar = 0.4, np.array([1.5, 0.7, 3.0])
+    v = capi.DeviceVTables(9, 9)  # the object's own bounds: max n = 9
+    v.fill(a)
+    capi.check(capi.lib().stb_fill_status())
+    vt = tio.VTab(v.packed_host(0), 9, 9)
+    ti = capi.TableIndicators(K, n, t)  # created without h
+    try:
+        for gamma in (0.0, math.nan):
+            with pytest.raises(capi.StbError, match="gamma"):
+                ti.sample_h(gamma, c["seed"], c["sweep"])
+        assert np.array_equal(ti.get_h(), np.ones(9))
+        ti.sweep(a, bpar, 11, 0)
+        t1, T1 = tio.sweep(K, n, t, None, a, bpar, vt, 9, 11, 0)  # (h None: every h is 1)
+        got_t, got_T = ti.get()
+        assert np.array_equal(got_t, t1) and np.array_equal(got_T, T1)
+        # a draw that goes through gives the object its h
+        ti.sample_h(c["gamma"], c["seed"], c["sweep"])
+        hk, _ = tlo.sample_h(c["K"], t1, c["gamma"], c["seed"], c["sweep"])
+        assert_replayed(ti.get_h(), tlo.spread_h(c["K"], hk), "h of an object created without one")
+    finally:
+        ti.free()
 
 
 # ---- 9. example ----
