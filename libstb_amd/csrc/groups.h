@@ -158,10 +158,28 @@ __device__ __forceinline__ unsigned stb_block_exclusive_1024(unsigned mine, unsi
 // lists.hip
 int stb_lists_slab_build(stb_groups_t *g, int which, int D, const hb_dot_info &H, const grid_geom &gg);  // 0 built (queued), 1 error, 2 not applicable
 void stb_lists_drop(stb_groups_t *g, bool keep_capacity);   // new pairs or new bounds: what was built from the old ones goes
+void stb_groups_new_pairs(stb_groups_t *g, int reused);     // the set's d_n / d_t hold new pairs
 int stb_groups_set_bounds(stb_groups_t *g, unsigned N, unsigned M);
 int stb_groups_sort_pairs(stb_groups_t *g);                  // groups.hip
 int stb_groups_alloc_dotp(stb_groups_t *g);
 int stb_lists_jobs_device(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *tnw);
 
+// groups.hip: what a resident-count object (stb_tcounts, stb_tindic) shows of itself when it hands its pairs to a set
+struct stb_counts_view {
+  int dev, I;
+  uint64_t G;
+  unsigned maxn, Mdraw;  // the largest n; the column bound the draws are truncated at
+  const uint32_t *d_n, *d_T;
+  const uint16_t *d_t;
+  const double *d_bpar;
+  bool resident;         // d_bpar holds concentrations
+  hipStream_t st;        // the object's stream
+  const char *noun;      // what the messages call the object's state: "counts", "indicators"
+};
+// The pairs and T of `v` into a set of the same shape on the object's device (current), device to device: what
+// stb_groups_update_pairs + stb_groups_update_restaurants do from host arrays.  bpar: null (the set keeps its own),
+// STB_BPAR_RESIDENT (the object's) or I host values.  g->st waits for what the object's stream holds, and the object's
+// later work for the set's copy.  A refusal leaves both as they were.
+int stb_groups_take_counts(stb_groups_t *g, const stb_counts_view &v, const double *bpar, const char *who);
 
 #endif

@@ -74,7 +74,7 @@ static int sort_pairs(uint32_t *d_n, uint16_t *d_t, uint64_t G, hipStream_t st) 
 extern "C" void stb_groups_free(stb_groups_t *g) {
   STB_ENTRY;
   if (!g) return;
-  const int prev_dev = stb_device_enter(g->dev);
+  stb_device_scope dev(g->dev);
   std::vector<void *> ptrs = {g->d_n, g->d_T, g->d_t, g->d_bpar, g->d_tables, g->d_S1, g->d_out, g->d_ws_fill, g->d_ws_sweep, g->d_ws_terms,
                               g->d_cnt, g->d_n2, g->d_t2, g->d_dotp, g->d_slab, g->d_icnt, g->d_ninf, g->d_scan_tmp,
                               g->d_gtab, g->d_dS1g, g->d_gout, g->d_ws_da, g->d_ws_dasweep};
@@ -95,7 +95,6 @@ extern "C" void stb_groups_free(stb_groups_t *g) {
     if (e) (void)hipEventDestroy(e);
   if (g->st) (void)hipStreamDestroy(g->st);
   free(g);
-  stb_device_leave(prev_dev);
 }
 
 #define GCHK(expr)                                                                            \
@@ -313,10 +312,8 @@ int stb_groups_sort_pairs(stb_groups_t *g) {
 extern "C" stb_groups_t *stb_groups_create(int I, const int *K, const uint32_t *T, const uint32_t *nflat,
                                            const uint16_t *tflat, const double *bpar, unsigned N, unsigned M, int Dmax) {
   STB_ENTRY;
-  const int prev_dev = stb_device_enter(stb_get_device());
-  stb_groups_t *g = groups_create_here(I, K, T, nflat, tflat, bpar, N, M, Dmax);
-  stb_device_leave(prev_dev);
-  return g;
+  stb_device_scope dev(stb_get_device());
+  return groups_create_here(I, K, T, nflat, tflat, bpar, N, M, Dmax);
 }
 
 // ---- sparse set-up of the fused evaluation, all on the device -----------------------------------
@@ -1253,14 +1250,13 @@ static int aterms_prepare(stb_groups_t *g, int D, bool allow_fuse, bool *fuse_ou
 static int groups_aterms(stb_groups_t *g, const double *x_host, int D, double *out_host, bool allow_fuse, float *ms_fill,
                          float *ms_sweep, float *ms_terms, bool ssum = false) {
   if (!g) return stb_fail("stb_groups_aterms: null group set");
-  const int prev_dev = stb_device_enter(g->dev);
+  stb_device_scope dev(g->dev);
   bool fuse = false;
   int v = 0;
   int rc = aterms_prepare(g, D, allow_fuse, &fuse, &v);
   if (!rc) rc = aterms_once(g, x_host, D, out_host, fuse, v, ms_fill, ms_sweep, ms_terms, ssum);
   if (rc == 2)  // no waits between workgroups in this form
     rc = aterms_once(g, x_host, D, out_host, false, STB_FILL_PC, ms_fill, ms_sweep, ms_terms, ssum) ? 1 : 0;
-  stb_device_leave(prev_dev);
   return rc;
 }
 
@@ -1272,17 +1268,13 @@ static int groups_aterms(stb_groups_t *g, const double *x_host, int D, double *o
 extern "C" int stb_groups_aterms_async(stb_groups_t *g, const double *x_host, int D, double *out_host, void *stream) {
   STB_ENTRY;
   if (!g) return stb_fail("stb_groups_aterms_async: null group set");
-  const int prev_dev = stb_device_enter(g->dev);
+  stb_device_scope dev(g->dev);
   bool fuse = false;
   int v = 0;
-  int rc = aterms_prepare(g, D, true, &fuse, &v);
-  if (!rc && stream) {
-    if (hipEventRecord(g->ev_dep, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(g->st, g->ev_dep, 0) != hipSuccess)
-      rc = stb_fail("stb_groups_aterms_async: %s", hipGetErrorString(hipGetLastError()));
-  }
-  if (!rc) rc = aterms_issue(g, x_host, D, out_host, fuse, v, false, false);
-  stb_device_leave(prev_dev);
-  return rc;
+  if (aterms_prepare(g, D, true, &fuse, &v)) return 1;
+  if (stream && (hipEventRecord(g->ev_dep, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(g->st, g->ev_dep, 0) != hipSuccess))
+    return stb_fail("stb_groups_aterms_async: %s", hipGetErrorString(hipGetLastError()));
+  return aterms_issue(g, x_host, D, out_host, fuse, v, false, false);
 }
 
 extern "C" int stb_groups_wait(stb_groups_t *g) {
@@ -1292,7 +1284,7 @@ extern "C" int stb_groups_wait(stb_groups_t *g) {
     g->pending = 0;
     return 0;
   }
-  const int prev_dev = stb_device_enter(g->dev);
+  stb_device_scope dev(g->dev);
   double *out = g->pend_out;
   const int D = g->pend_D;
   double x[STB_TERMS_DMAX];
@@ -1309,7 +1301,6 @@ extern "C" int stb_groups_wait(stb_groups_t *g) {
     if (hipMemcpyAsync(user, out, sizeof(double) * D, hipMemcpyHostToDevice, g->st) != hipSuccess || hipStreamSynchronize(g->st) != hipSuccess)
       rc = stb_fail("stb_groups_wait: %s", hipGetErrorString(hipGetLastError()));
   }
-  stb_device_leave(prev_dev);
   return rc;
 }
 
@@ -1321,7 +1312,7 @@ extern "C" int stb_groups_wait(stb_groups_t *g) {
 // d_out.
 static int groups_eval_device(stb_groups_t *g, const double *x_host, int D, double *d_out, void *stream, bool ssum, const char *who) {
   if (!g || !d_out) return stb_fail("%s: null argument", who);
-  const int prev_dev = stb_device_enter(g->dev);
+  stb_device_scope dev(g->dev);
   bool fuse = false;
   int v = 0;
   int rc = aterms_prepare(g, D, true, &fuse, &v);
@@ -1346,7 +1337,6 @@ static int groups_eval_device(stb_groups_t *g, const double *x_host, int D, doub
   }
   if (!rc && (hipEventRecord(g->ev_done, g->st) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, g->ev_done, 0) != hipSuccess))
     rc = stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()));
-  stb_device_leave(prev_dev);
   return rc;
 }
 
@@ -1421,9 +1411,10 @@ extern "C" int stb_groups_create_node(int ndev, int I, const int *K, const uint3
   }
   const int k = ndev < have ? ndev : have;
   for (int s = 0; s < k; s++) {
-    const int prev = stb_device_enter(s);
-    sets_out[s] = groups_create_here(I, K, T, nflat, tflat, bpar, N, M, Dmax);
-    stb_device_leave(prev);
+    {
+      stb_device_scope dev(s);
+      sets_out[s] = groups_create_here(I, K, T, nflat, tflat, bpar, N, M, Dmax);
+    }
     if (!sets_out[s]) {
       char msg[512];
       snprintf(msg, sizeof(msg), "%s", stb_last_error());
@@ -1446,23 +1437,57 @@ extern "C" int stb_groups_update_restaurants(stb_groups_t *g, const uint32_t *T,
   STB_ENTRY;
   if (!g) return stb_fail("stb_groups_update_restaurants: null group set");
   if (g->pending == 1) return stb_fail("stb_groups_update_restaurants: an evaluation queued with stb_groups_aterms_async has not been waited for");
-  const int prev_dev = stb_device_enter(g->dev);
-  int rc = 0;
+  stb_device_scope dev(g->dev);
   g->reused = 1;
-  if (g->I > 0) {
-    // through pinned memory: the caller's arrays are free again on return, and nothing waits for the copy but the
-    // evaluation queued behind it (the wait at the START is for an earlier copy out of the same staging area)
-    if (hipStreamSynchronize(g->st) != hipSuccess) rc = 1;
-    if (!rc) {
-      memcpy(g->h_T, T, sizeof(uint32_t) * (size_t)g->I);
-      memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);
-    }
-    if (rc || hipMemcpyAsync(g->d_T, g->h_T, sizeof(uint32_t) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess ||
-        hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess)
-      rc = stb_fail("stb_groups_update_restaurants: %s", hipGetErrorString(hipGetLastError()));
+  if (g->I <= 0) return 0;
+  // through pinned memory: the caller's arrays are free again on return, and nothing waits for the copy but the
+  // evaluation queued behind it (the wait at the START is for an earlier copy out of the same staging area)
+  if (hipStreamSynchronize(g->st) != hipSuccess) return stb_fail("stb_groups_update_restaurants: %s", hipGetErrorString(hipGetLastError()));
+  memcpy(g->h_T, T, sizeof(uint32_t) * (size_t)g->I);
+  memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);
+  if (hipMemcpyAsync(g->d_T, g->h_T, sizeof(uint32_t) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess ||
+      hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess)
+    return stb_fail("stb_groups_update_restaurants: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+// the hand-over of a resident-count object's pairs, T and (on request) concentrations: groups.h
+int stb_groups_take_counts(stb_groups_t *g, const stb_counts_view &v, const double *bpar, const char *who) {
+  if (g->I != v.I || g->G != v.G)
+    return stb_fail("%s: the group set has I=%d, G=%llu; the %s I=%d, G=%llu", who, g->I, (unsigned long long)g->G, v.noun, v.I,
+                    (unsigned long long)v.G);
+  if (g->dev != v.dev) return stb_fail("%s: the group set is on device %d, the %s on %d", who, g->dev, v.noun, v.dev);
+  if (g->pending == 1) return stb_fail("%s: an evaluation queued with stb_groups_aterms_async has not been waited for", who);
+  if (g->putting) return stb_fail("%s: the group set is between stb_groups_pairs_begin and _commit", who);
+  if (bpar == STB_BPAR_RESIDENT && !v.resident) return stb_fail("%s: STB_BPAR_RESIDENT, but the object holds no concentrations yet", who);
+  // the bounds the new pairs can need, known without looking at them: n up to max n, t up to min(max n, M)
+  unsigned N = g->have_bounds ? g->N : 0, M = g->have_bounds ? g->M : 0;
+  if (N < v.maxn) N = v.maxn;
+  const unsigned tcap = v.maxn < v.Mdraw ? v.maxn : v.Mdraw;
+  if (M < tcap) M = tcap;
+  if (N < 1) N = 1;
+  if (M < 1) M = 1;
+  if (hipStreamSynchronize(g->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  if (stb_groups_set_bounds(g, N, M)) return 1;  // (re-sizes what depends on the bounds when they grow)
+  stb_event_owner ev;
+  if (hipEventCreateWithFlags(&ev.ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev.ev, v.st) != hipSuccess ||
+      hipStreamWaitEvent(g->st, ev.ev, 0) != hipSuccess)
+    return STB_STREAM_FAIL(who);
+  if ((v.G && (hipMemcpyAsync(g->d_n, v.d_n, sizeof(uint32_t) * v.G, hipMemcpyDeviceToDevice, g->st) != hipSuccess ||
+               hipMemcpyAsync(g->d_t, v.d_t, sizeof(uint16_t) * v.G, hipMemcpyDeviceToDevice, g->st) != hipSuccess)) ||
+      hipMemcpyAsync(g->d_T, v.d_T, sizeof(uint32_t) * v.I, hipMemcpyDeviceToDevice, g->st) != hipSuccess)
+    return STB_STREAM_FAIL(who);
+  if (bpar == STB_BPAR_RESIDENT) {  // (g->st waits for the object's stream above)
+    for (int i = 0; i < g->I; i++) g->h_bpar[i] = NAN;  // (the host's copy no longer says what the set holds)
+    if (hipMemcpyAsync(g->d_bpar, v.d_bpar, sizeof(double) * g->I, hipMemcpyDeviceToDevice, g->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  } else if (bpar) {
+    memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);  // (g->st was idle above: its staging area is free)
+    if (hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess) return STB_STREAM_FAIL(who);
   }
-  stb_device_leave(prev_dev);
-  return rc;
+  // the object's later work must not overwrite the pairs before the set has its copy
+  if (hipEventRecord(ev.ev, g->st) != hipSuccess || hipStreamWaitEvent(v.st, ev.ev, 0) != hipSuccess) return STB_STREAM_FAIL(who);
+  stb_groups_new_pairs(g, 1);  // (reused, as stb_groups_update_restaurants marks: a set that serves sweep after sweep)
+  return 0;
 }
 
 extern "C" int stb_groups_last_form(const stb_groups_t *g, int *fused, int *which, int *sparse, int *C_out, int *R_out) {

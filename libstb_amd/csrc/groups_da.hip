@@ -75,10 +75,10 @@ extern "C" int stb_groups_aterms_grad(stb_groups_t *g, const double *x_host, int
     if (!(x_host[d] > 0.0 && x_host[d] < 1.0)) return stb_fail("stb_groups_aterms_grad: discount %g outside (0,1)", x_host[d]);
   double val[STB_TERMS_DMAX], grad[STB_TERMS_DMAX];
   if (stb_groups_aterms(g, x_host, D, val)) return 1;
-  const int prev_dev = stb_device_enter(g->dev);
-  const int rc = grad_here(g, x_host, D, val, grad);
-  stb_device_leave(prev_dev);
-  if (rc) return 1;
+  {
+    stb_device_scope dev(g->dev);
+    if (grad_here(g, x_host, D, val, grad)) return 1;
+  }
   memcpy(val_out, val, sizeof(double) * D);
   memcpy(grad_out, grad, sizeof(double) * D);
   return 0;

@@ -1,4 +1,4 @@
-/* hyperb.h -- private: what the object layers (tcounts.hip, tindic_obj.hip) and the tests need of hyperb.hip beyond
+/* hyperb.h -- private: what the object layers (tcounts_obj.hip, tindic_obj.hip) and the tests need of hyperb.hip beyond
  * include/stb_hip.h. */
 #ifndef STB_HYPERB_H
 #define STB_HYPERB_H
@@ -30,7 +30,11 @@ void stb_hb_release(void);
 #ifdef __cplusplus
 }
 
-/* what an object (stb_tcounts, stb_tindic) keeps for the step: its ranges and the step's L, Y and b_g, on its device */
+#include <vector>
+#include <hip/hip_runtime.h>
+
+/* what an object (stb_tcounts, stb_tindic) keeps for its concentrations d_bpar[I]: the staging of host values on their way
+ * there and what is known of the values it holds; and for the step its ranges and the step's L, Y and b_g, on its device */
 struct stb_hb_obj {
   int G = 0;                  /* groups (0: every restaurant its own) */
   uint64_t *d_goff = nullptr; /* [G + 1], or null */
@@ -39,9 +43,16 @@ struct stb_hb_obj {
   double *d_bgrp = nullptr;   /* [G or I] */
   bool resident = false;      /* the object's d_bpar holds concentrations (an upload, stb_*_set_bpar or a step put them there) */
   double min_b = 0.0;         /* a lower bound of what it holds: the smallest of the last upload, DBL_MIN after a step */
+  double *h_bpar[2] = {nullptr, nullptr};     /* pinned staging of bpar, used in turn: a sweep does not wait for the one before it */
+  hipEvent_t ev_bpar[2] = {nullptr, nullptr}; /* the copy out of h_bpar[k] is through */
+  int slot = 0;
+  std::vector<double> last_bpar;              /* the host values d_bpar holds (empty: nothing yet, or a device step wrote it) */
 };
-/* the staging helpers call this once bpar[I] is on its way to the object's d_bpar */
-void stb_hb_obj_uploaded(stb_hb_obj *o, const double *bpar, int I);
+/* the staging area for I concentrations, once, from the object's create (which releases the object when this fails) */
+int stb_hb_obj_init(stb_hb_obj *o, int I, const char *who);
+/* bpar on the device before what is queued on st next: STB_BPAR_RESIDENT is what d_bpar holds (refused when it holds nothing);
+ * I host values go through the staging buffer used two calls ago (its copy is long through), unchanged ones stay */
+int stb_hb_obj_stage(stb_hb_obj *o, int I, double *d_bpar, const double *bpar, hipStream_t st, const char *who);
 /* STB_BPAR_RESIDENT in a call with discount a: 0 when the object holds concentrations and all are > -a (what the
  * host-side check of a host bpar asks); else 1 with stb_last_error() set */
 int stb_hb_obj_resident(const stb_hb_obj *o, double a, const char *who);

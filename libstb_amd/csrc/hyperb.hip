@@ -248,11 +248,10 @@ static thread_local hb_ctx hb;
 
 static void hb_drop() {
   if (hb.dev < 0) return;
-  const int prev = stb_device_enter(hb.dev);
+  stb_device_scope dev(hb.dev);
   if (hb.d_ctl) stb_pool_free(hb.d_ctl);
   if (hb.h_out) stb_pool_free(hb.h_out);
   if (hb.d_Y) stb_pool_free(hb.d_Y);
-  stb_device_leave(prev);
   hb = hb_ctx();
 }
 
@@ -411,7 +410,19 @@ void stb_hb_obj_release(stb_hb_obj *o) {
   void *dev[] = {o->d_goff, o->d_L, o->d_Y, o->d_bgrp};
   for (void *p : dev)
     if (p) (void)hipFree(p);
+  for (int k = 0; k < 2; k++) {
+    if (o->h_bpar[k]) (void)hipHostFree(o->h_bpar[k]);
+    if (o->ev_bpar[k]) (void)hipEventDestroy(o->ev_bpar[k]);
+  }
   *o = stb_hb_obj();
+}
+
+int stb_hb_obj_init(stb_hb_obj *o, int I, const char *who) {
+  for (int k = 0; k < 2; k++)
+    if (hipHostMalloc((void **)&o->h_bpar[k], sizeof(double) * (size_t)I) != hipSuccess ||
+        hipEventCreateWithFlags(&o->ev_bpar[k], hipEventDisableTiming) != hipSuccess)
+      return STB_STREAM_FAIL(who);
+  return 0;
 }
 
 int stb_hb_obj_set_groups(stb_hb_obj *o, int I, int G, const uint64_t *goff_host, void *stream, const char *who) {
@@ -445,11 +456,23 @@ int stb_hb_obj_set_groups(stb_hb_obj *o, int I, int G, const uint64_t *goff_host
   return 0;
 }
 
-void stb_hb_obj_uploaded(stb_hb_obj *o, const double *bpar, int I) {
+int stb_hb_obj_stage(stb_hb_obj *o, int I, double *d_bpar, const double *bpar, hipStream_t st, const char *who) {
+  if (bpar == STB_BPAR_RESIDENT)  // what the object holds: nothing to upload
+    return o->resident ? 0 : stb_fail("%s: STB_BPAR_RESIDENT, but the object holds no concentrations yet", who);
+  if (o->last_bpar.size() == (size_t)I && memcmp(o->last_bpar.data(), bpar, sizeof(double) * I) == 0) return 0;
+  const int k = o->slot ^= 1;
+  o->last_bpar.clear();
+  if (hipEventSynchronize(o->ev_bpar[k]) != hipSuccess) return STB_STREAM_FAIL(who);
+  memcpy(o->h_bpar[k], bpar, sizeof(double) * I);
+  if (hipMemcpyAsync(d_bpar, o->h_bpar[k], sizeof(double) * I, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipEventRecord(o->ev_bpar[k], st) != hipSuccess)
+    return STB_STREAM_FAIL(who);
+  o->last_bpar.assign(bpar, bpar + I);
   double m = INFINITY;
   for (int i = 0; i < I; i++) m = bpar[i] < m ? bpar[i] : m;
   o->min_b = m;
   o->resident = true;
+  return 0;
 }
 
 int stb_hb_obj_resident(const stb_hb_obj *o, double a, const char *who) {
@@ -463,6 +486,7 @@ int stb_hb_obj_step(stb_hb_obj *o, double a, double shape, double scale, int I, 
                     const uint32_t *d_T, double *d_bpar, uint64_t seed, uint64_t sweep, void *stream, double *bgrp_host,
                     stb_bgroups_info_t *info, const char *who) {
   if (!o->resident) return stb_fail("%s: the object holds no concentrations yet (stb_*_set_bpar, or a call that takes bpar)", who);
+  o->last_bpar.clear();  // (from here on the step can have written d_bpar: the host values no longer describe it)
   const int G = o->d_goff ? o->G : I;
   if ((!o->d_L && hipMalloc((void **)&o->d_L, sizeof(double) * (size_t)I) != hipSuccess) ||
       (!o->d_Y && hipMalloc((void **)&o->d_Y, sizeof(uint32_t) * (size_t)I) != hipSuccess) ||

@@ -1,4 +1,4 @@
-/* hyperj.h -- private: what the object layers (tcounts.hip, tindic_obj.hip) and the samplers' cache need of hyperj.hip,
+/* hyperj.h -- private: what the object layers (tcounts_obj.hip, tindic_obj.hip) and the samplers' cache need of hyperj.hip,
  * beyond include/stb_hip.h. */
 #ifndef STB_HYPERJ_H
 #define STB_HYPERJ_H

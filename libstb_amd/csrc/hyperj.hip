@@ -278,12 +278,11 @@ static thread_local hj_ctx hj;
 
 static void hj_drop() {
   if (hj.dev < 0) return;
-  const int prev = stb_device_enter(hj.dev);
+  stb_device_scope dev(hj.dev);
   if (hj.d_partial) stb_pool_free(hj.d_partial);
   if (hj.d_ctl) stb_pool_free(hj.d_ctl);
   if (hj.d_buf) stb_pool_free(hj.d_buf);
   if (hj.h_out) stb_pool_free(hj.h_out);
-  stb_device_leave(prev);
   hj.dev = -1;
   hj.d_partial = nullptr;
   hj.cap = 0;
@@ -434,7 +433,7 @@ extern "C" int stb_hj_samplejoint(stb_groups_t *g, const uint32_t *d_N, const ui
     if (!(x == y) && !(x != x && y != y))
       return stb_fail("%s: the set's bpar are not all equal (bpar[%d]=%g, bpar[0]=%g): one shared concentration only", who, i, x, y);
   }
-  const int prev_dev = stb_device_enter(g->dev);
+  stb_device_scope dev(g->dev);  // (to the end of the call: what follows the last wait is host arithmetic)
   // (the block sums of the largest grid of this step, before anything is queued: the 1 x 1 calls then never replace them)
   int rc = hj_ready((size_t)(((uint64_t)(g->I > 0 ? g->I : 0) + HJ_CHUNK - 1) / HJ_CHUNK) * D * J, true);
   hipStream_t st = g->st;
@@ -442,7 +441,7 @@ extern "C" int stb_hj_samplejoint(stb_groups_t *g, const uint32_t *d_N, const ui
   const uint64_t key = stb_mix64(o->seed + (o->sweep + 1) * STB_GAMMA);
   double u[6];
   for (int k = 1; k <= 5; k++)  // element k of the sweep's stream (libstb_amd/synth.py: unit(., key)[k])
-    u[k] = (double)(stb_mix64(key + ((uint64_t)k + 1) * STB_GAMMA) >> 11) * (1.0 / 9007199254740992.0);
+    u[k] = stb_unit(key, (uint64_t)k + 1);
   const double beta_in = log(b_in);
   hj_stage S[HJ_STAGES];
   int nst = 0;
@@ -577,7 +576,6 @@ extern "C" int stb_hj_samplejoint(stb_groups_t *g, const uint32_t *d_N, const ui
       }
     }
   }
-  stb_device_leave(prev_dev);
   if (rc) return 1;
   if (info) {
     memset(info, 0, sizeof(*info));

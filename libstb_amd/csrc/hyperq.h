@@ -1,5 +1,5 @@
 /* hyperq.h -- private: what the device b step's host control flow (sampleb.c, C) needs of hyperq.hip and of the
- * object layers (tcounts.hip, tindic_obj.hip), beyond include/stb_hip.h. */
+ * object layers (tcounts_obj.hip, tindic_obj.hip), beyond include/stb_hip.h. */
 #ifndef STB_HYPERQ_H
 #define STB_HYPERQ_H
 #include <stdint.h>

@@ -141,11 +141,10 @@ static thread_local hq_ctx hq;
 
 static void hq_drop() {
   if (hq.dev < 0) return;
-  const int prev = stb_device_enter(hq.dev);
+  stb_device_scope dev(hq.dev);
   if (hq.d_partial) stb_pool_free(hq.d_partial);
   if (hq.d_ctl) stb_pool_free(hq.d_ctl);
   if (hq.h_out) stb_pool_free(hq.h_out);
-  stb_device_leave(prev);
   hq = hq_ctx();
 }
 

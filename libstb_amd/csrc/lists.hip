@@ -328,6 +328,15 @@ void stb_lists_drop(stb_groups_t *g, bool keep_capacity) {
   }
 }
 
+// The set's d_n / d_t hold new pairs (stb_groups_pairs_commit, stb_groups_take_counts): the cell lists are rebuilt and the
+// pairs sorted again on first need.  reused: the caller is one that serves sweep after sweep (stb_groups_update_restaurants)
+void stb_groups_new_pairs(stb_groups_t *g, int reused) {
+  stb_lists_drop(g, true);
+  g->sorted = 0;
+  g->have_pairs = 1;
+  g->reused = reused;
+}
+
 static size_t slab_limit_bytes() { return (size_t)stb_env_int("STB_SLAB_MB", 4096) << 20; }
 
 // Returns 0 with the lists of layout `which` queued on the set's stream (lists_ready set: an evaluation may be queued
@@ -469,20 +478,18 @@ extern "C" int stb_groups_pairs_begin(stb_groups_t *g) {
   STB_ENTRY;
   if (!g) return stb_fail("stb_groups_pairs_begin: null group set");
   if (g->pending == 1) return stb_fail("stb_groups_pairs_begin: an evaluation queued with stb_groups_aterms_async has not been waited for");
-  const int prev = stb_device_enter(g->dev);
-  int rc = 0;
-  // (whatever still reads the device copy of the old pairs, or copies out of the staging area, must be through)
-  if (hipStreamSynchronize(g->st) != hipSuccess) rc = stb_fail("stb_groups_pairs_begin: %s", hipGetErrorString(hipGetLastError()));
-  if (!rc && g->G) {  // (each staging area for itself: one may be there from a call that failed on the other)
-    if ((!g->h_pn && stb_pool_malloc((void **)&g->h_pn, 4 * (size_t)g->G, 1) != hipSuccess) ||
-        (!g->h_pt && stb_pool_malloc((void **)&g->h_pt, 2 * (size_t)g->G, 1) != hipSuccess))
-      rc = stb_fail("stb_groups_pairs_begin: out of pinned host memory");
-  }
+  stb_device_scope dev(g->dev);
   g->put_n = g->flushed_n = 0;
   g->put_maxn = g->put_maxt = 0;
-  g->putting = rc ? 0 : 1;
-  stb_device_leave(prev);
-  return rc;
+  g->putting = 0;
+  // (whatever still reads the device copy of the old pairs, or copies out of the staging area, must be through)
+  if (hipStreamSynchronize(g->st) != hipSuccess) return stb_fail("stb_groups_pairs_begin: %s", hipGetErrorString(hipGetLastError()));
+  // (each staging area for itself: one may be there from a call that failed on the other)
+  if (g->G && ((!g->h_pn && stb_pool_malloc((void **)&g->h_pn, 4 * (size_t)g->G, 1) != hipSuccess) ||
+               (!g->h_pt && stb_pool_malloc((void **)&g->h_pt, 2 * (size_t)g->G, 1) != hipSuccess)))
+    return stb_fail("stb_groups_pairs_begin: out of pinned host memory");
+  g->putting = 1;
+  return 0;
 }
 
 // copy and maxima in one pass (the compiler turns both loops into vector code)
@@ -528,40 +535,32 @@ extern "C" int stb_groups_pairs_put(stb_groups_t *g, const uint32_t *n, const ui
   if (maxn) *maxn = g->put_maxn;
   if (maxt) *maxt = g->put_maxt;
   if (g->put_n - g->flushed_n < STB_PUT_CHUNK) return 0;
-  const int prev = stb_device_enter(g->dev);
-  const int rc = put_flush(g, false);
-  stb_device_leave(prev);
-  return rc;
+  stb_device_scope dev(g->dev);
+  return put_flush(g, false);
 }
 
 extern "C" int stb_groups_pairs_commit(stb_groups_t *g, const uint32_t *T, const double *bpar, unsigned N, unsigned M) {
   STB_ENTRY;
   if (!g || !g->putting) return stb_fail("stb_groups_pairs_commit: stb_groups_pairs_begin comes first");
   if (g->put_n != g->G) return stb_fail("stb_groups_pairs_commit: %llu of the set's %llu pairs supplied", (unsigned long long)g->put_n, (unsigned long long)g->G);
-  const int prev = stb_device_enter(g->dev);
+  stb_device_scope dev(g->dev);
   g->putting = 0;
-  int rc = put_flush(g, true);
-  if (!rc && (N == 0 || M == 0)) {
-    if (!g->have_bounds) rc = stb_fail("stb_groups_pairs_commit: the set has no table bounds yet");
+  if (put_flush(g, true)) return 1;
+  if (N == 0 || M == 0) {
+    if (!g->have_bounds) return stb_fail("stb_groups_pairs_commit: the set has no table bounds yet");
     N = g->N;
     M = g->M;
   }
-  if (!rc) rc = stb_groups_set_bounds(g, N, M);  // (drops what depends on the bounds when they change)
-  if (!rc) {
-    stb_lists_drop(g, true);
-    g->sorted = 0;
-    g->have_pairs = 1;
-    g->reused = 0;
-  }
-  if (!rc && T && bpar && g->I > 0) {
+  if (stb_groups_set_bounds(g, N, M)) return 1;  // (drops what depends on the bounds when they change)
+  stb_groups_new_pairs(g, 0);
+  if (T && bpar && g->I > 0) {
     memcpy(g->h_T, T, sizeof(uint32_t) * (size_t)g->I);
     memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);
     if (hipMemcpyAsync(g->d_T, g->h_T, sizeof(uint32_t) * (size_t)g->I, hipMemcpyHostToDevice, g->st) != hipSuccess ||
         hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * (size_t)g->I, hipMemcpyHostToDevice, g->st) != hipSuccess)
-      rc = stb_fail("stb_groups_pairs_commit: %s", hipGetErrorString(hipGetLastError()));
+      return stb_fail("stb_groups_pairs_commit: %s", hipGetErrorString(hipGetLastError()));
   }
-  stb_device_leave(prev);
-  return rc;
+  return 0;
 }
 
 // ---- a whole set at once, copied by several host threads while the calling thread hands the finished pieces to the
@@ -763,12 +762,10 @@ static int put_all(stb_groups_t *g, int I, const int *K, uint32_t *const *n, uin
     P->cv.notify_all();
   }
   int rc = 0;
-  const int prev = stb_device_enter(g->dev);
-  if (!P) {
-    put_run(&J);  // (the calling thread copies; the pieces go out below)
-  }
-  // hand finished pieces to the stream, in order, while the workers copy
   {
+    stb_device_scope dev(g->dev);
+    if (!P) put_run(&J);  // (the calling thread copies; the pieces go out below)
+    // hand finished pieces to the stream, in order, while the workers copy
     uint64_t flushed = 0;
     int k = 0;
     while (k < J.nslices && !rc) {
@@ -787,7 +784,6 @@ static int put_all(stb_groups_t *g, int I, const int *K, uint32_t *const *n, uin
       }
     }
   }
-  stb_device_leave(prev);
   if (P) {  // (the job lives on this stack: every worker must have let go of it)
     std::unique_lock<std::mutex> lk(P->mu);
     P->job = nullptr;

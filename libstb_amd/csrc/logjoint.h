@@ -1,4 +1,4 @@
-/* logjoint.h -- private: what the object layers (tcounts.hip, tindic_obj.hip) and the samplers' cache need of
+/* logjoint.h -- private: what the object layers (tcounts_obj.hip, tindic_obj.hip) and the samplers' cache need of
  * logjoint.hip, beyond include/stb_hip.h. */
 #ifndef STB_LOGJOINT_H
 #define STB_LOGJOINT_H

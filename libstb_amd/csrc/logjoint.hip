@@ -275,11 +275,10 @@ static thread_local lj_ctx lj;
 
 static void lj_drop() {
   if (lj.dev < 0) return;
-  const int prev = stb_device_enter(lj.dev);
+  stb_device_scope dev(lj.dev);
   if (lj.d_partial) stb_pool_free(lj.d_partial);
   if (lj.d_ctl) stb_pool_free(lj.d_ctl);
   if (lj.h_out) stb_pool_free(lj.h_out);
-  stb_device_leave(prev);
   lj = lj_ctx();
 }
 

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(64 * STB_PT_MAXWAVES) void k_partition(const double
     unsigned Nr = n;
     if (!ref) {
       for (unsigned r = 0; r + 1u < t; r++) {
-        const unsigned l = pt_round(table, S1, M, Nr, t - 1u - r, a, tc_unit(key, g * 65536ull + r + 1u), lane);
+        const unsigned l = pt_round(table, S1, M, Nr, t - 1u - r, a, stb_unit(key, g * 65536ull + r + 1u), lane);
         if (lane == 0) {
           pt_count(lh, cnt, l);
           if (out) out[r] = (uint16_t)l;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(64 * STB_PT_MAXWAVES) void k_partition(const double
     } else {
 #pragma clang fp contract(off)
       const double ptot = pt_S(table, S1, M, n, t);
-      double rem = ptot + log(tc_unit(key, g * 65536ull + 1u));
+      double rem = ptot + log(stb_unit(key, g * 65536ull + 1u));
       for (unsigned Mc = t - 1u; Mc >= 1u; Mc--) {
         double fact = 0.0;
         unsigned l;

@@ -253,11 +253,10 @@ static thread_local pr_ctx pr;
 
 static void pr_drop() {
   if (pr.dev < 0) return;
-  const int prev = stb_device_enter(pr.dev);
+  stb_device_scope dev(pr.dev);
   if (pr.d_partial) stb_pool_free(pr.d_partial);
   if (pr.d_ctl) stb_pool_free(pr.d_ctl);
   if (pr.h_out) stb_pool_free(pr.h_out);
-  stb_device_leave(prev);
   pr = pr_ctx();
 }
 

@@ -11,6 +11,8 @@
 //   fill_rows.hip    k_fill_rows: the reference's own operation order (log domain / V ratios)
 //   sweep_terms.hip  k_lookup, k_to_float, k_sweep_partial, k_terms_partial, reductions
 //   groups.hip       stb_groups_*: device-resident (n,t) pairs and the aterms evaluation
+//   tcounts.hip, tindic.hip, tdish.hip, tcwin.hip, partition.hip   the sampler sweeps' kernels and raw calls
+//   tcounts_obj.hip, tindic_obj.hip   stb_tcounts_* / stb_tindic_*: the resident-count objects, host code only
 //   tools/ablation/ablation.hip   superseded fill forms, in a library of their own (make -C tools/ablation)
 #ifndef STB_COMMON_H
 #define STB_COMMON_H
@@ -67,6 +69,20 @@ struct stb_device_scope {
   stb_device_scope(const stb_device_scope &) = delete;
   stb_device_scope &operator=(const stb_device_scope &) = delete;
 };
+
+// an event made for one call: destroyed when the call ends.  Declared after the call's device scope, as any owner
+struct stb_event_owner {
+  hipEvent_t ev = nullptr;
+  stb_event_owner() {}
+  ~stb_event_owner() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  stb_event_owner(const stb_event_owner &) = delete;
+  stb_event_owner &operator=(const stb_event_owner &) = delete;
+};
+
+// a runtime call on a stream failed: the runtime's words for it, as `who`'s failure
+#define STB_STREAM_FAIL(who) stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()))
 
 // buffer cache (abi.hip): kind 0 device memory, 1 pinned host memory
 hipError_t stb_pool_malloc(void **out, size_t bytes, int kind = 0);

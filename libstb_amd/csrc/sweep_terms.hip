@@ -405,7 +405,7 @@ struct stb_bctx {
 extern "C" void stb_bterms_free(stb_bctx_t *c) {
   STB_ENTRY;
   if (!c) return;
-  const int prev = stb_device_enter(c->dev);
+  stb_device_scope dev(c->dev);
   if (!c->borrowed) {
     (void)hipStreamSynchronize(c->st);
     stb_pool_free(c->d_T);
@@ -413,7 +413,6 @@ extern "C" void stb_bterms_free(stb_bctx_t *c) {
   stb_pool_free(c->d_out);
   stb_pool_free(c->d_ws);
   stb_pool_free(c->h_out);
-  stb_device_leave(prev);
   free(c);
 }
 
@@ -425,7 +424,7 @@ extern "C" stb_bctx_t *stb_bterms_create(const uint32_t *T, int I) {
   }
   stb_bctx_t *c = (stb_bctx_t *)calloc(1, sizeof(*c));
   if (!c) return nullptr;
-  const int prev = stb_device_enter(stb_get_device());
+  stb_device_scope dev(stb_get_device());
   bool ok = hipGetDevice(&c->dev) == hipSuccess;
   c->I = (uint64_t)(I > 0 ? I : 0);
   c->cap = c->I;
@@ -443,11 +442,9 @@ extern "C" stb_bctx_t *stb_bterms_create(const uint32_t *T, int I) {
   if (!ok) {
     const hipError_t e = hipGetLastError();
     stb_fail("stb_bterms_create: %s", e != hipSuccess ? hipGetErrorString(e) : "out of memory");
-    stb_device_leave(prev);
     stb_bterms_free(c);
     return nullptr;
   }
-  stb_device_leave(prev);
   return c;
 }
 
@@ -458,14 +455,12 @@ extern "C" int stb_bterms_update(stb_bctx_t *c, const uint32_t *T, int I) {
   if (!c) return stb_fail("stb_bterms_update: null context");
   if (c->borrowed) return stb_fail("stb_bterms_update: the context borrows its T (stb_bterms_borrow)");
   if (I < 0 || (uint64_t)I > c->cap) return 1;
-  const int prev = stb_device_enter(c->dev);
-  int rc = 0;
+  stb_device_scope dev(c->dev);
   c->I = (uint64_t)I;
   if (I > 0 && (hipMemcpyAsync(c->d_T, T, sizeof(uint32_t) * (size_t)I, hipMemcpyHostToDevice, c->st) != hipSuccess ||
                 hipStreamSynchronize(c->st) != hipSuccess))
-    rc = stb_fail("stb_bterms_update: %s", hipGetErrorString(hipGetLastError()));
-  stb_device_leave(prev);
-  return rc;
+    return STB_STREAM_FAIL("stb_bterms_update");
+  return 0;
 }
 
 // A context over totals that already live on the device: evaluations read d_T in place, queued on `stream` behind
@@ -534,8 +529,7 @@ extern "C" int stb_bterms_eval(stb_bctx_t *c, const double *x_host, int J, doubl
     A.p[j] = lgamma(A.q[j]);                                     // lib/sampleb.c:36
     B.base[j] = -Q * x_host[j] + (shape - 1) * log(x_host[j]);   // lib/sampleb.c:37
   }
-  const int prev = stb_device_enter(c->dev);
-  int rc = 0;
+  stb_device_scope dev(c->dev);
   int nb = terms_blocks(c->I);
   if (nb < 1) nb = 1;
   dd_t *partial = (dd_t *)((char *)c->d_ws + stb_align_up((size_t)STB_TERMS_DMAX * sizeof(double), 256));
@@ -561,12 +555,11 @@ extern "C" int stb_bterms_eval(stb_bctx_t *c, const double *x_host, int J, doubl
   }
   if (spun) {
     out_host[0] = ((volatile double *)c->h_out)[0];
-  } else if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)
-    rc = stb_fail("stb_bterms_eval: %s", hipGetErrorString(hipGetLastError()));
-  else
-    for (int j = 0; j < J; j++) out_host[j] = c->h_out[j];
-  stb_device_leave(prev);
-  return rc;
+    return 0;
+  }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) return STB_STREAM_FAIL("stb_bterms_eval");
+  for (int j = 0; j < J; j++) out_host[j] = c->h_out[j];
+  return 0;
 }
 
 extern "C" int stb_bterms(const double *x_host, int J, double Q, double shape, double apar,
@@ -643,12 +636,11 @@ struct stb_hist {
 extern "C" void stb_hist_free(stb_hist_t *h) {
   STB_ENTRY;
   if (!h) return;
-  const int prev = stb_device_enter(h->dev);
+  stb_device_scope dev(h->dev);
   if (h->st) (void)hipStreamSynchronize(h->st);
   void *ptrs[] = {h->d_cnt, h->d_T, h->d_bpar, h->d_out, h->d_ws, h->d_partial};
   for (void *p : ptrs) stb_pool_free(p);
   if (h->st) (void)hipStreamDestroy(h->st);
-  stb_device_leave(prev);
   free(h);
 }
 
@@ -685,19 +677,16 @@ static stb_hist_t *hist_alloc(unsigned S, int I, const char *who) {
 
 extern "C" stb_hist_t *stb_hist_create(const uint32_t *cnt, unsigned S, int I, const uint32_t *T, const double *bpar) {
   STB_ENTRY;
-  const int prev = stb_device_enter(stb_get_device());
+  stb_device_scope dev(stb_get_device());
   stb_hist_t *h = hist_alloc(S, I, "stb_hist_create");
-  bool ok = h != nullptr;
-  if (ok && S) ok = hipMemcpy(h->d_cnt, cnt, sizeof(uint32_t) * S, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && I > 0)
-    ok = hipMemcpy(h->d_T, T, sizeof(uint32_t) * I, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(h->d_bpar, bpar, sizeof(double) * I, hipMemcpyHostToDevice) == hipSuccess;
-  if (h && !ok) {
-    stb_fail("stb_hist_create: %s", hipGetErrorString(hipGetLastError()));
+  if (!h) return nullptr;
+  if ((S && hipMemcpy(h->d_cnt, cnt, sizeof(uint32_t) * S, hipMemcpyHostToDevice) != hipSuccess) ||
+      (I > 0 && (hipMemcpy(h->d_T, T, sizeof(uint32_t) * I, hipMemcpyHostToDevice) != hipSuccess ||
+                 hipMemcpy(h->d_bpar, bpar, sizeof(double) * I, hipMemcpyHostToDevice) != hipSuccess))) {
+    STB_STREAM_FAIL("stb_hist_create");
     stb_hist_free(h);
-    h = nullptr;
+    return nullptr;
   }
-  stb_device_leave(prev);
   return h;
 }
 
@@ -708,22 +697,18 @@ extern "C" stb_hist_t *stb_hist_create_empty(unsigned S, int I) {
     stb_fail("stb_hist_create_empty: S=%u I=%d (S >= 2, I >= 0)", S, I);
     return nullptr;
   }
-  const int prev = stb_device_enter(stb_get_device());
+  stb_device_scope dev(stb_get_device());
   stb_hist_t *h = hist_alloc(S, I, "stb_hist_create_empty");
-  bool ok = h != nullptr;
-  if (ok) {
-    std::vector<double> ones((size_t)(I > 0 ? I : 1), 1.0);
-    ok = hipMemset(h->d_cnt, 0, sizeof(uint32_t) * S) == hipSuccess &&
-         hipMemset(h->d_T, 0, sizeof(uint32_t) * (I > 0 ? I : 1)) == hipSuccess &&
-         hipMemcpy(h->d_bpar, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipDeviceSynchronize() == hipSuccess;
-    if (!ok) {
-      stb_fail("stb_hist_create_empty: %s", hipGetErrorString(hipGetLastError()));
-      stb_hist_free(h);
-      h = nullptr;
-    }
+  if (!h) return nullptr;
+  std::vector<double> ones((size_t)(I > 0 ? I : 1), 1.0);
+  if (hipMemset(h->d_cnt, 0, sizeof(uint32_t) * S) != hipSuccess ||
+      hipMemset(h->d_T, 0, sizeof(uint32_t) * (I > 0 ? I : 1)) != hipSuccess ||
+      hipMemcpy(h->d_bpar, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) {
+    STB_STREAM_FAIL("stb_hist_create_empty");
+    stb_hist_free(h);
+    return nullptr;
   }
-  stb_device_leave(prev);
   return h;
 }
 
@@ -732,14 +717,12 @@ extern "C" int stb_hist_restaurants(stb_hist_t *h, const uint32_t *T, const doub
   STB_ENTRY;
   if (!h) return stb_fail("stb_hist_restaurants: null histogram");
   if (h->I > 0 && (!T || !bpar)) return stb_fail("stb_hist_restaurants: T and bpar are required");
-  const int prev = stb_device_enter(h->dev);
-  int rc = 0;
+  stb_device_scope dev(h->dev);
   if (hipStreamSynchronize(h->st) != hipSuccess ||
       (h->I > 0 && (hipMemcpy(h->d_T, T, sizeof(uint32_t) * h->I, hipMemcpyHostToDevice) != hipSuccess ||
                     hipMemcpy(h->d_bpar, bpar, sizeof(double) * h->I, hipMemcpyHostToDevice) != hipSuccess)))
-    rc = stb_fail("stb_hist_restaurants: %s", hipGetErrorString(hipGetLastError()));
-  stb_device_leave(prev);
-  return rc;
+    return STB_STREAM_FAIL("stb_hist_restaurants");
+  return 0;
 }
 
 extern "C" uint32_t *stb_hist_counts_device(stb_hist_t *h, unsigned *S, void **stream) {
@@ -756,13 +739,11 @@ extern "C" uint32_t *stb_hist_counts_device(stb_hist_t *h, unsigned *S, void **s
 extern "C" int stb_hist_get(stb_hist_t *h, uint32_t *cnt_out) {
   STB_ENTRY;
   if (!h || !cnt_out) return stb_fail("stb_hist_get: null histogram or output");
-  const int prev = stb_device_enter(h->dev);
-  int rc = 0;
+  stb_device_scope dev(h->dev);
   if (hipMemcpyAsync(cnt_out, h->d_cnt, sizeof(uint32_t) * h->S, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
       hipStreamSynchronize(h->st) != hipSuccess)
-    rc = stb_fail("stb_hist_get: %s", hipGetErrorString(hipGetLastError()));
-  stb_device_leave(prev);
-  return rc;
+    return STB_STREAM_FAIL("stb_hist_get");
+  return 0;
 }
 
 int stb_hist_view_of(stb_hist_t *h, stb_hist_view *v) {
@@ -788,24 +769,17 @@ extern "C" int stb_hist_aterms2(stb_hist_t *h, const double *x_host, int D, doub
     A.par[d] = 1.0 - x_host[d];
     A.lgpar[d] = lgamma(A.par[d]);  // lib/lgamma.c:32
   }
-  const int prev = stb_device_enter(h->dev);
-  int rc = 0;
+  stb_device_scope dev(h->dev);
   double hh[2 * STB_TERMS_DMAX];
-  do {
-    hipLaunchKernelGGL(k_hist_partial, dim3(h->nb, D), dim3(256), 0, h->st, A, h->d_cnt, h->S, h->d_partial, h->nb);
-    hipLaunchKernelGGL(k_reduce_final, dim3(D), dim3(256), 0, h->st, h->d_partial, h->nb, h->d_out, (const double *)nullptr);
-    if ((rc = stb_restaurant_terms(x_host, D, h->d_T, h->d_bpar, (uint64_t)(h->I > 0 ? h->I : 0), h->d_out + STB_TERMS_DMAX,
-                                   h->d_ws, h->ws_bytes, h->st)))
-      break;
-    if (hipMemcpyAsync(hh, h->d_out, sizeof(hh), hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-        hipStreamSynchronize(h->st) != hipSuccess) {
-      rc = stb_fail("stb_hist_aterms2: %s", hipGetErrorString(hipGetLastError()));
-      break;
-    }
-    for (int d = 0; d < D; d++) out_host[d] = hh[STB_TERMS_DMAX + d] + hh[d];
-  } while (0);
-  stb_device_leave(prev);
-  return rc;
+  hipLaunchKernelGGL(k_hist_partial, dim3(h->nb, D), dim3(256), 0, h->st, A, h->d_cnt, h->S, h->d_partial, h->nb);
+  hipLaunchKernelGGL(k_reduce_final, dim3(D), dim3(256), 0, h->st, h->d_partial, h->nb, h->d_out, (const double *)nullptr);
+  if (const int rc = stb_restaurant_terms(x_host, D, h->d_T, h->d_bpar, (uint64_t)(h->I > 0 ? h->I : 0), h->d_out + STB_TERMS_DMAX,
+                                          h->d_ws, h->ws_bytes, h->st))
+    return rc;
+  if (hipMemcpyAsync(hh, h->d_out, sizeof(hh), hipMemcpyDeviceToHost, h->st) != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess)
+    return STB_STREAM_FAIL("stb_hist_aterms2");
+  for (int d = 0; d < D; d++) out_host[d] = hh[STB_TERMS_DMAX + d] + hh[d];
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,21 +1,9 @@
-// tcounts.h -- what the table-count sweeps share: the counter-based uniforms and the S-row read (tcounts.hip,
-// tcwin.hip), and the windowed sweep's launch, which the stb_tcounts_* object of tcounts.hip also drives.
+// tcounts.h -- what the table-count sweeps share: the counter-based uniforms (uniforms.h) and the S-row read (tcounts.hip,
+// tcwin.hip), and the launches that the stb_tcounts_* object of tcounts_obj.hip drives.
 #pragma once
 
 #include "stb_common.h"
-
-static constexpr uint64_t STB_GAMMA = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ static inline uint64_t stb_mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// element j of a sweep's stream (key = mix(seed + (s+1) gamma)): top 53 bits of mix(key + j gamma) / 2^53
-__device__ __forceinline__ double tc_unit(uint64_t key, uint64_t j) {
-  return (double)(stb_mix64(key + j * STB_GAMMA) >> 11) * (1.0 / 9007199254740992.0);
-}
+#include "uniforms.h"
 
 // S_S(n, tau) for 1 <= tau <= min(n, M): dev_S_S of sweep_terms.hip for the cells a draw can address
 // (n <= N: the kernels leave pairs with n > N alone)
@@ -24,6 +12,12 @@ __device__ __forceinline__ double tc_S(const double *row, const double *S1, unsi
   if (tau == 1) return S1[n - 1];
   return row[tau - 2];
 }
+
+// the sweep's launch (tcounts.hip): nsweeps sweeps from `sweep` on, tau_max = the longest tau range a pair can have (sizes
+// the LDS row); the arguments are checked by the caller
+int stb_tc_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
+                  const uint64_t *d_koff, const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, uint64_t seed,
+                  uint64_t sweep, int nsweeps, unsigned tau_max, hipStream_t st);
 
 #define STB_TC_REF_WINDOW_FLAG 1u
 

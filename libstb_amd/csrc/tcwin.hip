@@ -249,7 +249,7 @@ __global__ __launch_bounds__(64 * STB_TCW_MAXWAVES) void k_tcwin(const double *t
         r.cell0 = cell;
         r.lw1 = 0.0;
         r.carry = 0.0;
-        tnew = tcw_visit(r, W, ref, tc_unit(key, 2 * g + 1), tc_unit(key, 2 * g + 2), lane);
+        tnew = tcw_visit(r, W, ref, stb_unit(key, 2 * g + 1), stb_unit(key, 2 * g + 2), lane);
       }
       T = T - p.t + tnew;
       if (tnew != p.t) tv[g] = (uint16_t)tnew;  // (every lane: the same value)

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsi
   const unsigned nblk = (K + 63) / 64;
 
   for (int s = 0; s < nsweeps; s++) {
-    const uint64_t key = ti_mix64(seed + (sweep0 + (uint64_t)s + 1) * TI_GAMMA);
+    const uint64_t key = stb_mix64(seed + (sweep0 + (uint64_t)s + 1) * STB_GAMMA);
     for (uint64_t cb = c0; cb < c1; cb += 64) {
       const unsigned Lc = c1 - cb < 64 ? (unsigned)(c1 - cb) : 64u;
       unsigned mk = 0, mc = 0;  // this lane's customer of the chunk: its dish and class
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsi
         const uint32_t T0 = T;
         unsigned n = n0, t = t0;
         if (n >= 2) {
-          if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
+          if (ti_remove(n, t, stb_unit(key, 2 * c + 1))) t--, T--;
           n--;
         } else {
           n = 0, t = 0, T--;
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsi
           stuck++;
           continue;
         }
-        const double thr = ti_unit(key, 2 * C + 1 + c) * Z;
+        const double thr = stb_unit(key, 2 * C + 1 + c) * Z;
         unsigned ks = 0;
         if (REG) {
           const uint64_t hit = __ballot(((pos >> lane) & 1) && cum > thr);
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsi
           n = 1, t = 1, T++;
         } else {
           n++;
-          if (ti_add(n, t, T, hs, a, b, td_V(vt, N, M, n, t + 1), ti_unit(key, 2 * c + 2), false)) t++, T++;
+          if (ti_add(n, t, T, hs, a, b, td_V(vt, N, M, n, t + 1), stb_unit(key, 2 * c + 2), false)) t++, T++;
         }
         {
           double A, B;

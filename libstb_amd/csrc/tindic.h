@@ -5,21 +5,9 @@
 #define STB_TINDIC_H
 
 #include "stb_common.h"
+#include "uniforms.h"  // u1 of customer c is element j = 2c+1 of the sweep's stream, u2 is j = 2c+2
 
 #define STB_TI_REF_ODDS_FLAG 1u
-
-static constexpr uint64_t TI_GAMMA = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ static inline uint64_t ti_mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// element j of the sweep's stream: u1 of customer c is j = 2c+1, u2 is j = 2c+2
-__device__ __forceinline__ double ti_unit(uint64_t key, uint64_t j) {
-  return (double)(ti_mix64(key + j * TI_GAMMA) >> 11) * (1.0 / 9007199254740992.0);
-}
 
 // V^n_m with stb_lookup_V's semantics for the cells a visit can address (2 <= n <= N): 0 outside 2 <= m <= min(n, M)
 __device__ __forceinline__ double ti_V(const double *vt, unsigned M, unsigned n, unsigned m) {

@@ -37,16 +37,16 @@ __global__ __launch_bounds__(64) void k_tindic_lane(const double *vt, unsigned N
   const double b = bpar[i];
   uint32_t T = Tv[i];
   for (int s = 0; s < nsweeps; s++) {
-    const uint64_t key = ti_mix64(seed + (sweep0 + (uint64_t)s + 1) * TI_GAMMA);
+    const uint64_t key = stb_mix64(seed + (sweep0 + (uint64_t)s + 1) * STB_GAMMA);
     if (cust) {
       for (uint64_t c = c0; c < c1; c++) {  // (t through global memory: this lane's own stores)
         const uint64_t g = k0 + cust[c];
         const unsigned n = nv[g];
         if (n <= 1 || n > N) continue;
         unsigned t = tv[g];
-        if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
+        if (ti_remove(n, t, stb_unit(key, 2 * c + 1))) t--, T--;
         const double h = hv ? hv[g] : 1.0;
-        if (ti_add(n, t, T, h, a, b, ti_V(vt, M, n, t + 1), ti_unit(key, 2 * c + 2), ref)) t++, T++;
+        if (ti_add(n, t, T, h, a, b, ti_V(vt, M, n, t + 1), stb_unit(key, 2 * c + 2), ref)) t++, T++;
         tv[g] = (uint16_t)t;
       }
     } else {  // pair order: a pair's customers are consecutive, its t stays in a register
@@ -61,8 +61,8 @@ __global__ __launch_bounds__(64) void k_tindic_lane(const double *vt, unsigned N
         const unsigned t0 = tv[g];
         unsigned t = t0;
         for (unsigned r = 0; r < n; r++, c++) {
-          if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
-          if (ti_add(n, t, T, h, a, b, ti_V(vt, M, n, t + 1), ti_unit(key, 2 * c + 2), ref)) t++, T++;
+          if (ti_remove(n, t, stb_unit(key, 2 * c + 1))) t--, T--;
+          if (ti_add(n, t, T, h, a, b, ti_V(vt, M, n, t + 1), stb_unit(key, 2 * c + 2), ref)) t++, T++;
         }
         if (t != t0) tv[g] = (uint16_t)t;
       }
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(64) void k_tindic_wave(const double *vt, unsigned N
     for (uint64_t k = lane; k < k1 - k0; k += 64) lt[k] = tv[k0 + k];
   __syncthreads();
   for (int s = 0; s < nsweeps; s++) {
-    const uint64_t key = ti_mix64(seed + (sweep0 + (uint64_t)s + 1) * TI_GAMMA);
+    const uint64_t key = stb_mix64(seed + (sweep0 + (uint64_t)s + 1) * STB_GAMMA);
     if (cust) {
       for (uint64_t cb = c0; cb < c1; cb += 64) {
         const unsigned L = c1 - cb < 64 ? (unsigned)(c1 - cb) : 64u;
@@ -118,11 +118,11 @@ __global__ __launch_bounds__(64) void k_tindic_wave(const double *vt, unsigned N
           const unsigned k = ti_rl(mk, j), t0 = ti_rl(mt0, j);
           const uint64_t c = cb + j;
           unsigned t = inlds ? lt[k] : tv[k0 + k];
-          if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
+          if (ti_remove(n, t, stb_unit(key, 2 * c + 1))) t--, T--;
           const unsigned m = t + 1;
           // (an earlier visit in this chunk may have moved the dish's t out of the prefetched pair: a direct load)
           const double V = m == t0 ? ti_rld(v0, j) : (m == t0 + 1 ? ti_rld(v1, j) : ti_V(vt, M, n, m));
-          if (ti_add(n, t, T, ti_rld(mh, j), a, b, V, ti_unit(key, 2 * c + 2), ref)) t++, T++;
+          if (ti_add(n, t, T, ti_rld(mh, j), a, b, V, stb_unit(key, 2 * c + 2), ref)) t++, T++;
           if (inlds) lt[k] = (uint16_t)t;  // (every lane stores the same value)
           else tv[k0 + k] = (uint16_t)t;
         }
@@ -150,13 +150,13 @@ __global__ __launch_bounds__(64) void k_tindic_wave(const double *vt, unsigned N
           unsigned wb = t0 > 32 ? t0 - 32 : 0;  // the window holds m = wb .. wb+63
           double win = ti_V(vt, M, n, wb + lane);
           for (unsigned r = 0; r < n; r++, c++) {
-            if (ti_remove(n, t, ti_unit(key, 2 * c + 1))) t--, T--;
+            if (ti_remove(n, t, stb_unit(key, 2 * c + 1))) t--, T--;
             const unsigned m = t + 1;
             if (m - wb >= 64u) {
               wb = m > 32 ? m - 32 : 0;
               win = ti_V(vt, M, n, wb + lane);
             }
-            if (ti_add(n, t, T, h, a, b, ti_rld(win, m - wb), ti_unit(key, 2 * c + 2), ref)) t++, T++;
+            if (ti_add(n, t, T, h, a, b, ti_rld(win, m - wb), stb_unit(key, 2 * c + 2), ref)) t++, T++;
           }
           if (t != t0) tv[pb + j] = (uint16_t)t;
         }

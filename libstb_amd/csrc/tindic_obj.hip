@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "stb_common.h"
+#include "pool_scratch.h"
 #include "groups.h"
 #include "hyperq.h"
 #include "hyperb.h"
@@ -48,11 +49,7 @@ struct stb_tindic {
   uint16_t *d_t;
   double *d_h;          // null: every h is 1
   double *d_bpar;
-  double *h_bpar[2];    // pinned staging of bpar, used in turn: a sweep does not wait for the one before it
-  hipEvent_t ev_bpar[2];  // the copy out of h_bpar[k] is through
-  int slot;
-  std::vector<double> last_bpar;  // what d_bpar holds (empty: nothing yet, or a device step wrote it)
-  stb_hb_obj hb;        // the per-group concentration step (hyperb.hip): ranges, L, Y, and whether d_bpar holds anything
+  stb_hb_obj hb;        // d_bpar's staging and what it holds; the per-group concentration step's ranges, L, Y (hyperb.hip)
   // the per-group base weights (hgroups.hip): the ranges, the root and the concentration live with the object
   int hg_G;             // ranges (0: every restaurant its own group)
   uint64_t *d_hgoff;    // [hg_G + 1], or null
@@ -81,8 +78,6 @@ struct stb_tindic {
 
 // ---- the steps the entry points share
 
-#define TI_STREAM_FAIL(who) stb_fail("%s: %s", who, hipGetErrorString(hipGetLastError()))
-
 static int ti_check_h(const double *h, uint64_t G, const char *who) {
   for (uint64_t g = 0; g < G; g++)
     if (!(h[g] > 0.0) || !std::isfinite(h[g])) return stb_fail("%s: h[%llu]=%g (must be > 0 and finite)", who, (unsigned long long)g, h[g]);
@@ -103,39 +98,6 @@ struct ti_bounds {  // what ti_table_bounds returns: the object's fields of thes
   unsigned N, Mdraw;
   bool need_table;
   unsigned M;
-};
-
-// what one call takes from the buffer cache: given back when the call ends, behind a wait for the object's stream (the cache
-// may hand a buffer on at once).  Declared after the call's device scope, so it goes while the object's device is current.
-struct ti_pool_scratch {
-  hipStream_t st;
-  void *p[4] = {nullptr, nullptr, nullptr, nullptr};
-  int n = 0;
-  explicit ti_pool_scratch(hipStream_t st_) : st(st_) {}
-  ti_pool_scratch(const ti_pool_scratch &) = delete;
-  ti_pool_scratch &operator=(const ti_pool_scratch &) = delete;
-  template <class T>
-  hipError_t take(T **out, size_t bytes, int kind = 0) {  // kind as stb_pool_malloc's
-    if (n == 4) return hipErrorOutOfMemory;
-    const hipError_t e = stb_pool_malloc((void **)out, bytes, kind);
-    if (e == hipSuccess) p[n++] = (void *)*out;
-    return e;
-  }
-  // who non-null: a failed wait is the call's failure
-  int give_back(bool wait, const char *who) {
-    int rc = 0;
-    if (n && wait && hipStreamSynchronize(st) != hipSuccess && who) rc = TI_STREAM_FAIL(who);
-    for (int k = 0; k < n; k++) stb_pool_free(p[k]);
-    n = 0;
-    return rc;
-  }
-  // rc of the call's last step, which has waited for its own answer where it succeeded (or, the draw of
-  // stb_tindic_sample_lik, left nothing the host waits for): no second wait then; a failed one waits
-  int last(int rc) {
-    if (!rc) (void)give_back(false, nullptr);
-    return rc;
-  }
-  ~ti_pool_scratch() { (void)give_back(true, nullptr); }
 };
 
 // a device array on its way to the host (ti_fetch)
@@ -171,31 +133,9 @@ static void ti_drop_sslab(stb_tindic_t *s) {
 // device arrays to the host on the object's stream, then a wait (a null destination or an empty array is left out)
 static int ti_fetch(stb_tindic_t *s, std::initializer_list<ti_copy> copies, const char *who) {
   for (const ti_copy &c : copies)
-    if (c.dst && c.bytes && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess) return TI_STREAM_FAIL(who);
-  if (hipStreamSynchronize(s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+    if (c.dst && c.bytes && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  if (hipStreamSynchronize(s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   return 0;
-}
-
-// new concentrations through the staging buffer used two calls ago (its copy is long through); unchanged ones stay
-static int ti_stage_bpar(stb_tindic_t *s, const double *bpar, const char *who) {
-  int rc = 0;
-  if (bpar == STB_BPAR_RESIDENT)  // what the object holds: nothing to upload
-    return s->hb.resident ? 0 : stb_fail("%s: STB_BPAR_RESIDENT, but the object holds no concentrations yet", who);
-  const bool same_b = s->last_bpar.size() == (size_t)s->I && memcmp(s->last_bpar.data(), bpar, sizeof(double) * s->I) == 0;
-  if (!same_b) {
-    const int k = s->slot ^= 1;
-    s->last_bpar.clear();
-    if (hipEventSynchronize(s->ev_bpar[k]) != hipSuccess) rc = TI_STREAM_FAIL(who);
-    if (!rc) {
-      memcpy(s->h_bpar[k], bpar, sizeof(double) * s->I);
-      if (hipMemcpyAsync(s->d_bpar, s->h_bpar[k], sizeof(double) * s->I, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-          hipEventRecord(s->ev_bpar[k], s->st) != hipSuccess)
-        rc = TI_STREAM_FAIL(who);
-    }
-    if (!rc) s->last_bpar.assign(bpar, bpar + s->I);
-    if (!rc) stb_hb_obj_uploaded(&s->hb, bpar, s->I);
-  }
-  return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -209,10 +149,6 @@ static void ti_release(stb_tindic_t *s) {
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (s->h_info) (void)hipHostFree(s->h_info);
-  for (int k = 0; k < 2; k++) {
-    if (s->h_bpar[k]) (void)hipHostFree(s->h_bpar[k]);
-    if (s->ev_bpar[k]) (void)hipEventDestroy(s->ev_bpar[k]);
-  }
   if (s->st) (void)hipStreamDestroy(s->st);
   delete s;
 }
@@ -317,13 +253,10 @@ static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, 
       hipMalloc((void **)&s->d_coff, sizeof(uint64_t) * (I + 1)) != hipSuccess ||
       hipMalloc((void **)&s->d_n, sizeof(uint32_t) * Gs) != hipSuccess || hipMalloc((void **)&s->d_t, sizeof(uint16_t) * Gs) != hipSuccess ||
       hipMalloc((void **)&s->d_T, sizeof(uint32_t) * I) != hipSuccess || hipMalloc((void **)&s->d_bpar, sizeof(double) * I) != hipSuccess ||
-      hipHostMalloc((void **)&s->h_bpar[0], sizeof(double) * I) != hipSuccess ||
-      hipHostMalloc((void **)&s->h_bpar[1], sizeof(double) * I) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_bpar[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_bpar[1], hipEventDisableTiming) != hipSuccess ||
       (hflat && hipMalloc((void **)&s->d_h, sizeof(double) * Gs) != hipSuccess) ||
       (cust && hipMalloc((void **)&s->d_cust, sizeof(uint32_t) * (C ? C : 1)) != hipSuccess))
-    rc = TI_STREAM_FAIL("stb_tindic_create");
+    rc = STB_STREAM_FAIL("stb_tindic_create");
+  if (!rc) rc = stb_hb_obj_init(&s->hb, I, "stb_tindic_create");
   // (no table where no visit reads one: every pair has n <= 1, or M = 1)
   s->vstride = s->need_table ? (stb_vtable_elems(s->N, s->M) + 31) & ~31ull : 0;
   s->ws_bytes = s->need_table ? stb_fill_workspace_bytes(s->N, s->M, 1) : 0;
@@ -337,7 +270,7 @@ static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, 
               hipMemcpy(s->d_T, T.data(), sizeof(uint32_t) * I, hipMemcpyHostToDevice) != hipSuccess ||
               (hflat && G && hipMemcpy(s->d_h, hflat, sizeof(double) * G, hipMemcpyHostToDevice) != hipSuccess) ||
               (cust && C && hipMemcpy(s->d_cust, cust, sizeof(uint32_t) * C, hipMemcpyHostToDevice) != hipSuccess)))
-    rc = TI_STREAM_FAIL("stb_tindic_create");
+    rc = STB_STREAM_FAIL("stb_tindic_create");
   if (rc) {
     ti_release(s);
     return nullptr;
@@ -370,13 +303,13 @@ extern "C" int stb_tindic_set_h(stb_tindic_t *s, const double *hflat) {
   if (!s) return stb_fail("%s: null object", who);
   if (hflat && ti_check_h(hflat, s->G, who)) return 1;
   stb_device_scope dev(s->dev);
-  if (hipStreamSynchronize(s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipStreamSynchronize(s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   if (!hflat && s->d_h) {
     (void)hipFree(s->d_h);
     s->d_h = nullptr;
   } else if (hflat && s->G) {
     if (!s->d_h && hipMalloc((void **)&s->d_h, sizeof(double) * s->G) != hipSuccess) return stb_fail("%s: out of device memory", who);
-    if (hipMemcpy(s->d_h, hflat, sizeof(double) * s->G, hipMemcpyHostToDevice) != hipSuccess) return TI_STREAM_FAIL(who);
+    if (hipMemcpy(s->d_h, hflat, sizeof(double) * s->G, hipMemcpyHostToDevice) != hipSuccess) return STB_STREAM_FAIL(who);
   }
   s->h_bad = false;
   return 0;
@@ -402,7 +335,7 @@ extern "C" int stb_tindic_set_bpar(stb_tindic_t *s, const double *bpar) {
   for (int i = 0; i < s->I; i++)
     if (!std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be finite)", who, i, bpar[i]);
   stb_device_scope dev(s->dev);
-  return ti_stage_bpar(s, bpar, who);
+  return stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who);
 }
 
 extern "C" int stb_tindic_get_bpar(stb_tindic_t *s, double *bpar_out) {
@@ -421,54 +354,13 @@ extern "C" int stb_tindic_get(stb_tindic_t *s, uint16_t *t_out, uint32_t *T_out)
   return ti_fetch(s, {{t_out, s->d_t, sizeof(uint16_t) * s->G}, {T_out, s->d_T, sizeof(uint32_t) * s->I}}, "stb_tindic_get");
 }
 
-// the pairs and T to a group set of the same shape, device to device: what stb_tcounts_to_groups does
+// the pairs and T to a group set of the same shape, device to device (stb_groups_take_counts, groups.hip)
 extern "C" int stb_tindic_to_groups(stb_tindic_t *s, stb_groups_t *g, const double *bpar) {
   STB_ENTRY;
-  const char *who = "stb_tindic_to_groups";
-  if (!s || !g) return stb_fail("%s: null object", who);
-  if (g->I != s->I || g->G != s->G)
-    return stb_fail("%s: the group set has I=%d, G=%llu; the indicators I=%d, G=%llu", who, g->I, (unsigned long long)g->G, s->I,
-                    (unsigned long long)s->G);
-  if (g->dev != s->dev) return stb_fail("%s: the group set is on device %d, the indicators on %d", who, g->dev, s->dev);
-  if (g->pending == 1) return stb_fail("%s: an evaluation queued with stb_groups_aterms_async has not been waited for", who);
-  if (g->putting) return stb_fail("%s: the group set is between stb_groups_pairs_begin and _commit", who);
-  if (bpar == STB_BPAR_RESIDENT && !s->hb.resident) return stb_fail("%s: STB_BPAR_RESIDENT, but the object holds no concentrations yet", who);
+  if (!s || !g) return stb_fail("stb_tindic_to_groups: null object");
+  const stb_counts_view v = {s->dev, s->I, s->G, s->maxn, s->Mdraw, s->d_n, s->d_T, s->d_t, s->d_bpar, s->hb.resident, s->st, "indicators"};
   stb_device_scope dev(s->dev);
-  int rc = 0;
-  // the bounds the new pairs can need, known without looking at them: n up to max n, t up to min(max n, M)
-  unsigned N = g->have_bounds ? g->N : 0, M = g->have_bounds ? g->M : 0;
-  if (N < s->maxn) N = s->maxn;
-  const unsigned tcap = s->maxn < s->Mdraw ? s->maxn : s->Mdraw;
-  if (M < tcap) M = tcap;
-  if (N < 1) N = 1;
-  if (M < 1) M = 1;
-  hipEvent_t ev = nullptr;
-  if (!rc && hipStreamSynchronize(g->st) != hipSuccess) rc = TI_STREAM_FAIL(who);
-  if (!rc) rc = stb_groups_set_bounds(g, N, M);  // (re-sizes what depends on the bounds when they grow)
-  if (!rc && (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, s->st) != hipSuccess ||
-              hipStreamWaitEvent(g->st, ev, 0) != hipSuccess))
-    rc = TI_STREAM_FAIL(who);
-  if (!rc && ((s->G && (hipMemcpyAsync(g->d_n, s->d_n, sizeof(uint32_t) * s->G, hipMemcpyDeviceToDevice, g->st) != hipSuccess ||
-                        hipMemcpyAsync(g->d_t, s->d_t, sizeof(uint16_t) * s->G, hipMemcpyDeviceToDevice, g->st) != hipSuccess)) ||
-              hipMemcpyAsync(g->d_T, s->d_T, sizeof(uint32_t) * s->I, hipMemcpyDeviceToDevice, g->st) != hipSuccess))
-    rc = TI_STREAM_FAIL(who);
-  if (!rc && bpar == STB_BPAR_RESIDENT) {  // (g->st waits for the object's stream above)
-    for (int i = 0; i < g->I; i++) g->h_bpar[i] = NAN;  // (the host's copy no longer says what the set holds)
-    if (hipMemcpyAsync(g->d_bpar, s->d_bpar, sizeof(double) * g->I, hipMemcpyDeviceToDevice, g->st) != hipSuccess) rc = TI_STREAM_FAIL(who);
-  } else if (!rc && bpar) {
-    memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);  // (g->st was idle above: its staging area is free)
-    if (hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * g->I, hipMemcpyHostToDevice, g->st) != hipSuccess) rc = TI_STREAM_FAIL(who);
-  }
-  // later sweeps must not overwrite the pairs before the set has its copy
-  if (!rc && (hipEventRecord(ev, g->st) != hipSuccess || hipStreamWaitEvent(s->st, ev, 0) != hipSuccess)) rc = TI_STREAM_FAIL(who);
-  if (ev) (void)hipEventDestroy(ev);
-  if (!rc) {  // as stb_groups_pairs_commit: new pairs, cell lists rebuilt and the pairs sorted again on first need
-    stb_lists_drop(g, true);
-    g->sorted = 0;
-    g->have_pairs = 1;
-    g->reused = 1;
-  }
-  return rc;
+  return stb_groups_take_counts(g, v, bpar, "stb_tindic_to_groups");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -493,7 +385,7 @@ extern "C" int stb_tindic_sweep(stb_tindic_t *s, double a, const double *bpar, u
   if (ti_check_bpar(s, a, bpar, who)) return 1;
   if (nsweeps == 0) return 0;
   stb_device_scope dev(s->dev);
-  if (ti_ensure_V(s, a) || ti_stage_bpar(s, bpar, who)) return 1;
+  if (ti_ensure_V(s, a) || stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
   return stb_ti_launch(s->d_vt, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T,
                        s->d_h, s->d_coff, s->d_cust, s->flags, seed, sweep, nsweeps, s->maxK, s->st);
 }
@@ -506,16 +398,14 @@ extern "C" int stb_tindic_set_bgroups(stb_tindic_t *s, int G, const uint64_t *go
 }
 
 // the per-group concentration step (hyperb.hip) on the object's T, customer offsets and concentrations, queued behind its
-// sweeps.  The step writes d_bpar: the host copy that spares an upload no longer describes it
+// sweeps
 extern "C" int stb_tindic_sampleb_groups(stb_tindic_t *s, double a, double shape, double scale, uint64_t seed, uint64_t sweep,
                                          double *bgrp_host, stb_bgroups_info_t *info) {
   STB_ENTRY;
   if (!s) return stb_fail("stb_tindic_sampleb_groups: null object");
   stb_device_scope dev(s->dev);
-  const int rc = stb_hb_obj_step(&s->hb, a, shape, scale, s->I, nullptr, s->d_coff, s->d_T, s->d_bpar, seed, sweep, s->st,
-                                 bgrp_host, info, "stb_tindic_sampleb_groups");
-  if (s->hb.resident) s->last_bpar.clear();
-  return rc;
+  return stb_hb_obj_step(&s->hb, a, shape, scale, s->I, nullptr, s->d_coff, s->d_T, s->d_bpar, seed, sweep, s->st, bgrp_host, info,
+                         "stb_tindic_sampleb_groups");
 }
 
 // the concentration step on the object's counts, as stb_tcounts_sampleb: N_i is the customer offsets' difference
@@ -551,7 +441,7 @@ static int ti_materialise_cust(stb_tindic_t *s, const char *who) {
   if (hipStreamSynchronize(s->st) != hipSuccess ||
       (s->G && hipMemcpy(n.data(), s->d_n, sizeof(uint32_t) * s->G, hipMemcpyDeviceToHost) != hipSuccess) ||
       hipMemcpy(koff.data(), s->d_koff, sizeof(uint64_t) * (s->I + 1), hipMemcpyDeviceToHost) != hipSuccess)
-    return TI_STREAM_FAIL(who);
+    return STB_STREAM_FAIL(who);
   uint64_t c = 0;
   for (int i = 0; i < s->I; i++)
     for (uint64_t g = koff[i]; g < koff[i + 1]; g++)
@@ -561,7 +451,7 @@ static int ti_materialise_cust(stb_tindic_t *s, const char *who) {
     return stb_fail("%s: out of device memory for %llu customers", who, (unsigned long long)s->C);
   if (s->C && hipMemcpy(d, cust.data(), sizeof(uint32_t) * s->C, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipFree(d);
-    return TI_STREAM_FAIL(who);
+    return STB_STREAM_FAIL(who);
   }
   s->d_cust = d;
   return 0;
@@ -575,8 +465,8 @@ static int ti_dish_prepare(stb_tindic_t *s, const char *who) {
                     "it with M <= 65535", who, (unsigned long long)s->maxNi);
   if (s->maxNi > 0x7fffffffull) return stb_fail("%s: a restaurant has %llu customers", who, (unsigned long long)s->maxNi);
   if (ti_materialise_cust(s, who)) return 1;
-  if (!s->d_info && hipMalloc((void **)&s->d_info, 2 * sizeof(unsigned long long)) != hipSuccess) return TI_STREAM_FAIL(who);
-  if (!s->h_info && hipHostMalloc((void **)&s->h_info, 2 * sizeof(unsigned long long)) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (!s->d_info && hipMalloc((void **)&s->d_info, 2 * sizeof(unsigned long long)) != hipSuccess) return STB_STREAM_FAIL(who);
+  if (!s->h_info && hipHostMalloc((void **)&s->h_info, 2 * sizeof(unsigned long long)) != hipSuccess) return STB_STREAM_FAIL(who);
   const unsigned maxn = (unsigned)s->maxNi;
   const ti_bounds tb = ti_table_bounds(maxn, s->Mgiven);
   if (tb.need_table && (!s->d_vt || tb.N != s->N || tb.M != s->M)) {
@@ -591,7 +481,7 @@ static int ti_dish_prepare(stb_tindic_t *s, const char *who) {
     if (hipStreamSynchronize(s->st) != hipSuccess) {  // (queued sweeps read the table that goes)
       (void)hipFree(vt);
       (void)hipFree(ws);
-      return TI_STREAM_FAIL(who);
+      return STB_STREAM_FAIL(who);
     }
     if (s->d_vt) (void)hipFree(s->d_vt);
     if (s->d_ws) (void)hipFree(s->d_ws);
@@ -624,7 +514,7 @@ extern "C" int stb_tindic_set_classes(stb_tindic_t *s, const uint32_t *cls_host,
       if (cls_host[c] >= rows) return stb_fail("%s: cls[%llu]=%u (must be < rows = %u)", who, (unsigned long long)c, cls_host[c], rows);
   }
   stb_device_scope dev(s->dev);
-  if (hipStreamSynchronize(s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipStreamSynchronize(s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   if (!cls_host) {
     if (s->d_cls) (void)hipFree(s->d_cls);
     s->d_cls = nullptr;
@@ -633,7 +523,7 @@ extern "C" int stb_tindic_set_classes(stb_tindic_t *s, const uint32_t *cls_host,
   }
   if (!s->d_cls && hipMalloc((void **)&s->d_cls, sizeof(uint32_t) * (s->C ? s->C : 1)) != hipSuccess)
     return stb_fail("%s: out of device memory", who);
-  if (s->C && hipMemcpy(s->d_cls, cls_host, sizeof(uint32_t) * s->C, hipMemcpyHostToDevice) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (s->C && hipMemcpy(s->d_cls, cls_host, sizeof(uint32_t) * s->C, hipMemcpyHostToDevice) != hipSuccess) return STB_STREAM_FAIL(who);
   s->cls_rows = rows;
   return 0;
 }
@@ -653,7 +543,7 @@ extern "C" int stb_tindic_set_lik(stb_tindic_t *s, const double *lik_host, unsig
           return stb_fail("%s: lik[%llu]=%g (must be finite and >= 0)", who, (unsigned long long)j, lik_host[j]);
   }
   stb_device_scope dev(s->dev);
-  if (hipStreamSynchronize(s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipStreamSynchronize(s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   double *d = nullptr;
   if (!drop) {
     const size_t cells = (size_t)rows * stride;
@@ -661,7 +551,7 @@ extern "C" int stb_tindic_set_lik(stb_tindic_t *s, const double *lik_host, unsig
     if (!lik_host) ones.assign(cells, 1.0);
     if (hipMalloc((void **)&d, sizeof(double) * cells) != hipSuccess) return stb_fail("%s: out of device memory", who);
     if (hipMemcpy(d, lik_host ? lik_host : ones.data(), sizeof(double) * cells, hipMemcpyHostToDevice) != hipSuccess) {
-      const int rc = TI_STREAM_FAIL(who);
+      const int rc = STB_STREAM_FAIL(who);
       (void)hipFree(d);
       return rc;
     }
@@ -707,8 +597,8 @@ extern "C" int stb_tindic_sweep_dishes(stb_tindic_t *s, double a, const double *
   if (info) info->skipped = info->stuck = 0;
   if (nsweeps == 0) return 0;
   stb_device_scope dev(s->dev);
-  if (ti_dish_prepare(s, who) || ti_ensure_V(s, a) || ti_stage_bpar(s, bpar, who)) return 1;
-  if (hipMemsetAsync(s->d_info, 0, 2 * sizeof(unsigned long long), s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (ti_dish_prepare(s, who) || ti_ensure_V(s, a) || stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  if (hipMemsetAsync(s->d_info, 0, 2 * sizeof(unsigned long long), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   if (stb_td_launch(s->d_vt, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h,
                     s->d_coff, s->d_cust, s->d_cls, s->d_lik, s->lik_rows, s->lik_stride, seed, sweep, nsweeps, s->maxK, s->d_info,
                     s->st))
@@ -738,12 +628,12 @@ extern "C" int stb_tindic_class_counts(stb_tindic_t *s, uint32_t *cnt_out) {
   const size_t bytes = sizeof(uint32_t) * (size_t)rows * stride;
   stb_device_scope dev(s->dev);
   if (ti_materialise_cust(s, who)) return 1;
-  ti_pool_scratch sc(s->st);
+  stb_pool_scratch sc(s->st);
   uint32_t *d_cnt = nullptr;
   if (sc.take(&d_cnt, bytes) != hipSuccess) return stb_fail("%s: out of device memory", who);
-  if (hipMemsetAsync(d_cnt, 0, bytes, s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipMemsetAsync(d_cnt, 0, bytes, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   if (stb_td_class_counts(s->d_cust, s->d_cls, s->C, rows, stride, d_cnt, s->st)) return 1;
-  if (hipMemcpyAsync(cnt_out, d_cnt, bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipMemcpyAsync(cnt_out, d_cnt, bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   return sc.give_back(true, who);
 }
 
@@ -760,11 +650,11 @@ static int ti_lik_ready(stb_tindic_t *s, const char *who) {
 }
 
 // customers per (class, dish) over the matrix's shape, into a buffer of the call's scratch, queued on the object's stream
-static int ti_count_classes(stb_tindic_t *s, ti_pool_scratch &sc, uint32_t **d_cnt, const char *who) {
+static int ti_count_classes(stb_tindic_t *s, stb_pool_scratch &sc, uint32_t **d_cnt, const char *who) {
   const size_t bytes = sizeof(uint32_t) * (size_t)s->lik_rows * s->lik_stride;
   if (ti_materialise_cust(s, who)) return 1;
   if (sc.take(d_cnt, bytes) != hipSuccess) return stb_fail("%s: out of device memory for the counts", who);
-  if (hipMemsetAsync(*d_cnt, 0, bytes, s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipMemsetAsync(*d_cnt, 0, bytes, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   return stb_td_class_counts(s->d_cust, s->d_cls, s->C, s->lik_rows, s->lik_stride, *d_cnt, s->st);
 }
 
@@ -775,7 +665,7 @@ extern "C" int stb_tindic_sample_lik(stb_tindic_t *s, const double *beta_host, d
   if (ti_lik_ready(s, who)) return 1;
   if (stb_tl_check_prior(beta_host, s->lik_rows, beta0, "beta", who)) return 1;
   stb_device_scope dev(s->dev);
-  ti_pool_scratch sc(s->st);
+  stb_pool_scratch sc(s->st);
   uint32_t *d_cnt = nullptr;
   if (ti_count_classes(s, sc, &d_cnt, who)) return 1;
   bool touched = false;
@@ -792,7 +682,7 @@ extern "C" int stb_tindic_loglik(stb_tindic_t *s, double *total, uint64_t *impos
   if (ti_lik_ready(s, who)) return 1;
   if (s->lik_bad) return stb_fail("%s: the last stb_tindic_sample_lik failed and left the likelihood undefined", who);
   stb_device_scope dev(s->dev);
-  ti_pool_scratch sc(s->st);
+  stb_pool_scratch sc(s->st);
   uint32_t *d_cnt = nullptr;
   if (ti_count_classes(s, sc, &d_cnt, who)) return 1;
   return sc.last(stb_tl_loglik(d_cnt, s->d_lik, s->lik_rows, s->lik_stride, total, impossible, s->st, who));
@@ -857,8 +747,8 @@ extern "C" int stb_tindic_set_hgroups(stb_tindic_t *s, int G, const uint64_t *go
   if (goff_host && hipMalloc((void **)&d_new, sizeof(uint64_t) * ((size_t)G + 1)) != hipSuccess)
     rc = stb_fail("%s: out of device memory for %d ranges", who, G);
   if (!rc && goff_host && hipMemcpy(d_new, goff_host, sizeof(uint64_t) * ((size_t)G + 1), hipMemcpyHostToDevice) != hipSuccess)
-    rc = TI_STREAM_FAIL(who);
-  if (!rc && hipStreamSynchronize(s->st) != hipSuccess) rc = TI_STREAM_FAIL(who);
+    rc = STB_STREAM_FAIL(who);
+  if (!rc && hipStreamSynchronize(s->st) != hipSuccess) rc = STB_STREAM_FAIL(who);
   if (rc) {
     if (d_new) (void)hipFree(d_new);
   } else {
@@ -881,7 +771,7 @@ static int ti_hroot(stb_tindic_t *s, const double *root_host, const char *who) {
   if (!d_new && hipMalloc((void **)&d_new, sizeof(double) * K) != hipSuccess) return stb_fail("%s: out of device memory", who);
   if (hipStreamSynchronize(s->st) != hipSuccess || hipMemcpy(d_new, root_host, sizeof(double) * K, hipMemcpyHostToDevice) != hipSuccess) {
     if (d_new != s->d_hroot) (void)hipFree(d_new);
-    return TI_STREAM_FAIL(who);
+    return STB_STREAM_FAIL(who);
   }
   s->d_hroot = d_new;
   return 0;
@@ -987,8 +877,8 @@ static int ti_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned f
   if (!total) return stb_fail("%s: total is required", who);
   if (ti_check_bpar(s, a, bpar, who)) return 1;
   stb_device_scope dev(s->dev);
-  if (ti_ensure_S(s, a, who) || ti_stage_bpar(s, bpar, who)) return 1;
-  ti_pool_scratch sc(s->st);
+  if (ti_ensure_S(s, a, who) || stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  stb_pool_scratch sc(s->st);
   double *d_Li = nullptr;
   if (Li_host && sc.take(&d_Li, sizeof(double) * (size_t)s->I) != hipSuccess)
     return stb_fail("%s: out of device memory for %d values", who, s->I);
@@ -1055,7 +945,7 @@ extern "C" int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const do
                o_beta = o_gam + (gvec ? (8 * (size_t)Kmax + up) & ~up : 0),
                o_root = o_beta + (bvec ? (8 * (size_t)s->lik_rows + up) & ~up : 0), bytes = o_root + 256;
   const size_t stage_bytes = 16 + (gvec ? 8 * (size_t)Kmax : 0) + (bvec ? 8 * (size_t)s->lik_rows : 0);
-  ti_pool_scratch sc(s->st);
+  stb_pool_scratch sc(s->st);
   char *d = nullptr, *h = nullptr, *stg = nullptr;
   void *h_dev = nullptr;
   if (sc.take(&d, bytes) != hipSuccess || sc.take(&h, 256, 1) != hipSuccess || hipHostGetDevicePointer(&h_dev, h, 0) != hipSuccess ||
@@ -1074,7 +964,7 @@ extern "C" int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const do
       (gvec && hipMemcpyAsync(d_gam, stg + 16, 8 * (size_t)Kmax, hipMemcpyHostToDevice, s->st) != hipSuccess) ||
       (bvec && hipMemcpyAsync(d_beta, stg + 16 + (gvec ? 8 * (size_t)Kmax : 0), 8 * (size_t)s->lik_rows, hipMemcpyHostToDevice,
                               s->st) != hipSuccess))
-    return TI_STREAM_FAIL(who);
+    return STB_STREAM_FAIL(who);
   if (want_root && stb_dm_root_queue(Kmax, s->d_hroot, d_gam, opts->gamma0, (double *)h_dev, s->st)) return 1;
   if (stb_hg_count_queue(s->I, s->d_koff, s->d_t, Kmax, G, flat ? goff1 : s->d_hgoff, c, Cg, s->st)) return 1;
   // flat: w = gamma, scale 1; grouped: w = the root (none: 1 / Kmax each), scale alpha
@@ -1112,7 +1002,7 @@ static int ti_dc_args(const double *base_host, uint64_t len, double s_in, double
 
 // head bytes of device scratch (*d) and, behind them, base_host[len] on the device (*d_base; null without a base), staged
 // through a pinned block that holds `head_host` (head bytes, may be null) in front of it
-static int ti_dc_stage(ti_pool_scratch &sc, size_t head, const void *head_host, const double *base_host, size_t len, char **d,
+static int ti_dc_stage(stb_pool_scratch &sc, size_t head, const void *head_host, const double *base_host, size_t len, char **d,
                        double **d_base, const char *who) {
   const size_t vec = base_host ? 8 * len : 0;
   char *stage = nullptr;
@@ -1123,7 +1013,7 @@ static int ti_dc_stage(ti_pool_scratch &sc, size_t head, const void *head_host, 
   if (base_host) memcpy(stage + head, base_host, vec);
   if ((head_host && hipMemcpyAsync(*d, stage, head, hipMemcpyHostToDevice, sc.st) != hipSuccess) ||
       (base_host && hipMemcpyAsync(*d_base, stage + head, vec, hipMemcpyHostToDevice, sc.st) != hipSuccess))
-    return TI_STREAM_FAIL(who);
+    return STB_STREAM_FAIL(who);
   return 0;
 }
 
@@ -1135,7 +1025,7 @@ extern "C" int stb_tindic_sample_beta(stb_tindic_t *s, const double *base_host, 
   if (ti_lik_ready(s, who)) return 1;
   if (ti_dc_args(base_host, s->lik_rows, s_in, shape, scale, info, who)) return 1;
   stb_device_scope dev(s->dev);
-  ti_pool_scratch sc(s->st);
+  stb_pool_scratch sc(s->st);
   char *d = nullptr;
   double *d_base = nullptr;
   uint32_t *d_cls_cnt = nullptr;
@@ -1158,7 +1048,7 @@ extern "C" int stb_tindic_sample_gamma(stb_tindic_t *s, const double *base_host,
   stb_device_scope dev(s->dev);
   // device scratch: the one range {0, I} (256 bytes), c[Kmax], C (256 bytes), then the base
   const size_t o_c = 256, o_C = o_c + ((4 * (size_t)Kmax + 255) & ~(size_t)255), head = o_C + 256;
-  ti_pool_scratch sc(s->st);
+  stb_pool_scratch sc(s->st);
   char *d = nullptr;
   double *d_base = nullptr;
   const uint64_t range[2] = {0, (uint64_t)s->I};
@@ -1198,7 +1088,7 @@ extern "C" int stb_tindic_set_heldout(stb_tindic_t *s, const uint64_t *hoff_host
   uint64_t *d_hoff = nullptr;
   uint32_t *d_hcls = nullptr;
   double *d_pacc = nullptr;
-  if (hipStreamSynchronize(s->st) != hipSuccess) rc = TI_STREAM_FAIL(who);
+  if (hipStreamSynchronize(s->st) != hipSuccess) rc = STB_STREAM_FAIL(who);
   if (!rc && hoff_host) {
     const size_t Hs = Hc ? Hc : 1;
     if (hipMalloc((void **)&d_hoff, sizeof(uint64_t) * ((size_t)s->I + 1)) != hipSuccess ||
@@ -1207,7 +1097,7 @@ extern "C" int stb_tindic_set_heldout(stb_tindic_t *s, const uint64_t *hoff_host
     if (!rc && (hipMemcpy(d_hoff, hoff_host, sizeof(uint64_t) * ((size_t)s->I + 1), hipMemcpyHostToDevice) != hipSuccess ||
                 (Hc && hipMemcpy(d_hcls, hcls_host, sizeof(uint32_t) * Hc, hipMemcpyHostToDevice) != hipSuccess) ||
                 hipMemset(d_pacc, 0, sizeof(double) * Hs) != hipSuccess))
-      rc = TI_STREAM_FAIL(who);
+      rc = STB_STREAM_FAIL(who);
   }
   if (rc) {  // the set the object had stays
     void *fresh[] = {d_hoff, d_hcls, d_pacc};
@@ -1254,14 +1144,14 @@ extern "C" int stb_tindic_predict(stb_tindic_t *s, double a, const double *bpar,
   if (tstride < s->maxK || tstride < 1) return stb_fail("%s: tstride=%u; the largest restaurant has K=%u dishes", who, tstride, s->maxK);
   stb_device_scope dev(s->dev);
   const size_t bytes = sizeof(double) * (size_t)s->I * tstride;
-  if (ti_stage_bpar(s, bpar, who)) return 1;
-  ti_pool_scratch sc(s->st);
+  if (stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  stb_pool_scratch sc(s->st);
   double *d_theta = nullptr;
   if (sc.take(&d_theta, bytes) != hipSuccess) return stb_fail("%s: out of device memory for %d x %u values", who, s->I, tstride);
   if (stb_pr_predict(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_h, d_theta, tstride, nullptr, nullptr, nullptr, 0, 0, nullptr,
                      0, nullptr, s->st, who))
     return 1;
-  if (hipMemcpyAsync(theta_host, d_theta, bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipMemcpyAsync(theta_host, d_theta, bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   return sc.give_back(true, who);
 }
 
@@ -1275,14 +1165,14 @@ extern "C" int stb_tindic_heldout(stb_tindic_t *s, double a, const double *bpar,
   const bool accumulate = (flags & STB_PR_ACCUMULATE) != 0;
   if (accumulate && s->hsamples == 0xffffffffu) return stb_fail("%s: the sample count is full (stb_tindic_heldout_reset)", who);
   stb_device_scope dev(s->dev);
-  if (ti_stage_bpar(s, bpar, who)) return 1;
-  ti_pool_scratch sc(s->st);
+  if (stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  stb_pool_scratch sc(s->st);
   double *d_p = nullptr, *d_Hi = nullptr;
   uint64_t *d_skip = nullptr;
   if ((!accumulate && sc.take(&d_p, sizeof(double) * (s->Hc ? s->Hc : 1)) != hipSuccess) ||
       (Hi_host && sc.take(&d_Hi, sizeof(double) * (size_t)s->I) != hipSuccess) || sc.take(&d_skip, sizeof(uint64_t)) != hipSuccess)
     return stb_fail("%s: out of device memory for %llu held-out customers", who, (unsigned long long)s->Hc);
-  if (hipMemsetAsync(d_skip, 0, sizeof(uint64_t), s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipMemsetAsync(d_skip, 0, sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   if (stb_pr_predict(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_h, nullptr, 0, s->d_hoff, s->d_hcls, s->d_lik, s->lik_rows,
                      s->lik_stride, accumulate ? s->d_pacc : d_p, flags, d_skip, s->st, who))
     return 1;
@@ -1297,7 +1187,7 @@ extern "C" int stb_tindic_heldout_reset(stb_tindic_t *s) {
   if (!s) return stb_fail("%s: null object", who);
   if (!s->d_hoff) return stb_fail("%s: no held-out customers are set (stb_tindic_set_heldout)", who);
   stb_device_scope dev(s->dev);
-  if (hipMemsetAsync(s->d_pacc, 0, sizeof(double) * (s->Hc ? s->Hc : 1), s->st) != hipSuccess) return TI_STREAM_FAIL(who);
+  if (hipMemsetAsync(s->d_pacc, 0, sizeof(double) * (s->Hc ? s->Hc : 1), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   s->hsamples = 0;
   return 0;
 }

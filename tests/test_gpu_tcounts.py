@@ -367,3 +367,138 @@ def test_queued_sweeps_with_changing_concentrations():
     finally:
         q.free()
         r.free()
+
+
+# ---- the hand-over to a group set, for both resident-count objects (stb_groups_take_counts)
+
+X3 = np.array([0.2, 0.4, 0.7])
+
+
+def make(kind, g, t=None, M=0):
+    t = g.t if t is None else t
+    return capi.TableCounts(g.K, g.n, t, None, M) if kind == "tcounts" else capi.TableIndicators(g.K, g.n, t, None, None, M)
+
+
+def aterms3(h):
+    out = np.zeros(3)
+    capi.check(capi.lib().stb_groups_aterms(h, capi.dp(X3), 3, capi.dp(out)))
+    return out
+
+
+def same_bits(x, y):
+    return np.array_equal(np.asarray(x).view(np.uint64), np.asarray(y).view(np.uint64))
+
+
+@pytest.mark.parametrize("kind", ["tcounts", "tindic"])
+def test_refused_hand_overs_leave_both_sides_as_they_were(kind):
+    L = capi.lib()
+    g = synth.groups(6, 5, 40, "realistic")
+    N = M = int(g.n.max())
+    obj = make(kind, g)
+    A = make_set(g, g.t, g.T, N, M, 3)
+
+    def unchanged(before, t0, T0):
+        assert same_bits(aterms3(A), before)
+        t, T = obj.get()
+        assert np.array_equal(t, t0) and np.array_equal(T, T0)
+        obj.to_groups(A, g.bpar)                                  # a valid hand-over still goes through
+        assert np.isfinite(aterms3(A)).all()
+
+    try:
+        t0, T0 = obj.get()
+        # the sentinel from an object that was never given concentrations
+        before = aterms3(A)
+        with pytest.raises(capi.StbError, match="holds no concentrations"):
+            obj.to_groups(A, capi.BPAR_RESIDENT)
+        unchanged(before, t0, T0)
+        # an evaluation queued and not waited for
+        before = aterms3(A)
+        out = np.zeros(3)
+        capi.check(L.stb_groups_aterms_async(A, capi.dp(X3), 3, capi.dp(out), None))
+        with pytest.raises(capi.StbError, match="has not been waited for"):
+            obj.to_groups(A, g.bpar)
+        capi.check(L.stb_groups_wait(A))
+        assert same_bits(out, before)
+        unchanged(before, t0, T0)
+        # a set between pairs_begin and _commit
+        before = aterms3(A)
+        capi.check(L.stb_groups_pairs_begin(A))
+        with pytest.raises(capi.StbError, match="pairs_begin and"):
+            obj.to_groups(A, g.bpar)
+        capi.check(L.stb_groups_pairs_put(A, orc.u32p(g.n), orc.u16p(t0), len(g.n), None, None))
+        capi.check(L.stb_groups_pairs_commit(A, orc.u32p(T0), orc.dp(g.bpar), 0, 0))
+        unchanged(before, t0, T0)
+    finally:
+        obj.free()
+        L.stb_groups_free(A)
+
+
+@pytest.mark.parametrize("way", ["host", "resident", "none"])
+def test_the_two_objects_hand_over_the_same_thing(way):
+    L = capi.lib()
+    g = synth.groups(6, 5, 40, "realistic")
+    N = int(g.n.max())
+    assert N > 4
+    t4 = np.minimum(g.t, 4).astype(np.uint16)                     # column bound 4, below the largest n
+    t3 = np.minimum(g.t, 3).astype(np.uint16)
+    off = np.concatenate([[0], np.cumsum(g.K)])
+    T4 = np.array([t4[off[i]:off[i + 1]].sum() for i in range(g.I)], dtype=np.uint32)
+    T3 = np.array([t3[off[i]:off[i + 1]].sum() for i in range(g.I)], dtype=np.uint32)
+    bnew = g.bpar * 0.5
+    objs = [make(kind, g, t4, 4) for kind in ("tcounts", "tindic")]
+    sets = [make_set(g, t3, T3, N, 3, 3) for _ in objs]           # bounds too small for t = 4: they grow
+    H = make_set(g, t3, T3, N, 4, 3)                              # the host route, at the grown bounds
+    try:
+        outs = []
+        for obj, h in zip(objs, sets):
+            if way == "host":
+                obj.to_groups(h, bnew)
+            elif way == "resident":
+                obj.set_bpar(bnew)
+                obj.to_groups(h, capi.BPAR_RESIDENT)
+            else:
+                obj.to_groups(h)                                  # the set keeps the bpar it was created with
+            Ns, Ms = capi.C.c_uint(), capi.C.c_uint()
+            capi.check(L.stb_groups_shape(h, None, None, capi.C.byref(Ns), capi.C.byref(Ms), None))
+            assert (Ns.value, Ms.value) == (N, 4)
+            outs.append(aterms3(h))
+        capi.check(L.stb_groups_update_pairs(H, orc.u32p(g.n), orc.u16p(t4)))
+        capi.check(L.stb_groups_update_restaurants(H, orc.u32p(T4), orc.dp(g.bpar if way == "none" else bnew)))
+        want = aterms3(H)
+        assert np.isfinite(want).all()
+        assert same_bits(outs[0], outs[1]) and same_bits(outs[0], want), (outs, want)
+    finally:
+        for obj in objs:
+            obj.free()
+        for h in sets + [H]:
+            L.stb_groups_free(h)
+
+
+@pytest.mark.parametrize("kind", ["tcounts", "tindic"])
+def test_the_hand_over_holds_later_sweeps_back(kind):
+    L = capi.lib()
+    g = synth.groups(200, 20, 300, "realistic", seed=77)
+    N = M = int(g.n.max())
+    a, b, seed = 0.45, g.bpar * 0.5, 2024
+    o1, o2, o3 = make(kind, g), make(kind, g), make(kind, g)
+    A = make_set(g, g.t, g.T, N, M, 3)
+    B = make_set(g, g.t, g.T, N, M, 3)
+    try:
+        o1.sweep(a, b, seed, 0, 1)
+        o1.to_groups(A, b)
+        o1.sweep(a, b, seed, 1, 3)                                # at once: the set's copy is still queued
+        outA = aterms3(A)
+        o2.sweep(a, b, seed, 0, 1)
+        t2, T2 = o2.get()
+        capi.check(L.stb_groups_update_pairs(B, orc.u32p(g.n), orc.u16p(t2)))
+        capi.check(L.stb_groups_update_restaurants(B, orc.u32p(T2), orc.dp(b)))
+        assert same_bits(outA, aterms3(B))
+        o3.sweep(a, b, seed, 0, 4)
+        t1, T1 = o1.get()
+        t3, T3 = o3.get()
+        assert np.array_equal(t1, t3) and np.array_equal(T1, T3) and not np.array_equal(t1, t2)
+    finally:
+        for o in (o1, o2, o3):
+            o.free()
+        for h in (A, B):
+            L.stb_groups_free(h)
