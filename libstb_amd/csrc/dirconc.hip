@@ -44,6 +44,7 @@
 #include "hyperb.h"
 #include "hg_cell.h"
 #include "dirconc.h"
+#include "ticket.h"
 
 #pragma clang fp contract(off)
 
@@ -63,14 +64,8 @@
 // host (pinned), u64: [0] the error word, [1] s' (a double's bits), [2] sum n, [3] sum M, [4] multinomials with n > 0,
 // [5] zero-weight cells
 
-__device__ __forceinline__ unsigned long long dc_tree_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 __device__ __forceinline__ void dc_publish(unsigned long long zw, bool bad, unsigned lane, unsigned *ctl) {
-  zw = dc_tree_u64(zw);
+  zw = stb_wave_sum(zw);
   if (lane == 0 && zw) __hip_atomic_fetch_add(&((unsigned long long *)ctl)[DC_CTL_ZW], zw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (bad) __hip_atomic_fetch_or(&ctl[0], DC_ERR_ZERO, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -128,7 +123,7 @@ __global__ __launch_bounds__(DC_MAXTHREADS) void k_dc_totals_rows(const uint32_t
       }
       if (cols - base <= 64) break;  // (base + 64 may wrap)
     }
-    sum = dc_tree_u64(sum);
+    sum = stb_wave_sum(sum);
     if (lane == 0) n[r] = sum;
   }
   dc_publish(zw, bad, lane, ctl);

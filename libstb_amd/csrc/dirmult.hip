@@ -65,6 +65,7 @@
 
 #include "stb_common.h"
 #include "dirmult.h"
+#include "ticket.h"
 
 #pragma clang fp contract(off)
 
@@ -79,19 +80,6 @@
 #define DM_CTL_ERR 16
 #define DM_CTL_W 16
 // host (pinned): [0] total, [1] cells, [2] norms; as u64 3 .. 6: nonzero, count, zero_weight, impossible; 7: the error word
-
-__device__ __forceinline__ double dm_tree(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long dm_tree_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 __device__ __forceinline__ double dm_rise(double x, unsigned m) {
 #pragma clang fp contract(off)
@@ -133,10 +121,10 @@ __device__ __forceinline__ double dm_visit(double w, unsigned c, dm_counts &n, b
 }
 
 __device__ __forceinline__ void dm_publish_counts(dm_counts n, unsigned lane, unsigned *ctl) {
-  n.nnz = dm_tree_u64(n.nnz);
-  n.cnt = dm_tree_u64(n.cnt);
-  n.zw = dm_tree_u64(n.zw);
-  n.imp = dm_tree_u64(n.imp);
+  n.nnz = stb_wave_sum(n.nnz);
+  n.cnt = stb_wave_sum(n.cnt);
+  n.zw = stb_wave_sum(n.zw);
+  n.imp = stb_wave_sum(n.imp);
   unsigned long long *cnt = (unsigned long long *)ctl;
   if (lane == 0) {
     if (n.nnz) __hip_atomic_fetch_add(&cnt[1], n.nnz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -144,23 +132,6 @@ __device__ __forceinline__ void dm_publish_counts(dm_counts n, unsigned lane, un
     if (n.zw) __hip_atomic_fetch_add(&cnt[3], n.zw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (n.imp) __hip_atomic_fetch_add(&cnt[4], n.imp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-}
-
-// the ticket: every store of the workgroup is published by an agent-scope release ahead of it; true in the last
-// workgroup to take one, which has acquired what the others published (k_logjoint's)
-__device__ __forceinline__ bool dm_last(unsigned *ctl, unsigned ngroups, unsigned *s_last) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    *s_last = __hip_atomic_fetch_add(&ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ngroups - 1 ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!*s_last) return false;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  return true;
 }
 
 // thread 0 of the last workgroup: the two double-doubles and the counters to the pinned words
@@ -210,7 +181,7 @@ __global__ __launch_bounds__(DM_BLOCK) void k_dm_weights(const double *wv, uint6
           x[q] = j0 + 64 * q < ncat ? s * wv[j0 + 64 * q] : 0.0;
           if (!(x[q] >= 0.0 && isfinite(x[q]))) err |= DM_ERR_W;
         }
-        const double v = dm_tree((x[0] + x[1]) + (x[2] + x[3]));
+        const double v = stb_wave_sum((x[0] + x[1]) + (x[2] + x[3]));
         if (lane == 0) schunk[c] = v;
       }
       __syncthreads();
@@ -234,7 +205,7 @@ __device__ __forceinline__ void dm_block_sums(const double (*sx)[DM_BLOCK], unsi
 #pragma clang fp contract(off)
   for (unsigned q = wave; q < 2; q += nw) {
     const double *x = sx[q];
-    const double v = dm_tree((x[lane] + x[lane + 64]) + (x[lane + 128] + x[lane + 192]));
+    const double v = stb_wave_sum((x[lane] + x[lane + 64]) + (x[lane + 128] + x[lane + 192]));
     if (lane == 0) out[q] = v;
   }
 }
@@ -257,10 +228,10 @@ __device__ __forceinline__ double dm_row(const uint32_t *row, unsigned cols, con
       sum += c;
       x = dm_visit(w, c, n, &bad);
     }
-    dd_add(acc, dm_tree(x));
+    dd_add(acc, stb_wave_sum(x));
     if (cols - base <= 64) break;  // (base + 64 may wrap)
   }
-  *C = dm_tree_u64(sum);
+  *C = stb_wave_sum(sum);
   *any = __ballot(bad) != 0ull;
   return acc.hi + acc.lo;
 }
@@ -310,7 +281,7 @@ __global__ __launch_bounds__(DM_MAXTHREADS) void k_dm_rows(const uint32_t *cnt, 
     __syncthreads();
   }
   dm_publish_counts(n, lane, ctl);
-  if (!dm_last(ctl, gridDim.x, &s_last)) return;
+  if (!stb_ticket_last(ctl, gridDim.x, &s_last)) return;
   dd_t acc{0.0, 0.0};  // threads 0, 1: one component each
   for (unsigned c0 = 0; c0 < nblk; c0 += DM_STAGE) {
     const unsigned cn = nblk - c0 < DM_STAGE ? nblk - c0 : DM_STAGE;
@@ -354,7 +325,7 @@ __global__ __launch_bounds__(DM_MAXTHREADS) void k_dm_rows_split(const uint32_t 
     }
   }
   dm_publish_counts(n, lane, ctl);
-  if (!dm_last(ctl, gridDim.x, &s_last)) return;
+  if (!stb_ticket_last(ctl, gridDim.x, &s_last)) return;
   // the blocks' trees a wave each (its lanes read the block's 256 values themselves), a stage of block sums at a time;
   // threads 0 and 1 add a component each in block order
   dd_t acc{0.0, 0.0};
@@ -367,7 +338,7 @@ __global__ __launch_bounds__(DM_MAXTHREADS) void k_dm_rows_split(const uint32_t 
         double x[4];
 #pragma unroll
         for (unsigned j = 0; j < 4; j++) x[j] = r0 + 64 * j < rows ? rowval[2 * (r0 + 64 * j) + q] : 0.0;
-        const double v = dm_tree((x[0] + x[1]) + (x[2] + x[3]));
+        const double v = stb_wave_sum((x[0] + x[1]) + (x[2] + x[3]));
         if (lane == 0) stage[q][b] = v;
       }
     }
@@ -427,7 +398,7 @@ __global__ __launch_bounds__(DM_MAXTHREADS) void k_dm_cols(const uint32_t *cnt, 
   }
   if (live && bad) __hip_atomic_fetch_or(&colflag[k], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   dm_publish_counts(n, lane, ctl);
-  if (!dm_last(ctl, gridDim.x * gridDim.y, &s_last)) return;
+  if (!stb_ticket_last(ctl, gridDim.x * gridDim.y, &s_last)) return;
   const double W = ((const double *)ctl)[DM_CTL_W], lgW = ((const double *)ctl)[DM_CTL_W + 1];
   dd_t accC{0.0, 0.0}, accN{0.0, 0.0};  // (thread 0's)
   // every column's value first, the threads strided over the columns; then the blocks of 256 columns

@@ -41,6 +41,7 @@
 #include "gamma_dev.h"
 #include "hyperb.h"
 #include "hgroups.h"
+#include "ticket.h"
 #include "hg_cell.h"  // HG_SALT_Y, HG_SALT_A, HG_TWAVE, hg_y, hg_cell: the cell's draw, shared with dirconc.hip
 
 #pragma clang fp contract(off)
@@ -73,8 +74,7 @@ __device__ __forceinline__ void hg_flush(unsigned (&acc)[HG_KREG], unsigned long
     if (k < Kmax && acc[j]) atomicAdd(&c[g * Kmax + k], acc[j]);
     acc[j] = 0;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) tot += __shfl_down(tot, off, 64);
+  tot = stb_wave_sum(tot);
   if (lane == 0 && tot) atomicAdd(&Cg[g], tot);
   tot = 0;
 }

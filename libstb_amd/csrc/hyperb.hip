@@ -37,6 +37,7 @@
 #include "tcounts.h"
 #include "hyperb.h"
 #include "gamma_dev.h"  // hq_unit, hq_log_gamma, hq_draw_L, HQ_CAP
+#include "ticket.h"
 
 #define HB_SALT_Y 0x59B1D5A7C3E9F24Dull  // the y substream of a restaurant: mix(key_i ^ HB_SALT_Y)
 #define HB_SALT_G 0x6A09E667F3BCC909ull  // the groups' key: mix(key ^ HB_SALT_G)
@@ -237,50 +238,11 @@ __global__ void k_hb_finish(const unsigned *ctl, unsigned long long *host_out) {
 // per calling thread: the device words, the pinned words the last kernel answers in, and Y where the caller keeps none.
 // A call waits for its answer before it returns, so one set per thread is never in use twice.
 
-struct hb_ctx {
-  int dev = -1;
-  unsigned *d_ctl = nullptr;
-  unsigned long long *h_out = nullptr, *h_out_dev = nullptr;
-  uint32_t *d_Y = nullptr;
-  size_t capY = 0;
-};
-static thread_local hb_ctx hb;
-
-static void hb_drop() {
-  if (hb.dev < 0) return;
-  stb_device_scope dev(hb.dev);
-  if (hb.d_ctl) stb_pool_free(hb.d_ctl);
-  if (hb.h_out) stb_pool_free(hb.h_out);
-  if (hb.d_Y) stb_pool_free(hb.d_Y);
-  hb = hb_ctx();
-}
+static thread_local stb_tset hb;  // h_out: four u64 words (k_hb_finish); d_buf: uint32 y, no floor
 
 extern "C" void stb_hb_release(void) {
   STB_ENTRY;
-  hb_drop();
-}
-
-static int hb_ready(size_t nY, const char *who) {
-  int dev = -1;
-  HIPCHK(hipGetDevice(&dev));
-  if (hb.dev >= 0 && hb.dev != dev) hb_drop();
-  if (hb.dev < 0) {
-    hb.dev = dev;
-    if (stb_pool_malloc((void **)&hb.d_ctl, 256) != hipSuccess || stb_pool_malloc((void **)&hb.h_out, 256, 1) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&hb.h_out_dev, hb.h_out, 0) != hipSuccess) {
-      hb_drop();
-      return stb_fail("%s: out of memory for the result words", who);
-    }
-  }
-  if (nY > hb.capY) {
-    if (hb.d_Y) stb_pool_free(hb.d_Y);
-    hb.d_Y = nullptr;
-    hb.capY = 0;
-    if (stb_pool_malloc((void **)&hb.d_Y, sizeof(uint32_t) * nY) != hipSuccess)
-      return stb_fail("%s: out of device memory for %zu counts", who, nY);
-    hb.capY = nY;
-  }
-  return 0;
+  stb_tset_drop(hb);
 }
 
 // the checks and the launches of a step, nothing waited for: *queued says whether hb_answer has words to read
@@ -304,8 +266,8 @@ static int hb_queue(double a, double shape, double scale, int I, const uint32_t 
   if (I > 0 && (!d_T || !d_bpar || !d_L)) return stb_fail("%s: d_T, d_bpar and d_L are required", who);
   if (G == 0) return 0;
   if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
-  if (hb_ready(d_Y || I == 0 ? 0 : (size_t)I, who)) return 1;
-  if (!d_Y) d_Y = hb.d_Y;
+  if (stb_tset_ready(hb, who) || stb_tset_room(hb, d_Y || I == 0 ? 0 : (size_t)I, 0, sizeof(uint32_t), who)) return 1;
+  if (!d_Y) d_Y = (uint32_t *)hb.d_buf;
   hipStream_t st = (hipStream_t)stream;
   int nw = stb_env_int("STB_HYPERB_WAVES", 0);
   const bool nw_given = nw == 1 || nw == 2 || nw == 4 || nw == 8;
@@ -326,7 +288,7 @@ static int hb_queue(double a, double shape, double scale, int I, const uint32_t 
   else
     STB_LAUNCH(k_hb_group_lane, dim3((unsigned)((G + 255) / 256)), dim3(256), st, 1.0 / scale, shape, (uint64_t)G,
                (const double *)d_L, (const uint32_t *)d_Y, d_bpar, d_bgrp, d_rate, keyG, hb.d_ctl);
-  STB_LAUNCH(k_hb_finish, dim3(1), dim3(1), st, (const unsigned *)hb.d_ctl, hb.h_out_dev);
+  STB_LAUNCH(k_hb_finish, dim3(1), dim3(1), st, (const unsigned *)hb.d_ctl, (unsigned long long *)hb.h_out_dev);
   HIPCHK(hipGetLastError());
   *queued = true;
   return 0;
@@ -334,7 +296,7 @@ static int hb_queue(double a, double shape, double scale, int I, const uint32_t 
 
 // the pinned words of the step hb_queue queued last on this thread, once its stream has been waited for
 static int hb_answer(int G, stb_bgroups_info_t *info, const char *who) {
-  const volatile unsigned long long *h = hb.h_out;
+  const volatile unsigned long long *h = (const volatile unsigned long long *)hb.h_out;
   const unsigned err = (unsigned)h[0];
   if (info) {
     info->error_word = err;

@@ -31,7 +31,7 @@
 #include "groups.h"
 #include "tcounts.h"
 #include "hyperj.h"
-#include "ticket_geom.h"
+#include "ticket.h"
 #include "../../include/psample.h"
 
 #include <vector>
@@ -113,18 +113,7 @@ __global__ __launch_bounds__(HJ_MAXTHREADS) void k_joint_terms(hj_args A, uint64
       }
     }
   }
-  // the block sums are published by an agent-scope release ahead of the ticket; the last workgroup acquires and sums
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = __hip_atomic_fetch_add(&ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * gridDim.y - 1 ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (!stb_ticket_last(ctl, gridDim.x * gridDim.y, &s_last)) return;  // (ticket.h)
   for (int cell = tid; cell < DJ; cell += nthr) {
     dd_t acc{0.0, 0.0};
     for (unsigned c = 0; c < nchunks; c++) dd_add(acc, partial[(size_t)c * DJ + cell]);
@@ -266,10 +255,7 @@ __global__ __launch_bounds__(64) void k_joint_final(hj_final_args A, const doubl
 // for its answers before it returns, so one set per thread is never in use twice.
 
 struct hj_ctx {
-  int dev = -1;
-  double *d_partial = nullptr;
-  size_t cap = 0;  // doubles d_partial holds
-  unsigned *d_ctl = nullptr;
+  stb_tset set;             // d_buf: doubles of block sums; its pinned words are not used (the stages have their own)
   double *d_buf = nullptr;  // [HJ_STAGES][HJ_CELLS] L, then R [HJ_CELLS], W [HJ_DMAX], pt [4]
   double *h_out = nullptr, *h_out_dev = nullptr;  // [HJ_STAGES + 1][HJ_HOST_STRIDE]
   std::vector<double> keepL;
@@ -277,18 +263,13 @@ struct hj_ctx {
 static thread_local hj_ctx hj;
 
 static void hj_drop() {
-  if (hj.dev < 0) return;
-  stb_device_scope dev(hj.dev);
-  if (hj.d_partial) stb_pool_free(hj.d_partial);
-  if (hj.d_ctl) stb_pool_free(hj.d_ctl);
+  if (hj.set.dev < 0) return;
+  stb_device_scope dev(hj.set.dev);
   if (hj.d_buf) stb_pool_free(hj.d_buf);
   if (hj.h_out) stb_pool_free(hj.h_out);
-  hj.dev = -1;
-  hj.d_partial = nullptr;
-  hj.cap = 0;
-  hj.d_ctl = nullptr;
   hj.d_buf = nullptr;
   hj.h_out = hj.h_out_dev = nullptr;
+  stb_tset_drop(hj.set);
 }
 
 extern "C" void stb_hj_release(void) {
@@ -299,14 +280,8 @@ extern "C" void stb_hj_release(void) {
 static int hj_ready(size_t partials, bool stages) {
   int dev = -1;
   HIPCHK(hipGetDevice(&dev));
-  if (hj.dev >= 0 && hj.dev != dev) hj_drop();
-  if (hj.dev < 0) {
-    hj.dev = dev;
-    if (stb_pool_malloc((void **)&hj.d_ctl, 256) != hipSuccess) {
-      hj_drop();
-      return stb_fail("stb_joint_terms: out of device memory");
-    }
-  }
+  if (hj.set.dev >= 0 && hj.set.dev != dev) hj_drop();  // (the stage buffers go with the set)
+  if (stb_tset_ready(hj.set, "stb_joint_terms", false)) return 1;
   if (stages && !hj.d_buf) {
     if (stb_pool_malloc((void **)&hj.d_buf, sizeof(double) * ((HJ_STAGES + 1) * HJ_CELLS + HJ_DMAX + 8)) != hipSuccess ||
         stb_pool_malloc((void **)&hj.h_out, sizeof(double) * (HJ_STAGES + 1) * HJ_HOST_STRIDE, 1) != hipSuccess ||
@@ -315,18 +290,9 @@ static int hj_ready(size_t partials, bool stages) {
       return stb_fail("stb_groups_samplejoint: out of memory for the stage buffers");
     }
   }
-  if (partials > hj.cap) {
-    // (a launch queued earlier may still write the old buffer, and the cache may hand it to another thread at once)
-    if (hj.d_partial) HIPCHK(hipDeviceSynchronize());
-    if (hj.d_partial) stb_pool_free(hj.d_partial);
-    hj.d_partial = nullptr;
-    hj.cap = 0;
-    const size_t want = partials < STB_TG_CAP0_HJ ? STB_TG_CAP0_HJ : partials;
-    if (stb_pool_malloc((void **)&hj.d_partial, sizeof(double) * want) != hipSuccess)
-      return stb_fail("stb_joint_terms: out of device memory for %zu block sums", want);
-    hj.cap = want;
-  }
-  return 0;
+  // (a launch queued earlier may still write the old buffer, and the cache may hand it to another thread at once)
+  if (partials > hj.set.cap && hj.set.d_buf) HIPCHK(hipDeviceSynchronize());
+  return stb_tset_room(hj.set, partials, STB_TG_CAP0_HJ, sizeof(double), "stb_joint_terms");
 }
 
 // R over the grid, queued on st; N given either way (d_N uint32, or d_coff uint64 prefix sums)
@@ -360,13 +326,13 @@ static int hj_terms(const double *a, int D, const double *b, int J, const uint32
   if (hj_ready(tg.need, false)) return 1;
   const unsigned nchunks = tg.nblk, gx = tg.gx, gy = tg.gy;
   const int nw = (int)tg.waves, nthr = 64 * nw;
-  HIPCHK(hipMemsetAsync(hj.d_ctl, 0, sizeof(unsigned), st));
+  HIPCHK(hipMemsetAsync(hj.set.d_ctl, 0, sizeof(unsigned), st));
   if (nw == 1)
-    STB_LAUNCH(k_joint_terms<4>, dim3(gx, gy), dim3(nthr), st, A, I, d_T, d_N, d_coff, hj.d_partial, nchunks, hj.d_ctl, d_out);
+    STB_LAUNCH(k_joint_terms<4>, dim3(gx, gy), dim3(nthr), st, A, I, d_T, d_N, d_coff, (double *)hj.set.d_buf, nchunks, hj.set.d_ctl, d_out);
   else if (nw == 2)
-    STB_LAUNCH(k_joint_terms<2>, dim3(gx, gy), dim3(nthr), st, A, I, d_T, d_N, d_coff, hj.d_partial, nchunks, hj.d_ctl, d_out);
+    STB_LAUNCH(k_joint_terms<2>, dim3(gx, gy), dim3(nthr), st, A, I, d_T, d_N, d_coff, (double *)hj.set.d_buf, nchunks, hj.set.d_ctl, d_out);
   else
-    STB_LAUNCH(k_joint_terms<1>, dim3(gx, gy), dim3(nthr), st, A, I, d_T, d_N, d_coff, hj.d_partial, nchunks, hj.d_ctl, d_out);
+    STB_LAUNCH(k_joint_terms<1>, dim3(gx, gy), dim3(nthr), st, A, I, d_T, d_N, d_coff, (double *)hj.set.d_buf, nchunks, hj.set.d_ctl, d_out);
   HIPCHK(hipGetLastError());
   return 0;
 }

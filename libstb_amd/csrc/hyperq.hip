@@ -37,7 +37,7 @@
 #include "tcounts.h"
 #include "hyperq.h"
 #include "gamma_dev.h"  // hq_unit, hq_log_gamma, hq_draw_L, HQ_CAP
-#include "ticket_geom.h"
+#include "ticket.h"
 
 #define HQ_CHUNK STB_TG_BLOCK  // (one constant for the kernel, the launch and stb_reduce_geometry)
 #define HQ_MAXTHREADS 512
@@ -77,20 +77,7 @@ __global__ __launch_bounds__(HQ_MAXTHREADS) void k_logq(double b, double inv_sca
     __syncthreads();
   }
   if (bad) __hip_atomic_fetch_or(&ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // the block sums are published by an agent-scope release ahead of the ticket; the last workgroup acquires and sums
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = __hip_atomic_fetch_add(&ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
-    if (s_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  __syncthreads();
-  if (!s_last || wave != 0) return;
+  if (!stb_ticket_last(ctl, gridDim.x, &s_last) || wave != 0) return;  // (ticket.h)
   dd_t acc{0.0, 0.0};
   for (unsigned c = lane; c < nchunks; c += 64) dd_add(acc, partial[c]);
 #pragma unroll
@@ -130,52 +117,11 @@ __global__ __launch_bounds__(256) void k_segsum(const uint64_t *koff, const uint
 // per calling thread: the block sums, the ticket and error words, and the pinned words the kernels answer in.  A call
 // waits for its answer before it returns, so one set per thread is never in use twice.
 
-struct hq_ctx {
-  int dev = -1;
-  double *d_partial = nullptr;
-  size_t cap = 0;  // block sums d_partial holds
-  unsigned *d_ctl = nullptr;
-  double *h_out = nullptr, *h_out_dev = nullptr;  // [0] Q, [1] error word, [2] (as uint64) sum of T
-};
-static thread_local hq_ctx hq;
-
-static void hq_drop() {
-  if (hq.dev < 0) return;
-  stb_device_scope dev(hq.dev);
-  if (hq.d_partial) stb_pool_free(hq.d_partial);
-  if (hq.d_ctl) stb_pool_free(hq.d_ctl);
-  if (hq.h_out) stb_pool_free(hq.h_out);
-  hq = hq_ctx();
-}
+static thread_local stb_tset hq;  // h_out: [0] Q, [1] error word, [2] (as uint64) sum of T
 
 extern "C" void stb_hq_release(void) {
   STB_ENTRY;
-  hq_drop();
-}
-
-// the calling thread's set on the current device, with room for nchunks block sums
-static int hq_ready(size_t nchunks) {
-  int dev = -1;
-  HIPCHK(hipGetDevice(&dev));
-  if (hq.dev >= 0 && hq.dev != dev) hq_drop();
-  if (hq.dev < 0) {
-    hq.dev = dev;
-    if (stb_pool_malloc((void **)&hq.d_ctl, 256) != hipSuccess || stb_pool_malloc((void **)&hq.h_out, 256, 1) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&hq.h_out_dev, hq.h_out, 0) != hipSuccess) {
-      hq_drop();
-      return stb_fail("stb_sample_logq: out of memory for the result words");
-    }
-  }
-  if (nchunks > hq.cap) {
-    if (hq.d_partial) stb_pool_free(hq.d_partial);
-    hq.d_partial = nullptr;
-    hq.cap = 0;
-    const size_t want = nchunks < STB_TG_CAP0_BLOCKS ? STB_TG_CAP0_BLOCKS : nchunks;
-    if (stb_pool_malloc((void **)&hq.d_partial, sizeof(double) * want) != hipSuccess)
-      return stb_fail("stb_sample_logq: out of device memory for %zu block sums", want);
-    hq.cap = want;
-  }
-  return 0;
+  stb_tset_drop(hq);
 }
 
 extern "C" int stb_hq_logq(double b, double scale, int I, const uint32_t *d_N, const uint64_t *d_coff, double *d_L,
@@ -194,12 +140,12 @@ extern "C" int stb_hq_logq(double b, double scale, int I, const uint32_t *d_N, c
   hipStream_t st = (hipStream_t)stream;
   stb_tgeom tg;
   if (stb_ticket_geom(STB_GEOM_LOGQ, (uint64_t)I, 0, 0, 0, &tg)) return stb_fail("stb_sample_logq: no launch geometry for I=%d", I);
-  if (hq_ready(tg.need)) return 1;
+  if (stb_tset_ready(hq, "stb_sample_logq") || stb_tset_room(hq, tg.need, STB_TG_CAP0_BLOCKS, sizeof(double), "stb_sample_logq")) return 1;
   const unsigned nchunks = tg.nblk, grid = tg.gx;
   const int nthr = 64 * (int)tg.waves;
   const uint64_t key = stb_mix64(seed + (sweep + 1) * STB_GAMMA);
   HIPCHK(hipMemsetAsync(hq.d_ctl, 0, 2 * sizeof(unsigned), st));
-  STB_LAUNCH(k_logq, dim3(grid), dim3(nthr), st, b, 1.0 / scale, (uint64_t)I, d_N, d_coff, d_L, key, hq.d_partial, nchunks,
+  STB_LAUNCH(k_logq, dim3(grid), dim3(nthr), st, b, 1.0 / scale, (uint64_t)I, d_N, d_coff, d_L, key, (double *)hq.d_buf, nchunks,
              hq.d_ctl, hq.h_out_dev);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
@@ -224,7 +170,7 @@ extern "C" int stb_hq_sum_u32(const uint32_t *d_T, int I, uint64_t *sum_host, vo
     *sum_host = 0;
     return 0;
   }
-  if (hq_ready(0)) return 1;
+  if (stb_tset_ready(hq, "stb_sampleb_device")) return 1;
   hipStream_t st = (hipStream_t)stream;
   unsigned long long *out_dev = (unsigned long long *)(hq.h_out_dev + 2);
   STB_LAUNCH(k_sum_u32, dim3(1), dim3(256), st, d_T, (uint64_t)I, out_dev);

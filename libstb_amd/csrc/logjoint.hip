@@ -60,7 +60,7 @@
 #include "stb_common.h"
 #include "tcounts.h"
 #include "logjoint.h"
-#include "ticket_geom.h"
+#include "ticket.h"
 
 #define LJ_BLOCK STB_TG_BLOCK  // (one constant for the kernel, the launch and stb_reduce_geometry)
 #define LJ_MAXTHREADS 512
@@ -68,19 +68,6 @@
 
 #define LJ_IMP_P 1u
 #define LJ_IMP_H 2u
-
-__device__ __forceinline__ double lj_tree(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long lj_tree_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // ctl: [0] ticket (u32); as u64 words 1 .. 4: outside, impossible (S), impossible (h), t_mismatch -- zeroed on the stream
 // ahead of the launch.  host: [0..3] pairs, base, restaurants, binom, [4] total, [5..7] (as u64) outside, impossible, t_mismatch
@@ -141,12 +128,12 @@ __global__ __launch_bounds__(LJ_MAXTHREADS) void k_logjoint(const double *table,
               c = -((lgamma((double)n) - lgamma((double)t)) - lgamma((double)(n - t) + 1.0));
           }
         }
-        dd_add(accP, lj_tree(p));
-        if (hv) dd_add(accH, lj_tree(q));
-        if (want_b) dd_add(accB, lj_tree(c));
+        dd_add(accP, stb_wave_sum(p));
+        if (hv) dd_add(accH, stb_wave_sum(q));
+        if (want_b) dd_add(accB, stb_wave_sum(c));
       }
-      sumT = lj_tree_u64(sumT);
-      sumN = lj_tree_u64(sumN);
+      sumT = stb_wave_sum(sumT);
+      sumN = stb_wave_sum(sumN);
       const unsigned any_p = __ballot(imp & LJ_IMP_P) != 0ull ? LJ_IMP_P : 0u;
       const unsigned any_h = __ballot(imp & LJ_IMP_H) != 0ull ? LJ_IMP_H : 0u;
       if (lane == 0) {
@@ -192,16 +179,16 @@ __global__ __launch_bounds__(LJ_MAXTHREADS) void k_logjoint(const double *table,
     // ---- the block's four sums, one fixed tree each
     for (unsigned q = wave; q < 4; q += nw) {
       const double *x = sx[q];
-      const double v = lj_tree((x[lane] + x[lane + 64]) + (x[lane + 128] + x[lane + 192]));
+      const double v = stb_wave_sum((x[lane] + x[lane + 64]) + (x[lane + 128] + x[lane + 192]));
       if (lane == 0) partial[(size_t)blk * 4 + q] = v;
     }
     __syncthreads();
   }
   // the counters: integers, exact in any order
-  c_out = lj_tree_u64(c_out);
-  c_imp_p = lj_tree_u64(c_imp_p);
-  c_imp_h = lj_tree_u64(c_imp_h);
-  c_mis = lj_tree_u64(c_mis);
+  c_out = stb_wave_sum(c_out);
+  c_imp_p = stb_wave_sum(c_imp_p);
+  c_imp_h = stb_wave_sum(c_imp_h);
+  c_mis = stb_wave_sum(c_mis);
   unsigned long long *cnt = (unsigned long long *)ctl;
   if (lane == 0) {
     if (c_out) __hip_atomic_fetch_add(&cnt[1], c_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -209,19 +196,7 @@ __global__ __launch_bounds__(LJ_MAXTHREADS) void k_logjoint(const double *table,
     if (c_imp_h) __hip_atomic_fetch_add(&cnt[3], c_imp_h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (c_mis) __hip_atomic_fetch_add(&cnt[4], c_mis, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  // the block sums and the counters are published by an agent-scope release ahead of the ticket; the last workgroup
-  // acquires and sums
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = __hip_atomic_fetch_add(&ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (!stb_ticket_last(ctl, gridDim.x, &s_last)) return;  // (ticket.h: the block sums and the counters are published)
   dd_t acc{0.0, 0.0};  // lanes 0 .. 3 of wave 0: one component each
   for (unsigned c0 = 0; c0 < nblk; c0 += LJ_STAGE) {
     const unsigned cn = nblk - c0 < LJ_STAGE ? nblk - c0 : LJ_STAGE;
@@ -264,51 +239,11 @@ __global__ __launch_bounds__(LJ_MAXTHREADS) void k_logjoint(const double *table,
 // per calling thread: the block sums, the ticket and counters, and the pinned words the kernel answers in.  A call
 // waits for its answer before it returns, so one set per thread is never in use twice.
 
-struct lj_ctx {
-  int dev = -1;
-  double *d_partial = nullptr;
-  size_t cap = 0;  // block sums (of four doubles) d_partial holds
-  unsigned *d_ctl = nullptr;
-  double *h_out = nullptr, *h_out_dev = nullptr;
-};
-static thread_local lj_ctx lj;
-
-static void lj_drop() {
-  if (lj.dev < 0) return;
-  stb_device_scope dev(lj.dev);
-  if (lj.d_partial) stb_pool_free(lj.d_partial);
-  if (lj.d_ctl) stb_pool_free(lj.d_ctl);
-  if (lj.h_out) stb_pool_free(lj.h_out);
-  lj = lj_ctx();
-}
+static thread_local stb_tset lj;  // d_buf: block sums of four doubles
 
 extern "C" void stb_lj_release(void) {
   STB_ENTRY;
-  lj_drop();
-}
-
-static int lj_ready(size_t nblk) {
-  int dev = -1;
-  HIPCHK(hipGetDevice(&dev));
-  if (lj.dev >= 0 && lj.dev != dev) lj_drop();
-  if (lj.dev < 0) {
-    lj.dev = dev;
-    if (stb_pool_malloc((void **)&lj.d_ctl, 256) != hipSuccess || stb_pool_malloc((void **)&lj.h_out, 256, 1) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&lj.h_out_dev, lj.h_out, 0) != hipSuccess) {
-      lj_drop();
-      return stb_fail("stb_logjoint: out of memory for the result words");
-    }
-  }
-  if (nblk > lj.cap) {
-    if (lj.d_partial) stb_pool_free(lj.d_partial);
-    lj.d_partial = nullptr;
-    lj.cap = 0;
-    const size_t want = nblk < STB_TG_CAP0_BLOCKS ? STB_TG_CAP0_BLOCKS : nblk;
-    if (stb_pool_malloc((void **)&lj.d_partial, sizeof(double) * 4 * want) != hipSuccess)
-      return stb_fail("stb_logjoint: out of device memory for %zu block sums", want);
-    lj.cap = want;
-  }
-  return 0;
+  stb_tset_drop(lj);
 }
 
 int stb_lj_check(double a, unsigned flags, int I, const char *who) {
@@ -331,12 +266,12 @@ int stb_lj_run(const double *d_table, const double *d_S1, unsigned N, unsigned M
   if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
   stb_tgeom tg;
   if (stb_ticket_geom(STB_GEOM_LOGJOINT, (uint64_t)I, 0, 0, 0, &tg)) return stb_fail("%s: no launch geometry for I=%d", who, I);
-  if (lj_ready(tg.need)) return 1;
+  if (stb_tset_ready(lj, who) || stb_tset_room(lj, tg.need, STB_TG_CAP0_BLOCKS, 4 * sizeof(double), who)) return 1;
   const unsigned nblk = tg.nblk, grid = tg.gx;
   const int nw = (int)tg.waves;
   HIPCHK(hipMemsetAsync(lj.d_ctl, 0, 64, st));
   STB_LAUNCH(k_logjoint, dim3(grid), dim3(64 * nw), st, d_table, d_S1, N, M, a, a > 0.0 ? log(a) : 0.0, d_bpar, (uint64_t)I,
-             d_koff, d_n, d_t, d_T, d_h, flags, d_Li, lj.d_partial, nblk, lj.d_ctl, lj.h_out_dev);
+             d_koff, d_n, d_t, d_T, d_h, flags, d_Li, (double *)lj.d_buf, nblk, lj.d_ctl, lj.h_out_dev);
   HIPCHK(hipGetLastError());
   if (d_Li && Li_host) HIPCHK(hipMemcpyAsync(Li_host, d_Li, sizeof(double) * (size_t)I, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

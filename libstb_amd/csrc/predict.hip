@@ -8,7 +8,7 @@
 //
 //   k_predict      a wave a restaurant, grid-stride; restaurants are independent: nobody waits for anybody
 //   k_heldout_sum  k_logjoint's shape (logjoint.hip): blocks of 256 restaurants, a wave a restaurant, the block sums added
-//                  by the last workgroup to finish (a ticket); geometry from ticket_geom.h
+//                  by the last workgroup to finish (a ticket); geometry and ticket from ticket.h
 //
 // The association (no contraction anywhere; FP64 throughout; u32 / u64 integers are exact) is the header's, word for
 // word; tests/pr_oracle.py replays it.  In short:
@@ -33,25 +33,12 @@
 
 #include "stb_common.h"
 #include "predict.h"
-#include "ticket_geom.h"
+#include "ticket.h"
 
 #define PR_BLOCK STB_TG_BLOCK  // restaurants of a block sum in k_heldout_sum
 #define PR_MAXTHREADS 512
 #define PR_STAGE 1024  // block sums the last workgroup stages in LDS at a time
 #define PR_CUST 4      // customers whose row loads are in flight before the first tree
-
-__device__ __forceinline__ double pr_tree(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long pr_tree_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // dynamic LDS: STB_TD_MAXK doubles a wave
 __global__ __launch_bounds__(PR_MAXTHREADS) void k_predict(double a, const double *bpar, uint64_t I, const uint64_t *koff,
@@ -84,8 +71,8 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_predict(double a, const doubl
       sT += tv[k0 + k];
       sN += nv[k0 + k];
     }
-    sT = __shfl(pr_tree_u64(sT), 0, 64);
-    sN = __shfl(pr_tree_u64(sN), 0, 64);
+    sT = __shfl(stb_wave_sum(sT), 0, 64);
+    sN = __shfl(stb_wave_sum(sN), 0, 64);
     // ---- theta: a lane a dish
     const double b = bpar[i], Td = (double)sT, Nd = (double)sN;
     const double g = b + Td * a, den = b + Nd;
@@ -130,7 +117,7 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_predict(double a, const doubl
             L[c] = k < Ki ? (lik ? (cls[c] < rows ? lik[(size_t)cls[c] * stride + k] : 0.0) : 1.0) : 0.0;
 #pragma unroll
           for (int c = 0; c < PR_CUST; c++) {
-            const double s = pr_tree(k < Ki ? th * L[c] : 0.0);
+            const double s = stb_wave_sum(k < Ki ? th * L[c] : 0.0);
             acc[c] = j == 0 ? s : acc[c] + s;
           }
         }
@@ -178,7 +165,7 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_heldout_sum(const double *p, 
             c_imp++;
           }
         }
-        dd_add(acc, pr_tree(x));
+        dd_add(acc, stb_wave_sum(x));
       }
       const unsigned any = __ballot(bad) != 0ull ? 1u : 0u;
       if (lane == 0) {
@@ -198,27 +185,15 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_heldout_sum(const double *p, 
     __syncthreads();
     // ---- the block's sum, the one fixed tree
     if (wave == 0) {
-      const double v = pr_tree((sx[lane] + sx[lane + 64]) + (sx[lane + 128] + sx[lane + 192]));
+      const double v = stb_wave_sum((sx[lane] + sx[lane + 64]) + (sx[lane + 128] + sx[lane + 192]));
       if (lane == 0) partial[blk] = v;
     }
     __syncthreads();
   }
-  c_imp = pr_tree_u64(c_imp);
+  c_imp = stb_wave_sum(c_imp);
   unsigned long long *cnt = (unsigned long long *)ctl;
   if (lane == 0 && c_imp) __hip_atomic_fetch_add(&cnt[1], c_imp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // the block sums and the counter are published by an agent-scope release ahead of the ticket; the last workgroup
-  // acquires and sums
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = __hip_atomic_fetch_add(&ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (!stb_ticket_last(ctl, gridDim.x, &s_last)) return;  // (ticket.h: the block sums and the counter are published)
   dd_t tot{0.0, 0.0};  // thread 0's
   for (unsigned b0 = 0; b0 < nblk; b0 += PR_STAGE) {
     const unsigned bn = nblk - b0 < PR_STAGE ? nblk - b0 : PR_STAGE;
@@ -242,51 +217,11 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_heldout_sum(const double *p, 
 // per calling thread: the block sums, the ticket and counter, and the pinned words k_heldout_sum answers in.  A call
 // waits for its answer before it returns, so one set per thread is never in use twice.
 
-struct pr_ctx {
-  int dev = -1;
-  double *d_partial = nullptr;
-  size_t cap = 0;  // block sums d_partial holds
-  unsigned *d_ctl = nullptr;
-  double *h_out = nullptr, *h_out_dev = nullptr;
-};
-static thread_local pr_ctx pr;
-
-static void pr_drop() {
-  if (pr.dev < 0) return;
-  stb_device_scope dev(pr.dev);
-  if (pr.d_partial) stb_pool_free(pr.d_partial);
-  if (pr.d_ctl) stb_pool_free(pr.d_ctl);
-  if (pr.h_out) stb_pool_free(pr.h_out);
-  pr = pr_ctx();
-}
+static thread_local stb_tset pr;
 
 extern "C" void stb_pr_release(void) {
   STB_ENTRY;
-  pr_drop();
-}
-
-static int pr_ready(size_t nblk) {
-  int dev = -1;
-  HIPCHK(hipGetDevice(&dev));
-  if (pr.dev >= 0 && pr.dev != dev) pr_drop();
-  if (pr.dev < 0) {
-    pr.dev = dev;
-    if (stb_pool_malloc((void **)&pr.d_ctl, 256) != hipSuccess || stb_pool_malloc((void **)&pr.h_out, 256, 1) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&pr.h_out_dev, pr.h_out, 0) != hipSuccess) {
-      pr_drop();
-      return stb_fail("stb_heldout_loglik: out of memory for the result words");
-    }
-  }
-  if (nblk > pr.cap) {
-    if (pr.d_partial) stb_pool_free(pr.d_partial);
-    pr.d_partial = nullptr;
-    pr.cap = 0;
-    const size_t want = nblk < STB_TG_CAP0_BLOCKS ? STB_TG_CAP0_BLOCKS : nblk;
-    if (stb_pool_malloc((void **)&pr.d_partial, sizeof(double) * want) != hipSuccess)
-      return stb_fail("stb_heldout_loglik: out of device memory for %zu block sums", want);
-    pr.cap = want;
-  }
-  return 0;
+  stb_tset_drop(pr);
 }
 
 // STB_PREDICT_WAVES where it names a workgroup size, else 0
@@ -331,9 +266,9 @@ int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned sa
   stb_tgeom tg;  // k_logjoint's geometry; the workgroup size from STB_PREDICT_WAVES where it is set
   if (stb_ticket_geom(STB_GEOM_LOGJOINT, (uint64_t)I, 0, 0, pr_env_waves(), &tg))
     return stb_fail("%s: no launch geometry for I=%d", who, I);
-  if (pr_ready(tg.need)) return 1;
+  if (stb_tset_ready(pr, who) || stb_tset_room(pr, tg.need, STB_TG_CAP0_BLOCKS, sizeof(double), who)) return 1;
   HIPCHK(hipMemsetAsync(pr.d_ctl, 0, 64, st));
-  STB_LAUNCH(k_heldout_sum, dim3(tg.gx), dim3(64 * tg.waves), st, d_p, d_hoff, (uint64_t)I, (double)samples, d_Hi, pr.d_partial,
+  STB_LAUNCH(k_heldout_sum, dim3(tg.gx), dim3(64 * tg.waves), st, d_p, d_hoff, (uint64_t)I, (double)samples, d_Hi, (double *)pr.d_buf,
              tg.nblk, pr.d_ctl, pr.h_out_dev, (const unsigned long long *)d_skipped);
   HIPCHK(hipGetLastError());
   if (d_Hi && Hi_host) HIPCHK(hipMemcpyAsync(Hi_host, d_Hi, sizeof(double) * (size_t)I, hipMemcpyDeviceToHost, st));

@@ -630,6 +630,77 @@ def test_objects_at_a_second_trip_equal_the_raw_calls(kind):
         L.stb_sampler_cache_clear()
 
 
+def test_one_thread_interleaves_the_ticket_families():
+    """the five per-thread sets of the ticket kernels (csrc/ticket.h) next to each other in one thread, at 257 restaurants:
+    one full block and a block of one restaurant, the smallest launch in which the ticket decides anything.  Every call alone
+    behind a stb_sampler_cache_clear, then the five back to back, then in the reverse order: the same bytes every time (no
+    state passes between the sets), and a set dropped twice is made again whole."""
+    import torch
+
+    L = capi.lib()
+    I = 257
+    a, M, indicators, _ = CONFIGS[0]
+    (K, n, t, h, bpar), per, _ = clean_types(0)
+    tabs = device_tables(a, M)
+    tl = Tiled(K, n, t, h, bpar, per["T"], I)
+    Nd = dev(tl.tile(per["Nc"]), np.uint32)
+    for which in (capi.GEOM_LOGQ, capi.GEOM_JOINT_TERMS, capi.GEOM_LOGJOINT):
+        g = capi.reduce_geometry(which, I, 3, 2)
+        assert g.blocks == 2 and g.grid_x == 2, which
+    rng = np.random.default_rng(611)
+    p, hoff = dev(0.01 + rng.random(I), np.float64), dev(np.arange(I + 1), np.uint64)
+    b0 = np.repeat([0.7, 5.0], [100, I - 100])   # (a group's restaurants share its concentration)
+    kend = int(np.cumsum(K)[I - 1])
+    obj = capi.TableCounts(K[:I], n[:kend], t[:kend])
+    obj.set_bgroups(np.array([0, 100, I], dtype=np.uint64))
+
+    def logq():
+        Q, Lt = capi.sample_logq(0.7, 20.0, Nd, seed=31, sweep=2)
+        assert math.isfinite(Q) and Q > 1 / 20.0
+        return np.float64(Q).tobytes(), Lt.cpu().numpy().tobytes()
+
+    def terms():
+        R = capi.joint_terms([0.2, 0.5, 0.8], [0.5, 3.0], tl.T, Nd)
+        torch.cuda.synchronize()
+        R = R.cpu().numpy()
+        assert R.shape == (3, 2) and np.isfinite(R).all() and (R != 0.0).all()
+        return (R.tobytes(),)
+
+    def logjoint():
+        tot, Li, info = tl.run(tabs, a, indicators)
+        assert math.isfinite(tot) and info.impossible == 0
+        return np.float64(tot).tobytes(), Li.tobytes(), bytes(info)
+
+    def heldout():
+        tot, Hi, info = capi.heldout_loglik(p, hoff)
+        torch.cuda.synchronize()
+        assert math.isfinite(tot) and info.customers == I
+        return np.float64(tot).tobytes(), Hi.cpu().numpy().tobytes(), bytes(info)
+
+    def bstep():
+        obj.set_bpar(b0)
+        bg, info = obj.sampleb_groups(a, 1.1, 20.0, seed=41, sweep=3)
+        assert info.kept_groups == 0 and np.isfinite(bg).all() and (bg > 0).all()
+        return bg.tobytes(), bytes(info), obj.get_bpar().tobytes()
+
+    calls = [logq, terms, logjoint, heldout, bstep]
+    try:
+        alone = []
+        for f in calls:
+            L.stb_sampler_cache_clear()
+            alone.append(f())
+        forward = [f() for f in calls]
+        backward = [f() for f in reversed(calls)][::-1]
+        for f, x, y, z in zip(calls, alone, forward, backward):
+            assert x == y and x == z, f.__name__
+        L.stb_sampler_cache_clear()
+        L.stb_sampler_cache_clear()
+        assert logq() == alone[0]
+    finally:
+        obj.free()
+        L.stb_sampler_cache_clear()
+
+
 # ---- refusals of the raw call
 
 def test_the_raw_call_refuses_before_anything_is_queued():

@@ -197,6 +197,56 @@ def test_past_one_block_per_workgroup(monkeypatch):
     check_big(I, monkeypatch)
 
 
+def test_heldout_outgrows_the_block_sums_and_the_calls_after_it():
+    """stb_heldout_loglik one block sum past what its first buffer holds, a call of two blocks in the larger buffer, and the
+    large call again.  One held-out customer a restaurant, so H_i = log p_i and the kernel's value for a customer depends
+    on p_i alone; the p are 257 values tiled, restaurant i of value i mod 257.  The 257 alone are held to the replay as
+    check_big holds them (one logarithm: numpy's to the last bits of either), and every H_i of the large call has the
+    bits of its customer's value there.  The totals: the replay's block trees and ordered double-double sum of the
+    replayed H_i, within check_big's bar."""
+    cap0 = int(pr_geom(1).cap0)
+    big, small = cap0 * 256 + 1, 257
+    gb, gs = pr_geom(big), pr_geom(small)
+    assert gb.need == gb.cap0 + 1 and gb.need == gb.blocks and gs.need == 2 <= gs.cap0
+    p_types = 0.001 + np.random.default_rng(4300).random(small)
+
+    def case(I):
+        """(p and hoff on the device, the replayed H_i, the replayed total, its bar)"""
+        Hi_types, _, nimp = pro.heldout_replay(p_types, np.arange(small + 1))
+        assert nimp == 0
+        Hi = np.resize(Hi_types, I)
+        full = np.zeros(-(-I // 256) * 256)
+        full[:I] = Hi
+        total = float(pro.ordered_dd_sum(pro.block_tree(full.reshape(-1, 256))))
+        mag = float(np.abs(Hi).sum())
+        bar = 4.0 * U * mag + 8.0 * U * mag + U * (2.0 * abs(total) + 16.0)
+        return dev(np.resize(p_types, I), np.float64), dev(np.arange(I + 1), np.uint64), Hi, total, bar
+
+    def run(p, hoff, Hi, total, bar, what):
+        import torch
+
+        tot, Hd, info = capi.heldout_loglik(p, hoff)
+        torch.cuda.synchronize()
+        Hd = Hd.cpu().numpy()
+        print(what, "total", tot, "replay", total, "difference", tot - total, "bar", bar)
+        assert abs(tot - total) <= bar and np.all(np.abs(Hd - Hi) <= 4.0 * U * np.abs(Hi))
+        assert info.impossible == 0 and info.skipped == 0 and info.customers == Hi.shape[0]
+        return Hd, (np.float64(tot).tobytes(), Hd.tobytes(), bytes(info))
+
+    cs, cb = case(small), case(big)
+    H_types, _ = run(*cs, "the 257 alone")
+    capi.lib().stb_sampler_cache_clear()   # (this thread's buffer of block sums: the next call allocates afresh)
+    try:
+        Hb, ref_b = run(*cb, "regrow")         # more than the first buffer would hold
+        assert same_bits(Hb, np.resize(H_types, big)) and Hb[-1] != 0.0
+        Hs, ref_s = run(*cs, "after the larger call")   # a smaller call in the larger buffer
+        assert same_bits(Hs, H_types)
+        Hb2, ref_b2 = run(*cb, "the large call again")
+        assert ref_b2 == ref_b
+    finally:
+        capi.lib().stb_sampler_cache_clear()
+
+
 # ---- 4. accumulation over states
 
 def small_object(seed=21):
