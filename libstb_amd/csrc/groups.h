@@ -1,8 +1,10 @@
-// groups.h -- the device-resident group set (stb_groups_t) as the translation units that work on it see it:
-// groups.hip (creation, evaluation), lists.hip (the cell lists of the fused evaluation built from a count slab,
-// the pairs' way to the device).
+// groups.h -- the device-resident group set (stb_groups_t) as the translation units that work on it see it: groups.hip
+// (creation, the evaluation flow), lists.hip (the cell lists of the fused evaluation: lifetime, the builder from a count
+// slab, helper jobs), lists_sorted.hip (the sort-based builder), pairs.hip (the pairs' way to the device).
 #ifndef STB_GROUPS_H
 #define STB_GROUPS_H
+
+#include <vector>
 
 #include "stb_common.h"
 
@@ -18,6 +20,26 @@ struct slab_info {
   unsigned UCp;          // words of a row of an item: column 1 (strip 0 only) + the strip's own columns
   const unsigned *rec_off;
 };
+
+// The cell lists of one layout of the fused evaluation's sparse form: CSR of the occurring cells per item, built when
+// first needed.  Layouts: [0] (trip, 64-column slice from column 1) for k_fill_chain, [1] the same from column 2 for
+// k_fill_ck, [2] (tile, group of 4 rows) for k_fill_hb's tile workers, [3] / [4] (strip, block, group of G rows) for
+// k_grid_hb's self-summing spine with 2 / 4 columns per lane, [5] with 8 (column 1 -- the pairs with t = 1 -- included)
+struct stb_cell_list {
+  unsigned *item_ptr;  // CSR of the occurring cells per item
+  unsigned short *ent_pos;
+  unsigned *ent_cnt;
+  // the grid layouts only: first tile of every strip (grid_hb.hip); the listed cells as words per lane, group after group
+  // (what the walk reads); per tile, where its words start and how many a group has; the tiles whose cells are left to helper
+  // waves, in the order they become ready; per tile its place in jobs, or 0xffffffff; words per group and first word of
+  // every tile (the dense layout), kept from build to build
+  unsigned *tile_off, *dense, *tinfo, *jobs, *tjob, *tnw, *toff;
+  unsigned n_jobs;
+  int ready, R, G;             // R, G: the block and group length the list was built for
+  size_t ent_cap, dense_cap;  // entries / dense words the buffers hold (0: sized exactly by the sort-based builder)
+};
+// built by the count slab: the buffers hold the most G pairs can need and stay from hand-over to hand-over; log-0 pairs in d_ninf
+static inline bool stb_list_from_slab(const stb_cell_list &l) { return l.ent_cap != 0; }
 
 // ------------------------------------------------------------------------------------------------
 // device-resident group set
@@ -46,22 +68,9 @@ struct stb_groups {
   double *d_dotp;
   size_t dotp_elems;
   int fused, fused_ready;
-  // sparse form of the fused evaluation: CSR of the occurring cells per item, in several layouts, each built when
-  // first needed: [0] (trip, 64-column slice from column 1) for k_fill_chain, [1] the same from column 2 for
-  // k_fill_ck, [2] (tile, group of 4 rows) for k_fill_hb's tile workers, [3] / [4] (strip, block, group of G rows)
-  // for k_grid_hb's self-summing spine with 2 / 4 columns per lane, [5] with 8 (column 1 -- the pairs with t = 1 -- included)
-  unsigned *d_item_ptr[STB_NLISTS];
-  unsigned short *d_ent_pos[STB_NLISTS];
-  unsigned *d_ent_cnt[STB_NLISTS];
+  // sparse form of the fused evaluation: a cell list per layout
+  stb_cell_list lists[STB_NLISTS];
   unsigned nsg;
-  int lists_ready[STB_NLISTS];
-  int list_R[STB_NLISTS], list_G[STB_NLISTS];  // [3], [4]: the block and group length the list was built for
-  unsigned *d_tile_off[STB_NLISTS];            // [3], [4]: first tile of every strip (grid_hb.hip)
-  unsigned *d_dense[STB_NLISTS];               // [3], [4]: the listed cells as words per lane, group after group: what the walk reads
-  unsigned *d_tinfo[STB_NLISTS];               // [3], [4]: per tile, where its words start and how many a group has
-  unsigned *d_jobs[STB_NLISTS];                // [3], [4]: the tiles whose cells are left to helper waves, in the order they become ready
-  unsigned *d_tjob[STB_NLISTS];                // [3], [4]: per tile its place in d_jobs, or 0xffffffff
-  unsigned n_jobs[STB_NLISTS];
   int hb_sum_C;                                // columns per lane of the halo-block summing form's strips for this set (stb_hb_sum_C at its creation)
   uint64_t n_inf;                              // pairs whose S_S is log 0 (t = 0, t > n, outside the bounds)
   int sparse;
@@ -83,7 +92,7 @@ struct stb_groups {
   double *pend_out;
   double pend_x[STB_TERMS_DMAX];
   last_fill pend_fill;
-  // ---- the pairs' way to the device (lists.hip).  A caller whose counts change between calls -- every Gibbs sampler:
+  // ---- the pairs' way to the device (pairs.hip).  A caller whose counts change between calls -- every Gibbs sampler:
   // the reference's own loop rewrites t[j][i] / T[j] each iteration, test/demo.c:405-445 -- hands the new pairs over
   // piece by piece (stb_groups_pairs_put); each piece is copied into pinned memory and goes to the device while the
   // caller is still copying the next.
@@ -100,7 +109,7 @@ struct stb_groups {
   // ---- cell lists from a count slab (lists.hip): a word per cell of the (tile, group) items, zero between builds
   unsigned *d_slab;
   size_t slab_elems;
-  int slab_which;              // the layout the slab is laid out for (2, 3, 4), with list_R / list_G / Dmax-dependent geometry below
+  int slab_which;              // the layout the slab is laid out for (2, 3, 4), with the R / G / Dmax-dependent geometry below
   int slab_R, slab_G, slab_UCp;
   unsigned slab_items;
   int slab_clean;              // every word of it is zero
@@ -108,9 +117,6 @@ struct stb_groups {
   unsigned long long *d_ninf;  // pairs whose S_S is log 0, counted on the device
   void *d_scan_tmp;
   size_t scan_tmp_bytes;
-  size_t ent_cap[STB_NLISTS];  // entries the list buffers of a layout hold (0: sized exactly by the sort-based builder)
-  size_t dense_cap[STB_NLISTS];
-  unsigned *d_tnw[STB_NLISTS], *d_toff[STB_NLISTS];  // [3] .. [5]: words per group and first word of every tile (the dense layout), kept
   // ---- the gradient in the discount (groups_da.hip): Dmax tables of g = d log S / da and their dS1 vectors, private to the
   // set, asked for when the first stb_groups_aterms_grad comes and sized by the bounds they were made for (da_N, da_M)
   double *d_gtab, *d_dS1g, *d_gout;  // d_gout: [2][Dmax] pair sums, restaurant terms
@@ -155,14 +161,31 @@ __device__ __forceinline__ unsigned stb_block_exclusive_1024(unsigned mine, unsi
 }
 #endif
 
-// lists.hip
-int stb_lists_slab_build(stb_groups_t *g, int which, int D, const hb_dot_info &H, const grid_geom &gg);  // 0 built (queued), 1 error, 2 not applicable
+// the grid form's dense layout: more words per lane than NWMAX, or a count beyond a word, and the tile is read from the CSR lists (NW = 63)
+#define STB_DENSE_NWMAX 40
+#define STB_DENSE_CSR 63u
+
+void stb_grid_tile_offsets(const grid_geom &g, std::vector<unsigned> &off);  // grid_hb.hip
+
+// lists.hip.  stb_list_release gives a list's buffers back: what a builder sizes for the pairs at hand (CSR entries, dense
+// words, the tiles' entries, helper jobs; both capacities to 0), and with_shape also what depends on the strip shape alone (tile
+// offsets, the tiles' word counts and first words), after which nothing is ready and there are no jobs.  The stream is idle.
+void stb_list_release(stb_cell_list &l, bool with_shape);
 void stb_lists_drop(stb_groups_t *g, bool keep_capacity);   // new pairs or new bounds: what was built from the old ones goes
-void stb_groups_new_pairs(stb_groups_t *g, int reused);     // the set's d_n / d_t hold new pairs
+void stb_list_request(const stb_groups_t *g, int which, dot_request *req);  // the list of layout `which` as the launchers take it
+// The list of layout `which` (3: whichever grid layout D discounts take), built where it is not there.  Returns 0 and sets
+// g->sparse = 1 when the sparse form was built, 0 with g->sparse = 0 when the pairs are too dense for it to pay (the caller
+// then builds the count slab), non-zero on error.
+int stb_lists_build(stb_groups_t *g, int which, int D);
+int stb_lists_slab_build(stb_groups_t *g, int which, int D, const hb_dot_info &H, const grid_geom &gg);  // 0 built (queued), 1 error, 2 not applicable
+int stb_lists_jobs_device(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *tnw);  // the helper jobs from the tiles' words per group on the device
+int stb_lists_jobs_from(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *h_nw);   // ... and on the host
+int stb_lists_sort_build(stb_groups_t *g, int which, int D, const hb_dot_info &H, const grid_geom &gg);  // lists_sorted.hip: returns as stb_lists_build
+void stb_groups_new_pairs(stb_groups_t *g, int reused);     // pairs.hip: the set's d_n / d_t hold new pairs
+// groups.hip
 int stb_groups_set_bounds(stb_groups_t *g, unsigned N, unsigned M);
-int stb_groups_sort_pairs(stb_groups_t *g);                  // groups.hip
+int stb_groups_sort_pairs(stb_groups_t *g);
 int stb_groups_alloc_dotp(stb_groups_t *g);
-int stb_lists_jobs_device(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *tnw);
 
 // groups.hip: what a resident-count object (stb_tcounts, stb_tindic) shows of itself when it hands its pairs to a set
 struct stb_counts_view {

@@ -1,17 +1,10 @@
 // groups.hip -- stb_groups_*: the (n,t) pairs and per-restaurant totals of one samplea call resident
-// in HBM, and aterms (reference lib/samplea.c:46-83) evaluated on them for one discount or a grid.
+// in HBM, and aterms (reference lib/samplea.c:46-83) evaluated on them for one discount or a grid: the set's lifetime, the
+// choice of form, the evaluation flow.  The cell lists: lists.hip, lists_sorted.hip; the pairs' way to the device: pairs.hip.
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
 
-#include <algorithm>
 #include <atomic>
-#include <vector>
-
-#include "stb_common.h"
-
-void stb_grid_tile_offsets(const grid_geom &g, std::vector<unsigned> &off);  // grid_hb.hip
 
 #include "groups.h"
 
@@ -78,12 +71,9 @@ extern "C" void stb_groups_free(stb_groups_t *g) {
   std::vector<void *> ptrs = {g->d_n, g->d_T, g->d_t, g->d_bpar, g->d_tables, g->d_S1, g->d_out, g->d_ws_fill, g->d_ws_sweep, g->d_ws_terms,
                               g->d_cnt, g->d_n2, g->d_t2, g->d_dotp, g->d_slab, g->d_icnt, g->d_ninf, g->d_scan_tmp,
                               g->d_gtab, g->d_dS1g, g->d_gout, g->d_ws_da, g->d_ws_dasweep};
-  for (int w = 0; w < STB_NLISTS; w++)
-    for (void *q : {(void *)g->d_item_ptr[w], (void *)g->d_ent_pos[w], (void *)g->d_ent_cnt[w], (void *)g->d_tile_off[w], (void *)g->d_dense[w],
-                    (void *)g->d_tinfo[w], (void *)g->d_jobs[w], (void *)g->d_tjob[w], (void *)g->d_tnw[w], (void *)g->d_toff[w]})
-      ptrs.push_back(q);
   if (g->st) (void)hipStreamSynchronize(g->st);  // nothing may still be using the buffers
   for (void *p : ptrs) stb_pool_free(p);
+  for (stb_cell_list &l : g->lists) stb_list_release(l, true);
   stb_pool_free(g->h_out);
   stb_pool_free(g->h_pn);
   stb_pool_free(g->h_pt);
@@ -259,6 +249,10 @@ static stb_groups_t *groups_create_here(int I, const int *K, const uint32_t *T, 
   g->Dmax = Dmax;
   GCHK(hipStreamCreate(&g->st));
   for (auto &e : g->ev) GCHK(hipEventCreate(&e));
+  // (the runtime brings a file's kernels to the device on first use: k_eval_tail closes the span an evaluation measures from
+  // its walk's start, so it is there before a walk is queued -- not loaded, for milliseconds, between the two launches)
+  hipFuncAttributes tail_attr;
+  GCHK(hipFuncGetAttributes(&tail_attr, reinterpret_cast<const void *>(k_eval_tail)));
   GCHK(stb_pool_malloc((void **)&g->d_n, sizeof(uint32_t) * (G ? G : 1)));
   GCHK(stb_pool_malloc((void **)&g->d_t, sizeof(uint16_t) * (G ? G : 1)));
   GCHK(stb_pool_malloc((void **)&g->d_T, sizeof(uint32_t) * (I > 0 ? I : 1)));
@@ -299,7 +293,7 @@ static stb_groups_t *groups_create_here(int I, const int *K, const uint32_t *T, 
   return g;
 }
 
-// the pairs in (n, t) order, for the gather over stored tables (on first need: see lists.hip)
+// the pairs in (n, t) order, for the gather over stored tables (on first need: see pairs.hip)
 int stb_groups_sort_pairs(stb_groups_t *g) {
   if (g->sorted || !stb_env_int("STB_SORT_PAIRS", 1)) return 0;
   if (sort_pairs(g->d_n, g->d_t, g->G, g->st)) return 1;
@@ -314,174 +308,6 @@ extern "C" stb_groups_t *stb_groups_create(int I, const int *K, const uint32_t *
   STB_ENTRY;
   stb_device_scope dev(stb_get_device());
   return groups_create_here(I, K, T, nflat, tflat, bpar, N, M, Dmax);
-}
-
-// ---- sparse set-up of the fused evaluation, all on the device -----------------------------------
-#define STB_KEY_OTHER 0xfffffffffffffffeull  // a pair that addresses no table cell (t = 1, t = n, out of bounds)
-#define STB_KEY_SKIP 0xffffffffffffffffull   // n <= 1: contributes nothing (lib/samplea.c:78)
-
-// key of a pair: (item index << 9) | (row in trip << 6) | column in slice, item = trip * nsg + slice
-__global__ void k_item_keys(const uint32_t *n, const uint16_t *t, uint64_t G, unsigned N, unsigned M, unsigned nsg,
-                            unsigned col0, uint64_t *key, uint32_t *payload) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= G) return;
-  const unsigned nn = n[g], tt = t[g];
-  uint64_t k;
-  if (nn <= 1) k = STB_KEY_SKIP;
-  else if (nn == tt || tt <= 1 || nn < tt || tt > M || nn > N) k = STB_KEY_OTHER;
-  else {
-    const unsigned trip = (nn - 3) >> 3, u = (nn - 3) & 7, sg = (tt - col0) >> 6, ln = (tt - col0) & 63;  // (tt >= 2)
-    k = (((uint64_t)trip * nsg + sg) << 9) | (u << 6) | ln;
-  }
-  key[g] = k;
-  payload[g] = (uint32_t)g;
-}
-
-// the same for the tiles of k_fill_hb: key = (item << 11) | (row in group << 8) | element of the wave (halo included),
-// item = (record index of tile (strip, block)) * NQ + group of H.G rows; row n belongs to block (n - 2) / R
-__global__ void k_item_keys_hb(const uint32_t *n, const uint16_t *t, uint64_t G, unsigned N, unsigned M, hb_dot_info H,
-                               uint64_t *key, uint32_t *payload) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= G) return;
-  const unsigned nn = n[g], tt = t[g];
-  uint64_t k;
-  // (column 1 -- t = 1 -- is a cell too: the last element of strip 0's halo, which that strip's tiles compute along;
-  // a pair with t = n contributes log 1 = 0; what is left as "other" has S_S = log 0, lib/stable.c:948-949)
-  if (nn <= 1 || nn == tt) k = STB_KEY_SKIP;
-  else if (tt == 0 || nn < tt || tt > M || nn > N) k = STB_KEY_OTHER;
-  else {
-    unsigned j = 0, cw = (unsigned)H.HC - 1u;  // t = 1
-    if (tt >= 2) {
-      const unsigned e = tt - 2;
-      j = e / (unsigned)H.UC;
-      cw = (unsigned)H.HC + (e - j * (unsigned)H.UC);
-    }
-    const unsigned b = (nn - 2) / (unsigned)H.R, r = (nn - 2) - b * (unsigned)H.R;
-    const unsigned b0 = (unsigned)(((unsigned long long)j * (unsigned)H.UC) / (unsigned)H.R);
-    const unsigned rec = H.rec_off[j + 1] + (b - b0);  // (b >= b0: the cell lies on or below the diagonal)
-    const unsigned q = r / (unsigned)H.G;
-    k = ((((uint64_t)rec * (unsigned)H.NQ) + q) << 11) | ((uint64_t)(r - q * (unsigned)H.G) << 8) | cw;
-  }
-  key[g] = k;
-  payload[g] = (uint32_t)g;
-}
-
-// ... and for the strips of the grid form (grid_hb.hip): key = (item << 13) | (row in group << 8) | element of the wave,
-// item = (record index of tile (strip, block)) * NQ + group of G rows.  Column 1 (t = 1) is a cell too -- the last
-// element of strip 0's halo, which that strip computes along -- and a pair with t = n contributes log 1 = 0: what is
-// left as "other" are the pairs whose S_S is log 0 (lib/stable.c:948-949).
-__global__ void k_item_keys_hb2(const uint32_t *n, const uint16_t *t, uint64_t G, unsigned N, unsigned M, hb_dot_info H, int posbits,
-                                uint64_t *key, uint32_t *payload) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= G) return;
-  const unsigned nn = n[g], tt = t[g];
-  uint64_t k;
-  if (nn <= 1 || nn == tt) k = STB_KEY_SKIP;
-  else if (tt == 0 || nn < tt || tt > M || nn > N) k = STB_KEY_OTHER;
-  else {
-    unsigned j = 0, cw = (unsigned)H.HC - 1u;  // t = 1
-    if (tt >= 2) {
-      const unsigned e = tt - 2;
-      j = e / (unsigned)H.UC;
-      cw = (unsigned)H.HC + (e - j * (unsigned)H.UC);
-    }
-    const unsigned b = (nn - 2) / (unsigned)H.R, r = (nn - 2) - b * (unsigned)H.R;
-    const unsigned b0 = (unsigned)(((unsigned long long)j * (unsigned)H.UC) / (unsigned)H.R);
-    const unsigned rec = H.rec_off[j + 1] + (b - b0);
-    const unsigned q = r / (unsigned)H.G;
-    k = ((((uint64_t)rec * (unsigned)H.NQ) + q) << (posbits + 5)) | ((uint64_t)(r - q * (unsigned)H.G) << posbits) | cw;
-  }
-  key[g] = k;
-  payload[g] = (uint32_t)g;
-}
-
-// counts[0] = keys below STB_KEY_OTHER (table cells), counts[1] = keys equal to it
-__global__ void k_key_bounds(const uint64_t *key, uint64_t G, uint64_t *counts) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  uint64_t lo = 0, hi = G;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) / 2;
-    if (key[mid] < STB_KEY_OTHER) lo = mid + 1;
-    else hi = mid;
-  }
-  const uint64_t a = lo;
-  hi = G;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) / 2;
-    if (key[mid] <= STB_KEY_OTHER) lo = mid + 1;
-    else hi = mid;
-  }
-  counts[0] = a;
-  counts[1] = lo - a;
-}
-
-__global__ void k_gather_pairs(const uint32_t *n, const uint16_t *t, const uint32_t *idx, uint64_t cnt, uint32_t *n2,
-                               uint16_t *t2) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g < cnt) {
-    n2[g] = n[idx[g]];
-    t2[g] = t[idx[g]];
-  }
-}
-
-__global__ void k_split_runs(const uint64_t *ukey, const unsigned *runs, unsigned short *pos, unsigned *item, int posbits) {
-  const unsigned r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < *runs) {
-    pos[r] = (unsigned short)(ukey[r] & ((1u << posbits) - 1u));
-    item[r] = (unsigned)(ukey[r] >> posbits);
-  }
-}
-
-// The grid form's dense layout.  A listed cell is one word, position | count << 13; a (tile, group of rows) holds its
-// cells in NW words per lane -- NW the same for the NQ groups of a tile: the most any of them needs -- at an address that
-// needs no look-up beyond the tile's own entry of `tinfo` (first word / 64 << 6 | NW), which the walking wave asks for a
-// block ahead: a group's cells are coalesced loads issued ahead of their use, whether it holds 20 cells or 2000 (the
-// pairs of a 10^4 x 10^4 table thin out like 1 / n: its first 4000 rows hold more than 63 cells per group of 12 x 208).
-// NW = 63 marks a tile taken from the CSR lists instead (a count of 2^19 or more, or more words than STB_DENSE_NWMAX).
-#define STB_DENSE_NWMAX 40
-#define STB_DENSE_CSR 63u
-__global__ void k_tile_words(const unsigned *item_ptr, const unsigned *cnt, unsigned n_tiles, unsigned NQ, int wbits, unsigned *tnw, unsigned *twords) {
-  const unsigned t = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
-  if (t >= n_tiles) return;
-  const unsigned e0 = item_ptr[(size_t)t * NQ], e1 = item_ptr[(size_t)t * NQ + NQ];
-  unsigned nw = 0;
-  for (unsigned q = 0; q < NQ; q++) {
-    const unsigned c = item_ptr[(size_t)t * NQ + q + 1] - item_ptr[(size_t)t * NQ + q];
-    nw = max(nw, (c + 63) / 64);
-  }
-  bool big = false;
-  for (unsigned e = e0 + lane; e < e1; e += 64) big = big || cnt[e] >= (1u << (32 - wbits));  // (a word is position | count << wbits)
-  if (__any(big) || nw > STB_DENSE_NWMAX) nw = STB_DENSE_CSR;
-  if (lane == 0) {
-    tnw[t] = nw;
-    twords[t] = (nw == STB_DENSE_CSR) ? 0u : nw * NQ;
-  }
-}
-
-__global__ void k_dense_fill(const unsigned *item_ptr, const unsigned short *pos, const unsigned *cnt, unsigned nitems, unsigned NQ, int wbits,
-                             const unsigned *tnw, const unsigned *toff, unsigned *dense, unsigned *tinfo) {
-  const unsigned i = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
-  if (i >= nitems) return;
-  const unsigned t = i / NQ, q = i - t * NQ;
-  const unsigned nw = tnw[t];
-  if (q == 0 && lane == 0) tinfo[t] = (toff[t] << 6) | nw;
-  if (nw == STB_DENSE_CSR) return;
-  const unsigned e0 = item_ptr[i], e1 = item_ptr[i + 1];
-  unsigned *dst = dense + ((size_t)toff[t] + (size_t)q * nw) * 64;
-  for (unsigned k = lane; k < nw * 64; k += 64) dst[k] = (e0 + k < e1) ? ((unsigned)pos[e0 + k] | (cnt[e0 + k] << wbits)) : 0u;
-}
-
-// item_ptr[i] = first run whose item index is >= i
-__global__ void k_item_ptr(const unsigned *item, const unsigned *runs, unsigned nitems, unsigned *ptr) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > nitems) return;
-  unsigned lo = 0, hi = *runs;
-  while (lo < hi) {
-    const unsigned mid = (lo + hi) / 2;
-    if (item[mid] < i) lo = mid + 1;
-    else hi = mid;
-  }
-  ptr[i] = lo;
 }
 
 // partial sums of the fused forms: (column blocks of 64) x 16 waves per table for the chain form, one per tile for the
@@ -505,399 +331,6 @@ int stb_groups_alloc_dotp(stb_groups_t *g) {
   if (hb2 > g->dotp_elems) g->dotp_elems = hb2;
   if (stb_pool_malloc((void **)&g->d_dotp, sizeof(double) * g->dotp_elems) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
   return 0;
-}
-
-// The same choice made ON the device (round 5: a set whose pairs are new gets its lists without a host round trip): one
-// workgroup; the tiles' words per group in, the job list in the layout of grid_hb.hip out (queue starts, number of jobs,
-// jobs in tile order = strip after strip, a strip's by block) together with every tile's place in it.
-__global__ __launch_bounds__(1024) void k_jobs_build(const unsigned *tnw, unsigned n_tiles, const unsigned *tile_off, int JW, int jlim, int R, int UC, int NB,
-                                                     unsigned cap, unsigned nwh0, unsigned *jobs, unsigned *tjob) {
-  __shared__ unsigned hist[64], s_nwh, s_scan[17], s_off[1024];
-  const unsigned tid = threadIdx.x;
-  if (tid < 64) hist[tid] = 0;
-  // (the strips' first tiles, looked at a dozen times per tile below: in LDS where they fit)
-  const bool off_lds = JW + 2 <= 1024;
-  if (off_lds)
-    for (int i = (int)tid; i < JW + 2; i += 1024) s_off[i] = tile_off[i];
-  __syncthreads();
-  const unsigned *toffp = off_lds ? s_off : tile_off;
-  for (unsigned t = tid; t < n_tiles; t += 1024) atomicAdd(&hist[min(tnw[t], 63u)], 1u);
-  __syncthreads();
-  if (tid == 0) {
-    // the smallest threshold from nwh0 on whose tiles fit (the tiles at or above a threshold grow as it falls): one pass
-    // from the top; 64 = none fits
-    unsigned nwh = 64, c = 0;
-    for (int k = 63; k >= (int)nwh0; k--) {
-      c += hist[k];
-      if (c > cap) break;
-      nwh = (unsigned)k;
-    }
-    s_nwh = nwh;
-  }
-  __syncthreads();
-  const unsigned nwh = s_nwh;
-  // strip of a tile: tile_off[j + 1] is the first tile of strip j (entry 0 holds the total)
-  auto strip_of = [&](unsigned t) -> int {
-    int lo = 0, hi = JW - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) / 2;
-      if (toffp[mid + 1] <= t) lo = mid;
-      else hi = mid - 1;
-    }
-    return lo;
-  };
-  const int jend = JW < jlim ? JW : jlim;  // strips that may have jobs
-  const unsigned per = (n_tiles + 1023u) / 1024u, t0 = tid * per, t1 = min(t0 + per, n_tiles);
-  unsigned mine = 0;
-  if (nwh <= 63)
-    for (unsigned t = t0; t < t1; t++) mine += (tnw[t] >= nwh && strip_of(t) < jend) ? 1u : 0u;
-  unsigned total = 0;
-  unsigned k = stb_block_exclusive_1024(mine, s_scan, &total);
-  for (unsigned t = t0; t < t1; t++) {
-    const int j = strip_of(t);
-    if (t == toffp[j + 1] && j <= GH_JQ_HOST) jobs[j] = (j < jend) ? k : total;  // the first tile of strip j: its queue starts here
-    if (nwh <= 63 && tnw[t] >= nwh && j < jend) {
-      const int b = (int)(((long long)j * UC) / R) + (int)(t - toffp[j + 1]);
-      jobs[128 + k] = (unsigned)j | ((unsigned)b << 16);
-      tjob[t] = k;
-      k++;
-    } else {
-      tjob[t] = 0xffffffffu;
-    }
-  }
-  // queue starts of the strips there are not (or that may have no jobs), and the number of jobs
-  for (int j = (int)tid; j <= GH_JQ_HOST; j += 1024)
-    if (j >= jend) jobs[j] = total;
-  if (tid == 0) jobs[GH_JQ_HOST + 1] = total;
-}
-
-// queued on the set's stream behind the kernels that produced `tnw`; no host synchronisation
-int stb_lists_jobs_device(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *tnw) {
-  const unsigned n_tiles = gg.n_tiles;
-  g->n_jobs[which] = 0;
-  const unsigned cap = stb_grid_job_cap(gg.C, g->Dmax, n_tiles, gg.phases);
-  if (!cap || !n_tiles) {
-    if (g->d_jobs[which]) HIPCHK(hipMemsetAsync(g->d_jobs[which], 0, 4 * 128, g->st));
-    return 0;
-  }
-  unsigned nwh = (unsigned)stb_env_int("STB_GRID_HELP_NW", 0);
-  if (nwh < 1) {
-    const double waves_per_simd = (double)gg.JW * D / (4.0 * stb_cu_count());
-    nwh = waves_per_simd <= 1.9 ? 4 : (waves_per_simd <= 2.7 ? 6 : 8);
-  }
-  int jlim = ((gg.JW - 1) / gg.P) * gg.P;
-  if (jlim > 64) jlim = 64;
-  if (!g->d_jobs[which] && stb_pool_malloc((void **)&g->d_jobs[which], 4 * ((size_t)n_tiles + 128 + 1)) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
-  if (!g->d_tjob[which] && stb_pool_malloc((void **)&g->d_tjob[which], 4 * (size_t)(n_tiles + 1)) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
-  hipLaunchKernelGGL(k_jobs_build, dim3(1), dim3(1024), 0, g->st, tnw, n_tiles, g->d_tile_off[which], gg.JW, jlim, gg.R, gg.U * gg.C, gg.NB, cap, nwh,
-                     g->d_jobs[which], g->d_tjob[which]);
-  HIPCHK(hipGetLastError());
-  g->n_jobs[which] = cap;  // (at most; the number itself stays on the device)
-  return 0;
-}
-
-// The tiles whose listed cells the strip's own wave does not look up: every strip of a table moves at the pace of
-// the strips to its left, and those hold most of the pairs (t uniform below n: columns like log) -- several
-// passes a group where the average strip has one.  Such a tile is only walked by its strip, which leaves the
-// state of its wave before the block as a record; waves whose strips the diagonal has not reached yet take the
-// tiles as jobs once their own strips have ended.  Which: all tiles of NWH passes a group and more (the lists in CSR
-// form among them), NWH chosen below and raised until the records fit (grid_geom::job_cap at Dmax discounts).
-// h_nw: words per group of every tile (host).  The lists go to the device on the set's stream.
-int stb_lists_jobs_from(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *h_nw) {
-  const unsigned n_tiles = gg.n_tiles;
-  g->n_jobs[which] = 0;
-  const unsigned cap = stb_grid_job_cap(gg.C, g->Dmax, n_tiles, gg.phases);
-  if (!cap || !n_tiles) {
-    // (no jobs: a list left by an earlier build must say so -- the kernels read the number of jobs from it)
-    if (g->d_jobs[which] && (hipMemsetAsync(g->d_jobs[which], 0, 4 * 128, g->st) != hipSuccess || hipStreamSynchronize(g->st) != hipSuccess))
-      return stb_fail("stb_groups_aterms: %s", hipGetErrorString(hipGetLastError()));
-    return 0;
-  }
-  unsigned hist[65] = {0};  // (an upper bound: the tiles of all strips)
-  for (unsigned t = 0; t < n_tiles; t++) hist[h_nw[t] > 63 ? 63 : h_nw[t]]++;
-  // NWH at the least: what a job takes off the critical path it adds to the chip's work (the tile is walked twice),
-  // which the fuller chip can afford less (MI355X, 10^6 pairs, N = 10^4, kernel ms without jobs / NWH = 3 / 4 / 6 /
-  // 8 / 12: 32 discounts 1.21 / 1.00 / 0.96 / 1.01 / 1.04 / 1.09, 40: 1.26 / 1.10 / 1.02 / 1.05 / 1.08 / 1.12,
-  // 48: 1.26 / 1.30 / 1.14 / 1.09 / 1.10 / 1.15, 64: 1.36 / 1.59 / 1.39 / 1.29 / 1.28 / 1.29)
-  unsigned nwh = (unsigned)stb_env_int("STB_GRID_HELP_NW", 0);
-  if (nwh < 1) {
-    const double waves_per_simd = (double)gg.JW * D / (4.0 * stb_cu_count());
-    nwh = waves_per_simd <= 1.9 ? 4 : (waves_per_simd <= 2.7 ? 6 : 8);
-  }
-  for (; nwh <= 63; nwh++) {
-    unsigned c = 0;
-    for (unsigned k = nwh; k <= 63; k++) c += hist[k];
-    if (c <= cap) break;
-  }
-  std::vector<unsigned> jobs, tjob(n_tiles, 0xffffffffu), off;
-  stb_grid_tile_offsets(gg, off);
-  const int UCg = gg.U * gg.C;
-  // (a job is taken by a wave of a workgroup further right -- one with a higher ticket, for which the strip's own
-  // workgroup is running or through: the strips of a table's last workgroup have no jobs; GH_JQ = 64 queues)
-  int jlim = ((gg.JW - 1) / gg.P) * gg.P;
-  if (jlim > 64) jlim = 64;
-  std::vector<unsigned> qoff(64 + 1, 0u);
-  if (nwh <= 63) {
-    // strip after strip, a strip's tiles by block: a queue per strip
-    for (int j = 0; j < gg.JW && j < jlim; j++) {
-      const int b00 = (int)(((long long)j * UCg) / gg.R);
-      qoff[j] = (unsigned)jobs.size();
-      for (int b = b00; b < gg.NB; b++)
-        if (h_nw[off[j + 1] + (unsigned)(b - b00)] >= nwh) {
-          tjob[off[j + 1] + (unsigned)(b - b00)] = (unsigned)jobs.size();
-          jobs.push_back((unsigned)j | ((unsigned)b << 16));
-        }
-    }
-    for (int j = (gg.JW < jlim ? gg.JW : jlim); j <= 64; j++) qoff[j] = (unsigned)jobs.size();
-    if (jobs.size() > cap) {  // (the bound above counted every strip's tiles: cannot happen)
-      jobs.clear();
-      std::fill(tjob.begin(), tjob.end(), 0xffffffffu);
-      std::fill(qoff.begin(), qoff.end(), 0u);
-    }
-  }
-  const size_t nj = jobs.size();
-  {
-    // the list as the kernels read it (grid_hb.hip: GH_JQ + 1 queue starts, the number of jobs at word 65, jobs from word 128)
-    std::vector<unsigned> lay(128, 0u);
-    for (int j = 0; j <= 64; j++) lay[(size_t)j] = qoff[(size_t)j];
-    lay[65] = (unsigned)nj;
-    lay.insert(lay.end(), jobs.begin(), jobs.end());
-    jobs.swap(lay);
-  }
-  // (buffers for the most there can be, kept from set to set; the copies are synchronous: the vectors above go away)
-  if (!g->d_jobs[which] && stb_pool_malloc((void **)&g->d_jobs[which], 4 * ((size_t)n_tiles + 128 + 1)) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
-  if (!g->d_tjob[which] && stb_pool_malloc((void **)&g->d_tjob[which], 4 * (size_t)(n_tiles + 1)) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
-  if (hipMemcpyAsync(g->d_tjob[which], tjob.data(), 4 * (size_t)n_tiles, hipMemcpyHostToDevice, g->st) != hipSuccess ||
-      hipMemcpyAsync(g->d_jobs[which], jobs.data(), 4 * jobs.size(), hipMemcpyHostToDevice, g->st) != hipSuccess || hipStreamSynchronize(g->st) != hipSuccess)
-    return stb_fail("stb_groups_aterms: %s", hipGetErrorString(hipGetLastError()));
-  g->n_jobs[which] = (unsigned)nj;
-  return 0;
-}
-
-// Returns 0 and sets g->sparse = 1 when the sparse form was built, 0 with g->sparse = 0 when the
-// pairs are too dense for it to pay (the caller then builds the count slab), non-zero on error.
-static int groups_fused_setup_sparse(stb_groups_t *g, int which, int D) {
-  const unsigned N = g->N, M = g->M;
-  const uint64_t G = g->G;
-  hb_dot_info H;
-  memset(&H, 0, sizeof(H));
-  if (which == 2 && stb_hb_dot_info(N, M, g->Dmax, &H, g->hb_sum_C)) return stb_fail("stb_groups_aterms: no halo-block geometry for N=%u M=%u", N, M);
-  grid_geom gg;
-  memset(&gg, 0, sizeof(gg));
-  if (which >= 3) {
-    // (the strip shape of the grid form depends on the number of discounts: a list per shape)
-    if (stb_grid_geometry(N, M, D, &gg)) return stb_fail("stb_groups_aterms: no grid geometry for N=%u M=%u", N, M);
-    which = stb_grid_which(gg.C);
-    H.R = gg.R;
-    H.UC = gg.U * gg.C;
-    H.HC = gg.HL * gg.C;
-    H.NB = gg.NB;
-    H.JW = gg.JW;
-    H.NQ = gg.NQ;
-    H.G = gg.G;
-    H.C = gg.C;
-    H.n_tiles = gg.n_tiles;
-    H.n_rec = gg.n_tiles;
-    if ((g->lists_ready[which] || g->d_tile_off[which]) && (g->list_R[which] != H.R || g->list_G[which] != H.G)) {
-      (void)hipStreamSynchronize(g->st);
-      void **olds[] = {(void **)&g->d_item_ptr[which], (void **)&g->d_ent_pos[which], (void **)&g->d_ent_cnt[which], (void **)&g->d_tile_off[which],
-                       (void **)&g->d_dense[which],    (void **)&g->d_tinfo[which],   (void **)&g->d_jobs[which],    (void **)&g->d_tjob[which],
-                       (void **)&g->d_tnw[which],      (void **)&g->d_toff[which]};
-      for (void **q : olds) {
-        stb_pool_free(*q);
-        *q = nullptr;
-      }
-      g->n_jobs[which] = 0;
-      g->ent_cap[which] = 0;
-      g->dense_cap[which] = 0;
-      g->lists_ready[which] = 0;
-    }
-    if (!g->lists_ready[which] && !g->d_tile_off[which]) {
-      std::vector<unsigned> off;
-      stb_grid_tile_offsets(gg, off);
-      if (stb_pool_malloc((void **)&g->d_tile_off[which], off.size() * sizeof(unsigned)) != hipSuccess ||
-          hipMemcpy(g->d_tile_off[which], off.data(), off.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess)
-        return stb_fail("stb_groups_aterms: out of device memory");
-    }
-    H.rec_off = g->d_tile_off[which];
-  }
-  if (g->lists_ready[which]) return 0;
-  {
-    // from the count slab (lists.hip): no sort, no host round trip; where it does not apply, the sort below
-    const int rc = stb_lists_slab_build(g, which, D, H, gg);
-    if (rc != 2) return rc;
-  }
-  if (!g->fused_ready) g->sparse = 0;
-  if (G == 0 || G >= 0xffffffffull) return 0;
-  const unsigned nsg = (M + 63) / 64 + 4;
-  const unsigned trips = (N - 2 + 7) / 8;
-  const uint64_t nitems64 = (which >= 2) ? (uint64_t)H.n_rec * (unsigned)H.NQ : (uint64_t)trips * nsg;
-  if (nitems64 >= (1ull << 31)) return 0;
-  const unsigned nitems = (unsigned)nitems64;
-  uint64_t *k0 = nullptr, *k1 = nullptr, *uk = nullptr, *d_counts = nullptr;
-  uint32_t *p0 = nullptr, *p1 = nullptr;
-  unsigned *cnt = nullptr, *runs = nullptr, *item = nullptr;
-  void *tmp = nullptr;
-  int rc = 1;
-  const unsigned blocks = (unsigned)((G + 255) / 256);
-  do {
-    if (stb_pool_malloc((void **)&k0, 8 * G) != hipSuccess || stb_pool_malloc((void **)&k1, 8 * G) != hipSuccess ||
-        stb_pool_malloc((void **)&p0, 4 * G) != hipSuccess || stb_pool_malloc((void **)&p1, 4 * G) != hipSuccess ||
-        stb_pool_malloc((void **)&uk, 8 * G) != hipSuccess || stb_pool_malloc((void **)&cnt, 4 * G) != hipSuccess ||
-        stb_pool_malloc((void **)&item, 4 * G) != hipSuccess || stb_pool_malloc((void **)&runs, 64) != hipSuccess ||
-        stb_pool_malloc((void **)&d_counts, 64) != hipSuccess) {
-      stb_fail("stb_groups_aterms: out of device memory");
-      break;
-    }
-    if (which >= 3)
-      hipLaunchKernelGGL(k_item_keys_hb2, dim3(blocks), dim3(256), 0, g->st, g->d_n, g->d_t, G, N, M, H, stb_pos_bits(H.C), k0, p0);
-    else if (which == 2)
-      hipLaunchKernelGGL(k_item_keys_hb, dim3(blocks), dim3(256), 0, g->st, g->d_n, g->d_t, G, N, M, H, k0, p0);
-    else
-      hipLaunchKernelGGL(k_item_keys, dim3(blocks), dim3(256), 0, g->st, g->d_n, g->d_t, G, N, M, nsg, which ? 2u : 1u, k0, p0);
-    size_t b1 = 0, b2 = 0;
-    if (rocprim::radix_sort_pairs(nullptr, b1, k0, k1, p0, p1, (size_t)G, 0, 64, g->st) != hipSuccess) break;
-    if (rocprim::run_length_encode(nullptr, b2, k1, (unsigned)G, uk, cnt, runs, g->st) != hipSuccess) break;
-    const size_t tmp_bytes = b1 > b2 ? b1 : b2;
-    if (stb_pool_malloc(&tmp, tmp_bytes ? tmp_bytes : 1) != hipSuccess) {
-      stb_fail("stb_groups_aterms: out of device memory");
-      break;
-    }
-    size_t bb = tmp_bytes;
-    if (rocprim::radix_sort_pairs(tmp, bb, k0, k1, p0, p1, (size_t)G, 0, 64, g->st) != hipSuccess) break;
-    hipLaunchKernelGGL(k_key_bounds, dim3(1), dim3(1), 0, g->st, k1, G, d_counts);
-    uint64_t h_counts[2] = {0, 0};
-    if (hipMemcpyAsync(h_counts, d_counts, 16, hipMemcpyDeviceToHost, g->st) != hipSuccess ||
-        hipStreamSynchronize(g->st) != hipSuccess)
-      break;
-    const uint64_t n_in = h_counts[0], n_other = h_counts[1];
-    // dense enough that every cell's log might as well be computed: leave it to the count slab
-    if (n_in * 3 > stb_table_cells(N, M)) {
-      rc = 0;
-      break;
-    }
-    // the pairs outside the table, in their sorted order (the same whichever layout is built first; the
-    // self-summing form has none but those whose S_S is log 0, which it only counts)
-    if (which >= 2) {
-      g->n_inf = n_other;
-    } else if (!g->d_n2) {
-      g->G2 = n_other;
-      if (stb_pool_malloc((void **)&g->d_n2, 4 * (n_other ? n_other : 1)) != hipSuccess ||
-          stb_pool_malloc((void **)&g->d_t2, 2 * (n_other ? n_other : 1)) != hipSuccess) {
-        stb_fail("stb_groups_aterms: out of device memory");
-        break;
-      }
-      if (n_other)
-        hipLaunchKernelGGL(k_gather_pairs, dim3((unsigned)((n_other + 255) / 256)), dim3(256), 0, g->st, g->d_n, g->d_t,
-                           p1 + n_in, n_other, g->d_n2, g->d_t2);
-    }
-    // distinct cells with their counts
-    unsigned h_runs = 0;
-    if (n_in) {
-      bb = tmp_bytes;
-      if (rocprim::run_length_encode(tmp, bb, k1, (unsigned)n_in, uk, cnt, runs, g->st) != hipSuccess) break;
-      if (hipMemcpyAsync(&h_runs, runs, 4, hipMemcpyDeviceToHost, g->st) != hipSuccess ||
-          hipStreamSynchronize(g->st) != hipSuccess)
-        break;
-    } else if (hipMemsetAsync(runs, 0, 4, g->st) != hipSuccess) {
-      break;
-    }
-    {
-      void **olds[] = {(void **)&g->d_ent_pos[which], (void **)&g->d_ent_cnt[which], (void **)&g->d_item_ptr[which], (void **)&g->d_dense[which],
-                       (void **)&g->d_tinfo[which], (void **)&g->d_jobs[which], (void **)&g->d_tjob[which]};
-      for (void **q : olds) {
-        stb_pool_free(*q);
-        *q = nullptr;
-      }
-      g->ent_cap[which] = 0;
-      g->dense_cap[which] = 0;
-    }
-    if (stb_pool_malloc((void **)&g->d_ent_pos[which], 2 * (size_t)(h_runs ? h_runs : 1)) != hipSuccess ||
-        stb_pool_malloc((void **)&g->d_ent_cnt[which], 4 * (size_t)(h_runs ? h_runs : 1)) != hipSuccess ||
-        stb_pool_malloc((void **)&g->d_item_ptr[which], 4 * ((size_t)nitems + 2)) != hipSuccess) {
-      stb_fail("stb_groups_aterms: out of device memory");
-      break;
-    }
-    if (h_runs) {
-      hipLaunchKernelGGL(k_split_runs, dim3((h_runs + 255) / 256), dim3(256), 0, g->st, uk, runs, g->d_ent_pos[which], item,
-                         which >= 3 ? stb_pos_bits(H.C) + 5 : (which == 2 ? 11 : 9));
-      if (hipMemcpyAsync(g->d_ent_cnt[which], cnt, 4 * (size_t)h_runs, hipMemcpyDeviceToDevice, g->st) != hipSuccess) break;
-    }
-    hipLaunchKernelGGL(k_item_ptr, dim3((nitems + 1 + 255) / 256), dim3(256), 0, g->st, item, runs, nitems, g->d_item_ptr[which]);
-    if (which >= 3) {
-      // the dense layout the walk reads: words per tile, their prefix sum, the words
-      const unsigned n_tiles = H.n_tiles, NQ = (unsigned)H.NQ;
-      unsigned *tnw = nullptr, *twords = nullptr, *toff = nullptr;
-      void *tmp2 = nullptr;
-      size_t b3 = 0;
-      bool ok = stb_pool_malloc((void **)&tnw, 4 * (size_t)(n_tiles + 1)) == hipSuccess &&
-                stb_pool_malloc((void **)&twords, 4 * (size_t)(n_tiles + 1)) == hipSuccess &&
-                stb_pool_malloc((void **)&toff, 4 * (size_t)(n_tiles + 1)) == hipSuccess &&
-                stb_pool_malloc((void **)&g->d_tinfo[which], 4 * (size_t)(n_tiles + 1)) == hipSuccess;
-      unsigned h_last[2] = {0, 0};
-      if (ok && n_tiles) {
-        hipLaunchKernelGGL(k_tile_words, dim3((n_tiles + 3) / 4), dim3(256), 0, g->st, g->d_item_ptr[which], g->d_ent_cnt[which], n_tiles, NQ,
-                           stb_pos_bits(H.C) + 5, tnw, twords);
-        ok = rocprim::exclusive_scan(nullptr, b3, twords, toff, 0u, (size_t)n_tiles, rocprim::plus<unsigned>(), g->st) == hipSuccess &&
-             stb_pool_malloc(&tmp2, b3 ? b3 : 1) == hipSuccess &&
-             rocprim::exclusive_scan(tmp2, b3, twords, toff, 0u, (size_t)n_tiles, rocprim::plus<unsigned>(), g->st) == hipSuccess &&
-             hipMemcpyAsync(&h_last[0], toff + (n_tiles - 1), 4, hipMemcpyDeviceToHost, g->st) == hipSuccess &&
-             hipMemcpyAsync(&h_last[1], twords + (n_tiles - 1), 4, hipMemcpyDeviceToHost, g->st) == hipSuccess &&
-             hipStreamSynchronize(g->st) == hipSuccess;
-      }
-      const size_t words = (size_t)h_last[0] + h_last[1];  // in units of 64 dwords
-      ok = ok && words < (1u << 26);                       // (a tile's first word / 64 goes into 26 bits of its entry)
-      ok = ok && stb_pool_malloc((void **)&g->d_dense[which], 256 * (words ? words : 1)) == hipSuccess;
-      if (ok && nitems)
-        hipLaunchKernelGGL(k_dense_fill, dim3((nitems + 3) / 4), dim3(256), 0, g->st, g->d_item_ptr[which], g->d_ent_pos[which],
-                           g->d_ent_cnt[which], nitems, NQ, stb_pos_bits(H.C) + 5, tnw, toff, g->d_dense[which], g->d_tinfo[which]);
-      if (ok) ok = hipStreamSynchronize(g->st) == hipSuccess;
-      // The tiles whose listed cells the strip's own wave does not look up: every strip of a table moves at the pace of
-      // the strips to its left, and those hold most of the pairs (t uniform below n: columns like log) -- several
-      // passes a group where the average strip has one.  Such a tile is only walked by its strip, which leaves the
-      // state of its wave before the block as a record; waves whose strips the diagonal has not reached yet take the
-      // tiles as jobs once their own strips have ended.  Which: all tiles of NWH passes a group and more (the lists in CSR
-      // form among them), NWH chosen below and raised until the records fit (grid_geom::job_cap at Dmax discounts).
-      g->n_jobs[which] = 0;
-      if (ok && n_tiles) {
-        std::vector<unsigned> h_nw(n_tiles);
-        ok = hipMemcpy(h_nw.data(), tnw, 4 * (size_t)n_tiles, hipMemcpyDeviceToHost) == hipSuccess && stb_lists_jobs_from(g, which, D, gg, h_nw.data()) == 0;
-      }
-      stb_pool_free(tnw);
-      stb_pool_free(twords);
-      stb_pool_free(toff);
-      stb_pool_free(tmp2);
-      if (!ok) {
-        stb_fail("stb_groups_aterms: out of device memory (or a dense list beyond 2^32 bytes)");
-        break;
-      }
-    }
-    if (!g->d_dotp && stb_groups_alloc_dotp(g)) break;
-    if (hipStreamSynchronize(g->st) != hipSuccess || hipGetLastError() != hipSuccess) break;
-    g->nsg = nsg;
-    g->sparse = 1;
-    g->lists_ready[which] = 1;
-    g->list_R[which] = H.R;
-    g->list_G[which] = H.G;
-    g->fused_ready = 1;
-    rc = 0;
-  } while (0);
-  if (rc != 0) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) stb_fail("stb_groups_aterms: sparse set-up failed: %s", hipGetErrorString(e));
-  }
-  (void)hipStreamSynchronize(g->st);
-  stb_pool_free(k0);
-  stb_pool_free(k1);
-  stb_pool_free(p0);
-  stb_pool_free(p1);
-  stb_pool_free(uk);
-  stb_pool_free(cnt);
-  stb_pool_free(item);
-  stb_pool_free(runs);
-  stb_pool_free(d_counts);
-  stb_pool_free(tmp);
-  return rc;
 }
 
 // Lazy set-up of the fused evaluation (first call with more than one discount): occurrence count
@@ -982,22 +415,7 @@ static int aterms_issue_lean(stb_groups_t *g, const double *x_host, int D, doubl
   if (stb_restaurant_partials(x_host, D, g->d_T, g->d_bpar, g->pend_ssum ? 0 : (uint64_t)g->I, g->d_ws_terms, g->ws_terms, a_dev, &tpart, &nbt, g->st))
     return 1;
   dot_request req;
-  req.item_ptr = g->d_item_ptr[which];
-  req.ent_pos = g->d_ent_pos[which];
-  req.ent_cnt = g->d_ent_cnt[which];
-  req.nsg = g->nsg;
-  req.col0 = which >= 3 ? 4 : 3;
-  if (which == 2) req.geom_C = g->hb_sum_C;  // (the strip shape the set's lists were built for)
-  if (which >= 3) {
-    req.geom_C = stb_which_C(which);
-    req.geom_R = g->list_R[which];
-    req.geom_G = g->list_G[which];
-    req.tile_off = g->d_tile_off[which];
-    req.dense = g->d_dense[which];
-    req.tinfo = g->d_tinfo[which];
-    req.jobs = g->d_jobs[which];
-    req.tjob = g->d_tjob[which];
-  }
+  stb_list_request(g, which, &req);
   req.dotp = g->d_dotp;
   req.dotp_cap = g->dotp_elems;
   req.ws_zero = g->ws_zero;
@@ -1025,7 +443,7 @@ static int aterms_issue_lean(stb_groups_t *g, const double *x_host, int D, doubl
   if (timed) HIPCHK(hipEventRecord(g->ev[1], g->st));
   if (timed) HIPCHK(hipEventRecord(g->ev[2], g->st));
   hipLaunchKernelGGL(k_eval_tail, dim3(D), dim3(256), 0, g->st, g->d_dotp, req.parts_per_table, req.parts_extra_dev, which >= 3 ? 2 : 1, tpart, nbt,
-                     (unsigned long long)g->n_inf, g->ent_cap[which] ? g->d_ninf : nullptr, hdr, g->d_out, g->h_out_dev, g->Dmax, g->pend_user,
+                     (unsigned long long)g->n_inf, stb_list_from_slab(g->lists[which]) ? g->d_ninf : nullptr, hdr, g->d_out, g->h_out_dev, g->Dmax, g->pend_user,
                      g->pend_seq);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(g->ev[3], g->st));
@@ -1061,15 +479,8 @@ static int aterms_issue(stb_groups_t *g, const double *x_host, int D, double *ou
     // the chain form as a DOT kernel: sum over table cells of count * log S, no table in memory;
     // then the few pairs that address no cell (t = 1 -> S1, t = n -> 0, out of bounds -> -inf)
     dot_request req;
-    if (g->sparse) {
-      req.item_ptr = g->d_item_ptr[which];
-      req.ent_pos = g->d_ent_pos[which];
-      req.ent_cnt = g->d_ent_cnt[which];
-      req.nsg = g->nsg;
-      req.col0 = which + 1;
-    } else {
-      req.cnt = g->d_cnt;
-    }
+    if (g->sparse) stb_list_request(g, which, &req);
+    else req.cnt = g->d_cnt;
     req.dotp = g->d_dotp;
     req.dotp_cap = g->dotp_elems;
     stb_set_dot_request(&req);
@@ -1232,16 +643,16 @@ static int aterms_prepare(stb_groups_t *g, int D, bool allow_fuse, bool *fuse_ou
     hb_dot_info H;
     if (stb_hb_dot_info(g->N, g->M, D, &H, g->hb_sum_C) == 0 && H.n_spine <= hb_max_spine()) which = 2;
   }
-  if (fuse && stb_env_int("STB_ATERMS_SPARSE", 1) && (!g->fused_ready || g->sparse) && groups_fused_setup_sparse(g, which, D)) return 1;
+  if (fuse && stb_env_int("STB_ATERMS_SPARSE", 1) && (!g->fused_ready || g->sparse) && stb_lists_build(g, which, D)) return 1;
   if (fuse && !g->fused_ready && groups_fused_setup(g)) return 1;
   if (fuse && !g->sparse) which = 0;  // (dense pair sets: the count slab, chain form only)
   bool fuse2 = fuse;
-  if (fuse && g->sparse && !g->lists_ready[which]) fuse2 = false;  // (no list in this layout: stored tables + gather)
+  if (fuse && g->sparse && !g->lists[which].ready) fuse2 = false;  // (no list in this layout: stored tables + gather)
   g->sel_which = which;
   // (diagnostics, stb_groups_last_form: the strip shape the lists of this layout were built for)
   g->last_fused = fuse2 ? 1 : 0;
   g->last_C = !fuse2 || which < 2 ? 0 : (which == 2 ? g->hb_sum_C : stb_which_C(which));
-  g->last_R = !fuse2 || which < 2 ? 0 : g->list_R[which];
+  g->last_R = !fuse2 || which < 2 ? 0 : g->lists[which].R;
   *fuse_out = fuse2;
   *v_out = !fuse2 ? v : (which >= 2 ? STB_FILL_HB : (which ? STB_FILL_CK : STB_FILL_CHAIN));
   return 0;

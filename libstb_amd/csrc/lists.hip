@@ -1,18 +1,13 @@
-// lists.hip -- what a group set needs when its (n,t) pairs are NEW: the pairs' way to the device and the cell lists
-// of the fused evaluation, rebuilt on the device without a sort and without a host round trip.
+// lists.hip -- the cell lists of the fused evaluation (struct stb_cell_list, groups.h): their lifetime, the builder that
+// makes them on the device from a COUNT SLAB without a sort and without a host round trip, the helper jobs of the grid
+// form.  stb_lists_build is the way in; where the slab builder does not apply, lists_sorted.hip's sort-based one does.
 //
 // Why.  The reference's callers change the counts between two samplea calls (test/demo.c:405-445 rewrites t[j][i] and
 // T[j] in every Gibbs iteration, then :478-480 resamples a): a set of pairs is used for ONE samplea call, i.e. ~8
 // posterior evaluations, and whatever is done once per set is paid on every call.  Rounds 2-4 sorted the pairs twice
 // per set (rocPRIM: 23 launches, 0.24 ms, by (n,t) for the gather; 21 launches + run-length encoding, 0.33 ms, by
 // (tile, group, cell) for the lists of the fused form) with four host round trips in between, and the host copied the
-// ragged arrays twice (flat, then to the device through the runtime's own staging): 3.1-3.8 ms a call where an
-// unchanged set took 1.57.  Here:
-//
-//   * stb_groups_pairs_begin / _put / _put_ragged / _commit: the caller's arrays are copied ONCE, into pinned memory (the
-//     maxima of n and t -- the table bounds of lib/samplea.c:186-208 -- fall out of the same pass); a whole set at once is
-//     copied by a few host threads of the library's own while the calling thread hands the finished pieces to the DMA
-//     engine (one core of the GPU box's host moves the 6 MB of 10^6 pairs in 0.41 ms, four in 0.18).
+// ragged arrays twice: 3.1-3.8 ms a call where an unchanged set took 1.57.  The copies: pairs.hip.  Here:
 //   * the lists come from a COUNT SLAB: one word per cell of every (tile, group of rows) item in the order the walk
 //     looks cells up, i.e. the table's cells once over (33 MB for N = M = 4096, 205 MB for 10^4), zero between builds.
 //     k_count_cells adds every pair to its word -- ONE device-scope atomic per pair: this part hands out 24 G of them a
@@ -22,25 +17,15 @@
 //     order, the order the sort produced, so the lists are THE SAME BYTES as the sort-based builder's -- and puts every
 //     word it read back to zero: the slab is clean for the next set without a memset.  For the grid form the prefix sums and
 //     the tiles' entries are one single-workgroup kernel (k_scan_lists), the compaction writes the dense words the walk
-//     reads along with the CSR entries (k_emit_both), and the tiles left to helper jobs are chosen by k_jobs_build
-//     (groups.hip), which leaves their number in the list for the kernels to read.  No host synchronisation anywhere: the
+//     reads along with the CSR entries (k_emit_both), and the tiles left to helper jobs are chosen by k_jobs_build,
+//     which leaves their number in the list for the kernels to read.  No host synchronisation anywhere: the
 //     evaluation is queued right behind (N = 4096, halo-block form: 75 us; N = 10^4, grid form: 166 us; the radix sort +
 //     run-length encoding they replace: 330-600 us and four host round trips).
-//   * pairs are no longer sorted by (n,t) when a set is made: the fused evaluation does not read them, and the gather
-//     over a stored table of 4000 x 4000 (64 MB: it lives in the Infinity Cache) is as fast on unsorted pairs
-//     (0.035 ms either way, profiles/r05_fresh_before.txt).  The sort is made on first need by the evaluations through
-//     stored tables, whose sum then does not depend on the caller's order, as before.
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
-#include <vector>
-
-#include <pthread.h>
-#include <sched.h>
 
 #include "groups.h"
-
-void stb_grid_tile_offsets(const grid_geom &g, std::vector<unsigned> &off);  // grid_hb.hip
 
 // ------------------------------------------------------------------------------------------------
 // count slab -> CSR lists
@@ -169,8 +154,6 @@ __global__ __launch_bounds__(256) void k_emit_cells(unsigned *slab, const unsign
 }
 
 // ---- the grid form: CSR lists AND the dense words the walk reads, in one pass over the slab ----
-#define STB_DENSE_NWMAX 40  // (as in groups.hip)
-
 // One workgroup: the exclusive scan of the items' distinct cells (the CSR row pointer) and, per tile, the words per lane
 // its groups get in the dense layout (the most any of them needs; 63: more than the layout takes, the tile is read from
 // the CSR lists), their prefix sum and the tile's entry -- what two library scans, k_tile_words and a launch gap did.
@@ -280,33 +263,30 @@ __global__ __launch_bounds__(256) void k_emit_both(unsigned *slab, const unsigne
     for (unsigned k = (end - first) + lane; k < room; k += 64) dw[k] = 0u;
 }
 
-int stb_lists_jobs_from(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *h_nw);
-
 static void free_z(void *&p) {
   stb_pool_free(p);
   p = nullptr;
 }
 #define FREE_Z(x) free_z(reinterpret_cast<void *&>(x))
 
+void stb_list_release(stb_cell_list &l, bool with_shape) {
+  void **sized[] = {(void **)&l.item_ptr, (void **)&l.ent_pos, (void **)&l.ent_cnt, (void **)&l.dense, (void **)&l.tinfo, (void **)&l.jobs, (void **)&l.tjob};
+  for (void **p : sized) free_z(*p);
+  l.ent_cap = l.dense_cap = 0;
+  if (!with_shape) return;
+  void **shaped[] = {(void **)&l.tile_off, (void **)&l.tnw, (void **)&l.toff};
+  for (void **p : shaped) free_z(*p);
+  l.n_jobs = 0;
+  l.ready = 0;
+}
+
 // New pairs (keep_capacity) or new table bounds: what was built from the old ones goes.  With keep_capacity the buffers
 // the slab builder sized for the most a set of G pairs can need stay; those the sort-based builder sized exactly go.
 void stb_lists_drop(stb_groups_t *g, bool keep_capacity) {
-  for (int w = 0; w < STB_NLISTS; w++) {
-    g->lists_ready[w] = 0;
-    g->n_jobs[w] = 0;
-    if (keep_capacity && g->ent_cap[w]) continue;
-    FREE_Z(g->d_item_ptr[w]);
-    FREE_Z(g->d_ent_pos[w]);
-    FREE_Z(g->d_ent_cnt[w]);
-    FREE_Z(g->d_tile_off[w]);
-    FREE_Z(g->d_dense[w]);
-    FREE_Z(g->d_tinfo[w]);
-    FREE_Z(g->d_jobs[w]);
-    FREE_Z(g->d_tjob[w]);
-    FREE_Z(g->d_tnw[w]);
-    FREE_Z(g->d_toff[w]);
-    g->ent_cap[w] = 0;
-    g->dense_cap[w] = 0;
+  for (stb_cell_list &l : g->lists) {
+    if (!keep_capacity || !stb_list_from_slab(l)) stb_list_release(l, true);
+    l.ready = 0;
+    l.n_jobs = 0;
   }
   // the forms that read the pairs outside the table and the dense count slab of the chain form
   FREE_Z(g->d_n2);
@@ -328,21 +308,34 @@ void stb_lists_drop(stb_groups_t *g, bool keep_capacity) {
   }
 }
 
-// The set's d_n / d_t hold new pairs (stb_groups_pairs_commit, stb_groups_take_counts): the cell lists are rebuilt and the
-// pairs sorted again on first need.  reused: the caller is one that serves sweep after sweep (stb_groups_update_restaurants)
-void stb_groups_new_pairs(stb_groups_t *g, int reused) {
-  stb_lists_drop(g, true);
-  g->sorted = 0;
-  g->have_pairs = 1;
-  g->reused = reused;
+// the list of layout `which` as a launcher takes it, with the strip shape it was built for (halo-block and grid forms)
+void stb_list_request(const stb_groups_t *g, int which, dot_request *req) {
+  const stb_cell_list &l = g->lists[which];
+  req->item_ptr = l.item_ptr;
+  req->ent_pos = l.ent_pos;
+  req->ent_cnt = l.ent_cnt;
+  req->nsg = g->nsg;
+  req->col0 = which >= 3 ? 4 : which + 1;
+  if (which == 2) req->geom_C = g->hb_sum_C;  // (the strip shape the set's lists were built for)
+  if (which >= 3) {
+    req->geom_C = stb_which_C(which);
+    req->geom_R = l.R;
+    req->geom_G = l.G;
+    req->tile_off = l.tile_off;
+    req->dense = l.dense;
+    req->tinfo = l.tinfo;
+    req->jobs = l.jobs;
+    req->tjob = l.tjob;
+  }
 }
 
 static size_t slab_limit_bytes() { return (size_t)stb_env_int("STB_SLAB_MB", 4096) << 20; }
 
-// Returns 0 with the lists of layout `which` queued on the set's stream (lists_ready set: an evaluation may be queued
+// Returns 0 with the lists of layout `which` queued on the set's stream (the list is ready: an evaluation may be queued
 // behind them), 2 when this builder does not apply (the caller takes the sort-based one), 1 on error.
 int stb_lists_slab_build(stb_groups_t *g, int which, int D, const hb_dot_info &H, const grid_geom &gg) {
   if (which < 2 || !stb_env_int("STB_LISTS_SLAB", 1)) return 2;
+  stb_cell_list &l = g->lists[which];
   const unsigned N = g->N, M = g->M;
   const uint64_t G = g->G;
   if (G == 0 || G >= 0xffffffffull) return 2;
@@ -406,15 +399,15 @@ int stb_lists_slab_build(stb_groups_t *g, int which, int D, const hb_dot_info &H
   }
   if (!g->slab_clean) HIPCHK(hipMemsetAsync(g->d_slab, 0, 4 * g->slab_elems, st));
   // the list buffers, for the most G pairs can ask for
-  if (g->ent_cap[which] < G || !g->d_item_ptr[which]) {
-    if (g->d_ent_pos[which]) HIPCHK(hipStreamSynchronize(st));
-    FREE_Z(g->d_ent_pos[which]);
-    FREE_Z(g->d_ent_cnt[which]);
-    FREE_Z(g->d_item_ptr[which]);
-    if (stb_pool_malloc((void **)&g->d_ent_pos[which], 2 * (size_t)G + 256) != hipSuccess || stb_pool_malloc((void **)&g->d_ent_cnt[which], 4 * (size_t)G + 256) != hipSuccess ||
-        stb_pool_malloc((void **)&g->d_item_ptr[which], 4 * ((size_t)nitems + 2)) != hipSuccess)
+  if (l.ent_cap < G || !l.item_ptr) {
+    if (l.ent_pos) HIPCHK(hipStreamSynchronize(st));
+    FREE_Z(l.ent_pos);
+    FREE_Z(l.ent_cnt);
+    FREE_Z(l.item_ptr);
+    if (stb_pool_malloc((void **)&l.ent_pos, 2 * (size_t)G + 256) != hipSuccess || stb_pool_malloc((void **)&l.ent_cnt, 4 * (size_t)G + 256) != hipSuccess ||
+        stb_pool_malloc((void **)&l.item_ptr, 4 * ((size_t)nitems + 2)) != hipSuccess)
       return stb_fail("stb_groups_aterms: out of device memory");
-    g->ent_cap[which] = (size_t)G;
+    l.ent_cap = (size_t)G;
   }
   g->slab_clean = 0;
   // (counting the pieces of a hand-over while the next ones still arrive -- on the guess that layout and bounds stay --
@@ -428,10 +421,10 @@ int stb_lists_slab_build(stb_groups_t *g, int which, int D, const hb_dot_info &H
   // still "not zero"; stb_lists_drop zeroes it with the pairs)
   if (which < 3) {
     size_t tb = g->scan_tmp_bytes;
-    if (rocprim::exclusive_scan(g->d_scan_tmp, tb, g->d_icnt, g->d_item_ptr[which], 0u, (size_t)nitems + 1, rocprim::plus<unsigned>(), st) != hipSuccess)
+    if (rocprim::exclusive_scan(g->d_scan_tmp, tb, g->d_icnt, l.item_ptr, 0u, (size_t)nitems + 1, rocprim::plus<unsigned>(), st) != hipSuccess)
       return stb_fail("stb_groups_aterms: exclusive_scan failed");
-    hipLaunchKernelGGL(k_emit_cells, dim3((nitems + 3) / 4), dim3(256), 0, st, g->d_slab, g->d_item_ptr[which], nitems, S, g->d_ent_pos[which],
-                       g->d_ent_cnt[which]);
+    hipLaunchKernelGGL(k_emit_cells, dim3((nitems + 3) / 4), dim3(256), 0, st, g->d_slab, l.item_ptr, nitems, S, l.ent_pos,
+                       l.ent_cnt);
     HIPCHK(hipGetLastError());
     g->slab_clean = 1;  // (once the stream has come this far; every later use is queued behind it)
   } else {
@@ -441,378 +434,256 @@ int stb_lists_slab_build(stb_groups_t *g, int which, int D, const hb_dot_info &H
     const size_t words_cap = (size_t)NQ * ((size_t)(G / 64) + n_tiles + 1);  // in units of 64 words: sum over tiles of NQ * ceil(most cells of a group / 64)
     if (words_cap >= (1u << 26)) return stb_fail("stb_groups_aterms: a dense list beyond 2^32 bytes");
     {
-      unsigned **bufs[] = {&g->d_tnw[which], &g->d_toff[which], &g->d_tinfo[which]};
+      unsigned **bufs[] = {&l.tnw, &l.toff, &l.tinfo};
       for (unsigned **q : bufs)
         if (!*q && stb_pool_malloc((void **)q, 4 * (size_t)(n_tiles + 2)) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
     }
-    if (g->dense_cap[which] < words_cap || !g->d_dense[which]) {
-      if (g->d_dense[which]) HIPCHK(hipStreamSynchronize(st));
-      FREE_Z(g->d_dense[which]);
-      if (stb_pool_malloc((void **)&g->d_dense[which], 256 * words_cap) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
-      g->dense_cap[which] = words_cap;
+    if (l.dense_cap < words_cap || !l.dense) {
+      if (l.dense) HIPCHK(hipStreamSynchronize(st));
+      FREE_Z(l.dense);
+      if (stb_pool_malloc((void **)&l.dense, 256 * words_cap) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
+      l.dense_cap = words_cap;
     }
-    hipLaunchKernelGGL(k_scan_lists, dim3(1), dim3(1024), 0, st, g->d_icnt, nitems, n_tiles, NQ, g->d_item_ptr[which], g->d_tnw[which], g->d_toff[which],
-                       g->d_tinfo[which]);
-    hipLaunchKernelGGL(k_emit_both, dim3((nitems + 3) / 4), dim3(256), 0, st, g->d_slab, g->d_item_ptr[which], nitems, S, g->d_ent_pos[which],
-                       g->d_ent_cnt[which], NQ, S.PB + 5, g->d_tnw[which], g->d_toff[which], g->d_tinfo[which], g->d_dense[which]);
+    hipLaunchKernelGGL(k_scan_lists, dim3(1), dim3(1024), 0, st, g->d_icnt, nitems, n_tiles, NQ, l.item_ptr, l.tnw, l.toff,
+                       l.tinfo);
+    hipLaunchKernelGGL(k_emit_both, dim3((nitems + 3) / 4), dim3(256), 0, st, g->d_slab, l.item_ptr, nitems, S, l.ent_pos,
+                       l.ent_cnt, NQ, S.PB + 5, l.tnw, l.toff, l.tinfo, l.dense);
     HIPCHK(hipGetLastError());
     g->slab_clean = 1;
-    if (stb_lists_jobs_device(g, which, D, gg, g->d_tnw[which])) return 1;
+    if (stb_lists_jobs_device(g, which, D, gg, l.tnw)) return 1;
   }
   if (!g->d_dotp && stb_groups_alloc_dotp(g)) return 1;
   g->sparse = 1;
-  g->lists_ready[which] = 1;
-  g->list_R[which] = H.R;
-  g->list_G[which] = H.G;
+  l.ready = 1;
+  l.R = H.R;
+  l.G = H.G;
   g->fused_ready = 1;
   g->nsg = (M + 63) / 64 + 4;
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// the pairs' way to the device
-
-#define STB_PUT_CHUNK (256u * 1024u)  // pairs per piece handed to the stream (1.5 MB)
-
-extern "C" int stb_groups_pairs_begin(stb_groups_t *g) {
-  STB_ENTRY;
-  if (!g) return stb_fail("stb_groups_pairs_begin: null group set");
-  if (g->pending == 1) return stb_fail("stb_groups_pairs_begin: an evaluation queued with stb_groups_aterms_async has not been waited for");
-  stb_device_scope dev(g->dev);
-  g->put_n = g->flushed_n = 0;
-  g->put_maxn = g->put_maxt = 0;
-  g->putting = 0;
-  // (whatever still reads the device copy of the old pairs, or copies out of the staging area, must be through)
-  if (hipStreamSynchronize(g->st) != hipSuccess) return stb_fail("stb_groups_pairs_begin: %s", hipGetErrorString(hipGetLastError()));
-  // (each staging area for itself: one may be there from a call that failed on the other)
-  if (g->G && ((!g->h_pn && stb_pool_malloc((void **)&g->h_pn, 4 * (size_t)g->G, 1) != hipSuccess) ||
-               (!g->h_pt && stb_pool_malloc((void **)&g->h_pt, 2 * (size_t)g->G, 1) != hipSuccess)))
-    return stb_fail("stb_groups_pairs_begin: out of pinned host memory");
-  g->putting = 1;
+// ---- the grid form's helper jobs.  The tiles whose listed cells the strip's own wave does not look up: every strip of a table moves at the pace of
+// the strips to its left, and those hold most of the pairs (t uniform below n: columns like log) -- several
+// passes a group where the average strip has one.  Such a tile is only walked by its strip, which leaves the
+// state of its wave before the block as a record; waves whose strips the diagonal has not reached yet take the
+// tiles as jobs once their own strips have ended.  Which: all tiles of NWH passes a group and more (the lists in CSR
+// form among them), NWH chosen here (returned) and raised until the records fit (grid_geom::job_cap at Dmax discounts);
+// *jlim: the strips from the left that may have jobs.
+static unsigned jobs_rule(const grid_geom &gg, int D, int *jlim) {
+  // NWH at the least: what a job takes off the critical path it adds to the chip's work (the tile is walked twice),
+  // which the fuller chip can afford less (MI355X, 10^6 pairs, N = 10^4, kernel ms without jobs / NWH = 3 / 4 / 6 /
+  // 8 / 12: 32 discounts 1.21 / 1.00 / 0.96 / 1.01 / 1.04 / 1.09, 40: 1.26 / 1.10 / 1.02 / 1.05 / 1.08 / 1.12,
+  // 48: 1.26 / 1.30 / 1.14 / 1.09 / 1.10 / 1.15, 64: 1.36 / 1.59 / 1.39 / 1.29 / 1.28 / 1.29)
+  unsigned nwh = (unsigned)stb_env_int("STB_GRID_HELP_NW", 0);
+  if (nwh < 1) {
+    const double waves_per_simd = (double)gg.JW * D / (4.0 * stb_cu_count());
+    nwh = waves_per_simd <= 1.9 ? 4 : (waves_per_simd <= 2.7 ? 6 : 8);
+  }
+  // (a job is taken by a wave of a workgroup further right -- one with a higher ticket, for which the strip's own
+  // workgroup is running or through: the strips of a table's last workgroup have no jobs; GH_JQ = 64 queues)
+  *jlim = ((gg.JW - 1) / gg.P) * gg.P;
+  if (*jlim > 64) *jlim = 64;
+  return nwh;
+}
+// room for the most jobs there can be, kept from set to set
+static int jobs_room(stb_cell_list &l, unsigned n_tiles) {
+  if (!l.jobs && stb_pool_malloc((void **)&l.jobs, 4 * ((size_t)n_tiles + 128 + 1)) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
+  if (!l.tjob && stb_pool_malloc((void **)&l.tjob, 4 * (size_t)(n_tiles + 1)) != hipSuccess) return stb_fail("stb_groups_aterms: out of device memory");
   return 0;
 }
 
-// copy and maxima in one pass (the compiler turns both loops into vector code)
-static unsigned copy_max_u32(uint32_t *__restrict d, const uint32_t *__restrict s, size_t n, unsigned m) {
-  for (size_t i = 0; i < n; i++) {
-    const uint32_t v = s[i];
-    d[i] = v;
-    m = v > m ? v : m;
-  }
-  return m;
-}
-static unsigned copy_max_u16(uint16_t *__restrict d, const uint16_t *__restrict s, size_t n, unsigned m) {
-  uint16_t mm = 0;
-  for (size_t i = 0; i < n; i++) {
-    const uint16_t v = s[i];
-    d[i] = v;
-    mm = v > mm ? v : mm;
-  }
-  return mm > m ? mm : m;
-}
-
-static int put_flush(stb_groups_t *g, bool all) {
-  while (g->put_n - g->flushed_n >= (all ? 1u : STB_PUT_CHUNK)) {
-    const uint64_t c = all ? g->put_n - g->flushed_n : STB_PUT_CHUNK;
-    const uint64_t o = g->flushed_n;
-    HIPCHK(hipMemcpyAsync(g->d_n + o, g->h_pn + o, 4 * c, hipMemcpyHostToDevice, g->st));
-    HIPCHK(hipMemcpyAsync(g->d_t + o, g->h_pt + o, 2 * c, hipMemcpyHostToDevice, g->st));
-    g->flushed_n += c;
-  }
-  return 0;
-}
-
-extern "C" int stb_groups_pairs_put(stb_groups_t *g, const uint32_t *n, const uint16_t *t, uint64_t count, unsigned *maxn, unsigned *maxt) {
-  // (no STB_ENTRY: called a thousand times per set, and nothing below can reach the runtime's initialisation -- the
-  // set exists, so the runtime is up)
-  if (!g || !g->putting) return stb_fail("stb_groups_pairs_put: stb_groups_pairs_begin comes first");
-  if (g->put_n + count > g->G) return stb_fail("stb_groups_pairs_put: %llu pairs for a set of %llu", (unsigned long long)(g->put_n + count), (unsigned long long)g->G);
-  if (count) {
-    g->put_maxn = copy_max_u32(g->h_pn + g->put_n, n, count, g->put_maxn);
-    g->put_maxt = copy_max_u16(g->h_pt + g->put_n, t, count, g->put_maxt);
-    g->put_n += count;
-  }
-  if (maxn) *maxn = g->put_maxn;
-  if (maxt) *maxt = g->put_maxt;
-  if (g->put_n - g->flushed_n < STB_PUT_CHUNK) return 0;
-  stb_device_scope dev(g->dev);
-  return put_flush(g, false);
-}
-
-extern "C" int stb_groups_pairs_commit(stb_groups_t *g, const uint32_t *T, const double *bpar, unsigned N, unsigned M) {
-  STB_ENTRY;
-  if (!g || !g->putting) return stb_fail("stb_groups_pairs_commit: stb_groups_pairs_begin comes first");
-  if (g->put_n != g->G) return stb_fail("stb_groups_pairs_commit: %llu of the set's %llu pairs supplied", (unsigned long long)g->put_n, (unsigned long long)g->G);
-  stb_device_scope dev(g->dev);
-  g->putting = 0;
-  if (put_flush(g, true)) return 1;
-  if (N == 0 || M == 0) {
-    if (!g->have_bounds) return stb_fail("stb_groups_pairs_commit: the set has no table bounds yet");
-    N = g->N;
-    M = g->M;
-  }
-  if (stb_groups_set_bounds(g, N, M)) return 1;  // (drops what depends on the bounds when they change)
-  stb_groups_new_pairs(g, 0);
-  if (T && bpar && g->I > 0) {
-    memcpy(g->h_T, T, sizeof(uint32_t) * (size_t)g->I);
-    memcpy(g->h_bpar, bpar, sizeof(double) * (size_t)g->I);
-    if (hipMemcpyAsync(g->d_T, g->h_T, sizeof(uint32_t) * (size_t)g->I, hipMemcpyHostToDevice, g->st) != hipSuccess ||
-        hipMemcpyAsync(g->d_bpar, g->h_bpar, sizeof(double) * (size_t)g->I, hipMemcpyHostToDevice, g->st) != hipSuccess)
-      return stb_fail("stb_groups_pairs_commit: %s", hipGetErrorString(hipGetLastError()));
-  }
-  return 0;
-}
-
-// ---- a whole set at once, copied by several host threads while the calling thread hands the finished pieces to the
-// stream.  One core copies 6 MB into pinned memory in 0.41 ms (14.6 GB/s: what a core of the GPU box's host moves),
-// which was the largest single piece of a samplea call on new pairs; four copy 1.5 MB each while the DMA engine takes
-// what is done.  The workers are the library's own (started on first use, STB_PUT_THREADS of them, default 4; 0: the
-// calling thread copies); they touch host memory only.
-#include <atomic>
-#include <condition_variable>
-#include <memory>
-#include <mutex>
-#include <thread>
-
-namespace {
-struct put_slice {
-  // restaurants [i0, i1) of a ragged set, or one flat range when K is null; the slice's pairs start at `off`
-  int i0, i1;
-  uint64_t off, count;
-  std::atomic<uint64_t> done;  // pairs of the slice copied so far
-  unsigned maxn, maxt;
-};
-struct put_job {
-  const int *K;
-  uint32_t *const *n;
-  uint16_t *const *t;
-  const uint32_t *nflat;
-  const uint16_t *tflat;
-  uint32_t *dn;
-  uint16_t *dt;
-  put_slice *slices;
-  int nslices;
-  std::atomic<int> next;  // the next slice nobody has taken
-};
-struct put_pool {
-  std::mutex use;  // one hand-over at a time has the workers; another thread's meanwhile is copied by that thread itself
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<std::thread> th;
-  put_job *job = nullptr;
-  unsigned long long gen = 0;
-  int busy = 0;
-};
-put_pool *g_put_pool = nullptr;  // (never destroyed: its threads sleep until the process ends)
-std::once_flag g_put_once;
-
-// one slice, if any is left: copied by whoever calls (a worker of the pool, or the calling thread while it waits for them)
-bool put_step(put_job *J) {
-  {
-    const int k = J->next.fetch_add(1);
-    if (k >= J->nslices) return false;
-    put_slice &S = J->slices[k];
-    unsigned mn = 0, mt = 0;
-    uint64_t o = S.off, since = 0;
-    if (J->K) {
-      for (int i = S.i0; i < S.i1; i++) {
-        const uint64_t c = (uint64_t)(J->K[i] > 0 ? J->K[i] : 0);
-        mn = copy_max_u32(J->dn + o, J->n[i], c, mn);
-        mt = copy_max_u16(J->dt + o, J->t[i], c, mt);
-        o += c;
-        since += c;
-        if (since >= 32768) {  // (publish: the calling thread hands finished pieces to the stream)
-          S.done.store(o - S.off, std::memory_order_release);
-          since = 0;
-        }
-      }
-    } else {
-      for (uint64_t c0 = 0; c0 < S.count; c0 += 32768) {
-        const uint64_t c = S.count - c0 < 32768 ? S.count - c0 : 32768;
-        mn = copy_max_u32(J->dn + o, J->nflat + o, c, mn);
-        mt = copy_max_u16(J->dt + o, J->tflat + o, c, mt);
-        o += c;
-        S.done.store(o - S.off, std::memory_order_release);
-      }
+// The choice made ON the device (round 5: a set whose pairs are new gets its lists without a host round trip): one
+// workgroup; the tiles' words per group in, the job list in the layout of grid_hb.hip out (queue starts, number of jobs,
+// jobs in tile order = strip after strip, a strip's by block) together with every tile's place in it.
+__global__ __launch_bounds__(1024) void k_jobs_build(const unsigned *tnw, unsigned n_tiles, const unsigned *tile_off, int JW, int jlim, int R, int UC, int NB,
+                                                     unsigned cap, unsigned nwh0, unsigned *jobs, unsigned *tjob) {
+  __shared__ unsigned hist[64], s_nwh, s_scan[17], s_off[1024];
+  const unsigned tid = threadIdx.x;
+  if (tid < 64) hist[tid] = 0;
+  // (the strips' first tiles, looked at a dozen times per tile below: in LDS where they fit)
+  const bool off_lds = JW + 2 <= 1024;
+  if (off_lds)
+    for (int i = (int)tid; i < JW + 2; i += 1024) s_off[i] = tile_off[i];
+  __syncthreads();
+  const unsigned *toffp = off_lds ? s_off : tile_off;
+  for (unsigned t = tid; t < n_tiles; t += 1024) atomicAdd(&hist[min(tnw[t], 63u)], 1u);
+  __syncthreads();
+  if (tid == 0) {
+    // the smallest threshold from nwh0 on whose tiles fit (the tiles at or above a threshold grow as it falls): one pass
+    // from the top; 64 = none fits
+    unsigned nwh = 64, c = 0;
+    for (int k = 63; k >= (int)nwh0; k--) {
+      c += hist[k];
+      if (c > cap) break;
+      nwh = (unsigned)k;
     }
-    S.maxn = mn;
-    S.maxt = mt;
-    S.done.store(S.count, std::memory_order_release);
+    s_nwh = nwh;
   }
-  return true;
-}
-void put_run(put_job *J) {
-  while (put_step(J)) {
-  }
-}
-
-// (a fork()ed child has the pool's pointer but none of its threads: it copies on its own thread)
-void put_atfork_child() { g_put_pool = nullptr; }
-
-void put_worker(put_pool *P) {
-  unsigned long long seen = 0;
-  for (;;) {
-    put_job *J;
-    {
-      std::unique_lock<std::mutex> lk(P->mu);
-      P->cv.wait(lk, [&] { return P->gen != seen; });
-      seen = P->gen;
-      J = P->job;
-      if (!J) continue;
-      P->busy++;
+  __syncthreads();
+  const unsigned nwh = s_nwh;
+  // strip of a tile: tile_off[j + 1] is the first tile of strip j (entry 0 holds the total)
+  auto strip_of = [&](unsigned t) -> int {
+    int lo = 0, hi = JW - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) / 2;
+      if (toffp[mid + 1] <= t) lo = mid;
+      else hi = mid - 1;
     }
-    put_run(J);
-    {
-      std::lock_guard<std::mutex> lk(P->mu);
-      P->busy--;
-    }
-    P->cv.notify_all();
-  }
-}
-}  // namespace
-
-// all G pairs of the set, ragged (K, n[i], t[i]) or flat (K null: nflat, tflat), between begin and commit
-static int put_all(stb_groups_t *g, int I, const int *K, uint32_t *const *n, uint16_t *const *t, const uint32_t *nflat, const uint16_t *tflat,
-                   unsigned *maxn, unsigned *maxt) {
-  if (!g || !g->putting || g->put_n != 0) return stb_fail("stb_groups_pairs_put_ragged: between stb_groups_pairs_begin and the first put only");
-  uint64_t G = 0;
-  if (K) {
-    for (int i = 0; i < I; i++) G += (uint64_t)(K[i] > 0 ? K[i] : 0);
-    if (G != g->G) return stb_fail("stb_groups_pairs_put_ragged: %llu pairs for a set of %llu", (unsigned long long)G, (unsigned long long)g->G);
-  } else {
-    G = g->G;
-  }
-  int W = stb_env_int("STB_PUT_THREADS", 4);
-  // (the cores this process may run on, not those of the machine: under taskset to one core the calling thread copies alone)
-  unsigned hw = std::thread::hardware_concurrency();
-  {
-    cpu_set_t cs;
-    CPU_ZERO(&cs);
-    if (sched_getaffinity(0, sizeof(cs), &cs) == 0 && CPU_COUNT(&cs) > 0) hw = (unsigned)CPU_COUNT(&cs);
-  }
-  if (hw && W > (int)hw - 1) W = (int)hw - 1;
-  if (W > 16) W = 16;
-  if (G < 131072) W = 0;  // (small sets: the calling thread is through before a worker is awake)
-  // slices of about 64 K pairs, taken in order by whoever is free
-  const uint64_t per = 65536;
-  const size_t cap = (size_t)(G / per + 2);  // (every slice but the last holds at least `per` pairs)
-  std::unique_ptr<put_slice[]> slices(new put_slice[cap]);
-  int ns = 0;
-  auto add = [&](int i0, int i1, uint64_t off, uint64_t cnt) {
-    put_slice &S = slices[(size_t)ns++];
-    S.i0 = i0;
-    S.i1 = i1;
-    S.off = off;
-    S.count = cnt;
-    S.done.store(0);
-    S.maxn = S.maxt = 0;
+    return lo;
   };
-  if (K) {
-    int i0 = 0;
-    uint64_t off = 0, cnt = 0;
-    for (int i = 0; i < I; i++) {
-      cnt += (uint64_t)(K[i] > 0 ? K[i] : 0);
-      if (cnt >= per || i == I - 1) {
-        add(i0, i + 1, off, cnt);
-        off += cnt;
-        cnt = 0;
-        i0 = i + 1;
-      }
-    }
-  } else {
-    for (uint64_t off = 0; off < G; off += per) add(0, 0, off, G - off < per ? G - off : per);
-  }
-  put_job J;
-  J.K = K;
-  J.n = n;
-  J.t = t;
-  J.nflat = nflat;
-  J.tflat = tflat;
-  J.dn = g->h_pn;
-  J.dt = g->h_pt;
-  J.slices = slices.get();
-  J.nslices = ns;
-  J.next.store(0);
-  put_pool *P = nullptr;
-  std::unique_lock<std::mutex> use_lk;
-  if (W > 0 && J.nslices > 1) {
-    std::call_once(g_put_once, [W] {
-      put_pool *np = new put_pool;
-      try {
-        for (int w = 0; w < W; w++) np->th.emplace_back(put_worker, np);
-      } catch (...) {  // (no more threads to be had: those that started serve; none: the callers copy themselves)
-      }
-      for (auto &th : np->th) th.detach();
-      g_put_pool = np;
-      (void)pthread_atfork(nullptr, nullptr, put_atfork_child);
-    });
-    P = (g_put_pool && !g_put_pool->th.empty()) ? g_put_pool : nullptr;
-    if (P) {
-      // (samplers of different host threads share the workers: whoever finds them busy copies on its own thread)
-      use_lk = std::unique_lock<std::mutex>(P->use, std::try_to_lock);
-      if (!use_lk.owns_lock()) P = nullptr;
+  const int jend = JW < jlim ? JW : jlim;  // strips that may have jobs
+  const unsigned per = (n_tiles + 1023u) / 1024u, t0 = tid * per, t1 = min(t0 + per, n_tiles);
+  unsigned mine = 0;
+  if (nwh <= 63)
+    for (unsigned t = t0; t < t1; t++) mine += (tnw[t] >= nwh && strip_of(t) < jend) ? 1u : 0u;
+  unsigned total = 0;
+  unsigned k = stb_block_exclusive_1024(mine, s_scan, &total);
+  for (unsigned t = t0; t < t1; t++) {
+    const int j = strip_of(t);
+    if (t == toffp[j + 1] && j <= GH_JQ_HOST) jobs[j] = (j < jend) ? k : total;  // the first tile of strip j: its queue starts here
+    if (nwh <= 63 && tnw[t] >= nwh && j < jend) {
+      const int b = (int)(((long long)j * UC) / R) + (int)(t - toffp[j + 1]);
+      jobs[128 + k] = (unsigned)j | ((unsigned)b << 16);
+      tjob[t] = k;
+      k++;
+    } else {
+      tjob[t] = 0xffffffffu;
     }
   }
-  if (P) {
-    {
-      std::lock_guard<std::mutex> lk(P->mu);
-      P->job = &J;
-      P->gen++;
-    }
-    P->cv.notify_all();
+  // queue starts of the strips there are not (or that may have no jobs), and the number of jobs
+  for (int j = (int)tid; j <= GH_JQ_HOST; j += 1024)
+    if (j >= jend) jobs[j] = total;
+  if (tid == 0) jobs[GH_JQ_HOST + 1] = total;
+}
+
+// queued on the set's stream behind the kernels that produced `tnw`; no host synchronisation
+int stb_lists_jobs_device(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *tnw) {
+  stb_cell_list &l = g->lists[which];
+  const unsigned n_tiles = gg.n_tiles;
+  l.n_jobs = 0;
+  const unsigned cap = stb_grid_job_cap(gg.C, g->Dmax, n_tiles, gg.phases);
+  if (!cap || !n_tiles) {
+    if (l.jobs) HIPCHK(hipMemsetAsync(l.jobs, 0, 4 * 128, g->st));
+    return 0;
   }
-  int rc = 0;
-  {
-    stb_device_scope dev(g->dev);
-    if (!P) put_run(&J);  // (the calling thread copies; the pieces go out below)
-    // hand finished pieces to the stream, in order, while the workers copy
-    uint64_t flushed = 0;
-    int k = 0;
-    while (k < J.nslices && !rc) {
-      put_slice &S = slices[(size_t)k];
-      const uint64_t d = S.done.load(std::memory_order_acquire);
-      const uint64_t upto = S.off + d;
-      if (d == S.count) k++;
-      if (upto - flushed >= 131072 || (k == J.nslices && upto > flushed)) {
-        if (hipMemcpyAsync(g->d_n + flushed, g->h_pn + flushed, 4 * (upto - flushed), hipMemcpyHostToDevice, g->st) != hipSuccess ||
-            hipMemcpyAsync(g->d_t + flushed, g->h_pt + flushed, 2 * (upto - flushed), hipMemcpyHostToDevice, g->st) != hipSuccess)
-          rc = stb_fail("stb_groups_pairs_put_ragged: %s", hipGetErrorString(hipGetLastError()));
-        flushed = upto;
-      } else if (d != S.count) {
-        // (nothing to hand over yet: take a slice too -- the workers may be busy, few, or, in a fork()ed child, gone)
-        if (!put_step(&J)) __builtin_ia32_pause();
-      }
-    }
-  }
-  if (P) {  // (the job lives on this stack: every worker must have let go of it)
-    std::unique_lock<std::mutex> lk(P->mu);
-    P->job = nullptr;
-    P->cv.wait(lk, [&] { return P->busy == 0; });
-  }
-  if (rc) return rc;
-  unsigned mn = 0, mt = 0;
-  for (int k = 0; k < ns; k++) {
-    mn = slices[(size_t)k].maxn > mn ? slices[(size_t)k].maxn : mn;
-    mt = slices[(size_t)k].maxt > mt ? slices[(size_t)k].maxt : mt;
-  }
-  g->put_n = g->flushed_n = G;
-  g->put_maxn = mn;
-  g->put_maxt = mt;
-  if (maxn) *maxn = mn;
-  if (maxt) *maxt = mt;
+  int jlim;
+  const unsigned nwh = jobs_rule(gg, D, &jlim);
+  if (jobs_room(l, n_tiles)) return 1;
+  hipLaunchKernelGGL(k_jobs_build, dim3(1), dim3(1024), 0, g->st, tnw, n_tiles, l.tile_off, gg.JW, jlim, gg.R, gg.U * gg.C, gg.NB, cap, nwh, l.jobs, l.tjob);
+  HIPCHK(hipGetLastError());
+  l.n_jobs = cap;  // (at most; the number itself stays on the device)
   return 0;
 }
 
-extern "C" int stb_groups_pairs_put_ragged(stb_groups_t *g, int I, const int *K, uint32_t *const *n, uint16_t *const *t, unsigned *maxn, unsigned *maxt) {
-  if (!K || !n || !t) return stb_fail("stb_groups_pairs_put_ragged: null argument");
-  return put_all(g, I, K, n, t, nullptr, nullptr, maxn, maxt);
+// The same choice on the host, for the sort-based builder.  h_nw: words per group of every tile (host).  The lists go to
+// the device on the set's stream.
+int stb_lists_jobs_from(stb_groups_t *g, int which, int D, const grid_geom &gg, const unsigned *h_nw) {
+  stb_cell_list &l = g->lists[which];
+  const unsigned n_tiles = gg.n_tiles;
+  l.n_jobs = 0;
+  const unsigned cap = stb_grid_job_cap(gg.C, g->Dmax, n_tiles, gg.phases);
+  if (!cap || !n_tiles) {
+    // (no jobs: a list left by an earlier build must say so -- the kernels read the number of jobs from it)
+    if (l.jobs && (hipMemsetAsync(l.jobs, 0, 4 * 128, g->st) != hipSuccess || hipStreamSynchronize(g->st) != hipSuccess))
+      return stb_fail("stb_groups_aterms: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+  }
+  unsigned hist[65] = {0};  // (an upper bound: the tiles of all strips)
+  for (unsigned t = 0; t < n_tiles; t++) hist[h_nw[t] > 63 ? 63 : h_nw[t]]++;
+  int jlim;
+  unsigned nwh = jobs_rule(gg, D, &jlim);
+  for (; nwh <= 63; nwh++) {
+    unsigned c = 0;
+    for (unsigned k = nwh; k <= 63; k++) c += hist[k];
+    if (c <= cap) break;
+  }
+  std::vector<unsigned> jobs, tjob(n_tiles, 0xffffffffu), off;
+  stb_grid_tile_offsets(gg, off);
+  const int UCg = gg.U * gg.C;
+  std::vector<unsigned> qoff(64 + 1, 0u);
+  if (nwh <= 63) {
+    // strip after strip, a strip's tiles by block: a queue per strip
+    for (int j = 0; j < gg.JW && j < jlim; j++) {
+      const int b00 = (int)(((long long)j * UCg) / gg.R);
+      qoff[j] = (unsigned)jobs.size();
+      for (int b = b00; b < gg.NB; b++)
+        if (h_nw[off[j + 1] + (unsigned)(b - b00)] >= nwh) {
+          tjob[off[j + 1] + (unsigned)(b - b00)] = (unsigned)jobs.size();
+          jobs.push_back((unsigned)j | ((unsigned)b << 16));
+        }
+    }
+    for (int j = (gg.JW < jlim ? gg.JW : jlim); j <= 64; j++) qoff[j] = (unsigned)jobs.size();
+    if (jobs.size() > cap) {  // (the bound above counted every strip's tiles: cannot happen)
+      jobs.clear();
+      std::fill(tjob.begin(), tjob.end(), 0xffffffffu);
+      std::fill(qoff.begin(), qoff.end(), 0u);
+    }
+  }
+  const size_t nj = jobs.size();
+  {
+    // the list as the kernels read it (grid_hb.hip: GH_JQ + 1 queue starts, the number of jobs at word 65, jobs from word 128)
+    std::vector<unsigned> lay(128, 0u);
+    for (int j = 0; j <= 64; j++) lay[(size_t)j] = qoff[(size_t)j];
+    lay[65] = (unsigned)nj;
+    lay.insert(lay.end(), jobs.begin(), jobs.end());
+    jobs.swap(lay);
+  }
+  // (the copies are synchronous: the vectors above go away)
+  if (jobs_room(l, n_tiles)) return 1;
+  if (hipMemcpyAsync(l.tjob, tjob.data(), 4 * (size_t)n_tiles, hipMemcpyHostToDevice, g->st) != hipSuccess ||
+      hipMemcpyAsync(l.jobs, jobs.data(), 4 * jobs.size(), hipMemcpyHostToDevice, g->st) != hipSuccess || hipStreamSynchronize(g->st) != hipSuccess)
+    return stb_fail("stb_groups_aterms: %s", hipGetErrorString(hipGetLastError()));
+  l.n_jobs = (unsigned)nj;
+  return 0;
 }
 
-// new pairs for the same shape and the same table bounds, from flat arrays
-extern "C" int stb_groups_update_pairs(stb_groups_t *g, const uint32_t *nflat, const uint16_t *tflat) {
-  if (!g) return stb_fail("stb_groups_update_pairs: null group set");
-  if (!g->have_bounds) return stb_fail("stb_groups_update_pairs: the set has no table bounds yet (stb_groups_pairs_commit sets them)");
-  if (stb_groups_pairs_begin(g)) return 1;
-  if (g->G && put_all(g, 0, nullptr, nullptr, nullptr, nflat, tflat, nullptr, nullptr)) return 1;
-  return stb_groups_pairs_commit(g, nullptr, nullptr, 0, 0);
+// ---- the way in: the layout an evaluation of D discounts in the form `which` reads, with the geometry of its items
+// (for the grid forms H is filled from gg; H.rec_off is left to match_strip_shape)
+static int resolve_layout(const stb_groups_t *g, int &which, int D, hb_dot_info &H, grid_geom &gg) {
+  memset(&H, 0, sizeof(H));
+  memset(&gg, 0, sizeof(gg));
+  if (which == 2 && stb_hb_dot_info(g->N, g->M, g->Dmax, &H, g->hb_sum_C)) return stb_fail("stb_groups_aterms: no halo-block geometry for N=%u M=%u", g->N, g->M);
+  if (which < 3) return 0;
+  // (the strip shape of the grid form depends on the number of discounts: a list per shape)
+  if (stb_grid_geometry(g->N, g->M, D, &gg)) return stb_fail("stb_groups_aterms: no grid geometry for N=%u M=%u", g->N, g->M);
+  which = stb_grid_which(gg.C);
+  H.R = gg.R;
+  H.UC = gg.U * gg.C;
+  H.HC = gg.HL * gg.C;
+  H.NB = gg.NB;
+  H.JW = gg.JW;
+  H.NQ = gg.NQ;
+  H.G = gg.G;
+  H.C = gg.C;
+  H.n_tiles = H.n_rec = gg.n_tiles;
+  return 0;
+}
+
+// a grid layout's list serves one strip shape: what was built for another goes, and the tile offsets of this one are there
+static int match_strip_shape(stb_groups_t *g, stb_cell_list &l, hb_dot_info &H, const grid_geom &gg) {
+  if ((l.ready || l.tile_off) && (l.R != H.R || l.G != H.G)) {
+    (void)hipStreamSynchronize(g->st);
+    stb_list_release(l, true);
+  }
+  if (!l.ready && !l.tile_off) {
+    std::vector<unsigned> off;
+    stb_grid_tile_offsets(gg, off);
+    if (stb_pool_malloc((void **)&l.tile_off, off.size() * sizeof(unsigned)) != hipSuccess ||
+        hipMemcpy(l.tile_off, off.data(), off.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess)
+      return stb_fail("stb_groups_aterms: out of device memory");
+  }
+  H.rec_off = l.tile_off;
+  return 0;
+}
+
+int stb_lists_build(stb_groups_t *g, int which, int D) {
+  hb_dot_info H;
+  grid_geom gg;
+  if (resolve_layout(g, which, D, H, gg)) return 1;
+  stb_cell_list &l = g->lists[which];
+  if (which >= 3 && match_strip_shape(g, l, H, gg)) return 1;
+  if (l.ready) return 0;
+  // from the count slab: no sort, no host round trip; where it does not apply, the sort
+  const int rc = stb_lists_slab_build(g, which, D, H, gg);
+  return rc != 2 ? rc : stb_lists_sort_build(g, which, D, H, gg);
 }

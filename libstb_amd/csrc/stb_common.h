@@ -11,6 +11,7 @@
 //   fill_rows.hip    k_fill_rows: the reference's own operation order (log domain / V ratios)
 //   sweep_terms.hip  k_lookup, k_to_float, k_sweep_partial, k_terms_partial, reductions
 //   groups.hip       stb_groups_*: device-resident (n,t) pairs and the aterms evaluation
+//   lists.hip, lists_sorted.hip, pairs.hip   the cell lists of the fused evaluation (two builders), the pairs' way to the device
 //   tcounts.hip, tindic.hip, tdish.hip, tcwin.hip, partition.hip   the sampler sweeps' kernels and raw calls
 //   tcounts_obj.hip, tindic_obj.hip   stb_tcounts_* / stb_tindic_*: the resident-count objects, host code only
 //   tools/ablation/ablation.hip   superseded fill forms, in a library of their own (make -C tools/ablation)

@@ -378,3 +378,99 @@ def test_random_shapes_lists_from_the_slab_equal_the_sorted_lists(monkeypatch, s
         assert np.all(np.isfinite(outs["1"])) and orc.close(outs["1"], want, 1e-12), (outs["1"], want)
     else:
         assert np.all(np.isneginf(outs["1"])) and np.all(np.isneginf(want))
+
+
+KEPT = [f for f in FORMS if f[0] in ("hb4", "grid4", "grid4jobs", "grid8")]
+
+
+@pytest.mark.parametrize("name,env,Ds", KEPT, ids=[f[0] for f in KEPT])
+def test_a_kept_set_whose_list_builders_alternate(monkeypatch, name, env, Ds):
+    """one set, hand-over after hand-over, its lists built by the count slab, the sort, the slab, the sort: what the slab
+    builder sized for the most the pairs can need is kept over a hand-over and re-sized exactly by the sort-based builder,
+    what the sort-based builder sized goes with the old pairs -- every evaluation has the bits of a set created from those
+    pairs under the same switch, and none is redone through stored tables"""
+    L = capi.lib()
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    N = M = 1500
+    g, n1, t1 = edgy(11)
+    _, n2, t2 = edgy(12)
+    n3, t3 = n1.copy(), t1.copy()
+    n3[100] += 1                                    # one customer joins one table
+    D = max(Ds)
+    x = synth.discount_grid(64)[::7][:D]
+
+    def fresh(n, t):
+        h0 = create(L, g, n, t, N, M, D)
+        try:
+            return [aterms(L, h0, x[:d]) for d in Ds]
+        finally:
+            L.stb_groups_free(h0)
+
+    fb = L.stb_groups_fallbacks()
+    monkeypatch.setenv("STB_LISTS_SLAB", "1")
+    first = fresh(n1, t1)
+    h = create(L, g, n1, t1, N, M, D)
+    try:
+        for d, want in zip(Ds, first):
+            assert np.all(np.isfinite(want)) and np.array_equal(aterms(L, h, x[:d]), want), ("created", d)
+        for slab, (n, t) in (("0", (n2, t2)), ("1", (n3, t3)), ("0", (n1, t1))):
+            monkeypatch.setenv("STB_LISTS_SLAB", slab)     # (read at every build)
+            wants = fresh(n, t)
+            capi.check(L.stb_groups_update_pairs(h, orc.u32p(n), orc.u16p(t)))
+            for d, want in zip(Ds, wants):
+                assert np.array_equal(aterms(L, h, x[:d]), want), (slab, d)
+        for d, want, was in zip(Ds, wants, first):          # the first pairs again: the first values, whichever builder
+            assert np.array_equal(want, was), d
+    finally:
+        L.stb_groups_free(h)
+    assert L.stb_groups_fallbacks() == fb
+
+
+def last_form(L, h):
+    v = [C.c_int() for _ in range(5)]
+    capi.check(L.stb_groups_last_form(h, *[C.byref(q) for q in v]))
+    return tuple(q.value for q in v)
+
+
+def test_a_kept_grid_set_whose_strip_shape_changes(monkeypatch):
+    """the grid form's lists are built for one strip shape (rows of a block, rows of a group): a kept set evaluated with
+    blocks of 24 rows, of 48, of 24 again drops the lists, tile offsets and helper jobs of the other shape each time and
+    has the bits of a set created under that setting.  Created with the 24-row blocks, the shape with more blocks, whose
+    workspace holds either."""
+    L = capi.lib()
+    monkeypatch.setenv("STB_ATERMS_GRID", "1")
+    monkeypatch.setenv("STB_GRID_C", "4")
+    N = M = 1500
+    D = 8
+    g, n, t = edgy(11)
+    x = synth.discount_grid(64)[::7][:D]
+    want = {}
+    for rows in ("24", None):
+        if rows:
+            monkeypatch.setenv("STB_GRID_ROWS", rows)
+        else:
+            monkeypatch.delenv("STB_GRID_ROWS")
+        h0 = create(L, g, n, t, N, M, D)
+        try:
+            want[rows] = aterms(L, h0, x)
+            assert last_form(L, h0)[4] == (24 if rows else 48)
+        finally:
+            L.stb_groups_free(h0)
+    assert np.all(np.isfinite(want["24"])) and np.all(np.isfinite(want[None]))
+    fb = L.stb_groups_fallbacks()
+    monkeypatch.setenv("STB_GRID_ROWS", "24")
+    h = create(L, g, n, t, N, M, D)
+    try:
+        for rows, R in (("24", 24), (None, 48), ("24", 24)):
+            if rows:
+                monkeypatch.setenv("STB_GRID_ROWS", rows)
+            else:
+                monkeypatch.delenv("STB_GRID_ROWS")
+            got = aterms(L, h, x)
+            fused, which, sparse, Cc, Rr = last_form(L, h)
+            assert (fused, which, sparse, Cc, Rr) == (1, 4, 1, 4, R), (rows, fused, which, sparse, Cc, Rr)
+            assert np.array_equal(got, want[rows]), (rows, got, want[rows])
+    finally:
+        L.stb_groups_free(h)
+    assert L.stb_groups_fallbacks() == fb
