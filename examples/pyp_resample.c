@@ -49,10 +49,16 @@
  *      Gamma(1.1, 1) prior (stb_tindic_sample_beta) and feeds that iteration's stb_tindic_sample_lik and -C; without -H
  *      gamma, the prior of the flat base weights, is drawn too, under Gamma(1.1, 10) (stb_tindic_sample_gamma), and feeds
  *      stb_tindic_sample_h and -C.  Each iteration prints the drawn values.  (Under -H the root's gamma stays 1.)
+ *  16. with -S (needs -d) the device loop does not start from the seating built in step 1: the object forgets it and seats
+ *      its customers one by one on the device, from empty restaurants, under the start values of a and b and (with -z) the
+ *      likelihood (stb_tindic_seat); the line printed is the log weight of that seating.
+ *  17. with -Q R (needs -P) each iteration's held-out figures gain the sequential estimate: every restaurant's held-out
+ *      customers seated one after another on a private copy of its state, R particles averaged inside the logarithm
+ *      (stb_tindic_heldout_seq) -- the likelihood of the held-out customers as a whole, where -P scores each one alone.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16]
  */
 #include <math.h>
 #include <stdio.h>
@@ -73,10 +79,10 @@ static int cmp_double(const void *x, const void *y) {
 }
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, c, j, i, it;
   double a0 = 0.5, b0 = 10.0, beta = 0.5, gam = 1.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CK")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -95,6 +101,8 @@ int main(int argc, char **argv) {
     else if (c == 'H') hgroups = atoi(optarg);
     else if (c == 'C') collapsed = 1;
     else if (c == 'K') drawconc = 1;
+    else if (c == 'S') seatdev = 1;
+    else if (c == 'Q') seqpart = atoi(optarg) >= 1 ? atoi(optarg) : -1;
     else return 2;
   }
   if (collapsed && !(explicit_d && dishes && redraw)) {
@@ -115,6 +123,14 @@ int main(int argc, char **argv) {
   }
   if (predict && !(explicit_d && dishes)) {
     fprintf(stderr, "pyp_resample: -P needs -d -z\n");
+    return 2;
+  }
+  if (seatdev && !explicit_d) {
+    fprintf(stderr, "pyp_resample: -S needs -d\n");
+    return 2;
+  }
+  if (seqpart < 0 || seqpart > 4096 || (seqpart && !predict)) {
+    fprintf(stderr, "pyp_resample: -Q R needs 1 <= R <= 4096 and -P\n");
     return 2;
   }
   if (pergroup && (!explicit_d || joint)) {
@@ -186,7 +202,7 @@ int main(int argc, char **argv) {
         hf[g] = 1.0 / DISHES;
       }
     for (cc = 0; cc < (size_t)J * ncust; cc++) cust[cc] = (scnt_int)dish_of[cc]; /* (K = DISHES: the dish is the local pair) */
-    stb_tindic_t *ti = stb_tindic_create(J, K, nf, tf, hf, cust, maxn > 65535 || (dishes && ncust > 65535) ? 65535 : 0, 0);
+    stb_tindic_t *ti = stb_tindic_create(J, K, nf, tf, hf, cust, maxn > 65535 || ((dishes || seatdev) && ncust > 65535) ? 65535 : 0, 0);
     stb_groups_t *gs = stb_groups_create(J, K, NULL, NULL, NULL, NULL, 0, 0, joint ? 25 : 3);
     int accepted = 0, steps = 0;
     if (!ti || !gs) yaps_quit("device loop: %s\n", stb_last_error());
@@ -224,6 +240,13 @@ int main(int argc, char **argv) {
       if (stb_tindic_set_hgroups(ti, hgroups, hgoff)) yaps_quit("stb_tindic_set_hgroups: %s\n", stb_last_error());
       free(hgoff);
       hflat = malloc(sizeof(double) * (size_t)J * DISHES);
+    }
+    if (seatdev) { /* the start state from the model, on the device: a seed of its own */
+      double lw;
+      stb_seat_info_t si;
+      if (stb_tindic_seat(ti, a, bp, (uint64_t)seed + 7, 0, &lw, &si)) yaps_quit("stb_tindic_seat: %s\n", stb_last_error());
+      printf("start state seated on the device: %llu customers, log weight %.6f, %llu impossible visits\n",
+             (unsigned long long)si.customers, lw, (unsigned long long)si.impossible);
     }
     for (it = 0; it < cycles; it++) {
       if (dishes) {
@@ -316,8 +339,15 @@ int main(int argc, char **argv) {
         double ho;
         if (stb_tindic_heldout(ti, a, bp, 0, &ho, NULL, NULL) || stb_tindic_heldout(ti, a, bp, STB_PR_ACCUMULATE, &ho_avg, NULL, NULL))
           yaps_quit("stb_tindic_heldout: %s\n", stb_last_error());
-        if (showlj) printf(" heldout %.6f avg %.6f\n", ho, ho_avg);
-        else printf("iteration %d: heldout %.6f avg %.6f\n", it, ho, ho_avg);
+        if (showlj) printf(" heldout %.6f avg %.6f", ho, ho_avg);
+        else printf("iteration %d: heldout %.6f avg %.6f", it, ho, ho_avg);
+        if (seqpart) { /* the held-out customers of a restaurant as a whole: seated one by one, a seed of its own */
+          double hs;
+          if (stb_tindic_heldout_seq(ti, a, bp, (unsigned)seqpart, (uint64_t)seed + 8, (uint64_t)it * 4096u, &hs, NULL, NULL))
+            yaps_quit("stb_tindic_heldout_seq: %s\n", stb_last_error());
+          printf(" seq %.6f", hs);
+        }
+        printf("\n");
       }
       if (collapsed) { /* h and the likelihood summed out: alpha 0 is the concentration the -H step left on the object */
         stb_cj_opts_t co = {0.0, hgroups ? 1.0 : gam, beta, NULL, NULL};
@@ -349,7 +379,7 @@ int main(int argc, char **argv) {
     if (joint) printf("joint steps: %d of %d proposals accepted, last a=%.4f b=%.3f\n", accepted, steps, a, b);
     for (j = 0, g = 0; j < J; j++)
       for (i = 0; i < DISHES; i++, g++) t[j][i] = tf[g];
-    if (dishes) { /* the customers moved: n comes back too */
+    if (dishes || seatdev) { /* the customers moved: n comes back too */
       unsigned long long moved = 0;
       if (stb_tindic_get_state(ti, nf, cust)) yaps_quit("stb_tindic_get_state: %s\n", stb_last_error());
       for (j = 0, g = 0; j < J; j++)
@@ -358,8 +388,9 @@ int main(int argc, char **argv) {
           if (nf[g] >= maxn) maxn = nf[g] + 1;
         }
       for (cc = 0; cc < (size_t)J * ncust; cc++) moved += cust[cc] != (scnt_int)dish_of[cc];
-      printf("dish sweeps: %llu of %llu customers ended at another dish, %llu visits found none\n", moved,
-             (unsigned long long)J * ncust, stuck);
+      if (dishes)
+        printf("dish sweeps: %llu of %llu customers ended at another dish, %llu visits found none\n", moved,
+               (unsigned long long)J * ncust, stuck);
     }
     stb_groups_free(gs);
     stb_tindic_free(ti);

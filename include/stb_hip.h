@@ -1135,6 +1135,84 @@ int stb_tindic_heldout(stb_tindic_t *s, double a, const double *bpar, unsigned f
 int stb_tindic_heldout_reset(stb_tindic_t *s);
 int stb_tindic_heldout_get(stb_tindic_t *s, double *p_out /* or NULL */, unsigned *samples /* or NULL */);
 
+/* ---- seating customers one by one: start states and the likelihood of unseen documents (seat.hip) ----
+ * The Chinese-restaurant seating run forwards.  Restaurant i has pairs (n_k, t_k, h_k), T = sum t, N = sum n, b_i and a.
+ * The next customer, of class w, sits in dish k at an old table with weight L_k (n_k - t_k a) and at a new one with
+ * weight L_k (b + T a) h_k, both over b + N, L_k = lik[w stride + k]: the theta of stb_predict_dishes.  Seat a sequence
+ * of customers this way, each (dish, old or new) drawn from those weights, and let W = prod_c p_c, p_c = sum_k theta_k
+ * L_k on the state before c.  Then for every final state (z, t)
+ *     sum over the paths that reach (z, t) of P(path) W(path)
+ *         = (b|a)_T / (b)_N  prod_k S^{n_k}_{t_k} h_k^{t_k}  prod_c L[cls_c][z_c],
+ * the unnormalised joint of the dish sweep.  So E[W] = p(w_1 .. w_N | L, h, a, b), the marginal
+ * likelihood of the sequence with the seating summed out: log((1/R) sum_r W_r) over R independent particles estimates
+ * its log (sequential importance sampling, the particle form of the left-to-right evaluation); and with L = 1 the
+ * final state is an exact draw from the prior.  With a truncation M (no new table in a dish that has t = M) the same
+ * holds over the states with t <= M.  No Stirling table is read.
+ *
+ * stb_seat_customers (k_seat): one wave per (restaurant, particle), lanes over dishes; K_i <= 64 keeps the state in
+ * registers, larger K_i in LDS, chosen per restaurant.  n and t on entry are the start state (all zero: an empty
+ * restaurant); T_i and N_i are the kernel's own integer sums over the pairs.  The customers to seat are CSR over
+ * d_coff[I + 1] with classes d_cls (read only with a matrix).  The arithmetic is part of the contract (FP64, no
+ * contraction, left to right as written, conversions to double first; tests/st_oracle.py replays it).  The stream of
+ * particle r is that of sweep `sweep + r`: key = mix(seed + (sweep + r + 1) gamma), element j = stb_unit(key, j); C =
+ * d_coff[I], c the flat customer index.  A visit to customer c of class w, on the particle's private (n_k, t_k, T, N):
+ *   1. g = b + T * a;  den = b + N;  x_k = n_k - t_k * a;  y_k = (n_k >= 1 && t_k + 1 > M) ? 0 : g * h_k;
+ *      theta_k = N == 0 ? h_k : (x_k + y_k) / den;  L_k as stb_predict_dishes (0 when w >= rows, 1 without a matrix);
+ *      q_k = theta_k * L_k.  (h = 1.0 without d_h.)
+ *   2. the cumulative sums of q in the dish sweep's association: blocks of 64 dishes (+0.0 past K_i), a Kogge-Stone
+ *      inclusive scan inside a block, the block bases added in sequence; Z = the last base, p_c = Z.  thr = u3 * Z, u3 =
+ *      element 2C + 1 + c; k* = the smallest k with q_k > 0 and cum_k > thr, else the largest k with q_k > 0.
+ *   3. impossible -- Z not positive and finite: p_c = 0, the particle's log weight is -inf, the visit is counted; so
+ *      that a committed state stays valid the customer is seated by the same rule on q_k = theta_k, with the same u3; if
+ *      that sum is not positive and finite either (h <= 0) it is seated at k = 0 and the visit is counted as stuck.
+ *   4. new = n_k* == 0 || u2 * (x + y) < y, with k*'s x and y and u2 = element 2c + 2.  n_k* += 1, N += 1; if new:
+ *      t_k* += 1, T += 1.  M = 0 means 65535 (t is a uint16).
+ *   5. lw += log(p_c) in seating order, in double-double; at the end lw = hi + lo.  d_lw[i particles + r] = lw.
+ * The bits of n, t, T, cust and every p_c depend on (seed, sweep, r, c, C) and the start state alone: not on the waves
+ * of a workgroup (STB_SEAT_WAVES = 1, 2, 4 or 8; default 4), the register or LDS form, or which restaurants share the
+ * call.  Without STB_SEAT_COMMIT nothing but d_lw is written.  With it particles must be 1, and n, t, d_T[i] = T,
+ * d_cust[c] = k* and (d_p non-null) d_p[c] = p_c are written.  A restaurant with K_i > STB_TD_MAXK, K_i > stride (with a
+ * matrix), or K_i = 0 with customers is left untouched, its lw is 0 and it is counted in skipped.  d_info: NULL, or
+ * three uint64 on the device the call adds to: skipped restaurants, impossible visits, stuck visits (visits counted
+ * per particle).  No wait: the call returns when the launch is queued.
+ *
+ * stb_seat_loglik (k_seat_sum): per restaurant m = max_r lw_r, s = sum_r exp(lw_r - m) in particle order in plain
+ * doubles, H_i = m + log(s / (double)R).  Every lw_r -inf: H_i = -inf, no NaN, the restaurant is counted
+ * (info->impossible; the other counters of info are 0) and the total is -inf.  Over restaurants: stb_logjoint's
+ * association, geometry and ticket, as stb_heldout_loglik (waves STB_SEAT_WAVES where it is set).  One launch, one wait;
+ * *total_host arrives through pinned memory.
+ * Refused before anything is queued, with stb_last_error() set: what stb_predict_dishes refuses (a outside [0, 1), a
+ * null koff, n, t, coff or bpar, a matrix without classes or with rows or stride 0, I < 0), M > 65535, particles = 0 or
+ * > 4096, STB_SEAT_COMMIT with particles != 1 or without d_T and d_cust, unknown flags, a null d_lw or total_host.
+ *
+ * Object layer, on an stb_tindic_t, queued on the object's stream:
+ *   stb_tindic_seat         forgets the object's seating and seats all its C customers in CSR order from empty
+ *                           restaurants, under the object's classes and matrix (the prior when none is set): writes n,
+ *                           t, T and cust.  It does to the bounds what the first dish sweep does (the customer sequence
+ *                           exists, N = max(3, max_i N_i), M as given at create, the largest n vouched for is max_i N_i),
+ *                           so every later call works on the result with no read-back.  *total = sum_i lw_i.  info:
+ *                           skipped, impossible, stuck as above, customers = C.  Refused as stb_tindic_sweep_dishes
+ *                           refuses, the state as it was.
+ *   stb_tindic_heldout_seq  the held-out customers of stb_tindic_set_heldout seated in their order on a private copy of
+ *                           every restaurant's current state, `particles` times: *total = sum_i H_i, Hi_host (or NULL)
+ *                           the I values.  An all-empty object with a trained matrix and h scores unseen documents.
+ *                           Writes nothing of the object, not the state, not the accumulator.  info: the seating's
+ *                           counters over all particles, customers = hoff[I].  Refused as stb_tindic_heldout refuses. */
+#define STB_SEAT_COMMIT 1u
+typedef struct stb_seat_info { uint64_t skipped, impossible, stuck, customers; } stb_seat_info_t;
+int stb_seat_customers(double a, const double *d_bpar, int I, const uint64_t *d_koff, uint32_t *d_n, uint16_t *d_t,
+                       uint32_t *d_T /* NULL unless COMMIT */, const double *d_h /* NULL: 1 */, unsigned M,
+                       const uint64_t *d_coff /* I+1: the customers to seat */, const uint32_t *d_cls, uint32_t *d_cust,
+                       const double *d_lik /* NULL: 1 */, unsigned rows, unsigned stride, unsigned particles,
+                       unsigned flags, uint64_t seed, uint64_t sweep, double *d_lw /* I x particles */,
+                       double *d_p /* C, or NULL */, uint64_t *d_info /* NULL or 3 uint64 added to */, void *stream);
+int stb_seat_loglik(const double *d_lw, int I, unsigned particles, double *d_Hi /* NULL, or I */, double *total_host,
+                    stb_seat_info_t *info /* or NULL */, void *stream);
+int stb_tindic_seat(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep,
+                    double *total /* or NULL */, stb_seat_info_t *info /* or NULL */);
+int stb_tindic_heldout_seq(stb_tindic_t *s, double a, const double *bpar, unsigned particles, uint64_t seed,
+                           uint64_t sweep, double *total, double *Hi_host /* or NULL */, stb_seat_info_t *info /* or NULL */);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

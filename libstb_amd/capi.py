@@ -77,6 +77,14 @@ class PredictInfo(C.Structure):
     _fields_ = [("skipped", C.c_uint64), ("impossible", C.c_uint64), ("customers", C.c_uint64)]
 
 
+SEAT_COMMIT = 1  # stb_seat_customers flag: the one particle's seating is written back (n, t, T, cust, p)
+
+
+class SeatInfo(C.Structure):
+    """stb_seat_info_t (include/stb_hip.h)"""
+    _fields_ = [("skipped", C.c_uint64), ("impossible", C.c_uint64), ("stuck", C.c_uint64), ("customers", C.c_uint64)]
+
+
 GEOM_LOGQ, GEOM_JOINT_TERMS, GEOM_LOGJOINT = 0, 1, 2  # stb_reduce_geometry's `which`
 
 
@@ -360,6 +368,12 @@ def lib() -> C.CDLL:
     sig("stb_tindic_heldout", i, [vp, d, c_double_p, u, c_double_p, c_double_p, pri])
     sig("stb_tindic_heldout_reset", i, [vp])
     sig("stb_tindic_heldout_get", i, [vp, c_double_p, C.POINTER(u)])
+    # ---- seating customers one by one
+    sti = C.POINTER(SeatInfo)
+    sig("stb_seat_customers", i, [d, vp, i, vp, vp, vp, vp, vp, u, vp, vp, vp, vp, u, u, u, u, u64, u64, vp, vp, vp, vp])
+    sig("stb_seat_loglik", i, [vp, i, u, vp, c_double_p, sti, vp])
+    sig("stb_tindic_seat", i, [vp, d, c_double_p, u64, u64, c_double_p, sti])
+    sig("stb_tindic_heldout_seq", i, [vp, d, c_double_p, u, u64, u64, c_double_p, c_double_p, sti])
     # (private entry points: the customers per restaurant as d_N or as d_coff prefix sums, for tests)
     sig("stb_hq_logq", i, [d, d, i, vp, vp, vp, c_double_p, u64, u64, vp])
     sig("stb_hj_joint_terms", i, [c_double_p, i, c_double_p, i, vp, vp, vp, u64, vp, vp])
@@ -903,6 +917,46 @@ def heldout_loglik(p, hoff, samples: int = 1, want_Hi: bool = True, stream=None)
     tot, info = C.c_double(0.0), PredictInfo()
     check(lib().stb_heldout_loglik(p.data_ptr(), hoff.data_ptr(), I, int(samples), None if Hi is None else Hi.data_ptr(),
                                    C.byref(tot), C.byref(info), stream_ptr(stream)))
+    return tot.value, Hi, info
+
+
+def seat_customers(a, bpar, koff, n, t, coff, h=None, M: int = 0, cls=None, lik=None, particles: int = 1,
+                   commit: bool = False, seed: int = 0, sweep: int = 0, T=None, cust=None, want_p: bool = True, info=None,
+                   stream=None, flags=None):
+    """stb_seat_customers on device tensors: koff, coff (int64 [I+1]), n (int32 holding uint32), t (int16 holding uint16),
+    bpar and h (float64; h None: all 1), cls (int32 holding uint32 classes), lik (float64 (rows, stride), or None: all 1).
+    commit: particles must be 1; n and t are written, and T (int32 [I]), cust (int32 [C]) and, with want_p, p (float64 [C])
+    are made where not given.  info: None, or an int64 device tensor of three elements the call adds to (skipped,
+    impossible, stuck).  Queued, no wait.  Returns (lw float64 (I, particles), T, cust, p), the last three None without
+    commit."""
+    torch = _torch()
+    I = int(koff.shape[0]) - 1
+    dev = koff.device
+    lw = torch.empty((max(I, 1), max(int(particles), 1)), dtype=torch.float64, device=dev)[:I]
+    fl = (SEAT_COMMIT if commit else 0) if flags is None else int(flags)
+    p = None
+    if fl & SEAT_COMMIT:
+        Cc = int(coff[-1].item())
+        T = torch.zeros(max(I, 1), dtype=torch.int32, device=dev)[:I] if T is None else T
+        cust = torch.zeros(max(Cc, 1), dtype=torch.int32, device=dev)[:Cc] if cust is None else cust
+        p = torch.zeros(max(Cc, 1), dtype=torch.float64, device=dev)[:Cc] if want_p else None
+    rows, stride = (int(lik.shape[0]), int(lik.shape[1])) if lik is not None else (0, 0)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    check(lib().stb_seat_customers(float(a), ptr(bpar), I, koff.data_ptr(), n.data_ptr(), t.data_ptr(), ptr(T), ptr(h), int(M),
+                                   coff.data_ptr(), ptr(cls), ptr(cust), ptr(lik), rows, stride, int(particles), fl, seed,
+                                   sweep, lw.data_ptr(), ptr(p), ptr(info), stream_ptr(stream)))
+    return lw, T, cust, p
+
+
+def seat_loglik(lw, want_Hi: bool = True, stream=None):
+    """stb_seat_loglik on a device tensor lw (float64 (I, particles)): (sum_i H_i, H_i as a float64 device tensor or None,
+    SeatInfo), H_i = log((1/R) sum_r exp(lw_ir)), after one wait"""
+    torch = _torch()
+    I, R = int(lw.shape[0]), int(lw.shape[1])
+    Hi = torch.empty(max(I, 1), dtype=torch.float64, device=lw.device)[:I] if want_Hi else None
+    tot, info = C.c_double(0.0), SeatInfo()
+    check(lib().stb_seat_loglik(lw.data_ptr(), I, R, None if Hi is None else Hi.data_ptr(), C.byref(tot), C.byref(info),
+                                stream_ptr(stream)))
     return tot.value, Hi, info
 
 
@@ -1525,6 +1579,26 @@ class TableIndicators(_BGroupsMixin):
         fl = (PR_ACCUMULATE if accumulate else 0) if flags is None else int(flags)
         check(self.L.stb_tindic_heldout(self.h, float(a), dp(bpar), fl, C.byref(tot), None if Hi is None else dp(Hi),
                                         C.byref(info)))
+        return tot.value, Hi, info
+
+    # ---- the seating run forwards (stb_tindic_seat / _heldout_seq)
+
+    def seat(self, a, bpar, seed: int, sweep: int):
+        """(total, SeatInfo): the object's seating is forgotten and all its customers are seated in CSR order from empty
+        restaurants, under its classes and matrix (the prior without); total = the sum of the restaurants' log weights"""
+        bpar = _bpar(bpar, self.I)
+        tot, info = C.c_double(0.0), SeatInfo()
+        check(self.L.stb_tindic_seat(self.h, float(a), dp(bpar), seed, sweep, C.byref(tot), C.byref(info)))
+        return tot.value, info
+
+    def heldout_seq(self, a, bpar, particles: int, seed: int, sweep: int, want_Hi: bool = True):
+        """(total, H_i[I] or None, SeatInfo): the held-out customers seated one after another on a private copy of every
+        restaurant's state, `particles` times; H_i = log of the mean particle weight.  Writes nothing of the object"""
+        bpar = _bpar(bpar, self.I)
+        Hi = np.zeros(self.I, dtype=np.float64) if want_Hi else None
+        tot, info = C.c_double(0.0), SeatInfo()
+        check(self.L.stb_tindic_heldout_seq(self.h, float(a), dp(bpar), int(particles), seed, sweep, C.byref(tot),
+                                            None if Hi is None else dp(Hi), C.byref(info)))
         return tot.value, Hi, info
 
     def heldout_reset(self):

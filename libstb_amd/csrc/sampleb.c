@@ -23,6 +23,7 @@
 #include "hyperj.h"
 #include "logjoint.h"
 #include "predict.h"
+#include "seat.h"
 
 #define NPRE 3 /* abscissae ARMS is known to ask for first (lib/arms.c:117-119) */
 
@@ -73,6 +74,7 @@ void stb_sampleb_cache_clear(void) {
   stb_hj_release();
   stb_lj_release();
   stb_pr_release();
+  stb_seat_release();
 }
 
 static int use_slice(void) {

@@ -1,0 +1,32 @@
+/* seat.h -- private: what the object layer (tindic_obj.hip) and the samplers' cache need of seat.hip, beyond
+ * include/stb_hip.h. */
+#ifndef STB_SEAT_H
+#define STB_SEAT_H
+#include <stdint.h>
+#include "../../include/stb_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* frees the calling thread's block sums, counters and result words (stb_sampler_cache_clear) */
+void stb_seat_release(void);
+#ifdef __cplusplus
+}
+#endif
+
+#if defined(__HIPCC__)
+/* the checks stb_seat_customers and the object's calls share (0, or 1 with stb_last_error() set) */
+int stb_seat_check(double a, unsigned M, unsigned particles, unsigned flags, int I, const char *who);
+/* k_seat on st, no wait; arguments checked by the caller.  maxK: the largest K_i where the caller knows it (at most 64:
+ * the launch takes no LDS), else 0.  d_info: three uint64 (skipped, impossible, stuck), added to */
+int stb_seat_launch(double a, const double *d_bpar, int I, const uint64_t *d_koff, uint32_t *d_n, uint16_t *d_t, uint32_t *d_T,
+                    const double *d_h, unsigned M, const uint64_t *d_coff, const uint32_t *d_cls, uint32_t *d_cust,
+                    const double *d_lik, unsigned rows, unsigned stride, unsigned particles, unsigned flags, uint64_t seed,
+                    uint64_t sweep, double *d_lw, double *d_p, uint64_t *d_info, unsigned maxK, hipStream_t st, const char *who);
+/* k_seat_sum on st, the copy of d_Hi to Hi_host (when both are given) and the wait.  d_info (or NULL): k_seat's three
+ * words, copied into info->skipped, ->impossible, ->stuck; without it info->impossible is the number of restaurants
+ * whose H_i is -inf and the other two are 0.  info->customers is left alone. */
+int stb_seat_sum(const double *d_lw, int I, unsigned particles, double *d_Hi, double *Hi_host, double *total_host,
+                 stb_seat_info_t *info, const uint64_t *d_info, hipStream_t st, const char *who);
+#endif
+#endif

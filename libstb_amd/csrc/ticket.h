@@ -2,16 +2,17 @@
  * workgroup takes a ticket when it is through, and the last one to take one adds the block sums; nobody waits.
  *
  *   geometry         stb_ticket_geom, stb_tg_cps, STB_TG_*: k_logq (hyperq.hip), k_joint_terms (hyperj.hip), k_logjoint
- *                    (logjoint.hip) and k_heldout_sum (predict.hip, k_logjoint's geometry).  The launch sites compute grid,
- *                    workgroup size and the room for block sums from stb_ticket_geom, and stb_reduce_geometry
- *                    (include/stb_hip.h) answers from the same function: what the query says is what is launched.
- *   stb_wave_sum     the 64-lane shuffle tree of a double or a 64-bit count: k_logjoint, k_predict and k_heldout_sum, the
- *                    k_dm_* (dirmult.hip), k_dc_totals and k_dc_totals_rows (dirconc.hip), k_hg_count (hgroups.hip).  The
+ *                    (logjoint.hip), k_heldout_sum (predict.hip) and k_seat_sum (seat.hip; both k_logjoint's geometry).
+ *                    The launch sites compute grid, workgroup size and the room for block sums from stb_ticket_geom, and
+ *                    stb_reduce_geometry (include/stb_hip.h) answers from the same function: what the query says is
+ *                    what is launched.
+ *   stb_wave_sum     the 64-lane shuffle tree of a double or a 64-bit count: k_logjoint, k_predict, k_heldout_sum,
+ *                    k_seat and k_seat_sum, the k_dm_* (dirmult.hip), k_dc_totals and k_dc_totals_rows (dirconc.hip), k_hg_count (hgroups.hip).  The
  *                    same tree stays written out in k_logq, k_sum_u32, k_joint_terms, k_hb_group_wg (hyperb.hip) and
  *                    k_eval_tail (groups.hip): there the call compiles to other code than the loop (MEASUREMENTS O3)
- *   stb_ticket_last  the ticket: the four kernels above and k_dm_rows, k_dm_rows_split, k_dm_cols (dirmult.hip)
- *   stb_tset         what a calling thread keeps for a ticket kernel: hq (hyperq.hip), lj (logjoint.hip), pr (predict.hip);
- *                    hj (hyperj.hip) and hb (hyperb.hip) hold one next to what is theirs alone
+ *   stb_ticket_last  the ticket: the five kernels above and k_dm_rows, k_dm_rows_split, k_dm_cols (dirmult.hip)
+ *   stb_tset         what a calling thread keeps for a ticket kernel: hq (hyperq.hip), lj (logjoint.hip), pr (predict.hip),
+ *                    sq (seat.hip); hj (hyperj.hip) and hb (hyperb.hip) hold one next to what is theirs alone
  */
 #ifndef STB_TICKET_H
 #define STB_TICKET_H

@@ -17,6 +17,7 @@
 #include "tindic.h"
 #include "tlik.h"
 #include "predict.h"
+#include "seat.h"
 #include "hgroups.h"
 #include "dirmult.h"
 #include "dirconc.h"
@@ -1179,6 +1180,74 @@ extern "C" int stb_tindic_heldout(stb_tindic_t *s, double a, const double *bpar,
   if (accumulate) s->hsamples++;
   return sc.last(stb_pr_heldout(accumulate ? s->d_pacc : d_p, s->d_hoff, s->I, accumulate ? s->hsamples : 1u, d_Hi, Hi_host, total,
                                 info, d_skip, s->st, who));
+}
+
+// ------------------------------------------------------------------------------------------------
+// the seating run forwards: a start state for the object, and its held-out customers seated one by one (seat.hip)
+
+extern "C" int stb_tindic_seat(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, double *total,
+                               stb_seat_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_seat";
+  if (!s) return stb_fail("%s: null object", who);
+  if (s->flags & STB_TI_REF_ODDS_FLAG)
+    return stb_fail("%s: the object was created with STB_TI_REF_ODDS; the seating has the exact weights only", who);
+  if (stb_seat_check(a, s->Mgiven, 1, STB_SEAT_COMMIT, s->I, who)) return 1;
+  if (!bpar) return stb_fail("%s: bpar is required", who);
+  if (ti_check_bpar(s, a, bpar, who)) return 1;
+  if (s->maxK > STB_TD_MAXK)
+    return stb_fail("%s: a restaurant has K=%u dishes; the seating holds at most STB_TD_MAXK = %d", who, s->maxK, STB_TD_MAXK);
+  if (s->d_lik && (!s->d_cls || s->cls_rows > s->lik_rows))
+    return stb_fail("%s: the likelihood has %u rows; classes %s", who, s->lik_rows,
+                    s->d_cls ? "were set with more" : "are not set (stb_tindic_set_classes)");
+  if ((s->d_lik && s->lik_bad) || s->h_bad)
+    return stb_fail("%s: the last stb_tindic_sample_%s failed and left %s undefined; draw again or set it", who,
+                    s->h_bad ? "h" : "lik", s->h_bad ? "h" : "the likelihood");
+  if (info) memset(info, 0, sizeof(*info));
+  stb_device_scope dev(s->dev);
+  if (ti_dish_prepare(s, who) || stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  stb_pool_scratch sc(s->st);
+  double *d_lw = nullptr;
+  uint64_t *d_cnt = nullptr;
+  if (sc.take(&d_lw, sizeof(double) * (size_t)s->I) != hipSuccess || sc.take(&d_cnt, 3 * sizeof(uint64_t)) != hipSuccess)
+    return stb_fail("%s: out of device memory for %d values", who, s->I);
+  // (no restaurant of an object is skipped -- K_i <= STB_TD_MAXK, the matrix covers the largest K_i, customers come from
+  // pairs -- so every pair is written again: the seating the object had goes here)
+  if (hipMemsetAsync(d_cnt, 0, 3 * sizeof(uint64_t), s->st) != hipSuccess ||
+      (s->G && (hipMemsetAsync(s->d_n, 0, sizeof(uint32_t) * s->G, s->st) != hipSuccess ||
+                hipMemsetAsync(s->d_t, 0, sizeof(uint16_t) * s->G, s->st) != hipSuccess)))
+    return STB_STREAM_FAIL(who);
+  if (stb_seat_launch(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, s->Mgiven, s->d_coff, s->d_cls, s->d_cust,
+                      s->d_lik, s->lik_rows, s->lik_stride, 1, STB_SEAT_COMMIT, seed, sweep, d_lw, nullptr, d_cnt, s->maxK, s->st, who))
+    return 1;
+  if (!total && !info) return sc.give_back(true, who);
+  if (info) info->customers = s->C;
+  return sc.last(stb_seat_sum(d_lw, s->I, 1, nullptr, nullptr, total, info, d_cnt, s->st, who));
+}
+
+extern "C" int stb_tindic_heldout_seq(stb_tindic_t *s, double a, const double *bpar, unsigned particles, uint64_t seed,
+                                      uint64_t sweep, double *total, double *Hi_host, stb_seat_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_heldout_seq";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!total) return stb_fail("%s: total is required", who);
+  if (ti_pr_ready(s, a, bpar, 0, true, who)) return 1;
+  if (stb_seat_check(a, s->Mgiven, particles, 0, s->I, who)) return 1;
+  if (info) memset(info, 0, sizeof(*info));
+  stb_device_scope dev(s->dev);
+  if (stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  stb_pool_scratch sc(s->st);
+  double *d_lw = nullptr, *d_Hi = nullptr;
+  uint64_t *d_cnt = nullptr;
+  if (sc.take(&d_lw, sizeof(double) * (size_t)s->I * particles) != hipSuccess ||
+      (Hi_host && sc.take(&d_Hi, sizeof(double) * (size_t)s->I) != hipSuccess) || sc.take(&d_cnt, 3 * sizeof(uint64_t)) != hipSuccess)
+    return stb_fail("%s: out of device memory for %d x %u log weights", who, s->I, particles);
+  if (hipMemsetAsync(d_cnt, 0, 3 * sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  if (stb_seat_launch(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, nullptr, s->d_h, s->Mgiven, s->d_hoff, s->d_hcls, nullptr,
+                      s->d_lik, s->lik_rows, s->lik_stride, particles, 0, seed, sweep, d_lw, nullptr, d_cnt, s->maxK, s->st, who))
+    return 1;
+  if (info) info->customers = s->Hc;
+  return sc.last(stb_seat_sum(d_lw, s->I, particles, d_Hi, Hi_host, total, info, d_cnt, s->st, who));
 }
 
 extern "C" int stb_tindic_heldout_reset(stb_tindic_t *s) {
