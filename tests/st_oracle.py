@@ -34,6 +34,9 @@ The bars (u = 2^-53), from the operations -- nothing here reads a device result
       rho + 2 u |log(s / R)|, the last sum u |H_i|.
   total: sum_i bar(H_i) + 8 u sum_i |H_i| (the block tree of 256: eight levels) + u (2 |total| + 16), as pr_oracle.
   Everything times 1 + 2^-20 for the second order.
+
+stb_seat_loglik alone (tests/test_gpu_seat_geometry.py): lw_types are exact doubles, so max_r bar(lw_r) = 0 and the H_i bar
+is loglik_rows_bar against loglik_rows_truth (x87 long double); given the H_i, the total is loglik_total bit for bit.
 """
 from __future__ import annotations
 
@@ -251,23 +254,155 @@ def replay(K, n, t, h, a, bpar, coff, cls=None, lik=None, M: int = 0, seed: int 
     return out
 
 
-def loglik_replay(lw):
-    """stb_seat_loglik on lw (I, R): (H_i, total, restaurants whose H_i is -inf)"""
-    lw = np.asarray(lw, dtype=np.float64)
-    I, R = lw.shape
-    m = lw.max(axis=1)
-    ok = m > NEG_INF
-    s = np.zeros(I)
-    with np.errstate(invalid="ignore"):
-        for r in range(R):
-            s = s + np.where(ok, np.exp(np.where(ok, lw[:, r] - m, 0.0)), 0.0)
-        Hi = np.where(ok, m + np.log(np.where(ok, s / np.float64(R), 1.0)), NEG_INF)
+LOGLIK_MUTS = ("meanpad", "max64", "base1", "plain", "linear", "stale", "skipstage")
+STAGE = 1024      # ST_STAGE: block sums the last workgroup stages at a time
+
+
+def loglik_total(Hi, mut=None, grid_x=None):
+    """k_seat_sum's total of the H_i it was given: dead rows (-inf) as 0.0, padded with 0.0 to whole blocks of 256, every
+    block by pro.block_tree, the block sums in order in double-double, hi + lo; -inf when a row is dead.  The kernel's own
+    association leaves no rounding freedom here: the device's total has these bits.  mut, the wrong totals: 'plain' adds
+    the block sums in plain double; 'linear' adds a block left to right; 'stale' leaves in the tail of a short last block
+    what the workgroup's previous block (grid_x blocks earlier; without grid_x the one before) held; 'skipstage' leaves out
+    the second STAGE block sums."""
+    Hi = np.asarray(Hi, dtype=np.float64)
+    I = Hi.shape[0]
+    dead = Hi == NEG_INF
     nblk = max(1, -(-I // 256))
     full = np.zeros(nblk * 256)
-    full[:I] = np.where(ok, Hi, 0.0)
-    total = float(pro.ordered_dd_sum(pro.block_tree(full.reshape(nblk, 256))))
-    nbad = int((~ok).sum())
-    return Hi, (NEG_INF if nbad else total), nbad
+    full[:I] = np.where(dead, 0.0, Hi)
+    full = full.reshape(nblk, 256)
+    if mut == "stale" and nblk > 1 and I % 256:
+        prev = nblk - 1 - grid_x if grid_x and nblk - 1 - grid_x >= 0 else nblk - 2
+        full[-1, I % 256:] = full[prev, I % 256:]
+    part = np.cumsum(full, axis=1)[:, -1] if mut == "linear" else pro.block_tree(full)
+    if mut == "skipstage":
+        part = np.concatenate([part[:STAGE], part[2 * STAGE:]])
+    if mut == "plain":
+        total = 0.0
+        for v in part:
+            total = total + float(v)
+    else:
+        total = float(pro.ordered_dd_sum(part))
+    return NEG_INF if dead.any() else total
+
+
+def loglik_replay(lw, mut=None, grid_x=None):
+    """stb_seat_loglik on lw (I, R): (H_i, total, restaurants whose H_i is -inf).  mut, the wrong rows: 'meanpad' takes the
+    mean over 64 ceil(R / 64) particles, 'max64' the maximum over the first 64 particles only, 'base1' the sum over the
+    first 64 only; the wrong totals are loglik_total's"""
+    lw = np.asarray(lw, dtype=np.float64)
+    I, R = lw.shape
+    m = (lw[:, :64] if mut == "max64" else lw).max(axis=1)
+    ok = m > NEG_INF
+    s = np.zeros(I)
+    Rs = min(R, 64) if mut == "base1" else R
+    Rm = 64 * -(-R // 64) if mut == "meanpad" else R
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for r in range(Rs):
+            s = s + np.where(ok, np.exp(np.where(ok, lw[:, r] - m, 0.0)), 0.0)
+        Hi = np.where(ok, m + np.log(np.where(ok, s / np.float64(Rm), 1.0)), NEG_INF)
+    return Hi, loglik_total(Hi, mut, grid_x), int((~ok).sum())
+
+
+def loglik_rows_truth(lw):
+    """H_i = log((1/R) sum_r exp(lw_ir)) of every row in x87 long double (hp_oracle.check_longdouble refuses a platform
+    without it): np.longdouble [I], -inf for a row of -inf only.  The inputs are exact doubles; lw_r - m rounds to 2^-64
+    relatively, exp and log are long double's, and the R - 1 additions of positive terms lose at most R 2^-64 of s: at
+    R = 4096 that is two u against a bar of 4098 u, and less for fewer particles."""
+    hp.check_longdouble()
+    lw = np.asarray(lw, dtype=np.float64).astype(hp.LD)
+    R = lw.shape[1]
+    m = lw.max(axis=1)
+    ok = m > NEG_INF
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = np.where(ok[:, None], lw - np.where(ok, m, hp.LD(0))[:, None], hp.LD(0))
+        s = np.where(ok, np.exp(d).sum(axis=1), hp.LD(1))
+        return np.where(ok, m + np.log(s / hp.LD(R)), hp.LD(NEG_INF))
+
+
+def loglik_rows_bar(lw, Hi):
+    """the docstring's H_i bar of rows whose lw are exact (max_r bar(lw_r) = 0): rho = max_r u |d_r| + (R + 2) u over the
+    live particles, plus 2 u |log(s / R)| = 2 u |H_i - m|, plus u |H_i|, times SLACK; 0 for a row of -inf only.  Hi: the
+    truth's (any H_i within the bar gives the same bar to second order)"""
+    lw = np.asarray(lw, dtype=np.float64)
+    R = lw.shape[1]
+    Hi = np.asarray(Hi).astype(np.float64)
+    m = lw.max(axis=1)
+    ok = m > NEG_INF
+    with np.errstate(invalid="ignore"):
+        d = np.where(np.isfinite(lw) & ok[:, None], np.abs(lw - np.where(ok, m, 0.0)[:, None]), 0.0).max(axis=1)
+        rho = U * d + (R + 2) * U
+        bar = (rho + 2.0 * U * np.abs(Hi - m) + U * np.abs(Hi)) * SLACK
+    return np.where(ok, bar, 0.0)
+
+
+def loglik_total_truth(Hi, Hb):
+    """(the sum of the truth's H_i, its bar): the docstring's total bar, sum_i bar(H_i) + 8 u sum_i |H_i| + u (2 |total| + 16),
+    times SLACK; (-inf, 0) when a row is dead.  The long-double sum of I terms loses at most I 2^-64 sum |H_i|: under the
+    8 u sum |H_i| by a factor of 2^14 / I (I <= 2^21 here: a hundredth)"""
+    Hi = np.asarray(Hi)
+    if (Hi == NEG_INF).any():
+        return NEG_INF, 0.0
+    tot = Hi.astype(hp.LD).sum()
+    bar = (float(np.sum(Hb)) + 8.0 * U * float(np.abs(Hi).sum()) + U * (2.0 * abs(float(tot)) + 16.0)) * SLACK
+    return tot, bar
+
+
+def over_bar(got, want, bar) -> float:
+    """the largest |got - want| / bar; infinities must agree exactly (else inf), a NaN is inf"""
+    got = np.asarray(got, dtype=np.float64)
+    want = np.asarray(want)
+    bar = np.asarray(bar, dtype=np.float64)
+    inf = ~np.isfinite(want.astype(np.float64))
+    if np.isnan(got).any() or not np.array_equal(got[inf], want[inf].astype(np.float64)) or np.isinf(got[~inf]).any():
+        return math.inf
+    if inf.all():
+        return 0.0
+    err = np.abs(got[~inf].astype(hp.LD) - want[~inf].astype(hp.LD)).astype(np.float64)
+    return float((err / bar[~inf]).max())
+
+
+LW_TYPES, LW_SEED = 257, 0x10C1
+LW_ALLEQ, LW_MAXLAST, LW_SPREAD, LW_MAX64 = 0, 1, 2, 4      # row types of a fixed make; the last type may be dead
+
+
+@lru_cache(maxsize=None)
+def lw_types(R: int, seed: int = LW_SEED, dead_row: bool = False):
+    """257 rows of R synthetic log weights (read-only): particle r of row i lies up to dep_i below the row's offset off_i,
+    off_i in [-500, 0] (one at -500), dep_i from 1e-3 to 600, log-uniform.  Rows 8, 13, 18, .. (i mod 5 = 3, R >= 2) have
+    dead particles (-inf) among live ones; row LW_ALLEQ has all particles equal; row LW_MAXLAST its maximum, by 1, at the
+    last particle; row LW_SPREAD (R >= 2) its live particles 720 to 820 apart -- the low ones first, the high ones from
+    particle 64 on (R <= 64: the last alone), so a maximum over the first 64 overflows and a sum over them flushes to 0;
+    row LW_MAX64 (R > 64) its maximum at particle 64.  dead_row: the last type is -inf throughout.  257 is coprime to 256:
+    tiled over I restaurants (row type i mod 257), every block of 256 sees another phase."""
+    rng = np.random.default_rng([seed, R])
+    T = LW_TYPES
+    off = -500.0 * rng.random(T)
+    off[6] = -500.0
+    dep = 10.0 ** rng.uniform(-3.0, math.log10(600.0), size=T)
+    lw = off[:, None] - dep[:, None] * rng.random((T, R))
+    if R >= 2:
+        for i in range(8, T, 5):
+            dead = rng.random(R) < 0.3
+            dead[int(rng.integers(R))] = False
+            lw[i, dead] = NEG_INF
+        low = off[LW_SPREAD] - 720.0 - 100.0 * rng.random(R)
+        high = np.arange(R) >= 64 if R > 64 else np.arange(R) == R - 1
+        lw[LW_SPREAD] = np.where(high, off[LW_SPREAD] - rng.random(R), low)
+    lw[LW_ALLEQ] = off[LW_ALLEQ]
+    lw[LW_MAXLAST, R - 1] = lw[LW_MAXLAST].max() + 1.0
+    if R > 64:
+        lw[LW_MAX64, 64] = lw[LW_MAX64].max() + 0.5
+    if dead_row:
+        lw[T - 1] = NEG_INF
+    lw.setflags(write=False)
+    return lw
+
+
+def past_one_block(grid_x: int) -> int:
+    """restaurants that give a grid of grid_x workgroups one block sum more than a step each (70000 at least)"""
+    return max(70000, grid_x * 256 + 1)
 
 
 # ---------------------------------------------------------------------------------------------------- truth and bars
@@ -525,6 +660,107 @@ def law_case():
 def law_replay(seed: int = LAW_SEED):
     K, n, t, h, bpar, coff, cls, lik = law_case()
     return replay(K, n, t, h, LAW_A, bpar, coff, cls, lik, seed=seed, sweep=LAW_SWEEP)
+
+
+GRID_I, GRID_R, GRID_A, GRID_SEED, GRID_SWEEP = 16385, 64, 0.4, 0x6E1D, 5
+GRID_CAP = 1 << 20    # k_seat's grid is capped at this many workgroups
+
+
+@lru_cache(maxsize=None)
+def grid_case(I: int = GRID_I):
+    """I restaurants of 2 dishes and 3 customers to seat, random small start pairs, h, a b per restaurant, 2 classes and a
+    2 x 2 matrix: (K, n, t, h, bpar, coff, cls, lik).  At GRID_I and GRID_R particles a launch of one wave a workgroup has
+    GRID_CAP + 64 items: the particles of the last restaurant are the grid-stride loop's second step."""
+    rng = np.random.default_rng([GRID_SEED, I])
+    n = rng.integers(0, 5, size=2 * I).astype(np.uint32)
+    t = np.where(n > 0, 1 + np.floor(rng.random(2 * I) * n), 0).astype(np.uint16)
+    out = (np.full(I, 2, dtype=np.int32), n, t, 0.05 + rng.random(2 * I), 0.3 + 4.0 * rng.random(I),
+           (3 * np.arange(I + 1)).astype(np.uint64), rng.integers(0, 2, size=3 * I).astype(np.uint32), np.array(LAW_LIK))
+    for x in out:
+        x.setflags(write=False)
+    return out
+
+
+def grid_band(I: int = GRID_I):
+    """the restaurants held to the replay: the last nine (at GRID_I, the second step and the eight before it) and the
+    first eight, in index order"""
+    return list(range(8)) + list(range(I - 9, I))
+
+
+def band_case(case, band):
+    """the case with every restaurant outside the band turned into one without dishes (skipped): the flat customer indices
+    and C stay, so the band's streams do"""
+    K, n, t, h, bpar, coff, cls, lik = case
+    koff = np.concatenate([[0], np.cumsum(K)]).astype(np.int64)
+    band = sorted(band)
+    keep = np.concatenate([np.arange(koff[i], koff[i + 1]) for i in band]).astype(np.int64)
+    K2 = np.zeros_like(K)
+    K2[band] = K[band]
+    return K2, n[keep], t[keep], h[keep], bpar, coff, cls, lik
+
+
+@lru_cache(maxsize=None)
+def grid_band_truth(I: int = GRID_I, R: int = GRID_R):
+    """(the band, its replay with bars on band_case, the truth along it)"""
+    band = grid_band(I)
+    K, n, t, h, bpar, coff, cls, lik = band_case(grid_case(I), band)
+    rep = replay(K, n, t, h, GRID_A, bpar, coff, cls, lik, seed=GRID_SEED, sweep=GRID_SWEEP, particles=R, bars=True)
+    return band, rep, truth(K, n, t, h, GRID_A, bpar, coff, cls, lik, 0, rep, restaurants=band)
+
+
+BOUND_A, BOUND_B, BOUND_N, BOUND_C, BOUND_SWEEP = 0.5, 1.0e5, 70000, 8, 0
+BOUND_T = (65534, 65535, 65534, 65535)     # the pinned dish's tables: restaurants 0, 1 (K = 1) and 2, 3 (K = 65, dish 64)
+# The smallest seed from 0 for which, in the replay, the pinned dish of restaurants 0 and 2 (t = 65534) opens its table
+# with at least two of the eight customers still to come to it: they meet the dish at t = 65535, where a table more would
+# wrap the uint16, and both restaurants of 65 dishes seat somebody at another dish as well (tests/test_seat_host.py:
+# test_the_bound_seed_is_the_first_that_opens_the_table_early).
+BOUND_SEED = 1
+
+
+def bound_seed_ok(seed: int) -> bool:
+    o = bound_opened(bound_replay(seed))
+    return all(o[i][0] == 1 and o[i][1] >= 2 for i in (0, 2)) and all(o[i][4] >= 1 for i in (2, 3))
+
+
+@lru_cache(maxsize=None)
+def bound_case():
+    """M = 0 (the kernel's 65535) and b = 1e5, so that a customer of the pinned dish opens a table with probability 0.78
+    while it may: four restaurants of eight customers, the pinned dish (n = 70000, h = 1) at t = 65534 and at 65535, alone
+    (K = 1, the register form) and as dish 64 of 65 (the LDS form; the others n = t = 1, h = 1e-3: one visit in twenty).
+    (K, n, t, h, bpar, coff, None, None)"""
+    K = np.array([1, 1, 65, 65], dtype=np.int32)
+    n, t, h = [], [], []
+    for Ki, tb in zip(K, BOUND_T):
+        n += [1] * (Ki - 1) + [BOUND_N]
+        t += [1] * (Ki - 1) + [tb]
+        h += [1.0e-3] * (Ki - 1) + [1.0]
+    out = (K, np.array(n, dtype=np.uint32), np.array(t, dtype=np.uint16), np.array(h), np.full(4, BOUND_B),
+           (BOUND_C * np.arange(5)).astype(np.uint64))
+    for x in out:
+        x.setflags(write=False)
+    return out + (None, None)
+
+
+@lru_cache(maxsize=None)
+def bound_replay(seed: int = BOUND_SEED):
+    K, n, t, h, bpar, coff, _, _ = bound_case()
+    return replay(K, n, t, h, BOUND_A, bpar, coff, M=0, seed=seed, sweep=BOUND_SWEEP, bars=True)
+
+
+def bound_opened(rep):
+    """per restaurant (tables the pinned dish opened, its visits after the first of them, its final t, the final T, the
+    visits of other dishes)"""
+    K, n, t, h, bpar, coff, _, _ = bound_case()
+    out = []
+    for i, Ki in enumerate(K):
+        sl = slice(int(coff[i]), int(coff[i + 1]))
+        at = rep["ks"][sl, 0] == Ki - 1
+        new = rep["new"][sl, 0] & at
+        first = int(np.argmax(new)) if new.any() else BOUND_C
+        koff = int(np.sum(K[:i]))
+        out.append((int(new.sum()), int(at[first + 1:].sum()), int(rep["t"][koff + Ki - 1]), int(rep["T"][i]),
+                    int((~at).sum())))
+    return out
 
 
 def law_cells(rep):

@@ -6,7 +6,10 @@ tests/test_gpu_seat.py).
   * with L = 1 and h summing to 1 the final state is a draw from the prior;
   * the replay lies within its derived bars of the 40-digit truth on the raw case;
   * four wrong replays are told apart, two by the bar and two by bits;
-  * the law through the replay: 20000 restaurants against the enumerated proposal law.
+  * the law through the replay: 20000 restaurants against the enumerated proposal law;
+  * what tests/test_gpu_seat_geometry.py relies on: the synthetic log weights, the long-double truth of their
+    log-mean-exp against mpmath, the numpy replay within the rows' bar of it, seven wrong k_seat_sum told apart by the very
+    assertions the device meets, the band of the grid case replayed alone, the dish at the uint16 bound.
 """
 import itertools
 import math
@@ -161,3 +164,142 @@ def test_law_through_the_replay():
     # p(w) is the joint's normaliser: sum over states of the unnormalised joint
     want = float(sto.ujoint_states(3, 2, sto.LAW_H, sto.LAW_A, sto.LAW_B, sto.LAW_CLS, sto.LAW_LIK).sum())
     assert abs(pw_true - want) <= 1e-13 * want
+
+
+# ---------------------------------------------------------------------------------------------------- the geometry tests' oracle
+
+LW_R = (1, 2, 3, 63, 64, 65, 127, 128, 129, 4096)      # every particle count tests/test_gpu_seat_geometry.py runs
+GX = 1024                                              # a device of 256 compute units: four workgroups each
+BIG = ((sto.past_one_block(GX), 3, GX), (sto.past_one_block(GX), 65, GX), (sto.past_one_block(200), 3, 200),
+       (4096 * 256 + 1, 1, GX))                        # (I, R, grid_x): past one block (twice, and at the floor), the regrow
+
+
+def _bits(x):
+    return np.float64(x).tobytes()
+
+
+def test_the_log_weight_types_hold_what_they_promise():
+    for R in LW_R:
+        lw = sto.lw_types(R)
+        assert lw.shape == (257, R) and not lw.flags.writeable and not np.isnan(lw).any()
+        assert np.all(lw.max(axis=1) > -math.inf) and lw.max() <= 1.0 and lw[np.isfinite(lw)].min() >= -1400.0
+        assert np.all(lw[sto.LW_ALLEQ] == lw[sto.LW_ALLEQ, 0]) and np.argmax(lw[sto.LW_MAXLAST]) == R - 1
+        assert lw.max(axis=1).min() <= -499.0
+        spread = lw.max(axis=1) - np.where(np.isfinite(lw), lw, math.inf).min(axis=1)
+        assert R == 1 or (spread.min() <= 2e-3 and spread.max() > 300.0)
+        if R >= 2:
+            assert spread[sto.LW_SPREAD] > 745.0 and np.isinf(lw).any(axis=1).sum() >= 10
+            assert np.argmax(lw[sto.LW_SPREAD]) >= min(64, R - 1)
+            assert np.all(lw[sto.LW_SPREAD, :min(64, R - 1)] < lw[sto.LW_SPREAD].max() - 719.0)
+        if R > 64:
+            assert np.argmax(lw[sto.LW_MAX64]) == 64
+        dead = sto.lw_types(R, dead_row=True)
+        assert np.all(dead[256] == -math.inf) and np.array_equal(dead[:256], lw[:256])
+
+
+def test_the_long_double_truth_agrees_with_mpmath():
+    mp = sto.hp._mp()
+    for R in (2, 65):
+        lw = sto.lw_types(R, dead_row=True)
+        tr = sto.loglik_rows_truth(lw)
+        assert tr[256] == -math.inf
+        for i in (sto.LW_ALLEQ, sto.LW_MAXLAST, sto.LW_SPREAD, sto.LW_MAX64, 8, 100):
+            W = [mp.exp(mp.mpf(float(v))) for v in lw[i] if v > -math.inf]
+            want = mp.log(mp.fsum(W) / R)
+            hi = float(tr[i])
+            got = mp.mpf(hi) + mp.mpf(float(tr[i] - sto.hp.LD(hi)))      # (the long double, exactly)
+            assert abs(got - want) <= 1e-2 * sto.U * abs(want), (R, i)   # a hundredth of the bar's u |H_i| alone
+
+
+def test_loglik_replay_lies_within_the_rows_bar_of_the_truth():
+    worst = {}
+    for R in LW_R:
+        for dead_row in (False, True):
+            lw = sto.lw_types(R, dead_row=dead_row)
+            tr = sto.loglik_rows_truth(lw)
+            bar = sto.loglik_rows_bar(lw, tr)
+            Hi, total, nbad = sto.loglik_replay(lw)
+            worst[R] = max(worst.get(R, 0.0), sto.over_bar(Hi, tr, bar))
+            assert worst[R] <= 1.0, (R, worst[R])
+            assert nbad == int(dead_row) and (total == -math.inf) == dead_row and (bar[:256] > 0.0).all()
+            if not dead_row:
+                ttot, tbar = sto.loglik_total_truth(tr, bar)
+                assert abs(total - ttot) <= tbar and tbar < 1e-9 * abs(total)
+    print("loglik_replay against the long-double truth, largest error over bar by R:", worst)
+
+
+@pytest.mark.parametrize("mut", ("meanpad", "max64", "base1"))
+def test_wrong_rows_leave_the_bar(mut):
+    """the assertion of tests/test_gpu_seat_geometry.py on every H_i, applied to a wrong k_seat_sum"""
+    for R in LW_R:
+        lw = sto.lw_types(R)
+        tr = sto.loglik_rows_truth(lw)
+        Hi, _, _ = sto.loglik_replay(lw, mut)
+        told = not sto.over_bar(Hi, tr, sto.loglik_rows_bar(lw, tr)) <= 1.0
+        assert told == (R % 64 != 0 if mut == "meanpad" else R > 64), (mut, R)
+
+
+@pytest.mark.parametrize("mut", ("plain", "linear", "stale", "skipstage"))
+def test_wrong_totals_lose_the_bits(mut):
+    """the total's bit-equality, applied to a wrong association on the H_i of the sizes the device tests run"""
+    for I, R, gx in BIG:
+        Hi = np.resize(sto.loglik_replay(sto.lw_types(R))[0], I)
+        right = sto.loglik_total(Hi)
+        assert _bits(right) == _bits(sto.loglik_replay(np.resize(sto.lw_types(R), (I, R)) if I < 100000 else
+                                                       sto.lw_types(R)[np.arange(I) % 257])[1])
+        nblk = -(-I // 256)
+        assert nblk > gx and (I % 256 == 1 or I == 70000)
+        told = _bits(sto.loglik_total(Hi, mut, gx)) != _bits(right)
+        assert told == (nblk > sto.STAGE or mut != "skipstage"), (mut, I, R)
+    if mut == "stale":          # three blocks, the last of one restaurant: every particle count tells
+        for R in LW_R:
+            Hi = np.resize(sto.loglik_replay(sto.lw_types(R))[0], 513)
+            assert _bits(sto.loglik_total(Hi, mut)) != _bits(sto.loglik_total(Hi))
+
+
+def test_a_dead_row_makes_the_total_minus_infinity_and_nothing_else():
+    Hi = np.resize(sto.loglik_replay(sto.lw_types(3))[0], 513).copy()
+    Hi[[7, 300, 512]] = -math.inf
+    assert sto.loglik_total(Hi) == -math.inf
+
+
+def test_the_band_alone_replays_as_the_band_among_all():
+    I, R = 40, 4
+    case = sto.grid_case(I)
+    K, n, t, h, bpar, coff, cls, lik = case
+    band = sto.grid_band(I)
+    assert band == list(range(8)) + list(range(31, 40)) and sto.grid_band() == list(range(8)) + list(range(16376, 16385))
+    full = sto.replay(K, n, t, h, sto.GRID_A, bpar, coff, cls, lik, seed=sto.GRID_SEED, sweep=sto.GRID_SWEEP, particles=R)
+    _, part, tr = sto.grid_band_truth(I, R)
+    assert full["skipped"] == 0 and part["skipped"] == I - len(band)
+    assert np.array_equal(full["lw"][band].view(np.uint64), part["lw"][band].view(np.uint64))
+    assert not part["lw"][[i for i in range(I) if i not in band]].any()
+    assert np.isfinite(full["lw"]).all() and len({float(v) for v in full["lw"].reshape(-1)}) > I * R // 2
+    assert all(sto.within(part["lw"][i, r], tr["lw"][i, r], tr["lw_bar"][i, r]) for i in band for r in range(R))
+
+
+def test_the_grid_case_crosses_the_cap_at_one_wave_and_at_no_other():
+    items = sto.GRID_I * sto.GRID_R
+    assert items == sto.GRID_CAP + 64 and all(-(-items // w) < sto.GRID_CAP for w in (2, 4, 8))
+    K, n, t, h, bpar, coff, cls, lik = sto.grid_case()
+    assert len(K) == sto.GRID_I and set(K) == {2} and np.all(np.diff(coff.astype(np.int64)) == 3) and n.max() <= 4
+    assert np.all((t <= n) & ((t > 0) == (n > 0))) and len(set(bpar)) == sto.GRID_I and set(cls) == {0, 1}
+
+
+def test_the_bound_case_closes_the_dish_at_65535():
+    K, n, t, h, bpar, coff, _, _ = sto.bound_case()
+    rep = sto.bound_replay()
+    opened = sto.bound_opened(rep)
+    print("tables opened, visits after, final t, final T, visits elsewhere:", opened)
+    koff = np.concatenate([[0], np.cumsum(K)])
+    for i in range(4):
+        new, after, tfin, T, other = opened[i]
+        assert new == (1 if sto.BOUND_T[i] == 65534 else 0) and tfin == 65535            # one table from 65534, none from 65535
+        assert T == int(rep["t"][koff[i]:koff[i + 1]].astype(np.int64).sum())           # and T follows
+        assert T - int(t[koff[i]:koff[i + 1]].astype(np.int64).sum()) == int(rep["new"][8 * i:8 * i + 8, 0].sum())
+        assert int(rep["n"][koff[i + 1] - 1]) == sto.BOUND_N + 8 - other
+    assert rep["impossible"] == rep["stuck"] == rep["skipped"] == 0
+
+
+def test_the_bound_seed_is_the_first_that_opens_the_table_early():
+    assert sto.bound_seed_ok(sto.BOUND_SEED) and not any(sto.bound_seed_ok(s) for s in range(sto.BOUND_SEED))
