@@ -55,10 +55,12 @@
  *  17. with -Q R (needs -P) each iteration's held-out figures gain the sequential estimate: every restaurant's held-out
  *      customers seated one after another on a private copy of its state, R particles averaged inside the logarithm
  *      (stb_tindic_heldout_seq) -- the likelihood of the held-out customers as a whole, where -P scores each one alone.
+ *  18. with -F tau (needs -Q R, R <= 64) the particle filter's figure stands next to it: the same R particles, resampled
+ *      between customers when their effective number falls below tau R (stb_tindic_heldout_pf), and the resamplings.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5]
  */
 #include <math.h>
 #include <stdio.h>
@@ -79,10 +81,11 @@ static int cmp_double(const void *x, const void *y) {
 }
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, filter = 0, c, j, i, it;
+  double ftau = 0.0;
   double a0 = 0.5, b0 = 10.0, beta = 0.5, gam = 1.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -103,6 +106,7 @@ int main(int argc, char **argv) {
     else if (c == 'K') drawconc = 1;
     else if (c == 'S') seatdev = 1;
     else if (c == 'Q') seqpart = atoi(optarg) >= 1 ? atoi(optarg) : -1;
+    else if (c == 'F') filter = 1, ftau = atof(optarg);
     else return 2;
   }
   if (collapsed && !(explicit_d && dishes && redraw)) {
@@ -131,6 +135,10 @@ int main(int argc, char **argv) {
   }
   if (seqpart < 0 || seqpart > 4096 || (seqpart && !predict)) {
     fprintf(stderr, "pyp_resample: -Q R needs 1 <= R <= 4096 and -P\n");
+    return 2;
+  }
+  if (filter && (!seqpart || seqpart > STB_PF_MAXR || !(ftau >= 0.0 && ftau <= 1.0))) {
+    fprintf(stderr, "pyp_resample: -F tau needs 0 <= tau <= 1 and -Q R with R <= %d\n", STB_PF_MAXR);
     return 2;
   }
   if (pergroup && (!explicit_d || joint)) {
@@ -346,6 +354,12 @@ int main(int argc, char **argv) {
           if (stb_tindic_heldout_seq(ti, a, bp, (unsigned)seqpart, (uint64_t)seed + 8, (uint64_t)it * 4096u, &hs, NULL, NULL))
             yaps_quit("stb_tindic_heldout_seq: %s\n", stb_last_error());
           printf(" seq %.6f", hs);
+          if (filter) { /* the same particles, resampled between customers */
+            stb_pf_info_t fi;
+            if (stb_tindic_heldout_pf(ti, a, bp, (unsigned)seqpart, ftau, (uint64_t)seed + 8, (uint64_t)it * 4096u, &hs, NULL, &fi))
+              yaps_quit("stb_tindic_heldout_pf: %s\n", stb_last_error());
+            printf(" pf %.6f (%llu resamplings)", hs, (unsigned long long)fi.resamplings);
+          }
         }
         printf("\n");
       }

@@ -1213,6 +1213,62 @@ int stb_tindic_seat(stb_tindic_t *s, double a, const double *bpar, uint64_t seed
 int stb_tindic_heldout_seq(stb_tindic_t *s, double a, const double *bpar, unsigned particles, uint64_t seed,
                            uint64_t sweep, double *total, double *Hi_host /* or NULL */, stb_seat_info_t *info /* or NULL */);
 
+/* ---- the seating as a particle filter: resampling between customers (seat_pf.hip) ----
+ * stb_seat_customers' R particles never meet: W_r is a product of N predictives, for a document of a few hundred
+ * customers all but one of the R weights are negligible, and log((1/R) sum W_r) is in effect one particle's.  Here the R
+ * particles ("slots") of a restaurant seat each customer side by side, and after a customer the light ones may be
+ * replaced by copies of the heavy ones.  The estimate Zhat (H_i = log Zhat) stays unbiased for p(w_1 .. w_N | L, h, a, b):
+ * a step without resampling preserves E[Zm (1/R) sum_r w_r p(future | state_r)] as E[p_c p(future | next)] = p(future |
+ * state); systematic resampling gives slot r an expected R w_r / S1 offspring; and the decision is a function of the
+ * present system with both branches preserving the expectation (tests/test_pf_host.py enumerates it).
+ *
+ * stb_seat_filter (k_seat_pf): one workgroup per restaurant.  A visit of slot r to customer c is stb_seat_customers'
+ * visit, word for word (steps 1 to 4 above: theta, q, the cumulative sums, k*, the impossible and stuck rules, new or old
+ * from u2), with u2 and u3 from the stream of sweep `sweep + r`: a run that never resamples seats slot r exactly as
+ * k_seat seats particle r.  Per restaurant: weights w_r (doubles, 1.0 at the start), a running factor Zm (1.0) and an
+ * exponent E (int64, 0).  After all R slots have seated customer c, with p_c(r) the visit's p:
+ *   1. w_r = w_r * p_c(r) (an impossible visit has p = 0: the particle is dead, and still seated by the fallback rule).
+ *   2. e = the largest ilogb(w_r) over the w_r > 0.  None: the restaurant is dead, H_i = -inf, it is counted; the other
+ *      customers are still seated with no more weight work.  Else w_r = +0.0 where ilogb(w_r) < e - 1000, ldexp(w_r, -e)
+ *      elsewhere, and E += e.  (No subnormal arises.)
+ *   3. cum = the cumulative sums of w in the dish sweep's association (one block: slot r in lane r, +0.0 past R: so R <=
+ *      STB_PF_MAXR = 64); S1 = the last; S2 = the last of the same scan over w_r * w_r.
+ *   4. resample iff c is not the restaurant's last customer and S1 * S1 < (tau * (double)R) * S2.  (tau = 0: never.)
+ *   5. Zm = Zm * (S1 / (double)R); ez = ilogb(Zm), Zm = ldexp(Zm, -ez), E += ez.  u4 = element 2c + 1 of slot 0's stream
+ *      (the dish sweep's u1: seating never draws it).  thr_j = (((double)j + u4) / (double)R) * S1; the ancestor A_j = the
+ *      smallest r with w_r > 0 and cum_r > thr_j, else the largest r with w_r > 0.  Slot j becomes a copy of slot A_j's
+ *      (n, t, T, N) -- it keeps its own stream -- and w_j = 1.0.  The restaurant's resampling count goes up by one.
+ *   6. after the last customer v = Zm * (S1 / (double)R), H_i = log(v) + (double)E * ln 2 (v = 0: -inf, never NaN).  No
+ *      customers: H_i = 0.
+ * Only + - x /, comparisons, conversions, ilogb and ldexp by integers decide the path: every slot's final (n, t), every
+ * w_r, E and the resampling count are bit-equal to tests/pf_oracle.py's replay whatever the waves of a workgroup
+ * (STB_SEAT_WAVES = 1, 2, 4 or 8), the register or LDS form, or whoever shares the launch; H_i holds one logarithm.
+ * The start state (d_n, d_t) is read and never written.  Outputs: d_Hi[I]; optional d_w[I x R] and d_E[I] (after the
+ * last customer's step 2), d_res[I], and the final states d_pn, d_pt: slot r of restaurant i at koff[i] R + r K_i + k, the
+ * weighted sample of the document's seating (weights w_r).  d_info: NULL, or five uint64 added to: skipped restaurants,
+ * impossible visits, stuck visits, dead restaurants, resamplings.  sum_i H_i is stb_seat_loglik(d_Hi, I, 1, ...) as it
+ * stands (one particle: H = m exactly).  No wait: the call returns when the launch is queued.
+ * The slots' states live in LDS twice over (a resampling copies from one buffer to the other): stb_seat_filter_budget(K)
+ * is the largest R the kernel takes for a restaurant of K dishes, min(64, 61440 / (12 K')) with K' = K rounded up to
+ * even -- 64 for K <= 80, 39 for K = 130, 5 for K = 1024 (a workgroup takes 64 KB at most).  A restaurant whose (K_i, R) is
+ * over it, or K_i > STB_TD_MAXK, K_i > stride (with a matrix), or K_i = 0 with customers, is left out: H_i = 0, counted in
+ * skipped, nothing else of it written.  Refused before anything is queued, with stb_last_error() set: what
+ * stb_seat_customers refuses of these arguments, particles = 0 or > 64, tau outside [0, 1] or NaN, a null d_Hi.
+ *
+ * stb_tindic_heldout_pf is stb_tindic_heldout_seq's twin: the held-out customers seated on a private copy of every
+ * restaurant's current state by the filter; writes nothing of the object; refused as _heldout_seq is. */
+#define STB_PF_MAXR 64
+typedef struct stb_pf_info { uint64_t skipped, impossible, stuck, dead, resamplings, customers; } stb_pf_info_t;
+int stb_seat_filter(double a, const double *d_bpar, int I, const uint64_t *d_koff, const uint32_t *d_n, const uint16_t *d_t,
+                    const double *d_h /* NULL: 1 */, unsigned M, const uint64_t *d_coff, const uint32_t *d_cls,
+                    const double *d_lik /* NULL: 1 */, unsigned rows, unsigned stride, unsigned particles, double tau,
+                    uint64_t seed, uint64_t sweep, double *d_Hi /* I */, double *d_w /* NULL, or I x particles */,
+                    int64_t *d_E /* NULL, or I */, uint32_t *d_res /* NULL, or I */, uint32_t *d_pn, uint16_t *d_pt /* NULL, or
+                    koff[I] x particles each */, uint64_t *d_info /* NULL or 5 uint64 added to */, void *stream);
+unsigned stb_seat_filter_budget(unsigned K);
+int stb_tindic_heldout_pf(stb_tindic_t *s, double a, const double *bpar, unsigned particles, double tau, uint64_t seed,
+                          uint64_t sweep, double *total, double *Hi_host /* or NULL */, stb_pf_info_t *info /* or NULL */);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

@@ -85,6 +85,15 @@ class SeatInfo(C.Structure):
     _fields_ = [("skipped", C.c_uint64), ("impossible", C.c_uint64), ("stuck", C.c_uint64), ("customers", C.c_uint64)]
 
 
+PF_MAXR = 64  # STB_PF_MAXR: the slots of stb_seat_filter, a slot a lane
+
+
+class PFInfo(C.Structure):
+    """stb_pf_info_t (include/stb_hip.h)"""
+    _fields_ = [("skipped", C.c_uint64), ("impossible", C.c_uint64), ("stuck", C.c_uint64), ("dead", C.c_uint64),
+                ("resamplings", C.c_uint64), ("customers", C.c_uint64)]
+
+
 GEOM_LOGQ, GEOM_JOINT_TERMS, GEOM_LOGJOINT = 0, 1, 2  # stb_reduce_geometry's `which`
 
 
@@ -374,6 +383,10 @@ def lib() -> C.CDLL:
     sig("stb_seat_loglik", i, [vp, i, u, vp, c_double_p, sti, vp])
     sig("stb_tindic_seat", i, [vp, d, c_double_p, u64, u64, c_double_p, sti])
     sig("stb_tindic_heldout_seq", i, [vp, d, c_double_p, u, u64, u64, c_double_p, c_double_p, sti])
+    # ---- the seating as a particle filter
+    sig("stb_seat_filter", i, [d, vp, i, vp, vp, vp, vp, u, vp, vp, vp, u, u, u, d, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig("stb_seat_filter_budget", u, [u])
+    sig("stb_tindic_heldout_pf", i, [vp, d, c_double_p, u, d, u64, u64, c_double_p, c_double_p, C.POINTER(PFInfo)])
     # (private entry points: the customers per restaurant as d_N or as d_coff prefix sums, for tests)
     sig("stb_hq_logq", i, [d, d, i, vp, vp, vp, c_double_p, u64, u64, vp])
     sig("stb_hj_joint_terms", i, [c_double_p, i, c_double_p, i, vp, vp, vp, u64, vp, vp])
@@ -958,6 +971,42 @@ def seat_loglik(lw, want_Hi: bool = True, stream=None):
     check(lib().stb_seat_loglik(lw.data_ptr(), I, R, None if Hi is None else Hi.data_ptr(), C.byref(tot), C.byref(info),
                                 stream_ptr(stream)))
     return tot.value, Hi, info
+
+
+def seat_filter_budget(K: int) -> int:
+    """stb_seat_filter_budget: the largest number of particles stb_seat_filter takes for a restaurant of K dishes"""
+    return int(lib().stb_seat_filter_budget(int(K)))
+
+
+def seat_filter(a, bpar, koff, n, t, coff, h=None, M: int = 0, cls=None, lik=None, particles: int = 1, tau: float = 0.5,
+                seed: int = 0, sweep: int = 0, want_w: bool = True, want_states: bool = True, info=None, stream=None, out=None):
+    """stb_seat_filter on device tensors (as seat_customers takes them; n and t are read only).  Queued, no wait.  Returns a
+    dict of device tensors: Hi float64 [I], and with want_w: w float64 (I, particles), E int64 [I], res int32 (holding
+    uint32) [I]; with want_states: pn int32 (holding uint32) and pt int16 (holding uint16), koff[I] * particles each, slot
+    r of restaurant i at koff[i] particles + r K_i + k.  info: None, or an int64 device tensor of five elements the call
+    adds to (skipped, impossible, stuck, dead, resamplings).  out: a dict of tensors to write into instead of new ones."""
+    torch = _torch()
+    I = int(koff.shape[0]) - 1
+    dev = koff.device
+    R = max(int(particles), 1)
+    o = dict(out) if out else {}
+    if "Hi" not in o:
+        o["Hi"] = torch.zeros(max(I, 1), dtype=torch.float64, device=dev)[:I]
+    if want_w and "w" not in o:
+        o["w"] = torch.zeros((max(I, 1), R), dtype=torch.float64, device=dev)[:I]
+        o["E"] = torch.zeros(max(I, 1), dtype=torch.int64, device=dev)[:I]
+        o["res"] = torch.zeros(max(I, 1), dtype=torch.int32, device=dev)[:I]
+    if want_states and "pn" not in o:
+        G = int(koff[-1].item()) * R
+        o["pn"] = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)[:G]
+        o["pt"] = torch.zeros(max(G, 1), dtype=torch.int16, device=dev)[:G]
+    rows, stride = (int(lik.shape[0]), int(lik.shape[1])) if lik is not None else (0, 0)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    check(lib().stb_seat_filter(float(a), ptr(bpar), I, koff.data_ptr(), n.data_ptr(), t.data_ptr(), ptr(h), int(M),
+                                coff.data_ptr(), ptr(cls), ptr(lik), rows, stride, int(particles), float(tau), seed, sweep,
+                                ptr(o.get("Hi")), ptr(o.get("w")), ptr(o.get("E")), ptr(o.get("res")), ptr(o.get("pn")),
+                                ptr(o.get("pt")), ptr(info), stream_ptr(stream)))
+    return o
 
 
 def reduce_geometry(which: int, I: int, D: int = 1, J: int = 1, waves: int = 0) -> ReduceGeom:
@@ -1599,6 +1648,16 @@ class TableIndicators(_BGroupsMixin):
         tot, info = C.c_double(0.0), SeatInfo()
         check(self.L.stb_tindic_heldout_seq(self.h, float(a), dp(bpar), int(particles), seed, sweep, C.byref(tot),
                                             None if Hi is None else dp(Hi), C.byref(info)))
+        return tot.value, Hi, info
+
+    def heldout_pf(self, a, bpar, particles: int, tau: float, seed: int, sweep: int, want_Hi: bool = True):
+        """(total, H_i[I] or None, PFInfo): heldout_seq's twin with resampling between customers (stb_seat_filter): at most
+        64 particles, resampled when the effective sample size falls below tau * particles.  Writes nothing of the object"""
+        bpar = _bpar(bpar, self.I)
+        Hi = np.zeros(self.I, dtype=np.float64) if want_Hi else None
+        tot, info = C.c_double(0.0), PFInfo()
+        check(self.L.stb_tindic_heldout_pf(self.h, float(a), dp(bpar), int(particles), float(tau), seed, sweep, C.byref(tot),
+                                           None if Hi is None else dp(Hi), C.byref(info)))
         return tot.value, Hi, info
 
     def heldout_reset(self):

@@ -18,6 +18,7 @@
 #include "tlik.h"
 #include "predict.h"
 #include "seat.h"
+#include "seat_pf.h"
 #include "hgroups.h"
 #include "dirmult.h"
 #include "dirconc.h"
@@ -1248,6 +1249,48 @@ extern "C" int stb_tindic_heldout_seq(stb_tindic_t *s, double a, const double *b
     return 1;
   if (info) info->customers = s->Hc;
   return sc.last(stb_seat_sum(d_lw, s->I, particles, d_Hi, Hi_host, total, info, d_cnt, s->st, who));
+}
+
+extern "C" int stb_tindic_heldout_pf(stb_tindic_t *s, double a, const double *bpar, unsigned particles, double tau, uint64_t seed,
+                                     uint64_t sweep, double *total, double *Hi_host, stb_pf_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_heldout_pf";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!total) return stb_fail("%s: total is required", who);
+  if (ti_pr_ready(s, a, bpar, 0, true, who)) return 1;
+  if (stb_seat_pf_check(a, s->Mgiven, particles, tau, s->I, who)) return 1;
+  if (info) memset(info, 0, sizeof(*info));
+  stb_device_scope dev(s->dev);
+  if (stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  stb_pool_scratch sc(s->st);
+  double *d_Hi = nullptr;
+  uint64_t *d_cnt = nullptr;
+  if (sc.take(&d_Hi, sizeof(double) * (size_t)(s->I ? s->I : 1)) != hipSuccess || sc.take(&d_cnt, 5 * sizeof(uint64_t)) != hipSuccess)
+    return stb_fail("%s: out of device memory for %d values", who, s->I);
+  if (hipMemsetAsync(d_cnt, 0, 5 * sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  if (stb_seat_pf_launch(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_h, s->Mgiven, s->d_hoff, s->d_hcls, s->d_lik,
+                         s->lik_rows, s->lik_stride, particles, tau, seed, sweep, d_Hi, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         d_cnt, s->maxK, s->st, who))
+    return 1;
+  // the total: k_seat_sum over one "particle" a restaurant, H = m + log(1 / 1) = m exactly (d_Hi is written with what was
+  // read); its three words are the seating's first three, the filter's own two are fetched behind it
+  stb_seat_info_t si;
+  uint64_t two[2] = {0, 0};
+  if (stb_seat_sum(d_Hi, s->I, 1, d_Hi, Hi_host, total, &si, d_cnt, s->st, who)) return sc.last(1);
+  if (s->I > 0 && info) {
+    if (hipMemcpyAsync(two, d_cnt + 3, sizeof(two), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+        hipStreamSynchronize(s->st) != hipSuccess)
+      return sc.last(STB_STREAM_FAIL(who));
+  }
+  if (info) {
+    info->skipped = si.skipped;
+    info->impossible = si.impossible;
+    info->stuck = si.stuck;
+    info->dead = two[0];
+    info->resamplings = two[1];
+    info->customers = s->Hc;
+  }
+  return sc.last(0);
 }
 
 extern "C" int stb_tindic_heldout_reset(stb_tindic_t *s) {
