@@ -57,10 +57,15 @@
  *      (stb_tindic_heldout_seq) -- the likelihood of the held-out customers as a whole, where -P scores each one alone.
  *  18. with -F tau (needs -Q R, R <= 64) the particle filter's figure stands next to it: the same R particles, resampled
  *      between customers when their effective number falls below tau R (stb_tindic_heldout_pf), and the resamplings.
+ *  19. with -V rows (needs -d -z) the corpus is the model's own: every dish's distribution over `rows` classes is a draw
+ *      from its Dirichlet(0.5) prior (stb_sample_lik on zero counts, into the object's matrix), and the seating and every
+ *      customer's class are drawn on the device given that matrix (stb_tindic_generate).  The chain then starts from a
+ *      fresh stb_tindic_seat under the generated classes, as with -S, and every iteration prints the data term
+ *      (stb_tindic_loglik) and the collapsed log joint of the flat model.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5] [-V 1000]
  */
 #include <math.h>
 #include <stdio.h>
@@ -81,11 +86,11 @@ static int cmp_double(const void *x, const void *y) {
 }
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, filter = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, filter = 0, vrows = 0, c, j, i, it;
   double ftau = 0.0;
   double a0 = 0.5, b0 = 10.0, beta = 0.5, gam = 1.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:V:")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -107,6 +112,7 @@ int main(int argc, char **argv) {
     else if (c == 'S') seatdev = 1;
     else if (c == 'Q') seqpart = atoi(optarg) >= 1 ? atoi(optarg) : -1;
     else if (c == 'F') filter = 1, ftau = atof(optarg);
+    else if (c == 'V') vrows = atoi(optarg) >= 2 ? atoi(optarg) : -1;
     else return 2;
   }
   if (collapsed && !(explicit_d && dishes && redraw)) {
@@ -139,6 +145,10 @@ int main(int argc, char **argv) {
   }
   if (filter && (!seqpart || seqpart > STB_PF_MAXR || !(ftau >= 0.0 && ftau <= 1.0))) {
     fprintf(stderr, "pyp_resample: -F tau needs 0 <= tau <= 1 and -Q R with R <= %d\n", STB_PF_MAXR);
+    return 2;
+  }
+  if (vrows < 0 || (vrows && !(explicit_d && dishes))) {
+    fprintf(stderr, "pyp_resample: -V rows needs rows >= 2 and -d -z\n");
     return 2;
   }
   if (pergroup && (!explicit_d || joint)) {
@@ -220,7 +230,30 @@ int main(int argc, char **argv) {
     double *bsort = malloc(sizeof(double) * J);
     if (pergroup && stb_tindic_set_bpar(ti, bvec)) yaps_quit("stb_tindic_set_bpar: %s\n", stb_last_error());
     unsigned long long stuck = 0;
-    if (dishes) { /* two classes by the customer's parity; a class likes the dishes of its parity twice as much */
+    if (vrows) { /* the model's own corpus: the matrix from its prior, then seating and classes drawn given it */
+      unsigned lr, ls;
+      void *lst;
+      const size_t cells = (size_t)vrows * DISHES;
+      scnt_int *zero = calloc(cells, sizeof(*zero));
+      void *d_zero = stb_device_malloc(sizeof(*zero) * cells);
+      stb_seat_info_t si;
+      stb_classes_info_t ci;
+      if (stb_tindic_set_lik(ti, NULL, (unsigned)vrows, DISHES)) yaps_quit("stb_tindic_set_lik: %s\n", stb_last_error());
+      double *d_lik = stb_tindic_lik_device(ti, &lr, &ls, &lst);
+      if (!d_zero || !d_lik || stb_memcpy_h2d(d_zero, zero, sizeof(*zero) * cells, lst) ||
+          stb_sample_lik(d_zero, lr, ls, NULL, beta, d_lik, (uint64_t)seed + 9, 0, lst))
+        yaps_quit("the matrix from its prior: %s\n", stb_last_error());
+      double *btrue = malloc(sizeof(double) * J); /* the corpus comes from the true a and b, the chain starts elsewhere */
+      for (j = 0; j < J; j++) btrue[j] = b0;
+      if (stb_tindic_generate(ti, a0, btrue, (uint64_t)seed + 10, 0, &si, &ci)) yaps_quit("stb_tindic_generate: %s\n", stb_last_error());
+      if (pergroup && stb_tindic_set_bpar(ti, bvec)) yaps_quit("stb_tindic_set_bpar: %s\n", stb_last_error());
+      free(btrue);
+      printf("corpus generated on the device: %llu customers, %llu classes drawn over %d rows, %llu left alone\n",
+             (unsigned long long)si.customers, (unsigned long long)ci.drawn, vrows, (unsigned long long)(ci.stuck + ci.skipped));
+      stb_device_free(d_zero);
+      free(zero);
+      seatdev = 1;
+    } else if (dishes) { /* two classes by the customer's parity; a class likes the dishes of its parity twice as much */
       scnt_int *cls = malloc(sizeof(*cls) * (size_t)J * ncust);
       double lik[2 * DISHES];
       for (cc = 0; cc < (size_t)J * ncust; cc++) cls[cc] = (scnt_int)(cc & 1);
@@ -372,6 +405,14 @@ int main(int argc, char **argv) {
           yaps_quit("stb_tindic_logjoint_collapsed: %s\n", stb_last_error());
         printf("iteration %d: collapsed log joint %.6f (pairs %.6f, restaurants %.6f, indicators %.6f, tables %.6f, data %.6f, "
                "root %.6f)\n", it, cj, ci.pairs, ci.restaurants, ci.binom, ci.tables, ci.data, ci.root);
+      }
+      if (vrows) { /* the generated corpus: the data term under the matrix, and the flat model's collapsed log joint */
+        stb_cj_opts_t co = {0.0, gam, beta, NULL, NULL};
+        double dt, cj;
+        if (stb_tindic_loglik(ti, &dt, NULL) ||
+            stb_tindic_logjoint_collapsed(ti, a, bp, STB_CJ_INDICATORS | STB_CJ_DATA | STB_CJ_FLAT, &co, &cj, NULL))
+          yaps_quit("stb_tindic_loglik / _logjoint_collapsed: %s\n", stb_last_error());
+        printf("iteration %d: generated corpus data %.6f collapsed %.6f\n", it, dt, cj);
       }
       if (pergroup) { /* the iteration's one read-back: the J concentrations */
         if (stb_tindic_get_bpar(ti, bvec)) yaps_quit("stb_tindic_get_bpar: %s\n", stb_last_error());

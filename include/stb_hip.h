@@ -1269,6 +1269,68 @@ unsigned stb_seat_filter_budget(unsigned K);
 int stb_tindic_heldout_pf(stb_tindic_t *s, double a, const double *bpar, unsigned particles, double tau, uint64_t seed,
                           uint64_t sweep, double *total, double *Hi_host /* or NULL */, stb_pf_info_t *info /* or NULL */);
 
+/* ---- customers' classes drawn on the device: generated and missing data (classgen.hip; additive) ----
+ * The one variable of DESIGN.md section 6's joint that the steps above take from the caller: customer c's class given
+ * its dish, cls_c ~ lik[.][z_c] / Z_{z_c}.  With it the object generates from its own model (stb_tindic_generate), and
+ * missing classes are part of the chain: alternated with the dish sweep, the draw is Gibbs sampling on the joint with
+ * the missing classes included.
+ *
+ * lik is rows x stride doubles, row-major, finite and >= 0; dish k is local pair k (the dish sweep's and
+ * stb_sample_lik's convention), so column k is dish k's class weights; k = cust[c] is customer c's dish.
+ *
+ * Cumulative sums of column k, in stb_sample_lik's chunk association (FP64, no contraction): rows in chunks of 256
+ * (chunk j = rows 256 j .. 256 j + 255); pre_w the running sum inside a chunk in row order, starting from the chunk's
+ * first row; S_j = pre at the chunk's last row; base_0 = 0, base_1 = S_0, base_{j+1} = base_j + S_j; cum_w = pre_w in
+ * chunk 0, else base_j + pre_w; Z_k = the last base, bit for bit the Z_k of stb_sample_lik on the same cells.  cum is
+ * non-decreasing, and cum_w > cum_{w-1} implies lik_wk > 0.
+ *
+ * The draw: u = element 3C + 1 + c of the stream of (seed, sweep), key = mix(seed + (sweep+1) gamma) as the sweeps'; C
+ * the call's number of customers, c the flat customer index.  (Elements 2c+1, 2c+2 and 2C+1+c are u1, u2/u4 and u3 of the
+ * sweeps and the seating: this one is free, so one (seed, sweep) serves a seating and a class draw together.)
+ * thr = u * Z_k; w* = the smallest w with cum_w > thr; if there is none, the smallest w with cum_w >= Z_k (the last row
+ * at which the sum grew).  For u < 1, fl(u Z) < Z holds for every Z > 2^-1022, so the second form is reachable only for
+ * columns whose total is at most 2^-1022 (there u Z can round to Z itself: DESIGN.md section 6); it keeps the rule total
+ * there, as the dish choice's is.  cls[c] = w*: never a class of zero weight.  The rule is a binary search over the chunk
+ * bases, then inside the chunk.
+ *
+ * Left alone, and counted (d_info: NULL, or three uint64 added to -- skipped, stuck, drawn):
+ *   cust[c] >= stride             the class stays; skipped
+ *   Z_k not positive and finite   the class stays; stuck
+ *   mask[c] == 0 (uint8 per customer; NULL: all are drawn)    the class stays; nothing is counted
+ *   otherwise                     drawn
+ * A class depends on (seed, sweep, c, C), the customer's dish and the matrix alone: not on launch geometry, on the waves
+ * of a workgroup (STB_CLS_WAVES = 1, 2, 4 or 8), or on who shares the call.
+ *
+ * stb_sample_classes      the raw call on device arrays.  It takes a rows x stride scratch (pre) from the buffer cache
+ *                         and fails before anything is written if there is none; it waits once, to give the scratch back.
+ *                         Refused before anything is queued: a null d_lik, a null d_cust or d_cls with C > 0, rows or
+ *                         stride 0.
+ * stb_tindic_sample_classes   the object's classes drawn from its matrix (which must not be one a failed
+ *                         stb_tindic_sample_lik left), queued on the object's stream behind its sweeps.  mask_host: C
+ *                         bytes or NULL.  The customer sequence is written out if the object still has pair order.  An
+ *                         object without classes gets them (mask must then be NULL: refused otherwise).  Afterwards the
+ *                         classes' rows are the matrix's, so _class_counts, _sample_lik and _loglik work on the result.
+ *                         Writes only the classes: not n, t, T, cust, h, the matrix or the held-out accumulator.  info
+ *                         NULL and no mask: no wait (a mask travels through the buffer cache, which is given back behind
+ *                         a wait).  The object keeps the scratch until its matrix changes shape or it is freed.
+ * stb_tindic_generate     a draw of (z, t, cls) from the model given (lik, h, a, b): all C customers seated from empty
+ *                         restaurants under the prior (stb_tindic_seat's launch with no matrix, whatever the object
+ *                         holds), then every class drawn.  Bit-equal to: remove the matrix, stb_tindic_seat, put the
+ *                         matrix back, stb_tindic_sample_classes with the same (seed, sweep).  Refuses what
+ *                         stb_tindic_seat refuses, an object with no matrix, and what _sample_classes refuses.
+ *                         seat_info: stb_tindic_seat's counters (customers = C); no total is computed.  Waits.
+ * stb_tindic_get_classes  the classes (C values) and their rows, after the queued work.
+ * Every refusal leaves the state as it was, with stb_last_error() set. */
+typedef struct stb_classes_info { uint64_t skipped, stuck, drawn; } stb_classes_info_t;
+int stb_sample_classes(const double *d_lik, unsigned rows, unsigned stride, const uint32_t *d_cust,
+                       const uint8_t *d_mask /* or NULL */, uint64_t C, uint64_t seed, uint64_t sweep,
+                       uint32_t *d_cls, uint64_t *d_info /* NULL or 3 uint64 added to */, void *stream);
+int stb_tindic_sample_classes(stb_tindic_t *s, const uint8_t *mask_host /* C, or NULL */, uint64_t seed,
+                              uint64_t sweep, stb_classes_info_t *info /* or NULL: no wait */);
+int stb_tindic_generate(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep,
+                        stb_seat_info_t *seat_info /* or NULL */, stb_classes_info_t *cls_info /* or NULL */);
+int stb_tindic_get_classes(stb_tindic_t *s, uint32_t *cls_out /* C */, unsigned *rows_out /* or NULL */);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

@@ -85,6 +85,11 @@ class SeatInfo(C.Structure):
     _fields_ = [("skipped", C.c_uint64), ("impossible", C.c_uint64), ("stuck", C.c_uint64), ("customers", C.c_uint64)]
 
 
+class ClassesInfo(C.Structure):
+    """stb_classes_info_t (include/stb_hip.h)"""
+    _fields_ = [("skipped", C.c_uint64), ("stuck", C.c_uint64), ("drawn", C.c_uint64)]
+
+
 PF_MAXR = 64  # STB_PF_MAXR: the slots of stb_seat_filter, a slot a lane
 
 
@@ -387,6 +392,12 @@ def lib() -> C.CDLL:
     sig("stb_seat_filter", i, [d, vp, i, vp, vp, vp, vp, u, vp, vp, vp, u, u, u, d, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("stb_seat_filter_budget", u, [u])
     sig("stb_tindic_heldout_pf", i, [vp, d, c_double_p, u, d, u64, u64, c_double_p, c_double_p, C.POINTER(PFInfo)])
+    # ---- customers' classes drawn on the device
+    cli = C.POINTER(ClassesInfo)
+    sig("stb_sample_classes", i, [vp, u, u, vp, vp, u64, u64, u64, vp, vp, vp])
+    sig("stb_tindic_sample_classes", i, [vp, vp, u64, u64, cli])
+    sig("stb_tindic_generate", i, [vp, d, c_double_p, u64, u64, sti, cli])
+    sig("stb_tindic_get_classes", i, [vp, c_u32_p, C.POINTER(u)])
     # (private entry points: the customers per restaurant as d_N or as d_coff prefix sums, for tests)
     sig("stb_hq_logq", i, [d, d, i, vp, vp, vp, c_double_p, u64, u64, vp])
     sig("stb_hj_joint_terms", i, [c_double_p, i, c_double_p, i, vp, vp, vp, u64, vp, vp])
@@ -1118,6 +1129,17 @@ def sample_lik(cnt, beta, seed: int, sweep: int, out=None, stream=None):
     return lik
 
 
+def sample_classes(lik, cust, seed: int, sweep: int, cls, mask=None, info=None, stream=None):
+    """stb_sample_classes on device tensors: lik float64 (rows, stride), cust int32 holding uint32 dishes (C), cls int32
+    holding uint32 classes (C; written where a class is drawn), mask uint8 (C) or None, info int64 (3: skipped, stuck,
+    drawn, added to) or None.  Returns cls"""
+    rows, stride = int(lik.shape[0]), int(lik.shape[1])
+    check(lib().stb_sample_classes(lik.data_ptr(), rows, stride, cust.data_ptr(), None if mask is None else mask.data_ptr(),
+                                   int(cust.shape[0]), seed, sweep, cls.data_ptr(), None if info is None else info.data_ptr(),
+                                   stream_ptr(stream)))
+    return cls
+
+
 def lik_loglik(cnt, lik, stream=None):
     """stb_lik_loglik on device tensors cnt (int32 holding uint32) and lik (float64), both (rows, stride):
     (sum cnt log lik, cells with a count and no likelihood)"""
@@ -1639,6 +1661,38 @@ class TableIndicators(_BGroupsMixin):
         tot, info = C.c_double(0.0), SeatInfo()
         check(self.L.stb_tindic_seat(self.h, float(a), dp(bpar), seed, sweep, C.byref(tot), C.byref(info)))
         return tot.value, info
+
+    # ---- customers' classes drawn from the matrix (stb_tindic_sample_classes / _generate / _get_classes)
+
+    def sample_classes(self, seed: int, sweep: int, mask=None, want_info: bool = True):
+        """every customer's class (mask: those with a non-zero byte) drawn from its dish's column of the matrix, behind the
+        queued sweeps; an object without classes gets them.  Returns ClassesInfo after a wait, or None without one"""
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape[0] != self.C:
+                raise StbError(f"TableIndicators.sample_classes: {mask.shape[0]} mask bytes, {self.C} customers")
+            mp = mask.ctypes.data_as(C.c_void_p)
+        info = ClassesInfo() if want_info else None
+        check(self.L.stb_tindic_sample_classes(self.h, mp, seed, sweep, None if info is None else C.byref(info)))
+        self.rows = self.lik_device()[1]
+        return info
+
+    def generate(self, a, bpar, seed: int, sweep: int):
+        """(SeatInfo, ClassesInfo): a draw of (z, t, cls) from the model given the matrix, h, a and b -- the seating of
+        seat() under the prior, whatever matrix the object holds, then every class from its dish's column"""
+        bpar = _bpar(bpar, self.I)
+        si, ci = SeatInfo(), ClassesInfo()
+        check(self.L.stb_tindic_generate(self.h, float(a), dp(bpar), seed, sweep, C.byref(si), C.byref(ci)))
+        self.rows = self.lik_device()[1]
+        return si, ci
+
+    def get_classes(self):
+        """(cls[C] uint32, rows) after the queued work"""
+        cls = np.zeros(self.C, dtype=np.uint32)
+        rows = C.c_uint(0)
+        check(self.L.stb_tindic_get_classes(self.h, cls.ctypes.data_as(c_u32_p) if self.C else None, C.byref(rows)))
+        return cls, rows.value
 
     def heldout_seq(self, a, bpar, particles: int, seed: int, sweep: int, want_Hi: bool = True):
         """(total, H_i[I] or None, SeatInfo): the held-out customers seated one after another on a private copy of every

@@ -22,6 +22,7 @@
 #include "hgroups.h"
 #include "dirmult.h"
 #include "dirconc.h"
+#include "classgen.h"
 
 // ------------------------------------------------------------------------------------------------
 // the object: pairs, totals, weights, customer order, its own V table for the current discount, its own stream
@@ -44,6 +45,9 @@ struct stb_tindic {
   unsigned lik_rows, lik_stride;
   bool lik_bad, h_bad;  // a draw of stb_tindic_sample_lik / _sample_h failed: the matrix / h is undefined, dish sweeps are refused
   unsigned long long *d_info, *h_info;  // {skipped, stuck} on the device, and pinned
+  void *d_cgs;          // the class draw's scratch (classgen.hip), from the buffer cache: kept while the matrix keeps its shape
+  size_t cgs_bytes;
+  uint64_t *d_cginfo;   // {skipped, stuck, drawn} of the class draw, and the seating's three words behind them
   bool need_table;      // some visit can read a V cell (max n >= 2 and M >= 2); otherwise no indicator is ever added
   uint64_t *d_koff, *d_coff;
   uint32_t *d_n, *d_T;
@@ -143,11 +147,19 @@ static int ti_fetch(stb_tindic_t *s, std::initializer_list<ti_copy> copies, cons
 // ------------------------------------------------------------------------------------------------
 // create and free
 
+// the class draw's scratch back to the buffer cache (the caller has waited for whatever uses it)
+static void ti_drop_cgs(stb_tindic_t *s) {
+  if (s->d_cgs) stb_pool_free(s->d_cgs);
+  s->d_cgs = nullptr;
+  s->cgs_bytes = 0;
+}
+
 static void ti_release(stb_tindic_t *s) {
   stb_hb_obj_release(&s->hb);
   ti_drop_sslab(s);
+  ti_drop_cgs(s);
   void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws,
-                 s->d_cls, s->d_lik, s->d_info, s->d_hoff, s->d_hcls, s->d_pacc, s->d_hgoff, s->d_hroot};
+                 s->d_cls, s->d_lik, s->d_info, s->d_hoff, s->d_hcls, s->d_pacc, s->d_hgoff, s->d_hroot, s->d_cginfo};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (s->h_info) (void)hipHostFree(s->h_info);
@@ -559,6 +571,7 @@ extern "C" int stb_tindic_set_lik(stb_tindic_t *s, const double *lik_host, unsig
     }
   }
   if (s->d_lik) (void)hipFree(s->d_lik);
+  if (drop || rows != s->lik_rows || stride != s->lik_stride) ti_drop_cgs(s);
   s->d_lik = d;
   s->lik_rows = drop ? 0 : rows;
   s->lik_stride = drop ? 0 : stride;
@@ -1186,11 +1199,9 @@ extern "C" int stb_tindic_heldout(stb_tindic_t *s, double a, const double *bpar,
 // ------------------------------------------------------------------------------------------------
 // the seating run forwards: a start state for the object, and its held-out customers seated one by one (seat.hip)
 
-extern "C" int stb_tindic_seat(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, double *total,
-                               stb_seat_info_t *info) {
-  STB_ENTRY;
-  const char *who = "stb_tindic_seat";
-  if (!s) return stb_fail("%s: null object", who);
+// what a seating of all the object's customers asks before anything is queued; prior: no matrix whatever the object holds
+static int ti_seat_ready(stb_tindic_t *s, double a, const double *bpar, bool prior, const char *who) {
+  const bool lik = s->d_lik && !prior;
   if (s->flags & STB_TI_REF_ODDS_FLAG)
     return stb_fail("%s: the object was created with STB_TI_REF_ODDS; the seating has the exact weights only", who);
   if (stb_seat_check(a, s->Mgiven, 1, STB_SEAT_COMMIT, s->I, who)) return 1;
@@ -1198,29 +1209,46 @@ extern "C" int stb_tindic_seat(stb_tindic_t *s, double a, const double *bpar, ui
   if (ti_check_bpar(s, a, bpar, who)) return 1;
   if (s->maxK > STB_TD_MAXK)
     return stb_fail("%s: a restaurant has K=%u dishes; the seating holds at most STB_TD_MAXK = %d", who, s->maxK, STB_TD_MAXK);
-  if (s->d_lik && (!s->d_cls || s->cls_rows > s->lik_rows))
+  if (lik && (!s->d_cls || s->cls_rows > s->lik_rows))
     return stb_fail("%s: the likelihood has %u rows; classes %s", who, s->lik_rows,
                     s->d_cls ? "were set with more" : "are not set (stb_tindic_set_classes)");
-  if ((s->d_lik && s->lik_bad) || s->h_bad)
+  if ((lik && s->lik_bad) || s->h_bad)
     return stb_fail("%s: the last stb_tindic_sample_%s failed and left %s undefined; draw again or set it", who,
                     s->h_bad ? "h" : "lik", s->h_bad ? "h" : "the likelihood");
-  if (info) memset(info, 0, sizeof(*info));
-  stb_device_scope dev(s->dev);
+  return 0;
+}
+
+// the seating from empty restaurants on the object's stream, no wait (stb_tindic_seat and stb_tindic_generate: one launch
+// site, so the two stay bit-equal).  d_lw: I doubles; d_cnt: k_seat's three words, zeroed here
+static int ti_seat_queue(stb_tindic_t *s, double a, const double *bpar, bool prior, uint64_t seed, uint64_t sweep, double *d_lw,
+                         uint64_t *d_cnt, const char *who) {
   if (ti_dish_prepare(s, who) || stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
-  stb_pool_scratch sc(s->st);
-  double *d_lw = nullptr;
-  uint64_t *d_cnt = nullptr;
-  if (sc.take(&d_lw, sizeof(double) * (size_t)s->I) != hipSuccess || sc.take(&d_cnt, 3 * sizeof(uint64_t)) != hipSuccess)
-    return stb_fail("%s: out of device memory for %d values", who, s->I);
   // (no restaurant of an object is skipped -- K_i <= STB_TD_MAXK, the matrix covers the largest K_i, customers come from
   // pairs -- so every pair is written again: the seating the object had goes here)
   if (hipMemsetAsync(d_cnt, 0, 3 * sizeof(uint64_t), s->st) != hipSuccess ||
       (s->G && (hipMemsetAsync(s->d_n, 0, sizeof(uint32_t) * s->G, s->st) != hipSuccess ||
                 hipMemsetAsync(s->d_t, 0, sizeof(uint16_t) * s->G, s->st) != hipSuccess)))
     return STB_STREAM_FAIL(who);
-  if (stb_seat_launch(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, s->Mgiven, s->d_coff, s->d_cls, s->d_cust,
-                      s->d_lik, s->lik_rows, s->lik_stride, 1, STB_SEAT_COMMIT, seed, sweep, d_lw, nullptr, d_cnt, s->maxK, s->st, who))
-    return 1;
+  const bool lik = s->d_lik && !prior;
+  return stb_seat_launch(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, s->Mgiven, s->d_coff, lik ? s->d_cls : nullptr,
+                         s->d_cust, lik ? s->d_lik : nullptr, lik ? s->lik_rows : 0, lik ? s->lik_stride : 0, 1, STB_SEAT_COMMIT, seed,
+                         sweep, d_lw, nullptr, d_cnt, s->maxK, s->st, who);
+}
+
+extern "C" int stb_tindic_seat(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, double *total,
+                               stb_seat_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_seat";
+  if (!s) return stb_fail("%s: null object", who);
+  if (ti_seat_ready(s, a, bpar, false, who)) return 1;
+  if (info) memset(info, 0, sizeof(*info));
+  stb_device_scope dev(s->dev);
+  stb_pool_scratch sc(s->st);
+  double *d_lw = nullptr;
+  uint64_t *d_cnt = nullptr;
+  if (sc.take(&d_lw, sizeof(double) * (size_t)s->I) != hipSuccess || sc.take(&d_cnt, 3 * sizeof(uint64_t)) != hipSuccess)
+    return stb_fail("%s: out of device memory for %d values", who, s->I);
+  if (ti_seat_queue(s, a, bpar, false, seed, sweep, d_lw, d_cnt, who)) return 1;
   if (!total && !info) return sc.give_back(true, who);
   if (info) info->customers = s->C;
   return sc.last(stb_seat_sum(d_lw, s->I, 1, nullptr, nullptr, total, info, d_cnt, s->st, who));
@@ -1313,4 +1341,140 @@ extern "C" int stb_tindic_heldout_get(stb_tindic_t *s, double *p_out, unsigned *
   if (ti_fetch(s, {{p_out, s->d_pacc, sizeof(double) * s->Hc}}, who)) return 1;
   if (samples) *samples = s->hsamples;
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// customers' classes drawn from the matrix given their dishes, and the model's own data (the kernels are classgen.hip's)
+
+// what a class draw asks of the object before anything is queued
+static int ti_cls_ready(stb_tindic_t *s, bool masked, const char *who) {
+  if (!s->d_lik) return stb_fail("%s: no likelihood matrix is set (stb_tindic_set_lik)", who);
+  if (s->lik_bad) return stb_fail("%s: the last stb_tindic_sample_lik failed and left the likelihood undefined; draw again or set it", who);
+  if (masked && !s->d_cls) return stb_fail("%s: a mask keeps classes, and none are set (stb_tindic_set_classes)", who);
+  // (also where every customer is visited: one that is masked out, stuck or skipped keeps its class, and afterwards the
+  // classes' rows are the matrix's)
+  if (s->d_cls && s->cls_rows > s->lik_rows)
+    return stb_fail("%s: the likelihood has %u rows; classes were set with %u", who, s->lik_rows, s->cls_rows);
+  return 0;
+}
+
+namespace {
+// what a class draw needs beyond the object's arrays, taken before anything is queued: the customer sequence, the scratch,
+// the counters, and a class array where the object has none (zeroed: a customer whose column is stuck keeps class 0).  A
+// fresh array that the object did not adopt goes when the call ends, behind a wait for what was queued on it
+struct ti_cls_room {
+  hipStream_t st;
+  uint32_t *d_cls = nullptr;
+  bool fresh = false;
+  explicit ti_cls_room(hipStream_t st_) : st(st_) {}
+  ti_cls_room(const ti_cls_room &) = delete;
+  ti_cls_room &operator=(const ti_cls_room &) = delete;
+  ~ti_cls_room() {
+    if (!fresh) return;
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(d_cls);
+  }
+};
+}  // namespace
+
+static int ti_cls_take(stb_tindic_t *s, ti_cls_room &room, const char *who) {
+  if (ti_materialise_cust(s, who)) return 1;
+  const size_t need = stb_cg_scratch_bytes(s->lik_rows, s->lik_stride);
+  if (!s->d_cgs || s->cgs_bytes != need) {
+    void *d = nullptr;
+    if (stb_pool_malloc(&d, need) != hipSuccess)
+      return stb_fail("%s: out of device memory for a %u x %u scratch", who, s->lik_rows, s->lik_stride);
+    if (s->d_cgs && hipStreamSynchronize(s->st) != hipSuccess) {
+      stb_pool_free(d);
+      return STB_STREAM_FAIL(who);
+    }
+    ti_drop_cgs(s);
+    s->d_cgs = d;
+    s->cgs_bytes = need;
+  }
+  if (!s->d_cginfo && hipMalloc((void **)&s->d_cginfo, 6 * sizeof(uint64_t)) != hipSuccess) return STB_STREAM_FAIL(who);
+  room.d_cls = s->d_cls;
+  if (!room.d_cls) {
+    const size_t bytes = sizeof(uint32_t) * (s->C ? s->C : 1);
+    if (hipMalloc((void **)&room.d_cls, bytes) != hipSuccess) return stb_fail("%s: out of device memory for %llu classes", who, (unsigned long long)s->C);
+    room.fresh = true;
+    if (hipMemsetAsync(room.d_cls, 0, bytes, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  }
+  return 0;
+}
+
+// the draw on the object's stream, no wait; the object adopts a fresh class array once the draw is queued
+static int ti_cls_draw(stb_tindic_t *s, ti_cls_room &room, const uint8_t *d_mask, uint64_t seed, uint64_t sweep, const char *who) {
+  if (hipMemsetAsync(s->d_cginfo, 0, 3 * sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  if (stb_cg_launch(s->d_lik, s->lik_rows, s->lik_stride, s->d_cust, d_mask, s->C, seed, sweep, room.d_cls, s->d_cginfo, s->d_cgs, s->st,
+                    who))
+    return 1;
+  room.fresh = false;
+  s->d_cls = room.d_cls;
+  s->cls_rows = s->lik_rows;
+  return 0;
+}
+
+static int ti_cls_info(stb_tindic_t *s, stb_classes_info_t *info, const char *who) {
+  uint64_t w[3] = {0, 0, 0};
+  if (ti_fetch(s, {{w, s->d_cginfo, sizeof(w)}}, who)) return 1;
+  info->skipped = w[0];
+  info->stuck = w[1];
+  info->drawn = w[2];
+  return 0;
+}
+
+extern "C" int stb_tindic_sample_classes(stb_tindic_t *s, const uint8_t *mask_host, uint64_t seed, uint64_t sweep,
+                                         stb_classes_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sample_classes";
+  if (!s) return stb_fail("%s: null object", who);
+  if (ti_cls_ready(s, mask_host != nullptr, who)) return 1;
+  if (info) info->skipped = info->stuck = info->drawn = 0;
+  stb_device_scope dev(s->dev);
+  stb_pool_scratch sc(s->st);
+  uint8_t *d_mask = nullptr;
+  if (mask_host && s->C) {
+    if (sc.take(&d_mask, s->C) != hipSuccess) return stb_fail("%s: out of device memory for the mask", who);
+    if (hipMemcpyAsync(d_mask, mask_host, s->C, hipMemcpyHostToDevice, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  }
+  ti_cls_room room(s->st);
+  if (ti_cls_take(s, room, who) || ti_cls_draw(s, room, d_mask, seed, sweep, who)) return 1;
+  if (info) return sc.last(ti_cls_info(s, info, who));
+  return sc.give_back(true, who);  // (nothing taken, no mask: no wait)
+}
+
+extern "C" int stb_tindic_generate(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep,
+                                   stb_seat_info_t *seat_info, stb_classes_info_t *cls_info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_generate";
+  if (!s) return stb_fail("%s: null object", who);
+  if (ti_seat_ready(s, a, bpar, true, who) || ti_cls_ready(s, false, who)) return 1;
+  if (seat_info) memset(seat_info, 0, sizeof(*seat_info));
+  if (cls_info) cls_info->skipped = cls_info->stuck = cls_info->drawn = 0;
+  stb_device_scope dev(s->dev);
+  stb_pool_scratch sc(s->st);
+  double *d_lw = nullptr;
+  if (sc.take(&d_lw, sizeof(double) * (size_t)s->I) != hipSuccess) return stb_fail("%s: out of device memory for %d values", who, s->I);
+  ti_cls_room room(s->st);
+  if (ti_cls_take(s, room, who)) return 1;
+  // the seating under the prior (its three words live behind the class draw's), then every class
+  uint64_t *d_cnt = s->d_cginfo + 3;
+  if (ti_seat_queue(s, a, bpar, true, seed, sweep, d_lw, d_cnt, who) || ti_cls_draw(s, room, nullptr, seed, sweep, who)) return 1;
+  if (seat_info) {
+    seat_info->customers = s->C;
+    if (stb_seat_sum(d_lw, s->I, 1, nullptr, nullptr, nullptr, seat_info, d_cnt, s->st, who)) return 1;
+  }
+  if (cls_info) return sc.last(ti_cls_info(s, cls_info, who));
+  return sc.give_back(true, who);
+}
+
+extern "C" int stb_tindic_get_classes(stb_tindic_t *s, uint32_t *cls_out, unsigned *rows_out) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_get_classes";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!s->d_cls) return stb_fail("%s: classes are not set (stb_tindic_set_classes, stb_tindic_sample_classes)", who);
+  if (rows_out) *rows_out = s->cls_rows;
+  stb_device_scope dev(s->dev);
+  return ti_fetch(s, {{cls_out, s->d_cls, sizeof(uint32_t) * s->C}}, who);
 }
