@@ -28,6 +28,9 @@ The bar of H (u = 2^-53), from the operations -- nothing here reads a device res
       argument plus its own ulp, rho_v + 2 u |log v|; the product E * ln 2 and the constant's own rounding, 2 u |E ln 2|;
       the last sum u |H|.
   Everything times st_oracle.SLACK for the second order.
+
+The chains (chain_case, chain_variant): a launch past k_seat_pf's grid cap in which eight workgroups take three listed
+restaurants each, and what a kernel that forgot one reset between two of them would return.
 """
 from __future__ import annotations
 
@@ -49,6 +52,7 @@ NEG_INF = -math.inf
 MAXR = 64
 LN2 = math.log(2.0)
 LDS_DYN = 61440     # bytes of a workgroup's LDS left to the slots' states (PF_LDS_DYN)
+GRID_CAP = 1 << 20  # k_seat_pf's grid is capped at this many workgroups
 
 
 def budget(K: int) -> int:
@@ -74,14 +78,17 @@ def skipped_mask(K, Cn, R, stride=None):
 
 
 def replay(K, n, t, h, a, bpar, coff, cls=None, lik=None, M: int = 0, seed: int = 0, sweep: int = 0, particles: int = 1,
-           tau: float = 0.5, mut=None, trace: bool = False):
+           tau: float = 0.5, mut=None, trace: bool = False, start=None, only=None):
     """stb_seat_filter on one start state.  Returns a dict: pn, pt (the slots' final pairs in the device's layout, a
     skipped restaurant's zero), w (I, R), E [I], Zm [I], res [I], anc (per restaurant a list of (c, ancestors)), H [I]
     (0 for a skipped restaurant), skipped, impossible, stuck, dead, resamplings, skip (the mask); with trace: steps, per
     restaurant a list over its customers of dicts p, pbar (R each), n0, t0 (the slots' pairs before the visit, (R, K_i)),
     e, S1, resampled, ez, anc, kept (slots not zeroed).
     mut: 'linear' (the weights' scan left to right), 'u4' (u4 taken from u3's element), 'noE' (E left out of H),
-    'noS1' (S1 / R left out of Zm at a resampling)"""
+    'noS1' (S1 / R left out of Zm at a resampling)
+    start, only: a wrong kernel's hand-over (chain_variant).  start: {restaurant: a dict of what it begins with instead
+    of the header's: nn, tt ((R, K_i) pairs), w [R], E, Zm, res, dead}; only: the restaurants that are walked -- the others
+    keep what they began with and their outputs mean nothing.  Neither given, nothing here is touched."""
     K = np.asarray(K, dtype=np.int64)
     I = K.shape[0]
     R = int(particles)
@@ -106,10 +113,19 @@ def replay(K, n, t, h, a, bpar, coff, cls=None, lik=None, M: int = 0, seed: int 
     anc = [[] for _ in range(I)]
     steps = [[] for _ in range(I)]
     out = {"skipped": int(skip.sum()), "impossible": 0, "stuck": 0}
+    walk = ~skip
+    if only is not None:
+        walk = walk & np.isin(np.arange(I), np.fromiter(only, dtype=np.int64))
+    for i, s0 in (start or {}).items():
+        if "nn" in s0:
+            nn[i], tt[i] = np.array(s0["nn"], dtype=np.int64), np.array(s0["tt"], dtype=np.int64)
+            assert nn[i].shape == tt[i].shape == (R, int(K[i]))
+        w[i] = s0.get("w", w[i])
+        E[i], Zm[i], res[i], dead[i] = s0.get("E", 0), s0.get("Zm", 1.0), s0.get("res", 0), s0.get("dead", False)
     key0 = np.uint64(particle_key(seed, sweep, 0))
     cls_full = None if cls is None else np.asarray(cls)
-    for j in range(int(Cn[~skip].max()) if (~skip).any() else 0):
-        act = [i for i in range(I) if not skip[i] and Cn[i] > j]
+    for j in range(int(Cn[walk].max()) if walk.any() else 0):
+        act = [i for i in range(I) if walk[i] and Cn[i] > j]
         # the call's restaurants: the active ones, each followed by one without dishes that holds the customers up to the
         # next one's (skipped there); before the first, one that holds the customers ahead of it
         Kc, co, bp = [0], [0], [1.0]
@@ -414,3 +430,115 @@ def partial_case():
     cls = np.array([0, 1, 1, 0, 1], dtype=np.uint32)
     coff = np.array([0, 5], dtype=np.uint64)
     return K, np.zeros(2, dtype=np.uint32), np.zeros(2, dtype=np.uint16), h, np.array([1.0]), coff, cls, lik
+
+
+# ---------------------------------------------------------------------------------------------------- the chains
+
+# A launch of more than GRID_CAP restaurants: workgroup g takes restaurant g, then GRID_CAP + g, then 2 GRID_CAP + g.  The
+# listed restaurants are three such trips of the first CHAIN_M workgroups, (K_i, customers_i) each; every other
+# restaurant of the launch has no dishes and no customers.  Down a column: register form -> LDS form -> register form,
+# LDS -> register -> register, a dead restaurant -> a live one, no customers -> some and some -> none; at 39 particles
+# K_i = 130 fills the LDS, at 40 those five are skipped.
+CHAIN_A = 0.5
+CHAIN_M = 8
+CHAIN_TRIPS = (((5, 21), (130, 9), (3, 20), (64, 20), (130, 6), (2, 0), (65, 12), (1, 7)),
+               ((130, 8), (3, 22), (65, 9), (1, 5), (2, 23), (64, 19), (128, 6), (5, 20)),
+               ((2, 20), (64, 13), (130, 7), (5, 0), (63, 21), (3, 9), (1, 6), (130, 5)))
+CHAIN_DEAD = 2                                    # the listed restaurant that dies mid-document (trip 0)
+CHAIN_RUNS = ((4, 0.5), (39, 1.0), (40, 0.5))     # (particles, tau)
+CHAIN_VARIANTS = ("keepE", "keepZ", "keepw", "keepdead", "keepres", "stale")
+
+
+@lru_cache(maxsize=None)
+def chain_case():
+    """(case, full): the listed restaurants alone, in launch order, as make_case's tuple, and the whole launch of
+    I = 2 GRID_CAP + CHAIN_M restaurants as a dict: I, K, koff, coff, bpar (full length; a filler's b is 1) and
+    listed (the listed restaurants' indices, ascending).  The fillers hold neither dishes nor customers, so n, t, h, cls
+    and lik are the compact case's and the listed restaurants' offsets are the compact case's too."""
+    trips = len(CHAIN_TRIPS)
+    shapes = [s for tr in CHAIN_TRIPS for s in tr]
+    K, n, t, h, bpar, coff, cls, lik = make_case(shapes, CHAIN_A, 777, rows=6, dead_class=5)
+    cls = np.where(cls == 5, 0, cls).astype(np.uint32)
+    cls[int(coff[CHAIN_DEAD]) + 9] = 5              # restaurant 2 of trip 0 dies at its tenth customer
+    listed = (np.arange(trips, dtype=np.int64)[:, None] * GRID_CAP + np.arange(CHAIN_M, dtype=np.int64)[None, :]).reshape(-1)
+    I = (trips - 1) * GRID_CAP + CHAIN_M
+    Kf, Cf, bf = np.zeros(I, dtype=np.int32), np.zeros(I, dtype=np.int64), np.ones(I)
+    Kf[listed], Cf[listed], bf[listed] = K, np.diff(coff.astype(np.int64)), bpar
+    full = {"I": I, "K": Kf, "koff": np.concatenate([[0], np.cumsum(Kf, dtype=np.int64)]).astype(np.uint64),
+            "coff": np.concatenate([[0], np.cumsum(Cf)]).astype(np.uint64), "bpar": bf, "listed": listed}
+    for x in (K, n, t, h, bpar, coff, cls, lik) + tuple(v for v in full.values() if isinstance(v, np.ndarray)):
+        x.setflags(write=False)
+    return (K, n, t, h, bpar, coff, cls, lik), full
+
+
+def chain_exact(case):
+    """the listed restaurants whose truth is cheap"""
+    K, coff = case[0], case[5].astype(np.int64)
+    return [i for i in range(len(K)) if K[i] <= 65 and 0 < coff[i + 1] - coff[i] <= 12]
+
+
+@lru_cache(maxsize=None)
+def chain_truth(R: int, tau: float):
+    """(rep, H_true, H_bar) of the compact chain case at pf.SEED, pf.SWEEP, M = 0"""
+    case, _ = chain_case()
+    K, n, t, h, bpar, coff, cls, lik = case
+    return truth(K, n, t, h, CHAIN_A, bpar, coff, cls, lik, 0, SEED, SWEEP, R, tau, restaurants=chain_exact(case))
+
+
+def chain_pred(rep, i: int):
+    """the restaurant whose registers and LDS a workgroup still holds when it starts listed restaurant i: the nearest one
+    up its column that was not skipped (a skipped one leaves before it touches either); None on the first trip"""
+    p = i - CHAIN_M
+    while p >= 0 and rep["skip"][p]:
+        p -= CHAIN_M
+    return p if p >= 0 else None
+
+
+def chain_variant(case, rep, R: int, tau: float, variant: str):
+    """What a kernel that forgot one reset between a workgroup's trips would return for the compact chain case: rep's pn,
+    pt, w, E, Zm, res, H and dead_mask with the restaurants of trips 1 and 2 replayed from the hand-over instead of the
+    header's start, a trip at a time, each from what the variant left behind on the trip before.
+      keepE, keepZ, keepres: E, Zm, res start from the predecessor's final value;  keepw: the weights do;
+      keepdead: the successor of a dead restaurant starts dead;
+      stale: dish k < min(K_i, K_pred) of every slot starts from the predecessor's final pair, not from the start state."""
+    assert variant in CHAIN_VARIANTS
+    K, n, t, h, bpar, coff, cls, lik = case
+    koff = np.concatenate([[0], np.cumsum(np.asarray(K, dtype=np.int64))])
+    cur = {f: np.array(rep[f]) for f in ("pn", "pt", "w", "E", "Zm", "res", "H", "dead_mask")}
+
+    def pairs(f, i):
+        return cur[f][int(koff[i]) * R:int(koff[i + 1]) * R].reshape(R, int(K[i])).astype(np.int64)
+
+    m = CHAIN_M
+    for trip in range(1, len(K) // m):
+        start = {}
+        for i in range(trip * m, (trip + 1) * m):
+            p = chain_pred(rep, i)
+            if rep["skip"][i] or p is None:
+                continue
+            if variant == "keepE":
+                start[i] = {"E": int(cur["E"][p])}
+            elif variant == "keepZ":
+                start[i] = {"Zm": float(cur["Zm"][p])}
+            elif variant == "keepres":
+                start[i] = {"res": int(cur["res"][p])}
+            elif variant == "keepw":
+                start[i] = {"w": cur["w"][p].copy()}
+            elif variant == "keepdead":
+                if cur["dead_mask"][p]:
+                    start[i] = {"dead": True}
+            else:
+                kk = int(min(K[i], K[p]))
+                nn = np.tile(np.asarray(n, dtype=np.int64)[koff[i]:koff[i + 1]], (R, 1))
+                tt = np.tile(np.asarray(t, dtype=np.int64)[koff[i]:koff[i + 1]], (R, 1))
+                nn[:, :kk], tt[:, :kk] = pairs("pn", p)[:, :kk], pairs("pt", p)[:, :kk]
+                start[i] = {"nn": nn, "tt": tt}
+        if not start:
+            continue
+        rv = replay(K, n, t, h, CHAIN_A, bpar, coff, cls, lik, 0, SEED, SWEEP, R, tau, start=start, only=start.keys())
+        for i in start:
+            sl = slice(int(koff[i]) * R, int(koff[i + 1]) * R)
+            cur["pn"][sl], cur["pt"][sl] = rv["pn"][sl], rv["pt"][sl]
+            for f in ("w", "E", "Zm", "res", "H", "dead_mask"):
+                cur[f][i] = rv[f][i]
+    return cur

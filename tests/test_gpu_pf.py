@@ -2,7 +2,8 @@
 seat_pf.hip): every slot's final pairs, the weights, the exponent and the resampling counts bit for bit against the numpy
 replay (tests/pf_oracle.py), H_i within the derived bar of the 40-digit truth; the same bits whatever the waves of a
 workgroup; the existing kernel when nothing is resampled; dead restaurants, dead particles, the budget, the refusals and
-the object's call.  The law itself is judged on the CPU (tests/test_pf_host.py)."""
+the object's call.  The law itself is judged on the CPU (tests/test_pf_host.py).  A workgroup's second and third
+restaurant, past the grid's cap, are tests/test_gpu_pf_geometry.py's."""
 import hashlib
 import math
 import os

@@ -2,7 +2,9 @@
 estimate is unbiased by exact enumeration, resampling triggered by the effective sample size included; a filter that
 never resamples is the sequential seating; the numpy replay (tests/pf_oracle.py) lies within the derived bar of the
 40-digit truth and wrong replays do not; the rescaling by powers of two is invisible.  The device is held to the replay
-by bit-equality in tests/test_gpu_pf.py."""
+by bit-equality in tests/test_gpu_pf.py.  The chain case of tests/test_gpu_pf_geometry.py (three restaurants a workgroup)
+holds every hand-over it is meant to, and a replay that forgets one reset between two of them is told apart by what
+that file compares."""
 import math
 
 import numpy as np
@@ -106,3 +108,103 @@ def test_the_rescaling_is_invisible():
 
 def test_the_budget_is_the_headers():
     assert [pf.budget(K) for K in (0, 1, 64, 80, 81, 130, 1024)] == [64, 64, 64, 64, 62, 39, 5]
+
+
+# ---- the chain case of tests/test_gpu_pf_geometry.py: a workgroup's second and third restaurant
+
+def test_the_chain_case_is_the_full_launch_restricted_to_the_listed_restaurants():
+    case, full = pf.chain_case()
+    K, n, t, h, bpar, coff, cls, lik = case
+    m, L = pf.CHAIN_M, full["listed"]
+    assert full["I"] == 2 * pf.GRID_CAP + m == len(full["K"]) == len(full["bpar"]) == len(full["koff"]) - 1 == len(full["coff"]) - 1
+    # workgroup g < m of a grid of GRID_CAP takes g, GRID_CAP + g, 2 GRID_CAP + g: the listed ones, three trips each
+    assert np.array_equal(L, np.concatenate([s * pf.GRID_CAP + np.arange(m) for s in range(3)])) and len(K) == 3 * m
+    assert [(int(k), int(c)) for k, c in zip(K, np.diff(coff.astype(np.int64)))] == [s for tr in pf.CHAIN_TRIPS for s in tr]
+    koff = np.concatenate([[0], np.cumsum(K, dtype=np.int64)]).astype(np.uint64)
+    assert np.array_equal(full["K"][L], K) and np.array_equal(full["bpar"][L], bpar)
+    assert np.array_equal(full["koff"][L], koff[:-1]) and np.array_equal(full["koff"][L + 1], koff[1:])
+    assert np.array_equal(full["coff"][L], coff[:-1]) and np.array_equal(full["coff"][L + 1], coff[1:])
+    assert full["koff"][-1] == koff[-1] == len(n) == len(t) == len(h) and full["coff"][-1] == coff[-1] == len(cls)
+    # the others: no dishes, no customers
+    rest = np.ones(full["I"], dtype=bool)
+    rest[L] = False
+    assert not full["K"][rest].any() and not np.diff(full["coff"].astype(np.int64))[rest].any() and np.all(full["bpar"][rest] == 1.0)
+    assert np.all(np.diff(full["koff"].astype(np.int64)) == full["K"])
+    assert not (cls >= lik.shape[0]).any() and int((cls == 5).sum()) == 1 and not lik[5].any() and lik[:5].all()
+
+
+def _kinds(case, rep):
+    """per listed restaurant what the workgroup did with it, from the replay's outputs, and the visit's form"""
+    K, Cn = case[0], np.diff(case[5].astype(np.int64))
+    kind = ["skipped" if rep["skip"][i] else "dead" if rep["dead_mask"][i] else "empty" if Cn[i] == 0 else "alive" for i in range(len(K))]
+    form = ["reg" if K[i] <= 64 else "lds" for i in range(len(K))]
+    return kind, form
+
+
+def _hands(kind, m):
+    """(kind of the restaurant before, kind of the one after) over every two consecutive trips of a workgroup"""
+    return {(kind[i - m], kind[i]) for i in range(m, len(kind))}
+
+
+def test_the_chains_hold_every_hand_over():
+    case, _ = pf.chain_case()
+    K, m = case[0], pf.CHAIN_M
+    reps = {R: pf.chain_truth(R, tau)[0] for R, tau in pf.CHAIN_RUNS}
+    assert sorted(reps) == [4, 39, 40] and pf.budget(130) == 39 and pf.budget(128) >= 40
+    for R, rep in reps.items():
+        kind, form = _kinds(case, rep)
+        hands = _hands(kind, m)
+        assert [i for i, k in enumerate(kind) if k == "dead"] == [pf.CHAIN_DEAD] and rep["dead"] == 1, (R, kind)
+        assert ("empty", "alive") in hands and ("alive", "empty") in hands, (R, hands)
+        assert ("dead", "alive") in hands and rep["resamplings"] > 0, (R, hands)
+        if R <= 39:
+            assert rep["skipped"] == 0
+            walked = [[form[g + s * m] for s in range(3)] for g in range(m) if all(kind[g + s * m] == "alive" for s in range(3))]
+            assert ["reg", "lds", "reg"] in walked and ["lds", "reg", "reg"] in walked, (R, walked)
+        else:
+            assert rep["skipped"] == 5 and [i for i, k in enumerate(kind) if k == "skipped"] == [i for i in range(3 * m) if K[i] == 130]
+            assert ("skipped", "alive") in hands and ("alive", "skipped") in hands, hands
+    # the buffer a predecessor ends in: both parities before a successor that is seated, in either form of the successor
+    rep = reps[39]
+    kind, form = _kinds(case, rep)
+    assert list(rep["res"]) == [18, 8, 8, 18, 4, 0, 11, 5, 6, 21, 8, 1, 21, 17, 4, 19, 18, 11, 5, 0, 20, 7, 4, 3]
+    seen = {(int(rep["res"][i - m]) & 1, form[i]) for i in range(m, 3 * m) if kind[i] == "alive"}
+    assert seen == {(0, "reg"), (1, "reg"), (0, "lds"), (1, "lds")}, seen
+
+
+def _differing(case, rep, Hb, var, R):
+    """the (restaurant, output) pairs of trips 1 and 2 in which a variant's results differ from the replay's by more than
+    the device tests allow: bits of pn, pt, w, E, res; H by an infinity or by more than two bars"""
+    K, m = case[0], pf.CHAIN_M
+    koff = np.concatenate([[0], np.cumsum(K, dtype=np.int64)])
+    out = []
+    for i in range(m, len(K)):
+        if rep["skip"][i]:
+            continue
+        sl = slice(int(koff[i]) * R, int(koff[i + 1]) * R)
+        out += [(i, f) for f in ("pn", "pt") if not np.array_equal(var[f][sl], rep[f][sl])]
+        out += [(i, "w")] if not np.array_equal(var["w"][i].view(np.uint64), rep["w"][i].view(np.uint64)) else []
+        out += [(i, f) for f in ("E", "res") if var[f][i] != rep[f][i]]
+        hv, hr = float(var["H"][i]), float(rep["H"][i])
+        if (math.isinf(hv) or math.isinf(hr)) and hv != hr or (math.isfinite(hv) and math.isfinite(hr) and abs(hv - hr) > 2.0 * Hb[i]):
+            out.append((i, "H"))
+    return out
+
+
+@pytest.mark.parametrize("variant", pf.CHAIN_VARIANTS)
+def test_a_forgotten_reset_between_two_trips_is_told_apart(variant):
+    case, _ = pf.chain_case()
+    # at the budget's limit; the dead restaurant's successors are cheapest at four particles (both are seated there)
+    R, tau = pf.CHAIN_RUNS[0] if variant == "keepdead" else pf.CHAIN_RUNS[1]
+    rep, _, Hb = pf.chain_truth(R, tau)
+    assert not _differing(case, rep, Hb, {f: rep[f] for f in ("pn", "pt", "w", "E", "res", "H")}, R)
+    var = pf.chain_variant(case, rep, R, tau, variant)
+    diff = _differing(case, rep, Hb, var, R)
+    print(variant, "R", R, "differs in", diff)
+    assert diff, variant
+    # trip 0 has no predecessor: untouched
+    koff0 = int(np.cumsum(case[0], dtype=np.int64)[pf.CHAIN_M - 1]) * R
+    assert np.array_equal(var["pn"][:koff0], rep["pn"][:koff0]) and np.array_equal(var["E"][:pf.CHAIN_M], rep["E"][:pf.CHAIN_M])
+    if variant == "keepdead":
+        succ = [pf.CHAIN_DEAD + pf.CHAIN_M, pf.CHAIN_DEAD + 2 * pf.CHAIN_M]
+        assert {i for i, _ in diff} == set(succ) and all((i, "H") in diff for i in succ) and np.all(np.isfinite(rep["H"][succ]))
