@@ -57,7 +57,11 @@
  *      (stb_tindic_heldout_seq) -- the likelihood of the held-out customers as a whole, where -P scores each one alone.
  *  18. with -F tau (needs -Q R, R <= 64) the particle filter's figure stands next to it: the same R particles, resampled
  *      between customers when their effective number falls below tau R (stb_tindic_heldout_pf), and the resamplings.
- *  19. with -V rows (needs -d -z) the corpus is the model's own: every dish's distribution over `rows` classes is a draw
+ *  19. with -A S (needs -Q R) annealed importance sampling stands next to them: the same held-out customers scored as
+ *      UNSEEN documents -- restaurants that start empty, with the chain's current h and likelihood -- by R particles that
+ *      climb S temperatures, one dish sweep at each (stb_tindic_heldout_ais, on an empty twin of the object: the ladder's
+ *      sweeps are exact only where every customer of a restaurant is the document's own).
+ *  20. with -V rows (needs -d -z) the corpus is the model's own: every dish's distribution over `rows` classes is a draw
  *      from its Dirichlet(0.5) prior (stb_sample_lik on zero counts, into the object's matrix), and the seating and every
  *      customer's class are drawn on the device given that matrix (stb_tindic_generate).  The chain then starts from a
  *      fresh stb_tindic_seat under the generated classes, as with -S, and every iteration prints the data term
@@ -65,7 +69,7 @@
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5] [-V 1000]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5] [-A 8] [-V 1000]
  */
 #include <math.h>
 #include <stdio.h>
@@ -86,11 +90,11 @@ static int cmp_double(const void *x, const void *y) {
 }
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, filter = 0, vrows = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, filter = 0, vrows = 0, anneal = 0, c, j, i, it;
   double ftau = 0.0;
   double a0 = 0.5, b0 = 10.0, beta = 0.5, gam = 1.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:V:")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:V:A:")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -112,6 +116,7 @@ int main(int argc, char **argv) {
     else if (c == 'S') seatdev = 1;
     else if (c == 'Q') seqpart = atoi(optarg) >= 1 ? atoi(optarg) : -1;
     else if (c == 'F') filter = 1, ftau = atof(optarg);
+    else if (c == 'A') anneal = atoi(optarg) >= 1 ? atoi(optarg) : -1;
     else if (c == 'V') vrows = atoi(optarg) >= 2 ? atoi(optarg) : -1;
     else return 2;
   }
@@ -145,6 +150,10 @@ int main(int argc, char **argv) {
   }
   if (filter && (!seqpart || seqpart > STB_PF_MAXR || !(ftau >= 0.0 && ftau <= 1.0))) {
     fprintf(stderr, "pyp_resample: -F tau needs 0 <= tau <= 1 and -Q R with R <= %d\n", STB_PF_MAXR);
+    return 2;
+  }
+  if (anneal < 0 || (anneal && !seqpart)) {
+    fprintf(stderr, "pyp_resample: -A S needs S >= 1 and -Q R\n");
     return 2;
   }
   if (vrows < 0 || (vrows && !(explicit_d && dishes))) {
@@ -274,6 +283,26 @@ int main(int argc, char **argv) {
       free(hoff);
       free(hcls);
     }
+    /* -A: an empty twin of the object -- the same dishes, no customers -- that scores the held-out customers as unseen
+     * documents; it is given the chain's h and matrix before every use */
+    stb_tindic_t *tu = NULL;
+    double *ulik = NULL, *uh = NULL;
+    if (anneal) {
+      int *Ku = malloc(sizeof(*Ku) * (size_t)J);
+      scnt_int *nu = calloc((size_t)J * DISHES, sizeof(*nu));
+      stcnt_int *tz = calloc((size_t)J * DISHES, sizeof(*tz));
+      const uint64_t per = (uint64_t)ncust / 5;
+      uint64_t *hoff = malloc(sizeof(*hoff) * ((size_t)J + 1));
+      scnt_int *hcls = malloc(sizeof(*hcls) * ((size_t)J * per + 1));
+      for (j = 0; j < J; j++) Ku[j] = DISHES;
+      for (j = 0; j <= J; j++) hoff[j] = (uint64_t)j * per;
+      for (cc = 0; cc < (size_t)J * per; cc++) hcls[cc] = (scnt_int)(cc & 1);
+      tu = stb_tindic_create(J, Ku, nu, tz, NULL, NULL, 0, 0);
+      if (!tu || stb_tindic_set_lik(tu, NULL, 2, DISHES) || stb_tindic_set_heldout(tu, hoff, hcls))
+        yaps_quit("the empty twin: %s\n", stb_last_error());
+      uh = malloc(sizeof(double) * (size_t)J * DISHES);
+      free(Ku), free(nu), free(tz), free(hoff), free(hcls);
+    }
     double *hflat = NULL;
     if (hgroups) { /* hgroups equal contiguous ranges of restaurants, each with base weights of its own */
       uint64_t *hgoff = malloc(sizeof(*hgoff) * ((size_t)hgroups + 1));
@@ -393,6 +422,20 @@ int main(int argc, char **argv) {
               yaps_quit("stb_tindic_heldout_pf: %s\n", stb_last_error());
             printf(" pf %.6f (%llu resamplings)", hs, (unsigned long long)fi.resamplings);
           }
+          if (anneal) { /* the same customers as unseen documents: the chain's h and matrix on the empty twin */
+            unsigned lr, ls;
+            void *lst;
+            stb_ais_info_t ai;
+            const double *d_lik = stb_tindic_lik_device(ti, &lr, &ls, &lst);
+            if (d_lik && !ulik) ulik = malloc(sizeof(double) * (size_t)lr * ls);
+            if (!d_lik || stb_memcpy_d2h(ulik, d_lik, sizeof(double) * (size_t)lr * ls, lst) || stb_tindic_get_h(ti, uh) ||
+                stb_tindic_set_lik(tu, ulik, lr, ls) || stb_tindic_set_h(tu, uh) || (pergroup && stb_tindic_get_bpar(ti, bvec)))
+              yaps_quit("the empty twin's h and matrix: %s\n", stb_last_error());
+            if (stb_tindic_heldout_ais(tu, a, pergroup ? bvec : bp, (unsigned)seqpart, (unsigned)anneal, NULL, 1, (uint64_t)seed + 8,
+                                       (uint64_t)it * 4096u, &hs, NULL, &ai))
+              yaps_quit("stb_tindic_heldout_ais: %s\n", stb_last_error());
+            printf(" ais %.6f (unseen, %d temperatures, %llu dead)", hs, anneal, (unsigned long long)ai.dead);
+          }
         }
         printf("\n");
       }
@@ -449,6 +492,8 @@ int main(int argc, char **argv) {
     }
     stb_groups_free(gs);
     stb_tindic_free(ti);
+    if (tu) stb_tindic_free(tu);
+    free(ulik), free(uh);
     free(hflat);
     free(nf);
     free(tf);

@@ -1269,6 +1269,83 @@ unsigned stb_seat_filter_budget(unsigned K);
 int stb_tindic_heldout_pf(stb_tindic_t *s, double a, const double *bpar, unsigned particles, double tau, uint64_t seed,
                           uint64_t sweep, double *total, double *Hi_host /* or NULL */, stb_pf_info_t *info /* or NULL */);
 
+/* ---- annealed importance sampling for unseen documents (seat_ais.hip) ----
+ * Both estimators above buy accuracy with particles.  This one buys it with temperatures: a particle starts as a draw
+ * from the prior and is moved, by dish sweeps, through laws that lean on the likelihood more and more.  Restaurant i
+ * starts EMPTY; its N_i customers have classes cls_c; the ladder is 0 = beta_0 < beta_1 < ... < beta_S = 1 and
+ *     f_s(z, t) = P(z, t | a, b, h, M) prod_c L[cls_c][z_c]^beta_s,
+ * so f_0 is the prior (Z_0 = 1: stb_seat_customers' statement with L = 1, with or without a truncation M) and
+ * Z_S = p(w_1 .. w_N | L, h, a, b).  Per particle:
+ *   1. x_0 ~ prior: stb_seat_customers without a matrix, one committed particle; lw starts at that seating's own log
+ *      weight.  Without a truncation that is 0 up to rounding (every sum of theta is 1).  With a truncation M the sums
+ *      fall short of 1 and the seating is a WEIGHTED draw from the prior over the states with t <= M -- its statement
+ *      above -- and the weight is what makes Z_S the truncated p(w), the quantity _heldout_seq estimates.
+ *   2. for s = 1 .. S:  lw += (beta_s - beta_{s-1}) * D(x_{s-1}),  D(x) = sum_c log L[cls_c][z_c];
+ *   3. if s < S, AFTER the increment:  x_s = `passes` dish sweeps (stb_sample_tdishes) of x_{s-1} under the matrix L^beta_s.
+ * The dish sweep leaves prior x prod_c L'[cls_c][z_c] invariant for any matrix L' >= 0, L^beta_s included, so
+ * E[exp lw] = Z_S for every S, every ladder and every number of passes, and H_i = log((1/R) sum_r exp lw_r) is
+ * stb_seat_loglik's, unchanged.  The order is part of the law: the increment is taken on the state BEFORE the sweep, and
+ * the sweep runs under the NEW temperature (DESIGN.md section 6 has the two wrong orders' numbers).  S = 1 has no sweep:
+ * importance sampling from the prior.  Only empty starts: the dish sweep's removal treats every customer of a pair as
+ * exchangeable, so moving only the held-out customers of a restaurant that holds training customers too could take t
+ * below the training seating's -- not the conditional given that seating.
+ *
+ * stb_seat_anneal queues, on one stream and with no wait, the existing kernels on a replicated problem of I R restaurants
+ * and R C customers: replica j = i R + r has its pairs at koff'[j] = koff[i] R + r K_i (stb_seat_filter's d_pn layout), its
+ * customers at coff'[j] = coff[i] R + r N_i, the classes, h and b of restaurant i, and n' = t' = 0 (k_ais_expand; all
+ * offsets uint64).  Then stb_seat_customers(particles = 1, STB_SEAT_COMMIT, no matrix, sweep number `sweep`) on the
+ * replicas, and per temperature s: the matrix lik^beta_s if s < S (k_ais_temper), the increment (k_ais_weight), and if
+ * s < S `passes` dish sweeps numbered sweep + 1 + (s-1) passes .. under that matrix.  Every uniform is therefore the one
+ * the two contracts above name, on the replicated problem: C' = R C, c the replica's flat customer index.  One M, the
+ * V table's, goes to the seating and to the sweeps.
+ *   stb_lik_temper (k_ais_temper): out = 0 where lik = 0, elsewhere exp(beta * log(lik)) -- a log, one product, an exp, in
+ *     FP64 with no contraction, a cell a thread.  Public so that a replay can fetch exactly the matrix the sweeps read:
+ *     a matrix per temperature is materialised (one streaming pass) so that no bit of the path depends on an exp the
+ *     host cannot reproduce.
+ *   D (k_ais_weight): a wave a replica.  Customer q of the replica (q = 0 .. N_i - 1) belongs to lane q mod 64; a lane
+ *     adds its x_q = log(lik[cls'_q stride + cust'_q]) in increasing q in double-double (dd_add: t = hi + x; if t is
+ *     finite, bb = t - hi and lo += (hi - (t - bb)) + (x - bb); hi = t -- k_seat's lw); the lanes 0 .. min(64, N_i) - 1
+ *     are then added in lane order into one double-double (the lane's hi by dd_add, its lo added to lo), and
+ *     D = hi + lo.  log 0 = -inf; a class >= rows counts as L = 0, as the dish sweep reads it.  Then
+ *     lw = lw + dbeta * D (one product, one sum), dbeta = beta_s - beta_{s-1} taken once on the host in FP64.  beta
+ *     strictly increasing keeps 0 * inf out; a particle at -inf stays there and counts as dead.  The bits of lw depend on
+ *     the replica's customers alone: not on the waves of a workgroup (STB_AIS_WAVES = 1, 2, 4 or 8; default 4), the grid,
+ *     or who shares the launch.
+ * Arguments: the V slab and its bounds (N, M) for discount a; a, d_bpar, I, d_koff, d_h (or NULL: 1), d_coff, d_cls,
+ * d_lik, rows, stride; G = koff[I] and C = coff[I] as the caller states them (the workspace is sized from them: they are
+ * checked on the device, and a disagreement leaves every restaurant out and counts all I as skipped); particles (1 ..
+ * 4096); S >= 1; betas_host (S values) or NULL for beta_s = (double)s / (double)S, beta_S = 1.0; passes >= 1; seed, sweep.
+ * Outputs: d_lw[I x particles], to be finished by stb_seat_loglik; optional final states d_pn, d_pt (G x particles) and
+ * d_pcust (C x particles) in the replicated layout, the weighted posterior sample; d_info: NULL, or three uint64 added
+ * to: skipped restaurants, dead particles (lw = -inf at the end), stuck visits of the seating and the sweeps.  A restaurant
+ * that one of the kernels would skip -- K_i > STB_TD_MAXK, K_i > stride, K_i = 0 with customers, N_i > the table's N -- is
+ * left out whole: lw = 0 for every r, H_i = 0, counted once in skipped; its replicas keep their places in the layout (so
+ * the others' streams do not move) and their final states mean nothing.  d_ws: stb_seat_anneal_workspace_bytes(I, G, C,
+ * particles, rows, stride) bytes of device memory, the call's own until the stream has run it.  No chunking inside the
+ * call -- the streams depend on C' -- so a caller short of memory splits its restaurants.  Refused before anything is
+ * queued, with stb_last_error() set: what stb_sample_tdishes and stb_seat_customers refuse of these arguments; S = 0 or
+ * passes = 0; betas not strictly increasing inside (0, 1] or not ending at exactly 1.0; a null matrix or null classes; a
+ * workspace that is null or too small; I x particles beyond an int.
+ *
+ * stb_tindic_heldout_ais is the twin of _heldout_seq and _heldout_pf over the customers of stb_tindic_set_heldout, for an
+ * object that holds NO customers of its own (otherwise refused, for the reason above) and has a matrix.  It keeps a V
+ * table of its own for this call, at N = max(3, max_i held-out N_i) and M as given at create, refilled only when a or the
+ * bounds change and checked with stb_fill_status as _sweep does.  It writes nothing of the object's state or
+ * accumulator.  info: skipped, dead, stuck as above, customers = hoff[I]. */
+typedef struct stb_ais_info { uint64_t skipped, dead, stuck, customers; } stb_ais_info_t;
+size_t stb_seat_anneal_workspace_bytes(int I, uint64_t G, uint64_t C, unsigned particles, unsigned rows, unsigned stride);
+int stb_lik_temper(const double *d_lik, unsigned rows, unsigned stride, double beta, double *d_out, void *stream);
+int stb_seat_anneal(const double *d_vtable, unsigned N, unsigned M, double a, const double *d_bpar, int I,
+                    const uint64_t *d_koff /* I+1 */, const double *d_h /* NULL: 1 */, const uint64_t *d_coff /* I+1 */,
+                    const uint32_t *d_cls, const double *d_lik, unsigned rows, unsigned stride, uint64_t G, uint64_t C,
+                    unsigned particles, unsigned S, const double *betas_host /* S, or NULL */, unsigned passes, uint64_t seed,
+                    uint64_t sweep, double *d_lw /* I x particles */, uint32_t *d_pn, uint16_t *d_pt /* NULL, or G x
+                    particles each */, uint32_t *d_pcust /* NULL, or C x particles */, uint64_t *d_info /* NULL or 3 uint64
+                    added to */, void *d_ws, size_t ws_bytes, void *stream);
+int stb_tindic_heldout_ais(stb_tindic_t *s, double a, const double *bpar, unsigned particles, unsigned S,
+                           const double *betas /* S, or NULL */, unsigned passes, uint64_t seed, uint64_t sweep,
+                           double *total, double *Hi_host /* or NULL */, stb_ais_info_t *info /* or NULL */);
+
 /* ---- customers' classes drawn on the device: generated and missing data (classgen.hip; additive) ----
  * The one variable of DESIGN.md section 6's joint that the steps above take from the caller: customer c's class given
  * its dish, cls_c ~ lik[.][z_c] / Z_{z_c}.  With it the object generates from its own model (stb_tindic_generate), and

@@ -102,6 +102,11 @@ class PFInfo(C.Structure):
 GEOM_LOGQ, GEOM_JOINT_TERMS, GEOM_LOGJOINT = 0, 1, 2  # stb_reduce_geometry's `which`
 
 
+class AISInfo(C.Structure):
+    """stb_ais_info_t (include/stb_hip.h)"""
+    _fields_ = [("skipped", C.c_uint64), ("dead", C.c_uint64), ("stuck", C.c_uint64), ("customers", C.c_uint64)]
+
+
 class ReduceGeom(C.Structure):
     """stb_reduce_geom_t (include/stb_hip.h)"""
     _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("steps", C.c_uint), ("chunks", C.c_uint),
@@ -392,6 +397,13 @@ def lib() -> C.CDLL:
     sig("stb_seat_filter", i, [d, vp, i, vp, vp, vp, vp, u, vp, vp, vp, u, u, u, d, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("stb_seat_filter_budget", u, [u])
     sig("stb_tindic_heldout_pf", i, [vp, d, c_double_p, u, d, u64, u64, c_double_p, c_double_p, C.POINTER(PFInfo)])
+    # ---- annealed importance sampling
+    sig("stb_seat_anneal_workspace_bytes", C.c_size_t, [i, u64, u64, u, u, u])
+    sig("stb_lik_temper", i, [vp, u, u, d, vp, vp])
+    sig("stb_seat_anneal", i, [vp, u, u, d, vp, i, vp, vp, vp, vp, vp, u, u, u64, u64, u, u, c_double_p, u, u64, u64, vp, vp, vp,
+                               vp, vp, vp, C.c_size_t, vp])
+    sig("stb_tindic_heldout_ais", i, [vp, d, c_double_p, u, u, c_double_p, u, u64, u64, c_double_p, c_double_p,
+                                      C.POINTER(AISInfo)])
     # ---- customers' classes drawn on the device
     cli = C.POINTER(ClassesInfo)
     sig("stb_sample_classes", i, [vp, u, u, vp, vp, u64, u64, u64, vp, vp, vp])
@@ -1017,6 +1029,55 @@ def seat_filter(a, bpar, koff, n, t, coff, h=None, M: int = 0, cls=None, lik=Non
                                 coff.data_ptr(), ptr(cls), ptr(lik), rows, stride, int(particles), float(tau), seed, sweep,
                                 ptr(o.get("Hi")), ptr(o.get("w")), ptr(o.get("E")), ptr(o.get("res")), ptr(o.get("pn")),
                                 ptr(o.get("pt")), ptr(info), stream_ptr(stream)))
+    return o
+
+
+def lik_temper(lik, beta: float, out=None, stream=None):
+    """stb_lik_temper on a device tensor lik (float64 (rows, stride)): lik^beta cell by cell (0 stays 0), the matrix the
+    dish sweeps of stb_seat_anneal read at temperature beta.  Queued, no wait."""
+    torch = _torch()
+    out = torch.empty_like(lik) if out is None else out
+    check(lib().stb_lik_temper(lik.data_ptr(), int(lik.shape[0]), int(lik.shape[1]), float(beta), out.data_ptr(),
+                               stream_ptr(stream)))
+    return out
+
+
+def seat_anneal(tabs, a, bpar, koff, coff, cls, lik, h=None, particles: int = 1, S: int = 1, betas=None, passes: int = 1,
+                seed: int = 0, sweep: int = 0, want_states: bool = True, info=None, stream=None, G=None, C_=None,
+                bounds=None, ws=None):
+    """stb_seat_anneal on device tensors (as seat_customers takes them) for restaurants that start empty.  tabs: a
+    DeviceVTables filled for a (None with bounds=(N, M): no table).  betas: None (the even ladder) or S values.  G, C_:
+    what the caller states for koff[I] and coff[I] (None: read from the tensors).  Queued, no wait.  Returns a dict of
+    device tensors: lw float64 (I, particles), to be finished by seat_loglik; with want_states pn int32 (holding uint32),
+    pt int16 (holding uint16) [G particles] and pcust int32 [C particles] in the replicated layout (replica i particles +
+    r: pairs from koff[i] particles + r K_i, customers from coff[i] particles + r N_i); ws, the workspace (keep it until
+    the stream has run the call).  info: None, or an int64 device tensor of three elements the call adds to (skipped,
+    dead, stuck)."""
+    torch = _torch()
+    I = int(koff.shape[0]) - 1
+    dev = koff.device
+    R = max(int(particles), 1)
+    G = int(koff[-1].item()) if G is None else int(G)
+    C_ = int(coff[-1].item()) if C_ is None else int(C_)
+    N, M = (tabs.N, tabs.M) if bounds is None else bounds
+    rows, stride = int(lik.shape[0]), int(lik.shape[1])
+    o = {"lw": torch.zeros((max(I, 1), R), dtype=torch.float64, device=dev)[:I]}
+    if want_states:
+        o["pn"] = torch.zeros(max(G * R, 1), dtype=torch.int32, device=dev)[:G * R]
+        o["pt"] = torch.zeros(max(G * R, 1), dtype=torch.int16, device=dev)[:G * R]
+        o["pcust"] = torch.zeros(max(C_ * R, 1), dtype=torch.int32, device=dev)[:C_ * R]
+    need = int(lib().stb_seat_anneal_workspace_bytes(I, G, C_, R, rows, stride))
+    o["ws"] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev) if ws is None else ws
+    bp = None
+    if betas is not None:
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        bp = dp(betas)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    check(lib().stb_seat_anneal(None if tabs is None else tabs.tables.data_ptr(), int(N), int(M), float(a), ptr(bpar), I,
+                                koff.data_ptr(), ptr(h), coff.data_ptr(), ptr(cls), ptr(lik), rows, stride, G, C_,
+                                int(particles), int(S), bp, int(passes), seed, sweep, o["lw"].data_ptr(), ptr(o.get("pn")),
+                                ptr(o.get("pt")), ptr(o.get("pcust")), ptr(info), o["ws"].data_ptr(), int(o["ws"].numel()),
+                                stream_ptr(stream)))
     return o
 
 
@@ -1712,6 +1773,22 @@ class TableIndicators(_BGroupsMixin):
         tot, info = C.c_double(0.0), PFInfo()
         check(self.L.stb_tindic_heldout_pf(self.h, float(a), dp(bpar), int(particles), float(tau), seed, sweep, C.byref(tot),
                                            None if Hi is None else dp(Hi), C.byref(info)))
+        return tot.value, Hi, info
+
+    def heldout_ais(self, a, bpar, particles: int, S: int, seed: int, sweep: int, betas=None, passes: int = 1,
+                    want_Hi: bool = True):
+        """(total, H_i[I] or None, AISInfo): the held-out customers of an object that holds none of its own, scored by
+        annealed importance sampling (stb_seat_anneal): S temperatures (betas: None for the even ladder), `passes` dish
+        sweeps at each but the last.  Writes nothing of the object"""
+        bpar = _bpar(bpar, self.I)
+        Hi = np.zeros(self.I, dtype=np.float64) if want_Hi else None
+        bp = None
+        if betas is not None:
+            betas = np.ascontiguousarray(betas, dtype=np.float64)
+            bp = dp(betas)
+        tot, info = C.c_double(0.0), AISInfo()
+        check(self.L.stb_tindic_heldout_ais(self.h, float(a), dp(bpar), int(particles), int(S), bp, int(passes), seed, sweep,
+                                            C.byref(tot), None if Hi is None else dp(Hi), C.byref(info)))
         return tot.value, Hi, info
 
     def heldout_reset(self):

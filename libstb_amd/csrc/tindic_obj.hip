@@ -19,6 +19,7 @@
 #include "predict.h"
 #include "seat.h"
 #include "seat_pf.h"
+#include "seat_ais.h"
 #include "hgroups.h"
 #include "dirmult.h"
 #include "dirconc.h"
@@ -79,6 +80,14 @@ struct stb_tindic {
   uint64_t Hc;
   unsigned hcls_max;    // the largest held-out class (0 when Hc = 0)
   unsigned hsamples;    // states accumulated
+  uint64_t hmaxNi;      // the largest held-out N_i
+  // the V table of stb_tindic_heldout_ais (seat_ais.hip): bounds from the held-out customers, not from the object's own
+  double *d_avt;
+  void *d_aws;
+  uint64_t avstride;
+  size_t aws_bytes;
+  unsigned aN, aM;
+  double a_afilled;     // the discount it holds (NaN: none yet)
   hipStream_t st;
 };
 
@@ -159,7 +168,8 @@ static void ti_release(stb_tindic_t *s) {
   ti_drop_sslab(s);
   ti_drop_cgs(s);
   void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws,
-                 s->d_cls, s->d_lik, s->d_info, s->d_hoff, s->d_hcls, s->d_pacc, s->d_hgoff, s->d_hroot, s->d_cginfo};
+                 s->d_cls, s->d_lik, s->d_info, s->d_hoff, s->d_hcls, s->d_pacc, s->d_hgoff, s->d_hroot, s->d_cginfo,
+                 s->d_avt, s->d_aws};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (s->h_info) (void)hipHostFree(s->h_info);
@@ -259,6 +269,7 @@ static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, 
   s->M = tb.M;
   s->a_filled = NAN;
   s->a_sfilled = NAN;
+  s->a_afilled = NAN;
   s->hg_alpha = NAN;
   const size_t Gs = G ? G : 1;
   int rc = 0;
@@ -1084,12 +1095,13 @@ extern "C" int stb_tindic_set_heldout(stb_tindic_t *s, const uint64_t *hoff_host
   STB_ENTRY;
   const char *who = "stb_tindic_set_heldout";
   if (!s) return stb_fail("%s: null object", who);
-  uint64_t Hc = 0;
+  uint64_t Hc = 0, hmax = 0;
   unsigned cmax = 0;
   if (hoff_host) {
     if (hoff_host[0] != 0) return stb_fail("%s: hoff[0]=%llu (must be 0)", who, (unsigned long long)hoff_host[0]);
     for (int i = 0; i < s->I; i++)
       if (hoff_host[i + 1] < hoff_host[i]) return stb_fail("%s: hoff[%d] < hoff[%d]", who, i + 1, i);
+    for (int i = 0; i < s->I; i++) hmax = std::max(hmax, hoff_host[i + 1] - hoff_host[i]);
     Hc = hoff_host[s->I];
     if (Hc && !hcls_host) return stb_fail("%s: the held-out classes are required", who);
     for (uint64_t c = 0; c < Hc; c++) {
@@ -1128,6 +1140,7 @@ extern "C" int stb_tindic_set_heldout(stb_tindic_t *s, const uint64_t *hoff_host
     s->Hc = Hc;
     s->hcls_max = cmax;
     s->hsamples = 0;
+    s->hmaxNi = hmax;
   }
   return rc;
 }
@@ -1316,6 +1329,92 @@ extern "C" int stb_tindic_heldout_pf(stb_tindic_t *s, double a, const double *bp
     info->stuck = si.stuck;
     info->dead = two[0];
     info->resamplings = two[1];
+    info->customers = s->Hc;
+  }
+  return sc.last(0);
+}
+
+// the V table the ladder's dish sweeps read: for discount a at the bounds the held-out customers can reach.  Kept with
+// the object; allocated again when the bounds change, refilled (checked: a wait) when they or the discount do
+static int ti_ais_table(stb_tindic_t *s, double a, const ti_bounds &tb, const char *who) {
+  if (!tb.need_table) return 0;
+  if (!s->d_avt || tb.N != s->aN || tb.M != s->aM) {
+    const uint64_t vstride = (stb_vtable_elems(tb.N, tb.M) + 31) & ~31ull;
+    const size_t ws_bytes = stb_fill_workspace_bytes(tb.N, tb.M, 1);
+    double *vt = nullptr;
+    void *ws = nullptr;
+    if (hipMalloc((void **)&vt, sizeof(double) * vstride) != hipSuccess || hipMalloc(&ws, ws_bytes ? ws_bytes : 1) != hipSuccess) {
+      if (vt) (void)hipFree(vt);
+      return stb_fail("%s: out of device memory for a %u x %u V table", who, tb.N, tb.M);
+    }
+    if (hipStreamSynchronize(s->st) != hipSuccess) {  // (a queued ladder reads the table that goes)
+      (void)hipFree(vt);
+      (void)hipFree(ws);
+      return STB_STREAM_FAIL(who);
+    }
+    if (s->d_avt) (void)hipFree(s->d_avt);
+    if (s->d_aws) (void)hipFree(s->d_aws);
+    s->d_avt = vt;
+    s->d_aws = ws;
+    s->avstride = vstride;
+    s->aws_bytes = ws_bytes;
+    s->aN = tb.N;
+    s->aM = tb.M;
+    s->a_afilled = NAN;
+  }
+  if (a == s->a_afilled) return 0;
+  s->a_afilled = NAN;
+  if (stb_fill_V(&a, 1, s->aN, s->aM, s->d_avt, s->avstride, s->d_aws, s->aws_bytes, s->st) || stb_fill_status()) return 1;
+  s->a_afilled = a;
+  return 0;
+}
+
+extern "C" int stb_tindic_heldout_ais(stb_tindic_t *s, double a, const double *bpar, unsigned particles, unsigned S,
+                                      const double *betas, unsigned passes, uint64_t seed, uint64_t sweep, double *total,
+                                      double *Hi_host, stb_ais_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_heldout_ais";
+  if (!s) return stb_fail("%s: null object", who);
+  if (!total) return stb_fail("%s: total is required", who);
+  if (ti_pr_ready(s, a, bpar, 0, true, who)) return 1;
+  if (s->flags & STB_TI_REF_ODDS_FLAG)
+    return stb_fail("%s: the object was created with STB_TI_REF_ODDS; the dish sweep has the exact weights only", who);
+  if (s->C != 0)
+    return stb_fail("%s: the object holds %llu customers of its own; the ladder's sweeps would move the held-out customers of a "
+                    "restaurant as if its own were exchangeable with them, which is not the conditional given their seating "
+                    "(only empty objects: unseen documents)", who, (unsigned long long)s->C);
+  if (!s->d_lik) return stb_fail("%s: the object has no likelihood (stb_tindic_set_lik): the prior alone has nothing to anneal to", who);
+  if (s->Mgiven == 0 && s->hmaxNi > 65535u)
+    return stb_fail("%s: a restaurant has %llu held-out customers and the object was created with M = 0; t is a uint16, so "
+                    "create it with M <= 65535", who, (unsigned long long)s->hmaxNi);
+  if (s->hmaxNi > 0x7fffffffull) return stb_fail("%s: a restaurant has %llu held-out customers", who, (unsigned long long)s->hmaxNi);
+  const ti_bounds tb = ti_table_bounds((unsigned)s->hmaxNi, s->Mgiven);
+  if (stb_seat_anneal_check(a, tb.N, tb.M, particles, S, betas, passes, s->I, who)) return 1;
+  if (info) memset(info, 0, sizeof(*info));
+  stb_device_scope dev(s->dev);
+  if (ti_ais_table(s, a, tb, who) || stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  const size_t ws_bytes = stb_seat_anneal_workspace_bytes(s->I, s->G, s->Hc, particles, s->lik_rows, s->lik_stride);
+  stb_pool_scratch sc(s->st);
+  double *d_lw = nullptr, *d_Hi = nullptr;
+  uint64_t *d_cnt = nullptr;
+  void *d_ws = nullptr;
+  if (sc.take(&d_lw, sizeof(double) * (size_t)s->I * particles) != hipSuccess ||
+      (Hi_host && sc.take(&d_Hi, sizeof(double) * (size_t)s->I) != hipSuccess) || sc.take(&d_cnt, 3 * sizeof(uint64_t)) != hipSuccess ||
+      sc.take(&d_ws, ws_bytes) != hipSuccess)
+    return stb_fail("%s: out of device memory for %d x %u replicas (%zu bytes of workspace: split the restaurants)", who, s->I,
+                    particles, ws_bytes);
+  if (hipMemsetAsync(d_cnt, 0, 3 * sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  if (stb_seat_anneal_launch(tb.need_table ? s->d_avt : nullptr, tb.N, tb.M, a, s->d_bpar, s->I, s->d_koff, s->d_h, s->d_hoff, s->d_hcls,
+                             s->d_lik, s->lik_rows, s->lik_stride, s->G, s->Hc, particles, S, betas, passes, seed, sweep, d_lw, nullptr,
+                             nullptr, nullptr, d_cnt, d_ws, ws_bytes, s->maxK, s->st, who))
+    return 1;
+  // k_seat_sum hands the three words on as they are: skipped, dead (in `impossible`'s place), stuck
+  stb_seat_info_t si;
+  if (stb_seat_sum(d_lw, s->I, particles, d_Hi, Hi_host, total, &si, d_cnt, s->st, who)) return sc.last(1);
+  if (info) {
+    info->skipped = si.skipped;
+    info->dead = si.impossible;
+    info->stuck = si.stuck;
     info->customers = s->Hc;
   }
   return sc.last(0);
