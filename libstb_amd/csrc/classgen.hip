@@ -136,16 +136,16 @@ size_t stb_cg_scratch_bytes(unsigned rows, unsigned stride) {
   return sizeof(double) * ((size_t)rows + cg_chunks(rows)) * stride;
 }
 
-int stb_cg_launch(const double *d_lik, unsigned rows, unsigned stride, const uint32_t *d_cust, const uint8_t *d_mask, uint64_t C,
-                  uint64_t seed, uint64_t sweep, uint32_t *d_cls, uint64_t *d_info, void *d_scratch, hipStream_t st,
-                  const char *who) {
+int stb_cg_launch(const stb_lik_view &L, const uint32_t *d_cust, const uint8_t *d_mask, uint64_t C, const stb_draw_key &k,
+                  uint32_t *d_cls, uint64_t *d_info, void *d_scratch, hipStream_t st, const char *who) {
   if (C == 0) return 0;
+  const unsigned rows = L.rows, stride = L.stride;
   const unsigned nw = cg_waves(), nchunks = cg_chunks(rows), cb = (stride + 63) / 64;
   double *pre = (double *)d_scratch, *ends = pre + (size_t)rows * stride;
   const uint64_t wanty = (nchunks + nw - 1) / nw, wantx = (C + 64 * nw - 1) / (64 * nw);
   const unsigned gy = wanty > 65535u ? 65535u : (unsigned)wanty, gx = wantx > CG_GRID_CAP ? CG_GRID_CAP : (unsigned)wantx;
-  const uint64_t key = stb_mix64(seed + (sweep + 1) * STB_GAMMA);
-  STB_LAUNCH(k_cls_pre, dim3(cb, gy), dim3(64 * nw), st, rows, stride, d_lik, pre, ends, nchunks);
+  const uint64_t key = stb_mix64(k.seed + (k.sweep + 1) * STB_GAMMA);
+  STB_LAUNCH(k_cls_pre, dim3(cb, gy), dim3(64 * nw), st, rows, stride, L.lik, pre, ends, nchunks);
   if (nchunks > 1) STB_LAUNCH(k_cls_base, dim3(cb), dim3(64), st, stride, ends, nchunks);
   STB_LAUNCH(k_cls_draw, dim3(gx), dim3(64 * nw), st, (const double *)pre, (const double *)ends, rows, stride, nchunks, d_cust,
              d_mask, C, key, d_cls, (unsigned long long *)d_info);
@@ -168,7 +168,7 @@ extern "C" int stb_sample_classes(const double *d_lik, unsigned rows, unsigned s
   void *d_scratch = nullptr;
   if (stb_pool_malloc(&d_scratch, stb_cg_scratch_bytes(rows, stride)) != hipSuccess)
     return stb_fail("%s: out of device memory for a %u x %u scratch", who, rows, stride);
-  int rc = stb_cg_launch(d_lik, rows, stride, d_cust, d_mask, C, seed, sweep, d_cls, d_info, d_scratch, st, who);
+  int rc = stb_cg_launch({d_lik, rows, stride}, d_cust, d_mask, C, {seed, sweep}, d_cls, d_info, d_scratch, st, who);
   // (the cache may hand the scratch on at once: the one wait)
   if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = STB_STREAM_FAIL(who);
   stb_pool_free(d_scratch);

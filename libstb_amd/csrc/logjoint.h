@@ -15,12 +15,11 @@ void stb_lj_release(void);
 #endif
 
 #if defined(__HIPCC__)
+#include "views.h"
 /* the checks stb_logjoint and the objects' calls share (0, or 1 with stb_last_error() set) */
 int stb_lj_check(double a, unsigned flags, int I, const char *who);
 /* the launch on st, the copy of d_Li to Li_host (when both are given) and the wait; arguments checked by the caller */
-int stb_lj_run(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
-               const uint64_t *d_koff, const uint32_t *d_n, const uint16_t *d_t, const uint32_t *d_T, const double *d_h,
-               unsigned flags, double *d_Li, double *Li_host, double *total_host, stb_logjoint_info_t *info, hipStream_t st,
-               const char *who);
+int stb_lj_run(const stb_table_view &S, const stb_rest_view &r, const stb_cnts_ro &c, unsigned flags, double *d_Li,
+               double *Li_host, double *total_host, stb_logjoint_info_t *info, hipStream_t st, const char *who);
 #endif
 #endif

@@ -254,10 +254,10 @@ int stb_lj_check(double a, unsigned flags, int I, const char *who) {
 }
 
 // one launch on st, the copy of d_Li to Li_host (when both are given), one wait; the arguments are checked by the caller
-int stb_lj_run(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
-               const uint64_t *d_koff, const uint32_t *d_n, const uint16_t *d_t, const uint32_t *d_T, const double *d_h,
-               unsigned flags, double *d_Li, double *Li_host, double *total_host, stb_logjoint_info_t *info, hipStream_t st,
-               const char *who) {
+int stb_lj_run(const stb_table_view &S, const stb_rest_view &r, const stb_cnts_ro &c, unsigned flags, double *d_Li,
+               double *Li_host, double *total_host, stb_logjoint_info_t *info, hipStream_t st, const char *who) {
+  const int I = r.I;
+  const double a = r.a;
   if (I == 0) {
     if (total_host) *total_host = 0.0;
     if (info) memset(info, 0, sizeof(*info));
@@ -270,8 +270,8 @@ int stb_lj_run(const double *d_table, const double *d_S1, unsigned N, unsigned M
   const unsigned nblk = tg.nblk, grid = tg.gx;
   const int nw = (int)tg.waves;
   HIPCHK(hipMemsetAsync(lj.d_ctl, 0, 64, st));
-  STB_LAUNCH(k_logjoint, dim3(grid), dim3(64 * nw), st, d_table, d_S1, N, M, a, a > 0.0 ? log(a) : 0.0, d_bpar, (uint64_t)I,
-             d_koff, d_n, d_t, d_T, d_h, flags, d_Li, (double *)lj.d_buf, nblk, lj.d_ctl, lj.h_out_dev);
+  STB_LAUNCH(k_logjoint, dim3(grid), dim3(64 * nw), st, S.tab, S.S1, S.N, S.M, a, a > 0.0 ? log(a) : 0.0, r.bpar,
+             (uint64_t)I, r.koff, c.n, c.t, c.T, r.h, flags, d_Li, (double *)lj.d_buf, nblk, lj.d_ctl, lj.h_out_dev);
   HIPCHK(hipGetLastError());
   if (d_Li && Li_host) HIPCHK(hipMemcpyAsync(Li_host, d_Li, sizeof(double) * (size_t)I, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -321,6 +321,7 @@ extern "C" int stb_logjoint(const double *d_table, const double *d_S1, unsigned 
   if (!d_koff || !d_n || !d_t) return stb_fail("stb_logjoint: the pair offsets, n and t are required");
   if (I > 0 && !d_bpar) return stb_fail("stb_logjoint: bpar is required");
   if (!total_host) return stb_fail("stb_logjoint: total_host is required");
-  return stb_lj_run(d_table, d_S1, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h, flags, d_Li, nullptr, total_host, info,
-                    (hipStream_t)stream, "stb_logjoint");
+  const stb_table_view S = {d_table, N, M, d_S1};
+  const stb_rest_view r = {a, d_bpar, I, d_koff, d_h};
+  return stb_lj_run(S, r, {d_n, d_t, d_T}, flags, d_Li, nullptr, total_host, info, (hipStream_t)stream, "stb_logjoint");
 }

@@ -199,16 +199,15 @@ static int pt_waves(void) {
   return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
 }
 
-int stb_pt_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, uint64_t G,
-                  const uint32_t *d_n, const uint16_t *d_t, uint32_t *d_cnt, unsigned S, uint16_t *d_sizes,
-                  const uint64_t *d_soff, unsigned flags, uint64_t seed, uint64_t sweep, hipStream_t st) {
-  HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * S, st));
+int stb_pt_launch(const stb_table_view &S, double a, uint64_t G, const stb_cnts_ro &c, uint32_t *d_cnt, unsigned Sh,
+                  unsigned flags, const stb_draw_key &k, hipStream_t st, uint16_t *d_sizes, const uint64_t *d_soff) {
+  HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * Sh, st));
   if (G == 0) return 0;
   const unsigned wpb = (unsigned)pt_waves();
   const uint64_t want = (G + wpb - 1) / wpb;
   const unsigned grid = want < STB_PT_GRID ? (unsigned)want : STB_PT_GRID;
-  STB_LAUNCH(k_partition, dim3(grid), dim3(64 * wpb), st, d_table, d_S1, N, M, a, G, d_n, d_t, d_cnt, S, d_sizes, d_soff,
-             flags, seed, sweep);
+  STB_LAUNCH(k_partition, dim3(grid), dim3(64 * wpb), st, S.tab, S.S1, S.N, S.M, a, G, c.n, c.t, d_cnt, Sh, d_sizes, d_soff,
+             flags, k.seed, k.sweep);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -230,6 +229,6 @@ extern "C" int stb_sample_partition(const double *d_table, const double *d_S1, u
   if (stb_pt_check(a, N, M, G, S, flags, "stb_sample_partition")) return 1;
   if (!d_cnt || (G && (!d_n || !d_t))) return stb_fail("stb_sample_partition: d_cnt, and d_n, d_t when G > 0, are required");
   if (!d_sizes != !d_soff) return stb_fail("stb_sample_partition: d_sizes and d_soff go together (both or neither)");
-  return stb_pt_launch(d_table, d_S1, N, M, a, G, d_n, d_t, d_cnt, S, d_sizes, d_soff, flags, seed, sweep,
-                       (hipStream_t)stream);
+  const stb_table_view tab = {d_table, N, M, d_S1};
+  return stb_pt_launch(tab, a, G, {d_n, d_t}, d_cnt, S, flags, {seed, sweep}, (hipStream_t)stream, d_sizes, d_soff);
 }

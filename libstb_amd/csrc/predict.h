@@ -15,13 +15,15 @@ void stb_pr_release(void);
 #endif
 
 #if defined(__HIPCC__)
+#include "views.h"
 /* the checks stb_predict_dishes and the object's calls share (0, or 1 with stb_last_error() set) */
 int stb_pr_check(double a, unsigned flags, int I, const char *who);
-/* k_predict on st, no wait; arguments checked by the caller */
-int stb_pr_predict(double a, const double *d_bpar, int I, const uint64_t *d_koff, const uint32_t *d_n, const uint16_t *d_t,
-                   const double *d_h, double *d_theta, unsigned tstride, const uint64_t *d_hoff, const uint32_t *d_hcls,
-                   const double *d_lik, unsigned rows, unsigned stride, double *d_p, unsigned flags, uint64_t *d_skipped,
-                   hipStream_t st, const char *who);
+/* what k_predict writes: the proportions (I x tstride), the held-out customers' p, one uint64 that is added to */
+struct stb_pr_out { double *theta = nullptr; unsigned tstride = 0; double *p = nullptr; uint64_t *skipped = nullptr; };
+/* k_predict on st, no wait; arguments checked by the caller.  held: the held-out customers' offsets and classes
+ * (stb_cust_ro{}: none), under L */
+int stb_pr_predict(const stb_rest_view &r, const stb_cnts_ro &c, const stb_cust_ro &held, const stb_lik_view &L,
+                   const stb_pr_out &out, unsigned flags, hipStream_t st, const char *who);
 /* k_heldout_sum on st, the copy of d_Hi to Hi_host (when both are given) and the wait; d_skipped (or NULL: 0) is a
  * device word whose value goes into info->skipped */
 int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned samples, double *d_Hi, double *Hi_host,

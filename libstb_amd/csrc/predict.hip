@@ -237,10 +237,9 @@ int stb_pr_check(double a, unsigned flags, int I, const char *who) {
   return 0;
 }
 
-int stb_pr_predict(double a, const double *d_bpar, int I, const uint64_t *d_koff, const uint32_t *d_n, const uint16_t *d_t,
-                   const double *d_h, double *d_theta, unsigned tstride, const uint64_t *d_hoff, const uint32_t *d_hcls,
-                   const double *d_lik, unsigned rows, unsigned stride, double *d_p, unsigned flags, uint64_t *d_skipped,
-                   hipStream_t st, const char *who) {
+int stb_pr_predict(const stb_rest_view &r, const stb_cnts_ro &c, const stb_cust_ro &held, const stb_lik_view &L,
+                   const stb_pr_out &out, unsigned flags, hipStream_t st, const char *who) {
+  const int I = r.I;
   if (I == 0) return 0;
   if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
   int nw = pr_env_waves();
@@ -248,9 +247,9 @@ int stb_pr_predict(double a, const double *d_bpar, int I, const uint64_t *d_koff
   const int cus = stb_cu_count();
   const uint64_t want = 32ull * (uint64_t)(cus > 0 ? cus : 1), groups = ((uint64_t)I + nw - 1) / nw;
   const unsigned grid = (unsigned)(groups < want ? groups : want);
-  STB_LAUNCH_SHM(k_predict, dim3(grid), dim3(64 * nw), sizeof(double) * STB_TD_MAXK * nw, st, a, d_bpar, (uint64_t)I, d_koff,
-                 d_n, d_t, d_h, d_theta, tstride, d_hoff, d_hcls, d_lik, rows, stride, d_p, flags,
-                 (unsigned long long *)d_skipped);
+  STB_LAUNCH_SHM(k_predict, dim3(grid), dim3(64 * nw), sizeof(double) * STB_TD_MAXK * nw, st, r.a, r.bpar, (uint64_t)I, r.koff,
+                 c.n, c.t, r.h, out.theta, out.tstride, held.off, held.cls, L.lik, L.rows, L.stride, out.p, flags,
+                 (unsigned long long *)out.skipped);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -296,8 +295,11 @@ extern "C" int stb_predict_dishes(double a, const double *d_bpar, int I, const u
   if (d_hoff && (!d_hcls || !d_p)) return stb_fail("%s: held-out offsets need their classes and p (d_hcls, d_p are required)", who);
   if (d_lik && (rows < 1 || stride < 1)) return stb_fail("%s: a likelihood of rows=%u stride=%u", who, rows, stride);
   if (d_theta && tstride < 1) return stb_fail("%s: theta with tstride=%u", who, tstride);
-  return stb_pr_predict(a, d_bpar, I, d_koff, d_n, d_t, d_h, d_theta, tstride, d_hoff, d_hcls, d_lik, rows, stride, d_p, flags,
-                        d_skipped, (hipStream_t)stream, who);
+  const stb_rest_view r = {a, d_bpar, I, d_koff, d_h};
+  const stb_cust_ro held = {d_hoff, d_hcls};
+  const stb_lik_view L = {d_lik, rows, stride};
+  const stb_pr_out out = {d_theta, tstride, d_p, d_skipped};
+  return stb_pr_predict(r, {d_n, d_t}, held, L, out, flags, (hipStream_t)stream, who);
 }
 
 extern "C" int stb_heldout_loglik(const double *d_p, const uint64_t *d_hoff, int I, unsigned samples, double *d_Hi,

@@ -265,41 +265,40 @@ int stb_seat_check(double a, unsigned M, unsigned particles, unsigned flags, int
   return 0;
 }
 
-int stb_seat_launch(double a, const double *d_bpar, int I, const uint64_t *d_koff, uint32_t *d_n, uint16_t *d_t, uint32_t *d_T,
-                    const double *d_h, unsigned M, const uint64_t *d_coff, const uint32_t *d_cls, uint32_t *d_cust,
-                    const double *d_lik, unsigned rows, unsigned stride, unsigned particles, unsigned flags, uint64_t seed,
-                    uint64_t sweep, double *d_lw, double *d_p, uint64_t *d_info, unsigned maxK, hipStream_t st, const char *who) {
-  if (I == 0) return 0;
+int stb_seat_launch(const stb_rest_view &r, const stb_cnts_rw &c, unsigned M, const stb_cust_rw &cu, const stb_lik_view &L,
+                    unsigned particles, unsigned flags, const stb_draw_key &k, const stb_seat_out &out, hipStream_t st,
+                    const char *who) {
+  if (r.I == 0) return 0;
   if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
   int nw = st_env_waves();
   if (!nw) nw = 4;
   const bool commit = (flags & STB_SEAT_COMMIT) != 0;
   seat_args A;
-  A.a = a;
-  A.bpar = d_bpar;
-  A.I = (uint64_t)I;
-  A.koff = d_koff;
-  A.nv = d_n;
-  A.tv = d_t;
-  A.Tv = commit ? d_T : nullptr;
-  A.hv = d_h;
+  A.a = r.a;
+  A.bpar = r.bpar;
+  A.I = (uint64_t)r.I;
+  A.koff = r.koff;
+  A.nv = c.n;
+  A.tv = c.t;
+  A.Tv = commit ? c.T : nullptr;
+  A.hv = r.h;
   A.M = M ? M : 65535u;
-  A.coff = d_coff;
-  A.cls = d_cls;
-  A.cust = d_cust;
-  A.lik = d_lik;
-  A.rows = rows;
-  A.stride = stride;
+  A.coff = cu.off;
+  A.cls = cu.cls;
+  A.cust = cu.cust;
+  A.lik = L.lik;
+  A.rows = L.rows;
+  A.stride = L.stride;
   A.R = particles;
   A.flags = flags;
-  A.seed = seed;
-  A.sweep = sweep;
-  A.lw = d_lw;
-  A.p = commit ? d_p : nullptr;
-  A.info = (unsigned long long *)d_info;
-  const uint64_t items = (uint64_t)I * particles, groups = (items + nw - 1) / nw;
+  A.seed = k.seed;
+  A.sweep = k.sweep;
+  A.lw = out.lw;
+  A.p = commit ? out.p : nullptr;
+  A.info = (unsigned long long *)out.info;
+  const uint64_t items = (uint64_t)r.I * particles, groups = (items + nw - 1) / nw;
   const unsigned grid = (unsigned)(groups < (1ull << 20) ? groups : (1ull << 20));
-  if (maxK >= 1 && maxK <= 64) {
+  if (r.maxK >= 1 && r.maxK <= 64) {
     STB_LAUNCH(k_seat<true>, dim3(grid), dim3(64 * nw), st, A);
   } else {
     STB_LAUNCH_SHM(k_seat<false>, dim3(grid), dim3(64 * nw), ST_LDS_WAVE * nw, st, A);
@@ -351,8 +350,11 @@ extern "C" int stb_seat_customers(double a, const double *d_bpar, int I, const u
   if (d_lik && (!d_cls || rows < 1 || stride < 1))
     return stb_fail("%s: a likelihood needs d_cls, rows >= 1 and stride >= 1 (rows=%u, stride=%u)", who, rows, stride);
   if ((flags & STB_SEAT_COMMIT) && (!d_T || !d_cust)) return stb_fail("%s: STB_SEAT_COMMIT writes d_T and d_cust (both are required)", who);
-  return stb_seat_launch(a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h, M, d_coff, d_cls, d_cust, d_lik, rows, stride, particles, flags,
-                         seed, sweep, d_lw, d_p, d_info, 0, (hipStream_t)stream, who);
+  const stb_rest_view r = {a, d_bpar, I, d_koff, d_h};
+  const stb_cnts_rw c = {d_n, d_t, d_T};
+  const stb_cust_rw cu = {d_coff, d_cls, d_cust};
+  const stb_lik_view L = {d_lik, rows, stride};
+  return stb_seat_launch(r, c, M, cu, L, particles, flags, {seed, sweep}, {d_lw, d_p, d_info}, (hipStream_t)stream, who);
 }
 
 extern "C" int stb_seat_loglik(const double *d_lw, int I, unsigned particles, double *d_Hi, double *total_host,

@@ -219,17 +219,16 @@ int stb_seat_anneal_check(double a, unsigned N, unsigned M, unsigned particles, 
   return 0;
 }
 
-int stb_seat_anneal_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I,
-                           const uint64_t *d_koff, const double *d_h, const uint64_t *d_coff, const uint32_t *d_cls,
-                           const double *d_lik, unsigned rows, unsigned stride, uint64_t G, uint64_t C, unsigned particles,
-                           unsigned S, const double *betas_host, unsigned passes, uint64_t seed, uint64_t sweep, double *d_lw,
-                           uint32_t *d_pn, uint16_t *d_pt, uint32_t *d_pcust, uint64_t *d_info, void *d_ws, size_t ws_bytes,
-                           unsigned maxK, hipStream_t st, const char *who) {
+int stb_seat_anneal_launch(const stb_table_view &V, const stb_rest_view &r, const stb_cust_ro &cu, const stb_lik_view &L,
+                           unsigned particles, const stb_ais_ladder &ld, const stb_draw_key &k, const stb_ais_out &out,
+                           void *d_ws, size_t ws_bytes, hipStream_t st, const char *who) {
+  const int I = r.I;
+  const unsigned S = ld.S, passes = ld.passes, maxK = r.maxK;
   if (I == 0) return 0;
   if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
   std::vector<double> beta;
-  if (ais_ladder(S, betas_host, &beta, who)) return 1;
-  const ais_plan p = ais_layout((uint64_t)I, G, C, particles, rows, stride);
+  if (ais_ladder(S, ld.betas_host, &beta, who)) return 1;
+  const ais_plan p = ais_layout((uint64_t)I, r.G, cu.C, particles, L.rows, L.stride);
   if (!d_ws || ws_bytes < p.bytes)
     return stb_fail("%s: the workspace holds %zu bytes, the call needs %zu (stb_seat_anneal_workspace_bytes)", who,
                     d_ws ? ws_bytes : (size_t)0, p.bytes);
@@ -238,56 +237,59 @@ int stb_seat_anneal_launch(const double *d_vt, unsigned N, unsigned M, double a,
   const unsigned tdcap = maxK == 0 || maxK > STB_TD_MAXK ? STB_TD_MAXK : maxK;
   ais_args A;
   A.I = (uint64_t)I;
-  A.G = G;
-  A.C = C;
+  A.G = r.G;
+  A.C = cu.C;
   A.R = particles;
-  A.rows = rows;
-  A.stride = stride;
-  A.N = N;
+  A.rows = L.rows;
+  A.stride = L.stride;
+  A.N = V.N;
   A.cap = tdcap <= 64 ? 64u : (tdcap + 63u) & ~63u;
-  A.koff = d_koff;
-  A.coff = d_coff;
-  A.bpar = d_bpar;
-  A.h = d_h;
-  A.lik = d_lik;
-  A.cls = d_cls;
+  A.koff = r.koff;
+  A.coff = cu.off;
+  A.bpar = r.bpar;
+  A.h = r.h;
+  A.lik = L.lik;
+  A.cls = cu.cls;
   A.koff2 = (uint64_t *)(ws + p.koff2);
   A.coff2 = (uint64_t *)(ws + p.coff2);
   A.bpar2 = (double *)(ws + p.bpar2);
-  A.h2 = d_h ? (double *)(ws + p.h2) : nullptr;
-  A.lw = d_lw;
-  A.n2 = d_pn ? d_pn : (uint32_t *)(ws + p.n2);
-  A.t2 = d_pt ? d_pt : (uint16_t *)(ws + p.t2);
-  A.cust2 = d_pcust ? d_pcust : (uint32_t *)(ws + p.cust2);
+  A.h2 = r.h ? (double *)(ws + p.h2) : nullptr;
+  A.lw = out.lw;
+  A.n2 = out.pn ? out.pn : (uint32_t *)(ws + p.n2);
+  A.t2 = out.pt ? out.pt : (uint16_t *)(ws + p.t2);
+  A.cust2 = out.pcust ? out.pcust : (uint32_t *)(ws + p.cust2);
   A.cls2 = (uint32_t *)(ws + p.cls2);
   A.skip = (unsigned char *)(ws + p.skip);
-  A.info = (unsigned long long *)d_info;
+  A.info = (unsigned long long *)out.info;
   unsigned long long *inner = (unsigned long long *)(ws + p.inner);
   A.inner = inner;
   double *d_tlik = (double *)(ws + p.tlik);
-  uint32_t *d_T2 = (uint32_t *)(ws + p.T2);
 
   const int nw = ais_waves();
   const uint64_t items = (uint64_t)I * particles, groups = (items + nw - 1) / nw;
   const unsigned grid = (unsigned)(groups < AIS_MAXGRID ? groups : AIS_MAXGRID);
-  const int I2 = (int)items;
+  // the replicated problem: I x particles restaurants, each with the pairs and the customers of its original.  (tdcap is
+  // at most 64 exactly when maxK is 1 .. 64: the seating takes its register form as it would under maxK)
+  const stb_rest_view r2 = {r.a, A.bpar2, (int)items, A.koff2, A.h2, tdcap};
+  const stb_cnts_rw c2 = {A.n2, A.t2, (uint32_t *)(ws + p.T2)};
+  const stb_cust_rw cu2 = {A.coff2, A.cls2, A.cust2};
   HIPCHK(hipMemsetAsync(inner, 0, sizeof(unsigned long long) * 8, st));
   STB_LAUNCH(k_ais_expand, dim3(grid), dim3(64 * nw), st, A);
   HIPCHK(hipGetLastError());
   // x_0 ~ prior: the committed seating of one particle a replica, no matrix.  Its own log weight is where lw starts: the
   // log of a product of sums of theta, 0 up to rounding -- but under a truncation M the sums fall short of 1 and the
   // seating is a weighted draw from the truncated prior (the header's statement), which is what the ladder needs
-  if (stb_seat_launch(a, A.bpar2, I2, A.koff2, A.n2, A.t2, d_T2, A.h2, M, A.coff2, nullptr, A.cust2, nullptr, 0, 0, 1,
-                      STB_SEAT_COMMIT, seed, sweep, d_lw, nullptr, (uint64_t *)inner, maxK, st, who))
+  // (without a matrix the seating reads no class)
+  if (stb_seat_launch(r2, c2, V.M, cu2, stb_lik_view{}, 1, STB_SEAT_COMMIT, k, {out.lw, nullptr, (uint64_t *)inner}, st, who))
     return 1;
+  const stb_lik_view tempered = {d_tlik, L.rows, L.stride};
   for (unsigned s = 1; s <= S; s++) {
     const double be = beta[s - 1], dbeta = be - (s >= 2 ? beta[s - 2] : 0.0);
-    if (s < S && ais_temper_launch(d_lik, rows, stride, be, d_tlik, st)) return 1;
+    if (s < S && ais_temper_launch(L.lik, L.rows, L.stride, be, d_tlik, st)) return 1;
     STB_LAUNCH(k_ais_weight, dim3(grid), dim3(64 * nw), st, A, dbeta, s == 1 ? 1 : 0, s == S ? 1 : 0);
     HIPCHK(hipGetLastError());
-    if (s < S && stb_td_launch(d_vt, N, M, a, A.bpar2, I2, A.koff2, A.n2, A.t2, d_T2, A.h2, A.coff2, A.cust2, A.cls2, d_tlik, rows,
-                               stride, seed, sweep + 1 + (uint64_t)(s - 1) * passes, (int)passes, tdcap, inner + 3, st))
-      return 1;
+    const stb_draw_key ks = {k.seed, k.sweep + 1 + (uint64_t)(s - 1) * passes};
+    if (s < S && stb_td_launch(V, r2, c2, cu2, tempered, ks, (int)passes, inner + 3, st)) return 1;
   }
   return 0;
 }
@@ -324,7 +326,13 @@ extern "C" int stb_seat_anneal(const double *d_vtable, unsigned N, unsigned M, d
   if (rows < 1 || stride < 1) return stb_fail("%s: a likelihood needs rows >= 1 and stride >= 1 (rows=%u, stride=%u)", who, rows, stride);
   if ((uint64_t)rows * stride > ((uint64_t)1 << 39)) return stb_fail("%s: %u x %u cells", who, rows, stride);
   if (!d_vtable && N >= 2 && M >= 2 && S >= 2) return stb_fail("%s: the V table is required (the sweeps read it)", who);
-  return stb_seat_anneal_launch(d_vtable, N, M, a, d_bpar, I, d_koff, d_h, d_coff, d_cls, d_lik, rows, stride, G, C, particles, S,
-                                betas_host, passes, seed, sweep, d_lw, d_pn, d_pt, d_pcust, d_info, d_ws, ws_bytes, 0,
+  const stb_table_view V = {d_vtable, N, M};
+  stb_rest_view r = {a, d_bpar, I, d_koff, d_h};
+  r.G = G;
+  stb_cust_ro cu = {d_coff, d_cls};
+  cu.C = C;
+  const stb_lik_view L = {d_lik, rows, stride};
+  const stb_ais_out out = {d_lw, d_info, d_pn, d_pt, d_pcust};
+  return stb_seat_anneal_launch(V, r, cu, L, particles, {S, betas_host, passes}, {seed, sweep}, out, d_ws, ws_bytes,
                                 (hipStream_t)stream, who);
 }

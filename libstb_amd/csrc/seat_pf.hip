@@ -255,12 +255,10 @@ int stb_seat_pf_check(double a, unsigned M, unsigned particles, double tau, int 
   return 0;
 }
 
-int stb_seat_pf_launch(double a, const double *d_bpar, int I, const uint64_t *d_koff, const uint32_t *d_n, const uint16_t *d_t,
-                       const double *d_h, unsigned M, const uint64_t *d_coff, const uint32_t *d_cls, const double *d_lik,
-                       unsigned rows, unsigned stride, unsigned particles, double tau, uint64_t seed, uint64_t sweep, double *d_Hi,
-                       double *d_w, int64_t *d_E, uint32_t *d_res, uint32_t *d_pn, uint16_t *d_pt, uint64_t *d_info, unsigned maxK,
-                       hipStream_t st, const char *who) {
-  if (I == 0) return 0;
+int stb_seat_pf_launch(const stb_rest_view &r, const stb_cnts_ro &c, unsigned M, const stb_cust_ro &cu, const stb_lik_view &L,
+                       unsigned particles, double tau, const stb_draw_key &k, const stb_pf_out &out, hipStream_t st,
+                       const char *who) {
+  if (r.I == 0) return 0;
   if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
   int nw = stb_env_int("STB_SEAT_WAVES", 0);
   if (!(nw == 1 || nw == 2 || nw == 4 || nw == 8)) {
@@ -270,40 +268,40 @@ int stb_seat_pf_launch(double a, const double *d_bpar, int I, const uint64_t *d_
     while (nw < 8 && 16u * (unsigned)nw < particles) nw *= 2;
   }
   seat_args A;
-  A.a = a;
-  A.bpar = d_bpar;
-  A.I = (uint64_t)I;
-  A.koff = d_koff;
-  A.nv = const_cast<uint32_t *>(d_n);  // (read only: the kernel stores to neither)
-  A.tv = const_cast<uint16_t *>(d_t);
+  A.a = r.a;
+  A.bpar = r.bpar;
+  A.I = (uint64_t)r.I;
+  A.koff = r.koff;
+  A.nv = const_cast<uint32_t *>(c.n);  // (read only: the kernel stores to neither)
+  A.tv = const_cast<uint16_t *>(c.t);
   A.Tv = nullptr;
-  A.hv = d_h;
+  A.hv = r.h;
   A.M = M ? M : 65535u;
-  A.coff = d_coff;
-  A.cls = d_cls;
+  A.coff = cu.off;
+  A.cls = cu.cls;
   A.cust = nullptr;
-  A.lik = d_lik;
-  A.rows = rows;
-  A.stride = stride;
+  A.lik = L.lik;
+  A.rows = L.rows;
+  A.stride = L.stride;
   A.R = particles;
   A.flags = 0;
-  A.seed = seed;
-  A.sweep = sweep;
+  A.seed = k.seed;
+  A.sweep = k.sweep;
   A.lw = nullptr;
   A.p = nullptr;
-  A.info = (unsigned long long *)d_info;
+  A.info = (unsigned long long *)out.info;
   pf_args P;
   P.tau = tau;
-  P.Hi = d_Hi;
-  P.w = d_w;
-  P.E = (long long *)d_E;
-  P.res = d_res;
-  P.pn = d_pn;
-  P.pt = d_pt;
+  P.Hi = out.Hi;
+  P.w = out.w;
+  P.E = (long long *)out.E;
+  P.res = out.res;
+  P.pn = out.pn;
+  P.pt = out.pt;
   // the largest K_i where the caller knows it and it fits: the launch takes what that needs; else the whole budget
   size_t shm = PF_LDS_DYN;
-  if (maxK >= 1 && particles <= pf_budget(maxK)) shm = (size_t)12u * particles * pf_kp(maxK);
-  const unsigned grid = (unsigned)((uint64_t)I < (1ull << 20) ? (uint64_t)I : (1ull << 20));
+  if (r.maxK >= 1 && particles <= pf_budget(r.maxK)) shm = (size_t)12u * particles * pf_kp(r.maxK);
+  const unsigned grid = (unsigned)((uint64_t)r.I < (1ull << 20) ? (uint64_t)r.I : (1ull << 20));
   STB_LAUNCH_SHM(k_seat_pf, dim3(grid), dim3(64 * nw), shm, st, A, P);
   HIPCHK(hipGetLastError());
   return 0;
@@ -322,6 +320,9 @@ extern "C" int stb_seat_filter(double a, const double *d_bpar, int I, const uint
   if (!d_Hi) return stb_fail("%s: d_Hi is required", who);
   if (d_lik && (!d_cls || rows < 1 || stride < 1))
     return stb_fail("%s: a likelihood needs d_cls, rows >= 1 and stride >= 1 (rows=%u, stride=%u)", who, rows, stride);
-  return stb_seat_pf_launch(a, d_bpar, I, d_koff, d_n, d_t, d_h, M, d_coff, d_cls, d_lik, rows, stride, particles, tau, seed, sweep,
-                            d_Hi, d_w, d_E, d_res, d_pn, d_pt, d_info, 0, (hipStream_t)stream, who);
+  const stb_rest_view r = {a, d_bpar, I, d_koff, d_h};
+  const stb_cust_ro cu = {d_coff, d_cls};
+  const stb_lik_view L = {d_lik, rows, stride};
+  const stb_pf_out out = {d_Hi, d_info, d_w, d_E, d_res, d_pn, d_pt};
+  return stb_seat_pf_launch(r, {d_n, d_t}, M, cu, L, particles, tau, {seed, sweep}, out, (hipStream_t)stream, who);
 }

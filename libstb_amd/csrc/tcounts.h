@@ -4,6 +4,7 @@
 
 #include "stb_common.h"
 #include "uniforms.h"
+#include "views.h"
 
 // S_S(n, tau) for 1 <= tau <= min(n, M): dev_S_S of sweep_terms.hip for the cells a draw can address
 // (n <= N: the kernels leave pairs with n > N alone)
@@ -13,25 +14,24 @@ __device__ __forceinline__ double tc_S(const double *row, const double *S1, unsi
   return row[tau - 2];
 }
 
-// the sweep's launch (tcounts.hip): nsweeps sweeps from `sweep` on, tau_max = the longest tau range a pair can have (sizes
+// the sweep's launch (tcounts.hip): nsweeps sweeps from k.sweep on, tau_max = the longest tau range a pair can have (sizes
 // the LDS row); the arguments are checked by the caller
-int stb_tc_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
-                  const uint64_t *d_koff, const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, uint64_t seed,
-                  uint64_t sweep, int nsweeps, unsigned tau_max, hipStream_t st);
+int stb_tc_launch(const stb_table_view &S, const stb_rest_view &r, const stb_cnts_tT &c, const stb_draw_key &k, int nsweeps,
+                  unsigned tau_max, hipStream_t st);
 
 #define STB_TC_REF_WINDOW_FLAG 1u
 
 // nsweeps windowed sweeps (include/stb_hip.h, stb_sample_tcounts_window); the arguments are checked by the caller
-int stb_tcw_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
-                   const uint64_t *d_koff, const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, unsigned W,
-                   unsigned flags, uint64_t seed, uint64_t sweep, int nsweeps, hipStream_t st);
+int stb_tcw_launch(const stb_table_view &S, const stb_rest_view &r, const stb_cnts_tT &c, unsigned W, unsigned flags,
+                   const stb_draw_key &k, int nsweeps, hipStream_t st);
 
 #define STB_PT_REF_WALK_FLAG 1u
 
-// the partition draw (partition.hip, include/stb_hip.h stb_sample_partition): zeroes cnt[S] on st, then fills it
-int stb_pt_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, uint64_t G,
-                  const uint32_t *d_n, const uint16_t *d_t, uint32_t *d_cnt, unsigned S, uint16_t *d_sizes,
-                  const uint64_t *d_soff, unsigned flags, uint64_t seed, uint64_t sweep, hipStream_t st);
+// the partition draw (partition.hip, include/stb_hip.h stb_sample_partition): zeroes cnt[S] on st, then fills it from the
+// G pairs' n and t; d_sizes and d_soff go together
+int stb_pt_launch(const stb_table_view &S, double a, uint64_t G, const stb_cnts_ro &c, uint32_t *d_cnt, unsigned Sh,
+                  unsigned flags, const stb_draw_key &k, hipStream_t st, uint16_t *d_sizes = nullptr,
+                  const uint64_t *d_soff = nullptr);
 // the checks of the raw call that the object's call shares (0, or 1 with stb_last_error() set)
 int stb_pt_check(double a, unsigned N, unsigned M, uint64_t G, unsigned S, unsigned flags, const char *who);
 

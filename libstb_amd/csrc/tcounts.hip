@@ -185,15 +185,14 @@ static int tc_threads(void) {
   return (v == 64 || v == 128 || v == 256 || v == 512 || v == 1024) ? v : 256;
 }
 
-int stb_tc_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
-                  const uint64_t *d_koff, const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, uint64_t seed,
-                  uint64_t sweep, int nsweeps, unsigned tau_max, hipStream_t st) {
-  if (I <= 0 || nsweeps <= 0) return 0;
+int stb_tc_launch(const stb_table_view &S, const stb_rest_view &r, const stb_cnts_tT &c, const stb_draw_key &k, int nsweeps,
+                  unsigned tau_max, hipStream_t st) {
+  if (r.I <= 0 || nsweeps <= 0) return 0;
   const int nt = tc_threads();
   unsigned cap = tau_max < STB_TC_CAP ? tau_max : STB_TC_CAP;
   if (cap < 1) cap = 1;
-  STB_LAUNCH_SHM(k_tcounts, dim3((unsigned)I), dim3(nt), sizeof(double) * cap, st, d_table, d_S1, N, M, a, d_bpar, I, d_koff,
-                 d_n, d_t, d_T, d_h, seed, sweep, nsweeps, cap);
+  STB_LAUNCH_SHM(k_tcounts, dim3((unsigned)r.I), dim3(nt), sizeof(double) * cap, st, S.tab, S.S1, S.N, S.M, r.a, r.bpar, r.I,
+                 r.koff, c.n, c.t, c.T, r.h, k.seed, k.sweep, nsweeps, cap);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -205,6 +204,8 @@ extern "C" int stb_sample_tcounts(const double *d_table, const double *d_S1, uns
   if (!(a >= 0.0 && a < 1.0)) return stb_fail("stb_sample_tcounts: discount a=%g outside [0, 1)", a);
   if (N < 1 || M < 1) return stb_fail("stb_sample_tcounts: table bounds N=%u M=%u", N, M);
   if (I < 0) return stb_fail("stb_sample_tcounts: I=%d", I);
-  return stb_tc_launch(d_table, d_S1, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h, seed, sweep, 1, N < M ? N : M,
-                       (hipStream_t)stream);
+  const stb_table_view S = {d_table, N, M, d_S1};
+  const stb_rest_view r = {a, d_bpar, I, d_koff, d_h};
+  const stb_cnts_tT c = {d_n, d_t, d_T};
+  return stb_tc_launch(S, r, c, {seed, sweep}, 1, N < M ? N : M, (hipStream_t)stream);
 }

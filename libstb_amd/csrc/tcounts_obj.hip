@@ -45,6 +45,11 @@ static int tc_check_h(const double *h, uint64_t G, const char *who) {
   return 0;
 }
 
+// the object's state as the launches take it (views.h)
+static stb_table_view tc_table(const stb_tcounts_t *s) { return {s->d_table, s->N, s->M, s->d_S1}; }
+static stb_rest_view tc_rest(const stb_tcounts_t *s, double a) { return {a, s->d_bpar, s->I, s->d_koff, s->d_h}; }
+static stb_cnts_tT tc_counts(const stb_tcounts_t *s) { return {s->d_n, s->d_t, s->d_T}; }
+
 // what every sweep of the object checks before anything changes: a failure leaves the state as it was
 static int tc_check_sweep(stb_tcounts_t *s, double a, const double *bpar, int nsweeps, const char *who) {
   if (!s) return stb_fail("%s: null object", who);
@@ -275,8 +280,7 @@ extern "C" int stb_tcounts_sweep(stb_tcounts_t *s, double a, const double *bpar,
   if (nsweeps == 0) return 0;
   stb_device_scope dev(s->dev);
   if (tc_stage(s, a, bpar, who)) return 1;
-  return stb_tc_launch(s->d_table, s->d_S1, s->N, s->M, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, seed, sweep,
-                       nsweeps, s->maxn < s->M ? s->maxn : s->M, s->st);
+  return stb_tc_launch(tc_table(s), tc_rest(s, a), tc_counts(s), {seed, sweep}, nsweeps, s->maxn < s->M ? s->maxn : s->M, s->st);
 }
 
 // the windowed sweep (tcwin.hip) on the same object: the same table, concentrations, stream and checks
@@ -290,8 +294,7 @@ extern "C" int stb_tcounts_sweep_window(stb_tcounts_t *s, double a, const double
   if (nsweeps == 0) return 0;
   stb_device_scope dev(s->dev);
   if (tc_stage(s, a, bpar, who)) return 1;
-  return stb_tcw_launch(s->d_table, s->d_S1, s->N, s->M, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, W, flags,
-                        seed, sweep, nsweeps, s->st);
+  return stb_tcw_launch(tc_table(s), tc_rest(s, a), tc_counts(s), W, flags, {seed, sweep}, nsweeps, s->st);
 }
 
 extern "C" int stb_tcounts_set_bgroups(stb_tcounts_t *s, int G, const uint64_t *goff_host) {
@@ -359,8 +362,7 @@ extern "C" int stb_tcounts_partition(stb_tcounts_t *s, double a, stb_hist_t *h, 
   if (hipEventCreateWithFlags(&ev.ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev.ev, v.st) != hipSuccess ||
       hipStreamWaitEvent(s->st, ev.ev, 0) != hipSuccess)
     return STB_STREAM_FAIL(who);
-  if (stb_pt_launch(s->d_table, s->d_S1, s->N, s->M, a, s->G, s->d_n, s->d_t, v.d_cnt, v.S, nullptr, nullptr, 0u, seed, sweep, s->st))
-    return 1;
+  if (stb_pt_launch(tc_table(s), a, s->G, tc_counts(s), v.d_cnt, v.S, 0u, {seed, sweep}, s->st)) return 1;
   if (hipMemcpyAsync(v.d_T, s->d_T, sizeof(uint32_t) * s->I, hipMemcpyDeviceToDevice, s->st) != hipSuccess ||
       hipMemcpyAsync(v.d_bpar, s->d_bpar, sizeof(double) * s->I, hipMemcpyDeviceToDevice, s->st) != hipSuccess ||
       hipEventRecord(ev.ev, s->st) != hipSuccess || hipStreamWaitEvent(v.st, ev.ev, 0) != hipSuccess)
@@ -385,6 +387,5 @@ extern "C" int stb_tcounts_logjoint(stb_tcounts_t *s, double a, const double *bp
   if (Li_host && sc.take(&d_Li, sizeof(double) * (size_t)s->I) != hipSuccess)
     return stb_fail("%s: out of device memory for %d values", who, s->I);
   // (a run that succeeded has waited for its own answer: the buffer goes back without a second wait)
-  return sc.last(stb_lj_run(s->d_table, s->d_S1, s->N, s->M, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, flags,
-                            d_Li, Li_host, total, info, s->st, who));
+  return sc.last(stb_lj_run(tc_table(s), tc_rest(s, a), tc_counts(s), flags, d_Li, Li_host, total, info, s->st, who));
 }

@@ -263,13 +263,12 @@ static int tcw_waves(void) {
   return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
 }
 
-int stb_tcw_launch(const double *d_table, const double *d_S1, unsigned N, unsigned M, double a, const double *d_bpar, int I,
-                   const uint64_t *d_koff, const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, unsigned W,
-                   unsigned flags, uint64_t seed, uint64_t sweep, int nsweeps, hipStream_t st) {
-  if (I <= 0 || nsweeps <= 0) return 0;
+int stb_tcw_launch(const stb_table_view &S, const stb_rest_view &r, const stb_cnts_tT &c, unsigned W, unsigned flags,
+                   const stb_draw_key &k, int nsweeps, hipStream_t st) {
+  if (r.I <= 0 || nsweeps <= 0) return 0;
   const int wpb = tcw_waves();
-  STB_LAUNCH(k_tcwin, dim3((unsigned)((I + wpb - 1) / wpb)), dim3(64 * wpb), st, d_table, d_S1, N, M, a, d_bpar, I, d_koff,
-             d_n, d_t, d_T, d_h, W, flags, seed, sweep, nsweeps);
+  STB_LAUNCH(k_tcwin, dim3((unsigned)((r.I + wpb - 1) / wpb)), dim3(64 * wpb), st, S.tab, S.S1, S.N, S.M, r.a, r.bpar, r.I,
+             r.koff, c.n, c.t, c.T, r.h, W, flags, k.seed, k.sweep, nsweeps);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -285,6 +284,8 @@ extern "C" int stb_sample_tcounts_window(const double *d_table, const double *d_
   if (W == 0) return stb_fail("stb_sample_tcounts_window: window W=0 (must be >= 1)");
   if (flags & ~STB_TC_REF_WINDOW_FLAG) return stb_fail("stb_sample_tcounts_window: unknown flags 0x%x", flags);
   if (I < 0) return stb_fail("stb_sample_tcounts_window: I=%d", I);
-  return stb_tcw_launch(d_table, d_S1, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h, W, flags, seed, sweep, 1,
-                        (hipStream_t)stream);
+  const stb_table_view S = {d_table, N, M, d_S1};
+  const stb_rest_view r = {a, d_bpar, I, d_koff, d_h};
+  const stb_cnts_tT c = {d_n, d_t, d_T};
+  return stb_tcw_launch(S, r, c, W, flags, {seed, sweep}, 1, (hipStream_t)stream);
 }

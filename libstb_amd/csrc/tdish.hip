@@ -251,29 +251,28 @@ __global__ __launch_bounds__(256) void k_td_class_counts(const uint32_t *cust, c
   if (r < rows && k < stride) atomicAdd(&cnt[(uint64_t)r * stride + k], 1u);
 }
 
-int stb_td_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I, const uint64_t *d_koff,
-                  uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, const uint64_t *d_coff, uint32_t *d_cust,
-                  const uint32_t *d_cls, const double *d_lik, unsigned rows, unsigned stride, uint64_t seed, uint64_t sweep,
-                  int nsweeps, unsigned cap, unsigned long long *d_info, hipStream_t st) {
+int stb_td_launch(const stb_table_view &V, const stb_rest_view &r, const stb_cnts_rw &c, const stb_cust_rw &cu,
+                  const stb_lik_view &L, const stb_draw_key &k, int nsweeps, unsigned long long *d_info, hipStream_t st) {
+  const int I = r.I;
   if (I <= 0 || nsweeps <= 0) return 0;
+  unsigned cap = r.maxK;
   if (cap > STB_TD_MAXK) cap = STB_TD_MAXK;
   if (cap <= 64) {
-    STB_LAUNCH(k_tdish<true>, dim3((unsigned)I), dim3(64), st, d_vt, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h, d_coff,
-               d_cust, d_cls, d_lik, rows, stride, seed, sweep, nsweeps, 64u, d_info);
+    STB_LAUNCH(k_tdish<true>, dim3((unsigned)I), dim3(64), st, V.tab, V.N, V.M, r.a, r.bpar, I, r.koff, c.n, c.t, c.T, r.h,
+               cu.off, cu.cust, cu.cls, L.lik, L.rows, L.stride, k.seed, k.sweep, nsweeps, 64u, d_info);
   } else {
     cap = (cap + 63u) & ~63u;
     const size_t shm = (size_t)cap * (3 * sizeof(double) + sizeof(uint32_t) + sizeof(uint16_t));
-    STB_LAUNCH_SHM(k_tdish<false>, dim3((unsigned)I), dim3(64), shm, st, d_vt, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h,
-                   d_coff, d_cust, d_cls, d_lik, rows, stride, seed, sweep, nsweeps, cap, d_info);
+    STB_LAUNCH_SHM(k_tdish<false>, dim3((unsigned)I), dim3(64), shm, st, V.tab, V.N, V.M, r.a, r.bpar, I, r.koff, c.n, c.t, c.T,
+                   r.h, cu.off, cu.cust, cu.cls, L.lik, L.rows, L.stride, k.seed, k.sweep, nsweeps, cap, d_info);
   }
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-int stb_td_class_counts(const uint32_t *d_cust, const uint32_t *d_cls, uint64_t C, unsigned rows, unsigned stride,
-                        uint32_t *d_cnt, hipStream_t st) {
-  if (C == 0) return 0;
-  STB_LAUNCH(k_td_class_counts, dim3((unsigned)((C + 255) / 256)), dim3(256), st, d_cust, d_cls, C, rows, stride, d_cnt);
+int stb_td_class_counts(const stb_cust_ro &cu, unsigned rows, unsigned stride, uint32_t *d_cnt, hipStream_t st) {
+  if (cu.C == 0) return 0;
+  STB_LAUNCH(k_td_class_counts, dim3((unsigned)((cu.C + 255) / 256)), dim3(256), st, cu.cust, cu.cls, cu.C, rows, stride, d_cnt);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -292,6 +291,10 @@ extern "C" int stb_sample_tdishes(const double *d_vtable, unsigned N, unsigned M
   if (!d_bpar || !d_koff || !d_n || !d_t || !d_T || !d_coff) return stb_fail("%s: bpar, koff, n, t, T and coff are required", who);
   if (d_lik && (!d_cls || rows < 1 || stride < 1))
     return stb_fail("%s: a likelihood needs d_cls, rows >= 1 and stride >= 1 (rows=%u, stride=%u)", who, rows, stride);
-  return stb_td_launch(d_vtable, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h, d_coff, d_cust, d_cls, d_lik, rows, stride, seed,
-                       sweep, 1, STB_TD_MAXK, (unsigned long long *)d_info, (hipStream_t)stream);
+  const stb_table_view V = {d_vtable, N, M};
+  const stb_rest_view r = {a, d_bpar, I, d_koff, d_h, STB_TD_MAXK};
+  const stb_cnts_rw c = {d_n, d_t, d_T};
+  const stb_cust_rw cu = {d_coff, d_cls, d_cust};
+  const stb_lik_view L = {d_lik, rows, stride};
+  return stb_td_launch(V, r, c, cu, L, {seed, sweep}, 1, (unsigned long long *)d_info, (hipStream_t)stream);
 }

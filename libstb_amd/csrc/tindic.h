@@ -5,6 +5,7 @@
 #define STB_TINDIC_H
 
 #include "stb_common.h"
+#include "views.h"
 #include "uniforms.h"  // u1 of customer c is element j = 2c+1 of the sweep's stream, u2 is j = 2c+2
 
 #define STB_TI_REF_ODDS_FLAG 1u
@@ -41,19 +42,15 @@ __device__ __forceinline__ double ti_rld(double v, unsigned j) {
   return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
-// the indicator sweep's launch (tindic.hip): nsweeps sweeps from `sweep` on, cap = dishes a wave keeps in LDS
-int stb_ti_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I, const uint64_t *d_koff,
-                  const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, const uint64_t *d_coff,
-                  const uint32_t *d_cust, unsigned flags, uint64_t seed, uint64_t sweep, int nsweeps, unsigned cap,
-                  hipStream_t st);
-// the dish sweep's launch (tdish.hip): nsweeps sweeps from `sweep` on, cap = dishes a wave holds (the largest K_i, at most
-// STB_TD_MAXK); d_info: two uint64 (skipped, stuck), added to
-int stb_td_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I, const uint64_t *d_koff,
-                  uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, const uint64_t *d_coff, uint32_t *d_cust,
-                  const uint32_t *d_cls, const double *d_lik, unsigned rows, unsigned stride, uint64_t seed, uint64_t sweep,
-                  int nsweeps, unsigned cap, unsigned long long *d_info, hipStream_t st);
-// customers per (class, dish): cnt[rows x stride] += 1 at (cls[c], cust[c]) for c < C
-int stb_td_class_counts(const uint32_t *d_cust, const uint32_t *d_cls, uint64_t C, unsigned rows, unsigned stride,
-                        uint32_t *d_cnt, hipStream_t st);
+// the indicator sweep's launch (tindic.hip): nsweeps sweeps from k.sweep on; r.maxK = dishes a wave keeps in LDS; of cu the
+// offsets and the dishes are read
+int stb_ti_launch(const stb_table_view &V, const stb_rest_view &r, const stb_cnts_tT &c, const stb_cust_ro &cu, unsigned flags,
+                  const stb_draw_key &k, int nsweeps, hipStream_t st);
+// the dish sweep's launch (tdish.hip): nsweeps sweeps from k.sweep on; r.maxK = dishes a wave holds (the largest K_i, at
+// most STB_TD_MAXK); d_info: two uint64 (skipped, stuck), added to
+int stb_td_launch(const stb_table_view &V, const stb_rest_view &r, const stb_cnts_rw &c, const stb_cust_rw &cu,
+                  const stb_lik_view &L, const stb_draw_key &k, int nsweeps, unsigned long long *d_info, hipStream_t st);
+// customers per (class, dish): cnt[rows x stride] += 1 at (cu.cls[c], cu.cust[c]) for c < cu.C
+int stb_td_class_counts(const stb_cust_ro &cu, unsigned rows, unsigned stride, uint32_t *d_cnt, hipStream_t st);
 
 #endif

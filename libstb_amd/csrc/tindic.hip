@@ -183,20 +183,20 @@ static int ti_form(int I) {
   return I < STB_TI_WAVE_BELOW ? 1 : 0;
 }
 
-// cap: dishes a wave keeps in LDS (the largest K_i when it is known and smaller than STB_TI_LDS_CAP)
-int stb_ti_launch(const double *d_vt, unsigned N, unsigned M, double a, const double *d_bpar, int I, const uint64_t *d_koff,
-                  const uint32_t *d_n, uint16_t *d_t, uint32_t *d_T, const double *d_h, const uint64_t *d_coff,
-                  const uint32_t *d_cust, unsigned flags, uint64_t seed, uint64_t sweep, int nsweeps, unsigned cap,
-                  hipStream_t st) {
+// r.maxK: dishes a wave keeps in LDS (the largest K_i when it is known and smaller than STB_TI_LDS_CAP)
+int stb_ti_launch(const stb_table_view &V, const stb_rest_view &r, const stb_cnts_tT &c, const stb_cust_ro &cu, unsigned flags,
+                  const stb_draw_key &k, int nsweeps, hipStream_t st) {
+  const int I = r.I;
   if (I <= 0 || nsweeps <= 0) return 0;
   if (ti_form(I) == 0) {
-    STB_LAUNCH(k_tindic_lane, dim3((unsigned)((I + 63) / 64)), dim3(64), st, d_vt, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T,
-               d_h, d_coff, d_cust, flags, seed, sweep, nsweeps);
+    STB_LAUNCH(k_tindic_lane, dim3((unsigned)((I + 63) / 64)), dim3(64), st, V.tab, V.N, V.M, r.a, r.bpar, I, r.koff, c.n, c.t,
+               c.T, r.h, cu.off, cu.cust, flags, k.seed, k.sweep, nsweeps);
   } else {
+    unsigned cap = r.maxK;
     if (cap > STB_TI_LDS_CAP) cap = STB_TI_LDS_CAP;
-    if (!d_cust) cap = 0;
-    STB_LAUNCH_SHM(k_tindic_wave, dim3((unsigned)I), dim3(64), sizeof(uint16_t) * (cap ? cap : 1), st, d_vt, N, M, a, d_bpar,
-                   I, d_koff, d_n, d_t, d_T, d_h, d_coff, d_cust, flags, seed, sweep, nsweeps, cap);
+    if (!cu.cust) cap = 0;
+    STB_LAUNCH_SHM(k_tindic_wave, dim3((unsigned)I), dim3(64), sizeof(uint16_t) * (cap ? cap : 1), st, V.tab, V.N, V.M, r.a,
+                   r.bpar, I, r.koff, c.n, c.t, c.T, r.h, cu.off, cu.cust, flags, k.seed, k.sweep, nsweeps, cap);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -212,6 +212,9 @@ extern "C" int stb_sample_tindic(const double *d_vtable, unsigned N, unsigned M,
   if (M > 65535u) return stb_fail("stb_sample_tindic: M=%u (t is a uint16: at most 65535)", M);
   if (flags & ~STB_TI_REF_ODDS_FLAG) return stb_fail("stb_sample_tindic: unknown flags 0x%x", flags);
   if (I < 0) return stb_fail("stb_sample_tindic: I=%d", I);
-  return stb_ti_launch(d_vtable, N, M, a, d_bpar, I, d_koff, d_n, d_t, d_T, d_h, d_coff, d_cust, flags, seed, sweep, 1,
-                       STB_TI_LDS_CAP, (hipStream_t)stream);
+  const stb_table_view V = {d_vtable, N, M};
+  const stb_rest_view r = {a, d_bpar, I, d_koff, d_h, STB_TI_LDS_CAP};
+  const stb_cnts_tT c = {d_n, d_t, d_T};
+  const stb_cust_ro cu = {d_coff, nullptr, d_cust};
+  return stb_ti_launch(V, r, c, cu, flags, {seed, sweep}, 1, (hipStream_t)stream);
 }

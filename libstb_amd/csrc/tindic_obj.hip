@@ -135,6 +135,19 @@ static ti_bounds ti_table_bounds(unsigned maxn, unsigned Mgiven) {
   return b;
 }
 
+// ---- the object's state as the launches take it (views.h).  Customers: the object's own (lik false: without their classes,
+// for a launch under no matrix), the held-out ones.  Tables: the sweeps' V, the log joint's S, the anneal ladder's V
+static stb_rest_view ti_rest(const stb_tindic_t *s, double a, bool with_h = true) {
+  return {a, s->d_bpar, s->I, s->d_koff, with_h ? s->d_h : nullptr, s->maxK, s->G};
+}
+static stb_cnts_rw ti_counts(const stb_tindic_t *s) { return {s->d_n, s->d_t, s->d_T}; }
+static stb_lik_view ti_matrix(const stb_tindic_t *s) { return {s->d_lik, s->lik_rows, s->lik_stride}; }
+static stb_cust_rw ti_customers(const stb_tindic_t *s, bool lik = true) { return {s->d_coff, lik ? s->d_cls : nullptr, s->d_cust, s->C}; }
+static stb_cust_rw ti_heldout(const stb_tindic_t *s) { return {s->d_hoff, s->d_hcls, nullptr, s->Hc}; }
+static stb_table_view ti_vtable(const stb_tindic_t *s) { return {s->d_vt, s->N, s->need_table ? s->M : s->Mdraw}; }
+static stb_table_view ti_stable(const stb_tindic_t *s) { return {s->d_stab, s->N, s->need_table ? s->M : s->Mdraw, s->d_sS1}; }
+static stb_table_view ti_atable(const stb_tindic_t *s, const ti_bounds &tb) { return {tb.need_table ? s->d_avt : nullptr, tb.N, tb.M}; }
+
 // the S slab back to the buffer cache (the caller has waited for whatever reads it)
 static void ti_drop_sslab(stb_tindic_t *s) {
   void *pooled[] = {s->d_stab, s->d_sS1, s->d_sws};
@@ -411,8 +424,7 @@ extern "C" int stb_tindic_sweep(stb_tindic_t *s, double a, const double *bpar, u
   if (nsweeps == 0) return 0;
   stb_device_scope dev(s->dev);
   if (ti_ensure_V(s, a) || stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
-  return stb_ti_launch(s->d_vt, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T,
-                       s->d_h, s->d_coff, s->d_cust, s->flags, seed, sweep, nsweeps, s->maxK, s->st);
+  return stb_ti_launch(ti_vtable(s), ti_rest(s, a), ti_counts(s), ti_customers(s), s->flags, {seed, sweep}, nsweeps, s->st);
 }
 
 extern "C" int stb_tindic_set_bgroups(stb_tindic_t *s, int G, const uint64_t *goff_host) {
@@ -625,9 +637,7 @@ extern "C" int stb_tindic_sweep_dishes(stb_tindic_t *s, double a, const double *
   stb_device_scope dev(s->dev);
   if (ti_dish_prepare(s, who) || ti_ensure_V(s, a) || stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
   if (hipMemsetAsync(s->d_info, 0, 2 * sizeof(unsigned long long), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
-  if (stb_td_launch(s->d_vt, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h,
-                    s->d_coff, s->d_cust, s->d_cls, s->d_lik, s->lik_rows, s->lik_stride, seed, sweep, nsweeps, s->maxK, s->d_info,
-                    s->st))
+  if (stb_td_launch(ti_vtable(s), ti_rest(s, a), ti_counts(s), ti_customers(s), ti_matrix(s), {seed, sweep}, nsweeps, s->d_info, s->st))
     return 1;
   if (!info) return 0;
   if (ti_fetch(s, {{s->h_info, s->d_info, 2 * sizeof(unsigned long long)}}, who)) return 1;
@@ -658,7 +668,7 @@ extern "C" int stb_tindic_class_counts(stb_tindic_t *s, uint32_t *cnt_out) {
   uint32_t *d_cnt = nullptr;
   if (sc.take(&d_cnt, bytes) != hipSuccess) return stb_fail("%s: out of device memory", who);
   if (hipMemsetAsync(d_cnt, 0, bytes, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
-  if (stb_td_class_counts(s->d_cust, s->d_cls, s->C, rows, stride, d_cnt, s->st)) return 1;
+  if (stb_td_class_counts(ti_customers(s), rows, stride, d_cnt, s->st)) return 1;
   if (hipMemcpyAsync(cnt_out, d_cnt, bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   return sc.give_back(true, who);
 }
@@ -681,7 +691,7 @@ static int ti_count_classes(stb_tindic_t *s, stb_pool_scratch &sc, uint32_t **d_
   if (ti_materialise_cust(s, who)) return 1;
   if (sc.take(d_cnt, bytes) != hipSuccess) return stb_fail("%s: out of device memory for the counts", who);
   if (hipMemsetAsync(*d_cnt, 0, bytes, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
-  return stb_td_class_counts(s->d_cust, s->d_cls, s->C, s->lik_rows, s->lik_stride, *d_cnt, s->st);
+  return stb_td_class_counts(ti_customers(s), s->lik_rows, s->lik_stride, *d_cnt, s->st);
 }
 
 extern "C" int stb_tindic_sample_lik(stb_tindic_t *s, const double *beta_host, double beta0, uint64_t seed, uint64_t sweep) {
@@ -908,8 +918,7 @@ static int ti_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned f
   double *d_Li = nullptr;
   if (Li_host && sc.take(&d_Li, sizeof(double) * (size_t)s->I) != hipSuccess)
     return stb_fail("%s: out of device memory for %d values", who, s->I);
-  return sc.last(stb_lj_run(s->d_stab, s->d_sS1, s->N, s->need_table ? s->M : s->Mdraw, a, s->d_bpar, s->I, s->d_koff, s->d_n,
-                            s->d_t, s->d_T, with_h ? s->d_h : nullptr, flags, d_Li, Li_host, total, info, s->st, who));
+  return sc.last(stb_lj_run(ti_stable(s), ti_rest(s, a, with_h), ti_counts(s), flags, d_Li, Li_host, total, info, s->st, who));
 }
 
 extern "C" int stb_tindic_logjoint(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total, double *Li_host,
@@ -1163,6 +1172,13 @@ static int ti_pr_ready(stb_tindic_t *s, double a, const double *bpar, unsigned f
   return 0;
 }
 
+// how the four held-out estimators open: an object, somewhere for the total, and ti_pr_ready's refusals, in that order
+static int ti_heldout_ready(stb_tindic_t *s, double a, const double *bpar, unsigned flags, const double *total, const char *who) {
+  if (!s) return stb_fail("%s: null object", who);
+  if (!total) return stb_fail("%s: total is required", who);
+  return ti_pr_ready(s, a, bpar, flags, true, who);
+}
+
 extern "C" int stb_tindic_predict(stb_tindic_t *s, double a, const double *bpar, double *theta_host, unsigned tstride) {
   STB_ENTRY;
   const char *who = "stb_tindic_predict";
@@ -1176,9 +1192,7 @@ extern "C" int stb_tindic_predict(stb_tindic_t *s, double a, const double *bpar,
   stb_pool_scratch sc(s->st);
   double *d_theta = nullptr;
   if (sc.take(&d_theta, bytes) != hipSuccess) return stb_fail("%s: out of device memory for %d x %u values", who, s->I, tstride);
-  if (stb_pr_predict(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_h, d_theta, tstride, nullptr, nullptr, nullptr, 0, 0, nullptr,
-                     0, nullptr, s->st, who))
-    return 1;
+  if (stb_pr_predict(ti_rest(s, a), ti_counts(s), stb_cust_ro{}, stb_lik_view{}, {d_theta, tstride}, 0, s->st, who)) return 1;
   if (hipMemcpyAsync(theta_host, d_theta, bytes, hipMemcpyDeviceToHost, s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   return sc.give_back(true, who);
 }
@@ -1187,26 +1201,22 @@ extern "C" int stb_tindic_heldout(stb_tindic_t *s, double a, const double *bpar,
                                   stb_predict_info_t *info) {
   STB_ENTRY;
   const char *who = "stb_tindic_heldout";
-  if (!s) return stb_fail("%s: null object", who);
-  if (!total) return stb_fail("%s: total is required", who);
-  if (ti_pr_ready(s, a, bpar, flags, true, who)) return 1;
+  if (ti_heldout_ready(s, a, bpar, flags, total, who)) return 1;
   const bool accumulate = (flags & STB_PR_ACCUMULATE) != 0;
   if (accumulate && s->hsamples == 0xffffffffu) return stb_fail("%s: the sample count is full (stb_tindic_heldout_reset)", who);
   stb_device_scope dev(s->dev);
   if (stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
   stb_pool_scratch sc(s->st);
-  double *d_p = nullptr, *d_Hi = nullptr;
-  uint64_t *d_skip = nullptr;
-  if ((!accumulate && sc.take(&d_p, sizeof(double) * (s->Hc ? s->Hc : 1)) != hipSuccess) ||
-      (Hi_host && sc.take(&d_Hi, sizeof(double) * (size_t)s->I) != hipSuccess) || sc.take(&d_skip, sizeof(uint64_t)) != hipSuccess)
+  stb_pr_out out;  // p: the accumulator, or a buffer of the call's
+  double *d_Hi = nullptr;
+  if (accumulate) out.p = s->d_pacc;
+  if ((!accumulate && sc.take(&out.p, sizeof(double) * (s->Hc ? s->Hc : 1)) != hipSuccess) ||
+      (Hi_host && sc.take(&d_Hi, sizeof(double) * (size_t)s->I) != hipSuccess) || sc.take(&out.skipped, sizeof(uint64_t)) != hipSuccess)
     return stb_fail("%s: out of device memory for %llu held-out customers", who, (unsigned long long)s->Hc);
-  if (hipMemsetAsync(d_skip, 0, sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
-  if (stb_pr_predict(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_h, nullptr, 0, s->d_hoff, s->d_hcls, s->d_lik, s->lik_rows,
-                     s->lik_stride, accumulate ? s->d_pacc : d_p, flags, d_skip, s->st, who))
-    return 1;
-  if (accumulate) s->hsamples++;
-  return sc.last(stb_pr_heldout(accumulate ? s->d_pacc : d_p, s->d_hoff, s->I, accumulate ? s->hsamples : 1u, d_Hi, Hi_host, total,
-                                info, d_skip, s->st, who));
+  if (hipMemsetAsync(out.skipped, 0, sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  if (stb_pr_predict(ti_rest(s, a), ti_counts(s), ti_heldout(s), ti_matrix(s), out, flags, s->st, who)) return 1;
+  const unsigned samples = accumulate ? ++s->hsamples : 1u;
+  return sc.last(stb_pr_heldout(out.p, s->d_hoff, s->I, samples, d_Hi, Hi_host, total, info, out.skipped, s->st, who));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1243,9 +1253,8 @@ static int ti_seat_queue(stb_tindic_t *s, double a, const double *bpar, bool pri
                 hipMemsetAsync(s->d_t, 0, sizeof(uint16_t) * s->G, s->st) != hipSuccess)))
     return STB_STREAM_FAIL(who);
   const bool lik = s->d_lik && !prior;
-  return stb_seat_launch(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_T, s->d_h, s->Mgiven, s->d_coff, lik ? s->d_cls : nullptr,
-                         s->d_cust, lik ? s->d_lik : nullptr, lik ? s->lik_rows : 0, lik ? s->lik_stride : 0, 1, STB_SEAT_COMMIT, seed,
-                         sweep, d_lw, nullptr, d_cnt, s->maxK, s->st, who);
+  return stb_seat_launch(ti_rest(s, a), ti_counts(s), s->Mgiven, ti_customers(s, lik), lik ? ti_matrix(s) : stb_lik_view{}, 1,
+                         STB_SEAT_COMMIT, {seed, sweep}, {d_lw, nullptr, d_cnt}, s->st, who);
 }
 
 extern "C" int stb_tindic_seat(stb_tindic_t *s, double a, const double *bpar, uint64_t seed, uint64_t sweep, double *total,
@@ -1271,9 +1280,7 @@ extern "C" int stb_tindic_heldout_seq(stb_tindic_t *s, double a, const double *b
                                       uint64_t sweep, double *total, double *Hi_host, stb_seat_info_t *info) {
   STB_ENTRY;
   const char *who = "stb_tindic_heldout_seq";
-  if (!s) return stb_fail("%s: null object", who);
-  if (!total) return stb_fail("%s: total is required", who);
-  if (ti_pr_ready(s, a, bpar, 0, true, who)) return 1;
+  if (ti_heldout_ready(s, a, bpar, 0, total, who)) return 1;
   if (stb_seat_check(a, s->Mgiven, particles, 0, s->I, who)) return 1;
   if (info) memset(info, 0, sizeof(*info));
   stb_device_scope dev(s->dev);
@@ -1285,8 +1292,8 @@ extern "C" int stb_tindic_heldout_seq(stb_tindic_t *s, double a, const double *b
       (Hi_host && sc.take(&d_Hi, sizeof(double) * (size_t)s->I) != hipSuccess) || sc.take(&d_cnt, 3 * sizeof(uint64_t)) != hipSuccess)
     return stb_fail("%s: out of device memory for %d x %u log weights", who, s->I, particles);
   if (hipMemsetAsync(d_cnt, 0, 3 * sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
-  if (stb_seat_launch(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, nullptr, s->d_h, s->Mgiven, s->d_hoff, s->d_hcls, nullptr,
-                      s->d_lik, s->lik_rows, s->lik_stride, particles, 0, seed, sweep, d_lw, nullptr, d_cnt, s->maxK, s->st, who))
+  if (stb_seat_launch(ti_rest(s, a), ti_counts(s), s->Mgiven, ti_heldout(s), ti_matrix(s), particles, 0, {seed, sweep},
+                      {d_lw, nullptr, d_cnt}, s->st, who))
     return 1;
   if (info) info->customers = s->Hc;
   return sc.last(stb_seat_sum(d_lw, s->I, particles, d_Hi, Hi_host, total, info, d_cnt, s->st, who));
@@ -1296,9 +1303,7 @@ extern "C" int stb_tindic_heldout_pf(stb_tindic_t *s, double a, const double *bp
                                      uint64_t sweep, double *total, double *Hi_host, stb_pf_info_t *info) {
   STB_ENTRY;
   const char *who = "stb_tindic_heldout_pf";
-  if (!s) return stb_fail("%s: null object", who);
-  if (!total) return stb_fail("%s: total is required", who);
-  if (ti_pr_ready(s, a, bpar, 0, true, who)) return 1;
+  if (ti_heldout_ready(s, a, bpar, 0, total, who)) return 1;
   if (stb_seat_pf_check(a, s->Mgiven, particles, tau, s->I, who)) return 1;
   if (info) memset(info, 0, sizeof(*info));
   stb_device_scope dev(s->dev);
@@ -1309,9 +1314,8 @@ extern "C" int stb_tindic_heldout_pf(stb_tindic_t *s, double a, const double *bp
   if (sc.take(&d_Hi, sizeof(double) * (size_t)(s->I ? s->I : 1)) != hipSuccess || sc.take(&d_cnt, 5 * sizeof(uint64_t)) != hipSuccess)
     return stb_fail("%s: out of device memory for %d values", who, s->I);
   if (hipMemsetAsync(d_cnt, 0, 5 * sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
-  if (stb_seat_pf_launch(a, s->d_bpar, s->I, s->d_koff, s->d_n, s->d_t, s->d_h, s->Mgiven, s->d_hoff, s->d_hcls, s->d_lik,
-                         s->lik_rows, s->lik_stride, particles, tau, seed, sweep, d_Hi, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         d_cnt, s->maxK, s->st, who))
+  if (stb_seat_pf_launch(ti_rest(s, a), ti_counts(s), s->Mgiven, ti_heldout(s), ti_matrix(s), particles, tau, {seed, sweep},
+                         {d_Hi, d_cnt}, s->st, who))
     return 1;
   // the total: k_seat_sum over one "particle" a restaurant, H = m + log(1 / 1) = m exactly (d_Hi is written with what was
   // read); its three words are the seating's first three, the filter's own two are fetched behind it
@@ -1374,9 +1378,7 @@ extern "C" int stb_tindic_heldout_ais(stb_tindic_t *s, double a, const double *b
                                       double *Hi_host, stb_ais_info_t *info) {
   STB_ENTRY;
   const char *who = "stb_tindic_heldout_ais";
-  if (!s) return stb_fail("%s: null object", who);
-  if (!total) return stb_fail("%s: total is required", who);
-  if (ti_pr_ready(s, a, bpar, 0, true, who)) return 1;
+  if (ti_heldout_ready(s, a, bpar, 0, total, who)) return 1;
   if (s->flags & STB_TI_REF_ODDS_FLAG)
     return stb_fail("%s: the object was created with STB_TI_REF_ODDS; the dish sweep has the exact weights only", who);
   if (s->C != 0)
@@ -1404,9 +1406,8 @@ extern "C" int stb_tindic_heldout_ais(stb_tindic_t *s, double a, const double *b
     return stb_fail("%s: out of device memory for %d x %u replicas (%zu bytes of workspace: split the restaurants)", who, s->I,
                     particles, ws_bytes);
   if (hipMemsetAsync(d_cnt, 0, 3 * sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
-  if (stb_seat_anneal_launch(tb.need_table ? s->d_avt : nullptr, tb.N, tb.M, a, s->d_bpar, s->I, s->d_koff, s->d_h, s->d_hoff, s->d_hcls,
-                             s->d_lik, s->lik_rows, s->lik_stride, s->G, s->Hc, particles, S, betas, passes, seed, sweep, d_lw, nullptr,
-                             nullptr, nullptr, d_cnt, d_ws, ws_bytes, s->maxK, s->st, who))
+  if (stb_seat_anneal_launch(ti_atable(s, tb), ti_rest(s, a), ti_heldout(s), ti_matrix(s), particles, {S, betas, passes},
+                             {seed, sweep}, {d_lw, d_cnt}, d_ws, ws_bytes, s->st, who))
     return 1;
   // k_seat_sum hands the three words on as they are: skipped, dead (in `impossible`'s place), stuck
   stb_seat_info_t si;
@@ -1505,9 +1506,7 @@ static int ti_cls_take(stb_tindic_t *s, ti_cls_room &room, const char *who) {
 // the draw on the object's stream, no wait; the object adopts a fresh class array once the draw is queued
 static int ti_cls_draw(stb_tindic_t *s, ti_cls_room &room, const uint8_t *d_mask, uint64_t seed, uint64_t sweep, const char *who) {
   if (hipMemsetAsync(s->d_cginfo, 0, 3 * sizeof(uint64_t), s->st) != hipSuccess) return STB_STREAM_FAIL(who);
-  if (stb_cg_launch(s->d_lik, s->lik_rows, s->lik_stride, s->d_cust, d_mask, s->C, seed, sweep, room.d_cls, s->d_cginfo, s->d_cgs, s->st,
-                    who))
-    return 1;
+  if (stb_cg_launch(ti_matrix(s), s->d_cust, d_mask, s->C, {seed, sweep}, room.d_cls, s->d_cginfo, s->d_cgs, s->st, who)) return 1;
   room.fresh = false;
   s->d_cls = room.d_cls;
   s->cls_rows = s->lik_rows;
