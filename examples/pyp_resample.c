@@ -66,10 +66,15 @@
  *      customer's class are drawn on the device given that matrix (stb_tindic_generate).  The chain then starts from a
  *      fresh stb_tindic_seat under the generated classes, as with -S, and every iteration prints the data term
  *      (stb_tindic_loglik) and the collapsed log joint of the flat model.
+ *  21. with -T a:b[:c...] (needs -d -z -w; not with -H or -C) the base weights sit on a tree of nested groups: a nodes of
+ *      level 1 cut the restaurants into equal contiguous ranges as -H does, b nodes of level 2 cut those, and so on up to
+ *      the root; stb_tindic_sample_htree takes stb_tindic_sample_h's place (auxiliary tables upwards, the root, every
+ *      level's concentration from a Gamma(1.1, 20) prior, then the rows downwards, one call); each iteration prints the
+ *      concentrations, level 1's first.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5] [-A 8] [-V 1000]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5] [-A 8] [-V 1000] [-T 8:2]
  */
 #include <math.h>
 #include <stdio.h>
@@ -90,11 +95,11 @@ static int cmp_double(const void *x, const void *y) {
 }
 
 int main(int argc, char **argv) {
-  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, filter = 0, vrows = 0, anneal = 0, c, j, i, it;
+  int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, filter = 0, vrows = 0, anneal = 0, tlevels = 0, tnodes[STB_HT_MAXL], c, j, i, it;
   double ftau = 0.0;
   double a0 = 0.5, b0 = 10.0, beta = 0.5, gam = 1.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:V:A:")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:V:A:T:")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -117,6 +122,21 @@ int main(int argc, char **argv) {
     else if (c == 'Q') seqpart = atoi(optarg) >= 1 ? atoi(optarg) : -1;
     else if (c == 'F') filter = 1, ftau = atof(optarg);
     else if (c == 'A') anneal = atoi(optarg) >= 1 ? atoi(optarg) : -1;
+    else if (c == 'T') { /* the nodes of every level, level 1 first */
+      const char *p = optarg;
+      tlevels = 0;
+      while (*p) {
+        char *end;
+        const long v = strtol(p, &end, 10);
+        if (end == p || v < 1 || v > 1000000 || tlevels == STB_HT_MAXL || (*end && (*end != ':' || !end[1]))) {
+          tlevels = -1;
+          break;
+        }
+        tnodes[tlevels++] = (int)v;
+        p = *end ? end + 1 : end;
+      }
+      if (tlevels == 0) tlevels = -1;
+    }
     else if (c == 'V') vrows = atoi(optarg) >= 2 ? atoi(optarg) : -1;
     else return 2;
   }
@@ -134,6 +154,10 @@ int main(int argc, char **argv) {
   }
   if (hgroups < 0 || (hgroups && !(explicit_d && dishes && redraw))) {
     fprintf(stderr, "pyp_resample: -H G needs G >= 1 and -d -z -w\n");
+    return 2;
+  }
+  if (tlevels < 0 || (tlevels && (!(explicit_d && dishes && redraw) || hgroups || collapsed))) {
+    fprintf(stderr, "pyp_resample: -T a:b[:c] needs 1 to %d levels of >= 1 nodes and -d -z -w, without -H and -C\n", STB_HT_MAXL);
     return 2;
   }
   if (predict && !(explicit_d && dishes)) {
@@ -311,6 +335,18 @@ int main(int argc, char **argv) {
       free(hgoff);
       hflat = malloc(sizeof(double) * (size_t)J * DISHES);
     }
+    if (tlevels) { /* every level cuts the one below into equal contiguous ranges */
+      uint64_t *toff[STB_HT_MAXL];
+      int below = J;
+      for (i = 0; i < tlevels; i++) {
+        toff[i] = malloc(sizeof(uint64_t) * ((size_t)tnodes[i] + 1));
+        for (j = 0; j <= tnodes[i]; j++) toff[i][j] = (uint64_t)j * (uint64_t)below / (uint64_t)tnodes[i];
+        below = tnodes[i];
+      }
+      if (stb_tindic_set_htree(ti, tlevels, tnodes, (const uint64_t *const *)toff)) yaps_quit("stb_tindic_set_htree: %s\n", stb_last_error());
+      for (i = 0; i < tlevels; i++) free(toff[i]);
+      hflat = malloc(sizeof(double) * (size_t)J * DISHES);
+    }
     if (seatdev) { /* the start state from the model, on the device: a seed of its own */
       double lw;
       stb_seat_info_t si;
@@ -330,7 +366,7 @@ int main(int argc, char **argv) {
           beta = ki.s;
           printf("iteration %d: beta %.6f from %llu customers, %llu auxiliary\n", it, beta, (unsigned long long)ki.count,
                  (unsigned long long)ki.aux_tables);
-          if (!hgroups) {
+          if (!hgroups && !tlevels) {
             if (stb_tindic_sample_gamma(ti, NULL, gam, 1.1, 10.0, (uint64_t)seed + 6, (uint64_t)it, &ki))
               yaps_quit("stb_tindic_sample_gamma: %s\n", stb_last_error());
             gam = ki.s;
@@ -353,6 +389,23 @@ int main(int argc, char **argv) {
           }
           printf("iteration %d: base weights in %d groups, alpha %.6f, %llu tables, %llu auxiliary, largest |sum h - 1| %.3g\n", it,
                  hgroups, hi.alpha, (unsigned long long)hi.tables, (unsigned long long)hi.aux_tables, worst);
+        } else if (redraw && tlevels) { /* every alpha: 5 to start with, then what the step before left on the device */
+          const double start[STB_HT_MAXL] = {5.0, 5.0, 5.0, 5.0, 5.0, 5.0, 5.0, 5.0};
+          stb_htree_opts_t to = {tlevels, it == 0 ? start : NULL, 1.0, 1.1, 20.0, NULL, STB_HT_SAMPLE_ALPHA, 0};
+          stb_htree_info_t hi;
+          double worst = 0.0;
+          if (stb_tindic_sample_lik(ti, NULL, beta, (uint64_t)seed + 3, (uint64_t)it) ||
+              stb_tindic_sample_htree(ti, &to, (uint64_t)seed + 4, (uint64_t)it, &hi) || stb_tindic_get_h(ti, hflat))
+            yaps_quit("stb_tindic_sample_lik / _sample_htree: %s\n", stb_last_error());
+          for (j = 0; j < J; j++) {
+            double sum = 0.0;
+            for (i = 0; i < DISHES; i++) sum += hflat[(size_t)j * DISHES + i];
+            if (fabs(sum - 1.0) > worst) worst = fabs(sum - 1.0);
+          }
+          printf("iteration %d: base weights on a tree of %d levels, alpha", it, tlevels);
+          for (i = 0; i < tlevels; i++) printf(" %.6f", hi.alpha[i]);
+          printf(", %llu tables, %llu auxiliary at level 1, largest |sum h - 1| %.3g\n", (unsigned long long)hi.tables[0],
+                 (unsigned long long)hi.aux_tables[0], worst);
         } else if (redraw && (stb_tindic_sample_lik(ti, NULL, beta, (uint64_t)seed + 3, (uint64_t)it) ||
                               stb_tindic_sample_h(ti, NULL, gam, (uint64_t)seed + 4, (uint64_t)it)))
           yaps_quit("stb_tindic_sample_lik / _sample_h: %s\n", stb_last_error());

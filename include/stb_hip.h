@@ -833,6 +833,90 @@ int stb_tindic_get_hroot(stb_tindic_t *s, double *root_out /* Kmax */);
 int stb_tindic_sample_hgroups(stb_tindic_t *s, const stb_hgroups_opts_t *opts, uint64_t seed, uint64_t sweep,
                               stb_hgroups_info_t *info);
 
+/* ---- base weights on a tree of nested groups (htree.hip; additive: the reference has no such step) ----
+ * stb_sample_hgroups has two layers, groups under one root.  Here the tree has levels 1 .. L, 1 <= L <= STB_HT_MAXL (corpus ->
+ * year -> author -> document):
+ *   level 1 cuts the restaurants 0 .. I-1 into G_1 contiguous ranges off[0][G_1 + 1] (stb_sample_bgroups' convention:
+ *   0 = off[0] <= ... <= off[G_1] = I, empty ranges allowed); level l + 1 cuts the G_l nodes of level l into G_(l+1) contiguous
+ *   ranges off[l][G_(l+1) + 1] that end at G_l (childless nodes allowed); above level L sits the root.
+ *     r ~ Dirichlet(gamma_1 .. gamma_Kmax);   h_v | h_par(v) ~ Dirichlet(alpha_l h_par(v)) for a node v of level l (the root
+ *     its parent at level L);   every table of a restaurant of the level-1 node g draws its dish from h_g.
+ * Dish k is local pair k of every restaurant and Kmax <= STB_TD_MAXK, as for _sample_h and _sample_hgroups.  Arrays over
+ * levels (G_host, d_off, d_hnode, d_c, d_m, alpha, info's) are indexed l - 1: level 1 first.  One call is one exact Gibbs
+ * step, in this order:
+ *   1. level 1's counts c_gk (integers) and C_g, as stb_sample_hgroups' step 1.
+ *   2. upwards, l = 1 .. L: for every node v and dish k, w = alpha_l * h_par(v),k (one FP64 product; h_par(v) the row that
+ *      d_hnode holds for level l + 1 on entry, d_root at l = L), m_vk by stb_sample_hgroups' step 2 exactly as written there,
+ *      M_v = sum_k m_vk; the next level's counts are the integer sums c_(par(v)),k = sum over the children of m_vk, C_par their
+ *      sum over k (64-bit); at l = L the sums are s_k.  Only the auxiliary tables are handed up, never all tables.
+ *   3. r' ~ Dirichlet(gamma_k + s_k), written over d_root.  Skipped with STB_HT_KEEP_ROOT (gamma is then not read).
+ *   4. with STB_HT_SAMPLE_ALPHA: one stb_sample_bgroups step with a = 0 over all nodes of all levels concatenated (level 1's
+ *      first) as "restaurants" of N = C_v customers and T = M_v tables, L ranges, one a level, b = alpha_l on level l's nodes,
+ *      one shape and scale for every level, seed ^ 0xA54FF53A5F1D36F1 (same sweep).  alpha'_l stays in device words and feeds
+ *      step 5.  With L = 1 this is stb_sample_hgroups' step 4.  Without the flag alpha'_l = alpha_l.
+ *   5. downwards, l = L .. 1: h'_v ~ Dirichlet(alpha'_l * h'_par(v),k + c_vk) for every node (childless and empty ones too: a
+ *      draw from the prior given the new parent); levels >= 2 are written over d_hnode[l - 1], level 1 to every pair (i, k)
+ *      with k < K_i and to d_hnode[0] when given.  d_c[l - 1] and d_m[l - 1] receive c and m of level l when given.
+ * Uniforms: key = mix(seed + (sweep+1) gamma); key_1 = key and key_l = mix(key ^ (0x3C6EF372FE94F82B + l)) for l >= 2.  Cell
+ * e = v * Kmax + k (uint64) of level l owns key_e = mix(key_l + (e+1) gamma): its variate takes key_e's elements 1, 2, ..., its
+ * u_j are element j of mix(key_e ^ 0x59B1D5A7C3E9F24D).  Root cell k owns mix(key_R + (k+1) gamma), key_R = mix(key ^
+ * 0x6A09E667F3BCC909).  Every draw depends on (seed, sweep, level, cell) alone; with L = 1 every stream, every operation and
+ * every output bit is stb_sample_hgroups'.  Each Dirichlet is normalised as stb_sample_hgroups': shape_k = alpha'_l *
+ * h'_par,k + (double)c_vk.  No bit depends on the launch geometry (STB_HTREE_WAVES = 1, 2, 4 or 8 waves a workgroup) or on who
+ * takes a cell's Bernoulli draws (STB_HTREE_FORM = lane | wave; default: a wave takes the cells with c_vk > 257, and where a
+ * level has few rows several waves a slice of the draws each).  tests/ht_oracle.py replays the step.
+ * The step is exact: going up, level l's h is integrated out when m of level l is drawn given the level above, so m is an
+ * exact conditional of the model with the levels <= l summed out (dropping the stale row of level l + 1 before m of level
+ * l + 1 is drawn marginalises a variable of a stationary sample); alpha_l | (C, M) of level l and r | s are exact conditionals
+ * of that collapsed model; the downward draws restore the rows from their full conditionals, top first.
+ * All launches are queued back to back on the stream; one wait (the raw call first reads every level's offsets back to check
+ * them).  info (may be NULL): per level alpha', tables = sum_v C_v, aux_tables = sum_v M_v (entries past `levels`: NaN, 0).
+ * Refused before anything is queued, with stb_last_error() set and nothing written: a null d_koff, d_t, G_host, d_off, a
+ * d_off[l], d_root, d_hnode, a d_hnode[l] with l >= 1, d_h, opts or opts->alpha; I < 1; levels outside 1 .. STB_HT_MAXL; Kmax
+ * outside 1 .. STB_TD_MAXK; a G_l < 1; ranges of a level that are not monotone from 0 to the size of the level below; unknown
+ * flags; an alpha_l, gamma (unless STB_HT_KEEP_ROOT) or shape, scale (with STB_HT_SAMPLE_ALPHA) not positive and finite.
+ * Fails after the wait with stb_sample_hgroups' error words (8: a node's C_v is above 2^32 - 1), or when a concentration's
+ * draw was not a positive finite double.  The outputs are then undefined.
+ * Object layer, queued on the object's stream behind its sweeps; the tree's ranges (independent of _set_hgroups'), the rows
+ * and the concentrations live with the object, the root is _set_hroot's:
+ *   stb_tindic_set_htree        levels, G_host[levels] and off_host[levels] (checked as above); the rows of the levels >= 2
+ *                               are made and set to the object's root (1/Kmax each on a new object); the concentrations are
+ *                               forgotten.  levels = 0 removes the tree
+ *   stb_tindic_set_htree_level  the G_l x Kmax rows of a level l >= 2 (1-based), positive and finite
+ *   stb_tindic_get_htree_level  a level's rows to the host, after the queued work; level 1: what the last step drew (refused
+ *                               before the first)
+ *   stb_tindic_sample_htree     the step on the object's t; opts->levels must be the tree's.  opts->alpha NULL: the
+ *                               concentrations the last successful step left, refused when there are none.  It replaces the
+ *                               object's h, root and stored rows; the sweeps, _logjoint, _loglik, _predict, the held-out calls
+ *                               and _generate see the new h through the pairs.
+ * Refusals and the rule that a step which fails after its wait blocks stb_tindic_sweep_dishes are stb_tindic_sample_hgroups'.
+ * stb_tindic_logjoint_collapsed is refused on an object whose tree has two or more levels: its grouped formula is not this
+ * model's. */
+#define STB_HT_MAXL 8
+#define STB_HT_KEEP_ROOT 1u
+#define STB_HT_SAMPLE_ALPHA 2u
+typedef struct stb_htree_opts {
+  int levels;
+  const double *alpha; /* [levels], level 1 first */
+  double gamma0, shape, scale;
+  const double *gamma_host; /* Kmax, or NULL for gamma0 */
+  unsigned flags, reserved;
+} stb_htree_opts_t;
+typedef struct stb_htree_info {
+  double alpha[STB_HT_MAXL];
+  uint64_t tables[STB_HT_MAXL], aux_tables[STB_HT_MAXL];
+  unsigned error_word, reserved;
+} stb_htree_info_t;
+int stb_sample_htree(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, const int *G_host /* [levels] */,
+                     const uint64_t *const *d_off /* [levels] */, const stb_htree_opts_t *opts, double *d_root /* Kmax: in r, out r' */,
+                     double *const *d_hnode /* [levels]: level >= 2 in and out (G x Kmax); level 1 out or NULL */,
+                     double *d_h /* pairs, out */, uint32_t *const *d_c, uint32_t *const *d_m /* [levels] or NULL, entries may be NULL */,
+                     uint64_t seed, uint64_t sweep, void *stream, stb_htree_info_t *info);
+int stb_tindic_set_htree(stb_tindic_t *s, int levels, const int *G_host /* [levels] */, const uint64_t *const *off_host /* [levels] */);
+int stb_tindic_set_htree_level(stb_tindic_t *s, int level /* 2 .. levels */, const double *rows /* G x Kmax */);
+int stb_tindic_get_htree_level(stb_tindic_t *s, int level /* 1 .. levels */, double *rows /* G x Kmax */);
+int stb_tindic_sample_htree(stb_tindic_t *s, const stb_htree_opts_t *opts, uint64_t seed, uint64_t sweep, stb_htree_info_t *info);
+
 /* ---- the log joint probability of a sampler state (logjoint.hip): what a Gibbs chain is watched by, what runs are
  * compared on, what annealed and bridge estimates of the evidence feed on.  Pairs, h, b_i and a as for stb_tcounts above;
  * T_i = sum_k t_ik, N_i = sum_k n_ik:

@@ -135,6 +135,23 @@ class HGroupsInfo(C.Structure):
                 ("reserved", C.c_uint)]
 
 
+HT_MAXL = 8           # STB_HT_MAXL
+HT_KEEP_ROOT = 1      # stb_htree_opts_t flags (include/stb_hip.h)
+HT_SAMPLE_ALPHA = 2
+
+
+class HTreeOpts(C.Structure):
+    """stb_htree_opts_t (include/stb_hip.h)"""
+    _fields_ = [("levels", C.c_int), ("alpha", c_double_p), ("gamma0", C.c_double), ("shape", C.c_double), ("scale", C.c_double),
+                ("gamma_host", c_double_p), ("flags", C.c_uint), ("reserved", C.c_uint)]
+
+
+class HTreeInfo(C.Structure):
+    """stb_htree_info_t (include/stb_hip.h)"""
+    _fields_ = [("alpha", C.c_double * HT_MAXL), ("tables", C.c_uint64 * HT_MAXL), ("aux_tables", C.c_uint64 * HT_MAXL),
+                ("error_word", C.c_uint), ("reserved", C.c_uint)]
+
+
 DM_ROWS, DM_COLUMNS = 1, 2  # stb_dirmult_logml's orientation: a multinomial a row / a column
 
 
@@ -337,6 +354,12 @@ def lib() -> C.CDLL:
     sig("stb_tindic_set_hroot", i, [vp, c_double_p])
     sig("stb_tindic_get_hroot", i, [vp, c_double_p])
     sig("stb_tindic_sample_hgroups", i, [vp, hgo, u64, u64, hgi])
+    hto, hti, vpp = C.POINTER(HTreeOpts), C.POINTER(HTreeInfo), C.POINTER(C.c_void_p)
+    sig("stb_sample_htree", i, [i, vp, vp, u, C.POINTER(i), vpp, hto, vp, vpp, vp, vpp, vpp, u64, u64, vp, hti])
+    sig("stb_tindic_set_htree", i, [vp, i, C.POINTER(i), vpp])
+    sig("stb_tindic_set_htree_level", i, [vp, i, c_double_p])
+    sig("stb_tindic_get_htree_level", i, [vp, i, c_double_p])
+    sig("stb_tindic_sample_htree", i, [vp, hto, u64, u64, hti])
     sig("stb_sample_partition", i, [vp, vp, u, u, d, u64, vp, vp, vp, u, vp, vp, u, u64, u64, vp])
     sig("stb_tcounts_partition", i, [vp, d, vp, c_double_p, u64, u64])
     sig("stb_hist_create_empty", vp, [u, i])
@@ -1168,6 +1191,49 @@ def sample_hgroups(koff, t, Kmax: int, root, alpha, gamma, seed: int, sweep: int
     return h, out, info
 
 
+def htree_opts(levels: int, alpha, gamma=1.0, shape=1.0, scale=1.0, flags: int = 0, Kmax: int = 0):
+    """(the host vectors to keep alive, HTreeOpts): alpha one value a level, level 1 first (None: the object's own);
+    gamma a scalar or Kmax values"""
+    keep, gp, g0 = _prior(gamma, Kmax)
+    av = None if alpha is None else np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    if av is not None and av.shape != (levels,):
+        raise StbError(f"expected {levels} concentrations, got {av.shape[0]}")
+    return (keep, av), HTreeOpts(int(levels), None if av is None else dp(av), g0, float(shape), float(scale), gp, int(flags), 0)
+
+
+def _ptr_array(ptrs):
+    """a C array of pointers (None entries are NULL)"""
+    return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def sample_htree(koff, t, Kmax: int, G, off, root, hnode, alpha, gamma, seed: int, sweep: int, flags: int = 0, shape=1.0,
+                 scale=1.0, want=("c", "m"), stream=None):
+    """stb_sample_htree on device tensors: koff, t and root as for sample_hgroups; G the nodes of every level, level 1
+    first; off[l] (int64 [G[l]+1]) the ranges of level l + 1; hnode[l] (float64 [G[l], Kmax]) the rows of the levels >= 2,
+    overwritten, hnode[0] ignored.  Returns (h [pairs], dict with rows (a list, level 1's made here) and whichever of c, m
+    (lists of int32 holding uint32) `want` names, HTreeInfo)"""
+    torch = _torch()
+    I, L = int(koff.shape[0]) - 1, len(G)
+    dev = root.device
+    h = torch.empty(int(t.shape[0]), dtype=torch.float64, device=dev)
+    rows = [torch.empty((int(G[0]), Kmax), dtype=torch.float64, device=dev)] + list(hnode[1:L])
+    out = {n: [torch.empty((int(g), Kmax), dtype=torch.int32, device=dev) for g in G] for n in want}
+    out["rows"] = rows
+    keep, opts = htree_opts(L, alpha, gamma, shape, scale, flags, Kmax)
+    info = HTreeInfo()
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    Gv = (C.c_int * L)(*[int(g) for g in G])
+    lists = lambda name: _ptr_array([ptr(x) for x in out[name]]) if name in out else None
+    rc = lib().stb_sample_htree(I, ptr(koff), ptr(t), Kmax, Gv, _ptr_array([ptr(o) for o in off]), C.byref(opts), ptr(root),
+                                _ptr_array([ptr(r) for r in rows]), ptr(h), lists("c"), lists("m"), seed, sweep,
+                                stream_ptr(stream), C.byref(info))
+    if rc:
+        err = StbError(last_error())
+        err.info = info
+        raise err
+    return h, out, info
+
+
 def _prior(v, n: int):
     """a Dirichlet parameter, a scalar for every entry or n values, as (the host vector to keep alive or None, its pointer or
     None, the scalar)"""
@@ -1658,6 +1724,54 @@ class TableIndicators(_BGroupsMixin):
         keep, opts = hgroups_opts(alpha, gamma, shape, scale, flags, self.maxK)
         info = HGroupsInfo()
         rc = self.L.stb_tindic_sample_hgroups(self.h, C.byref(opts), seed, sweep, C.byref(info))
+        if rc:
+            err = StbError(last_error())
+            err.info = info
+            raise err
+        return info
+
+    # ---- base weights on a tree of nested groups (stb_tindic_set_htree / _set_htree_level / _get_htree_level / _sample_htree)
+
+    def set_htree(self, off=None):
+        """the tree: off[l] the contiguous ranges that cut level l (the restaurants for l = 0) into the nodes of level
+        l + 1; None or an empty list removes it.  The rows of the levels >= 2 are set to the object's root"""
+        offs = [np.ascontiguousarray(o, dtype=np.uint64) for o in (off or [])]
+        L = len(offs)
+        if not L:
+            check(self.L.stb_tindic_set_htree(self.h, 0, None, None))
+            self._htree_G = []
+            return
+        G = [int(o.shape[0]) - 1 for o in offs]
+        check(self.L.stb_tindic_set_htree(self.h, L, (C.c_int * L)(*G), _ptr_array([o.ctypes.data for o in offs])))
+        self._htree_G = G
+
+    def set_htree_level(self, level: int, rows):
+        """the rows of a level >= 2 (1-based): (G_level, maxK) positive values"""
+        G = getattr(self, "_htree_G", [])
+        if not 1 <= level <= len(G):
+            raise StbError(f"level {level}: the tree has {len(G)} levels")
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.shape != (G[level - 1], self.maxK):
+            raise StbError(f"expected shape {(G[level - 1], self.maxK)}, got {rows.shape}")
+        check(self.L.stb_tindic_set_htree_level(self.h, level, dp(rows)))
+
+    def get_htree_level(self, level: int):
+        """a level's rows (G_level, maxK), after the queued work; level 1: what the last step drew"""
+        G = getattr(self, "_htree_G", [])
+        if not 1 <= level <= len(G):
+            raise StbError(f"level {level}: the tree has {len(G)} levels")
+        rows = np.zeros((G[level - 1], self.maxK), dtype=np.float64)
+        check(self.L.stb_tindic_get_htree_level(self.h, level, dp(rows)))
+        return rows
+
+    def sample_htree(self, alpha, gamma=1.0, seed: int = 0, sweep: int = 0, flags: int = 0, shape=1.0, scale=1.0, levels=None):
+        """one step of the base weights on the tree: auxiliary tables upwards, the root, with HT_SAMPLE_ALPHA every level's
+        concentration, then the rows downwards; alpha one value a level (level 1 first), None: what the last step left.
+        Returns HTreeInfo (alpha, tables, aux_tables a level).  Give it another seed than sample_lik"""
+        L = len(getattr(self, "_htree_G", [])) if levels is None else levels
+        keep, opts = htree_opts(L, alpha, gamma, shape, scale, flags, self.maxK)
+        info = HTreeInfo()
+        rc = self.L.stb_tindic_sample_htree(self.h, C.byref(opts), seed, sweep, C.byref(info))
         if rc:
             err = StbError(last_error())
             err.info = info

@@ -19,5 +19,13 @@ int stb_hg_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned K
 // by k_hg_count with the geometry stb_hg_sample gives it.  d_goff null: G = I.  Queued on st; no wait
 int stb_hg_count_queue(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
                        uint32_t *d_c, unsigned long long *d_Cg, hipStream_t st);
+// two more launches of the step alone, for the tree step (htree.hip); nw = 1, 2, 4 or 8 waves a workgroup.  Queued on st; no wait.
+// The root's row: d_root[k] ~ Dirichlet(gamma_k + d_s[k]) (d_gam[Kmax], or null for gamma0) on mix(key ^ HG_SALT_R)'s cells, the
+// error bits or-ed into d_ctl[0]
+int stb_hg_root_queue(unsigned Kmax, const unsigned long long *d_s, const double *d_gam, double gamma0, uint64_t key,
+                      double *d_root, unsigned *d_ctl, unsigned nw, hipStream_t st);
+// the scatter: d_hgrp's row of restaurant i's range to its pairs
+int stb_hg_scatter_queue(int I, const uint64_t *d_koff, unsigned Kmax, int G, const uint64_t *d_goff, const double *d_hgrp,
+                         double *d_h, unsigned nw, hipStream_t st);
 
 #endif

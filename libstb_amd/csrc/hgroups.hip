@@ -413,6 +413,25 @@ int stb_hg_count_queue(int I, const uint64_t *d_koff, const uint16_t *d_t, unsig
   return 0;
 }
 
+// the root's row and the scatter as stb_hg_sample launches them, for the tree step (htree.hip)
+int stb_hg_root_queue(unsigned Kmax, const unsigned long long *d_s, const double *d_gam, double gamma0, uint64_t key,
+                      double *d_root, unsigned *d_ctl, unsigned nw, hipStream_t st) {
+  const unsigned cb = (Kmax + 63) / 64, thr_row = 64u * nw < 64u * cb ? 64u * nw : 64u * cb;
+  STB_LAUNCH(k_hg_rows, dim3(1), dim3(thr_row), st, (uint64_t)1, Kmax, (const uint32_t *)nullptr, d_s, d_gam, gamma0,
+             (const double *)nullptr, stb_mix64(key ^ HG_SALT_R), d_root, d_ctl);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int stb_hg_scatter_queue(int I, const uint64_t *d_koff, unsigned Kmax, int G, const uint64_t *d_goff, const double *d_hgrp,
+                         double *d_h, unsigned nw, hipStream_t st) {
+  const uint64_t runs = ((uint64_t)I + HG_RUN - 1) / HG_RUN;
+  STB_LAUNCH(k_hg_scatter, dim3((unsigned)((runs + nw - 1) / nw)), dim3(64 * nw), st, (uint64_t)I, d_koff, Kmax, (uint64_t)G, d_goff,
+             d_hgrp, d_h);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // ---- the raw layer ------------------------------------------------------------------------------------------------
 
 extern "C" int stb_sample_hgroups(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,

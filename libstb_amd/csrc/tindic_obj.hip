@@ -21,6 +21,7 @@
 #include "seat_pf.h"
 #include "seat_ais.h"
 #include "hgroups.h"
+#include "htree.h"
 #include "dirmult.h"
 #include "dirconc.h"
 #include "classgen.h"
@@ -62,6 +63,13 @@ struct stb_tindic {
   uint64_t *d_hgoff;    // [hg_G + 1], or null
   double *d_hroot;      // [maxK] (null: 1/maxK each)
   double hg_alpha;      // what the last successful step left (NaN: none yet)
+  // the tree of nested groups (htree.hip): its ranges, every level's rows and the concentrations live with the object
+  int ht_L;                        // levels (0: no tree)
+  int ht_G[STB_HT_MAXL];           // nodes of every level
+  uint64_t *d_htoff[STB_HT_MAXL];  // [ht_G[l] + 1]
+  double *d_htnode[STB_HT_MAXL];   // [ht_G[l] x maxK]; level 1's are what the last step drew
+  double ht_alpha[STB_HT_MAXL];    // what the last successful step left
+  bool ht_have_alpha, ht_have_rows1;
   double *d_vt;
   uint64_t vstride;
   void *d_ws;
@@ -185,6 +193,10 @@ static void ti_release(stb_tindic_t *s) {
                  s->d_avt, s->d_aws};
   for (void *p : dev)
     if (p) (void)hipFree(p);
+  for (int l = 0; l < STB_HT_MAXL; l++) {
+    if (s->d_htoff[l]) (void)hipFree(s->d_htoff[l]);
+    if (s->d_htnode[l]) (void)hipFree(s->d_htnode[l]);
+  }
   if (s->h_info) (void)hipHostFree(s->h_info);
   if (s->st) (void)hipStreamDestroy(s->st);
   delete s;
@@ -877,6 +889,136 @@ extern "C" int stb_tindic_sample_hgroups(stb_tindic_t *s, const stb_hgroups_opts
 }
 
 // ------------------------------------------------------------------------------------------------
+// base weights on a tree of nested groups (htree.hip)
+
+extern "C" int stb_tindic_set_htree(stb_tindic_t *s, int levels, const int *G_host, const uint64_t *const *off_host) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_htree";
+  if (!s) return stb_fail("%s: null object", who);
+  if (levels < 0 || levels > STB_HT_MAXL) return stb_fail("%s: levels=%d (0 to STB_HT_MAXL = %d)", who, levels, STB_HT_MAXL);
+  if (levels && (!G_host || !off_host)) return stb_fail("%s: G_host and off_host are required", who);
+  if (levels && ti_hg_maxk(s, who)) return 1;
+  for (int l = 0; l < levels; l++) {
+    if (G_host[l] < 1) return stb_fail("%s: G[%d]=%d (must be >= 1)", who, l, G_host[l]);
+    if (!off_host[l]) return stb_fail("%s: off_host[%d] is required", who, l);
+    if (stb_ht_check_ranges(l, G_host[l], off_host[l], l == 0 ? (uint64_t)s->I : (uint64_t)G_host[l - 1], who)) return 1;
+  }
+  stb_device_scope dev(s->dev);
+  const unsigned K = s->maxK;
+  // the new tree first: a call that fails leaves the object with the tree it had
+  uint64_t *d_off[STB_HT_MAXL] = {};
+  double *d_node[STB_HT_MAXL] = {};
+  int rc = 0;
+  std::vector<double> root(K, K ? 1.0 / (double)K : 0.0), rows;
+  if (levels && s->d_hroot && ti_fetch(s, {{root.data(), s->d_hroot, sizeof(double) * K}}, who)) return 1;
+  if (hipStreamSynchronize(s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+  for (int l = 0; l < levels && !rc; l++) {
+    const size_t G = (size_t)G_host[l];
+    if (hipMalloc((void **)&d_off[l], sizeof(uint64_t) * (G + 1)) != hipSuccess ||
+        hipMalloc((void **)&d_node[l], sizeof(double) * G * K) != hipSuccess) {
+      rc = stb_fail("%s: out of device memory for level %d's %zu nodes", who, l + 1, G);
+      break;
+    }
+    if (hipMemcpy(d_off[l], off_host[l], sizeof(uint64_t) * (G + 1), hipMemcpyHostToDevice) != hipSuccess) rc = STB_STREAM_FAIL(who);
+    if (!rc && l >= 1) {
+      rows.resize(G * K);
+      for (size_t v = 0; v < G; v++) std::copy(root.begin(), root.end(), rows.begin() + v * K);
+      if (hipMemcpy(d_node[l], rows.data(), sizeof(double) * G * K, hipMemcpyHostToDevice) != hipSuccess) rc = STB_STREAM_FAIL(who);
+    }
+  }
+  for (int l = 0; l < STB_HT_MAXL; l++) {
+    uint64_t *&off = rc ? d_off[l] : s->d_htoff[l];
+    double *&node = rc ? d_node[l] : s->d_htnode[l];
+    if (off) (void)hipFree(off);
+    if (node) (void)hipFree(node);
+    off = nullptr;
+    node = nullptr;
+  }
+  if (rc) return rc;
+  s->ht_L = levels;
+  for (int l = 0; l < STB_HT_MAXL; l++) {
+    s->ht_G[l] = l < levels ? G_host[l] : 0;
+    s->d_htoff[l] = d_off[l];
+    s->d_htnode[l] = d_node[l];
+  }
+  s->ht_have_alpha = s->ht_have_rows1 = false;
+  return 0;
+}
+
+static int ti_ht_level(const stb_tindic_t *s, int level, int lowest, const char *who) {
+  if (s->ht_L < 1) return stb_fail("%s: the object has no tree (stb_tindic_set_htree)", who);
+  if (level < lowest || level > s->ht_L) return stb_fail("%s: level=%d (%d to the tree's %d)", who, level, lowest, s->ht_L);
+  return 0;
+}
+
+extern "C" int stb_tindic_set_htree_level(stb_tindic_t *s, int level, const double *rows) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_htree_level";
+  if (!s || !rows) return stb_fail("%s: null %s", who, s ? "rows" : "object");
+  if (ti_ht_level(s, level, 2, who)) return 1;
+  const size_t cells = (size_t)s->ht_G[level - 1] * s->maxK;
+  for (size_t e = 0; e < cells; e++)
+    if (!(rows[e] > 0.0) || !std::isfinite(rows[e])) return stb_fail("%s: rows[%zu]=%g (must be > 0 and finite)", who, e, rows[e]);
+  stb_device_scope dev(s->dev);
+  if (hipStreamSynchronize(s->st) != hipSuccess ||
+      hipMemcpy(s->d_htnode[level - 1], rows, sizeof(double) * cells, hipMemcpyHostToDevice) != hipSuccess)
+    return STB_STREAM_FAIL(who);
+  return 0;
+}
+
+extern "C" int stb_tindic_get_htree_level(stb_tindic_t *s, int level, double *rows) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_get_htree_level";
+  if (!s || !rows) return stb_fail("%s: null %s", who, s ? "rows" : "object");
+  if (ti_ht_level(s, level, 1, who)) return 1;
+  if (level == 1 && !s->ht_have_rows1) return stb_fail("%s: level 1's rows are what a step draws, and none has succeeded yet", who);
+  stb_device_scope dev(s->dev);
+  return ti_fetch(s, {{rows, s->d_htnode[level - 1], sizeof(double) * (size_t)s->ht_G[level - 1] * s->maxK}}, who);
+}
+
+extern "C" int stb_tindic_sample_htree(stb_tindic_t *s, const stb_htree_opts_t *opts, uint64_t seed, uint64_t sweep,
+                                       stb_htree_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sample_htree";
+  if (info) {
+    for (int l = 0; l < STB_HT_MAXL; l++) {
+      info->alpha[l] = NAN;
+      info->tables[l] = info->aux_tables[l] = 0;
+    }
+    info->error_word = info->reserved = 0;
+  }
+  if (!s) return stb_fail("%s: null object", who);
+  if (!opts) return stb_fail("%s: opts is required", who);
+  if (s->flags & STB_TI_REF_ODDS_FLAG)
+    return stb_fail("%s: the object was created with STB_TI_REF_ODDS; its sweeps do not leave the law h is drawn under", who);
+  if (ti_hg_maxk(s, who)) return 1;
+  if (s->ht_L < 1) return stb_fail("%s: the object has no tree (stb_tindic_set_htree)", who);
+  if (opts->levels != s->ht_L) return stb_fail("%s: levels=%d; the object's tree has %d", who, opts->levels, s->ht_L);
+  const double *alpha = opts->alpha;
+  if (!alpha) {
+    if (!s->ht_have_alpha) return stb_fail("%s: alpha=NULL asks for the object's concentrations, and it has none yet", who);
+    alpha = s->ht_alpha;
+  }
+  if (stb_ht_check_opts(opts, alpha, s->maxK, who)) return 1;
+  stb_device_scope dev(s->dev);
+  if (!s->d_hroot && ti_hroot(s, nullptr, who)) return 1;
+  ti_fresh_h h(s);
+  if (!h.d) return stb_fail("%s: out of device memory", who);
+  bool touched = false;
+  stb_htree_info_t mine;
+  if (!info) info = &mine;
+  const int rc = stb_ht_sample(s->I, s->d_koff, s->d_t, s->maxK, s->ht_G, s->d_htoff, opts, alpha, s->d_hroot, s->d_htnode, h.d, nullptr,
+                               nullptr, seed, sweep, s->st, info, who, &touched);
+  h.settle(touched, rc);
+  if (touched) s->ht_have_rows1 = !rc;
+  if (touched && !rc) {
+    for (int l = 0; l < s->ht_L; l++) s->ht_alpha[l] = info->alpha[l];
+    s->ht_have_alpha = true;
+  }
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
 // the log joint of the object's state (logjoint.hip), and the collapsed one (dirmult.hip)
 
 // the S slab for discount a, with the V table's bounds: taken from the buffer cache on first use, refilled only when the
@@ -944,6 +1086,9 @@ extern "C" int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const do
   if (s->flags & STB_TI_REF_ODDS_FLAG)
     return stb_fail("%s: the object was created with STB_TI_REF_ODDS; its sweeps do not leave the law this is the joint of", who);
   if (ti_hg_maxk(s, who)) return 1;
+  if (s->ht_L >= 2)
+    return stb_fail("%s: the object has a tree of %d levels (stb_tindic_set_htree); the collapsed joint's grouped formula is "
+                    "not that model's", who, s->ht_L);
   double alpha = 1.0;
   if (!flat) {
     alpha = opts->alpha;
