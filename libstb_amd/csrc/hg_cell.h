@@ -1,5 +1,5 @@
-// hg_cell.h -- private: the Antoniak auxiliary-table draw of one count cell, the one copy hgroups.hip (k_hg_aux) and
-// dirconc.hip (k_dc_aux_rows, k_dc_aux_cols) share.  A cell with count c and weight w owns the substream ky =
+// hg_cell.h -- private: the Antoniak auxiliary-table draw of one count cell, the one copy hgroups.hip (k_hg_aux, for the grouped and the
+// tree step) and dirconc.hip (k_dc_aux_rows, k_dc_aux_cols) share.  A cell with count c and weight w owns the substream ky =
 // mix(key_e ^ HG_SALT_Y) and draws
 //     m = [c >= 1] + sum_{j=1}^{c-1} [u_j (w + (double)j) < w],     u_j = element j of ky (hq_unit's open interval)
 // in FP64 as written, no contraction.  m is an integer, so who adds which Bernoulli changes no bit.

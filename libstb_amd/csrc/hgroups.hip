@@ -1,33 +1,40 @@
 // hgroups.hip -- base weights per group of restaurants under a shared root, drawn on the device (include/stb_hip.h,
-// stb_sample_hgroups).  Restaurants are cut into G contiguous ranges; the root r ~ Dirichlet(gamma),
-// group g's weights h_g | r ~ Dirichlet(alpha r), every table of a restaurant of group g draws its dish from h_g, and
-// c_gk counts the tables of group g that serve dish k.  One step, h integrated out until its own draw:
+// stb_sample_hgroups), and the kernels of that step on a tree of nested groups (htree.hip), of which it
+// is the one-level case.  Restaurants are cut into G contiguous ranges; the root r ~ Dirichlet(gamma), group g's weights
+// h_g | r ~ Dirichlet(alpha r), every table of a restaurant of group g draws its dish from h_g, and c_gk counts the tables of
+// group g that serve dish k.  One step, h integrated out until its own draw:
 //     m_gk | c, alpha, r     Antoniak: [c_gk >= 1] + sum_{j=1}^{c_gk - 1} Bernoulli(alpha r_k / (alpha r_k + j))
 //     r' | m                 Dirichlet(gamma_k + sum_g m_gk)
 //     alpha' | m, c          Teh's auxiliaries: stb_sample_bgroups with a = 0, a "restaurant" per group (N = C_g, T = M_g)
 //     h_g | r', alpha', c    Dirichlet(alpha' r'_k + c_gk)
+// On a tree a level's rows are the groups, the level above holds their base rows (the root above the top level), and a
+// parent's counts are the integer sums of its children's m.
 //
-//   k_hg_count    c_gk and C_g: a wave a run of HG_RUN restaurants, lanes over the dishes, sums kept in registers while
+//   k_hg_count    level 1's c and C: a wave a run of HG_RUN restaurants, lanes over the dishes, sums kept in registers while
 //                 the group does not change (integers: atomics)
-//   k_hg_aux      m_gk, M_g, s_k: lanes along k, a wave a group row; a cell with many draws is taken by its whole wave,
-//                 and where the rows are few by several waves, each a slice of the draws (integers: atomics)
-//   k_hg_prep     C_g as hyperb's N (and the 2^32 check), alpha for every group, the one range {0, G}
-//   k_hg_rows     a Dirichlet row a workgroup: the root (one row) and the groups (G rows)
-//   k_hg_scatter  h_g to the pairs of its restaurants
-//   k_hg_finish   error word, alpha', the totals to pinned words
-// All are queued back to back, the concentration's three launches (hyperb.hip, through hyperb.h's queue entry) among
-// them; alpha' stays in a device word between them; the call waits once.  No kernel waits for another workgroup.
+//   k_hg_aux      a level's m, M_v, and its parents' c and C (above the top level: s_k): lanes along k, a wave a run of
+//                 successive rows, the parent's column sums kept in registers while the parent does not change (one parent:
+//                 the rows strided over the waves); a cell with
+//                 many draws is taken by its whole wave, and where the rows are few by several waves, each a slice of the
+//                 draws (integers: atomics)
+//   k_hg_rows     a Dirichlet row a workgroup: the root (one row), and a level's rows on their parents' new rows
+//   k_hg_scatter  level 1's rows to the pairs of their restaurants
+// stb_ht_sample (htree.hip) queues them back to back with its own k_ht_prep and k_ht_finish and the concentration's three
+// launches (hyperb.hip, through hyperb.h's queue entry); the call waits once.  No kernel waits for another workgroup.
 //
-// Streams (gamma_dev.h's uniforms): key = mix(seed + (sweep+1) gamma).  Cell e = g Kmax + k owns key_e = mix(key + (e+1)
-// gamma): its group variate takes key_e's elements 1, 2, ... as tlik.hip's k_th_draw does with e = k, its Bernoulli draws
-// take u_j = element j of mix(key_e ^ HG_SALT_Y), hyperb.hip's y substream.  Root cell k owns mix(key_R + (k+1) gamma),
-// key_R = mix(key ^ HG_SALT_R).  The concentration is hyperb's own step with seed ^ HG_SALT_A.
+// Streams (gamma_dev.h's uniforms): key = mix(seed + (sweep+1) gamma); key_1 = key, key_l = mix(key ^ (HT_SALT_L + l)) for a
+// level l >= 2.  Cell e = v Kmax + k of level l owns key_e = mix(key_l + (e+1) gamma): its row's variate takes key_e's
+// elements 1, 2, ... as tlik.hip's k_th_draw does with e = k, its Bernoulli draws take u_j = element j of
+// mix(key_e ^ HG_SALT_Y), hyperb.hip's y substream.  Root cell k owns mix(key_R + (k+1) gamma), key_R = mix(key ^ HG_SALT_R).
+// The concentrations are one hyperb step with seed ^ HG_SALT_A, a range a level.
 //
-// Associations (FP64, no contraction).  w = alpha r_k is one product; a Bernoulli is u_j (w + (double)j) < w.  A row's
-// shapes are w + (double)c (the root's gamma_k + (double)s_k); M = the largest lg_k (exact in any order), e_k = exp(lg_k -
-// M), Z adds the e_k one after another in k order (one thread), h_k = e_k / Z: stb_tindic_sample_h's.  Counts and m are
-// integers.  So no bit depends on STB_HGROUPS_WAVES = 1, 2, 4 or 8 waves a workgroup (default 4) or on
-// STB_HGROUPS_FORM = lane | wave (who takes a cell's Bernoulli draws; default: its wave when c_gk - 1 > HG_TWAVE).
+// Associations (FP64, no contraction).  w = alpha_l base_k is one product, base the parent's stored row (the root r at the top);
+// a Bernoulli is u_j (w + (double)j) < w.  A row's shapes are alpha'_l base'_k + (double)c on the parent's new row (the
+// root's gamma_k + (double)s_k); M = the largest lg_k (exact in any order), e_k = exp(lg_k - M), Z adds the e_k one after
+// another in k order (one thread), h_k = e_k / Z: stb_tindic_sample_h's.  Counts and m are integers.  So no bit depends on
+// the waves a workgroup (1, 2, 4 or 8; default 4) or on who takes a cell's Bernoulli draws (lane | wave; default: its wave
+// when c - 1 > HG_TWAVE): STB_HGROUPS_WAVES and STB_HGROUPS_FORM for the grouped entry points, STB_HTREE_WAVES and
+// STB_HTREE_FORM for the tree's.
 //
 // What should set the pace, from the counts alone (MEASUREMENTS section H1 has what was measured): G Kmax Gamma variates
 // of about seven FP64 transcendentals each in k_hg_rows, against 12 bytes read and 8 written a cell; the Bernoulli draws
@@ -39,8 +46,8 @@
 
 #include "stb_common.h"
 #include "gamma_dev.h"
-#include "hyperb.h"
 #include "hgroups.h"
+#include "htree.h"
 #include "ticket.h"
 #include "hg_cell.h"  // HG_SALT_Y, HG_SALT_A, HG_TWAVE, hg_y, hg_cell: the cell's draw, shared with dirconc.hip
 
@@ -50,11 +57,7 @@
 #define HG_MAXTHREADS 512
 #define HG_RUN 32u     // restaurants a wave counts (or scatters) in a row
 #define HG_KREG (STB_TD_MAXK / 64)
-#define HG_ERR_CAP 1u
-#define HG_ERR_Z 2u
-#define HG_ERR_SHAPE 4u
-#define HG_ERR_TOTAL 8u
-// ctl[0]: the error word
+static_assert(STB_HG_KEEP_ROOT == STB_HT_KEEP_ROOT && STB_HG_SAMPLE_ALPHA == STB_HT_SAMPLE_ALPHA, "the grouped step hands its flags on");
 
 // the last range that starts at or before restaurant i (empty ranges in front of it start there too)
 __device__ __forceinline__ uint64_t hg_group_of(const uint64_t *goff, uint64_t G, uint64_t i) {
@@ -116,56 +119,78 @@ __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_count(uint64_t I, const ui
   hg_flush(acc, tot, g, Kmax, lane, c, Cg);
 }
 
-// workgroup (x, y): the columns 64 x .. 64 x + 63; its wave v the rows y nw + v, then + gridDim.y nw, ...
-__global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_aux(unsigned Kmax, uint64_t G, const uint32_t *c, const double *root,
-                                                          double alpha, uint64_t key, unsigned twave, unsigned parts,
-                                                          uint32_t *m, uint32_t *Mg, unsigned long long *s) {
-  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+// what a wave holds of parent `par`: its lanes' column sums, and (lane 0) the rows' totals
+__device__ __forceinline__ void hg_hand_up(unsigned long long &acc, unsigned long long &tot, uint64_t par, unsigned Kmax, unsigned k,
+                                           bool live, unsigned lane, uint32_t *cpar, unsigned long long *Cpar, unsigned long long *s) {
+  if (live && acc) {
+    if (cpar) atomicAdd(&cpar[par * Kmax + k], (unsigned)acc);  // (a wrap shows in C_par > 2^32 - 1: error 8)
+    else atomicAdd(&s[k], acc);
+  }
+  acc = 0;
+  if (lane == 0 && tot && Cpar) atomicAdd(&Cpar[par], tot);
+  tot = 0;
+}
+
+// workgroup (x, y): the columns 64 x .. 64 x + 63.  The G rows, each cut into `parts` (hg_cell.h), are dealt to the grid's
+// waves in runs of successive (row, part), or strided (below).  poff[Gp + 1] cuts the rows into their parents' ranges (null:
+// one parent, row 0 of base).  The parents' counts go to cpar[Gp Kmax] and Cpar[Gp], or, above the top level, to s[Kmax] (cpar
+// and Cpar null).  m may be null; with parts > 1 it arrives zeroed
+__global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_aux(unsigned Kmax, uint64_t G, const uint32_t *c, uint64_t Gp, const uint64_t *poff,
+                                                          const double *base, double alpha, uint64_t key, unsigned twave, unsigned parts,
+                                                          uint32_t *m, uint32_t *Mv, uint32_t *cpar, unsigned long long *Cpar,
+                                                          unsigned long long *s) {
+  const unsigned lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (what follows from it stays in scalar registers)
   const unsigned k = blockIdx.x * 64 + lane;
   const bool live = k < Kmax;  // (no lane leaves: the wave's shuffles need them all)
-  const double w = live ? alpha * root[k] : 1.0;
-  unsigned long long sk = 0;
-  // a row is taken by `parts` waves: part 0 the cells a lane draws alone and every cell's first table, part p the draws
-  // j = 1 + 64 p + lane, + 64 parts, ... of the cells a wave takes.  With parts > 1 m arrives zeroed and is added to
-  for (uint64_t q = (uint64_t)blockIdx.y * nw + wave; q < G * parts; q += (uint64_t)gridDim.y * nw) {
+  const uint64_t total = G * parts, waves = (uint64_t)gridDim.y * nw, run = (total + waves - 1) / waves;
+  const uint64_t gw = (uint64_t)blockIdx.y * nw + wave;
+  // (uniform over the grid) one parent: nothing to keep from row to row, so wave gw strides, gw, gw + waves, ..., and the
+  // waves of a workgroup read neighbouring rows
+  const bool runs = poff != nullptr;
+  const uint64_t q0 = runs ? gw * run : gw, step = runs ? 1 : waves;
+  if (q0 >= total) return;  // (the whole wave)
+  const uint64_t q1 = runs && q0 + run < total ? q0 + run : total;
+  uint64_t par = poff ? hg_group_of(poff, Gp, q0 / parts) : 0;
+  const double w1 = live ? alpha * base[k] : 1.0;  // (one parent: every row's w, kept out of the loop's loads)
+  unsigned long long acc = 0, tot = 0;
+  for (uint64_t q = q0; q < q1; q += step) {
     const uint64_t g = q / parts;
     const unsigned p = (unsigned)(q % parts);
+    if (poff) {
+      uint64_t pn = par;
+      while (pn + 1 < Gp && poff[pn + 1] <= g) pn++;
+      if (pn != par) {  // (uniform over the wave)
+        hg_hand_up(acc, tot, par, Kmax, k, live, lane, cpar, Cpar, s);
+        par = pn;
+      }
+    }
     const uint64_t e = g * Kmax + k;
     const unsigned cc = live ? c[e] : 0u;
+    const double w = !poff ? w1 : live ? alpha * base[par * Kmax + k] : 1.0;
     const uint64_t ky = stb_mix64(stb_mix64(key + (e + 1) * STB_GAMMA) ^ HG_SALT_Y);
     const unsigned mm = hg_cell(cc, w, ky, p, parts, twave, lane);
-    if (live) {
+    if (live && m) {
       if (parts == 1) m[e] = mm;
       else if (mm) atomicAdd(&m[e], mm);
     }
-    sk += mm;
+    acc += mm;
     unsigned row = mm;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) row += __shfl_down(row, off, 64);
-    if (lane == 0 && row) atomicAdd(&Mg[g], row);
+    if (lane == 0 && row) atomicAdd(&Mv[g], row);
+    tot += row;  // (lane 0's is the row's)
   }
-  if (live && sk) atomicAdd(&s[k], sk);
+  hg_hand_up(acc, tot, par, Kmax, k, live, lane, cpar, Cpar, s);
 }
 
-__global__ __launch_bounds__(256) void k_hg_prep(uint64_t G, const unsigned long long *Cg, double alpha, uint32_t *N32,
-                                                 double *al, uint64_t *goff1, unsigned *ctl) {
-  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= G) return;
-  const unsigned long long C = Cg[g];
-  if (C > 0xffffffffull) __hip_atomic_fetch_or(&ctl[0], HG_ERR_TOTAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  N32[g] = (uint32_t)C;
-  al[g] = alpha;
-  if (g == 0) {
-    goff1[0] = 0;
-    goff1[1] = G;
-  }
-}
-
-// a workgroup a row (rows r = blockIdx.x, + gridDim.x, ...), its threads strided over k: shape_k = f base_k + count,
-// f = *factor (1 when null), base_k = base[k] (base0 when null), count = cnt32[r Kmax + k] or cnt64[k]; cell e = r Kmax + k
+// a workgroup a row (rows r = blockIdx.x, + gridDim.x, ...), its threads strided over k: shape_k = f base_k + count, f = *factor
+// (1 when null), count = cnt32[r Kmax + k] or cnt64[k]; base_k = base0 when base is null, else base[par(r) Kmax + k] with
+// par(r) from poff[Gp + 1] (null: row 0).  Cell e = r Kmax + k.  The root's row: rows = 1, cnt64 = s, no factor, no poff
 __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_rows(uint64_t rows, unsigned Kmax, const uint32_t *cnt32,
-                                                           const unsigned long long *cnt64, const double *base, double base0,
-                                                           const double *factor, uint64_t key, double *out, unsigned *ctl) {
+                                                           const unsigned long long *cnt64, uint64_t Gp, const uint64_t *poff,
+                                                           const double *base, double base0, const double *factor, uint64_t key,
+                                                           double *out, unsigned *ctl) {
   __shared__ double sv[STB_TD_MAXK];
   __shared__ double s_max[HG_MAXTHREADS / 64];
   __shared__ double s_Z;
@@ -173,12 +198,13 @@ __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_rows(uint64_t rows, unsign
   const double f = factor ? *factor : 1.0;
   unsigned err = 0;
   for (uint64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+    const double *brow = base ? base + (poff ? hg_group_of(poff, Gp, r) : 0) * Kmax : nullptr;
     bool bad = false;
     double mx = -INFINITY;
     for (unsigned k = tid; k < Kmax; k += nthr) {
       const uint64_t e = r * Kmax + k;
       const double cnt = cnt32 ? (double)cnt32[e] : (double)cnt64[k];
-      const double shape = f * (base ? base[k] : base0) + cnt;
+      const double shape = f * (brow ? brow[k] : base0) + cnt;
       double lg = NAN;
       if (shape > 0.0 && isfinite(shape)) {
         const uint64_t ke = stb_mix64(key + (e + 1) * STB_GAMMA);
@@ -234,178 +260,57 @@ __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_scatter(uint64_t I, const 
   }
 }
 
-// one workgroup: the totals over the groups, then the words the host waits for
-__global__ __launch_bounds__(256) void k_hg_finish(uint64_t G, const unsigned long long *Cg, const uint32_t *Mg, const double *al,
-                                                   const unsigned *ctl, unsigned long long *host_out) {
-  __shared__ unsigned long long s_c, s_m;
-  if (threadIdx.x == 0) s_c = s_m = 0;
-  __syncthreads();
-  unsigned long long cs = 0, ms = 0;
-  for (uint64_t g = threadIdx.x; g < G; g += 256) {
-    cs += Cg[g];
-    ms += Mg[g];
-  }
-  if (cs) atomicAdd(&s_c, cs);
-  if (ms) atomicAdd(&s_m, ms);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    host_out[0] = ctl[0];
-    host_out[1] = (unsigned long long)__double_as_longlong(al[0]);
-    host_out[2] = s_c;
-    host_out[3] = s_m;
-  }
+// ------------------------------------------------------------------------------------------------
+// host side: the checks, the launches one by one (the step that queues them is htree.hip's stb_ht_sample), the grouped step
+
+stb_hg_geom stb_hg_geom_env(const char *waves_name, const char *form_name) {
+  const int nwi = stb_env_int(waves_name, 4);
+  const char *form = getenv(form_name);
+  stb_hg_geom geo;
+  geo.nw = nwi == 1 || nwi == 2 || nwi == 4 || nwi == 8 ? (unsigned)nwi : 4u;
+  geo.twave = form && !strcmp(form, "lane") ? 0xffffffffu : form && !strcmp(form, "wave") ? 0u : HG_TWAVE;
+  return geo;
 }
 
-// ------------------------------------------------------------------------------------------------
-// host side.  The scratch comes from the buffer cache and goes back behind the call's one wait.
-
-struct hg_scratch {
-  void *d = nullptr, *h = nullptr, *h_dev = nullptr, *stage = nullptr;
-  hipStream_t st = nullptr;
-  bool queued = false;  // work that uses the buffers may be on st: wait before the cache hands them on
-  ~hg_scratch() {
-    if (queued) (void)hipStreamSynchronize(st);
-    if (d) stb_pool_free(d);
-    if (h) stb_pool_free(h);
-    if (stage) stb_pool_free(stage);
-  }
-};
-
-static size_t hg_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int stb_hg_check_opts(const stb_hgroups_opts_t *opts, unsigned Kmax, const char *who) {
-  if (!opts) return stb_fail("%s: opts is required", who);
+int stb_hg_check_common(unsigned flags, const double *alpha, int levels, bool indexed, double gamma0, const double *gamma_host,
+                        double shape, double scale, unsigned Kmax, const char *who) {
   if (Kmax < 1 || Kmax > STB_TD_MAXK) return stb_fail("%s: Kmax=%u (1 to STB_TD_MAXK = %d)", who, Kmax, STB_TD_MAXK);
-  if (opts->flags & ~(STB_HG_KEEP_ROOT | STB_HG_SAMPLE_ALPHA)) return stb_fail("%s: unknown flags 0x%x", who, opts->flags);
-  if (!(opts->alpha > 0.0) || !std::isfinite(opts->alpha))
-    return stb_fail("%s: alpha=%g (must be > 0 and finite)", who, opts->alpha);
-  if (!(opts->flags & STB_HG_KEEP_ROOT)) {
-    if (opts->gamma_host) {
+  if (flags & ~(STB_HG_KEEP_ROOT | STB_HG_SAMPLE_ALPHA)) return stb_fail("%s: unknown flags 0x%x", who, flags);
+  if (!alpha) return stb_fail("%s: opts->alpha is required", who);
+  for (int l = 0; l < levels; l++)
+    if (!(alpha[l] > 0.0) || !std::isfinite(alpha[l]))
+      return indexed ? stb_fail("%s: alpha[%d]=%g (must be > 0 and finite)", who, l, alpha[l])
+                     : stb_fail("%s: alpha=%g (must be > 0 and finite)", who, alpha[l]);
+  if (!(flags & STB_HG_KEEP_ROOT)) {
+    if (gamma_host) {
       for (unsigned k = 0; k < Kmax; k++)
-        if (!(opts->gamma_host[k] > 0.0) || !std::isfinite(opts->gamma_host[k]))
-          return stb_fail("%s: gamma[%u]=%g (must be > 0 and finite)", who, k, opts->gamma_host[k]);
-    } else if (!(opts->gamma0 > 0.0) || !std::isfinite(opts->gamma0)) {
-      return stb_fail("%s: gamma0=%g (must be > 0 and finite)", who, opts->gamma0);
+        if (!(gamma_host[k] > 0.0) || !std::isfinite(gamma_host[k]))
+          return stb_fail("%s: gamma[%u]=%g (must be > 0 and finite)", who, k, gamma_host[k]);
+    } else if (!(gamma0 > 0.0) || !std::isfinite(gamma0)) {
+      return stb_fail("%s: gamma0=%g (must be > 0 and finite)", who, gamma0);
     }
   }
-  if (opts->flags & STB_HG_SAMPLE_ALPHA) {
-    if (!(opts->shape > 0.0) || !std::isfinite(opts->shape))
-      return stb_fail("%s: shape=%g (must be > 0 and finite)", who, opts->shape);
-    if (!(opts->scale > 0.0) || !std::isfinite(opts->scale))
-      return stb_fail("%s: scale=%g (must be > 0 and finite)", who, opts->scale);
+  if (flags & STB_HG_SAMPLE_ALPHA) {
+    if (!(shape > 0.0) || !std::isfinite(shape)) return stb_fail("%s: shape=%g (must be > 0 and finite)", who, shape);
+    if (!(scale > 0.0) || !std::isfinite(scale)) return stb_fail("%s: scale=%g (must be > 0 and finite)", who, scale);
   }
   return 0;
 }
 
-static void hg_clear(stb_hgroups_info_t *info) {
+int stb_hg_check_opts(const stb_hgroups_opts_t *opts, unsigned Kmax, const char *who) {
+  if (!opts) return stb_fail("%s: opts is required", who);
+  return stb_hg_check_common(opts->flags, &opts->alpha, 1, false, opts->gamma0, opts->gamma_host, opts->shape, opts->scale, Kmax, who);
+}
+
+void stb_hg_clear(stb_hgroups_info_t *info) {
   if (!info) return;
   info->alpha = NAN;
   info->tables = info->aux_tables = 0;
   info->error_word = info->reserved = 0;
 }
 
-int stb_hg_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
-                  const stb_hgroups_opts_t *opts, double *d_root, double *d_h, double *d_hgrp, uint32_t *d_c, uint32_t *d_m,
-                  uint64_t seed, uint64_t sweep, hipStream_t st, stb_hgroups_info_t *info, const char *who, bool *touched) {
-  hg_clear(info);
-  const bool keep_root = (opts->flags & STB_HG_KEEP_ROOT) != 0, draw_alpha = (opts->flags & STB_HG_SAMPLE_ALPHA) != 0;
-  const bool gvec = !keep_root && opts->gamma_host;
-  int nwi = stb_env_int("STB_HGROUPS_WAVES", 4);
-  const unsigned nw = nwi == 1 || nwi == 2 || nwi == 4 || nwi == 8 ? (unsigned)nwi : 4u;
-  const char *form = getenv("STB_HGROUPS_FORM");
-  const unsigned twave = form && !strcmp(form, "lane") ? 0xffffffffu : form && !strcmp(form, "wave") ? 0u : HG_TWAVE;
-  const size_t Gs = (size_t)G, cells = Gs * Kmax;
-  // scratch.  Zeroed: ctl (256 bytes), s[Kmax], Cg[G], Mg[G] -- and c.  Then N32[G], al[G], the range {0, G}, hyperb's L[G]
-  // and Y[G], gamma[Kmax], and whichever of c, m, hgrp the caller did not give
-  const size_t o_s = 256, o_Cg = o_s + hg_up(8 * (size_t)Kmax), o_Mg = o_Cg + hg_up(8 * Gs), o_N = o_Mg + hg_up(4 * Gs),
-               o_al = o_N + hg_up(4 * Gs), o_go = o_al + hg_up(8 * Gs), o_L = o_go + 256,
-               o_Y = o_L + (draw_alpha ? hg_up(8 * Gs) : 0), o_gam = o_Y + (draw_alpha ? hg_up(4 * Gs) : 0),
-               o_c = o_gam + (gvec ? hg_up(8 * (size_t)Kmax) : 0), o_m = o_c + (d_c ? 0 : hg_up(4 * cells)),
-               o_hg = o_m + (d_m ? 0 : hg_up(4 * cells)), bytes = o_hg + (d_hgrp ? 0 : hg_up(8 * cells));
-  hg_scratch sc;
-  sc.st = st;
-  if (stb_pool_malloc(&sc.d, bytes) != hipSuccess || stb_pool_malloc(&sc.h, 256, 1) != hipSuccess ||
-      hipHostGetDevicePointer(&sc.h_dev, sc.h, 0) != hipSuccess ||
-      (gvec && stb_pool_malloc(&sc.stage, 8 * (size_t)Kmax, 1) != hipSuccess))
-    return stb_fail("%s: out of memory for %zu bytes of scratch", who, bytes);
-  char *d = (char *)sc.d;
-  unsigned *ctl = (unsigned *)d;
-  unsigned long long *s = (unsigned long long *)(d + o_s), *Cg = (unsigned long long *)(d + o_Cg);
-  uint32_t *Mg = (uint32_t *)(d + o_Mg), *N32 = (uint32_t *)(d + o_N), *Y = (uint32_t *)(d + o_Y);
-  double *al = (double *)(d + o_al), *L = (double *)(d + o_L), *d_gam = gvec ? (double *)(d + o_gam) : nullptr;
-  uint64_t *goff1 = (uint64_t *)(d + o_go);
-  uint32_t *c = d_c ? d_c : (uint32_t *)(d + o_c), *m = d_m ? d_m : (uint32_t *)(d + o_m);
-  double *hgrp = d_hgrp ? d_hgrp : (double *)(d + o_hg);
-  volatile unsigned long long *h_out = (volatile unsigned long long *)sc.h;
-  h_out[0] = 0xffffffffull;
-  sc.queued = true;
-  HIPCHK(hipMemsetAsync(d, 0, o_N, st));
-  HIPCHK(hipMemsetAsync(c, 0, 4 * cells, st));
-  if (gvec) {
-    memcpy(sc.stage, opts->gamma_host, 8 * (size_t)Kmax);
-    HIPCHK(hipMemcpyAsync(d_gam, sc.stage, 8 * (size_t)Kmax, hipMemcpyHostToDevice, st));
-  }
-  const uint64_t key = stb_mix64(seed + (sweep + 1) * STB_GAMMA), keyR = stb_mix64(key ^ HG_SALT_R);
-  const unsigned cus = (unsigned)(stb_cu_count() > 0 ? stb_cu_count() : 1);
-  const uint64_t runs = ((uint64_t)I + HG_RUN - 1) / HG_RUN;
-  const unsigned gx_rest = (unsigned)((runs + nw - 1) / nw), cb = (Kmax + 63) / 64;
-  // few rows: each is cut into parts, so that the cells a wave takes (a group of many restaurants has tens of thousands
-  // of draws a cell) keep about 8 waves a compute unit busy
-  const uint64_t cap_y = (uint64_t)8 * cus / cb + 1, fill = cap_y * nw;
-  const unsigned parts = twave != 0xffffffffu && Gs < fill ? (unsigned)((fill + Gs - 1) / Gs < 1024 ? (fill + Gs - 1) / Gs : 1024) : 1u;
-  const uint64_t want_y = (Gs * parts + nw - 1) / nw;
-  const unsigned gy_aux = (unsigned)(want_y < cap_y ? want_y : cap_y);
-  const unsigned thr_row = 64u * nw < 64u * cb ? 64u * nw : 64u * cb;  // (no more waves than the row has columns for)
-  const uint64_t cap_rows = (uint64_t)32 * cus;
-  const unsigned gx_rows = (unsigned)(Gs < cap_rows ? Gs : cap_rows);
-  if (parts > 1) HIPCHK(hipMemsetAsync(m, 0, 4 * cells, st));
-  if (stb_hg_count_queue(I, d_koff, d_t, Kmax, G, d_goff, c, Cg, st)) return 1;
-  STB_LAUNCH(k_hg_aux, dim3(cb, gy_aux), dim3(64 * nw), st, Kmax, (uint64_t)G, (const uint32_t *)c, (const double *)d_root,
-             opts->alpha, key, twave, parts, m, Mg, s);
-  if (touched) *touched = true;
-  if (!keep_root)
-    STB_LAUNCH(k_hg_rows, dim3(1), dim3(thr_row), st, (uint64_t)1, Kmax, (const uint32_t *)nullptr, (const unsigned long long *)s,
-               (const double *)d_gam, opts->gamma0, (const double *)nullptr, keyR, d_root, ctl);
-  STB_LAUNCH(k_hg_prep, dim3((unsigned)((Gs + 255) / 256)), dim3(256), st, (uint64_t)G, (const unsigned long long *)Cg,
-             opts->alpha, N32, al, goff1, ctl);
-  if (draw_alpha &&
-      stb_hb_bgroups_queue(0.0, opts->shape, opts->scale, G, N32, Mg, 1, goff1, al, L, Y, seed ^ HG_SALT_A, sweep, st, who))
-    return 1;
-  STB_LAUNCH(k_hg_rows, dim3(gx_rows), dim3(thr_row), st, (uint64_t)G, Kmax, (const uint32_t *)c,
-             (const unsigned long long *)nullptr, (const double *)d_root, 0.0, (const double *)al, key, hgrp, ctl);
-  STB_LAUNCH(k_hg_scatter, dim3(gx_rest), dim3(64 * nw), st, (uint64_t)I, d_koff, Kmax, (uint64_t)G, d_goff,
-             (const double *)hgrp, d_h);
-  STB_LAUNCH(k_hg_finish, dim3(1), dim3(256), st, (uint64_t)G, (const unsigned long long *)Cg, (const uint32_t *)Mg,
-             (const double *)al, (const unsigned *)ctl, (unsigned long long *)sc.h_dev);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  sc.queued = false;
-  const unsigned err = (unsigned)h_out[0];
-  if (info) {
-    const unsigned long long bits = h_out[1];
-    memcpy(&info->alpha, &bits, sizeof(double));
-    info->tables = h_out[2];
-    info->aux_tables = h_out[3];
-    info->error_word = err;
-  }
-  if (err)
-    return stb_fail("%s: failed, error word 0x%x (1: a Gamma draw was not accepted within %d attempts; 2: a normaliser is not "
-                    "positive and finite; 4: a shape alpha r_k + c_gk is not positive and finite; 8: a group has more than "
-                    "2^32 - 1 tables) (seed=%llu, sweep=%llu); the outputs are undefined",
-                    who, err, HQ_CAP, (unsigned long long)seed, (unsigned long long)sweep);
-  if (draw_alpha) {
-    stb_bgroups_info_t bi;
-    if (stb_hb_bgroups_answer(1, &bi, who)) return 1;
-    if (bi.kept_groups) return stb_fail("%s: the concentration's draw is not a positive finite double; the outputs are undefined", who);
-  }
-  return 0;
-}
-
-// k_hg_count as stb_hg_sample launches it, for a caller that wants the counts alone (the collapsed log joint, tindic_obj.hip)
 int stb_hg_count_queue(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
-                       uint32_t *d_c, unsigned long long *d_Cg, hipStream_t st) {
-  const int nwi = stb_env_int("STB_HGROUPS_WAVES", 4);
-  const unsigned nw = nwi == 1 || nwi == 2 || nwi == 4 || nwi == 8 ? (unsigned)nwi : 4u;
+                       uint32_t *d_c, unsigned long long *d_Cg, unsigned nw, hipStream_t st) {
   const uint64_t runs = ((uint64_t)I + HG_RUN - 1) / HG_RUN;
   STB_LAUNCH(k_hg_count, dim3((unsigned)((runs + nw - 1) / nw)), dim3(64 * nw), st, (uint64_t)I, d_koff, d_t, Kmax, (uint64_t)G,
              d_goff, d_c, d_Cg);
@@ -413,12 +318,41 @@ int stb_hg_count_queue(int I, const uint64_t *d_koff, const uint16_t *d_t, unsig
   return 0;
 }
 
-// the root's row and the scatter as stb_hg_sample launches them, for the tree step (htree.hip)
+int stb_hg_aux_queue(unsigned Kmax, uint64_t G, const uint32_t *d_c, uint64_t Gp, const uint64_t *d_poff, const double *d_base,
+                     double alpha, uint64_t key, stb_hg_geom geo, uint32_t *d_m, uint32_t *d_Mv, uint32_t *d_cpar,
+                     unsigned long long *d_Cpar, unsigned long long *d_s, hipStream_t st) {
+  const unsigned cus = (unsigned)stb_cu_count(), cb = (Kmax + 63) / 64, nw = geo.nw;
+  // few rows: each is cut into parts, so that the cells a wave takes keep about 8 waves a compute unit busy -- a group of
+  // many restaurants has tens of thousands of draws a cell, a high node collects the auxiliary tables of a whole subtree
+  const uint64_t cap_y = (uint64_t)8 * cus / cb + 1, fill = cap_y * nw;
+  const unsigned parts = geo.twave != 0xffffffffu && G < fill ? (unsigned)((fill + G - 1) / G < 1024 ? (fill + G - 1) / G : 1024) : 1u;
+  // whole rows are light: two a wave, so that half as many waves add their sums to the same s_k or parent
+  const uint64_t per = parts > 1 ? 1 : 2, want_y = (G * parts + nw * per - 1) / (nw * per);
+  if (parts > 1 && d_m) HIPCHK(hipMemsetAsync(d_m, 0, 4 * (size_t)G * Kmax, st));
+  STB_LAUNCH(k_hg_aux, dim3(cb, (unsigned)(want_y < cap_y ? want_y : cap_y)), dim3(64 * nw), st, Kmax, G, d_c, Gp, d_poff, d_base,
+             alpha, key, geo.twave, parts, d_m, d_Mv, d_cpar, d_Cpar, d_s);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+static unsigned hg_row_threads(unsigned Kmax, unsigned nw) {  // (no more waves than the row has columns for)
+  const unsigned cb = (Kmax + 63) / 64;
+  return 64u * (nw < cb ? nw : cb);
+}
+
 int stb_hg_root_queue(unsigned Kmax, const unsigned long long *d_s, const double *d_gam, double gamma0, uint64_t key,
                       double *d_root, unsigned *d_ctl, unsigned nw, hipStream_t st) {
-  const unsigned cb = (Kmax + 63) / 64, thr_row = 64u * nw < 64u * cb ? 64u * nw : 64u * cb;
-  STB_LAUNCH(k_hg_rows, dim3(1), dim3(thr_row), st, (uint64_t)1, Kmax, (const uint32_t *)nullptr, d_s, d_gam, gamma0,
-             (const double *)nullptr, stb_mix64(key ^ HG_SALT_R), d_root, d_ctl);
+  STB_LAUNCH(k_hg_rows, dim3(1), dim3(hg_row_threads(Kmax, nw)), st, (uint64_t)1, Kmax, (const uint32_t *)nullptr, d_s, (uint64_t)1,
+             (const uint64_t *)nullptr, d_gam, gamma0, (const double *)nullptr, stb_mix64(key ^ HG_SALT_R), d_root, d_ctl);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int stb_hg_rows_queue(uint64_t G, unsigned Kmax, const uint32_t *d_c, uint64_t Gp, const uint64_t *d_poff, const double *d_base,
+                      const double *d_factor, uint64_t key, double *d_out, unsigned *d_ctl, unsigned nw, hipStream_t st) {
+  const uint64_t cap_rows = (uint64_t)32 * (unsigned)stb_cu_count();
+  STB_LAUNCH(k_hg_rows, dim3((unsigned)(G < cap_rows ? G : cap_rows)), dim3(hg_row_threads(Kmax, nw)), st, G, Kmax, d_c,
+             (const unsigned long long *)nullptr, Gp, d_poff, d_base, 0.0, d_factor, key, d_out, d_ctl);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -432,6 +366,31 @@ int stb_hg_scatter_queue(int I, const uint64_t *d_koff, unsigned Kmax, int G, co
   return 0;
 }
 
+// the grouped step is the tree's with one level: the ranges (or none) are level 1's, the root sits right above
+int stb_hg_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
+                  const stb_hgroups_opts_t *opts, double *d_root, double *d_h, double *d_hgrp, uint32_t *d_c, uint32_t *d_m,
+                  uint64_t seed, uint64_t sweep, hipStream_t st, stb_hgroups_info_t *info, const char *who, bool *touched) {
+  stb_hg_clear(info);
+  stb_htree_opts_t o;
+  memset(&o, 0, sizeof o);
+  o.levels = 1;
+  o.gamma0 = opts->gamma0;
+  o.shape = opts->shape;
+  o.scale = opts->scale;
+  o.gamma_host = opts->gamma_host;
+  o.flags = opts->flags;  // (STB_HG_KEEP_ROOT and _SAMPLE_ALPHA are STB_HT_'s)
+  stb_htree_info_t ti;
+  const int rc = stb_ht_sample(I, d_koff, d_t, Kmax, &G, &d_goff, &o, &opts->alpha, d_root, &d_hgrp, d_h, &d_c, &d_m, seed, sweep, st, &ti,
+                               stb_hg_geom_env("STB_HGROUPS_WAVES", "STB_HGROUPS_FORM"), who, touched);
+  if (info) {
+    info->alpha = ti.alpha[0];
+    info->tables = ti.tables[0];
+    info->aux_tables = ti.aux_tables[0];
+    info->error_word = ti.error_word;
+  }
+  return rc;
+}
+
 // ---- the raw layer ------------------------------------------------------------------------------------------------
 
 extern "C" int stb_sample_hgroups(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, int G, const uint64_t *d_goff,
@@ -439,7 +398,7 @@ extern "C" int stb_sample_hgroups(int I, const uint64_t *d_koff, const uint16_t 
                                   uint32_t *d_m, uint64_t seed, uint64_t sweep, void *stream, stb_hgroups_info_t *info) {
   STB_ENTRY;
   const char *who = "stb_sample_hgroups";
-  hg_clear(info);
+  stb_hg_clear(info);
   if (!d_koff || !d_t || !d_root || !d_h) return stb_fail("%s: d_koff, d_t, d_root and d_h are required", who);
   if (I < 1) return stb_fail("%s: I=%d (must be >= 1)", who, I);
   if (stb_hg_check_opts(opts, Kmax, who)) return 1;

@@ -7,118 +7,28 @@
 //     alpha'_l            Teh's auxiliaries for all levels in one hyperb step: every node a "restaurant" (N = C_v, T = M_v),
 //                         a range a level
 //     down, l = L .. 1    h'_v ~ Dirichlet(alpha'_l h'_par(v),k + c_vk), the parent's new row
-//
-//   k_hg_count    (hgroups.hip) level 1's c and C
-//   k_ht_aux      a level's m, M_v, and its parents' c and C: lanes along k, a wave a run of successive rows; the parent's
-//                 column sums stay in registers while the parent does not change (integers: atomics)
-//   k_hg_rows     (hgroups.hip) the root's row
+// stb_ht_sample is that step for every caller, stb_sample_hgroups (L = 1) included.  It queues hgroups.hip's kernels through
+// hgroups.h's entries -- k_hg_count, a k_hg_aux a level, the root's k_hg_rows, a k_hg_rows a level, k_hg_scatter -- and
+// between them
 //   k_ht_prep     every node's C as hyperb's N (and the 2^32 check), its level's alpha, the L ranges
-//   k_ht_rows     a Dirichlet row a workgroup, its base row the parent's
-//   k_hg_scatter  (hgroups.hip) level 1's rows to the pairs
 //   k_ht_finish   error word, the L concentrations, the totals of every level to pinned words
-// All are queued back to back, hyperb's three launches among them; the call waits once.  No kernel waits for another
-// workgroup.
-//
-// Streams: key = mix(seed + (sweep+1) gamma); key_1 = key, key_l = mix(key ^ (HT_SALT_L + l)) for l >= 2.  Cell e = v Kmax + k
-// of level l owns mix(key_l + (e+1) gamma) and its Bernoulli draws that key's ^ HG_SALT_Y substream; the root and the
-// concentration as hgroups.hip's.  Associations are hgroups.hip's (FP64, no contraction): w = alpha_l base_k one product, a
-// row's shapes alpha'_l base'_k + (double)c.  With L = 1 every launch computes what stb_sample_hgroups' does.  Counts and m are
-// integers, so no bit depends on STB_HTREE_WAVES = 1, 2, 4 or 8 or on STB_HTREE_FORM = lane | wave.
+// and hyperb's three launches; the call waits once.  No kernel waits for another workgroup.  The streams, the FP64
+// associations and why no bit depends on the launch geometry are stated in hgroups.hip's header.
 
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "stb_common.h"
-#include "gamma_dev.h"
 #include "hyperb.h"
-#include "hgroups.h"
 #include "htree.h"
-#include "hg_cell.h"
-
-#pragma clang fp contract(off)
-
-#define HT_MAXTHREADS 512
-#define HT_ERR_CAP 1u
-#define HT_ERR_Z 2u
-#define HT_ERR_SHAPE 4u
-#define HT_ERR_TOTAL 8u
+#include "hg_cell.h"  // HG_SALT_A
 
 struct ht_levels {  // by value to k_ht_prep and k_ht_finish
   double alpha[STB_HT_MAXL];
   uint64_t noff[STB_HT_MAXL + 1];  // level l's nodes are noff[l] .. noff[l+1] - 1 of the concatenation
   unsigned L;
 };
-
-// the last range that starts at or before i (empty ranges in front of it start there too)
-__device__ __forceinline__ uint64_t ht_range_of(const uint64_t *off, uint64_t G, uint64_t i) {
-  uint64_t lo = 0, hi = G;
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// what a wave holds of parent `par`: its lanes' column sums, and (lane 0) the rows' totals
-__device__ __forceinline__ void ht_flush(unsigned long long &acc, unsigned long long &tot, uint64_t par, unsigned Kmax, unsigned k,
-                                         bool live, unsigned lane, uint32_t *cpar, unsigned long long *Cpar, unsigned long long *s) {
-  if (live && acc) {
-    if (cpar) atomicAdd(&cpar[par * Kmax + k], (unsigned)acc);  // (a wrap shows in C_par > 2^32 - 1: error 8)
-    else atomicAdd(&s[k], acc);
-  }
-  acc = 0;
-  if (lane == 0 && tot && Cpar) atomicAdd(&Cpar[par], tot);
-  tot = 0;
-}
-
-// workgroup (x, y): the columns 64 x .. 64 x + 63.  The G rows, each cut into `parts` (hg_cell.h), are dealt to the grid's
-// waves in runs of successive (row, part).  poff[Gp + 1] cuts the rows into their parents' ranges (null: one parent, row 0 of
-// base).  The parents' counts go to cpar[Gp Kmax] and Cpar[Gp], or, above the top level, to s[Kmax] (cpar and Cpar null).
-// m may be null; with parts > 1 it arrives zeroed
-__global__ __launch_bounds__(HT_MAXTHREADS) void k_ht_aux(unsigned Kmax, uint64_t G, const uint32_t *c, uint64_t Gp, const uint64_t *poff,
-                                                          const double *base, double alpha, uint64_t key, unsigned twave, unsigned parts,
-                                                          uint32_t *m, uint32_t *Mv, uint32_t *cpar, unsigned long long *Cpar,
-                                                          unsigned long long *s) {
-  const unsigned lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (what follows from it stays in scalar registers)
-  const unsigned k = blockIdx.x * 64 + lane;
-  const bool live = k < Kmax;  // (no lane leaves: the wave's shuffles need them all)
-  const uint64_t total = G * parts, waves = (uint64_t)gridDim.y * nw, run = (total + waves - 1) / waves;
-  const uint64_t q0 = ((uint64_t)blockIdx.y * nw + wave) * run;
-  if (q0 >= total) return;  // (the whole wave)
-  const uint64_t q1 = q0 + run < total ? q0 + run : total;
-  uint64_t par = poff ? ht_range_of(poff, Gp, q0 / parts) : 0;
-  unsigned long long acc = 0, tot = 0;
-  for (uint64_t q = q0; q < q1; q++) {
-    const uint64_t g = q / parts;
-    const unsigned p = (unsigned)(q % parts);
-    if (poff) {
-      uint64_t pn = par;
-      while (pn + 1 < Gp && poff[pn + 1] <= g) pn++;
-      if (pn != par) {  // (uniform over the wave)
-        ht_flush(acc, tot, par, Kmax, k, live, lane, cpar, Cpar, s);
-        par = pn;
-      }
-    }
-    const uint64_t e = g * Kmax + k;
-    const unsigned cc = live ? c[e] : 0u;
-    const double w = live ? alpha * base[par * Kmax + k] : 1.0;
-    const uint64_t ky = stb_mix64(stb_mix64(key + (e + 1) * STB_GAMMA) ^ HG_SALT_Y);
-    const unsigned mm = hg_cell(cc, w, ky, p, parts, twave, lane);
-    if (live && m) {
-      if (parts == 1) m[e] = mm;
-      else if (mm) atomicAdd(&m[e], mm);
-    }
-    acc += mm;
-    unsigned row = mm;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) row += __shfl_down(row, off, 64);
-    if (lane == 0 && row) atomicAdd(&Mv[g], row);
-    tot += row;  // (lane 0's is the row's)
-  }
-  ht_flush(acc, tot, par, Kmax, k, live, lane, cpar, Cpar, s);
-}
 
 __global__ __launch_bounds__(256) void k_ht_prep(ht_levels lv, const unsigned long long *Cv, uint32_t *N32, double *al, uint64_t *loff,
                                                  unsigned *ctl) {
@@ -128,65 +38,9 @@ __global__ __launch_bounds__(256) void k_ht_prep(ht_levels lv, const unsigned lo
   unsigned l = 0;
   while (l + 1 < lv.L && lv.noff[l + 1] <= v) l++;
   const unsigned long long C = Cv[v];
-  if (C > 0xffffffffull) __hip_atomic_fetch_or(&ctl[0], HT_ERR_TOTAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (C > 0xffffffffull) __hip_atomic_fetch_or(&ctl[0], HG_ERR_TOTAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   N32[v] = (uint32_t)C;
   al[v] = lv.alpha[l];
-}
-
-// k_hg_rows with a base row per output row: a workgroup a row (rows r = blockIdx.x, + gridDim.x, ...), its threads strided
-// over k: shape_k = f base[par(r) Kmax + k] + (double)cnt[r Kmax + k], f = *factor; par(r) from poff[Gp + 1] (null: row 0);
-// cell e = r Kmax + k
-__global__ __launch_bounds__(HT_MAXTHREADS) void k_ht_rows(uint64_t rows, unsigned Kmax, const uint32_t *cnt, uint64_t Gp,
-                                                           const uint64_t *poff, const double *base, const double *factor, uint64_t key,
-                                                           double *out, unsigned *ctl) {
-  __shared__ double sv[STB_TD_MAXK];
-  __shared__ double s_max[HT_MAXTHREADS / 64];
-  __shared__ double s_Z;
-  const unsigned nthr = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
-  const double f = *factor;
-  unsigned err = 0;
-  for (uint64_t r = blockIdx.x; r < rows; r += gridDim.x) {
-    const double *brow = base + (poff ? ht_range_of(poff, Gp, r) : 0) * Kmax;
-    bool bad = false;
-    double mx = -INFINITY;
-    for (unsigned k = tid; k < Kmax; k += nthr) {
-      const uint64_t e = r * Kmax + k;
-      const double shape = f * brow[k] + (double)cnt[e];
-      double lg = NAN;
-      if (shape > 0.0 && isfinite(shape)) {
-        const uint64_t ke = stb_mix64(key + (e + 1) * STB_GAMMA);
-        uint64_t j = 0;
-        lg = hq_log_gamma(shape, ke, j, bad);
-      } else {
-        err |= HT_ERR_SHAPE;
-      }
-      sv[k] = lg;
-      if (lg > mx) mx = lg;  // (a NaN is never greater)
-    }
-    if (bad) err |= HT_ERR_CAP;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const double o = __shfl_xor(mx, off, 64);
-      mx = o > mx ? o : mx;
-    }
-    if (lane == 0) s_max[wave] = mx;
-    __syncthreads();
-    double M = s_max[0];
-    for (unsigned q = 1; q < nw; q++) M = s_max[q] > M ? s_max[q] : M;
-    for (unsigned k = tid; k < Kmax; k += nthr) sv[k] = exp(sv[k] - M);
-    __syncthreads();
-    if (tid == 0) {
-      double z = sv[0];
-      for (unsigned k = 1; k < Kmax; k++) z = z + sv[k];
-      s_Z = z;
-      if (!(z > 0.0 && isfinite(z))) err |= HT_ERR_Z;
-    }
-    __syncthreads();
-    const double Z = s_Z;
-    for (unsigned k = tid; k < Kmax; k += nthr) out[r * Kmax + k] = sv[k] / Z;
-    __syncthreads();  // (sv, s_max and s_Z are the next row's)
-  }
-  if (err) __hip_atomic_fetch_or(&ctl[0], err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // one workgroup: every level's totals, then the words the host waits for: [0] the error word, [1 + l] alpha'_l's bits,
@@ -232,7 +86,7 @@ struct ht_scratch {
 
 static size_t ht_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static void ht_clear(stb_htree_info_t *info) {
+void stb_ht_clear(stb_htree_info_t *info) {
   if (!info) return;
   for (int l = 0; l < STB_HT_MAXL; l++) {
     info->alpha[l] = NAN;
@@ -244,28 +98,7 @@ static void ht_clear(stb_htree_info_t *info) {
 int stb_ht_check_opts(const stb_htree_opts_t *opts, const double *alpha, unsigned Kmax, const char *who) {
   if (!opts) return stb_fail("%s: opts is required", who);
   if (opts->levels < 1 || opts->levels > STB_HT_MAXL) return stb_fail("%s: levels=%d (1 to STB_HT_MAXL = %d)", who, opts->levels, STB_HT_MAXL);
-  if (Kmax < 1 || Kmax > STB_TD_MAXK) return stb_fail("%s: Kmax=%u (1 to STB_TD_MAXK = %d)", who, Kmax, STB_TD_MAXK);
-  if (opts->flags & ~(STB_HT_KEEP_ROOT | STB_HT_SAMPLE_ALPHA)) return stb_fail("%s: unknown flags 0x%x", who, opts->flags);
-  if (!alpha) return stb_fail("%s: opts->alpha is required", who);
-  for (int l = 0; l < opts->levels; l++)
-    if (!(alpha[l] > 0.0) || !std::isfinite(alpha[l]))
-      return stb_fail("%s: alpha[%d]=%g (must be > 0 and finite)", who, l, alpha[l]);
-  if (!(opts->flags & STB_HT_KEEP_ROOT)) {
-    if (opts->gamma_host) {
-      for (unsigned k = 0; k < Kmax; k++)
-        if (!(opts->gamma_host[k] > 0.0) || !std::isfinite(opts->gamma_host[k]))
-          return stb_fail("%s: gamma[%u]=%g (must be > 0 and finite)", who, k, opts->gamma_host[k]);
-    } else if (!(opts->gamma0 > 0.0) || !std::isfinite(opts->gamma0)) {
-      return stb_fail("%s: gamma0=%g (must be > 0 and finite)", who, opts->gamma0);
-    }
-  }
-  if (opts->flags & STB_HT_SAMPLE_ALPHA) {
-    if (!(opts->shape > 0.0) || !std::isfinite(opts->shape))
-      return stb_fail("%s: shape=%g (must be > 0 and finite)", who, opts->shape);
-    if (!(opts->scale > 0.0) || !std::isfinite(opts->scale))
-      return stb_fail("%s: scale=%g (must be > 0 and finite)", who, opts->scale);
-  }
-  return 0;
+  return stb_hg_check_common(opts->flags, alpha, opts->levels, true, opts->gamma0, opts->gamma_host, opts->shape, opts->scale, Kmax, who);
 }
 
 int stb_ht_check_ranges(int level, int G, const uint64_t *off, uint64_t below, const char *who) {
@@ -280,15 +113,11 @@ int stb_ht_check_ranges(int level, int G, const uint64_t *off, uint64_t below, c
 int stb_ht_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned Kmax, const int *G_host, const uint64_t *const *d_off,
                   const stb_htree_opts_t *opts, const double *alpha, double *d_root, double *const *d_hnode, double *d_h,
                   uint32_t *const *d_c, uint32_t *const *d_m, uint64_t seed, uint64_t sweep, hipStream_t st, stb_htree_info_t *info,
-                  const char *who, bool *touched) {
-  ht_clear(info);
-  const unsigned L = (unsigned)opts->levels;
+                  stb_hg_geom geo, const char *who, bool *touched) {
+  stb_ht_clear(info);
+  const unsigned L = (unsigned)opts->levels, nw = geo.nw;
   const bool keep_root = (opts->flags & STB_HT_KEEP_ROOT) != 0, draw_alpha = (opts->flags & STB_HT_SAMPLE_ALPHA) != 0;
   const bool gvec = !keep_root && opts->gamma_host;
-  int nwi = stb_env_int("STB_HTREE_WAVES", 4);
-  const unsigned nw = nwi == 1 || nwi == 2 || nwi == 4 || nwi == 8 ? (unsigned)nwi : 4u;
-  const char *form = getenv("STB_HTREE_FORM");
-  const unsigned twave = form && !strcmp(form, "lane") ? 0xffffffffu : form && !strcmp(form, "wave") ? 0u : HG_TWAVE;
   ht_levels lv;
   memset(&lv, 0, sizeof lv);
   lv.L = L;
@@ -341,24 +170,16 @@ int stb_ht_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned K
   const uint64_t key = stb_mix64(seed + (sweep + 1) * STB_GAMMA);
   uint64_t keys[STB_HT_MAXL];
   for (unsigned l = 0; l < L; l++) keys[l] = l == 0 ? key : stb_mix64(key ^ (HT_SALT_L + (uint64_t)(l + 1)));
-  const unsigned cus = (unsigned)(stb_cu_count() > 0 ? stb_cu_count() : 1);
-  const unsigned cb = (Kmax + 63) / 64;
-  const unsigned thr_row = 64u * nw < 64u * cb ? 64u * nw : 64u * cb;  // (no more waves than the row has columns for)
-  const uint64_t cap_y = (uint64_t)8 * cus / cb + 1, fill = cap_y * nw, cap_rows = (uint64_t)32 * cus;
-  if (stb_hg_count_queue(I, d_koff, d_t, Kmax, G_host[0], d_off[0], c[0], Cv, st)) return 1;
+  // level l's parents: the nodes of level l + 1 and their stored rows, or, above the top level, the root alone
+  auto Gp = [&](unsigned l) { return l + 1 == L ? (uint64_t)1 : (uint64_t)G_host[l + 1]; };
+  auto poff = [&](unsigned l) { return l + 1 == L ? (const uint64_t *)nullptr : d_off[l + 1]; };
+  auto base = [&](unsigned l) { return l + 1 == L ? (const double *)d_root : (const double *)d_hnode[l + 1]; };
+  if (stb_hg_count_queue(I, d_koff, d_t, Kmax, G_host[0], d_off[0], c[0], Cv, nw, st)) return 1;
   for (unsigned l = 0; l < L; l++) {  // up
-    const size_t Gs = (size_t)G_host[l];
-    // few rows: each is cut into parts, so that the cells a wave takes keep about 8 waves a compute unit busy -- a high node
-    // collects the auxiliary tables of a whole subtree in one cell
-    const unsigned parts = twave != 0xffffffffu && Gs < fill ? (unsigned)((fill + Gs - 1) / Gs < 1024 ? (fill + Gs - 1) / Gs : 1024) : 1u;
-    const uint64_t want_y = (Gs * parts + nw - 1) / nw;
-    const unsigned gy = (unsigned)(want_y < cap_y ? want_y : cap_y);
     const bool top = l + 1 == L;
-    if (parts > 1 && m[l]) HIPCHK(hipMemsetAsync(m[l], 0, 4 * Gs * Kmax, st));
-    STB_LAUNCH(k_ht_aux, dim3(cb, gy), dim3(64 * nw), st, Kmax, (uint64_t)Gs, (const uint32_t *)c[l],
-               top ? (uint64_t)1 : (uint64_t)G_host[l + 1], top ? (const uint64_t *)nullptr : d_off[l + 1],
-               top ? (const double *)d_root : (const double *)d_hnode[l + 1], alpha[l], keys[l], twave, parts, m[l],
-               Mv + lv.noff[l], top ? (uint32_t *)nullptr : c[l + 1], top ? (unsigned long long *)nullptr : Cv + lv.noff[l + 1], s);
+    if (stb_hg_aux_queue(Kmax, (uint64_t)G_host[l], c[l], Gp(l), poff(l), base(l), alpha[l], keys[l], geo, m[l], Mv + lv.noff[l],
+                         top ? nullptr : c[l + 1], top ? nullptr : Cv + lv.noff[l + 1], s, st))
+      return 1;
   }
   if (touched) *touched = true;
   if (!keep_root && stb_hg_root_queue(Kmax, s, d_gam, opts->gamma0, key, d_root, ctl, nw, st)) return 1;
@@ -366,15 +187,10 @@ int stb_ht_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned K
   if (draw_alpha && stb_hb_bgroups_queue(0.0, opts->shape, opts->scale, (int)NV, N32, Mv, (int)L, loff, al, Lh, Y, seed ^ HG_SALT_A,
                                          sweep, st, who))
     return 1;
-  for (unsigned l = L; l-- > 0;) {  // down
-    const size_t Gs = (size_t)G_host[l];
-    const bool top = l + 1 == L;
-    const unsigned gx = (unsigned)(Gs < cap_rows ? Gs : cap_rows);
-    STB_LAUNCH(k_ht_rows, dim3(gx), dim3(thr_row), st, (uint64_t)Gs, Kmax, (const uint32_t *)c[l],
-               top ? (uint64_t)1 : (uint64_t)G_host[l + 1], top ? (const uint64_t *)nullptr : d_off[l + 1],
-               top ? (const double *)d_root : (const double *)d_hnode[l + 1], (const double *)(al + lv.noff[l]), keys[l],
-               l == 0 ? h1 : d_hnode[l], ctl);
-  }
+  for (unsigned l = L; l-- > 0;)  // down
+    if (stb_hg_rows_queue((uint64_t)G_host[l], Kmax, c[l], Gp(l), poff(l), base(l), al + lv.noff[l], keys[l], l == 0 ? h1 : d_hnode[l],
+                          ctl, nw, st))
+      return 1;
   if (stb_hg_scatter_queue(I, d_koff, Kmax, G_host[0], d_off[0], h1, d_h, nw, st)) return 1;
   STB_LAUNCH(k_ht_finish, dim3(1), dim3(256), st, lv, (const unsigned long long *)Cv, (const uint32_t *)Mv, (const double *)al,
              (const unsigned *)ctl, (unsigned long long *)sc.h_dev);
@@ -393,8 +209,9 @@ int stb_ht_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned K
   }
   if (err)
     return stb_fail("%s: failed, error word 0x%x (1: a Gamma draw was not accepted within %d attempts; 2: a normaliser is not "
-                    "positive and finite; 4: a shape alpha h_k + c_vk is not positive and finite; 8: a node has more than "
-                    "2^32 - 1 tables) (seed=%llu, sweep=%llu); the outputs are undefined",
+                    "positive and finite; 4: a shape alpha base_k + c_k (base the row above, the root at the top) is not positive "
+                    "and finite; 8: a group or node has more than 2^32 - 1 tables) (seed=%llu, sweep=%llu); the outputs are "
+                    "undefined",
                     who, err, HQ_CAP, (unsigned long long)seed, (unsigned long long)sweep);
   if (draw_alpha) {
     stb_bgroups_info_t bi;
@@ -412,7 +229,7 @@ extern "C" int stb_sample_htree(int I, const uint64_t *d_koff, const uint16_t *d
                                 stb_htree_info_t *info) {
   STB_ENTRY;
   const char *who = "stb_sample_htree";
-  ht_clear(info);
+  stb_ht_clear(info);
   if (!d_koff || !d_t || !d_root || !d_h || !G_host || !d_off || !d_hnode)
     return stb_fail("%s: d_koff, d_t, G_host, d_off, d_root, d_hnode and d_h are required", who);
   if (I < 1) return stb_fail("%s: I=%d (must be >= 1)", who, I);
@@ -434,6 +251,6 @@ extern "C" int stb_sample_htree(int I, const uint64_t *d_koff, const uint16_t *d
   HIPCHK(hipStreamSynchronize(st));
   for (int l = 0; l < L; l++)
     if (stb_ht_check_ranges(l, G_host[l], off[l].data(), l == 0 ? (uint64_t)I : (uint64_t)G_host[l - 1], who)) return 1;
-  return stb_ht_sample(I, d_koff, d_t, Kmax, G_host, d_off, opts, opts->alpha, d_root, d_hnode, d_h, d_c, d_m, seed, sweep, st, info, who,
-                       nullptr);
+  return stb_ht_sample(I, d_koff, d_t, Kmax, G_host, d_off, opts, opts->alpha, d_root, d_hnode, d_h, d_c, d_m, seed, sweep, st, info,
+                       stb_hg_geom_env("STB_HTREE_WAVES", "STB_HTREE_FORM"), who, nullptr);
 }

@@ -858,11 +858,7 @@ extern "C" int stb_tindic_sample_hgroups(stb_tindic_t *s, const stb_hgroups_opts
                                          stb_hgroups_info_t *info) {
   STB_ENTRY;
   const char *who = "stb_tindic_sample_hgroups";
-  if (info) {
-    info->alpha = NAN;
-    info->tables = info->aux_tables = 0;
-    info->error_word = info->reserved = 0;
-  }
+  stb_hg_clear(info);
   if (!s) return stb_fail("%s: null object", who);
   if (!opts) return stb_fail("%s: opts is required", who);
   if (s->flags & STB_TI_REF_ODDS_FLAG)
@@ -980,13 +976,7 @@ extern "C" int stb_tindic_sample_htree(stb_tindic_t *s, const stb_htree_opts_t *
                                        stb_htree_info_t *info) {
   STB_ENTRY;
   const char *who = "stb_tindic_sample_htree";
-  if (info) {
-    for (int l = 0; l < STB_HT_MAXL; l++) {
-      info->alpha[l] = NAN;
-      info->tables[l] = info->aux_tables[l] = 0;
-    }
-    info->error_word = info->reserved = 0;
-  }
+  stb_ht_clear(info);
   if (!s) return stb_fail("%s: null object", who);
   if (!opts) return stb_fail("%s: opts is required", who);
   if (s->flags & STB_TI_REF_ODDS_FLAG)
@@ -1008,7 +998,7 @@ extern "C" int stb_tindic_sample_htree(stb_tindic_t *s, const stb_htree_opts_t *
   stb_htree_info_t mine;
   if (!info) info = &mine;
   const int rc = stb_ht_sample(s->I, s->d_koff, s->d_t, s->maxK, s->ht_G, s->d_htoff, opts, alpha, s->d_hroot, s->d_htnode, h.d, nullptr,
-                               nullptr, seed, sweep, s->st, info, who, &touched);
+                               nullptr, seed, sweep, s->st, info, stb_hg_geom_env("STB_HTREE_WAVES", "STB_HTREE_FORM"), who, &touched);
   h.settle(touched, rc);
   if (touched) s->ht_have_rows1 = !rc;
   if (touched && !rc) {
@@ -1146,7 +1136,9 @@ extern "C" int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const do
                               s->st) != hipSuccess))
     return STB_STREAM_FAIL(who);
   if (want_root && stb_dm_root_queue(Kmax, s->d_hroot, d_gam, opts->gamma0, (double *)h_dev, s->st)) return 1;
-  if (stb_hg_count_queue(s->I, s->d_koff, s->d_t, Kmax, G, flat ? goff1 : s->d_hgoff, c, Cg, s->st)) return 1;
+  if (stb_hg_count_queue(s->I, s->d_koff, s->d_t, Kmax, G, flat ? goff1 : s->d_hgoff, c, Cg,
+                         stb_hg_geom_env("STB_HGROUPS_WAVES", "STB_HGROUPS_FORM").nw, s->st))
+    return 1;
   // flat: w = gamma, scale 1; grouped: w = the root (none: 1 / Kmax each), scale alpha
   if (stb_dm_run(c, (uint64_t)G, Kmax, Kmax, STB_DM_ROWS, flat ? d_gam : s->d_hroot, flat ? opts->gamma0 : 1.0 / (double)Kmax, alpha,
                  nullptr, nullptr, &info->tables, &info->dm_tables, s->st, who))
@@ -1236,7 +1228,7 @@ extern "C" int stb_tindic_sample_gamma(stb_tindic_t *s, const double *base_host,
   memcpy(head_host.data(), range, sizeof(range));
   if (ti_dc_stage(sc, head, head_host.data(), base_host, Kmax, &d, &d_base, who)) return 1;
   if (stb_hg_count_queue(s->I, s->d_koff, s->d_t, Kmax, 1, (const uint64_t *)d, (uint32_t *)(d + o_c), (unsigned long long *)(d + o_C),
-                         s->st))
+                         stb_hg_geom_env("STB_HGROUPS_WAVES", "STB_HGROUPS_FORM").nw, s->st))
     return 1;
   return stb_dc_run((const uint32_t *)(d + o_c), 1, Kmax, Kmax, STB_DM_ROWS, d_base, 1.0, s_in, shape, scale, nullptr, nullptr, seed,
                     sweep, s->st, info, who);

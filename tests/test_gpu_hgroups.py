@@ -1,9 +1,12 @@
 """Base weights per group of restaurants under a shared root, drawn on the device (libstb_amd/csrc/hgroups.hip;
 include/stb_hip.h stb_sample_hgroups): the step against the numpy replay (tests/hh_oracle.py), the row sums, the anchors
 to stb_tindic_sample_h and stb_sample_bgroups, launch geometries, the law, the object layer and examples/pyp_resample -H."""
+import hashlib
+import json
 import math
 import os
 import re
+import struct
 import subprocess
 from functools import lru_cache
 
@@ -47,6 +50,32 @@ def device_step(c, **kw):
     return dict(h=h.cpu().numpy(), root=root.cpu().numpy(), hgrp=out["hgrp"].cpu().numpy(),
                 c=out["c"].cpu().numpy().view(np.uint32).astype(np.int64), m=out["m"].cpu().numpy().view(np.uint32).astype(np.int64),
                 alpha=info.alpha, tables=info.tables, aux_tables=info.aux_tables)
+
+
+BITS = os.path.join(ROOT, "tests", "golden", "hstep_bits.json")
+
+
+def step_bits(h, root, rows, c, m, alpha, tables, aux_tables):
+    """what tests/golden/hstep_bits.json keeps of a step (tools/record_hstep_bits.py): SHA-256 of the arrays' bytes (rows, c
+    and m a list a level; the counts as uint32), the concentrations' bit patterns, the totals"""
+    def sha(x, dtype):
+        return hashlib.sha256(np.ascontiguousarray(x, dtype=dtype).tobytes()).hexdigest()
+
+    return dict(h=sha(h, np.float64), root=sha(root, np.float64), rows=[sha(x, np.float64) for x in rows],
+                c=[sha(x, np.uint32) for x in c], m=[sha(x, np.uint32) for x in m],
+                alpha=[struct.pack(">d", float(a)).hex() for a in alpha], tables=[int(x) for x in tables],
+                aux_tables=[int(x) for x in aux_tables])
+
+
+def bits_of(got):
+    return step_bits(got["h"], got["root"], [got["hgrp"]], [got["c"]], [got["m"]], [got["alpha"]], [got["tables"]],
+                     [got["aux_tables"]])
+
+
+@lru_cache(maxsize=None)
+def recorded():
+    with open(BITS) as f:
+        return json.load(f)
 
 
 @lru_cache(maxsize=None)
@@ -97,6 +126,13 @@ def test_the_step_equals_the_replay(name):
         assert got["alpha"] == c["alpha"]
     assert_replayed(got["hgrp"], want["hgrp"], name + " hgrp")
     assert_replayed(got["h"], want["h"], name + " h")
+
+
+@pytest.mark.parametrize("name", list(hho.CASES))
+def test_the_step_keeps_the_recorded_bits(name):
+    """every output bit is what the library gave before the grouped step became the one-level tree"""
+    _, got, _ = stepped(name)
+    assert bits_of(got) == recorded()["hgroups"][name]
 
 
 # ---- 2. row sums, and the pairs ----
@@ -150,7 +186,7 @@ def same_bits(a, b):
     return all(np.array_equal(a[k], b[k]) for k in ("h", "root", "hgrp", "c", "m")) and a["alpha"] == b["alpha"]
 
 
-@pytest.mark.parametrize("name", ["ragged_full", "k1024_alpha"])
+@pytest.mark.parametrize("name", ["ragged_full", "k1024_alpha", "each_keep"])
 def test_the_bits_do_not_depend_on_the_launch(name, monkeypatch):
     c, got, _ = stepped(name)
     for waves, form in ((1, "lane"), (2, "wave"), (4, "lane"), (8, "wave"), (8, ""), (4, "wave")):

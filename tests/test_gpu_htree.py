@@ -104,6 +104,17 @@ def test_the_step_equals_the_replay(name, flags):
     assert np.array_equal(got["h"], hho.spread(c["K"], want["owner"], got["rows"][0]))
 
 
+def bits_of(got):
+    return tgh.step_bits(got["h"], got["root"], got["rows"], got["c"], got["m"], got["alpha"], got["tables"], got["aux_tables"])
+
+
+@pytest.mark.parametrize("name,flags", hto.STEPS)
+def test_the_step_keeps_the_recorded_bits(name, flags):
+    """every output bit is what the library gave before the grouped step became the one-level tree"""
+    _, got, _ = stepped(name, flags)
+    assert bits_of(got) == tgh.recorded()["htree"]["%s/%d" % (name, flags)]
+
+
 # ---- 3. geometry ----
 
 def same_bits(a, b):

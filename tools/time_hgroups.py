@@ -1,4 +1,4 @@
-"""Time the grouped base-weight step (stb_tindic_sample_hgroups, libstb_amd/csrc/hgroups.hip) against the flat draw it
+"""Time the grouped base-weight step (stb_tindic_sample_hgroups; libstb_amd/csrc/hgroups.hip's kernels queued by htree.hip's step) against the flat draw it
 generalises (stb_tindic_sample_h) on the same state.
 
   python tools/time_hgroups.py [--reps 5] [--restaurants 100000] [--customers 200] [--kmax 64,1024] [--groups 1,100,0]

@@ -1,5 +1,5 @@
 """Time the base-weight step on a tree of nested groups (stb_tindic_sample_htree, libstb_amd/csrc/htree.hip) against the
-grouped step it generalises (stb_tindic_sample_hgroups) on the same state.
+grouped step (stb_tindic_sample_hgroups), its one-level case behind another entry point, on the same state.
 
   python tools/time_htree.py [--reps 5] [--restaurants 100000] [--customers 200] [--kmax 64,1024]
                              [--trees 10000/10000:100/10000:100:4] [--out FILE]
@@ -9,8 +9,8 @@ random, one table a pair with customers.  --trees: the nodes of every level, lev
 ranges; a tree of one level is also run as the grouped step over the same ranges.  The step is the full one (auxiliary tables
 upwards, root, every level's concentration, rows downwards; every alpha = 5 going in, gamma0 = 1, a Gamma(1.1, 20) prior)
 and, for comparison, the one that keeps root and concentrations.  Times are wall-clock around calls that wait for their own
-answer (median, min, max after one warm-up call).  `launches` counts the kernels of one full step: k_hg_count, a k_ht_aux
-and a k_ht_rows a level, the root's row, k_ht_prep, the concentration step's three, the scatter and k_ht_finish.
+answer (median, min, max after one warm-up call).  `launches` counts the kernels of one full step: k_hg_count, a k_hg_aux
+and a k_hg_rows a level, the root's k_hg_rows, k_ht_prep, the concentration step's three, the scatter and k_ht_finish.
 """
 import argparse
 import json
