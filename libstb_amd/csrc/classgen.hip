@@ -125,11 +125,6 @@ __global__ __launch_bounds__(CG_MAXTHREADS) void k_cls_draw(const double *pre, c
 // ------------------------------------------------------------------------------------------------
 // host side
 
-static unsigned cg_waves() {
-  const int w = stb_env_int("STB_CLS_WAVES", 4);
-  return w == 1 || w == 2 || w == 4 || w == 8 ? (unsigned)w : 4u;
-}
-
 static unsigned cg_chunks(unsigned rows) { return (unsigned)(((uint64_t)rows + CG_CHUNK - 1) / CG_CHUNK); }
 
 size_t stb_cg_scratch_bytes(unsigned rows, unsigned stride) {
@@ -140,7 +135,7 @@ int stb_cg_launch(const stb_lik_view &L, const uint32_t *d_cust, const uint8_t *
                   uint32_t *d_cls, uint64_t *d_info, void *d_scratch, hipStream_t st, const char *who) {
   if (C == 0) return 0;
   const unsigned rows = L.rows, stride = L.stride;
-  const unsigned nw = cg_waves(), nchunks = cg_chunks(rows), cb = (stride + 63) / 64;
+  const unsigned nw = (unsigned)stb_env_waves("STB_CLS_WAVES", 4), nchunks = cg_chunks(rows), cb = (stride + 63) / 64;
   double *pre = (double *)d_scratch, *ends = pre + (size_t)rows * stride;
   const uint64_t wanty = (nchunks + nw - 1) / nw, wantx = (C + 64 * nw - 1) / (64 * nw);
   const unsigned gy = wanty > 65535u ? 65535u : (unsigned)wanty, gx = wantx > CG_GRID_CAP ? CG_GRID_CAP : (unsigned)wantx;
@@ -162,7 +157,7 @@ extern "C" int stb_sample_classes(const double *d_lik, unsigned rows, unsigned s
   const char *who = "stb_sample_classes";
   if (!d_lik || (C && (!d_cls || !d_cust))) return stb_fail("%s: d_lik, d_cust and d_cls are required", who);
   if (rows < 1 || stride < 1) return stb_fail("%s: rows=%u stride=%u (both must be >= 1)", who, rows, stride);
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   if (C == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   void *d_scratch = nullptr;

@@ -291,12 +291,11 @@ int stb_dc_check(const uint32_t *d_cnt, uint64_t rows, unsigned cols, unsigned s
 int stb_dc_run(const uint32_t *d_cnt, uint64_t rows, unsigned cols, unsigned stride, unsigned flags, const double *d_w, double w0,
                double s, double shape, double scale, uint32_t *d_m, uint32_t *d_M, uint64_t seed, uint64_t sweep, hipStream_t st,
                stb_dirconc_info_t *info, const char *who) {
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   const bool by_rows = flags == STB_DM_ROWS;
   const size_t nm = by_rows ? (size_t)rows : (size_t)cols;
   const uint64_t ncat = by_rows ? (uint64_t)cols : rows;
-  const int nwi = stb_env_int("STB_DIRCONC_WAVES", 4);
-  const unsigned nw = nwi == 1 || nwi == 2 || nwi == 4 || nwi == 8 ? (unsigned)nwi : 4u;
+  const unsigned nw = (unsigned)stb_env_waves("STB_DIRCONC_WAVES", 4);
   const char *form = getenv("STB_DIRCONC_FORM");
   const unsigned twave = form && !strcmp(form, "lane") ? 0xffffffffu : form && !strcmp(form, "wave") ? 0u : HG_TWAVE;
   // scratch.  Zeroed: ctl (256 bytes), n[nm], M[nm] unless the caller gave one.  Then N32[nm], B[nm], the range {0, nm},

@@ -501,8 +501,7 @@ struct dm_scratch {
 static size_t dm_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static unsigned dm_waves() {
-  const int w = stb_env_int("STB_DIRMULT_WAVES", 4);
-  return w == 1 || w == 2 || w == 4 || w == 8 ? (unsigned)w : 4u;
+  return (unsigned)stb_env_waves("STB_DIRMULT_WAVES", 4);
 }
 
 static void dm_clear(stb_dirmult_info_t *info) {
@@ -528,7 +527,7 @@ int stb_dm_run(const uint32_t *d_cnt, uint64_t rows, unsigned cols, unsigned str
     dm_clear(info);
     return 0;
   }
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   const bool by_rows = flags == STB_DM_ROWS;
   const uint64_t nunits = (rows + DM_BLOCK - 1) / DM_BLOCK;  // blocks of rows, or chunks of rows
   if (nunits > 0x7fffffffull) return stb_fail("%s: rows=%llu", who, (unsigned long long)rows);

@@ -225,7 +225,7 @@ static int ensure_tables(stb_groups_t *g) {
 static stb_groups_t *groups_create_here(int I, const int *K, const uint32_t *T, const uint32_t *nflat,
                                         const uint16_t *tflat, const double *bpar, unsigned N, unsigned M, int Dmax) {
   if (stb_device_count() < 1) {
-    stb_fail("stb_groups_create: no HIP device (libstb_amd has no CPU path)");
+    stb_no_device("stb_groups_create");
     return nullptr;
   }
   if (Dmax < 1 || Dmax > STB_TERMS_DMAX) {

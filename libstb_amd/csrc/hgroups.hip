@@ -264,10 +264,9 @@ __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_scatter(uint64_t I, const 
 // host side: the checks, the launches one by one (the step that queues them is htree.hip's stb_ht_sample), the grouped step
 
 stb_hg_geom stb_hg_geom_env(const char *waves_name, const char *form_name) {
-  const int nwi = stb_env_int(waves_name, 4);
   const char *form = getenv(form_name);
   stb_hg_geom geo;
-  geo.nw = nwi == 1 || nwi == 2 || nwi == 4 || nwi == 8 ? (unsigned)nwi : 4u;
+  geo.nw = (unsigned)stb_env_waves(waves_name, 4);
   geo.twave = form && !strcmp(form, "lane") ? 0xffffffffu : form && !strcmp(form, "wave") ? 0u : HG_TWAVE;
   return geo;
 }
@@ -404,7 +403,7 @@ extern "C" int stb_sample_hgroups(int I, const uint64_t *d_koff, const uint16_t 
   if (stb_hg_check_opts(opts, Kmax, who)) return 1;
   if (G < 1) return stb_fail("%s: G=%d (must be >= 1)", who, G);
   if (!d_goff && G != I) return stb_fail("%s: without ranges every restaurant is its own group: G=%d, I=%d", who, G, I);
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   hipStream_t st = (hipStream_t)stream;
   if (d_goff) {  // the ranges steer stores: they are read back and checked before anything is queued
     std::vector<uint64_t> goff((size_t)G + 1);

@@ -240,7 +240,7 @@ extern "C" int stb_sample_htree(int I, const uint64_t *d_koff, const uint16_t *d
     if (!d_off[l]) return stb_fail("%s: d_off[%d] is required", who, l);
     if (l >= 1 && !d_hnode[l]) return stb_fail("%s: d_hnode[%d] is required (the rows of level %d)", who, l, l + 1);
   }
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   hipStream_t st = (hipStream_t)stream;
   // the ranges steer stores: they are read back and checked before anything is queued
   std::vector<std::vector<uint64_t>> off((size_t)L);

@@ -265,12 +265,12 @@ static int hb_queue(double a, double shape, double scale, int I, const uint32_t 
   if (I > 0 && !d_N == !d_coff) return stb_fail("%s: the customers per restaurant are required, as d_N or as d_coff", who);
   if (I > 0 && (!d_T || !d_bpar || !d_L)) return stb_fail("%s: d_T, d_bpar and d_L are required", who);
   if (G == 0) return 0;
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   if (stb_tset_ready(hb, who) || stb_tset_room(hb, d_Y || I == 0 ? 0 : (size_t)I, 0, sizeof(uint32_t), who)) return 1;
   if (!d_Y) d_Y = (uint32_t *)hb.d_buf;
   hipStream_t st = (hipStream_t)stream;
-  int nw = stb_env_int("STB_HYPERB_WAVES", 0);
-  const bool nw_given = nw == 1 || nw == 2 || nw == 4 || nw == 8;
+  int nw = stb_env_waves("STB_HYPERB_WAVES", 0);
+  const bool nw_given = nw != 0;
   if (!nw_given) nw = 4;
   const unsigned nthr = 64u * (unsigned)nw;
   // pass 2 over ranges: a group's sums are one workgroup's, so large groups get the most waves a workgroup can hold

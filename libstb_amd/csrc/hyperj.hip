@@ -318,7 +318,7 @@ static int hj_terms(const double *a, int D, const double *b, int J, const uint32
     HIPCHK(hipMemsetAsync(d_out, 0, sizeof(double) * D * J, st));
     return 0;
   }
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   const uint64_t nch64 = (I + HJ_CHUNK - 1) / HJ_CHUNK;
   if (nch64 * (uint64_t)(D * J) > (1ull << 28)) return stb_fail("%s: %llu restaurants x %d cells: more block sums than 2 GB hold", who, (unsigned long long)I, D * J);
   stb_tgeom tg;

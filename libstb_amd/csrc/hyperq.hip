@@ -136,7 +136,7 @@ extern "C" int stb_hq_logq(double b, double scale, int I, const uint32_t *d_N, c
     *Q_host = 1.0 / scale;
     return 0;
   }
-  if (stb_device_count() < 1) return stb_fail("stb_sample_logq: no HIP device (libstb_amd has no CPU path)");
+  if (stb_device_count() < 1) return stb_no_device("stb_sample_logq");
   hipStream_t st = (hipStream_t)stream;
   stb_tgeom tg;
   if (stb_ticket_geom(STB_GEOM_LOGQ, (uint64_t)I, 0, 0, 0, &tg)) return stb_fail("stb_sample_logq: no launch geometry for I=%d", I);

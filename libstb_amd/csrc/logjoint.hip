@@ -263,7 +263,7 @@ int stb_lj_run(const stb_table_view &S, const stb_rest_view &r, const stb_cnts_r
     if (info) memset(info, 0, sizeof(*info));
     return 0;
   }
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   stb_tgeom tg;
   if (stb_ticket_geom(STB_GEOM_LOGJOINT, (uint64_t)I, 0, 0, 0, &tg)) return stb_fail("%s: no launch geometry for I=%d", who, I);
   if (stb_tset_ready(lj, who) || stb_tset_room(lj, tg.need, STB_TG_CAP0_BLOCKS, 4 * sizeof(double), who)) return 1;
@@ -295,7 +295,7 @@ extern "C" int stb_reduce_geometry(int which, uint64_t I, int D, int J, int wave
   if (!out) return stb_fail("stb_reduce_geometry: null argument");
   if (which == STB_GEOM_JOINT_TERMS && (D < 1 || J < 1 || D > 64 || J > 64))
     return stb_fail("stb_reduce_geometry: a grid of %d x %d (1..64 each way)", D, J);
-  if (stb_device_count() < 1) return stb_fail("stb_reduce_geometry: no HIP device (libstb_amd has no CPU path)");
+  if (stb_device_count() < 1) return stb_no_device("stb_reduce_geometry");
   stb_tgeom tg;
   if (stb_ticket_geom(which, I, D, J, waves, &tg))
     return stb_fail("stb_reduce_geometry: which=%d, I=%llu, waves=%d (which 0..2, I >= 1, waves 0, 1, 2, 4 or 8)", which,

@@ -50,15 +50,6 @@ __device__ __forceinline__ double pt_S(const double *table, const double *S1, un
   return tc_S(table + stb_row_offset(n, M), S1, n, tau);
 }
 
-__device__ __forceinline__ double pt_scan(double v, unsigned lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double u = __shfl_up(v, o, 64);
-    if (lane >= (unsigned)o) v += u;
-  }
-  return v;
-}
-
 // round's candidate l = 64k + lane + 1 (k given): its w, the wave's F carry advanced
 __device__ __forceinline__ double pt_weight(const double *table, const double *S1, unsigned TM, unsigned Nr, unsigned Mc,
                                             unsigned L, double a, double ptot, unsigned k, unsigned lane, double &fcarry) {
@@ -66,7 +57,7 @@ __device__ __forceinline__ double pt_weight(const double *table, const double *S
   const unsigned l = 64u * k + lane + 1u;
   const bool in = l <= L;
   const double x = (in && l >= 2u) ? log((((double)(l - 1u) - a) * (double)(Nr - l + 1u)) / (double)(l - 1u)) : 0.0;
-  const double F = pt_scan(x, lane) + fcarry;
+  const double F = stb_wave_scan(x, lane) + fcarry;
   fcarry = __shfl(F, 63, 64);
   return in ? exp((F + pt_S(table, S1, TM, Nr - l, Mc)) - ptot) : 0.0;
 }
@@ -81,7 +72,7 @@ __device__ unsigned pt_round(const double *table, const double *S1, unsigned TM,
   const unsigned nc = (L + 63u) / 64u;
   double f = 0.0, W = 0.0, c1 = 0.0;
   for (unsigned k = 0; k < nc; k++) {
-    const double c = pt_scan(pt_weight(table, S1, TM, Nr, Mc, L, a, ptot, k, lane, f), lane) + W;
+    const double c = stb_wave_scan(pt_weight(table, S1, TM, Nr, Mc, L, a, ptot, k, lane, f), lane) + W;
     W = __shfl(c, 63, 64);
     c1 = c;
   }
@@ -93,7 +84,7 @@ __device__ unsigned pt_round(const double *table, const double *S1, unsigned TM,
   f = 0.0;
   double C = 0.0;
   for (unsigned k = 0; k < nc; k++) {
-    const double c = pt_scan(pt_weight(table, S1, TM, Nr, Mc, L, a, ptot, k, lane, f), lane) + C;
+    const double c = stb_wave_scan(pt_weight(table, S1, TM, Nr, Mc, L, a, ptot, k, lane, f), lane) + C;
     C = __shfl(c, 63, 64);
     const unsigned long long m = __ballot(64u * k + lane + 1u <= L && c > target);
     if (m) return 64u * k + (unsigned)__ffsll(m);
@@ -194,16 +185,11 @@ __global__ __launch_bounds__(64 * STB_PT_MAXWAVES) void k_partition(const double
   }
 }
 
-static int pt_waves(void) {
-  const int v = stb_env_int("STB_PARTITION_WAVES", 4);
-  return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
-}
-
 int stb_pt_launch(const stb_table_view &S, double a, uint64_t G, const stb_cnts_ro &c, uint32_t *d_cnt, unsigned Sh,
                   unsigned flags, const stb_draw_key &k, hipStream_t st, uint16_t *d_sizes, const uint64_t *d_soff) {
   HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * Sh, st));
   if (G == 0) return 0;
-  const unsigned wpb = (unsigned)pt_waves();
+  const unsigned wpb = (unsigned)stb_env_waves("STB_PARTITION_WAVES", 4);
   const uint64_t want = (G + wpb - 1) / wpb;
   const unsigned grid = want < STB_PT_GRID ? (unsigned)want : STB_PT_GRID;
   STB_LAUNCH(k_partition, dim3(grid), dim3(64 * wpb), st, S.tab, S.S1, S.N, S.M, a, G, c.n, c.t, d_cnt, Sh, d_sizes, d_soff,

@@ -224,12 +224,6 @@ extern "C" void stb_pr_release(void) {
   stb_tset_drop(pr);
 }
 
-// STB_PREDICT_WAVES where it names a workgroup size, else 0
-static int pr_env_waves() {
-  const int nw = stb_env_int("STB_PREDICT_WAVES", 0);
-  return nw == 1 || nw == 2 || nw == 4 || nw == 8 ? nw : 0;
-}
-
 int stb_pr_check(double a, unsigned flags, int I, const char *who) {
   if (!(a >= 0.0 && a < 1.0)) return stb_fail("%s: discount a=%g outside [0, 1)", who, a);
   if (flags & ~STB_PR_ACCUMULATE) return stb_fail("%s: unknown flags 0x%x", who, flags);
@@ -241,8 +235,8 @@ int stb_pr_predict(const stb_rest_view &r, const stb_cnts_ro &c, const stb_cust_
                    const stb_pr_out &out, unsigned flags, hipStream_t st, const char *who) {
   const int I = r.I;
   if (I == 0) return 0;
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
-  int nw = pr_env_waves();
+  if (stb_device_count() < 1) return stb_no_device(who);
+  int nw = stb_env_waves("STB_PREDICT_WAVES", 0);
   if (!nw) nw = 4;
   const int cus = stb_cu_count();
   const uint64_t want = 32ull * (uint64_t)(cus > 0 ? cus : 1), groups = ((uint64_t)I + nw - 1) / nw;
@@ -261,9 +255,9 @@ int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned sa
     if (info) memset(info, 0, sizeof(*info));
     return 0;
   }
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   stb_tgeom tg;  // k_logjoint's geometry; the workgroup size from STB_PREDICT_WAVES where it is set
-  if (stb_ticket_geom(STB_GEOM_LOGJOINT, (uint64_t)I, 0, 0, pr_env_waves(), &tg))
+  if (stb_ticket_geom(STB_GEOM_LOGJOINT, (uint64_t)I, 0, 0, stb_env_waves("STB_PREDICT_WAVES", 0), &tg))
     return stb_fail("%s: no launch geometry for I=%d", who, I);
   if (stb_tset_ready(pr, who) || stb_tset_room(pr, tg.need, STB_TG_CAP0_BLOCKS, sizeof(double), who)) return 1;
   HIPCHK(hipMemsetAsync(pr.d_ctl, 0, 64, st));

@@ -27,7 +27,6 @@
 #include "seat.h"
 #include "seat_visit.h"
 #include "ticket.h"
-#include "tindic.h"
 
 #pragma clang fp contract(off)
 
@@ -37,7 +36,7 @@
 #define ST_MAXPART 4096u
 #define ST_LDS_WAVE ((size_t)STB_TD_MAXK * (sizeof(uint32_t) + sizeof(uint16_t)))
 
-// (seat_args, the scan, theta and one visit -- steps 1 to 4 -- are seat_visit.h's, shared with seat_pf.hip)
+// (seat_args, theta and one visit -- steps 1 to 4 -- are seat_visit.h's, shared with seat_pf.hip; the scan is wave.h's)
 
 // one (restaurant, particle); counters: lane-uniform counts of this wave
 template <bool REG>
@@ -83,7 +82,7 @@ __device__ __forceinline__ void seat_item(const seat_args &A, uint64_t i, unsign
   if (lik && c0 + lane < c1) mcn = A.cls[c0 + lane];
   double Lnext = 1.0;  // register form: the next customer's row of L, a lane a dish
   if (REG && lik && c0 < c1) {
-    const unsigned cl = ti_rl(mcn, 0);
+    const unsigned cl = stb_wave_rl(mcn, 0);
     Lnext = cl < A.rows && lane < K ? lik[(uint64_t)cl * A.stride + lane] : 0.0;
   }
   for (uint64_t cb = c0; cb < c1; cb += 64) {
@@ -95,11 +94,11 @@ __device__ __forceinline__ void seat_item(const seat_args &A, uint64_t i, unsign
     double mp = 1.0;   // and its p (1 past the chunk's end: log 1 = 0 is never added)
     for (unsigned j = 0; j < Lc; j++) {
       const uint64_t c = cb + j;
-      const unsigned cl = ti_rl(mc, j);
+      const unsigned cl = stb_wave_rl(mc, j);
       const bool lrow = lik && cl < A.rows;
       const double Lcur = Lnext;
       if (REG && lik) {  // the next customer's row, on its way while this one is decided
-        const unsigned cn = j + 1 < Lc ? ti_rl(mc, j + 1) : ti_rl(mcn, 0);
+        const unsigned cn = j + 1 < Lc ? stb_wave_rl(mc, j + 1) : stb_wave_rl(mcn, 0);
         const bool more = c + 1 < c1;
         Lnext = more && cn < A.rows && lane < K ? lik[(uint64_t)cn * A.stride + lane] : 0.0;
       }
@@ -115,7 +114,7 @@ __device__ __forceinline__ void seat_item(const seat_args &A, uint64_t i, unsign
       if (A.p) A.p[cb + lane] = mp;
     }
     const double xl = mp > 0.0 ? log(mp) : 0.0;
-    for (unsigned j = 0; j < Lc; j++) dd_add(acc, ti_rld(xl, j));
+    for (unsigned j = 0; j < Lc; j++) dd_add(acc, stb_wave_rld(xl, j));
   }
   if (commit) {
     if (REG) {
@@ -186,15 +185,14 @@ __global__ __launch_bounds__(ST_MAXTHREADS) void k_seat_sum(const double *lw, ui
       const double *row = lw + (i0 + q) * R;
       double m = -HUGE_VAL;
       for (unsigned r = lane; r < R; r += 64) m = fmax(m, row[r]);
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+      m = stb_wave_all_max(m);
       double H = -HUGE_VAL;
       if (m > -HUGE_VAL) {
         double s = 0.0;
         for (unsigned base = 0; base < R; base += 64) {
           const unsigned cn = R - base < 64 ? R - base : 64u;
           const double e = lane < cn ? exp(row[base + lane] - m) : 0.0;
-          for (unsigned j = 0; j < cn; j++) s = s + ti_rld(e, j);
+          for (unsigned j = 0; j < cn; j++) s = s + stb_wave_rld(e, j);
         }
         H = m + log(s / (double)R);
       } else if (lane == 0) {
@@ -248,12 +246,6 @@ extern "C" void stb_seat_release(void) {
   stb_tset_drop(sq);
 }
 
-// STB_SEAT_WAVES where it names a workgroup size, else 0
-static int st_env_waves() {
-  const int nw = stb_env_int("STB_SEAT_WAVES", 0);
-  return nw == 1 || nw == 2 || nw == 4 || nw == 8 ? nw : 0;
-}
-
 int stb_seat_check(double a, unsigned M, unsigned particles, unsigned flags, int I, const char *who) {
   if (!(a >= 0.0 && a < 1.0)) return stb_fail("%s: discount a=%g outside [0, 1)", who, a);
   if (flags & ~STB_SEAT_COMMIT) return stb_fail("%s: unknown flags 0x%x", who, flags);
@@ -269,33 +261,15 @@ int stb_seat_launch(const stb_rest_view &r, const stb_cnts_rw &c, unsigned M, co
                     unsigned particles, unsigned flags, const stb_draw_key &k, const stb_seat_out &out, hipStream_t st,
                     const char *who) {
   if (r.I == 0) return 0;
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
-  int nw = st_env_waves();
-  if (!nw) nw = 4;
+  if (stb_device_count() < 1) return stb_no_device(who);
+  const int nw = stb_env_waves("STB_SEAT_WAVES", 4);
   const bool commit = (flags & STB_SEAT_COMMIT) != 0;
-  seat_args A;
-  A.a = r.a;
-  A.bpar = r.bpar;
-  A.I = (uint64_t)r.I;
-  A.koff = r.koff;
-  A.nv = c.n;
-  A.tv = c.t;
+  seat_args A = st_args(r, c, M, cu, L, particles, k, out.info);
   A.Tv = commit ? c.T : nullptr;
-  A.hv = r.h;
-  A.M = M ? M : 65535u;
-  A.coff = cu.off;
-  A.cls = cu.cls;
   A.cust = cu.cust;
-  A.lik = L.lik;
-  A.rows = L.rows;
-  A.stride = L.stride;
-  A.R = particles;
-  A.flags = flags;
-  A.seed = k.seed;
-  A.sweep = k.sweep;
   A.lw = out.lw;
   A.p = commit ? out.p : nullptr;
-  A.info = (unsigned long long *)out.info;
+  A.flags = flags;
   const uint64_t items = (uint64_t)r.I * particles, groups = (items + nw - 1) / nw;
   const unsigned grid = (unsigned)(groups < (1ull << 20) ? groups : (1ull << 20));
   if (r.maxK >= 1 && r.maxK <= 64) {
@@ -314,9 +288,9 @@ int stb_seat_sum(const double *d_lw, int I, unsigned particles, double *d_Hi, do
     if (total_host) *total_host = 0.0;
     return 0;
   }
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   stb_tgeom tg;  // k_logjoint's geometry; the workgroup size from STB_SEAT_WAVES where it is set
-  if (stb_ticket_geom(STB_GEOM_LOGJOINT, (uint64_t)I, 0, 0, st_env_waves(), &tg))
+  if (stb_ticket_geom(STB_GEOM_LOGJOINT, (uint64_t)I, 0, 0, stb_env_waves("STB_SEAT_WAVES", 0), &tg))
     return stb_fail("%s: no launch geometry for I=%d", who, I);
   if (stb_tset_ready(sq, who) || stb_tset_room(sq, tg.need, STB_TG_CAP0_BLOCKS, sizeof(double), who)) return 1;
   HIPCHK(hipMemsetAsync(sq.d_ctl, 0, 64, st));

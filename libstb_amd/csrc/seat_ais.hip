@@ -122,8 +122,8 @@ __global__ __launch_bounds__(AIS_MAXTHREADS) void k_ais_weight(ais_args A, doubl
     dd_t tot{0.0, 0.0};
     for (unsigned l = 0; l < nl; l++) {
       dd_t o;
-      o.hi = ti_rld(acc.hi, l);
-      o.lo = ti_rld(acc.lo, l);
+      o.hi = stb_wave_rld(acc.hi, l);
+      o.lo = stb_wave_rld(acc.lo, l);
       dd_merge(tot, o);
     }
     const double D = tot.hi + tot.lo;
@@ -177,12 +177,6 @@ ais_plan ais_layout(uint64_t I, uint64_t G, uint64_t C, unsigned R, unsigned row
   return p;
 }
 
-// STB_AIS_WAVES where it names a workgroup size, else 4
-int ais_waves() {
-  const int nw = stb_env_int("STB_AIS_WAVES", 0);
-  return nw == 1 || nw == 2 || nw == 4 || nw == 8 ? nw : 4;
-}
-
 // the ladder 0 < beta_1 < ... < beta_S = 1 (0, or 1 with stb_last_error() set)
 int ais_ladder(unsigned S, const double *betas_host, std::vector<double> *out, const char *who) {
   double prev = 0.0;
@@ -225,7 +219,7 @@ int stb_seat_anneal_launch(const stb_table_view &V, const stb_rest_view &r, cons
   const int I = r.I;
   const unsigned S = ld.S, passes = ld.passes, maxK = r.maxK;
   if (I == 0) return 0;
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   std::vector<double> beta;
   if (ais_ladder(S, ld.betas_host, &beta, who)) return 1;
   const ais_plan p = ais_layout((uint64_t)I, r.G, cu.C, particles, L.rows, L.stride);
@@ -265,7 +259,7 @@ int stb_seat_anneal_launch(const stb_table_view &V, const stb_rest_view &r, cons
   A.inner = inner;
   double *d_tlik = (double *)(ws + p.tlik);
 
-  const int nw = ais_waves();
+  const int nw = stb_env_waves("STB_AIS_WAVES", 4);
   const uint64_t items = (uint64_t)I * particles, groups = (items + nw - 1) / nw;
   const unsigned grid = (unsigned)(groups < AIS_MAXGRID ? groups : AIS_MAXGRID);
   // the replicated problem: I x particles restaurants, each with the pairs and the customers of its original.  (tdcap is
@@ -306,7 +300,7 @@ extern "C" int stb_lik_temper(const double *d_lik, unsigned rows, unsigned strid
   if (!d_lik || !d_out) return stb_fail("%s: the matrix and the output are required", who);
   if (!(beta >= 0.0) || !std::isfinite(beta)) return stb_fail("%s: beta=%g", who, beta);
   if ((uint64_t)rows * stride > ((uint64_t)1 << 39)) return stb_fail("%s: %u x %u cells", who, rows, stride);
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   return ais_temper_launch(d_lik, rows, stride, beta, d_out, (hipStream_t)stream);
 }
 

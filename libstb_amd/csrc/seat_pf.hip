@@ -28,7 +28,6 @@
 #include "seat_pf.h"
 #include "seat_visit.h"
 #include "ticket.h"
-#include "tindic.h"
 
 #pragma clang fp contract(off)
 
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(PF_MAXTHREADS) void k_seat_pf(seat_args A, pf_args 
     if (lik && c0 + lane < c1) mcn = A.cls[c0 + lane];
     double Lnext = 1.0;  // register form: the next customer's row of L, a lane a dish
     if (reg && lik && c0 < c1) {
-      const unsigned cl = ti_rl(mcn, 0);
+      const unsigned cl = stb_wave_rl(mcn, 0);
       Lnext = cl < A.rows && lane < K ? lik[(uint64_t)cl * A.stride + lane] : 0.0;
     }
     for (uint64_t cb = c0; cb < c1; cb += 64) {
@@ -117,17 +116,17 @@ __global__ __launch_bounds__(PF_MAXTHREADS) void k_seat_pf(seat_args A, pf_args 
       for (unsigned j = 0; j < Lc; j++) {
         const uint64_t c = cb + j;
         const unsigned par = (unsigned)(c - c0) & 1u;
-        const unsigned cl = ti_rl(mc, j);
+        const unsigned cl = stb_wave_rl(mc, j);
         const bool lrow = lik && cl < A.rows;
         const double Lcur = Lnext;
         if (reg && lik) {
-          const unsigned cn = j + 1 < Lc ? ti_rl(mc, j + 1) : ti_rl(mcn, 0);
+          const unsigned cn = j + 1 < Lc ? stb_wave_rl(mc, j + 1) : stb_wave_rl(mcn, 0);
           const bool more = c + 1 < c1;
           Lnext = more && cn < A.rows && lane < K ? lik[(uint64_t)cn * A.stride + lane] : 0.0;
         }
         // ---- every slot of this wave seats customer c: st_visit, and 1. the weight
         for (unsigned r = wave; r < R; r += nw) {
-          const uint64_t key = st_rl64(keyv, r);
+          const uint64_t key = stb_wave_rl64(keyv, r);
           const double u2 = stb_unit(key, 2 * c + 2), u3 = stb_unit(key, 2 * C + 1 + c);
           uint32_t *ln = np(cur, r);
           uint16_t *lt = tp(cur, r);
@@ -148,7 +147,7 @@ __global__ __launch_bounds__(PF_MAXTHREADS) void k_seat_pf(seat_args A, pf_args 
           s_T[cur][r] = T;
           s_N[cur][r] = N;
           if (!rdead) {
-            const double wr = ti_rld(wv, r) * pc;
+            const double wr = stb_wave_rld(wv, r) * pc;
             if (lane == 0) s_w[par][r] = wr;
           }
         }
@@ -172,26 +171,26 @@ __global__ __launch_bounds__(PF_MAXTHREADS) void k_seat_pf(seat_args A, pf_args 
         w = (w > 0.0 && (long long)ex >= (long long)e - 1000) ? ldexp(w, -e) : 0.0;
         E += e;
         // ---- 3. the sums, 4. the decision
-        const double cum = 0.0 + st_scan(w, lane);
-        S1 = ti_rld(cum, 63);
-        const double S2 = ti_rld(0.0 + st_scan(w * w, lane), 63);
+        const double cum = 0.0 + stb_wave_scan(w, lane);
+        S1 = stb_wave_rld(cum, 63);
+        const double S2 = stb_wave_rld(0.0 + stb_wave_scan(w * w, lane), 63);
         if (c + 1 < c1 && S1 * S1 < (tau * (double)R) * S2) {
           // ---- 5. systematic resampling on slot 0's u4
           Zm = Zm * (S1 / (double)R);
           const int ez = ilogb(Zm);
           Zm = ldexp(Zm, -ez);
           E += ez;
-          const double u4 = stb_unit(st_rl64(keyv, 0), 2 * c + 1);
+          const double u4 = stb_unit(stb_wave_rl64(keyv, 0), 2 * c + 1);
           const double thr = (((double)lane + u4) / (double)R) * S1;  // lane j: slot j's threshold
           const uint64_t pos = __ballot(w > 0.0);
           unsigned anc = 63u - (unsigned)__builtin_clzll(pos);
           bool found = false;
           for (unsigned r = 0; r < R; r++) {
-            const double cr = ti_rld(cum, r);
+            const double cr = stb_wave_rld(cum, r);
             if (!found && ((pos >> r) & 1) && cr > thr) anc = r, found = true;
           }
           for (unsigned jj = wave; jj < R; jj += nw) {
-            const unsigned aj = ti_rl(anc, jj);
+            const unsigned aj = stb_wave_rl(anc, jj);
             const uint32_t *sn = np(cur, aj);
             const uint16_t *st = tp(cur, aj);
             uint32_t *dn = np(cur ^ 1u, jj);
@@ -259,37 +258,15 @@ int stb_seat_pf_launch(const stb_rest_view &r, const stb_cnts_ro &c, unsigned M,
                        unsigned particles, double tau, const stb_draw_key &k, const stb_pf_out &out, hipStream_t st,
                        const char *who) {
   if (r.I == 0) return 0;
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
-  int nw = stb_env_int("STB_SEAT_WAVES", 0);
-  if (!(nw == 1 || nw == 2 || nw == 4 || nw == 8)) {
+  if (stb_device_count() < 1) return stb_no_device(who);
+  int nw = stb_env_waves("STB_SEAT_WAVES", 0);
+  if (!nw) {
     // sixteen slots a wave: every wave repeats the weight step of a customer, so that step is paid once per wave and
     // customer whatever the wave seats; at R = 16 one wave beat two, four and eight (MEASUREMENTS.md section F1)
     nw = 1;
     while (nw < 8 && 16u * (unsigned)nw < particles) nw *= 2;
   }
-  seat_args A;
-  A.a = r.a;
-  A.bpar = r.bpar;
-  A.I = (uint64_t)r.I;
-  A.koff = r.koff;
-  A.nv = const_cast<uint32_t *>(c.n);  // (read only: the kernel stores to neither)
-  A.tv = const_cast<uint16_t *>(c.t);
-  A.Tv = nullptr;
-  A.hv = r.h;
-  A.M = M ? M : 65535u;
-  A.coff = cu.off;
-  A.cls = cu.cls;
-  A.cust = nullptr;
-  A.lik = L.lik;
-  A.rows = L.rows;
-  A.stride = L.stride;
-  A.R = particles;
-  A.flags = 0;
-  A.seed = k.seed;
-  A.sweep = k.sweep;
-  A.lw = nullptr;
-  A.p = nullptr;
-  A.info = (unsigned long long *)out.info;
+  const seat_args A = st_args(r, c, M, cu, L, particles, k, out.info);  // (read only: the kernel stores to neither n nor t)
   pf_args P;
   P.tau = tau;
   P.Hi = out.Hi;

@@ -1,11 +1,20 @@
 /* seat_visit.h -- private: one visit of the forward seating (include/stb_hip.h, "seating customers one by one", steps
  * 1 to 4), shared by the kernels that seat: k_seat (seat.hip: a wave a particle, nobody waits) and k_seat_pf
  * (seat_pf.hip: a workgroup a restaurant, the particles meet after every customer).  The arithmetic is the header's, word
- * for word; whoever includes this seats by the same bits. */
+ * for word; whoever includes this seats by the same bits.  st_args fills the kernels' arguments for both launches.
+ *
+ * Moved out (MEASUREMENTS O6): the scan, the 64-bit readlane and the register form's choice are wave.h's, and this header
+ * takes the readlanes from there, not from tindic.h.
+ * Stayed out: the customer walk (the next chunk's classes and the next customer's row of L, prefetched) is written out
+ * twice, in seat_item (seat.hip) and in k_seat_pf.  Written once here and called from both, it cost k_seat_pf 0.7 to 1.3 % at
+ * every tau of tools/time_seat_pf.py, outside the parent's own spread (its code moved though no count did: 2664 lines
+ * before and after, the same registers); k_seat stayed inside its spread, but a walk with one caller shares nothing. */
 #ifndef STB_SEAT_VISIT_H
 #define STB_SEAT_VISIT_H
 #include "stb_common.h"
-#include "tindic.h"
+#include "uniforms.h"
+#include "views.h"
+#include "wave.h"
 
 struct seat_args {
   double a;
@@ -27,19 +36,36 @@ struct seat_args {
   unsigned long long *info;
 };
 
-// inclusive Kogge-Stone scan over the wave's 64 lanes (k_tdish's)
-__device__ __forceinline__ double st_scan(double x, unsigned lane) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (unsigned d = 1; d < 64; d <<= 1) {
-    const double y = __shfl_up(x, d, 64);
-    if (lane >= d) x = x + y;
-  }
-  return x;
-}
-
-__device__ __forceinline__ uint64_t st_rl64(uint64_t v, unsigned j) {
-  return ((uint64_t)ti_rl((unsigned)(v >> 32), j) << 32) | ti_rl((unsigned)v, j);
+// what both launches fill alike, from the view records they hold: a seating that commits nothing, weighs nothing and
+// writes no state (Tv, cust, lw and p null, flags 0).  stb_seat_launch sets those five; stb_seat_pf_launch none.  (n and
+// t lose their const here: k_seat stores to them under STB_SEAT_COMMIT alone, whose caller holds them writable, and
+// k_seat_pf never)
+static inline seat_args st_args(const stb_rest_view &r, const stb_cnts_ro &c, unsigned M, const stb_cust_ro &cu,
+                                const stb_lik_view &L, unsigned particles, const stb_draw_key &k, uint64_t *info) {
+  seat_args A;
+  A.a = r.a;
+  A.bpar = r.bpar;
+  A.I = (uint64_t)r.I;
+  A.koff = r.koff;
+  A.nv = const_cast<uint32_t *>(c.n);
+  A.tv = const_cast<uint16_t *>(c.t);
+  A.Tv = nullptr;
+  A.hv = r.h;
+  A.M = M ? M : 65535u;
+  A.coff = cu.off;
+  A.cls = cu.cls;
+  A.cust = nullptr;
+  A.lik = L.lik;
+  A.rows = L.rows;
+  A.stride = L.stride;
+  A.R = particles;
+  A.flags = 0;
+  A.seed = k.seed;
+  A.sweep = k.sweep;
+  A.lw = nullptr;
+  A.p = nullptr;
+  A.info = (unsigned long long *)info;
+  return A;
 }
 
 // x, y and theta of a pair (n, t, h) in a restaurant with g = b + T a, den = b + N
@@ -77,9 +103,9 @@ __device__ __forceinline__ void st_visit(const seat_args &A, uint64_t kg, unsign
     double x, y;
     th0 = lane < K ? st_theta(rn, rt, rh, a, g, den, empty, M, x, y) : 0.0;
     const double q = lane < K ? th0 * (lik ? Lcur : 1.0) : 0.0;
-    cum = 0.0 + st_scan(q, lane);
+    cum = 0.0 + stb_wave_scan(q, lane);
     pos = __ballot(q > 0.0);
-    Z = ti_rld(cum, 63);
+    Z = stb_wave_rld(cum, 63);
   } else {
     double base = 0.0;
     for (unsigned blk = 0; blk < nblk; blk++) {
@@ -90,10 +116,10 @@ __device__ __forceinline__ void st_visit(const seat_args &A, uint64_t kg, unsign
         const double th = st_theta(ln[k], lt[k], hv ? hv[kg + k] : 1.0, a, g, den, empty, M, x, y);
         q = th * (lik ? (lrow ? lik[(uint64_t)cl * A.stride + k] : 0.0) : 1.0);
       }
-      const double cm = base + st_scan(q, lane);
+      const double cm = base + stb_wave_scan(q, lane);
       const uint64_t pm = __ballot(q > 0.0);
       if (lane == blk) pos = pm, basev = base;
-      base = ti_rld(cm, 63);
+      base = stb_wave_rld(cm, 63);
     }
     Z = base;
   }
@@ -108,9 +134,9 @@ __device__ __forceinline__ void st_visit(const seat_args &A, uint64_t kg, unsign
     useL = false;
     if (REG) {
       const double q = lane < K ? th0 : 0.0;
-      cum = 0.0 + st_scan(q, lane);
+      cum = 0.0 + stb_wave_scan(q, lane);
       pos = __ballot(q > 0.0);
-      Z = ti_rld(cum, 63);
+      Z = stb_wave_rld(cum, 63);
     } else {
       double base = 0.0;
       pos = 0;
@@ -121,10 +147,10 @@ __device__ __forceinline__ void st_visit(const seat_args &A, uint64_t kg, unsign
           double x, y;
           q = st_theta(ln[k], lt[k], hv ? hv[kg + k] : 1.0, a, g, den, empty, M, x, y);
         }
-        const double cm = base + st_scan(q, lane);
+        const double cm = base + stb_wave_scan(q, lane);
         const uint64_t pm = __ballot(q > 0.0);
         if (lane == blk) pos = pm, basev = base;
-        base = ti_rld(cm, 63);
+        base = stb_wave_rld(cm, 63);
       }
       Z = base;
     }
@@ -138,14 +164,13 @@ __device__ __forceinline__ void st_visit(const seat_args &A, uint64_t kg, unsign
   if (!nowhere) {
     const double thr = u3 * Z;
     if (REG) {
-      const uint64_t hit = __ballot(((pos >> lane) & 1) && cum > thr);
-      ks = hit ? (unsigned)__builtin_ctzll(hit) : 63u - (unsigned)__builtin_clzll(pos);
+      ks = stb_wave_choice(pos, cum, thr, lane);
     } else {
       bool found = false;
       unsigned lastb = 0;
       uint64_t lastm = 1;
       for (unsigned blk = 0; blk < nblk && !found; blk++) {
-        const uint64_t pm = st_rl64(pos, blk);
+        const uint64_t pm = stb_wave_rl64(pos, blk);
         if (!pm) continue;
         const unsigned k = blk * 64 + lane;
         double q = 0.0;
@@ -154,7 +179,7 @@ __device__ __forceinline__ void st_visit(const seat_args &A, uint64_t kg, unsign
           const double th = st_theta(ln[k], lt[k], hv ? hv[kg + k] : 1.0, a, g, den, empty, M, x, y);
           q = useL ? th * (lik ? (lrow ? lik[(uint64_t)cl * A.stride + k] : 0.0) : 1.0) : th;
         }
-        const double cm = ti_rld(basev, blk) + st_scan(q, lane);
+        const double cm = stb_wave_rld(basev, blk) + stb_wave_scan(q, lane);
         const uint64_t hit = __ballot(((pm >> lane) & 1) && cm > thr);
         if (hit) {
           ks = blk * 64 + (unsigned)__builtin_ctzll(hit);
@@ -166,8 +191,8 @@ __device__ __forceinline__ void st_visit(const seat_args &A, uint64_t kg, unsign
     }
   }
   // ---- 4. the head, from the chosen dish's own x and y
-  const unsigned ns = REG ? ti_rl(rn, ks) : ln[ks], ts = REG ? ti_rl(rt, ks) : (unsigned)lt[ks];
-  const double hs = REG ? ti_rld(rh, ks) : (hv ? hv[kg + ks] : 1.0);
+  const unsigned ns = REG ? stb_wave_rl(rn, ks) : ln[ks], ts = REG ? stb_wave_rl(rt, ks) : (unsigned)lt[ks];
+  const double hs = REG ? stb_wave_rld(rh, ks) : (hv ? hv[kg + ks] : 1.0);
   double xs, ys;
   (void)st_theta(ns, ts, hs, a, g, den, empty, M, xs, ys);
   const bool isnew = ns == 0 || u2 * (xs + ys) < ys;
@@ -184,4 +209,5 @@ __device__ __forceinline__ void st_visit(const seat_args &A, uint64_t kg, unsign
   ks_out = ks;
   pc_out = pc;
 }
+
 #endif

@@ -14,6 +14,7 @@
 //   lists.hip, lists_sorted.hip, pairs.hip   the cell lists of the fused evaluation (two builders), the pairs' way to the device
 //   tcounts.hip, tindic.hip, tdish.hip, tcwin.hip, partition.hip   the sampler sweeps' kernels and raw calls
 //   tcounts_obj.hip, tindic_obj.hip   stb_tcounts_* / stb_tindic_*: the resident-count objects, host code only
+//   wave.h           private: the sampler kernels' wave primitives (readlanes, the scan, the butterflies, the choice)
 //   tools/ablation/ablation.hip   superseded fill forms, in a library of their own (make -C tools/ablation)
 #ifndef STB_COMMON_H
 #define STB_COMMON_H
@@ -101,6 +102,14 @@ static inline int stb_env_int(const char *name, int dflt) {
   if (!s || !*s) return dflt;
   return atoi(s);
 }
+// waves a workgroup from the environment: the value of `name` where it is 1, 2, 4 or 8, else dflt (dflt = 0 tells the
+// caller that no size was given)
+static inline int stb_env_waves(const char *name, int dflt) {
+  const int nw = stb_env_int(name, 0);
+  return nw == 1 || nw == 2 || nw == 4 || nw == 8 ? nw : dflt;
+}
+// the refusal of a call that needs a device where stb_device_count() finds none; returns 1
+static inline int stb_no_device(const char *who) { return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who); }
 
 // ------------------------------------------------------------------------------------------------
 // fill kernels: common arguments

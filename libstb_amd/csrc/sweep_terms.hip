@@ -419,7 +419,7 @@ extern "C" void stb_bterms_free(stb_bctx_t *c) {
 extern "C" stb_bctx_t *stb_bterms_create(const uint32_t *T, int I) {
   STB_ENTRY;
   if (stb_device_count() < 1) {
-    stb_fail("stb_bterms_create: no HIP device (libstb_amd has no CPU path)");
+    stb_no_device("stb_bterms_create");
     return nullptr;
   }
   stb_bctx_t *c = (stb_bctx_t *)calloc(1, sizeof(*c));
@@ -479,7 +479,7 @@ extern "C" stb_bctx_t *stb_bterms_borrow(stb_bctx_t *c, const uint32_t *d_T, int
   }
   int dev = -1;
   if (stb_device_count() < 1 || hipGetDevice(&dev) != hipSuccess) {
-    stb_fail("stb_bterms_borrow: no HIP device (libstb_amd has no CPU path)");
+    stb_no_device("stb_bterms_borrow");
     if (c) stb_bterms_free(c);
     return nullptr;
   }
@@ -647,7 +647,7 @@ extern "C" void stb_hist_free(stb_hist_t *h) {
 // the buffers and stream of a histogram of S sizes for I restaurants, nothing uploaded (the current device's)
 static stb_hist_t *hist_alloc(unsigned S, int I, const char *who) {
   if (stb_device_count() < 1) {
-    stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+    stb_no_device(who);
     return nullptr;
   }
   stb_hist_t *h = (stb_hist_t *)calloc(1, sizeof(*h));

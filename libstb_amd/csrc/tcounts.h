@@ -5,6 +5,7 @@
 #include "stb_common.h"
 #include "uniforms.h"
 #include "views.h"
+#include "wave.h"  // the scan and the butterflies of k_tcounts, k_tcwin and k_partition
 
 // S_S(n, tau) for 1 <= tau <= min(n, M): dev_S_S of sweep_terms.hip for the cells a draw can address
 // (n <= N: the kernels leave pairs with n > N alone)

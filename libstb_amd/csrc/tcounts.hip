@@ -31,7 +31,8 @@
 #define STB_TC_CAP 4096      // tau values a workgroup keeps in LDS (32 KB); longer rows recompute
 #define STB_TC_MAXWAVES 16
 
-// ---- workgroup collectives (nw = waves of the workgroup; every thread gets the same bits) ----
+// ---- workgroup collectives (nw = waves of the workgroup; every thread gets the same bits); the wave's part of each is
+// wave.h's ----
 
 struct tc_shared {
   double wsum[STB_TC_MAXWAVES];
@@ -41,11 +42,7 @@ struct tc_shared {
 // inclusive prefix sum over the workgroup in thread order; *total = the sum over all threads
 __device__ __forceinline__ double tc_scan(double v, int nw, tc_shared &sh, double *total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
+  v = stb_wave_scan(v, (unsigned)lane);
   if (nw == 1) {
     *total = __shfl(v, 63, 64);
     return v;
@@ -64,8 +61,7 @@ __device__ __forceinline__ double tc_scan(double v, int nw, tc_shared &sh, doubl
 }
 
 __device__ __forceinline__ double tc_max(double v, int nw, tc_shared &sh) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  v = stb_wave_all_max(v);
   if (nw == 1) return v;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) sh.wsum[wave] = v;
@@ -77,8 +73,7 @@ __device__ __forceinline__ double tc_max(double v, int nw, tc_shared &sh) {
 }
 
 __device__ __forceinline__ unsigned tc_min(unsigned v, int nw, tc_shared &sh) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = min(v, (unsigned)__shfl_xor((int)v, o, 64));
+  v = stb_wave_all_min(v);
   if (nw == 1) return v;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) sh.wmin[wave] = v;

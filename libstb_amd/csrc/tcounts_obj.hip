@@ -107,7 +107,7 @@ static stb_tcounts_t *tc_create_here(int I, const int *K, const uint32_t *nflat,
                                      unsigned M) {
   const char *who = "stb_tcounts_create";
   if (stb_device_count() < 1) {
-    stb_fail("stb_tcounts_create: no HIP device (libstb_amd has no CPU path)");
+    stb_no_device("stb_tcounts_create");
     return nullptr;
   }
   if (I < 1 || !K || !nflat || !tflat) {

@@ -69,28 +69,7 @@ __device__ __forceinline__ double tcw_cell(const double *table, const double *S1
   return tc_S(table + stb_row_offset(n, M), S1, n, tau);
 }
 
-// ---- wave collectives (every lane gets the same bits) ----
-
-__device__ __forceinline__ double tcw_max(double v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ __forceinline__ double tcw_sum(double v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);  // (x + y and y + x: the same bits in both lanes)
-  return v;
-}
-
-__device__ __forceinline__ double tcw_scan(double v, unsigned lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double u = __shfl_up(v, o, 64);
-    if (lane >= (unsigned)o) v += u;
-  }
-  return v;
-}
+// (the wave collectives -- the all-lanes max and sum, the scan: every lane gets the same bits -- are wave.h's)
 
 // the log weights of the span a pair visit reads, relative to a constant (which the scale exp(-max) removes)
 struct tcw_row {
@@ -133,7 +112,7 @@ struct tcw_row {
     const unsigned tau = q.slo + 64u * k + lane;
     const bool in = tau <= q.shi;
     const double x = (in && tau > q.slo) ? term(tau) : 0.0;
-    const double P = tcw_scan(x, lane) + carry;
+    const double P = stb_wave_scan(x, lane) + carry;
     carry = __shfl(P, 63, 64);
     if (!in) return -HUGE_VAL;
     const double S = k == 0 ? cell0 : tcw_cell(table, S1, n, M, q, k, lane);
@@ -154,12 +133,12 @@ __device__ __forceinline__ unsigned tcw_visit(tcw_row &r, unsigned W, bool ref, 
     const double lw = r.lw(k, lane);
     m1 = fmax(m1, tau >= lo1 && tau <= hi1 ? lw : -HUGE_VAL);
   }
-  m1 = tcw_max(m1);
+  m1 = stb_wave_all_max(m1);
   double Z1 = 0.0, c1 = 0.0;
   for (unsigned k = 0; k < r.nc; k++) {
     const unsigned tau = slo + 64u * k + lane;
     const double lw = r.lw(k, lane);
-    const double c = tcw_scan(tau >= lo1 && tau <= hi1 ? exp(lw - m1) : 0.0, lane) + Z1;
+    const double c = stb_wave_scan(tau >= lo1 && tau <= hi1 ? exp(lw - m1) : 0.0, lane) + Z1;
     Z1 = __shfl(c, 63, 64);
     c1 = c;  // (nc == 1: the cumulative weights, kept for the crossing)
   }
@@ -174,7 +153,7 @@ __device__ __forceinline__ unsigned tcw_visit(tcw_row &r, unsigned W, bool ref, 
     for (unsigned k = 0; k < r.nc; k++) {
       const unsigned tau = slo + 64u * k + lane;
       const double lw = r.lw(k, lane);
-      const double c = tcw_scan(tau >= lo1 && tau <= hi1 ? exp(lw - m1) : 0.0, lane) + C;
+      const double c = stb_wave_scan(tau >= lo1 && tau <= hi1 ? exp(lw - m1) : 0.0, lane) + C;
       C = __shfl(c, 63, 64);
       const unsigned long long m = __ballot(tau >= lo1 && tau <= hi1 && c > target);
       if (m) {
@@ -193,14 +172,14 @@ __device__ __forceinline__ unsigned tcw_visit(tcw_row &r, unsigned W, bool ref, 
     const double lw = r.lw(k, lane);
     m2 = fmax(m2, tau >= lo2 && tau <= hi2 ? lw : -HUGE_VAL);
   }
-  m2 = tcw_max(m2);
+  m2 = stb_wave_all_max(m2);
   double Zt = 0.0, Zp = 0.0;
   for (unsigned k = 0; k < r.nc; k++) {
     const unsigned tau = slo + 64u * k + lane;
     const double lw = r.lw(k, lane);
     const double e = tau >= lo2 && tau <= hi2 ? exp(lw - m2) : 0.0;
-    Zt += tcw_sum(tau >= lo1 && tau <= hi1 ? e : 0.0);
-    Zp += tcw_sum(tau >= lop && tau <= hip ? e : 0.0);
+    Zt += stb_wave_all_sum(tau >= lo1 && tau <= hi1 ? e : 0.0);
+    Zp += stb_wave_all_sum(tau >= lop && tau <= hip ? e : 0.0);
   }
   return u2 * Zp < Zt ? tp : tc;
 }
@@ -258,15 +237,10 @@ __global__ __launch_bounds__(64 * STB_TCW_MAXWAVES) void k_tcwin(const double *t
   if (lane == 0) Tv[i] = T;
 }
 
-static int tcw_waves(void) {
-  const int v = stb_env_int("STB_TCWIN_WAVES", 4);
-  return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
-}
-
 int stb_tcw_launch(const stb_table_view &S, const stb_rest_view &r, const stb_cnts_tT &c, unsigned W, unsigned flags,
                    const stb_draw_key &k, int nsweeps, hipStream_t st) {
   if (r.I <= 0 || nsweeps <= 0) return 0;
-  const int wpb = tcw_waves();
+  const int wpb = stb_env_waves("STB_TCWIN_WAVES", 4);
   STB_LAUNCH(k_tcwin, dim3((unsigned)((r.I + wpb - 1) / wpb)), dim3(64 * wpb), st, S.tab, S.S1, S.N, S.M, r.a, r.bpar, r.I,
              r.koff, c.n, c.t, c.T, r.h, W, flags, k.seed, k.sweep, nsweeps);
   HIPCHK(hipGetLastError());

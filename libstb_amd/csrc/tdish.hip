@@ -47,20 +47,7 @@ __device__ __forceinline__ double td_z(double L, double A, double g, double B) {
   return L * (A + gB);
 }
 
-// inclusive Kogge-Stone scan over the wave's 64 lanes
-__device__ __forceinline__ double td_scan(double x, unsigned lane) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (unsigned d = 1; d < 64; d <<= 1) {
-    const double y = __shfl_up(x, d, 64);
-    if (lane >= d) x = x + y;
-  }
-  return x;
-}
-
-__device__ __forceinline__ uint64_t td_rl64(uint64_t v, unsigned j) {
-  return ((uint64_t)ti_rl((unsigned)(v >> 32), j) << 32) | ti_rl((unsigned)v, j);
-}
+// (the inclusive Kogge-Stone scan, the readlanes and the choice are wave.h's)
 
 template <bool REG>
 __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsigned M, double a, const double *bpar, int I,
@@ -121,14 +108,14 @@ __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsi
       }
       const unsigned mk_in = mk;
       for (unsigned j = 0; j < Lc; j++) {
-        const unsigned k0 = ti_rl(mk, j), cl = ti_rl(mc, j);
+        const unsigned k0 = stb_wave_rl(mk, j), cl = stb_wave_rl(mc, j);
         const uint64_t c = cb + j;
         if (k0 >= K) continue;  // (not a dish of this restaurant: a raw caller's error, nothing is touched)
         // ---- 1. remove
-        const unsigned n0 = REG ? ti_rl(rn, k0) : ln[k0], t0 = REG ? ti_rl(rt, k0) : lt[k0];
+        const unsigned n0 = REG ? stb_wave_rl(rn, k0) : ln[k0], t0 = REG ? stb_wave_rl(rt, k0) : lt[k0];
         if (n0 == 0 || T == 0) continue;  // (counts that do not hold the customer: likewise)
-        const double A0 = REG ? ti_rld(rA, k0) : lA[k0], B0 = REG ? ti_rld(rB, k0) : lB[k0];
-        const double h0 = REG ? ti_rld(rh, k0) : (hv ? hv[kg + k0] : 1.0);
+        const double A0 = REG ? stb_wave_rld(rA, k0) : lA[k0], B0 = REG ? stb_wave_rld(rB, k0) : lB[k0];
+        const double h0 = REG ? stb_wave_rld(rh, k0) : (hv ? hv[kg + k0] : 1.0);
         const uint32_t T0 = T;
         unsigned n = n0, t = t0;
         if (n >= 2) {
@@ -154,20 +141,20 @@ __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsi
         if (REG) {
           const double Lk = lik ? (lrow && lane < K ? lik[(uint64_t)cl * stride + lane] : 0.0) : 1.0;
           const double z = lane < K ? td_z(Lk, rA, g, rB) : 0.0;
-          cum = 0.0 + td_scan(z, lane);
+          cum = 0.0 + stb_wave_scan(z, lane);
           pos = __ballot(z > 0.0);
-          Z = ti_rld(cum, 63);
+          Z = stb_wave_rld(cum, 63);
         } else {
           double base = 0.0;
           for (unsigned blk = 0; blk < nblk; blk++) {
             const unsigned k = blk * 64 + lane;
             const double Lk = lik ? (lrow && k < K ? lik[(uint64_t)cl * stride + k] : 0.0) : 1.0;
             const double z = k < K ? td_z(Lk, lA[k], g, lB[k]) : 0.0;
-            const double cm = base + td_scan(z, lane);
+            const double cm = base + stb_wave_scan(z, lane);
             lcum[k] = cm;  // (cap is a multiple of 64)
             const uint64_t pm = __ballot(z > 0.0);
             if (lane == blk) pos = pm;
-            base = ti_rld(cm, 63);
+            base = stb_wave_rld(cm, 63);
           }
           Z = base;
         }
@@ -184,14 +171,13 @@ __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsi
         const double thr = stb_unit(key, 2 * C + 1 + c) * Z;
         unsigned ks = 0;
         if (REG) {
-          const uint64_t hit = __ballot(((pos >> lane) & 1) && cum > thr);
-          ks = hit ? (unsigned)__builtin_ctzll(hit) : 63u - (unsigned)__builtin_clzll(pos);
+          ks = stb_wave_choice(pos, cum, thr, lane);
         } else {
           bool found = false;
           unsigned lastb = 0;
           uint64_t lastm = 0;
           for (unsigned blk = 0; blk < nblk && !found; blk++) {
-            const uint64_t pm = td_rl64(pos, blk);
+            const uint64_t pm = stb_wave_rl64(pos, blk);
             const uint64_t hit = __ballot(((pm >> lane) & 1) && lcum[blk * 64 + lane] > thr);
             if (hit) {
               ks = blk * 64 + (unsigned)__builtin_ctzll(hit);
@@ -202,9 +188,9 @@ __global__ __launch_bounds__(64) void k_tdish(const double *vt, unsigned N, unsi
           if (!found) ks = lastb * 64 + 63u - (unsigned)__builtin_clzll(lastm);
         }
         // ---- 4. seat
-        n = REG ? ti_rl(rn, ks) : ln[ks];
-        t = REG ? ti_rl(rt, ks) : lt[ks];
-        const double hs = REG ? ti_rld(rh, ks) : (hv ? hv[kg + ks] : 1.0);
+        n = REG ? stb_wave_rl(rn, ks) : ln[ks];
+        t = REG ? stb_wave_rl(rt, ks) : lt[ks];
+        const double hs = REG ? stb_wave_rld(rh, ks) : (hv ? hv[kg + ks] : 1.0);
         if (n == 0) {
           n = 1, t = 1, T++;
         } else {

@@ -6,7 +6,8 @@
  *                    The launch sites compute grid, workgroup size and the room for block sums from stb_ticket_geom, and
  *                    stb_reduce_geometry (include/stb_hip.h) answers from the same function: what the query says is
  *                    what is launched.
- *   stb_wave_sum     the 64-lane shuffle tree of a double or a 64-bit count: k_logjoint, k_predict, k_heldout_sum,
+ *   stb_wave_sum     the 64-lane shuffle tree of a double or a 64-bit count.  Moved out to wave.h, which this header
+ *                    includes (MEASUREMENTS O6); its callers are still listed here: k_logjoint, k_predict, k_heldout_sum,
  *                    k_seat and k_seat_sum, the k_dm_* (dirmult.hip), k_dc_totals and k_dc_totals_rows (dirconc.hip), k_hg_count (hgroups.hip).  The
  *                    same tree stays written out in k_logq, k_sum_u32, k_joint_terms, k_hb_group_wg (hyperb.hip) and
  *                    k_eval_tail (groups.hip): there the call compiles to other code than the loop (MEASUREMENTS O3)
@@ -17,6 +18,7 @@
 #ifndef STB_TICKET_H
 #define STB_TICKET_H
 #include "stb_common.h"
+#include "wave.h"
 
 #define STB_TG_BLOCK 256u        // restaurants of a block sum: HQ_CHUNK, HJ_CHUNK, LJ_BLOCK and PR_BLOCK are defined as this
 #define STB_TG_CAP0_BLOCKS 4096u // block sums k_logq's and k_logjoint's first buffer holds
@@ -45,8 +47,8 @@ static inline int stb_ticket_geom(int which, uint64_t I, int D, int J, int waves
   g->nblk = (unsigned)((I + STB_TG_BLOCK - 1) / STB_TG_BLOCK);
   int nw = waves;
   if (!nw) {
-    nw = stb_env_int(which == STB_GEOM_LOGQ ? "STB_HYPERQ_WAVES" : which == STB_GEOM_JOINT_TERMS ? "STB_HYPERJ_WAVES" : "STB_LOGJOINT_WAVES", 0);
-    if (!(nw == 1 || nw == 2 || nw == 4 || nw == 8))
+    nw = stb_env_waves(which == STB_GEOM_LOGQ ? "STB_HYPERQ_WAVES" : which == STB_GEOM_JOINT_TERMS ? "STB_HYPERJ_WAVES" : "STB_LOGJOINT_WAVES", 0);
+    if (!nw)
       nw = which == STB_GEOM_LOGJOINT && g->nblk < 2u * (unsigned)(cus > 0 ? cus : 1) ? 8 : 4;
   }
   g->waves = (unsigned)nw;
@@ -69,20 +71,7 @@ static inline int stb_ticket_geom(int which, uint64_t I, int D, int J, int waves
 }
 
 // ------------------------------------------------------------------------------------------------
-// device: the sum over a wave's 64 lanes, v += shfl_down(v, o) for o = 32, 16, .. 1; the result is lane 0's
-
-__device__ __forceinline__ double stb_wave_sum(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long stb_wave_sum(unsigned long long v) {  // (integers: exact in any order)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
+// device
 
 // the ticket, called by all threads of every workgroup (ngroups of them): every store of the workgroup is published by
 // an agent-scope release ahead of it; true in the last workgroup to take one, which has acquired what the others published

@@ -1,11 +1,13 @@
 // tindic.h -- what tindic.hip (the indicator sweep), tdish.hip (the dish sweep) and tindic_obj.hip (the object) share: the counter-based uniforms, the V
-// cell look-up, the two decisions of a visit, and the wave's readlane helpers.  Both kernels evaluate a visit with these
-// functions, so a dish visit whose customer stays in its dish gives the indicator visit's bits.
+// cell look-up and the two decisions of a visit.  Both kernels evaluate a visit with these functions, so a dish visit whose
+// customer stays in its dish gives the indicator visit's bits.  Moved out (MEASUREMENTS O6): the wave's readlane helpers,
+// ti_rl and ti_rld, are wave.h's stb_wave_rl and stb_wave_rld; this header includes it.
 #ifndef STB_TINDIC_H
 #define STB_TINDIC_H
 
 #include "stb_common.h"
 #include "views.h"
+#include "wave.h"
 #include "uniforms.h"  // u1 of customer c is element j = 2c+1 of the sweep's stream, u2 is j = 2c+2
 
 #define STB_TI_REF_ODDS_FLAG 1u
@@ -27,19 +29,6 @@ __device__ __forceinline__ bool ti_add(unsigned n, unsigned t, uint32_t T, doubl
   const double odds = h * (b + (double)T * a) * (double)t / (double)(ref ? n - t + 1 : n - t) * V;
   const double p = isinf(odds) ? 1.0 : odds / (odds + 1.0);
   return u2 < p;
-}
-
-// ---- readlane helpers: every lane of a wave walks the same chain on the same values ----
-
-__device__ __forceinline__ unsigned ti_rl(unsigned v, unsigned j) {
-  return (unsigned)__builtin_amdgcn_readlane((int)v, (int)__builtin_amdgcn_readfirstlane((int)j));
-}
-__device__ __forceinline__ double ti_rld(double v, unsigned j) {
-  const int jj = __builtin_amdgcn_readfirstlane((int)j);
-  const uint64_t x = (uint64_t)__double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, jj);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), jj);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
 // the indicator sweep's launch (tindic.hip): nsweeps sweeps from k.sweep on; r.maxK = dishes a wave keeps in LDS; of cu the

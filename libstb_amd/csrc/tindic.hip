@@ -113,16 +113,16 @@ __global__ __launch_bounds__(64) void k_tindic_wave(const double *vt, unsigned N
           }
         }
         for (unsigned j = 0; j < L; j++) {
-          const unsigned n = ti_rl(mn, j);
+          const unsigned n = stb_wave_rl(mn, j);
           if (n <= 1 || n > N) continue;
-          const unsigned k = ti_rl(mk, j), t0 = ti_rl(mt0, j);
+          const unsigned k = stb_wave_rl(mk, j), t0 = stb_wave_rl(mt0, j);
           const uint64_t c = cb + j;
           unsigned t = inlds ? lt[k] : tv[k0 + k];
           if (ti_remove(n, t, stb_unit(key, 2 * c + 1))) t--, T--;
           const unsigned m = t + 1;
           // (an earlier visit in this chunk may have moved the dish's t out of the prefetched pair: a direct load)
-          const double V = m == t0 ? ti_rld(v0, j) : (m == t0 + 1 ? ti_rld(v1, j) : ti_V(vt, M, n, m));
-          if (ti_add(n, t, T, ti_rld(mh, j), a, b, V, stb_unit(key, 2 * c + 2), ref)) t++, T++;
+          const double V = m == t0 ? stb_wave_rld(v0, j) : (m == t0 + 1 ? stb_wave_rld(v1, j) : ti_V(vt, M, n, m));
+          if (ti_add(n, t, T, stb_wave_rld(mh, j), a, b, V, stb_unit(key, 2 * c + 2), ref)) t++, T++;
           if (inlds) lt[k] = (uint16_t)t;  // (every lane stores the same value)
           else tv[k0 + k] = (uint16_t)t;
         }
@@ -139,13 +139,13 @@ __global__ __launch_bounds__(64) void k_tindic_wave(const double *vt, unsigned N
           mh = hv ? hv[pb + lane] : 1.0;
         }
         for (unsigned j = 0; j < P; j++) {
-          const unsigned n = ti_rl(mn, j);
+          const unsigned n = stb_wave_rl(mn, j);
           if (n <= 1 || n > N) {
             c += n;
             continue;
           }
-          const unsigned t0 = ti_rl(mt, j);
-          const double h = ti_rld(mh, j);
+          const unsigned t0 = stb_wave_rl(mt, j);
+          const double h = stb_wave_rld(mh, j);
           unsigned t = t0;
           unsigned wb = t0 > 32 ? t0 - 32 : 0;  // the window holds m = wb .. wb+63
           double win = ti_V(vt, M, n, wb + lane);
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(64) void k_tindic_wave(const double *vt, unsigned N
               wb = m > 32 ? m - 32 : 0;
               win = ti_V(vt, M, n, wb + lane);
             }
-            if (ti_add(n, t, T, h, a, b, ti_rld(win, m - wb), stb_unit(key, 2 * c + 2), ref)) t++, T++;
+            if (ti_add(n, t, T, h, a, b, stb_wave_rld(win, m - wb), stb_unit(key, 2 * c + 2), ref)) t++, T++;
           }
           if (t != t0) tv[pb + j] = (uint16_t)t;
         }

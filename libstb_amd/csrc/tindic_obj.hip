@@ -205,7 +205,7 @@ static void ti_release(stb_tindic_t *s) {
 static stb_tindic_t *ti_create_here(int I, const int *K, const uint32_t *nflat, const uint16_t *tflat, const double *hflat,
                                     const uint32_t *cust, unsigned Mgiven, unsigned flags) {
   if (stb_device_count() < 1) {
-    stb_fail("stb_tindic_create: no HIP device (libstb_amd has no CPU path)");
+    stb_no_device("stb_tindic_create");
     return nullptr;
   }
   if (I < 1 || !K || !nflat || !tflat) {

@@ -229,8 +229,7 @@ __global__ __launch_bounds__(256) void k_tlik_llfinal(unsigned stride, const dou
 // host side.  Every call takes its scratch from the buffer cache and gives it back behind its one wait.
 
 static unsigned tl_waves() {
-  const int w = stb_env_int("STB_TLIK_WAVES", 4);
-  return w == 1 || w == 2 || w == 4 || w == 8 ? (unsigned)w : 4u;
+  return (unsigned)stb_env_waves("STB_TLIK_WAVES", 4);
 }
 
 static unsigned tl_cap_y(uint64_t want) { return want < 1 ? 1u : (want > 65535u ? 65535u : (unsigned)want); }
@@ -385,7 +384,7 @@ extern "C" int stb_sample_lik(const uint32_t *d_cnt, unsigned rows, unsigned str
   if (!d_cnt || !d_lik) return stb_fail("%s: d_cnt and d_lik are required", who);
   if (rows < 1 || stride < 1) return stb_fail("%s: rows=%u stride=%u (both must be >= 1)", who, rows, stride);
   if (stb_tl_check_prior(beta_host, rows, beta0, "beta", who)) return 1;
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   return stb_tl_sample_lik(d_cnt, rows, stride, beta_host, beta0, d_lik, seed, sweep, (hipStream_t)stream, who, nullptr);
 }
 
@@ -395,6 +394,6 @@ extern "C" int stb_lik_loglik(const uint32_t *d_cnt, const double *d_lik, unsign
   const char *who = "stb_lik_loglik";
   if (!d_cnt || !d_lik || !total_host) return stb_fail("%s: d_cnt, d_lik and total_host are required", who);
   if (rows < 1 || stride < 1) return stb_fail("%s: rows=%u stride=%u (both must be >= 1)", who, rows, stride);
-  if (stb_device_count() < 1) return stb_fail("%s: no HIP device (libstb_amd has no CPU path)", who);
+  if (stb_device_count() < 1) return stb_no_device(who);
   return stb_tl_loglik(d_cnt, d_lik, rows, stride, total_host, impossible_host, (hipStream_t)stream, who);
 }

@@ -61,7 +61,7 @@ def dense(S1, tab, N: int, M: int) -> np.ndarray:
 
 
 def _wave_scan(v: np.ndarray) -> np.ndarray:
-    """the Hillis-Steele scan of a 64-lane chunk, as the kernel's pt_scan adds"""
+    """the Hillis-Steele scan of a 64-lane chunk, as the kernel's stb_wave_scan (wave.h) adds"""
     v = v.copy()
     o = 1
     while o < 64:

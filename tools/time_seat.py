@@ -7,6 +7,8 @@ Shapes (restaurants x customers x dishes, 1000 classes):
   S = 10^5 x 200 x 50: stb_tindic_seat on all customers, then one dish sweep on the state it left
   Q = 1000 x 200 x 50, every customer held out on an empty object: stb_tindic_heldout_seq at R = 1, 16 and 64 particles,
       then (the customers seated) one dish sweep
+  L = 10^4 x 200 x 100: as S with more than 64 dishes a restaurant -- k_seat<false> and the LDS form of the visit and of
+      the dish sweep (not among the defaults)
 Classes at random, a = 0.3, b = 2, h = 1 / dishes, a random likelihood matrix.  Times are wall-clock around calls that
 wait for their own answer (median, min, max after one warm-up call); the first stb_tindic_seat of an object also
 materialises the customer sequence, so it is the warm-up.  Nothing here sets a threshold.
@@ -23,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from libstb_amd import capi  # noqa: E402
 
-SHAPES = {"S": (100000, 200, 50, 1000), "Q": (1000, 200, 50, 1000)}
+SHAPES = {"S": (100000, 200, 50, 1000), "Q": (1000, 200, 50, 1000), "L": (10000, 200, 100, 1000)}
 A_DISC, B_CONC = 0.3, 2.0
 PARTICLES = (1, 16, 64)
 
@@ -60,7 +62,7 @@ def run(name, reps):
            "waves": int(os.environ.get("STB_SEAT_WAVES", "4"))}
     ti, cls = make(I, per, K, rows, rng, seated=True)
     out = {}
-    if name == "S":
+    if name in ("S", "L"):
         def seat(r):
             out["total"], out["info"] = ti.seat(A_DISC, bpar, 5, r)
 
