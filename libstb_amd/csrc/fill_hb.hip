@@ -1519,7 +1519,7 @@ int stb_hb_dot_info(unsigned N, unsigned M, int D, hb_dot_info *out, int sum_C) 
   return 0;
 }
 
-int stb_launch_hb(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, unsigned **hdr_out, hipStream_t st, int out_kind) {
+int stb_launch_hb(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, a_pending *pend, unsigned **hdr_out, hipStream_t st, int out_kind) {
   const unsigned N = A.N, M = A.M;
   if (out_kind < 0 || out_kind > 3 || (out_kind && dot)) return stb_fail("stb_fill: output kind %d", out_kind);
   const hb_geom g = hb_geometry(N, M, D, dot ? ((dot->geom_C == 2 || dot->geom_C == 3) ? dot->geom_C : 4) : 0, (out_kind & 2) != 0);
@@ -1593,9 +1593,9 @@ int stb_launch_hb(fill_args &A, int D, char *ws, size_t ws_left, const dot_reque
     const bool need_zero = !dot || dot->ws_zero < g.zero_bytes;
     const bool need_s1 = !(dot && dot->no_s1) && !(out_kind & 2);  // (the V table has no column 1)
     if (need_zero && need_s1 && !(g.zero_bytes & 15) && !((uintptr_t)ws & 15) && stb_env_int("STB_HB_PREP", 1)) {
-      if (stb_launch_prep(A, D, ws, g.zero_bytes, st)) return 1;
+      if (stb_launch_prep(A, D, ws, g.zero_bytes, pend, st)) return 1;
     } else {
-      if (stb_a_flush(A, st)) return 1;
+      if (stb_a_flush(A, pend, st)) return 1;
       if (need_zero) HIPCHK(hipMemsetAsync(ws, 0, g.zero_bytes, st));
       if (need_s1 && stb_launch_s1(A, D, st)) return 1;
     }

@@ -285,19 +285,19 @@ __global__ __launch_bounds__(256) void k_prep(double *a, double *S1, uint64_t s1
     S1[(uint64_t)d * s1stride + n - 1] = (n == 1) ? 0.0 : lgamma((double)n - ad) - lg1;
 }
 
-int stb_launch_prep(const fill_args &A, int D, void *ws, size_t zero_bytes, hipStream_t st) {
+int stb_launch_prep(const fill_args &A, int D, void *ws, size_t zero_bytes, a_pending *pend, hipStream_t st) {
   if ((zero_bytes & 15) || ((uintptr_t)ws & 15)) return stb_fail("stb_fill: workspace of %zu bytes at %p is not 16-byte aligned", zero_bytes, ws);
   const unsigned nb = (A.N + 255) / 256 < 64 ? (A.N + 255) / 256 : 64;
   const uint64_t n16 = zero_bytes / 16;
   unsigned nz = (unsigned)((n16 + 1023) / 1024);  // four stores a thread at least
   if (nz > 2048) nz = 2048;
   if (nz < 1) nz = 1;
-  stb_a64 av;
-  int Da = 0;
-  if (!stb_a_take(&av, &Da)) Da = 0;
-  if (Da != 0 && Da != D) return stb_fail("stb_fill: %d discounts on their way, %d tables", Da, D);
+  a_pending none;
+  if (!pend) pend = &none;
+  if (pend->n != 0 && pend->n != D) return stb_fail("stb_fill: %d discounts on their way, %d tables", pend->n, D);
   hipLaunchKernelGGL(k_prep, dim3(nz + nb * (unsigned)D), dim3(256), 0, st, const_cast<double *>(A.a), A.S1, A.s1stride, A.N, nz, nb, (uint4 *)ws, n16,
-                     av, Da, nb * (unsigned)D);
+                     pend->av, pend->n, nb * (unsigned)D);
+  pend->n = 0;
   return 0;
 }
 

@@ -866,7 +866,7 @@ static int gh_launch(const gh_args &X, int G, unsigned grid, int P, hipStream_t 
   return 0;
 }
 
-int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, unsigned **hdr_out, hipStream_t st) {
+int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, a_pending *pend, unsigned **hdr_out, hipStream_t st) {
   const unsigned N = A.N, M = A.M;
   grid_geom g;
   if (stb_grid_geometry(N, M, D, &g)) return stb_fail("stb_groups_aterms: the grid form does not take N=%u M=%u D=%d", N, M, D);
@@ -925,7 +925,7 @@ int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_req
     HIPCHK(hipMalloc((void **)&X.dbg, dbg_words * 8));
     HIPCHK(hipMemsetAsync(X.dbg, 0, dbg_words * 8, st));
   }
-  if (stb_a_flush(A, st)) return 1;
+  if (stb_a_flush(A, pend, st)) return 1;
   if (!dot || dot->ws_zero < g.zero_bytes) HIPCHK(hipMemsetAsync(ws, 0, g.zero_bytes, st));
   if (dot) const_cast<dot_request *>(dot)->zero_bytes = g.zero_bytes;
   *hdr_out = X.hdr;

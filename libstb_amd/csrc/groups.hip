@@ -438,7 +438,7 @@ static int aterms_issue_lean(stb_groups_t *g, const double *x_host, int D, doubl
     g->pend_seq = g->seq;
     ((volatile double *)g->h_out)[2 * g->Dmax + 2] = 0.0;
   }
-  if (which >= 3 ? stb_launch_grid(A, D, ws, ws_left, &req, &hdr, g->st) : stb_launch_hb(A, D, ws, ws_left, &req, &hdr, g->st)) return 1;
+  if (which >= 3 ? stb_launch_grid(A, D, ws, ws_left, &req, nullptr, &hdr, g->st) : stb_launch_hb(A, D, ws, ws_left, &req, nullptr, &hdr, g->st)) return 1;
   // (the partial sums' room was checked inside the launch functions, before anything was queued: dot_request::dotp_cap)
   if (timed) HIPCHK(hipEventRecord(g->ev[1], g->st));
   if (timed) HIPCHK(hipEventRecord(g->ev[2], g->st));
@@ -483,11 +483,8 @@ static int aterms_issue(stb_groups_t *g, const double *x_host, int D, double *ou
     else req.cnt = g->d_cnt;
     req.dotp = g->d_dotp;
     req.dotp_cap = g->dotp_elems;
-    stb_set_dot_request(&req);
-    const int rc = stb_fill_S(x_host, D, g->N, g->M, g->d_tables, g->tstride, g->d_S1, g->N, g->d_ws_fill,
-                              g->ws_fill, which ? STB_FILL_CK : STB_FILL_CHAIN, g->st);
-    stb_set_dot_request(nullptr);
-    if (rc) return 1;
+    const fill_request q = {g->N, g->M, D, which ? STB_FILL_CK : STB_FILL_CHAIN, 0, false, &req};
+    if (stb_fill(q, x_host, g->d_tables, g->tstride, g->d_S1, g->N, g->d_ws_fill, g->ws_fill, g->st)) return 1;
     stb_fill_last(&g->pend_fill);
     if ((size_t)D * req.parts_per_table > g->dotp_elems) return stb_fail("stb_groups_aterms: partial-sum buffer too small");
     HIPCHK(hipEventRecord(g->ev[1], g->st));
@@ -580,10 +577,7 @@ static int aterms_once(stb_groups_t *g, const double *x_host, int D, double *out
 // The summing halo-block form (tile workers sum) holds while its spine workgroups leave the workers a quarter of the
 // chip: 25/32 of the compute units (200 of an MI355X's 256: 28 discounts of 10^4 columns at 7 strips a workgroup;
 // measured 28 discounts 0.99 ms against the grid form's 1.21, 30: 1.55, 32: 2.03 against 1.23).  STB_ATERMS_HB_MAX_SPINE overrides.
-static unsigned hb_max_spine() {
-  const int e = stb_env_int("STB_ATERMS_HB_MAX_SPINE", 0);
-  return e > 0 ? (unsigned)e : (unsigned)(stb_cu_count() * 25 / 32);
-}
+static unsigned hb_max_spine() { return stb_spine_room("STB_ATERMS_HB_MAX_SPINE"); }
 
 // which form an evaluation of D discounts takes, with the one-off set-up of the fused form done
 static int aterms_prepare(stb_groups_t *g, int D, bool allow_fuse, bool *fuse_out, int *v_out) {

@@ -169,7 +169,8 @@ void stb_note_span(double span_ms, double expect_ms, const char *what);
 #define STB_HDR_T1 8
 
 // the forms (each in its own translation unit); all return 0 or stb_fail(...)
-struct dot_request {  // set by stb_groups_aterms around its fill: the chain form sums count * log S
+struct a_pending;  // (a fill's discounts not on the device yet: below)
+struct dot_request {  // what stb_groups_aterms asks of its fill (fill_request::dot): the form sums count * log S
   const unsigned *cnt = nullptr;           // dense: occurrence count per cell, table layout
   const unsigned *item_ptr = nullptr;      // sparse: CSR over (trip, slice) items
   const unsigned short *ent_pos = nullptr; //         row-in-trip << 6 | column-in-slice
@@ -191,7 +192,18 @@ struct dot_request {  // set by stb_groups_aterms around its fill: the chain for
   size_t zero_bytes = 0;                   // out: bytes at the start of the workspace the launch needs zero (and dirties)
   int no_s1 = 0;                           // in: nobody reads the S1 vector (column 1 is among the listed cells)
 };
-void stb_set_dot_request(const dot_request *r);  // for the next stb_fill_S of this thread
+// what a caller asks of a fill (fill.hip makes one plan of it: the form, its geometry, what stb_fill_status may do after)
+struct fill_request {
+  unsigned N, M;
+  int D;
+  int variant;             // STB_FILL_* (kinds 1-3: STB_FILL_SCALED)
+  int kind;                // 0 log S (double), 1 log S (float), 2 V (double), 3 V (float)
+  bool v_exact;            // kind 2: the reference's own V recurrence whatever the size (stb_fill_V_exact)
+  const dot_request *dot;  // kind 0: the fused evaluation's sums instead of stored cells, or null
+};
+// the fill behind stb_fill_S / _Sf / _V / _Vf (d_tables: the slab of the kind's type; d_S1 null for the V kinds)
+int stb_fill(const fill_request &q, const double *a_host, double *d_tables, uint64_t table_stride, double *d_S1, uint64_t s1_stride,
+             void *d_ws, size_t ws_bytes, hipStream_t st);
 size_t stb_chain_workspace(unsigned N, unsigned M, int D);
 int stb_launch_chain(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, unsigned **hdr_out,
                      hipStream_t st);
@@ -208,6 +220,13 @@ unsigned stb_ck_dot_parts(unsigned N, unsigned M, int D) __attribute__((weak)); 
 unsigned stb_ck_dot_spine(unsigned N, unsigned M, int D) __attribute__((weak));  // spine workgroups it launches for D tables
 
 int stb_cu_count();  // compute units of the current device
+// spine workgroups a one-launch form may take while its tile workers keep room: 25/32 of the compute units (200 of an
+// MI355X's 256), or what the variable `override_env` says where it is positive (STB_HB_MAX_SPINE for the storing fill,
+// STB_ATERMS_HB_MAX_SPINE for the summing one)
+static inline unsigned stb_spine_room(const char *override_env) {
+  const int e = stb_env_int(override_env, 0);
+  return e > 0 ? (unsigned)e : (unsigned)(stb_cu_count() * 25 / 32);
+}
 // halo-block form (fill_hb.hip): a spine that walks blocks of rows alone + tile workers, one launch
 bool stb_hb_eligible(unsigned N, unsigned M, int D);
 bool stb_hb_eligible_out(unsigned N, unsigned M, int D, int out_kind);
@@ -215,7 +234,7 @@ size_t stb_hb_workspace(unsigned N, unsigned M, int D);
 unsigned stb_hb_spine(unsigned N, unsigned M, int D);  // spine workgroups of a fill of D tables
 int stb_hb_tuning(unsigned N, unsigned M, int D, int *W_out, int *rows_out);  // own columns of a strip, rows of a block
 // out_kind: 0 log S (double), 1 log S (float), 2 V = S^n_m / S^n_{m-1} (double), 3 V (float); A.tables is the slab of that type
-int stb_launch_hb(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, unsigned **hdr_out, hipStream_t st, int out_kind = 0);
+int stb_launch_hb(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, a_pending *pend, unsigned **hdr_out, hipStream_t st, int out_kind = 0);
 struct hb_dot_info {  // the tiles of the summing halo-block form (cell lists: item = record index * NQ + group of 4 rows)
   int R, UC, HC, NB, JW, NQ;   // rows of a block, own columns of a strip, halo columns, blocks, strips, groups per item base
   int G, C;                    // rows of a group, columns per lane
@@ -239,18 +258,22 @@ struct grid_geom {
 int stb_grid_geometry(unsigned N, unsigned M, int D, grid_geom *out);
 size_t stb_grid_workspace(unsigned N, unsigned M, int D);
 unsigned stb_grid_job_cap(int C, int D, unsigned n_tiles, int phases);
-int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, unsigned **hdr_out, hipStream_t st);
+int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_request *dot, a_pending *pend, unsigned **hdr_out, hipStream_t st);
 
 int stb_launch_pc(fill_args &A, int D, hipStream_t st);
 int stb_launch_s1(const fill_args &A, int D, hipStream_t st);
 // The discounts of a fill on their way to A.a (device): a copy of a few bytes from pageable host memory is a 4.4 us copy
 // kernel of its own behind a staging buffer; up to 64 discounts travel as kernel arguments instead -- of k_prep when the
-// launcher has one (stb_a_take), else of a kernel of their own (stb_a_flush; no-ops when nothing is on its way).
+// launcher has one (stb_launch_prep), else of a kernel of their own (stb_a_flush).  The caller of a launcher owns them in
+// an a_pending and passes its address; whoever puts them on the device sets n to 0.  A null pointer, or n = 0: they are
+// there already, and nothing is launched for them.
 struct stb_a64 { double v[64]; };
-void stb_a_defer(const double *a_host, int D);
-bool stb_a_take(stb_a64 *out, int *D_out);
-int stb_a_flush(const fill_args &A, hipStream_t st);
-int stb_launch_prep(const fill_args &A, int D, void *ws, size_t zero_bytes, hipStream_t st);  // k_s1 + a zeroed workspace (+ the discounts on their way), one launch
+struct a_pending {
+  stb_a64 av = {};
+  int n = 0;  // > 0: that many discounts are not on the device yet
+};
+int stb_a_flush(const fill_args &A, a_pending *pend, hipStream_t st);
+int stb_launch_prep(const fill_args &A, int D, void *ws, size_t zero_bytes, a_pending *pend, hipStream_t st);  // k_s1 + a zeroed workspace (+ the discounts on their way), one launch
 #define STB_ROWS_LOGDOM 1
 #define STB_ROWS_VRATIO 2
 int stb_launch_rows(fill_args &A, int D, int C, int what, hipStream_t st);
