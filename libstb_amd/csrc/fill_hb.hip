@@ -29,7 +29,7 @@
 // computes it along.  The state before block b is row 1 + b R; row 1 is S^1_1 = 1.
 //
 // Round 6: what lies between two blocks' rows on a spine wave (hand-over, record, halo, renormalisation) was ~125
-// instructions and ~840 cycles beside the rows' ~1500; the block loop below (HB_LEAN) does it in ~60 and ~440 -- nothing
+// instructions and ~840 cycles beside the rows' ~1500; the block loop below (the lean top) does it in ~60 and ~440 -- nothing
 // masked, one LDS word per lane for all signalling, the halo asked for a record's stores ahead of its use, the
 // renormalisation shift taken four rows before the block's end.  MEASUREMENTS.md section R6.1.
 //
@@ -43,24 +43,17 @@
 #include <type_traits>
 #include <vector>
 
-#include "fill_chain.h"
+#include "hb_spine.h"
 
 #ifndef HB_NW
 #define HB_NW 8          // waves per workgroup: up to HB_PMAX spine waves and a fetcher
 #endif
-#define HB_PMAX 7
 #define HB_SLOTS 8       // ring of hand-overs between two spine waves of a workgroup (blocks); looked after every 4th block
 #define HB_FSLOTS 8      // ring of hand-overs from the fetcher to spine wave 0
-#define HB_MAXHL 32      // halo lanes at most
-// ... per strip shape: blocks have at most 48 rows with 2 or 4 columns per lane (+ a lane for the V table), 32 with one -- what
-// the hand-over rings in LDS are sized by (4 columns: 23 KB instead of 57)
-__host__ __device__ constexpr int hb_mhl(int C) { return C == 1 ? HB_MAXHL : (C == 2 ? 25 : (C == 3 ? 17 : 13)); }
 #ifndef HB_NW_DOT4
 #define HB_NW_DOT4 14
 #endif                   // waves per workgroup of the summing form with 4 columns per lane: its tile workers are what a grid of 8-28
                          // discounts waits for, and a workgroup has its compute unit alone (LDS) -- four more of them on it
-#define HB_EOFF32 (1u << 30)
-#define HB_WRITTEN 0x8000000000000000ull  // a record's significands (never negative) travel with the sign bit set
 #define HB_DOT_GR 8        // rows of a group of the summing form: its listed cells are looked up together, one per lane and pass
                            // (4 rows: 12 passes a tile, each with its LDS round trips exposed -- a worker wave has one
                            // partner on its SIMD -- and a quarter of the lanes at work; 8 rows: 6 fuller passes)
@@ -73,22 +66,12 @@ __host__ __device__ constexpr int hb_mhl(int C) { return C == 1 ? HB_MAXHL : (C 
 #define HB_PROG_STRIDE 32  // words between two strips' progress words: a line each (a strip's waiting workers poll
                            // the word its spine wave writes; 125 strips' words in four lines made those lines the
                            // busiest of the chip and the spine's stores to them slow: its store queue filled up)
-#define HB_SPIN 48         // looks at a neighbour's counter, ~0.1 us apart, before the out-of-line wait
 // timeline stamps of the spine: the 100 MHz wall clock, or (diagnostic build -DHB_TL_CYCLES) the shader clock,
 // which tells a slower clock from waiting
 #ifdef HB_TL_CYCLES
 #define HB_STAMP() ((unsigned long long)clock64())
 #else
 #define HB_STAMP() ((unsigned long long)wall_clock64())
-#endif
-#ifndef HB_LTX
-#define HB_LTX 0           // 1: the storing kernels hold the log table 16 times in LDS (no bank conflicts), 0: once.  Measured
-                           // (MI355X, tools/ab_lib.py, N = M = 10^4, medians): 8 tables 0.772 / 0.813 ms with either, 16 tables
-                           // 1.446 against 1.444, one table 0.332 against 0.325 (32 KB more to set up per workgroup): the
-                           // storing workers wait for their stores, not for LDS -- left off
-#endif
-#ifndef HB_DIAG
-#define HB_DIAG 0          // diagnostic builds: 1 the spine stores no records, 2 it stores every record twice, 8 the workers store nothing, 16 summing workers look nothing up, 32 ... and stage nothing (results wrong)
 #endif
 
 struct hb_args {
@@ -123,67 +106,14 @@ struct hb_args {
                                // then [n_tiles][4] workers (claimed, inputs loaded, done, hardware id)
 };
 
-typedef double hb_double2 __attribute__((ext_vector_type(2)));
-
-// aligned 16-byte store at (wave-uniform base) + (per-lane byte offset); see store_sbase
-__device__ __forceinline__ void hb_store16(const void *sbase, unsigned byte_off, double x, double y) {
-  unsigned long long base_copy;
-  hb_double2 v2 = {x, y};
-  asm volatile("s_mov_b64 %0, %3\n\tglobal_store_dwordx4 %1, %2, %0\n\ts_nop 1"
-               : "=&s"(base_copy)
-               : "v"(byte_off), "v"(v2), "s"(sbase)
-               : "memory");
-}
-
-// two record words with one write-through store (what __hip_atomic_store at agent scope compiles to, 16 bytes wide)
-__device__ __forceinline__ void hb_store_wt16(unsigned long long *p, unsigned long long a, unsigned long long b) {
-  typedef unsigned long long hb_u64x2 __attribute__((ext_vector_type(2)));
-  const hb_u64x2 v2 = {a, b};
-  // (s_nop: a store of more than 8 bytes reads its data a cycle or two after it issues, and the compiler does
-  // not look into an asm statement for the VALU write of those registers that may follow)
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v2) : "memory");
-}
-
-// the record of a spine block: C words per lane (each with the sign bit set) behind `p`, written through, by the lanes of
-// `mask` only -- the mask goes into exec and comes out again inside the statement: no branch round the stores (the
-// compiler's own masked region moved them out of line, two taken branches a block on the lone wave's path)
-template <int C>
-__device__ __forceinline__ void hb_store_record(unsigned long long mask, unsigned long long *p, const double (&v)[C]) {
-  typedef unsigned long long hb_u64x2 __attribute__((ext_vector_type(2)));
-  unsigned long long saved;
-  if constexpr (C == 1) {
-    const unsigned long long a = (unsigned long long)__double_as_longlong(v[0]) | HB_WRITTEN;
-    asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dwordx2 %2, %3, off sc1\n\ts_mov_b64 exec, %0" : "=&s"(saved) : "s"(mask), "v"(p), "v"(a) : "memory");
-  } else if constexpr (C == 2) {
-    const hb_u64x2 a = {(unsigned long long)__double_as_longlong(v[0]) | HB_WRITTEN, (unsigned long long)__double_as_longlong(v[1]) | HB_WRITTEN};
-    asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dwordx4 %2, %3, off sc1\n\ts_nop 0\n\ts_mov_b64 exec, %0" : "=&s"(saved) : "s"(mask), "v"(p), "v"(a) : "memory");
-  } else if constexpr (C == 3) {
-    const hb_u64x2 a = {(unsigned long long)__double_as_longlong(v[0]) | HB_WRITTEN, (unsigned long long)__double_as_longlong(v[1]) | HB_WRITTEN};
-    const unsigned long long c = (unsigned long long)__double_as_longlong(v[2]) | HB_WRITTEN;
-    asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dwordx4 %2, %3, off sc1\n\tglobal_store_dwordx2 %2, %4, off offset:16 sc1\n\ts_nop 0\n\ts_mov_b64 exec, %0"
-                 : "=&s"(saved) : "s"(mask), "v"(p), "v"(a), "v"(c) : "memory");
-  } else {
-    static_assert(C == 4, "columns per lane");
-    const hb_u64x2 a = {(unsigned long long)__double_as_longlong(v[0]) | HB_WRITTEN, (unsigned long long)__double_as_longlong(v[1]) | HB_WRITTEN};
-    const hb_u64x2 c = {(unsigned long long)__double_as_longlong(v[2]) | HB_WRITTEN, (unsigned long long)__double_as_longlong(v[3]) | HB_WRITTEN};
-    asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dwordx4 %2, %3, off sc1\n\tglobal_store_dwordx4 %2, %4, off offset:16 sc1\n\ts_nop 0\n\ts_mov_b64 exec, %0"
-                 : "=&s"(saved) : "s"(mask), "v"(p), "v"(a), "v"(c) : "memory");
-  }
-}
-
 // ---- the log of a block-floating cell, eight cells at a time, stage-major (as in k_fill_chain) ----
-// (LTX: the table is held 16 times, entry e of copy c at lt[e * 16 + c], and a lane reads copy lane & 15: the sixteen lanes
-// a 16-byte LDS read serves per cycle then sit on sixteen different slots whatever their entries -- no bank conflicts,
-// where 64 random entries of ONE 2 KB table cost a storing worker 56 % of its LDS cycles, profiles/r03_sq_counters_fill8.txt)
-template <bool LTX>
 __device__ __forceinline__ void hb_logs8(const double (&x)[8], const int (&ep8)[8], const double2 *lt, int one_hi, double (&val)[8]) {
   double z[8], kf[8], r[8], pl[8];
   double2 tt[8];
-  const int l15 = LTX ? (int)(threadIdx.x & 15) : 0;
 #pragma unroll
   for (int u = 0; u < 8; u++) {
     const int e = (__double2hiint(x[u]) >> 13) & 127;
-    tt[u] = lt[LTX ? (e << 4) | l15 : e];
+    tt[u] = lt[e];
   }
 #pragma unroll
   for (int u = 0; u < 8; u++) {
@@ -205,69 +135,12 @@ __device__ __forceinline__ void hb_logs8(const double (&x)[8], const int (&ep8)[
   for (int u = 0; u < 8; u++) val[u] = fma(kf[u], 0.693147180559945309417, fma(r[u], pl[u], tt[u].y));
 }
 
-// renormalise a lane: the largest of its C significands (none is negative) back to 2^-PC_BIAS * [0.5,1)
-template <int C>
-__device__ __forceinline__ void hb_renorm(double (&v)[C], int &ep) {
-  double vmax = v[0];
-#pragma unroll
-  for (int i = 1; i < C; i++) vmax = fmax(vmax, v[i]);
-  const int sh = (vmax != 0.0) ? __builtin_amdgcn_frexp_exp(vmax) + PC_BIAS : 0;
-#pragma unroll
-  for (int i = 0; i < C; i++) v[i] = ldexp(v[i], -sh);
-  ep += sh;
-}
-
-// ... in two steps: the shift (from the lane as it stands) and its application (possibly to the lane a few rows later: any
-// shift that keeps the significands in range is as good as any other -- the arithmetic is scale-free and the logs are taken
-// from exponent field + lane exponent together)
-template <int C>
-__device__ __forceinline__ int hb_renorm_shift(const double (&v)[C]) {
-  // (v_max_f64 as written: fmax() first quiets its operands, an instruction each -- nothing here is a NaN)
-  double vmax = v[0];
-#pragma unroll
-  for (int i = 1; i < C; i++) asm("v_max_f64 %0, %1, %2" : "=v"(vmax) : "v"(vmax), "v"(v[i]));
-  int sh = (vmax != 0.0) ? __builtin_amdgcn_frexp_exp(vmax) + PC_BIAS : 0;
-  asm volatile("" : "+v"(sh));  // (here, not where it is used)
-  return sh;
-}
-template <int C>
-__device__ __forceinline__ void hb_renorm_apply(double (&v)[C], int &ep, int sh) {
-#pragma unroll
-  for (int i = 0; i < C; i++) v[i] = ldexp(v[i], -sh);
-  ep += sh;
-}
-
-// eight rows of the recurrence: lane l takes the last column of lane l - 1 (lane 0: nothing), scaled
-// by s = 2^(exponent of lane l-1 - exponent of lane l), frozen for the block
-template <int C>
-__device__ __forceinline__ void hb_row(double (&v)[C], double (&coef)[C], double s) {
-  const double t0 = wave_shr1_zero(v[C - 1]) * s;
-#pragma unroll
-  for (int i = C - 1; i >= 1; i--) v[i] = fma(coef[i], v[i], v[i - 1]);
-  v[0] = fma(coef[0], v[0], t0);
-#pragma unroll
-  for (int i = 0; i < C; i++) coef[i] += 1.0;
-}
-
-// first block of strip j: the state before it has nothing in the strip's own columns (2 + j U C and up)
-__host__ __device__ static inline int hb_first_block(int j, int UC, int R) { return (int)(((long long)j * UC) / R); }
-
 // OUT: what the tile workers store -- 0 log S^n_m as double (S_remake_part, lib/stable.c:321-388), 1 the same narrowed to
 // float (S_FLOAT, lib/stable.c:389-449: all arithmetic in double, only the stored value is a float), 2 the ratio
 // V^n_m = S^n_m / S^n_{m-1} as double (S_UVTABLE, lib/stable.c:451-482: a block-floating cell and its left neighbour are
 // one division away from it), 3 that ratio as float (lib/stable.c:483-537).
 #define HB_LIKELY(x) __builtin_expect(!!(x), 1)
 #define HB_UNLIKELY(x) __builtin_expect(!!(x), 0)
-#ifndef HB_LEAN
-#define HB_LEAN 1  // 0: the block top as rounds 3-5 had it (a masked region per step, two waits for LDS; kept for A/B runs: make variant DEFS=-DHB_LEAN=0)
-#endif
-#define HB_EB (HB_LEAN ? HB_EOFF32 : 0u)
-#ifndef HB_LEAN_MASK
-#define HB_LEAN_MASK 0  // 1: the lean top's hand-over and halo touch LDS with their own lanes only (masked regions again, less LDS work): measured, see MEASUREMENTS R6.1
-#endif
-#ifndef HB_ABL
-#define HB_ABL 0  // timing-only builds (results wrong): the spine leaves out 1 the halo read, 2 the ring store, 4 the renormalisation, 8 the record, 16 the progress word
-#endif
 template <int C, int DOT, int OUT = 0>
 __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (DOT != 0 && C >= 3) ? 1 : 2) void k_fill_hb(fill_args A, hb_args X) {
   static_assert(C == 1 || C == 2 || C == 4 || (C == 3 && DOT != 0), "columns per lane (3: the summing form only)");
@@ -275,8 +148,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
   constexpr bool VT = (OUT & 2) != 0, FL = (OUT & 1) != 0;
   // a worker lane's groups of adjacent elements (see the workers; a float row of 4 columns per lane is one 16-byte store)
   constexpr int NG = (C == 4 && DOT == 0 && !FL) ? 2 : 1, CG = C / NG;
-  constexpr bool LTX = (DOT == 0) && (HB_LTX != 0);  // the storing kernels hold the log table 16 times (see hb_logs8)
-  __shared__ double2 lt[LTX ? 128 * 16 : 128];
+  __shared__ double2 lt[128];
   // what a spine wave hands to its right neighbour at the start of a block: its rightmost HL lanes
   constexpr int NW = (DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW, MHL = hb_mhl(C);
   // Ring r (r = 0 .. P) is what spine wave r READS its halo from: ring 0 is filled by the fetcher (the left workgroup's last
@@ -300,11 +172,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid == 0) s_ticket = atomicAdd(X.hdr, 1u);
-  if constexpr (LTX) {
-    for (int i = tid; i < 128 * 16; i += blockDim.x) lt[i] = A.lt[i >> 4];
-  } else {
-    if (tid < 128) lt[tid] = A.lt[tid];
-  }
+  if (tid < 128) lt[tid] = A.lt[tid];
   const bool order_in_lds = X.order_lds != 0;
   if (order_in_lds)
     for (unsigned i = tid; i < X.n_order; i += blockDim.x) s_order[i] = X.order[i];
@@ -345,20 +213,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
     __syncthreads();
     const unsigned who = (unsigned)(j | (d << 16));
     bool aborted = false;
-    // (neighbours reach a block's end within a fraction of a microsecond of each other: a short wait is
-    // spun out here -- the out-of-line wait is a call, and a call waits for every store under way)
-    auto wait_ge = [&](const int *cnt, int need, unsigned code) {
-      if (aborted) return;
-      for (int k = 0; k < HB_SPIN; k++) {
-        if (lds_peek(cnt) >= need) {
-          asm volatile("" ::: "memory");  // (what the counter guards is read or written after it)
-          return;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (!chain_wait_slow(cnt, need, &s_abort, X.hdr, X.timeout, code, who, 1)) aborted = true;
-      asm volatile("" ::: "memory");
-    };
+    auto wait_ge = [&](const int *cnt, int need, unsigned code) { hb_wait_ge(cnt, need, code, aborted, &s_abort, X.hdr, X.timeout, who); };
     const size_t tab_rec = (size_t)d * X.n_rec;
 
     if (wave < P) {
@@ -377,7 +232,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
           v[i] = 0.0;
           coef[i] = (double)(1 + b0 * R) - (double)(m0 + i) * a;
         }
-        int ep = 1 + PC_BIAS + (int)HB_EB;  // (HB_EB: what the lean spine's exponents carry, in registers and in the rings: a record's own offset)
+        int ep = 1 + PC_BIAS + (int)HB_EOFF32;  // (the spine's exponents carry a record's own offset, in registers and in the rings)
         if (jw == 0 && lane == HL - 1) v[C - 1] = ldexp(1.0, -1 - PC_BIAS);  // row 1: S^1_1 = 1
         const bool has_next = (w + 1 < P) && (jw + 1 < X.JW);
         const int *left_cnt = &c_posted[w];
@@ -401,8 +256,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
 #else
 #define HB_FINE(k)
 #endif
-#if HB_LEAN
-        // ---- the lean block top (round 6).  A block's 48 rows are ~1500 cycles of a lone wave; what the compiler made of
+        // ---- the lean block top (round 6). A block's 48 rows are ~1500 cycles of a lone wave; what the compiler made of
         // the hand-over, the record and the halo between two blocks' rows was ~125 instructions and ~800 cycles more (masked
         // regions with their branches, three waits for LDS, address products).  Here nothing is masked and nothing is
         // multiplied: every lane writes its significands to a ring (the lanes that hand nothing over into a spare one),
@@ -438,7 +292,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
           HB_FINE(1);
           const int so = b & (HB_SLOTS - 1);
           // ---- hand-over to the right: significands and exponent of every lane, then the counters ----
-          if (!HB_LEAN_MASK || hand) {
+          {
             double *dst = &rgv[wv_idx + so * SLOTV];
             if constexpr (C == 1) {
               dst[0] = v[0];
@@ -461,11 +315,11 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
           asm volatile("" ::: "memory");
           double hv[C];
           int he = 0;
-          if constexpr (HB_LEAN_MASK != 0) {
-#pragma unroll
-            for (int i = 0; i < C; i++) hv[i] = 0.0;
-          }
-          if (!HB_LEAN_MASK || lane < HL) {
+          // (HL is named here so that the loop's closure still holds it, as it did while a switched-off alternative masked
+          // this read by it.  Without it the compiler lays the closure out otherwise and every k_fill_hb comes out with
+          // other registers and a few instructions more or fewer -- nothing measured, so nothing moved: MEASUREMENTS O8.)
+          (void)HL;
+          {
             const double *src = &rgv[rv_idx + so * SLOTV];
             if constexpr (C == 1) {
               hv[0] = src[0];
@@ -545,10 +399,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
           }
           HB_FINE(4);
           // ---- R rows alone ----
-          {
-            const int dl = wave_shr1(ep, ep) - ep;
-            s = ldexp(1.0, min(max(dl, -1100), 220));
-          }
+          s = hb_left_scale(ep);
           HB_FINE(5);
           // (the next block's renormalisation shift is taken from the lane four rows before the block's end -- the rows hide
           // its dependent steps; what the significands grow by in four rows, at most 2^(4 (2 log2 N + 1)), is inside the
@@ -578,129 +429,6 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
           spine_loop(std::true_type{});
         else
           spine_loop(std::false_type{});
-#else
-        // what a block begins with and needs no halo for: the hand-over to the right neighbour in the workgroup and the
-        // block's record, both of the wave as it stands
-        auto block_top = [&](const int b) {
-          // ---- the rightmost HL lanes, for the right neighbour in this workgroup ----
-            if (has_next && (HB_ABL & 2)) lds_post(&c_posted[w + 1], b + 1);
-            if (HB_LIKELY(has_next) && !(HB_ABL & 2)) {
-              // (the ring holds 8 blocks: every 4th block it is made sure that the right neighbour has taken all
-              // but the last 4, which covers this block and the next three)
-              if (HB_UNLIKELY((b & 3) == 0 || b == b0)) wait_ge(&c_taken[w + 1], b - 4, 0x400u);
-              if (lane >= U) {
-                double *dst = &rgv[(w + 1) * RINGV + (b & (HB_SLOTS - 1)) * SLOTV + (lane - U) * C];
-#pragma unroll
-                for (int i = 0; i < C; i++) dst[i] = v[i];
-                rge[(w + 1) * RINGE + (b & (HB_SLOTS - 1)) * MHL + lane - U] = ep;
-              }
-              lds_post(&c_posted[w + 1], b + 1);
-            }
-            HB_FINE(2);
-            // ---- the record of the block: the own lanes as they stand before it (the halo lanes of strip 0 are
-            // exact: they go to strip index 0 at the place a left neighbour's rightmost lanes would have).
-            // (A publisher wave that takes the row from LDS and stores it in the spine's stead was tried: the spine
-            // got slower, 36 against 32.5 ns a row alone and 53 against 48 beside eight tables' workers.) ----
-            if (HB_LIKELY(own || jw == 0) && !(HB_DIAG & 1) && !(HB_ABL & 8)) {
-              unsigned long long *dst = rec_v + (size_t)b * (size_t)(U * C);
-              if constexpr (C == 1) {
-                __hip_atomic_store(dst, (unsigned long long)__double_as_longlong(v[0]) | HB_WRITTEN, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-              } else if constexpr (C == 3) {
-                hb_store_wt16(dst, (unsigned long long)__double_as_longlong(v[0]) | HB_WRITTEN, (unsigned long long)__double_as_longlong(v[1]) | HB_WRITTEN);
-                __hip_atomic_store(dst + 2, (unsigned long long)__double_as_longlong(v[2]) | HB_WRITTEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              } else {
-#pragma unroll
-                for (int i = 0; i < C; i += 2)
-                  hb_store_wt16(dst + i, (unsigned long long)__double_as_longlong(v[i]) | HB_WRITTEN,
-                                (unsigned long long)__double_as_longlong(v[i + 1]) | HB_WRITTEN);
-              }
-              __hip_atomic_store(rec_e + (size_t)b * (size_t)U, (unsigned)ep + HB_EOFF32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (lane == 0 && !(HB_ABL & 16)) __hip_atomic_store(prog, (unsigned)(b + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        // Everything is set up (the loads above included) -- and the first block's top done: its record and hand-over are
-        // the wave as it stands, nothing of the halo -- before the wave dozes until the fetcher has the first
-        // halo: a strip can never make up for a late start -- its neighbours walk at the same pace -- so what a
-        // workgroup loses at its start is added to the end of the fill, once per workgroup of the table
-        // (tools/hop_hb.py: a hop is 0.8 us of hand-over and as much again of never-recovered start).
-        block_top(b0);
-        while (!lds_peek(&s_awake) && !lds_peek(&s_abort)) __builtin_amdgcn_s_sleep(2);
-        // ... and until its left neighbour in the workgroup is about to hand over the first halo: a wave that spins on
-        // the counter inside the block loop (every 64 cycles) takes issue slots from the spine wave it shares a SIMD
-        // with (waves w and w + 4 of a workgroup) for as many blocks as the diagonal is away
-        if (w > 0 && X.doze)
-          while (lds_peek(left_cnt) < b0 + 1 && !lds_peek(&s_abort)) __builtin_amdgcn_s_sleep(8);
-        __builtin_amdgcn_s_setprio(3);
-        if (dbg) dbg[0] = HB_STAMP();
-        for (int b = b0; b < NB; b++) {
-          HB_FINE(0);
-          if (HB_LIKELY(b > b0)) {
-            if (!(HB_ABL & 4)) hb_renorm<C>(v, ep);
-            HB_FINE(1);
-            block_top(b);
-          }
-          HB_FINE(3);
-          // ---- the halo: the left neighbour's rightmost HL lanes as they stand before the block ----
-          if (jw > 0 && (HB_ABL & 1)) lds_post(&c_taken[w], b + 1);
-          if (HB_LIKELY(jw > 0) && !(HB_ABL & 1)) {
-            // (the counter and the data are asked for together -- LDS serves a wave's requests in order, so data
-            // read after a counter that says "there" is there -- and only if the counter says "not yet" is it
-            // waited for and the data read again: one LDS round trip instead of two.  Asking at the top of the block,
-            // so that the round trip passes behind the hand-over and the record above, gains nothing: measured 0.316 ms
-            // either way for one table -- the round trip is not what a block waits for)
-            double hv[C];
-            int he = 0;
-            const double *src = &rgv[w * RINGV + (b & (HB_SLOTS - 1)) * SLOTV + lane * C];
-            const int *srce = &rge[w * RINGE + (b & (HB_SLOTS - 1)) * MHL + lane];
-            const int seen = aborted ? 0x7fffffff : lds_peek(left_cnt);
-#ifdef HB_TL_FINE
-            if (fdbg) fdbg[(size_t)b * 8 + 7] = (unsigned long long)(unsigned)(seen - b + 100);
-#endif
-            asm volatile("" ::: "memory");
-            if (lane < HL) {
-#pragma unroll
-              for (int i = 0; i < C; i++) hv[i] = src[i];
-              he = *srce;
-            }
-            if (HB_UNLIKELY(seen < b + 1)) {
-              wait_ge(left_cnt, b + 1, 0x100u);
-              if (lane < HL) {
-#pragma unroll
-                for (int i = 0; i < C; i++) hv[i] = src[i];
-                he = *srce;
-              }
-            }
-            if (lane < HL) {
-#pragma unroll
-              for (int i = 0; i < C; i++) v[i] = hv[i];
-              ep = he;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the slot is in registers: it may be written again)
-            lds_post(&c_taken[w], b + 1);
-          }
-          if (dbg) dbg[1 + b] = HB_STAMP();
-          HB_FINE(4);
-          // ---- R rows alone ----
-          {
-            const int dl = wave_shr1(ep, ep) - ep;
-            s = ldexp(1.0, min(max(dl, -1100), 220));
-          }
-          HB_FINE(5);
-          // (a taken branch costs a lone wave ~28 cycles, most of a row: tools/ubench/rowvar.hip, 35.5 cycles a row in a
-          // loop of 8 rows, 31.0 with the 48 rows of a block in line)
-          if (HB_LIKELY(R == 48)) {
-#pragma unroll
-            for (int u = 0; u < 48; u++) hb_row<C>(v, coef, s);
-          } else {
-            for (int r = 0; r < R; r += 8) {
-#pragma unroll
-              for (int u = 0; u < 8; u++) hb_row<C>(v, coef, s);
-            }
-          }
-          HB_FINE(6);
-        }
-#endif
         if (lane == 0) __hip_atomic_store(prog, 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (dbg) dbg[NB + 1] = HB_STAMP();
         if (lane == 0) {
@@ -766,7 +494,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
             double *dst = &rgv[(mb & (HB_FSLOTS - 1)) * SLOTV + sub * C];
 #pragma unroll
             for (int i = 0; i < C; i++) dst[i] = __longlong_as_double((long long)(bv[i] & ~HB_WRITTEN));
-            rge[(mb & (HB_FSLOTS - 1)) * MHL + sub] = (int)(be - HB_EOFF32 + HB_EB);
+            rge[(mb & (HB_FSLOTS - 1)) * MHL + sub] = (int)(be - HB_EOFF32 + HB_EOFF32);  // (the record's offset off, the spine's own -- the same -- on)
           }
           bb += k;
           lds_post(&c_posted[0], bb);
@@ -1009,12 +737,12 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
       double s[NG], z1 = 0.0;
 #pragma unroll
       for (int g = 0; g < NG; g++) {
-        const int dl = wave_shr1(ep[g], ep[g]) - ep[g];
-        s[g] = (lane == 0) ? 0.0 : ldexp(1.0, min(max(dl, -1100), 220));
+        const double sg = hb_left_scale(ep[g]);
+        s[g] = (lane == 0) ? 0.0 : sg;
       }
       if constexpr (NG == 2) {
         const int e63 = __builtin_amdgcn_readlane(ep[0], 63);
-        if (lane == 0) z1 = ldexp(1.0, min(max(e63 - ep[1], -1100), 220));
+        if (lane == 0) z1 = hb_left_scale(e63, ep[1]);
       }
       if constexpr (DOT != 0) {
         // ---- the tile as a sum: no logs but those of the cells that occur, nothing stored.  Of every group of eight
@@ -1052,7 +780,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
               v[0][0] = fma(coef[0][0], v[0][0], t0);
 #pragma unroll
               for (int i = 0; i < C; i++) coef[0][i] += 1.0;
-              if ((u & 1) == 0 && b0 != b1 && !(HB_DIAG & 32)) {  // (a group none of whose cells occurs is only walked)
+              if ((u & 1) == 0 && b0 != b1) {  // (a group none of whose cells occurs is only walked)
                 if constexpr (C == 4) {
                   *reinterpret_cast<hb_double2 *>(stage + (u >> 1) * WS + lane * 4) = hb_double2{v[0][0], v[0][1]};
                   *reinterpret_cast<hb_double2 *>(stage + (u >> 1) * WS + lane * 4 + 2) = hb_double2{v[0][2], v[0][3]};
@@ -1068,7 +796,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
                 }
               }
             }
-            if (b0 != b1 && !(HB_DIAG & 16)) {
+            if (b0 != b1) {
               unsigned kk = b0 + lane, pos = pp[q], cnt = cc[q];
               for (;;) {
                 if (kk < b1) {
@@ -1079,8 +807,8 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
                   double x = row[cw];
                   // (rows 1 and 3 of the group: n - 1 - m a times the cell above, plus the cell above and to the left
                   // -- under the left lane's exponent where that is another lane: the walk's own operations)
-                  const int dl = (ln > 0 ? se[ln - 1] : e) - e;
-                  const double xl = row[cw - 1 < 0 ? 0 : cw - 1] * (((cw % C) == 0) ? ldexp(1.0, min(max(dl, -1100), 220)) : 1.0);
+                  const int el = ln > 0 ? se[ln - 1] : e;
+                  const double xl = row[cw - 1 < 0 ? 0 : cw - 1] * (((cw % C) == 0) ? hb_left_scale(el, e) : 1.0);
                   const double c1 = fma(-(double)(mE0 + cw), a, (double)(1 + b * R + q * HB_DOT_GR + r));
                   if (r & 1) x = fma(c1, x, xl);
                   const double val = bfp_log(x, e, lt);
@@ -1183,7 +911,7 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
 #pragma unroll
             for (int q = 0; q < 8; q++) val[q] = x[q] / xl[q];
           } else {
-            hb_logs8<LTX>(x, ep8, lt, one_hi, val);
+            hb_logs8(x, ep8, lt, one_hi, val);
           }
 #pragma unroll
           for (int u = 0; u < RS; u++) {
@@ -1200,8 +928,6 @@ __global__ __launch_bounds__(64 * ((DOT != 0 && C >= 3) ? HB_NW_DOT4 : HB_NW), (
                   const double p1 = __hiloint2double(__float_as_int((float)val[u * C + 3]), __float_as_int((float)val[u * C + 2]));
                   if (own[0]) hb_store16(rpf, voff, p0, p1);
                 }
-              } else if constexpr ((HB_DIAG & 8) != 0) {
-                asm volatile("" ::"v"(val[u * C]), "v"(val[u * C + C - 1]));
               } else if constexpr (C == 1) {
                 if (own[0]) store_sbase(rp, voff, val[u]);
               } else if constexpr (C == 2) {
@@ -1284,13 +1010,12 @@ static hb_geom hb_geometry(unsigned N, unsigned M, int D, int sum_C = 0, bool vt
   // (halo: R columns -- a halo column k from the left is exact for k rows, so the own columns are through all R rows of
   // a block.  The V table divides an own cell by its left neighbour IN THE SAME ROW, which for a strip's first own
   // column is the last halo column: one lane more keeps that one exact in the block's last row too.)
-  g.HL = R / g.C + (vt ? 1 : 0);
-  if (g.HL > hb_mhl(g.C)) return g;
-  g.U = 64 - g.HL;
-  const int UC = g.U * g.C;
   const unsigned cmax = vt ? ((M < N) ? M : N) : ((M < N - 1) ? M : N - 1);  // columns 2..cmax hold stored cells: elements 0 .. cmax - 2
-  g.JW = (int)((cmax - 1 + UC - 1) / UC);
-  if (g.JW < 1) g.JW = 1;
+  const hb_strip sh = hb_strip_shape(N, cmax, g.C, R, vt ? 1 : 0);
+  g.HL = sh.HL;
+  if (g.HL > hb_mhl(g.C)) return g;
+  g.U = sh.U;
+  g.JW = sh.JW;
   // Strips per spine workgroup.  4 -- a spine wave per SIMD -- while the spine decides; once a storing fill's spine
   // workgroups would take more than 100 compute units, the tile workers decide (the spine is through long before
   // them), and 7 strips a workgroup -- 0.56 of the compute units for a spine a third slower -- serve them
@@ -1305,16 +1030,10 @@ static hb_geom hb_geometry(unsigned N, unsigned M, int D, int sum_C = 0, bool vt
     if (g.P < 1 || g.P > HB_PMAX) g.P = 4;
   }
   g.B = (g.JW + g.P - 1) / g.P;
-  g.NB = (int)((N - 1 + R - 1) / R);  // the state before block b is row 1 + b R
+  g.NB = sh.NB;
   if (g.JW >= 65535 || g.NB >= 65536) return g;
-  uint64_t nt = 0;
-  for (int j = 0; j < g.JW; j++) {
-    const int b0 = hb_first_block(j, UC, R);
-    if (b0 >= g.NB) return g;  // (cannot happen: column 2 + j U C <= N - 1)
-    nt += (uint64_t)(g.NB - b0);
-  }
-  if (nt >= (1ull << 31)) return g;
-  g.n_tiles = (unsigned)nt;
+  if (!sh.ok || sh.tiles >= (1ull << 31)) return g;
+  g.n_tiles = (unsigned)sh.tiles;
   g.n_rec = g.n_tiles + (unsigned)g.NB;
   size_t o = HB_HDR_BYTES;
   g.off_prog = o;
@@ -1362,15 +1081,10 @@ size_t stb_hb_workspace(unsigned N, unsigned M, int D) {
       int R = std::min(std::min(r0, Pc), (hb_mhl(c) - 1) * c) / 8 * 8;
       if (c == 3) R = R / 24 * 24;
       if (R < 8) continue;
-      const int HL = R / c + 1, U = 64 - HL, UC = U * c;  // (the V table's strips: a halo lane more, see hb_geometry)
-      const unsigned cmax = (M < N) ? M : N;  // (the V table's: one column more than the S table's)
-      const size_t JW = (cmax - 1 + UC - 1) / UC, NB = (N - 1 + R - 1) / R;
-      size_t nrec = NB;
-      for (size_t j = 0; j < JW; j++) {
-        const size_t b0 = (size_t)hb_first_block((int)j, UC, R);
-        nrec += (b0 < NB) ? NB - b0 : 0;
-      }
-      const size_t b = 1024 + HB_HDR_BYTES + (size_t)D * JW * 4 * HB_PROG_STRIDE + (size_t)D * nrec * U * (4 + 8 * c) + 1024;
+      // (the V table's strips: a halo lane more, see hb_geometry, and one column more than the S table's)
+      const hb_strip sh = hb_strip_shape(N, (M < N) ? M : N, c, R, 1);
+      const size_t nrec = (size_t)sh.NB + sh.tiles;
+      const size_t b = 1024 + HB_HDR_BYTES + (size_t)D * sh.JW * 4 * HB_PROG_STRIDE + (size_t)D * nrec * sh.U * (4 + 8 * c) + 1024;
       if (b > need) need = b;
     }
   return need + 256;
@@ -1418,14 +1132,10 @@ static int hb_order_list(const hb_geom &g, unsigned N, unsigned M, const unsigne
   std::vector<unsigned> buf((size_t)g.JW + 2);
   std::vector<item> v;
   v.reserve(g.n_tiles + (size_t)3 * split * g.JW);
-  unsigned off = 0;
-  buf[0] = off;  // strip index 0: the halo of strip 0, blocks 0 .. NB - 1
-  off += (unsigned)g.NB;
+  buf[0] = 0;  // strip index 0: the halo of strip 0, blocks 0 .. NB - 1
+  const unsigned off = buf[g.JW + 1] = hb_strip_starts(UC, g.R, g.JW, g.NB, (unsigned)g.NB, &buf[1]);
   for (int j = 0; j < g.JW; j++) {
-    const int b0 = hb_first_block(j, UC, g.R);
-    buf[j + 1] = off;
-    off += (unsigned)(g.NB - b0);
-    for (int b = b0; b < g.NB; b++) {
+    for (int b = hb_first_block(j, UC, g.R); b < g.NB; b++) {
       item it;
       it.key = (long)b * g.R * r_ns + (long)(j / g.P) * L_ns + (long)(j % g.P) * lag_ns;
       it.code = (unsigned)j | ((unsigned)b << 16);
@@ -1437,7 +1147,6 @@ static int hb_order_list(const hb_geom &g, unsigned N, unsigned M, const unsigne
         }
     }
   }
-  buf[g.JW + 1] = off;
   if (off != g.n_rec || (!split && v.size() != g.n_tiles)) return stb_fail("stb_fill_S: record count %u != %u", off, g.n_rec);
   std::stable_sort(v.begin(), v.end(), [](const item &x, const item &y) { return x.key < y.key; });
   buf.resize((size_t)g.JW + 2 + v.size());
@@ -1545,9 +1254,9 @@ int stb_launch_hb(fill_args &A, int D, char *ws, size_t ws_left, const dot_reque
   X.U = g.U;
   X.n_tiles = g.n_tiles;
   X.n_spine = (unsigned)g.B * (unsigned)D;
-  X.timeout = (unsigned long long)stb_env_int("STB_CHAIN_TIMEOUT_MS", 2000) * 100000ull;  // wall_clock64: 100 MHz
-  X.poll_nap = stb_env_int("STB_HB_POLL_NAP", 4);
-  if (X.poll_nap < 1) X.poll_nap = 1;
+  const hb_wait_settings wt = hb_wait_env();
+  X.timeout = wt.timeout;
+  X.poll_nap = wt.poll_nap;
   // a waiting worker sleeps this many x 512 cycles per block its tile is away: about half of what the spine takes
   // for a block (48 rows x 22 ns with 2 columns per lane, x 32-45 ns with 4), so that it looks again well before
   // the tile is due -- longer and it oversleeps (one table: 0.33 ms with 6 against 0.31 with 3; a table of 4000
@@ -1579,16 +1288,13 @@ int stb_launch_hb(fill_args &A, int D, char *ws, size_t ws_left, const dot_reque
   if (X.split < 0) X.split = 0;
   X.n_order = g.n_tiles;
   if (hb_order_list(g, N, M, &X.rec_off, &X.order, X.split, &X.n_order)) return 1;
-  const char *tl_file = getenv("STB_HB_TIMELINE");
 #ifdef HB_TL_FINE
   const size_t dbg_words = (size_t)g.JW * (g.NB + 2) + (size_t)X.n_order * 4 + (size_t)g.JW * g.NB * 8 + (size_t)g.JW * g.NB * 2;
 #else
   const size_t dbg_words = (size_t)g.JW * (g.NB + 2) + (size_t)X.n_order * 4;
 #endif
-  if (tl_file && *tl_file) {
-    HIPCHK(hipMalloc((void **)&X.dbg, dbg_words * 8));
-    HIPCHK(hipMemsetAsync(X.dbg, 0, dbg_words * 8, st));
-  }
+  hb_timeline tl;
+  if (tl.open(dbg_words, st, &X.dbg)) return 1;
   {
     const bool need_zero = !dot || dot->ws_zero < g.zero_bytes;
     const bool need_s1 = !(dot && dot->no_s1) && !(out_kind & 2);  // (the V table has no column 1)
@@ -1655,21 +1361,6 @@ int stb_launch_hb(fill_args &A, int D, char *ws, size_t ws_left, const dot_reque
     }
   }
   HIPCHK(hipGetLastError());
-  if (X.dbg) {
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<unsigned long long> h(dbg_words);
-    HIPCHK(hipMemcpy(h.data(), X.dbg, dbg_words * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(X.dbg);
-    FILE *f = fopen(tl_file, "wb");
-    if (f) {
-      const int hd[8] = {g.JW, g.NB, (int)X.n_order, g.C, g.P, g.R, g.U, D | (X.split << 16)};
-      fwrite(hd, sizeof(int), 8, f);
-      std::vector<unsigned> ord(X.n_order);
-      HIPCHK(hipMemcpy(ord.data(), X.order, (size_t)X.n_order * sizeof(unsigned), hipMemcpyDeviceToHost));
-      fwrite(ord.data(), sizeof(unsigned), X.n_order, f);
-      fwrite(h.data(), 8, dbg_words, f);
-      fclose(f);
-    }
-  }
-  return 0;
+  const int hd[8] = {g.JW, g.NB, (int)X.n_order, g.C, g.P, g.R, g.U, D | (X.split << 16)};
+  return tl.write(hd, X.order, X.n_order, st);
 }

@@ -26,16 +26,12 @@
 #include <mutex>
 #include <vector>
 
-#include "fill_chain.h"
+#include "hb_spine.h"
 
-#define GH_PMAX 7
 #define GH_NWMAX 8
 #define GH_MAXR 48            // rows of a block at most
 #define GH_SL 4               // ring of hand-overs between two spine waves of a workgroup (blocks)
 #define GH_FSL 4              // ring of hand-overs from the fetcher to spine wave 0
-#define GH_EOFF32 (1u << 30)
-#define GH_WRITTEN 0x8000000000000000ull
-#define GH_SPIN 48
 #define GH_MAXPH 16           // phases at most
 #define GH_JOB_MB 192          // room for the records of helper jobs
 #define GH_JOBS 1500           // jobs of a table at most
@@ -48,9 +44,6 @@
 // a listed cell's position: row in group << GH_PB(C) | element of the wave (64 C of them, halo included); a dense word is
 // position | count << (GH_PB(C) + 5)
 #define GH_PB(C) ((C) == 8 ? 9 : 8)
-#ifndef GH_NOSTORE
-#define GH_NOSTORE 0          // diagnostic build: 1 nothing is staged (results wrong)
-#endif
 
 struct gh_args {
   const double *a;             // [D] discounts
@@ -58,7 +51,7 @@ struct gh_args {
   unsigned *hdr;               // [1] error code, [2] error detail (shared by the phases)
   unsigned *ticket;            // this phase's role ticket
   unsigned long long *ck_v;    // [D][B][NB][HL * C] records: the rightmost HL lanes of a workgroup's last strip before a block
-  unsigned *ck_e;              // [D][B][NB][HL]     ... and their lane exponents + GH_EOFF32
+  unsigned *ck_e;              // [D][B][NB][HL]     ... and their lane exponents + HB_EOFF32
   double *state_v;             // [D][JW][64 * C]  a strip's significands between two phases
   int *state_e;                // [D][JW][64]      ... and lane exponents
   const unsigned *tile_off;    // [JW + 2], entry j + 1: tiles of the strips before strip j (a strip's tiles are its blocks from its first one on)
@@ -88,37 +81,6 @@ struct gh_args {
   unsigned long long *dbg;     // STB_HB_TIMELINE: table 0, [JW][NB + 2] (start, block starts, end)
 };
 
-typedef double gh_double2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void gh_store_wt16(unsigned long long *p, unsigned long long a, unsigned long long b) {
-  typedef unsigned long long gh_u64x2 __attribute__((ext_vector_type(2)));
-  const gh_u64x2 v2 = {a, b};
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v2) : "memory");
-}
-
-template <int C>
-__device__ __forceinline__ void gh_renorm(double (&v)[C], int &ep) {
-  double vmax = v[0];
-#pragma unroll
-  for (int i = 1; i < C; i++) vmax = fmax(vmax, v[i]);
-  const int sh = (vmax != 0.0) ? __builtin_amdgcn_frexp_exp(vmax) + PC_BIAS : 0;
-#pragma unroll
-  for (int i = 0; i < C; i++) v[i] = ldexp(v[i], -sh);
-  ep += sh;
-}
-
-template <int C>
-__device__ __forceinline__ void gh_row(double (&v)[C], double (&coef)[C], double s) {
-  const double t0 = wave_shr1_zero(v[C - 1]) * s;
-#pragma unroll
-  for (int i = C - 1; i >= 1; i--) v[i] = fma(coef[i], v[i], v[i - 1]);
-  v[0] = fma(coef[0], v[0], t0);
-#pragma unroll
-  for (int i = 0; i < C; i++) coef[i] += 1.0;
-}
-
-__host__ __device__ static inline int gh_first_block(int j, int UC, int R) { return (int)(((long long)j * UC) / R); }
-
 // One look-up pass: every lane with `valid` takes one listed cell of the group just walked.  Every K-th row of the
 // group is staged (rows 0, K, 2K, ..: row r at stage + (r / K) WS); a cell of a row in between is one to K - 1 steps
 // of the recurrence away from the staged row above it -- the very operations the walking wave itself performs for that
@@ -136,8 +98,7 @@ __device__ __forceinline__ void gh_lookup(bool valid, unsigned pos, unsigned cnt
     const int ln = cw / C;
     const int e = se[ln];
     // (what lives in the lane to the left is under that lane's exponent: the factor the walk uses)
-    const int dl = (ln > 0 ? se[ln - 1] : e) - e;
-    const double sfac = ldexp(1.0, min(max(dl, -1100), 220));
+    const double sfac = hb_left_scale(ln > 0 ? se[ln - 1] : e, e);
     const int ci = cw & (C - 1);  // the cell's place in its lane
     // coefficient n' - 1 - m' a of row n0 + 1 (n0: the staged row) at the cell's column m = mE0 + cw; a column to the
     // left adds a, a row down adds 1
@@ -185,13 +146,13 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
   constexpr int MHL = GH_MAXR / C;
   constexpr int SL = GH_SL, SLH = SL / 2, FSL = GH_FSL;
   __shared__ double2 lt[128];
-  __shared__ __attribute__((aligned(16))) double xv[GH_PMAX][SL][MHL * C];
-  __shared__ int xe[GH_PMAX][SL][MHL];
+  __shared__ __attribute__((aligned(16))) double xv[HB_PMAX][SL][MHL * C];
+  __shared__ int xe[HB_PMAX][SL][MHL];
   __shared__ __attribute__((aligned(16))) double fv[FSL][MHL * C];
   __shared__ int fe[FSL][MHL];
   __shared__ int posted[GH_NWMAX], taken[GH_NWMAX], fetched, s_abort, s_awake;
   __shared__ unsigned s_ticket;
-  __shared__ int w_se[GH_PMAX][64];
+  __shared__ int w_se[HB_PMAX][64];
   __shared__ unsigned s_jq[GH_JQ + 1];  // first job of every strip's queue
   extern __shared__ __attribute__((aligned(16))) double gh_dyn[];  // per spine wave SR staged rows
 
@@ -215,12 +176,12 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
   const int jw0 = j * P;
   if (tid < GH_NWMAX) {
     const int jw = jw0 + tid;
-    const int b0 = (jw < X.JWa) ? max(gh_first_block(jw, UC, R), bB) : bE;
+    const int b0 = (jw < X.JWa) ? max(hb_first_block(jw, UC, R), bB) : bE;
     posted[tid] = b0;
     taken[tid] = b0;
   }
   if (tid == 0) {
-    fetched = max(gh_first_block(jw0, UC, R), bB);
+    fetched = max(hb_first_block(jw0, UC, R), bB);
     s_abort = 0;
     s_awake = (j == 0) ? 1 : 0;
   }
@@ -233,19 +194,8 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
     const int jw = jw0 + w;
     if (jw >= X.JWa) return;
     bool aborted = false;
-    auto wait_ge = [&](const int *cnt, int need, unsigned code) {
-      if (aborted) return;
-      for (int k = 0; k < GH_SPIN; k++) {
-        if (lds_peek(cnt) >= need) {
-          asm volatile("" ::: "memory");
-          return;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (!chain_wait_slow(cnt, need, &s_abort, X.hdr, X.timeout, code, who, 1)) aborted = true;
-      asm volatile("" ::: "memory");
-    };
-    const int b00 = gh_first_block(jw, UC, R);  // the strip's own first block
+    auto wait_ge = [&](const int *cnt, int need, unsigned code) { hb_wait_ge(cnt, need, code, aborted, &s_abort, X.hdr, X.timeout, who); };
+    const int b00 = hb_first_block(jw, UC, R);  // the strip's own first block
     const int b0 = max(b00, bB);                // ... and its first one in this phase
     // what the group loop below works on: the strip's own wave, or (after the strip has ended) a tile of another strip, of
     // any table, taken as a job
@@ -284,10 +234,7 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
     // for a block ago; 0: none), whose first word is asked for during the last group and left in `wcur`.  `only_walk`:
     // the tile's cells are somebody else's (a helper's). ----
     auto block_rows = [&](int b, unsigned ti, unsigned &wcur, unsigned tin, size_t item_blk, bool only_walk) {
-      {
-        const int dl = wave_shr1(ep, ep) - ep;
-        s = ldexp(1.0, min(max(dl, -1100), 220));
-      }
+      s = hb_left_scale(ep);
       // (the coefficient n - 1 - m a of the next row, from its closed form at every block: + 1 a row drifts)
 #pragma unroll
       for (int i = 0; i < C; i++) coef[i] = (double)(1 + b * R) - (double)(m0 + i) * a;
@@ -310,11 +257,11 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
         if (listed && !(X.diag & 8)) {
 #pragma unroll
           for (int r = 0; r < G; r++) {
-            gh_row<C>(v, coef, s);
-            if ((r % K) == 0 && !GH_NOSTORE) {
+            hb_row<C>(v, coef, s);
+            if ((r % K) == 0) {
               double *dst = stage + (r / K) * WS + lane * C;
 #pragma unroll
-              for (int i = 0; i < C; i += 2) *reinterpret_cast<gh_double2 *>(dst + i) = gh_double2{v[i], v[i + 1]};
+              for (int i = 0; i < C; i += 2) *reinterpret_cast<hb_double2 *>(dst + i) = hb_double2{v[i], v[i + 1]};
             }
           }
           const int nrow0 = 2 + b * R + q * G;  // the row the group's first step produces
@@ -348,7 +295,7 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
         } else {
           // (a group none of whose cells occurs, or whose cells are a helper's, is only walked)
 #pragma unroll
-          for (int r = 0; r < G; r++) gh_row<C>(v, coef, s);
+          for (int r = 0; r < G; r++) hb_row<C>(v, coef, s);
         }
         wcur = wnext;
       }
@@ -415,7 +362,7 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
       const unsigned jd = X.jobs[GH_JBASE + job];
       const int jj = (int)(jd & 0xffffu), jb = (int)(jd >> 16);
       const size_t slot = (size_t)dd * n_jobs + job;
-      const unsigned tile = X.tile_off[jj + 1] + (unsigned)(jb - gh_first_block(jj, UC, R));
+      const unsigned tile = X.tile_off[jj + 1] + (unsigned)(jb - hb_first_block(jj, UC, R));
       unsigned ti = X.tinfo[tile];
       // the record: written a block after the tile's own wave walked past it
       {
@@ -510,9 +457,9 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
         unsigned long long *dst = rec_v + (size_t)b * (size_t)(HL * C);
 #pragma unroll
         for (int i = 0; i < C; i += 2)
-          gh_store_wt16(dst + i, (unsigned long long)__double_as_longlong(v[i]) | GH_WRITTEN,
-                        (unsigned long long)__double_as_longlong(v[i + 1]) | GH_WRITTEN);
-        __hip_atomic_store(rec_e + (size_t)b * (size_t)HL, (unsigned)ep + GH_EOFF32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          hb_store_wt16(dst + i, (unsigned long long)__double_as_longlong(v[i]) | HB_WRITTEN,
+                        (unsigned long long)__double_as_longlong(v[i + 1]) | HB_WRITTEN);
+        __hip_atomic_store(rec_e + (size_t)b * (size_t)HL, (unsigned)ep + HB_EOFF32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     };
     // (the first block's top before the wave dozes for its first halo: what a strip loses at its start it never makes up
@@ -525,7 +472,7 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
     __builtin_amdgcn_s_setprio(3);
     if (dbg) dbg[0] = wall_clock64();
     for (int b = b0; b < bE; b++) {
-      if (b > b00) gh_renorm<C>(v, ep);
+      if (b > b00) hb_renorm<C>(v, ep);
       if (b > b0 || !top_done) block_top(b);
       // ---- the halo: the left neighbour's rightmost HL lanes as they stand before the block ----
       if (jw > 0) {
@@ -570,7 +517,7 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
         unsigned long long *dst = reinterpret_cast<unsigned long long *>(X.jrec_v) + (slot * 64 + lane) * C;
 #pragma unroll
         for (int i = 0; i < C; i += 2)
-          gh_store_wt16(dst + i, (unsigned long long)__double_as_longlong(v[i]), (unsigned long long)__double_as_longlong(v[i + 1]));
+          hb_store_wt16(dst + i, (unsigned long long)__double_as_longlong(v[i]), (unsigned long long)__double_as_longlong(v[i + 1]));
         __hip_atomic_store(X.jrec_e + slot * 64 + lane, ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         pend = tj;
       }
@@ -604,7 +551,7 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
     const int grp = lane / gl, sub = lane % gl, ngrp = 64 / gl;
     const bool act = sub < HL;
     const size_t rec_left = ((size_t)d * X.B + (j - 1)) * (size_t)NB;
-    int bb = max(gh_first_block(jw0, UC, R), bB);  // blocks below it are delivered
+    int bb = max(hb_first_block(jw0, UC, R), bB);  // blocks below it are delivered
     bool woke = false;
     unsigned long long t_begin = 0;
     bool timing = false;
@@ -634,8 +581,8 @@ __global__ __launch_bounds__(64 * GH_NWMAX, (C == 8 ? GH_C8_WAVES : 2)) void k_g
         if (want && grp < k) {
           double *dst = &fv[mb & (FSL - 1)][sub * C];
 #pragma unroll
-          for (int i = 0; i < C; i++) dst[i] = __longlong_as_double((long long)(bv[i] & ~GH_WRITTEN));
-          fe[mb & (FSL - 1)][sub] = (int)(be - GH_EOFF32);
+          for (int i = 0; i < C; i++) dst[i] = __longlong_as_double((long long)(bv[i] & ~HB_WRITTEN));
+          fe[mb & (FSL - 1)][sub] = (int)(be - HB_EOFF32);
         }
         bb += k;
         lds_post(&fetched, bb);
@@ -693,8 +640,7 @@ int stb_grid_geometry(unsigned N, unsigned M, int D, grid_geom *out) {
   // 2 columns per lane -- the faster walk, 32 against 50 cycles a row -- while every strip of the batch gets a SIMD
   // to itself (one workgroup of 4 strips per compute unit); 4 beyond: 2.6 times fewer waves for the same columns
   {
-    const int HL2 = R / 2, U2 = 64 - HL2;
-    const uint64_t strips2 = (cmax - 1 + U2 * 2 - 1) / (U2 * 2);
+    const uint64_t strips2 = (uint64_t)hb_strip_shape(N, cmax, 2, R, 0).JW;
     const uint64_t wgs2 = (strips2 + 3) / 4 * (uint64_t)D;
     // ... 8 columns per lane (round 5; a strip is 58 own lanes = 464 columns, a table of 10^4 columns 22 strips) only when
     // asked for, STB_GRID_C=8 or a threshold of 4-column workgroups in STB_GRID_C8_WGS.  Built on the review's advice for
@@ -706,8 +652,7 @@ int stb_grid_geometry(unsigned N, unsigned M, int D, grid_geom *out) {
     // lane takes 62 ns against 41 -- strip 0 alone is 0.65 ms against 0.41 -- so what the wider strip saves in
     // instructions and residency it loses on every table's critical path.  The form is kept (tested in every strip
     // shape) for batches whose chain is not what bounds them.
-    const int HL4 = R / 4, U4 = 64 - HL4;
-    const uint64_t strips4 = (cmax - 1 + U4 * 4 - 1) / (U4 * 4);
+    const uint64_t strips4 = (uint64_t)hb_strip_shape(N, cmax, 4, R, 0).JW;
     const uint64_t wgs4 = (strips4 + 3) / 4 * (uint64_t)D;
     const int c8_from = stb_env_int("STB_GRID_C8_WGS", 0);  // 4-column workgroups from which the 8-column form takes over (0: never)
     g.C = stb_env_int("STB_GRID_C", wgs2 <= (uint64_t)cus ? 2 : ((c8_from > 0 && wgs4 > (uint64_t)c8_from && R % 8 == 0) ? 8 : 4));
@@ -715,18 +660,17 @@ int stb_grid_geometry(unsigned N, unsigned M, int D, grid_geom *out) {
     if (R % g.C != 0) return 1;
   }
   g.R = R;
-  g.HL = R / g.C;
-  g.U = 64 - g.HL;
-  const int UC = g.U * g.C;
-  g.JW = (int)((cmax - 1 + UC - 1) / UC);
-  if (g.JW < 1) g.JW = 1;
-  g.NB = (int)((N - 1 + R - 1) / R);
+  const hb_strip sh = hb_strip_shape(N, cmax, g.C, R, 0);
+  g.HL = sh.HL;
+  g.U = sh.U;
+  g.JW = sh.JW;
+  g.NB = sh.NB;
   if (g.JW >= 65535 || g.NB >= 65536) return 1;
   // strips per workgroup: 4, a walking wave per SIMD (MI355X, 64 discounts x 10^6 pairs, N = M = 10^4, groups of 12
   // rows, kernel ms: 3 strips 1.84, 4: 1.73, 5: 1.81, 6: 1.90, 7: 1.85)
   // (8 columns per lane: 3 -- a staged row is 4 KB; 512 workgroups of 4 waves for 64 tables of 10^4 columns, two a unit)
   g.P = stb_env_int("STB_GRID_P", g.C == 8 ? 3 : 4);
-  if (g.P < 1 || g.P > GH_PMAX) g.P = g.C == 8 ? 3 : 4;
+  if (g.P < 1 || g.P > HB_PMAX) g.P = g.C == 8 ? 3 : 4;
   g.B = (g.JW + g.P - 1) / g.P;
   // rows per group: a look-up pass costs the same for 1 or 64 listed cells (10^6 pairs over a 10^4 x 10^4 table: 1.6
   // a row in a strip of 80 columns, 4.2 in one of 208), and half of a group's rows are staged in LDS per walking wave
@@ -745,14 +689,8 @@ int stb_grid_geometry(unsigned N, unsigned M, int D, grid_geom *out) {
     g.G = Gd;
     g.NQ = R / Gd;
   }
-  uint64_t nt = 0;
-  for (int j = 0; j < g.JW; j++) {
-    const int b0 = gh_first_block(j, UC, R);
-    if (b0 >= g.NB) return 1;  // (cannot happen: column 2 + j U C <= N - 1)
-    nt += (uint64_t)(g.NB - b0);
-  }
-  if (nt * g.NQ >= (1ull << 31)) return 1;
-  g.n_tiles = (unsigned)nt;
+  if (!sh.ok || sh.tiles * g.NQ >= (1ull << 31)) return 1;
+  g.n_tiles = (unsigned)sh.tiles;
   // Phases.  One walking wave keeps a SIMD's vector issue busy and every strip of a table moves at the pace of the
   // slowest, while the strips right of the diagonal have nothing to do yet: with more strips than SIMDs the launch is
   // cut into phases of blocks, each launched with the strips the diagonal reaches before its end -- evenly spread
@@ -826,8 +764,8 @@ size_t stb_grid_workspace(unsigned N, unsigned M, int D) {
   const unsigned cmax = (M < N - 1) ? M : N - 1;
   for (int c : cs) {
     if (R % c != 0) continue;
-    const int HL = R / c, U = 64 - HL, UC = U * c;
-    const size_t JW = (cmax - 1 + UC - 1) / UC, NB = (N - 1 + R - 1) / R, B = (JW + (c == 8 ? 0 : 3)) / (c == 8 ? 1 : 4);
+    const hb_strip sh = hb_strip_shape(N, cmax, c, R, 0);
+    const size_t HL = (size_t)sh.HL, JW = (size_t)sh.JW, NB = (size_t)sh.NB, B = (JW + (c == 8 ? 0 : 3)) / (c == 8 ? 1 : 4);
     const size_t jobs = stb_grid_job_cap(c, D, (unsigned)(JW * NB), 1);  // (records and "written" words of the helper jobs)
     const size_t b = 4096 + 64 * (GH_MAXPH + GH_JQ) + (size_t)D * B * NB * HL * (4 + 8 * c) + (size_t)D * JW * 64 * (4 + 8 * c) + 2048 +
                      (size_t)D * jobs * (64 * (4 + 8 * c) + 4) + 1024;
@@ -839,13 +777,7 @@ size_t stb_grid_workspace(unsigned N, unsigned M, int D) {
 // first tile of every strip (entry j + 1; a strip's tiles are its blocks from its first one on), [JW + 2] words
 void stb_grid_tile_offsets(const grid_geom &g, std::vector<unsigned> &off) {
   off.assign((size_t)g.JW + 2, 0u);
-  const int UC = g.U * g.C;
-  unsigned o = 0;
-  for (int j = 0; j < g.JW; j++) {
-    off[j + 1] = o;
-    o += (unsigned)(g.NB - gh_first_block(j, UC, g.R));
-  }
-  off[0] = o;  // (the total, for whoever wants to check)
+  off[0] = hb_strip_starts(g.U * g.C, g.R, g.JW, g.NB, 0u, &off[1]);  // (the total, for whoever wants to check)
 }
 
 template <int C, int K>
@@ -902,9 +834,9 @@ int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_req
   X.R = g.R;
   X.HL = g.HL;
   X.U = g.U;
-  X.timeout = (unsigned long long)stb_env_int("STB_CHAIN_TIMEOUT_MS", 2000) * 100000ull;  // wall_clock64: 100 MHz
-  X.poll_nap = stb_env_int("STB_HB_POLL_NAP", 4);
-  if (X.poll_nap < 1) X.poll_nap = 1;
+  const hb_wait_settings wt = hb_wait_env();
+  X.timeout = wt.timeout;
+  X.poll_nap = wt.poll_nap;
   X.diag = stb_env_int("STB_GRID_DIAG", 0);
   if (dot->jobs && !dot->tjob) return stb_fail("stb_groups_aterms: a job list without the tiles' places in it");
   X.jobs = dot->jobs;
@@ -919,12 +851,8 @@ int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_req
   const_cast<dot_request *>(dot)->parts_per_table = g.JW;
   const_cast<dot_request *>(dot)->parts_extra_dev = X.jobs ? X.jobs + GH_JNUM : nullptr;
   if (dot->dotp_cap && (size_t)D * (size_t)(g.JW + (int)g.job_cap) * 2 > dot->dotp_cap) return stb_fail("stb_groups_aterms: partial-sum buffer too small");
-  const char *tl_file = getenv("STB_HB_TIMELINE");
-  const size_t dbg_words = (size_t)g.JW * (g.NB + 2);
-  if (tl_file && *tl_file) {
-    HIPCHK(hipMalloc((void **)&X.dbg, dbg_words * 8));
-    HIPCHK(hipMemsetAsync(X.dbg, 0, dbg_words * 8, st));
-  }
+  hb_timeline tl;
+  if (tl.open((size_t)g.JW * (g.NB + 2), st, &X.dbg)) return 1;
   if (stb_a_flush(A, pend, st)) return 1;
   if (!dot || dot->ws_zero < g.zero_bytes) HIPCHK(hipMemsetAsync(ws, 0, g.zero_bytes, st));
   if (dot) const_cast<dot_request *>(dot)->zero_bytes = g.zero_bytes;
@@ -935,7 +863,7 @@ int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_req
     X.b_end = (int)((int64_t)g.NB * (ph + 1) / g.phases);
     if (X.b_end <= X.b_begin) continue;
     int jwa = 0;
-    while (jwa < g.JW && gh_first_block(jwa, UC, g.R) < X.b_end) jwa++;
+    while (jwa < g.JW && hb_first_block(jwa, UC, g.R) < X.b_end) jwa++;
     X.JWa = jwa;
     X.ticket = X.hdr + 64 + 16 * ph;
     const unsigned grid = (unsigned)((jwa + g.P - 1) / g.P) * (unsigned)D;
@@ -945,18 +873,6 @@ int stb_launch_grid(fill_args &A, int D, char *ws, size_t ws_left, const dot_req
     if (rc) return 1;
   }
   HIPCHK(hipGetLastError());
-  if (X.dbg) {
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<unsigned long long> h(dbg_words);
-    HIPCHK(hipMemcpy(h.data(), X.dbg, dbg_words * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(X.dbg);
-    FILE *f = fopen(tl_file, "wb");
-    if (f) {
-      const int hd[8] = {g.JW, g.NB, 0, g.C, g.P, g.R, g.U, D};  // (the format of tools/timeline_hb.py, no tile part)
-      fwrite(hd, sizeof(int), 8, f);
-      fwrite(h.data(), 8, dbg_words, f);
-      fclose(f);
-    }
-  }
-  return 0;
+  const int hd[8] = {g.JW, g.NB, 0, g.C, g.P, g.R, g.U, D};  // (the format of tools/timeline_hb.py, no tile part)
+  return tl.write(hd, nullptr, 0, st);
 }

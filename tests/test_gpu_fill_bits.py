@@ -1,9 +1,10 @@
-"""The bytes a table fill and a fused evaluation leave, on every route of the fill's plan, against a recording of the
-commit before the plan (tests/golden/fill_bits.json, tools/record_fill_bits.py): the kernels did not change with it, so
-identical launch arguments give identical bytes, and this is the test that the launch arguments did not move.
+"""The bytes a table fill and a fused evaluation leave, on every route of the fill's plan and in every strip shape of the
+halo-block spine, against a recording of an earlier commit's library (tests/golden/fill_bits.json names it;
+tools/record_fill_bits.py): a refactor of the fill's plan or of the spine's kernels leaves every one of them as it was.
 
 Fill cases: a SHA-256 of the slab's stored cells (row padding left out) and of the S1 vectors where the fill writes
-them; each at the smallest bounds at which its route exists.  Fused cases: the doubles stb_groups_aterms returns for 2000
+them; each at the smallest bounds at which its route exists -- for the spine, at which a table has more than one spine
+workgroup, so that records travel between workgroups through the fetcher wave.  Fused cases: the doubles stb_groups_aterms returns for 2000
 synthetic pairs.  A fused case that the recorded commit itself did not reproduce from run to run is marked in the
 recording ("exact": false) and compared at the evaluations' usual 1e-10 instead."""
 import contextlib
@@ -38,6 +39,17 @@ FILLS = {
     "rows-log 100": ("S", 100, 100, 1, capi.FILL_LOGDOMAIN, {}, -1),
     "shared S 600": ("S", 600, 600, 1, capi.FILL_SCALED, {}, 1),
     "shared V 600": ("V", 600, 600, 1, None, {}, 1),
+    # the halo-block spine across workgroups (the fetcher at work): the smallest shapes with more than one spine workgroup a
+    # table, in every strip shape and output kind
+    "hb S C=4 P=2": ("S", 512, 512, 1, capi.FILL_SCALED, {"STB_HB_C": "4", "STB_HB_P": "2"}, -1),  # 3 strips, 2 workgroups
+    "hb Sf C=4 P=2": ("Sf", 512, 512, 1, None, {"STB_HB_C": "4", "STB_HB_P": "2"}, -1),  # the 16-byte float row
+    "hb V C=4 P=2": ("V", 512, 512, 1, None, {"STB_HB_C": "4", "STB_HB_P": "2"}, -1),  # the extra halo lane
+    "hb Vf C=4 P=2": ("Vf", 512, 512, 1, None, {"STB_HB_C": "4", "STB_HB_P": "2"}, -1),
+    "hb S C=1 rows=16 P=3": ("S", 512, 512, 1, capi.FILL_SCALED, {"STB_HB_C": "1", "STB_HB_ROWS": "16", "STB_HB_P": "3"}, -1),  # 11 strips, 4 workgroups
+    "hb S C=2 rows=24": ("S", 512, 512, 1, capi.FILL_SCALED, {"STB_HB_C": "2", "STB_HB_ROWS": "24"}, -1),  # blocks not 48 rows in line; 5 strips
+    "hb S C=2 P=7 700x700": ("S", 700, 700, 1, capi.FILL_SCALED, {"STB_HB_C": "2", "STB_HB_P": "7"}, -1),  # 9 strips, 2 workgroups of 7
+    "hb S split=0": ("S", 512, 512, 1, capi.FILL_SCALED, {"STB_HB_SPLIT": "0"}, -1),  # no quartered last tiles
+    "hb S 600x200 D=3 C=4 P=2": ("S", 600, 200, 3, capi.FILL_SCALED, {"STB_HB_C": "4", "STB_HB_P": "2"}, -1),
 }
 # name -> (bound N = M, D, environment, the form it takes: [fused, list layout -- 0 chain, 2 halo blocks, 3 and up grid])
 # (without STB_ATERMS_HB=0 an evaluation takes the halo-block sum at 300 rows too: the chain form's sum, which goes
@@ -49,6 +61,12 @@ FUSED = {
     "600 D=32 STB_ATERMS_GRID=1 (grid)": (600, 32, {"STB_ATERMS_GRID": "1"}, [1, 3]),
     "300 D=1 STB_ATERMS_HB=0 (stored tables)": (300, 1, {"STB_ATERMS_HB": "0"}, [0, 0]),
     "300 D=2 STB_ATERMS_HB=0 (chain sum)": (300, 2, {"STB_ATERMS_HB": "0"}, [1, 0]),
+    # more than one spine workgroup a table: the summing fill's and the grid walk's fetchers
+    "600 D=2 STB_HB_DOT_C=3": (600, 2, {"STB_HB_DOT_C": "3"}, [1, 2]),  # 5 strips, 2 workgroups
+    "600 D=2 STB_HB_DOT_C=4 STB_HB_DOT_P=2": (600, 2, {"STB_HB_DOT_C": "4", "STB_HB_DOT_P": "2"}, [1, 2]),
+    "600 D=32 grid C=4 P=2": (600, 32, {"STB_ATERMS_GRID": "1", "STB_GRID_C": "4", "STB_GRID_P": "2"}, [1, 4]),
+    "600 D=32 grid C=8 P=1": (600, 32, {"STB_ATERMS_GRID": "1", "STB_GRID_C": "8", "STB_GRID_P": "1"}, [1, 5]),
+    "600 D=32 grid C=4 jobs": (600, 32, {"STB_ATERMS_GRID": "1", "STB_GRID_C": "4", "STB_GRID_HELP_NW": "1"}, [1, 4]),  # (tests/hp_pairs.py's grid4jobs)
 }
 
 
