@@ -71,10 +71,14 @@
  *      the root; stb_tindic_sample_htree takes stb_tindic_sample_h's place (auxiliary tables upwards, the root, every
  *      level's concentration from a Gamma(1.1, 20) prior, then the rows downwards, one call); each iteration prints the
  *      concentrations, level 1's first.
+ *  22. with -X D the observations are real-valued: a PYP mixture of Gaussians with diagonal precisions in R^D
+ *      (stb_tindic_set_obs).  Data from a few well-separated centres, a random start, then dish sweep ->
+ *      stb_tindic_sample_gauss -> stb_tindic_sample_h -> stb_tindic_sampleb; every iteration prints the collapsed evidence
+ *      log p(x | z) (stb_tindic_gauss_logml), which rises from the random start.  The other flags but -J -n -c -s are ignored.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
- *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5] [-A 8] [-V 1000] [-T 8:2]
+ *                                                    [-g 64] [-G 2] [-s seed] [-d] [-j] [-L] [-z] [-w] [-P] [-B] [-H 4] [-C] [-K] [-S] [-Q 16] [-F 0.5] [-A 8] [-V 1000] [-T 8:2] [-X 2]
  */
 #include <math.h>
 #include <stdio.h>
@@ -94,12 +98,71 @@ static int cmp_double(const void *x, const void *y) {
   return a < b ? -1 : a > b;
 }
 
+/* -X D: a PYP mixture of Gaussians.  J restaurants x ncust customers; customer c carries x_c in R^D, drawn around one of
+ * XTRUE well-separated centres (its restaurant prefers some of them); the model has XDISHES dishes, every customer starts
+ * at a random one, and each iteration is dish sweep -> stb_tindic_sample_gauss -> stb_tindic_sample_h -> sampleb.  Prints
+ * the collapsed evidence log p(x | z) (stb_tindic_gauss_logml) every iteration; returns 1 if it did not rise. */
+#define XTRUE 4
+#define XDISHES 8
+static int gauss_mixture(int J, int ncust, int D, int cycles, long seed) {
+  const size_t C = (size_t)J * ncust, G = (size_t)J * XDISHES;
+  const double a = 0.1;
+  double b = 1.0, centre[XTRUE][STB_GS_MAXD], first = 0.0, last = 0.0;
+  double *x = malloc(sizeof(double) * C * D), *hf = malloc(sizeof(double) * G), *bvec = malloc(sizeof(double) * J);
+  scnt_int *nf = calloc(G, sizeof(*nf)), *cust = malloc(sizeof(*cust) * C);
+  stcnt_int *tf = calloc(G, sizeof(*tf));
+  int *K = malloc(sizeof(int) * J), j, d, it;
+  size_t c, g;
+  for (j = 0; j < XTRUE; j++)
+    for (d = 0; d < D; d++) centre[j][d] = 8.0 * ((j >> (d & 1)) & 1 ? 1.0 : -1.0) + (d > 1 ? 2.0 * j : 0.0);
+  for (c = 0; c < C; c++) {
+    const int rest = (int)(c / ncust), z = drand48() < 0.7 ? rest % XTRUE : (int)(drand48() * XTRUE) % XTRUE;
+    for (d = 0; d < D; d++) /* Box-Muller's cosine member */
+      x[c * D + d] = centre[z][d] + sqrt(-2.0 * log(1.0 - drand48())) * cos(6.283185307179586 * drand48());
+    cust[c] = (scnt_int)((int)(drand48() * XDISHES) % XDISHES); /* the random start */
+    nf[(size_t)rest * XDISHES + cust[c]]++;
+  }
+  for (g = 0; g < G; g++) {
+    tf[g] = nf[g] ? 1 : 0;
+    hf[g] = 1.0 / XDISHES;
+  }
+  for (j = 0; j < J; j++) K[j] = XDISHES, bvec[j] = b;
+  const stb_gauss_prior_t prior = {0.01, 1.0, 1.0, NULL, NULL};
+  stb_gauss_info_t gi;
+  stb_tindic_t *ti = stb_tindic_create(J, K, nf, tf, hf, cust, ncust > 65535 ? 65535 : 0, 0);
+  if (!ti || stb_tindic_set_obs(ti, x, (unsigned)D)) yaps_quit("the observations: %s\n", stb_last_error());
+  if (stb_tindic_sample_gauss(ti, &prior, (uint64_t)seed + 2, 0, &gi) || stb_tindic_gauss_logml(ti, &prior, &first))
+    yaps_quit("the first draw: %s\n", stb_last_error());
+  printf("Gaussian mixture: %d restaurants x %d customers in R^%d, %d centres, %d dishes; start: log p(x | z) = %.6f\n", J, ncust, D,
+         XTRUE, XDISHES, first);
+  for (it = 1; it <= cycles; it++) {
+    stb_tdish_info_t di;
+    double data = 0.0;
+    if (stb_tindic_sweep_dishes(ti, a, bvec, (uint64_t)seed, (uint64_t)it, 1, &di) ||
+        stb_tindic_sample_gauss(ti, &prior, (uint64_t)seed + 2, (uint64_t)it, &gi) ||
+        stb_tindic_sample_h(ti, NULL, 1.0, (uint64_t)seed + 3, (uint64_t)it))
+      yaps_quit("iteration %d: %s\n", it, stb_last_error());
+    b = stb_tindic_sampleb(ti, b, 1.1, 20.0, a, 0, 1, 0, (uint64_t)seed + 1, (uint64_t)it);
+    if (b != b) yaps_quit("stb_tindic_sampleb: %s\n", stb_last_error());
+    for (j = 0; j < J; j++) bvec[j] = b;
+    if (stb_tindic_gauss_logml(ti, &prior, &last) || stb_tindic_gauss_loglik(ti, &data))
+      yaps_quit("the evidence: %s\n", stb_last_error());
+    printf("iter %3d  b=%.4f  log p(x | z) = %.6f  log p(x | z, mu, tau) = %.6f  stuck %llu dead rows %llu\n", it, b, last, data,
+           (unsigned long long)di.stuck, (unsigned long long)gi.dead);
+  }
+  printf("evidence: %.6f -> %.6f (%s)\n", first, last, last > first ? "rose" : "DID NOT RISE");
+  stb_tindic_free(ti);
+  free(x), free(hf), free(bvec), free(nf), free(cust), free(tf), free(K);
+  return last > first ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
+  int xdim = 0;
   int J = 3, ncust = 2000, cycles = 60, grid = 0, nsets = 0, ondev = 0, joint = 0, showlj = 0, dishes = 0, redraw = 0, predict = 0, explicit_d = 0, pergroup = 0, hgroups = 0, collapsed = 0, drawconc = 0, seatdev = 0, seqpart = 0, filter = 0, vrows = 0, anneal = 0, tlevels = 0, tnodes[STB_HT_MAXL], c, j, i, it;
   double ftau = 0.0;
   double a0 = 0.5, b0 = 10.0, beta = 0.5, gam = 1.0;
   long seed = 12345;
-  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:V:A:T:")) >= 0) {
+  while ((c = getopt(argc, argv, "J:n:a:b:c:g:G:s:djLzwPBH:CKSQ:F:V:A:T:X:")) >= 0) {
     if (c == 'J') J = atoi(optarg);
     else if (c == 'n') ncust = atoi(optarg);
     else if (c == 'a') a0 = atof(optarg);
@@ -138,6 +201,7 @@ int main(int argc, char **argv) {
       if (tlevels == 0) tlevels = -1;
     }
     else if (c == 'V') vrows = atoi(optarg) >= 2 ? atoi(optarg) : -1;
+    else if (c == 'X') xdim = atoi(optarg) >= 1 && atoi(optarg) <= STB_GS_MAXD ? atoi(optarg) : -1;
     else return 2;
   }
   if (collapsed && !(explicit_d && dishes && redraw)) {
@@ -188,8 +252,13 @@ int main(int argc, char **argv) {
     fprintf(stderr, joint ? "pyp_resample: -B with -j is refused: the joint step models one shared b\n" : "pyp_resample: -B needs -d\n");
     return 2;
   }
+  if (xdim < 0) {
+    fprintf(stderr, "pyp_resample: -X D needs 1 <= D <= %d\n", STB_GS_MAXD);
+    return 2;
+  }
   srand48(seed);
   srand((unsigned)seed);
+  if (xdim) return gauss_mixture(J, ncust, xdim, cycles, seed); /* 22.: a mixture of Gaussians, nothing else of this file */
 
   /* ---- 1. data: seat customers, remember per (restaurant, dish) customers n and tables t ---- */
   scnt_int **n = malloc(sizeof(*n) * J), *N = calloc(J, sizeof(*N)), *T = calloc(J, sizeof(*T));

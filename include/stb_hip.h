@@ -1492,6 +1492,115 @@ int stb_tindic_generate(stb_tindic_t *s, double a, const double *bpar, uint64_t 
                         stb_seat_info_t *seat_info /* or NULL */, stb_classes_info_t *cls_info /* or NULL */);
 int stb_tindic_get_classes(stb_tindic_t *s, uint32_t *cls_out /* C */, unsigned *rows_out /* or NULL */);
 
+/* ---- Gaussian observations: a PYP mixture of Gaussians on the device (gauss.hip; additive) ----
+ * Every likelihood step above takes a customer's observation to be a class index.  Here customer c (flat index, as for
+ * cls) carries x_c in R^D, 1 <= D <= STB_GS_MAXD, and dish k (local pair k of every restaurant, stb_tindic_sample_h's
+ * convention; k < K <= STB_TD_MAXK) has a mean mu_k in R^D and a diagonal precision tau_k in R^D_+:
+ *     x_cd | z_c = k ~ N(mu_kd, 1 / tau_kd), independent over d;
+ *     tau_kd ~ Gamma(alpha0, rate beta0_d),  mu_kd | tau_kd ~ N(m0_d, 1 / (kappa0 tau_kd)), independent over (k, d).
+ * Given the n customers of dish k, their mean xbar and centred sum of squares Q, the posterior is Normal-Gamma with
+ *     kappa_n = kappa0 + n,  m_n = (kappa0 m0 + n xbar) / kappa_n,  alpha_n = alpha0 + n / 2,
+ *     beta_n = beta0 + Q / 2 + kappa0 n (xbar - m0)^2 / (2 kappa_n).
+ * The dish sweep needs no change: k_tdish reads L_k = lik[cls[c] * stride + k], it is exact because the matrix is a fixed
+ * table while it runs, and multiplying a row by a positive constant changes no choice.  With one row per customer
+ * (cls[c] = c, rows = C) a matrix of Gaussian densities makes the dish sweep the assignment step of the mixture, and
+ * alternating it with the redraw of (mu, tau) is Gibbs sampling on (seating, mu, tau).  The matrix
+ * takes 8 C stride bytes.
+ *
+ * Everything is FP64 without contraction; x is C x D, mu, tau, mean and Q are K x D, all row-major; no bit depends on
+ * launch geometry (STB_GAUSS_WAVES = 1, 2, 4 or 8 waves a workgroup).  tests/gs_oracle.py replays every operation below.
+ *
+ * Sums over the customers of a dish (S and Q, nothing else): customers in chunks of 256 by flat index (chunk j =
+ * customers 256 j .. 256 j + 255); inside a chunk the members of dish k are added one after another in customer order,
+ * starting from the chunk's first member; non-members add nothing and a chunk without members is skipped; the chunk
+ * partials are combined in chunk order in double-double (TwoSum on the high word, the error into the low: dd_add,
+ * libstb_amd/csrc/stb_common.h, as stb_dirmult_logml's chunk sums) starting from (0, 0); the result is hi + lo.
+ * stb_gauss_stats, two passes: A -- n_k as an integer count, S_kd = sum x_cd, mean_kd = S_kd / (double)n_k; B --
+ * Q_kd = sum (x_cd - mean_kd) * (x_cd - mean_kd).  n_k = 0: mean and Q are +0.0.  A customer with cust[c] >= K counts in
+ * info.skipped and belongs to no dish.  (The one-pass form sum x^2 - n xbar^2 cancels: tests/test_gauss_host.py shows it
+ * many bars out where the two passes are inside theirs.)  The outputs need no initialisation.  Scratch from the buffer
+ * cache: 8 D K + 4 K bytes per chunk.  Four launches, one wait.
+ * stb_sample_gauss: key = mix(seed + (sweep+1) gamma), the constant and mix of stb_sample_lik; cell e = k * D + d owns
+ * key_e = mix(key + (e+1) gamma).  With n = (double)n_k, dm = mean - m0_d (m0 NULL: 0.0; beta0 NULL: beta00 for every d):
+ *     kappa_n = kappa0 + n;  m_n = (kappa0 * m0_d + n * mean) / kappa_n;  alpha_n = alpha0 + 0.5 * n;
+ *     beta_n = (beta0_d + 0.5 * Q) + 0.5 * (((kappa0 * n) / kappa_n) * (dm * dm));
+ * n_k = 0: the prior's values, nothing evaluated.  lg = log of a Gamma(alpha_n) variate from key_e by stb_sample_lik's
+ * recipe unchanged (gamma_dev.h); lt = lg - log(beta_n); tau = exp(lt); the next two uniforms of the same substream are
+ * u1, u2; z = sqrt(-2 log u1) * cos(6.283185307179586 * u2); mu = m_n + z / sqrt(kappa_n * tau).  A rejection loop that
+ * runs out, or a tau that is not positive and finite, fails the call after its wait; mu and tau are then undefined.
+ * One launch, one wait.
+ * stb_gauss_lik: H_k = sum_d 0.5 * log(tau_kd) and q_ck = sum_d ((x_cd - mu_kd) * (x_cd - mu_kd)) * tau_kd, both added one
+ * after another in d order starting from the d = 0 term; l_ck = H_k - 0.5 * q_ck; m_c = max over k < K of l_ck;
+ * lik[c * stride + k] = exp(l_ck - m_c) for k < K and 0.0 for K <= k < stride (stride >= K): every row holds an exact
+ * 1.0.  A row whose m_c is not finite is written as zeros and counted in info.dead; the dish sweep reports its customer as
+ * stuck.  Two launches, one wait.
+ * stb_gauss_loglik: the data term log p(x | z, mu, tau).  v_c = l_{c, cust[c]}, recomputed as above; a customer with
+ * cust[c] >= K adds 0.0 and counts in info.skipped.  Customers 256 b .. 256 b + 255 (0.0 beyond C) are block b, summed by
+ * stb_logjoint's block tree: (v[l] + v[l + 64]) + (v[l + 128] + v[l + 192]) per lane l, then v += shfl_down(v, o),
+ * o = 32, 16, .. 1; the block sums are added in order in double-double, and the total is
+ * (hi + lo) + (double)(C * D) * (-0.9189385332046727).  C = 0 gives that constant's 0.  -inf or finite, never a NaN, for
+ * finite x, mu and positive finite tau.  The answer arrives through pinned memory: two launches, one wait.
+ * stb_gauss_logml: the collapsed evidence log p(x | z), mu and tau summed out.  Cell e = k * D + d with n_k > 0 is
+ *     lgamma(alpha_n) - lgamma(alpha0) + alpha0 * log(beta0_d) - alpha_n * log(beta_n)
+ *         + 0.5 * (log(kappa0) - log(kappa_n)) - (0.5 * n) * 1.8378770664093453
+ * evaluated left to right (the posterior's values as in the draw); a cell with n_k = 0 is exactly 0.0.  The K * D cells
+ * are summed in blocks of 256 by the same tree and the block sums in order in double-double: hi + lo.  One launch, one
+ * wait.
+ * Refused before anything is queued, with stb_last_error() set: a null array that would be read or written, D outside
+ * 1 .. STB_GS_MAXD, K outside 1 .. STB_TD_MAXK, stride < K, for stb_gauss_stats C above 2^32 - 1 (n_k is a uint32); a prior whose kappa0, alpha0 or a beta0 is not positive and
+ * finite, or with an m0 that is not finite.  info may be NULL; the member a call does not count is 0. */
+#define STB_GS_MAXD 64
+typedef struct stb_gauss_prior {
+  double kappa0, alpha0, beta00;
+  const double *m0;    /* host, D, NULL: 0 */
+  const double *beta0; /* host, D, NULL: beta00 */
+} stb_gauss_prior_t;
+typedef struct stb_gauss_info { uint64_t skipped, dead; } stb_gauss_info_t;
+int stb_gauss_stats(const double *d_x, unsigned D, const uint32_t *d_cust, uint64_t C, unsigned K, uint32_t *d_n,
+                    double *d_mean, double *d_Q, stb_gauss_info_t *info /* or NULL */, void *stream);
+int stb_sample_gauss(const uint32_t *d_n, const double *d_mean, const double *d_Q, unsigned K, unsigned D,
+                     const stb_gauss_prior_t *prior, uint64_t seed, uint64_t sweep, double *d_mu, double *d_tau, void *stream);
+int stb_gauss_lik(const double *d_x, unsigned D, uint64_t C, const double *d_mu, const double *d_tau, unsigned K,
+                  double *d_lik, unsigned stride, stb_gauss_info_t *info /* or NULL */, void *stream);
+int stb_gauss_loglik(const double *d_x, unsigned D, const uint32_t *d_cust, uint64_t C, const double *d_mu,
+                     const double *d_tau, unsigned K, double *total_host, stb_gauss_info_t *info /* or NULL */, void *stream);
+int stb_gauss_logml(const uint32_t *d_n, const double *d_mean, const double *d_Q, unsigned K, unsigned D,
+                    const stb_gauss_prior_t *prior, double *total_host, void *stream);
+/* Object layer: an stb_tindic_t in observation mode.  K = the largest K_i, which every restaurant must have; the calls queue
+ * on the object's stream behind its sweeps.
+ *   stb_tindic_set_obs      x_host is C x D.  Refused: a non-finite x, D outside 1 .. STB_GS_MAXD, K outside 1 .. STB_TD_MAXK,
+ *                           restaurants whose K_i are not all equal, no customers.  Puts x on the device, sets the classes to
+ *                           the identity with rows = C, makes a C x K matrix of ones (8 C K bytes) and materialises cust as
+ *                           the first dish sweep does.  The object is then in observation mode, without parameters.
+ *                           stb_tindic_set_obs(s, NULL, 0) removes the observations and leaves the object with neither
+ *                           classes nor a matrix.  A later stb_tindic_set_classes or _set_lik by the caller ends the mode too
+ *                           (and keeps what the other of the two holds).
+ *   stb_tindic_set_gauss    mu and tau from host K x D arrays (mu finite, tau positive and finite), and the matrix rewritten
+ *                           from them (stb_gauss_lik).  stb_tindic_get_gauss returns them.
+ *   stb_tindic_sample_gauss stb_gauss_stats on (x, cust), stb_sample_gauss, stb_gauss_lik into the object's matrix: the raw
+ *                           calls' launches in their order, bit for bit, with one wait; nothing per customer or dish crosses
+ *                           to the host, and n, t, T, cust and h are not written.  A draw that fails after its wait leaves
+ *                           the parameters and the matrix undefined: dish sweeps (and _get_gauss, _gauss_loglik) are refused
+ *                           until a _sample_gauss or _set_gauss that succeeds.
+ *   stb_tindic_gauss_loglik the data term under the object's parameters; with stb_tindic_logjoint's total it is the
+ *                           complete-data log joint.  stb_tindic_gauss_logml: statistics, then the evidence: the figure to
+ *                           watch a chain by (it needs no parameters).
+ * In observation mode these work as they stand: stb_tindic_sweep_dishes, _sweep and _seat (they read the matrix row
+ * cls[c] = c, and a row's scale changes no choice -- but stb_tindic_seat's total, a log weight, carries every row's own
+ * scale and means nothing there: pass NULL); every h, b, a and joint step; stb_tindic_logjoint, _predict (it reads no
+ * matrix), _logjoint_collapsed without STB_CJ_DATA; the get_* calls, stb_tindic_lik_device, _set_heldout, _heldout_reset and
+ * _heldout_get.  These are refused, the state untouched and stb_last_error() set, because they read rows as classes or
+ * depend on a row's scale: stb_tindic_sample_lik, _loglik, _class_counts, _sample_beta, _logjoint_collapsed with
+ * STB_CJ_DATA, _sample_classes, _generate, _heldout, _heldout_seq, _heldout_pf, _heldout_ais.  Outside observation mode no
+ * call changes in any way. */
+int stb_tindic_set_obs(stb_tindic_t *s, const double *x_host /* C x D, or NULL */, unsigned D);
+int stb_tindic_set_gauss(stb_tindic_t *s, const double *mu, const double *tau);
+int stb_tindic_get_gauss(stb_tindic_t *s, double *mu_out, double *tau_out);
+int stb_tindic_sample_gauss(stb_tindic_t *s, const stb_gauss_prior_t *prior, uint64_t seed, uint64_t sweep,
+                            stb_gauss_info_t *info /* or NULL */);
+int stb_tindic_gauss_loglik(stb_tindic_t *s, double *total);
+int stb_tindic_gauss_logml(stb_tindic_t *s, const stb_gauss_prior_t *prior, double *total);
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

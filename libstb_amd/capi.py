@@ -90,6 +90,18 @@ class ClassesInfo(C.Structure):
     _fields_ = [("skipped", C.c_uint64), ("stuck", C.c_uint64), ("drawn", C.c_uint64)]
 
 
+class GaussPrior(C.Structure):
+    """stb_gauss_prior_t (include/stb_hip.h)"""
+    _fields_ = [("kappa0", C.c_double), ("alpha0", C.c_double), ("beta00", C.c_double),
+                ("m0", C.POINTER(C.c_double)), ("beta0", C.POINTER(C.c_double))]
+
+
+class GaussInfo(C.Structure):
+    """stb_gauss_info_t (include/stb_hip.h)"""
+    _fields_ = [("skipped", C.c_uint64), ("dead", C.c_uint64)]
+
+
+GS_MAXD = 64  # STB_GS_MAXD
 PF_MAXR = 64  # STB_PF_MAXR: the slots of stb_seat_filter, a slot a lane
 
 
@@ -433,6 +445,19 @@ def lib() -> C.CDLL:
     sig("stb_tindic_sample_classes", i, [vp, vp, u64, u64, cli])
     sig("stb_tindic_generate", i, [vp, d, c_double_p, u64, u64, sti, cli])
     sig("stb_tindic_get_classes", i, [vp, c_u32_p, C.POINTER(u)])
+    # ---- Gaussian observations
+    gsp, gsi = C.POINTER(GaussPrior), C.POINTER(GaussInfo)
+    sig("stb_gauss_stats", i, [vp, u, vp, u64, u, vp, vp, vp, gsi, vp])
+    sig("stb_sample_gauss", i, [vp, vp, vp, u, u, gsp, u64, u64, vp, vp, vp])
+    sig("stb_gauss_lik", i, [vp, u, u64, vp, vp, u, vp, u, gsi, vp])
+    sig("stb_gauss_loglik", i, [vp, u, vp, u64, vp, vp, u, c_double_p, gsi, vp])
+    sig("stb_gauss_logml", i, [vp, vp, vp, u, u, gsp, c_double_p, vp])
+    sig("stb_tindic_set_obs", i, [vp, c_double_p, u])
+    sig("stb_tindic_set_gauss", i, [vp, c_double_p, c_double_p])
+    sig("stb_tindic_get_gauss", i, [vp, c_double_p, c_double_p])
+    sig("stb_tindic_sample_gauss", i, [vp, gsp, u64, u64, gsi])
+    sig("stb_tindic_gauss_loglik", i, [vp, c_double_p])
+    sig("stb_tindic_gauss_logml", i, [vp, gsp, c_double_p])
     # (private entry points: the customers per restaurant as d_N or as d_coff prefix sums, for tests)
     sig("stb_hq_logq", i, [d, d, i, vp, vp, vp, c_double_p, u64, u64, vp])
     sig("stb_hj_joint_terms", i, [c_double_p, i, c_double_p, i, vp, vp, vp, u64, vp, vp])
@@ -1276,6 +1301,81 @@ def lik_loglik(cnt, lik, stream=None):
     return tot.value, imp.value
 
 
+def gauss_prior(kappa0, alpha0, beta0, m0=None, D: int = 0):
+    """(a GaussPrior, what keeps its vectors alive): beta0 a scalar or D values, m0 None (zeros) or D values"""
+    keep = []
+    p = GaussPrior(float(kappa0), float(alpha0), 0.0, None, None)
+    if np.ndim(beta0) == 0:
+        p.beta00 = float(beta0)
+    else:
+        keep.append(np.ascontiguousarray(beta0, dtype=np.float64))
+        p.beta0 = dp(keep[-1])
+    if m0 is not None:
+        keep.append(np.ascontiguousarray(m0, dtype=np.float64))
+        p.m0 = dp(keep[-1])
+    for v in keep:
+        if D and v.shape != (D,):
+            raise StbError(f"expected a scalar or {D} values, got shape {v.shape}")
+    return p, keep
+
+
+def gauss_stats(x, cust, K: int, out=None, stream=None):
+    """stb_gauss_stats on device tensors x float64 (C, D) and cust int32 holding uint32 dishes (C): (n int32 (K), mean
+    float64 (K, D), Q float64 (K, D), GaussInfo); out: (n, mean, Q) to write into"""
+    torch = _torch()
+    Cn, D = int(x.shape[0]), int(x.shape[1])
+    if out is None:
+        out = (torch.empty(K, dtype=torch.int32, device=x.device), torch.empty((K, D), dtype=torch.float64, device=x.device),
+               torch.empty((K, D), dtype=torch.float64, device=x.device))
+    n, mean, Q = out
+    info = GaussInfo()
+    check(lib().stb_gauss_stats(x.data_ptr(), D, cust.data_ptr(), Cn, K, n.data_ptr(), mean.data_ptr(), Q.data_ptr(),
+                                C.byref(info), stream_ptr(stream)))
+    return n, mean, Q, info
+
+
+def sample_gauss(n, mean, Q, prior, seed: int, sweep: int, stream=None):
+    """stb_sample_gauss on the statistics of gauss_stats: (mu, tau), float64 device tensors (K, D); prior a GaussPrior (or
+    the pair gauss_prior returns)"""
+    torch = _torch()
+    K, D = int(mean.shape[0]), int(mean.shape[1])
+    p = prior[0] if isinstance(prior, tuple) else prior
+    mu, tau = torch.empty_like(mean), torch.empty_like(mean)
+    check(lib().stb_sample_gauss(n.data_ptr(), mean.data_ptr(), Q.data_ptr(), K, D, C.byref(p), seed, sweep, mu.data_ptr(),
+                                 tau.data_ptr(), stream_ptr(stream)))
+    return mu, tau
+
+
+def gauss_lik(x, mu, tau, stride: int = 0, out=None, stream=None):
+    """stb_gauss_lik: the (C, stride) matrix exp(l_ck - max_k l_ck) of the Gaussian densities (stride = 0: K), and GaussInfo"""
+    torch = _torch()
+    Cn, D, K = int(x.shape[0]), int(x.shape[1]), int(mu.shape[0])
+    stride = int(stride) if stride else K
+    lik = torch.empty((Cn, stride), dtype=torch.float64, device=x.device) if out is None else out
+    info = GaussInfo()
+    check(lib().stb_gauss_lik(x.data_ptr(), D, Cn, mu.data_ptr(), tau.data_ptr(), K, lik.data_ptr(), stride, C.byref(info),
+                              stream_ptr(stream)))
+    return lik, info
+
+
+def gauss_loglik(x, cust, mu, tau, stream=None):
+    """stb_gauss_loglik: (log p(x | z, mu, tau), GaussInfo)"""
+    Cn, D, K = int(x.shape[0]), int(x.shape[1]), int(mu.shape[0])
+    tot, info = C.c_double(0.0), GaussInfo()
+    check(lib().stb_gauss_loglik(x.data_ptr(), D, cust.data_ptr(), Cn, mu.data_ptr(), tau.data_ptr(), K, C.byref(tot),
+                                 C.byref(info), stream_ptr(stream)))
+    return tot.value, info
+
+
+def gauss_logml(n, mean, Q, prior, stream=None):
+    """stb_gauss_logml: the collapsed evidence log p(x | z) from the statistics of gauss_stats"""
+    K, D = int(mean.shape[0]), int(mean.shape[1])
+    p = prior[0] if isinstance(prior, tuple) else prior
+    tot = C.c_double(0.0)
+    check(lib().stb_gauss_logml(n.data_ptr(), mean.data_ptr(), Q.data_ptr(), K, D, C.byref(p), C.byref(tot), stream_ptr(stream)))
+    return tot.value
+
+
 def dirmult_logml(cnt, w, orientation: int = DM_ROWS, cols: int = 0, scale=1.0, want_each: bool = True, stream=None):
     """stb_dirmult_logml on a device tensor cnt (int32 holding uint32 counts, (rows, stride); cols = 0: stride columns):
     the log marginal of its rows (DM_ROWS) or columns (DM_COLUMNS) as multinomials under a Dirichlet prior.  w: a float64
@@ -1868,6 +1968,56 @@ class TableIndicators(_BGroupsMixin):
         rows = C.c_uint(0)
         check(self.L.stb_tindic_get_classes(self.h, cls.ctypes.data_as(c_u32_p) if self.C else None, C.byref(rows)))
         return cls, rows.value
+
+    # ---- Gaussian observations (stb_tindic_set_obs and what follows it in include/stb_hip.h)
+
+    def set_obs(self, x=None):
+        """x (C, D) float64: the object goes into observation mode (identity classes, a C x K matrix of ones); None: the
+        observations, the classes and the matrix go"""
+        if x is None:
+            check(self.L.stb_tindic_set_obs(self.h, None, 0))
+            self.obs_D = self.rows = self.stride = 0
+            return
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[0] != self.C:
+            raise StbError(f"set_obs: x has shape {x.shape}; the object has {self.C} customers")
+        check(self.L.stb_tindic_set_obs(self.h, dp(x), int(x.shape[1])))
+        self.obs_D = int(x.shape[1])
+        self.rows, self.stride = self.C, self.maxK      # (the identity classes and the C x K matrix)
+
+    def set_gauss(self, mu, tau):
+        """the dishes' means and precisions (K, D), and the matrix rewritten from them"""
+        mu, tau = np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(tau, dtype=np.float64)
+        shape = (self.maxK, getattr(self, "obs_D", 0))
+        if shape[1] and (mu.shape != shape or tau.shape != shape):
+            raise StbError(f"set_gauss: mu {mu.shape}, tau {tau.shape}; expected {shape}")
+        check(self.L.stb_tindic_set_gauss(self.h, dp(mu), dp(tau)))
+
+    def get_gauss(self):
+        """(mu, tau), each (K, D), after the queued work"""
+        D = getattr(self, "obs_D", 0)
+        mu, tau = np.zeros((self.maxK, max(D, 1))), np.zeros((self.maxK, max(D, 1)))
+        check(self.L.stb_tindic_get_gauss(self.h, dp(mu), dp(tau)))
+        return mu, tau
+
+    def sample_gauss(self, prior, seed: int, sweep: int):
+        """statistics, the draw of (mu, tau) and the matrix in one call (stb_tindic_sample_gauss); prior a GaussPrior or the
+        pair gauss_prior returns.  Returns GaussInfo"""
+        p = prior[0] if isinstance(prior, tuple) else prior
+        info = GaussInfo()
+        check(self.L.stb_tindic_sample_gauss(self.h, C.byref(p), seed, sweep, C.byref(info)))
+        return info
+
+    def gauss_loglik(self):
+        tot = C.c_double(0.0)
+        check(self.L.stb_tindic_gauss_loglik(self.h, C.byref(tot)))
+        return tot.value
+
+    def gauss_logml(self, prior):
+        p = prior[0] if isinstance(prior, tuple) else prior
+        tot = C.c_double(0.0)
+        check(self.L.stb_tindic_gauss_logml(self.h, C.byref(p), C.byref(tot)))
+        return tot.value
 
     def heldout_seq(self, a, bpar, particles: int, seed: int, sweep: int, want_Hi: bool = True):
         """(total, H_i[I] or None, SeatInfo): the held-out customers seated one after another on a private copy of every

@@ -25,6 +25,7 @@
 #include "dirmult.h"
 #include "dirconc.h"
 #include "classgen.h"
+#include "gauss.h"
 
 // ------------------------------------------------------------------------------------------------
 // the object: pairs, totals, weights, customer order, its own V table for the current discount, its own stream
@@ -45,7 +46,14 @@ struct stb_tindic {
   unsigned cls_rows;
   double *d_lik;        // [lik_rows x lik_stride] (null: every L is 1)
   unsigned lik_rows, lik_stride;
-  bool lik_bad, h_bad;  // a draw of stb_tindic_sample_lik / _sample_h failed: the matrix / h is undefined, dish sweeps are refused
+  bool lik_bad, h_bad;  // a draw of stb_tindic_sample_lik / _sample_gauss / _sample_h failed: the matrix / h is undefined, dish sweeps are refused
+  // Gaussian observations (gauss.hip).  d_x set: observation mode -- the classes are the identity, the matrix has a row per
+  // customer and is written by the object from (mu, tau)
+  double *d_x;          // [C x obs_D] (null: none)
+  unsigned obs_D;
+  double *d_gpar;       // mu, tau [maxK x obs_D each], then the statistics' mean and Q [maxK x obs_D each]
+  uint32_t *d_gn;       // [maxK] the statistics' counts
+  bool g_have;          // mu and tau hold values (stb_tindic_set_gauss, or a stb_tindic_sample_gauss that succeeded)
   unsigned long long *d_info, *h_info;  // {skipped, stuck} on the device, and pinned
   void *d_cgs;          // the class draw's scratch (classgen.hip), from the buffer cache: kept while the matrix keeps its shape
   size_t cgs_bytes;
@@ -113,6 +121,24 @@ static int ti_check_bpar(stb_tindic_t *s, double a, const double *bpar, const ch
   for (int i = 0; i < s->I; i++)
     if (!(bpar[i] > -a) || !std::isfinite(bpar[i])) return stb_fail("%s: bpar[%d]=%g (must be > -a = %g)", who, i, bpar[i], -a);
   return 0;
+}
+
+// the refusal of a call that reads the matrix's rows as classes, or depends on a row's scale, in observation mode
+static int ti_not_obs(const stb_tindic_t *s, const char *who) {
+  if (!s->d_x) return 0;
+  return stb_fail("%s: the object holds Gaussian observations (stb_tindic_set_obs): its matrix has one row per customer, each "
+                  "scaled by its own maximum, and its classes are the customers' indices", who);
+}
+
+// the observations and what goes with them, freed (the caller has waited for whatever reads them)
+static void ti_drop_obs(stb_tindic_t *s) {
+  void *dev[] = {s->d_x, s->d_gpar, s->d_gn};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  s->d_x = s->d_gpar = nullptr;
+  s->d_gn = nullptr;
+  s->obs_D = 0;
+  s->g_have = false;
 }
 
 namespace {  // (the helper types are this file's own: no symbols of theirs leave it)
@@ -188,6 +214,7 @@ static void ti_release(stb_tindic_t *s) {
   stb_hb_obj_release(&s->hb);
   ti_drop_sslab(s);
   ti_drop_cgs(s);
+  ti_drop_obs(s);
   void *dev[] = {s->d_koff, s->d_coff, s->d_n, s->d_T, s->d_cust, s->d_t, s->d_h, s->d_bpar, s->d_vt, s->d_ws,
                  s->d_cls, s->d_lik, s->d_info, s->d_hoff, s->d_hcls, s->d_pacc, s->d_hgoff, s->d_hroot, s->d_cginfo,
                  s->d_avt, s->d_aws};
@@ -565,6 +592,7 @@ extern "C" int stb_tindic_set_classes(stb_tindic_t *s, const uint32_t *cls_host,
   stb_device_scope dev(s->dev);
   if (hipStreamSynchronize(s->st) != hipSuccess) return STB_STREAM_FAIL(who);
   if (!cls_host) {
+    ti_drop_obs(s);  // (nothing below can fail: the observation mode ends with its classes)
     if (s->d_cls) (void)hipFree(s->d_cls);
     s->d_cls = nullptr;
     s->cls_rows = 0;
@@ -573,6 +601,7 @@ extern "C" int stb_tindic_set_classes(stb_tindic_t *s, const uint32_t *cls_host,
   if (!s->d_cls && hipMalloc((void **)&s->d_cls, sizeof(uint32_t) * (s->C ? s->C : 1)) != hipSuccess)
     return stb_fail("%s: out of device memory", who);
   if (s->C && hipMemcpy(s->d_cls, cls_host, sizeof(uint32_t) * s->C, hipMemcpyHostToDevice) != hipSuccess) return STB_STREAM_FAIL(who);
+  ti_drop_obs(s);  // (the caller's classes are in place: they end the observation mode)
   s->cls_rows = rows;
   return 0;
 }
@@ -606,6 +635,7 @@ extern "C" int stb_tindic_set_lik(stb_tindic_t *s, const double *lik_host, unsig
     }
   }
   if (s->d_lik) (void)hipFree(s->d_lik);
+  ti_drop_obs(s);  // (the caller's matrix ends the observation mode)
   if (drop || rows != s->lik_rows || stride != s->lik_stride) ti_drop_cgs(s);
   s->d_lik = d;
   s->lik_rows = drop ? 0 : rows;
@@ -643,7 +673,7 @@ extern "C" int stb_tindic_sweep_dishes(stb_tindic_t *s, double a, const double *
                     s->d_cls ? "were set with more" : "are not set (stb_tindic_set_classes)");
   if ((s->d_lik && s->lik_bad) || s->h_bad)
     return stb_fail("%s: the last stb_tindic_sample_%s failed and left %s undefined; draw again or set it", who,
-                    s->h_bad ? "h" : "lik", s->h_bad ? "h" : "the likelihood");
+                    s->h_bad ? "h" : s->d_x ? "gauss" : "lik", s->h_bad ? "h" : "the likelihood");
   if (info) info->skipped = info->stuck = 0;
   if (nsweeps == 0) return 0;
   stb_device_scope dev(s->dev);
@@ -671,6 +701,7 @@ extern "C" int stb_tindic_class_counts(stb_tindic_t *s, uint32_t *cnt_out) {
   STB_ENTRY;
   const char *who = "stb_tindic_class_counts";
   if (!s || !cnt_out) return stb_fail("%s: null %s", who, s ? "cnt_out" : "object");
+  if (ti_not_obs(s, who)) return 1;
   if (!s->d_cls) return stb_fail("%s: classes are not set (stb_tindic_set_classes)", who);
   const unsigned rows = s->cls_rows, stride = s->d_lik ? s->lik_stride : (s->maxK ? s->maxK : 1);
   const size_t bytes = sizeof(uint32_t) * (size_t)rows * stride;
@@ -710,6 +741,7 @@ extern "C" int stb_tindic_sample_lik(stb_tindic_t *s, const double *beta_host, d
   STB_ENTRY;
   const char *who = "stb_tindic_sample_lik";
   if (!s) return stb_fail("%s: null object", who);
+  if (ti_not_obs(s, who)) return 1;
   if (ti_lik_ready(s, who)) return 1;
   if (stb_tl_check_prior(beta_host, s->lik_rows, beta0, "beta", who)) return 1;
   stb_device_scope dev(s->dev);
@@ -727,6 +759,7 @@ extern "C" int stb_tindic_loglik(stb_tindic_t *s, double *total, uint64_t *impos
   const char *who = "stb_tindic_loglik";
   if (!s) return stb_fail("%s: null object", who);
   if (!total) return stb_fail("%s: total is required", who);
+  if (ti_not_obs(s, who)) return 1;
   if (ti_lik_ready(s, who)) return 1;
   if (s->lik_bad) return stb_fail("%s: the last stb_tindic_sample_lik failed and left the likelihood undefined", who);
   stb_device_scope dev(s->dev);
@@ -1091,6 +1124,7 @@ extern "C" int stb_tindic_logjoint_collapsed(stb_tindic_t *s, double a, const do
   const bool read_gamma = flat || want_root;
   if (read_gamma && stb_tl_check_prior(opts->gamma_host, s->maxK, opts->gamma0, "gamma", who)) return 1;
   if (want_data) {
+    if (ti_not_obs(s, who)) return 1;
     if (ti_lik_ready(s, who)) return 1;
     if (stb_tl_check_prior(opts->beta_host, s->lik_rows, opts->beta0, "beta", who)) return 1;
   }
@@ -1194,6 +1228,7 @@ extern "C" int stb_tindic_sample_beta(stb_tindic_t *s, const double *base_host, 
   STB_ENTRY;
   const char *who = "stb_tindic_sample_beta";
   if (!s) return stb_fail("%s: null object", who);
+  if (ti_not_obs(s, who)) return 1;
   if (ti_lik_ready(s, who)) return 1;
   if (ti_dc_args(base_host, s->lik_rows, s_in, shape, scale, info, who)) return 1;
   stb_device_scope dev(s->dev);
@@ -1313,6 +1348,7 @@ static int ti_pr_ready(stb_tindic_t *s, double a, const double *bpar, unsigned f
 static int ti_heldout_ready(stb_tindic_t *s, double a, const double *bpar, unsigned flags, const double *total, const char *who) {
   if (!s) return stb_fail("%s: null object", who);
   if (!total) return stb_fail("%s: total is required", who);
+  if (ti_not_obs(s, who)) return 1;
   return ti_pr_ready(s, a, bpar, flags, true, who);
 }
 
@@ -1374,7 +1410,7 @@ static int ti_seat_ready(stb_tindic_t *s, double a, const double *bpar, bool pri
                     s->d_cls ? "were set with more" : "are not set (stb_tindic_set_classes)");
   if ((lik && s->lik_bad) || s->h_bad)
     return stb_fail("%s: the last stb_tindic_sample_%s failed and left %s undefined; draw again or set it", who,
-                    s->h_bad ? "h" : "lik", s->h_bad ? "h" : "the likelihood");
+                    s->h_bad ? "h" : s->d_x ? "gauss" : "lik", s->h_bad ? "h" : "the likelihood");
   return 0;
 }
 
@@ -1664,6 +1700,7 @@ extern "C" int stb_tindic_sample_classes(stb_tindic_t *s, const uint8_t *mask_ho
   STB_ENTRY;
   const char *who = "stb_tindic_sample_classes";
   if (!s) return stb_fail("%s: null object", who);
+  if (ti_not_obs(s, who)) return 1;
   if (ti_cls_ready(s, mask_host != nullptr, who)) return 1;
   if (info) info->skipped = info->stuck = info->drawn = 0;
   stb_device_scope dev(s->dev);
@@ -1684,6 +1721,7 @@ extern "C" int stb_tindic_generate(stb_tindic_t *s, double a, const double *bpar
   STB_ENTRY;
   const char *who = "stb_tindic_generate";
   if (!s) return stb_fail("%s: null object", who);
+  if (ti_not_obs(s, who)) return 1;
   if (ti_seat_ready(s, a, bpar, true, who) || ti_cls_ready(s, false, who)) return 1;
   if (seat_info) memset(seat_info, 0, sizeof(*seat_info));
   if (cls_info) cls_info->skipped = cls_info->stuck = cls_info->drawn = 0;
@@ -1712,4 +1750,155 @@ extern "C" int stb_tindic_get_classes(stb_tindic_t *s, uint32_t *cls_out, unsign
   if (rows_out) *rows_out = s->cls_rows;
   stb_device_scope dev(s->dev);
   return ti_fetch(s, {{cls_out, s->d_cls, sizeof(uint32_t) * s->C}}, who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Gaussian observations: the object in observation mode (the kernels are gauss.hip's)
+
+static double *ti_gmu(const stb_tindic_t *s) { return s->d_gpar; }
+static double *ti_gtau(const stb_tindic_t *s) { return s->d_gpar + (size_t)s->maxK * s->obs_D; }
+static double *ti_gmean(const stb_tindic_t *s) { return s->d_gpar + 2 * (size_t)s->maxK * s->obs_D; }
+static double *ti_gQ(const stb_tindic_t *s) { return s->d_gpar + 3 * (size_t)s->maxK * s->obs_D; }
+
+// what the calls of this section ask of the object before anything is queued; params: mu and tau must be defined
+static int ti_obs_ready(stb_tindic_t *s, bool params, const char *who) {
+  if (!s) return stb_fail("%s: null object", who);
+  if (!s->d_x) return stb_fail("%s: the object holds no observations (stb_tindic_set_obs)", who);
+  if (params && s->lik_bad)
+    return stb_fail("%s: the last stb_tindic_sample_gauss failed and left the parameters undefined; draw again or set them", who);
+  if (params && !s->g_have) return stb_fail("%s: no parameters yet (stb_tindic_set_gauss, stb_tindic_sample_gauss)", who);
+  return 0;
+}
+
+extern "C" int stb_tindic_set_obs(stb_tindic_t *s, const double *x_host, unsigned D) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_obs";
+  if (!s) return stb_fail("%s: null object", who);
+  stb_device_scope dev(s->dev);
+  if (!x_host) {
+    if (D != 0) return stb_fail("%s: D=%u without observations", who, D);
+    if (hipStreamSynchronize(s->st) != hipSuccess) return STB_STREAM_FAIL(who);
+    ti_drop_obs(s);
+    ti_drop_cgs(s);
+    if (s->d_cls) (void)hipFree(s->d_cls);
+    if (s->d_lik) (void)hipFree(s->d_lik);
+    s->d_cls = nullptr;
+    s->d_lik = nullptr;
+    s->cls_rows = s->lik_rows = s->lik_stride = 0;
+    s->lik_bad = false;
+    return 0;
+  }
+  if (stb_gs_check_shape(s->maxK, D, who)) return 1;
+  if (s->C < 1 || s->C > 0xffffffffull) return stb_fail("%s: %llu customers (the matrix has a row per customer: 1 .. 2^32 - 1)", who, (unsigned long long)s->C);
+  for (uint64_t j = 0; j < s->C * D; j++)
+    if (!std::isfinite(x_host[j])) return stb_fail("%s: x[%llu]=%g (must be finite)", who, (unsigned long long)j, x_host[j]);
+  std::vector<uint64_t> koff((size_t)s->I + 1);
+  if (hipStreamSynchronize(s->st) != hipSuccess ||
+      hipMemcpy(koff.data(), s->d_koff, sizeof(uint64_t) * (s->I + 1), hipMemcpyDeviceToHost) != hipSuccess)
+    return STB_STREAM_FAIL(who);
+  for (int i = 0; i < s->I; i++)
+    if (koff[i + 1] - koff[i] != s->maxK)
+      return stb_fail("%s: restaurant %d has K=%llu dishes and another %u; observation mode needs every K_i equal", who, i,
+                      (unsigned long long)(koff[i + 1] - koff[i]), s->maxK);
+  if (ti_materialise_cust(s, who)) return 1;
+  const size_t KD = (size_t)s->maxK * D, cells = (size_t)s->C * s->maxK;
+  double *dx = nullptr, *gpar = nullptr, *lik = nullptr;
+  uint32_t *gn = nullptr, *cls = nullptr;
+  int rc = 0;
+  if (hipMalloc((void **)&dx, sizeof(double) * s->C * D) != hipSuccess || hipMalloc((void **)&gpar, sizeof(double) * 4 * KD) != hipSuccess ||
+      hipMalloc((void **)&gn, sizeof(uint32_t) * s->maxK) != hipSuccess || hipMalloc((void **)&cls, sizeof(uint32_t) * s->C) != hipSuccess ||
+      hipMalloc((void **)&lik, sizeof(double) * cells) != hipSuccess)
+    rc = stb_fail("%s: out of device memory for %llu x %u observations and a %llu x %u matrix", who, (unsigned long long)s->C, D,
+                  (unsigned long long)s->C, s->maxK);
+  if (!rc && hipMemcpy(dx, x_host, sizeof(double) * s->C * D, hipMemcpyHostToDevice) != hipSuccess) rc = STB_STREAM_FAIL(who);
+  if (!rc) rc = stb_gs_init(cls, s->C, lik, s->maxK, s->st);
+  if (!rc && hipStreamSynchronize(s->st) != hipSuccess) rc = STB_STREAM_FAIL(who);
+  if (rc) {
+    void *fresh[] = {dx, gpar, gn, cls, lik};
+    for (void *p : fresh)
+      if (p) (void)hipFree(p);
+    return 1;
+  }
+  ti_drop_obs(s);
+  ti_drop_cgs(s);
+  if (s->d_cls) (void)hipFree(s->d_cls);
+  if (s->d_lik) (void)hipFree(s->d_lik);
+  s->d_x = dx;
+  s->obs_D = D;
+  s->d_gpar = gpar;
+  s->d_gn = gn;
+  s->g_have = false;
+  s->d_cls = cls;
+  s->cls_rows = (unsigned)s->C;
+  s->d_lik = lik;
+  s->lik_rows = (unsigned)s->C;
+  s->lik_stride = s->maxK;
+  s->lik_bad = false;
+  return 0;
+}
+
+extern "C" int stb_tindic_set_gauss(stb_tindic_t *s, const double *mu, const double *tau) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_gauss";
+  if (ti_obs_ready(s, false, who)) return 1;
+  if (!mu || !tau) return stb_fail("%s: mu and tau are required", who);
+  const size_t KD = (size_t)s->maxK * s->obs_D;
+  for (size_t e = 0; e < KD; e++) {
+    if (!std::isfinite(mu[e])) return stb_fail("%s: mu[%zu]=%g (must be finite)", who, e, mu[e]);
+    if (!(tau[e] > 0.0) || !std::isfinite(tau[e])) return stb_fail("%s: tau[%zu]=%g (must be > 0 and finite)", who, e, tau[e]);
+  }
+  stb_device_scope dev(s->dev);
+  if (hipStreamSynchronize(s->st) != hipSuccess || hipMemcpy(ti_gmu(s), mu, sizeof(double) * KD, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(ti_gtau(s), tau, sizeof(double) * KD, hipMemcpyHostToDevice) != hipSuccess)
+    return STB_STREAM_FAIL(who);
+  const int rc = stb_gs_lik(s->d_x, s->obs_D, s->C, ti_gmu(s), ti_gtau(s), s->maxK, s->d_lik, s->lik_stride, nullptr, s->st, who);
+  s->g_have = rc == 0;
+  s->lik_bad = rc != 0;
+  return rc;
+}
+
+extern "C" int stb_tindic_get_gauss(stb_tindic_t *s, double *mu_out, double *tau_out) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_get_gauss";
+  if (ti_obs_ready(s, true, who)) return 1;
+  const size_t KD = (size_t)s->maxK * s->obs_D;
+  stb_device_scope dev(s->dev);
+  return ti_fetch(s, {{mu_out, ti_gmu(s), sizeof(double) * KD}, {tau_out, ti_gtau(s), sizeof(double) * KD}}, who);
+}
+
+extern "C" int stb_tindic_sample_gauss(stb_tindic_t *s, const stb_gauss_prior_t *prior, uint64_t seed, uint64_t sweep,
+                                       stb_gauss_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_sample_gauss";
+  if (ti_obs_ready(s, false, who)) return 1;
+  if (stb_gs_check_prior(prior, s->obs_D, who)) return 1;
+  stb_device_scope dev(s->dev);
+  bool touched = false;
+  const int rc = stb_gs_step(s->d_x, s->obs_D, s->d_cust, s->C, s->maxK, prior, seed, sweep, s->d_gn, ti_gmean(s), ti_gQ(s), ti_gmu(s),
+                             ti_gtau(s), s->d_lik, s->lik_stride, info, s->st, who, &touched);
+  if (touched) {  // (a call that failed before its first launch left the parameters and the matrix as they were)
+    s->lik_bad = rc != 0;
+    s->g_have = rc == 0;
+  }
+  return rc;
+}
+
+extern "C" int stb_tindic_gauss_loglik(stb_tindic_t *s, double *total) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_gauss_loglik";
+  if (ti_obs_ready(s, true, who)) return 1;
+  if (!total) return stb_fail("%s: total is required", who);
+  stb_device_scope dev(s->dev);
+  return stb_gs_loglik(s->d_x, s->obs_D, s->d_cust, s->C, ti_gmu(s), ti_gtau(s), s->maxK, total, nullptr, s->st, who);
+}
+
+extern "C" int stb_tindic_gauss_logml(stb_tindic_t *s, const stb_gauss_prior_t *prior, double *total) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_gauss_logml";
+  if (ti_obs_ready(s, false, who)) return 1;
+  if (!total) return stb_fail("%s: total is required", who);
+  if (stb_gs_check_prior(prior, s->obs_D, who)) return 1;
+  stb_device_scope dev(s->dev);
+  if (stb_gs_stats(s->d_x, s->obs_D, s->d_cust, s->C, s->maxK, s->d_gn, ti_gmean(s), ti_gQ(s), nullptr, s->st, who)) return 1;
+  return stb_gs_logml(s->d_gn, ti_gmean(s), ti_gQ(s), s->maxK, s->obs_D, prior, total, s->st, who);
 }
