@@ -795,8 +795,11 @@ int stb_tindic_get_h(stb_tindic_t *s, double *h_out);
  * I < 1; Kmax outside 1 .. STB_TD_MAXK; G < 1, G != I without ranges, ranges that are not 0 = goff[0] <= ... <= goff[G] = I;
  * unknown flags; alpha, gamma (unless STB_HG_KEEP_ROOT) or shape, scale (with STB_HG_SAMPLE_ALPHA) not positive and finite.
  * Fails after the wait, error word: 1 a rejection loop ran out, 2 a Z is not positive and finite, 4 a shape
- * alpha r_k + c_gk is not positive and finite, 8 a group's C_g is above 2^32 - 1; or the concentration's draw was not a
- * positive finite double.  The outputs are then undefined.
+ * alpha r_k + c_gk is negative, infinite or NaN, 8 a group's C_g is above 2^32 - 1; or the concentration's draw was not a
+ * positive finite double.  The outputs are then undefined.  A shape of exactly 0 is no failure: it is a base weight that
+ * underflowed to 0 (a Dirichlet coordinate of a shape far below 1 is often smaller than the smallest double) under c_gk = 0,
+ * its coordinate is 0 -- the limit of the draw -- and it takes no uniform.  (On the tree below, where a drawn row is the
+ * base of the rows under it, that is a common event with many dishes and few tables, not a rare one.)
  * Object layer, queued on the object's stream behind its sweeps; ranges, root and alpha live with the object:
  *   stb_tindic_set_hgroups     the ranges (goff_host[G+1], checked as above; NULL: every restaurant its own group, the
  *                              state of a new object)

@@ -210,6 +210,8 @@ __global__ __launch_bounds__(HG_MAXTHREADS) void k_hg_rows(uint64_t rows, unsign
         const uint64_t ke = stb_mix64(key + (e + 1) * STB_GAMMA);
         uint64_t j = 0;
         lg = hq_log_gamma(shape, ke, j, bad);
+      } else if (shape == 0.0) {
+        lg = -INFINITY;  // an underflowed base weight under no count: the coordinate is 0, and no uniform is taken
       } else {
         err |= HG_ERR_SHAPE;
       }

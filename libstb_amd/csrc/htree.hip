@@ -209,8 +209,8 @@ int stb_ht_sample(int I, const uint64_t *d_koff, const uint16_t *d_t, unsigned K
   }
   if (err)
     return stb_fail("%s: failed, error word 0x%x (1: a Gamma draw was not accepted within %d attempts; 2: a normaliser is not "
-                    "positive and finite; 4: a shape alpha base_k + c_k (base the row above, the root at the top) is not positive "
-                    "and finite; 8: a group or node has more than 2^32 - 1 tables) (seed=%llu, sweep=%llu); the outputs are "
+                    "positive and finite; 4: a shape alpha base_k + c_k (base the row above, the root at the top) is negative, "
+                    "infinite or NaN; 8: a group or node has more than 2^32 - 1 tables) (seed=%llu, sweep=%llu); the outputs are "
                     "undefined",
                     who, err, HQ_CAP, (unsigned long long)seed, (unsigned long long)sweep);
   if (draw_alpha) {

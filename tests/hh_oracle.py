@@ -54,9 +54,13 @@ def aux_tables(c, w, seed, sweep, law="right"):
 
 
 def dirichlet_rows(shape, keys):
-    """(rows normalised as the header says, smallest margin); shape[rows, Kmax], keys flat"""
+    """(rows normalised as the header says, smallest margin); shape[rows, Kmax], keys flat.  A shape of exactly 0 (an
+    underflowed base weight under no count) takes no uniform: its coordinate is 0"""
     rows, Kmax = shape.shape
-    lg, margin = tlo.log_gamma(shape.reshape(-1), keys)
+    flat = shape.reshape(-1)
+    pos = flat != 0.0
+    lg = np.full(flat.shape, -np.inf)
+    lg[pos], margin = tlo.log_gamma(flat[pos], np.asarray(keys)[pos])
     lg = lg.reshape(rows, Kmax)
     e = np.exp(lg - lg.max(axis=1, keepdims=True))
     Z = e[:, 0].copy()

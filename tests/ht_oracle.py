@@ -63,7 +63,8 @@ def aux_tables(c, w, key, first=True):
         u = hqo.unit(ky[owner], j)
         b = wf[owner]
         lhs = u * (b + j.astype(np.float64))
-        margin = float(np.min(np.abs(lhs - b) / b))
+        pos = b > 0.0                     # (under w = 0, an underflowed parent weight, u j < 0 never holds: no tie to sit on)
+        margin = float(np.min(np.abs(lhs[pos] - b[pos]) / b[pos])) if pos.any() else math.inf
         m += np.bincount(owner, weights=(lhs < b).astype(np.float64), minlength=G * Kmax).astype(np.int64)
     return m.reshape(G, Kmax), margin
 

@@ -368,15 +368,21 @@ def test_refusals_leave_the_state_and_failures_block_the_dish_sweep():
             assert re.search(match, capi.last_error()), (match, capi.last_error())
         torch.cuda.synchronize()
         assert torch.all(h == 7.0) and torch.all(root == 0.5)
-        # a failure after the wait: a root so small that alpha r_k + 0 is not positive.  h is then undefined and the dish
-        # sweep refused, as after a failed sample_h, until a draw succeeds
+        # a root so small that alpha r_k + 0 is exactly 0 is no failure: the coordinate is 0 where the group has no table
+        # and a draw of shape c where it has.  A failure after the wait: a root so large that alpha r_k is infinite.  h is then
+        # undefined and the dish sweep refused, as after a failed sample_h, until a draw succeeds
         cust = np.array([0, 0, 2, 0, 1], dtype=np.uint32)          # two restaurants of three dishes; c_01 = c_12 = 0
         n2 = np.array([2, 0, 1, 1, 1, 0], dtype=np.uint32)
         two = capi.TableIndicators(np.full(2, 3, dtype=np.int32), n2, (n2 > 0).astype(np.uint16), None, cust)
         try:
             two.set_hroot(np.array([0.3, 5e-324, 0.3]))
+            two.sample_hgroups(0.25, 1.0, 9, 0, flags=capi.HG_KEEP_ROOT)
+            h2 = two.get_h().reshape(2, 3)
+            assert h2[0, 1] == 0.0 and h2[1, 1] > 0.0 and np.all(h2[:, [0, 2]] > 0.0)
+            assert np.all(np.abs(h2.sum(axis=1) - 1.0) <= 6.0 * 2.0 ** -53)
+            two.set_hroot(np.array([0.3, 1e308, 0.3]))
             with pytest.raises(capi.StbError, match="error word 0x") as e:
-                two.sample_hgroups(0.25, 1.0, 9, 0, flags=capi.HG_KEEP_ROOT)
+                two.sample_hgroups(1e10, 1.0, 9, 0, flags=capi.HG_KEEP_ROOT)
             assert e.value.info.error_word & 4
             with pytest.raises(capi.StbError, match="undefined"):
                 two.sweep_dishes(a, np.full(2, 2.0), 65, 0)

@@ -348,17 +348,18 @@ def test_raw_refusals_write_nothing_and_a_failed_step_blocks_the_dish_sweep():
         assert re.search(match, capi.last_error()), (match, capi.last_error())
     torch.cuda.synchronize()
     assert torch.all(h == 7.0) and torch.all(root == 0.5) and torch.all(rows2 == 0.25)
-    # a failure after the wait: a root so small that alpha r_k + 0 is not positive at level 2.  h is then undefined and the
-    # dish sweep refused, as after a failed sample_h, until a draw succeeds
+    # a failure after the wait: a root so large that alpha r_k is infinite at level 2.  h is then undefined and the dish
+    # sweep refused, as after a failed sample_h, until a draw succeeds.  A root so small that alpha r_k + 0 is exactly 0 is no
+    # failure: the coordinate is 0 at level 2 and, through alpha 0 + 0, in both leaves, where nobody serves that dish
     a = 0.3
     cust = np.array([0, 0, 1, 0, 1], dtype=np.uint32)          # two restaurants of three dishes; nobody serves the third
     n2 = np.array([2, 1, 0, 1, 1, 0], dtype=np.uint32)
     two = capi.TableIndicators(np.full(2, 3, dtype=np.int32), n2, (n2 > 0).astype(np.uint16), None, cust)
     try:
-        two.set_hroot(np.array([0.3, 0.3, 5e-324]))
+        two.set_hroot(np.array([0.3, 0.3, 1e308]))
         two.set_htree([np.array([0, 1, 2], dtype=np.uint64), np.array([0, 2], dtype=np.uint64)])
         with pytest.raises(capi.StbError, match="error word 0x") as e:
-            two.sample_htree([0.25, 0.25], 1.0, 9, 0, flags=capi.HT_KEEP_ROOT)
+            two.sample_htree([0.25, 1e10], 1.0, 9, 0, flags=capi.HT_KEEP_ROOT)
         assert e.value.info.error_word & 4
         with pytest.raises(capi.StbError, match="undefined"):
             two.sweep_dishes(a, np.full(2, 2.0), 65, 0)
@@ -368,6 +369,12 @@ def test_raw_refusals_write_nothing_and_a_failed_step_blocks_the_dish_sweep():
         two.set_htree_level(2, np.full((1, 3), 1.0 / 3.0))
         two.sample_htree([0.25, 0.25], 1.0, 9, 0)
         assert two.sweep_dishes(a, np.full(2, 2.0), 65, 0).stuck == 0
+        two.set_hroot(np.array([0.3, 0.3, 5e-324]))
+        two.sample_htree([0.25, 0.25], 1.0, 9, 1, flags=capi.HT_KEEP_ROOT)
+        h2, up = two.get_h().reshape(2, 3), two.get_htree_level(2)
+        assert up[0, 2] == 0.0 and np.all(h2[:, 2] == 0.0) and np.all(h2[:, :2] > 0.0) and np.all(up[0, :2] > 0.0)
+        assert np.all(np.abs(h2.sum(axis=1) - 1.0) <= 6.0 * 2.0 ** -53)
+        assert two.sweep_dishes(a, np.full(2, 2.0), 65, 1).stuck == 0
     finally:
         two.free()
 
