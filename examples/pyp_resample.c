@@ -74,7 +74,12 @@
  *  22. with -X D the observations are real-valued: a PYP mixture of Gaussians with diagonal precisions in R^D
  *      (stb_tindic_set_obs).  Data from a few well-separated centres, a random start, then dish sweep ->
  *      stb_tindic_sample_gauss -> stb_tindic_sample_h -> stb_tindic_sampleb; every iteration prints the collapsed evidence
- *      log p(x | z) (stb_tindic_gauss_logml), which rises from the random start.  The other flags but -J -n -c -s are ignored.
+ *      log p(x | z) (stb_tindic_gauss_logml), which rises from the random start.  The other flags but -J -n -c -s -P are
+ *      ignored.  With -P every restaurant gets NCUST / 5 further points from the same clusters, held out
+ *      (stb_tindic_set_heldout_obs); each iteration prints their log predictive density under the state (`heldout`) and under
+ *      the average over the iterations so far (`avg`, stb_tindic_gauss_heldout with STB_GH_ACCUMULATE), and the run ends
+ *      with the share of held-out points whose largest responsibility names the dish that most training points of their
+ *      generating cluster sit at.
  *
  * All table builds and every log-posterior evaluation run on the GPU through libstb_amd.so; this file
  * only uses the public headers.  Usage: pyp_resample [-J 3] [-n 2000] [-a 0.5] [-b 10] [-c 60]
@@ -104,7 +109,7 @@ static int cmp_double(const void *x, const void *y) {
  * the collapsed evidence log p(x | z) (stb_tindic_gauss_logml) every iteration; returns 1 if it did not rise. */
 #define XTRUE 4
 #define XDISHES 8
-static int gauss_mixture(int J, int ncust, int D, int cycles, long seed) {
+static int gauss_mixture(int J, int ncust, int D, int cycles, long seed, int predict) {
   const size_t C = (size_t)J * ncust, G = (size_t)J * XDISHES;
   const double a = 0.1;
   double b = 1.0, centre[XTRUE][STB_GS_MAXD], first = 0.0, last = 0.0;
@@ -113,15 +118,28 @@ static int gauss_mixture(int J, int ncust, int D, int cycles, long seed) {
   stcnt_int *tf = calloc(G, sizeof(*tf));
   int *K = malloc(sizeof(int) * J), j, d, it;
   size_t c, g;
+  /* -P: NCUST / 5 further points a restaurant from the same clusters, held out; ztrue / zheld: the generating clusters */
+  const size_t nheld = predict ? (size_t)(ncust / 5 > 0 ? ncust / 5 : 1) : 0, Ch = (size_t)J * nheld;
+  int *ztrue = malloc(sizeof(int) * C), *zheld = malloc(sizeof(int) * (Ch ? Ch : 1));
+  double *y = malloc(sizeof(double) * (Ch ? Ch : 1) * D), *resp = malloc(sizeof(double) * (Ch ? Ch : 1) * XDISHES);
+  uint64_t *hoff = malloc(sizeof(uint64_t) * (J + 1));
   for (j = 0; j < XTRUE; j++)
     for (d = 0; d < D; d++) centre[j][d] = 8.0 * ((j >> (d & 1)) & 1 ? 1.0 : -1.0) + (d > 1 ? 2.0 * j : 0.0);
   for (c = 0; c < C; c++) {
     const int rest = (int)(c / ncust), z = drand48() < 0.7 ? rest % XTRUE : (int)(drand48() * XTRUE) % XTRUE;
+    ztrue[c] = z;
     for (d = 0; d < D; d++) /* Box-Muller's cosine member */
       x[c * D + d] = centre[z][d] + sqrt(-2.0 * log(1.0 - drand48())) * cos(6.283185307179586 * drand48());
     cust[c] = (scnt_int)((int)(drand48() * XDISHES) % XDISHES); /* the random start */
     nf[(size_t)rest * XDISHES + cust[c]]++;
   }
+  for (c = 0; c < Ch; c++) { /* (after the training points: without -P the data are what they were) */
+    const int rest = (int)(c / nheld), z = drand48() < 0.7 ? rest % XTRUE : (int)(drand48() * XTRUE) % XTRUE;
+    zheld[c] = z;
+    for (d = 0; d < D; d++)
+      y[c * D + d] = centre[z][d] + sqrt(-2.0 * log(1.0 - drand48())) * cos(6.283185307179586 * drand48());
+  }
+  for (j = 0; j <= J; j++) hoff[j] = (uint64_t)j * nheld;
   for (g = 0; g < G; g++) {
     tf[g] = nf[g] ? 1 : 0;
     hf[g] = 1.0 / XDISHES;
@@ -131,6 +149,7 @@ static int gauss_mixture(int J, int ncust, int D, int cycles, long seed) {
   stb_gauss_info_t gi;
   stb_tindic_t *ti = stb_tindic_create(J, K, nf, tf, hf, cust, ncust > 65535 ? 65535 : 0, 0);
   if (!ti || stb_tindic_set_obs(ti, x, (unsigned)D)) yaps_quit("the observations: %s\n", stb_last_error());
+  if (predict && stb_tindic_set_heldout_obs(ti, hoff, y)) yaps_quit("the held-out points: %s\n", stb_last_error());
   if (stb_tindic_sample_gauss(ti, &prior, (uint64_t)seed + 2, 0, &gi) || stb_tindic_gauss_logml(ti, &prior, &first))
     yaps_quit("the first draw: %s\n", stb_last_error());
   printf("Gaussian mixture: %d restaurants x %d customers in R^%d, %d centres, %d dishes; start: log p(x | z) = %.6f\n", J, ncust, D,
@@ -147,12 +166,41 @@ static int gauss_mixture(int J, int ncust, int D, int cycles, long seed) {
     for (j = 0; j < J; j++) bvec[j] = b;
     if (stb_tindic_gauss_logml(ti, &prior, &last) || stb_tindic_gauss_loglik(ti, &data))
       yaps_quit("the evidence: %s\n", stb_last_error());
-    printf("iter %3d  b=%.4f  log p(x | z) = %.6f  log p(x | z, mu, tau) = %.6f  stuck %llu dead rows %llu\n", it, b, last, data,
+    printf("iter %3d  b=%.4f  log p(x | z) = %.6f  log p(x | z, mu, tau) = %.6f  stuck %llu dead rows %llu", it, b, last, data,
            (unsigned long long)di.stuck, (unsigned long long)gi.dead);
+    if (predict) { /* this state's log predictive density of the held-out points, and the average over the states so far */
+      double ho = 0.0, ho_avg = 0.0;
+      if (stb_tindic_gauss_heldout(ti, a, bvec, 0, &ho, NULL, NULL, NULL) ||
+          stb_tindic_gauss_heldout(ti, a, bvec, STB_GH_ACCUMULATE, &ho_avg, NULL, it == cycles ? resp : NULL, NULL))
+        yaps_quit("stb_tindic_gauss_heldout: %s\n", stb_last_error());
+      printf("  heldout = %.6f  avg = %.6f", ho, ho_avg);
+    }
+    printf("\n");
+  }
+  if (predict && cycles > 0) {
+    /* a cluster's dish: where most of its training points sit now; a held-out point is classified by its largest
+     * responsibility under the last state */
+    unsigned long votes[XTRUE][XDISHES] = {{0}}, hit = 0;
+    uint32_t *now = malloc(sizeof(uint32_t) * C);
+    int major[XTRUE], k;
+    if (stb_tindic_get_state(ti, NULL, now)) yaps_quit("stb_tindic_get_state: %s\n", stb_last_error());
+    for (c = 0; c < C; c++) votes[ztrue[c]][now[c] % XDISHES]++;
+    for (j = 0; j < XTRUE; j++)
+      for (major[j] = 0, k = 1; k < XDISHES; k++)
+        if (votes[j][k] > votes[j][major[j]]) major[j] = k;
+    for (c = 0; c < Ch; c++) {
+      int best = 0;
+      for (k = 1; k < XDISHES; k++)
+        if (resp[c * XDISHES + k] > resp[c * XDISHES + best]) best = k;
+      hit += best == major[zheld[c]];
+    }
+    printf("held-out points classified to their cluster's dish: %lu of %lu (%.1f %%)\n", hit, (unsigned long)Ch, 100.0 * hit / Ch);
+    free(now);
   }
   printf("evidence: %.6f -> %.6f (%s)\n", first, last, last > first ? "rose" : "DID NOT RISE");
   stb_tindic_free(ti);
   free(x), free(hf), free(bvec), free(nf), free(cust), free(tf), free(K);
+  free(ztrue), free(zheld), free(y), free(resp), free(hoff);
   return last > first ? 0 : 1;
 }
 
@@ -224,7 +272,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "pyp_resample: -T a:b[:c] needs 1 to %d levels of >= 1 nodes and -d -z -w, without -H and -C\n", STB_HT_MAXL);
     return 2;
   }
-  if (predict && !(explicit_d && dishes)) {
+  if (predict && !xdim && !(explicit_d && dishes)) {
     fprintf(stderr, "pyp_resample: -P needs -d -z\n");
     return 2;
   }
@@ -258,7 +306,7 @@ int main(int argc, char **argv) {
   }
   srand48(seed);
   srand((unsigned)seed);
-  if (xdim) return gauss_mixture(J, ncust, xdim, cycles, seed); /* 22.: a mixture of Gaussians, nothing else of this file */
+  if (xdim) return gauss_mixture(J, ncust, xdim, cycles, seed, predict); /* 22.: a mixture of Gaussians, nothing else of this file */
 
   /* ---- 1. data: seat customers, remember per (restaurant, dish) customers n and tables t ---- */
   scnt_int **n = malloc(sizeof(*n) * J), *N = calloc(J, sizeof(*N)), *T = calloc(J, sizeof(*T));

@@ -1604,6 +1604,71 @@ int stb_tindic_sample_gauss(stb_tindic_t *s, const stb_gauss_prior_t *prior, uin
 int stb_tindic_gauss_loglik(stb_tindic_t *s, double *total);
 int stb_tindic_gauss_logml(stb_tindic_t *s, const stb_gauss_prior_t *prior, double *total);
 
+/* ---- Held-out points under Gaussian observations (gauss.hip, predict.hip; additive) ----
+ * The Gaussian twin of stb_predict_dishes / stb_heldout_loglik.  Held-out point j (flat index, CSR over hoff[I + 1] as the
+ * held-out customers above; y is C_h x D row-major, C_h = hoff[I]) of restaurant i has, under one state,
+ *     log p(y_j | state) = log sum_k theta_ik N(y_j | mu_k, 1 / tau_k),
+ * computed from x-space quantities with the true normalisation: the row-scaled matrix never enters.  Densities in up to
+ * 64 dimensions leave the range of a double, so everything per point is kept as a logarithm, the accumulator over
+ * states included.  FP64, no contraction; K is the common K_i; tests/gh_oracle.py replays every operation.
+ *   theta_ik   stb_predict_dishes' theta, bit for bit: call it with d_theta, no held-out customers and no matrix.
+ *   l_jk       = H_k - 0.5 * q_jk, stb_gauss_lik's values with y_j for x_c (H_k, q_jk added in d order from the d = 0 term).
+ *   m_j        = max of l_jk over the k < K with theta_ik > 0 (a NaN is never greater).  m_j not finite: the point is
+ *              impossible -- ell_j = -inf, its responsibilities are 0, its accumulator is left alone, and the sum counts
+ *              it.  The restriction to theta_ik > 0 guarantees s_j >= theta_ik* > 0 for a possible point: under the plain
+ *              maximum a dish with theta = 0 that lies nearest the point can underflow every term.
+ *   w_jk       = theta_ik * exp(l_jk - m_j); +0.0 where theta_ik is not > 0 or k >= K.
+ *   s_j        the w_jk in blocks of 64 dishes, lane l taking dish 64 b + l, a block by the shuffle tree
+ *              v += shfl_down(v, o), o = 32 .. 1, the block sums added in block order: stb_predict_dishes' p_c.
+ *   ell_j      = (m_j + log(s_j)) + (double)D * (-0.9189385332046727).
+ *   r_jk       = w_jk / s_j into d_resp[j * rstride + k], 0.0 for K <= k < rstride.
+ *   (M_j, A_j) with STB_GH_ACCUMULATE, standing for A_j e^{M_j} = sum over the accumulated states of p_j; empty: (-inf, 0.0).
+ *              ell_j = -inf leaves the pair alone; ell_j > M_j: A_j = A_j * exp(M_j - ell_j) + 1.0 (1.0 from the empty pair),
+ *              then M_j = ell_j; otherwise A_j = A_j + exp(ell_j - M_j).  One lane owns a point: S calls give the bits of
+ *              the S updates in call order.
+ * stb_gauss_heldout (k_gs_prep, then k_gh_point_reg for K <= 64 and D <= 16, else k_gh_point: a wave a point, lanes along
+ * k) queues its two launches and returns; the transposed parameters live in a buffer of the calling thread, so calls of
+ * one thread on different streams must not be in flight together.  No bit depends on STB_GAUSS_WAVES or on the grid.
+ * stb_gauss_heldout_loglik (k_gh_sum, which shares k_heldout_sum's body): x_j = ell_j (d_accM and d_accA NULL; a value
+ * that is not finite is impossible), or x_j = M_j + log(A_j / (double)samples), impossible when A_j / samples is not a
+ * positive finite number.  An impossible point adds +0.0, counts in info.impossible and makes H_i and the total -inf.
+ * The x_j are summed exactly as stb_heldout_loglik sums its x_c: chunks of 64 in CSR order through the tree, the chunk
+ * sums in order in double-double, H_i = hi + lo; over restaurants stb_logjoint's association, geometry and ticket.  One
+ * launch, one wait.  No NaN is produced for finite y, finite mu and positive finite tau.
+ * Refused before anything is queued, with stb_last_error() set: a null required array, D outside 1 .. STB_GS_MAXD, K
+ * outside 1 .. STB_TD_MAXK, tstride < K, rstride < K with d_resp, STB_GH_ACCUMULATE without both accumulator arrays,
+ * samples = 0 with accumulators, unknown flag bits, I < 0. */
+#define STB_GH_ACCUMULATE 1u
+int stb_gauss_heldout(const double *d_theta, unsigned tstride, int I, const uint64_t *d_hoff, const double *d_y, unsigned D,
+                      const double *d_mu, const double *d_tau, unsigned K, double *d_ell /* NULL, or C_h */,
+                      double *d_resp /* NULL, or C_h x rstride */, unsigned rstride, double *d_accM,
+                      double *d_accA /* both with STB_GH_ACCUMULATE, else ignored */, unsigned flags, void *stream);
+int stb_gauss_heldout_loglik(const double *d_ell, const double *d_accM, const double *d_accA, unsigned samples,
+                             const uint64_t *d_hoff, int I, double *d_Hi /* NULL, or I */, double *total_host,
+                             stb_predict_info_t *info /* or NULL */, void *stream);
+/* Object layer, in observation mode only.  The observation held-out set is storage of its own: stb_tindic_set_heldout, its
+ * classes and its accumulator are untouched, and _heldout, _heldout_seq, _heldout_pf, _heldout_ais stay refused.
+ *   stb_tindic_set_heldout_obs     hoff_host[I + 1] and y_host (hoff[I] x D, D as set_obs gave it); NULL offsets remove the
+ *                                  set.  An empty accumulator, no samples.  Refused: outside observation mode, hoff[0] != 0
+ *                                  or decreasing offsets, a y that is not finite.  Leaving the mode (set_obs(NULL, 0), a
+ *                                  caller's set_classes / set_lik) drops the set, and so does a set_obs with another D.
+ *   stb_tindic_gauss_heldout       stb_predict_dishes into scratch theta (tstride = K), stb_gauss_heldout (rstride = K),
+ *                                  stb_gauss_heldout_loglik: the raw composition bit for bit, queued behind the object's
+ *                                  sweeps with one wait; n, t, T, cust, h, mu, tau and the matrix are not written.  Without
+ *                                  flags it scores the current state through a scratch ell and leaves the accumulator
+ *                                  alone; with STB_GH_ACCUMULATE it updates the accumulator, counts the sample and returns
+ *                                  the running estimate sum_j log((1/S) sum_s p_j).  STB_BPAR_RESIDENT, per-group and tree
+ *                                  h work as for stb_tindic_predict.  Refused, state and accumulator as they were: no
+ *                                  observations, no held-out set, parameters undefined (none yet, or a failed
+ *                                  _sample_gauss), h undefined after a failed _sample_h, a / bpar as the sweeps refuse them.
+ *   stb_tindic_gauss_heldout_reset an empty accumulator and no samples; _gauss_heldout_get returns the pairs and the count. */
+int stb_tindic_set_heldout_obs(stb_tindic_t *s, const uint64_t *hoff_host /* I+1, or NULL */, const double *y_host /* hoff[I] x D */);
+int stb_tindic_gauss_heldout(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total,
+                             double *Hi_host /* or NULL */, double *resp_host /* NULL, or hoff[I] x K */,
+                             stb_predict_info_t *info /* or NULL */);
+int stb_tindic_gauss_heldout_reset(stb_tindic_t *s);
+int stb_tindic_gauss_heldout_get(stb_tindic_t *s, double *M_out, double *A_out, unsigned *samples); /* each or NULL */
+
 /* ---- aterms2, the S-free discount posterior of samplea2 (lib/samplea.c:85-150) ----
  * For a sampled partition of the customers into tables the posterior needs only how many tables have
  * each size: cnt[s] = number of tables with s customers (s = 2 .. S-1; entries 0 and 1 are ignored),

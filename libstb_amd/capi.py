@@ -69,6 +69,7 @@ class TDishInfo(C.Structure):
     _fields_ = [("skipped", C.c_uint64), ("stuck", C.c_uint64)]
 
 
+GH_ACCUMULATE = 1  # stb_gauss_heldout / stb_tindic_gauss_heldout flag: update the log-domain accumulator
 PR_ACCUMULATE = 1  # stb_predict_dishes / stb_tindic_heldout flag: add the state's p into the accumulator
 
 
@@ -458,6 +459,13 @@ def lib() -> C.CDLL:
     sig("stb_tindic_sample_gauss", i, [vp, gsp, u64, u64, gsi])
     sig("stb_tindic_gauss_loglik", i, [vp, c_double_p])
     sig("stb_tindic_gauss_logml", i, [vp, gsp, c_double_p])
+    # ---- held-out points under Gaussian observations
+    sig("stb_gauss_heldout", i, [vp, u, i, vp, vp, u, vp, vp, u, vp, vp, u, vp, vp, u, vp])
+    sig("stb_gauss_heldout_loglik", i, [vp, vp, vp, u, vp, i, vp, c_double_p, pri, vp])
+    sig("stb_tindic_set_heldout_obs", i, [vp, C.POINTER(u64), c_double_p])
+    sig("stb_tindic_gauss_heldout", i, [vp, d, c_double_p, u, c_double_p, c_double_p, c_double_p, pri])
+    sig("stb_tindic_gauss_heldout_reset", i, [vp])
+    sig("stb_tindic_gauss_heldout_get", i, [vp, c_double_p, c_double_p, C.POINTER(u)])
     # (private entry points: the customers per restaurant as d_N or as d_coff prefix sums, for tests)
     sig("stb_hq_logq", i, [d, d, i, vp, vp, vp, c_double_p, u64, u64, vp])
     sig("stb_hj_joint_terms", i, [c_double_p, i, c_double_p, i, vp, vp, vp, u64, vp, vp])
@@ -1376,6 +1384,37 @@ def gauss_logml(n, mean, Q, prior, stream=None):
     return tot.value
 
 
+def gauss_heldout(theta, hoff, y, mu, tau, want_ell: bool = True, rstride: int = 0, acc=None, stream=None, flags=None):
+    """stb_gauss_heldout on device tensors: theta float64 (I, tstride) as predict_dishes returns it, hoff int64 (I + 1), y
+    float64 (C_h, D), mu and tau float64 (K, D).  rstride > 0: the responsibilities come back as a float64 (C_h, rstride)
+    device tensor.  acc: None, or the pair (M, A) of float64 device tensors (C_h) the call updates (empty: -inf and 0).
+    Queued, no wait.  Returns (ell or None, resp or None)."""
+    torch = _torch()
+    I, Ch, D, K = int(hoff.shape[0]) - 1, int(y.shape[0]), int(y.shape[1]), int(mu.shape[0])
+    ell = torch.empty(max(Ch, 1), dtype=torch.float64, device=y.device)[:Ch] if want_ell else None
+    resp = torch.empty((max(Ch, 1), rstride), dtype=torch.float64, device=y.device)[:Ch] if rstride > 0 else None
+    fl = (GH_ACCUMULATE if acc is not None else 0) if flags is None else int(flags)
+    M, A = acc if acc is not None else (None, None)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    check(lib().stb_gauss_heldout(theta.data_ptr(), int(theta.shape[1]), I, hoff.data_ptr(), y.data_ptr(), D, mu.data_ptr(),
+                                  tau.data_ptr(), K, ptr(ell), ptr(resp), int(rstride), ptr(M), ptr(A), fl, stream_ptr(stream)))
+    return ell, resp
+
+
+def gauss_heldout_loglik(hoff, ell=None, acc=None, samples: int = 1, want_Hi: bool = True, stream=None):
+    """stb_gauss_heldout_loglik: the sum of ell (float64 device tensor), or with acc = (M, A) of sum_j M_j + log(A_j /
+    samples): (total, H_i as a float64 device tensor or None, PredictInfo), after one wait"""
+    torch = _torch()
+    I = int(hoff.shape[0]) - 1
+    Hi = torch.empty(max(I, 1), dtype=torch.float64, device=hoff.device)[:I] if want_Hi else None
+    tot, info = C.c_double(0.0), PredictInfo()
+    M, A = acc if acc is not None else (None, None)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    check(lib().stb_gauss_heldout_loglik(ptr(ell), ptr(M), ptr(A), int(samples), hoff.data_ptr(), I, ptr(Hi), C.byref(tot),
+                                         C.byref(info), stream_ptr(stream)))
+    return tot.value, Hi, info
+
+
 def dirmult_logml(cnt, w, orientation: int = DM_ROWS, cols: int = 0, scale=1.0, want_each: bool = True, stream=None):
     """stb_dirmult_logml on a device tensor cnt (int32 holding uint32 counts, (rows, stride); cols = 0: stride columns):
     the log marginal of its rows (DM_ROWS) or columns (DM_COLUMNS) as multinomials under a Dirichlet prior.  w: a float64
@@ -2018,6 +2057,49 @@ class TableIndicators(_BGroupsMixin):
         tot = C.c_double(0.0)
         check(self.L.stb_tindic_gauss_logml(self.h, C.byref(p), C.byref(tot)))
         return tot.value
+
+    # ---- held-out points under Gaussian observations (stb_tindic_set_heldout_obs / _gauss_heldout)
+
+    def set_heldout_obs(self, hoff=None, y=None):
+        """the held-out points of every restaurant: hoff[I+1] prefix sums and y (hoff[I], D); None removes them.  An empty
+        accumulator, no samples"""
+        if hoff is None:
+            check(self.L.stb_tindic_set_heldout_obs(self.h, None, None))
+            self.gHc = 0
+            return
+        hoff = np.ascontiguousarray(hoff, dtype=np.uint64)
+        D = getattr(self, "obs_D", 0)
+        y = np.ascontiguousarray(np.zeros((0, max(D, 1))) if y is None else y, dtype=np.float64)
+        if hoff.shape != (self.I + 1,) or y.ndim != 2 or (D and y.shape != (int(hoff[-1]), D)):
+            raise StbError(f"TableIndicators.set_heldout_obs: {hoff.shape[0]} offsets for {self.I} restaurants, y of shape "
+                           f"{y.shape} for {int(hoff[-1])} points of {D} dimensions")
+        check(self.L.stb_tindic_set_heldout_obs(self.h, hoff.ctypes.data_as(C.POINTER(C.c_uint64)), dp(y)))
+        self.gHc = int(hoff[-1])
+
+    def gauss_heldout(self, a, bpar, accumulate: bool = False, want_Hi: bool = True, want_resp: bool = False, flags=None):
+        """(total, H_i[I] or None, resp (Hc, K) or None, PredictInfo): the held-out points' log predictive density under the
+        current state, or with accumulate the running estimate sum_j log((1/S) sum_s p_j) after this state went into the
+        log-domain accumulator"""
+        bpar = _bpar(bpar, self.I)
+        Hi = np.zeros(self.I, dtype=np.float64) if want_Hi else None
+        resp = np.zeros((getattr(self, "gHc", 0), self.maxK), dtype=np.float64) if want_resp else None
+        tot, info = C.c_double(0.0), PredictInfo()
+        fl = (GH_ACCUMULATE if accumulate else 0) if flags is None else int(flags)
+        check(self.L.stb_tindic_gauss_heldout(self.h, float(a), dp(bpar), fl, C.byref(tot), None if Hi is None else dp(Hi),
+                                              None if resp is None else dp(resp), C.byref(info)))
+        return tot.value, Hi, resp, info
+
+    def gauss_heldout_reset(self):
+        """an empty accumulator and no samples"""
+        check(self.L.stb_tindic_gauss_heldout_reset(self.h))
+
+    def gauss_heldout_get(self):
+        """(M[Hc], A[Hc], the states accumulated): A e^M is the sum of the states' densities"""
+        S = C.c_uint(0)
+        n = getattr(self, "gHc", 0)
+        M, A = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        check(self.L.stb_tindic_gauss_heldout_get(self.h, dp(M) if n else None, dp(A) if n else None, C.byref(S)))
+        return M, A, S.value
 
     def heldout_seq(self, a, bpar, particles: int, seed: int, sweep: int, want_Hi: bool = True):
         """(total, H_i[I] or None, SeatInfo): the held-out customers seated one after another on a private copy of every

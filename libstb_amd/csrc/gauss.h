@@ -31,5 +31,16 @@ int stb_gs_loglik(const double *d_x, unsigned D, const uint32_t *d_cust, uint64_
                   unsigned K, double *total_host, stb_gauss_info_t *info, hipStream_t st, const char *who);
 int stb_gs_logml(const uint32_t *d_n, const double *d_mean, const double *d_Q, unsigned K, unsigned D,
                  const stb_gauss_prior_t *prior, double *total_host, hipStream_t st, const char *who);
+// STB_GAUSS_WAVES (1, 2, 4 or 8; default 4)
+unsigned stb_gs_waves();
+// k_gs_prep alone on st, no wait: T holds muT, tauT (K D each) and H (K)
+void stb_gs_queue_prep(const double *d_mu, const double *d_tau, unsigned K, unsigned D, double *T, hipStream_t st);
+// held-out points (gauss_heldout.hip, stb_gauss_heldout): k_gs_prep and the point kernel queued on st, no wait.  d_accM null: no accumulation;
+// d_resp null: no responsibilities
+int stb_gs_heldout(const double *d_theta, unsigned tstride, int I, const uint64_t *d_hoff, const double *d_y, unsigned D,
+                   const double *d_mu, const double *d_tau, unsigned K, double *d_ell, double *d_resp, unsigned rstride,
+                   double *d_accM, double *d_accA, hipStream_t st, const char *who);
+// (M, A) = (-inf, 0.0) on n points, queued on st: no wait
+int stb_gs_heldout_reset(double *d_accM, double *d_accA, uint64_t n, hipStream_t st);
 
 #endif

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(GS_MAXTHREADS) void k_gs_logml(const uint32_t *n, c
 // ------------------------------------------------------------------------------------------------
 // host side.  Every call takes its scratch from the buffer cache and gives it back behind its one wait.
 
-static unsigned gs_waves() {
+unsigned stb_gs_waves() {
   return (unsigned)stb_env_waves("STB_GAUSS_WAVES", 4);
 }
 
@@ -478,7 +478,7 @@ static size_t gs_stats_bytes(uint64_t C, unsigned K, unsigned D) {
 // the four launches of the statistics on st; ws: gs_stats_bytes of device scratch
 static void gs_queue_stats(const double *d_x, unsigned D, const uint32_t *d_cust, uint64_t C, unsigned K, uint32_t *d_n,
                            double *d_mean, double *d_Q, char *ws, unsigned long long *ctl, hipStream_t st) {
-  const unsigned nw = gs_waves(), nchunks = (unsigned)((C + GS_CHUNK - 1) / GS_CHUNK), cb = (K + 63) / 64,
+  const unsigned nw = stb_gs_waves(), nchunks = (unsigned)((C + GS_CHUNK - 1) / GS_CHUNK), cb = (K + 63) / 64,
                  dz = (D + GS_DT - 1) / GS_DT;
   double *csum = (double *)ws;
   uint32_t *ccnt = (uint32_t *)(ws + 8 * (size_t)nchunks * D * K);
@@ -512,7 +512,7 @@ static int gs_draw_failed(unsigned long long err, uint64_t seed, uint64_t sweep,
 int stb_gs_draw(const uint32_t *d_n, const double *d_mean, const double *d_Q, unsigned K, unsigned D,
                 const stb_gauss_prior_t *prior, uint64_t seed, uint64_t sweep, double *d_mu, double *d_tau, hipStream_t st,
                 const char *who) {
-  const unsigned nw = gs_waves();
+  const unsigned nw = stb_gs_waves();
   gs_scratch sc;
   if (gs_take(sc, 256 + 16 * (size_t)D, 16 * (size_t)D, st, who)) return 1;
   char *d = (char *)sc.d;
@@ -532,7 +532,7 @@ int stb_gs_draw(const uint32_t *d_n, const double *d_mean, const double *d_Q, un
 // k_gs_prep and the matrix's kernel on st; T: 2 K D + K doubles of device scratch
 static void gs_queue_lik(const double *d_x, unsigned D, uint64_t C, const double *d_mu, const double *d_tau, unsigned K,
                          double *d_lik, unsigned stride, double *T, unsigned long long *ctl, hipStream_t st) {
-  const unsigned nw = gs_waves();
+  const unsigned nw = stb_gs_waves();
   double *muT = T, *tauT = T + (size_t)K * D, *H = tauT + (size_t)K * D;
   STB_LAUNCH(k_gs_prep, dim3((K + 255) / 256), dim3(256), st, d_mu, d_tau, K, D, muT, tauT, H);
   if (!C) return;
@@ -541,6 +541,11 @@ static void gs_queue_lik(const double *d_x, unsigned D, uint64_t C, const double
     STB_LAUNCH(k_gs_lik_reg, grid, block, st, d_x, D, C, muT, tauT, H, K, d_lik, stride, ctl);
   else
     STB_LAUNCH(k_gs_lik, grid, block, st, d_x, D, C, muT, tauT, H, K, d_lik, stride, ctl);
+}
+
+// k_gs_prep alone on st, no wait: T as gs_queue_lik's
+void stb_gs_queue_prep(const double *d_mu, const double *d_tau, unsigned K, unsigned D, double *T, hipStream_t st) {
+  STB_LAUNCH(k_gs_prep, dim3((K + 255) / 256), dim3(256), st, d_mu, d_tau, K, D, T, T + (size_t)K * D, T + 2 * (size_t)K * D);
 }
 
 int stb_gs_lik(const double *d_x, unsigned D, uint64_t C, const double *d_mu, const double *d_tau, unsigned K, double *d_lik,
@@ -560,7 +565,7 @@ int stb_gs_lik(const double *d_x, unsigned D, uint64_t C, const double *d_mu, co
 int stb_gs_step(const double *d_x, unsigned D, const uint32_t *d_cust, uint64_t C, unsigned K, const stb_gauss_prior_t *prior,
                 uint64_t seed, uint64_t sweep, uint32_t *d_n, double *d_mean, double *d_Q, double *d_mu, double *d_tau,
                 double *d_lik, unsigned stride, stb_gauss_info_t *info, hipStream_t st, const char *who, bool *touched) {
-  const unsigned nw = gs_waves();
+  const unsigned nw = stb_gs_waves();
   // scratch: ctl (256 bytes), the prior's vectors (2 D), muT, tauT, H (2 K D + K), the statistics'
   const size_t o_v = 256, o_T = o_v + 16 * (size_t)D, o_s = o_T + 8 * (2 * (size_t)K * D + K), bytes = o_s + gs_stats_bytes(C, K, D);
   gs_scratch sc;
@@ -606,7 +611,7 @@ int stb_gs_loglik(const double *d_x, unsigned D, const uint32_t *d_cust, uint64_
     *total_host = add;
     return 0;
   }
-  const unsigned nw = gs_waves(), nblk = gs_blocks(C);
+  const unsigned nw = stb_gs_waves(), nblk = gs_blocks(C);
   // scratch: ctl (256 bytes), muT, tauT (unused by the sum, written by k_gs_prep), H[K], partial[nblk]
   const size_t o_T = 256, o_p = o_T + 8 * (2 * (size_t)K * D + K), bytes = o_p + 8 * (size_t)nblk;
   gs_scratch sc;
@@ -629,7 +634,7 @@ int stb_gs_loglik(const double *d_x, unsigned D, const uint32_t *d_cust, uint64_
 
 int stb_gs_logml(const uint32_t *d_n, const double *d_mean, const double *d_Q, unsigned K, unsigned D,
                  const stb_gauss_prior_t *prior, double *total_host, hipStream_t st, const char *who) {
-  const unsigned nw = gs_waves(), nblk = gs_blocks((uint64_t)K * D);
+  const unsigned nw = stb_gs_waves(), nblk = gs_blocks((uint64_t)K * D);
   // scratch: ctl (256 bytes), the prior's vectors (2 D), partial[nblk]
   const size_t o_v = 256, o_p = o_v + 16 * (size_t)D, bytes = o_p + 8 * (size_t)nblk;
   gs_scratch sc;

@@ -10,6 +10,8 @@ extern "C" {
 #endif
 /* frees the calling thread's block sums, counters and result words (stb_sampler_cache_clear) */
 void stb_pr_release(void);
+/* the same for the held-out points' transposed parameters (gauss.hip) */
+void stb_gh_release(void);
 #ifdef __cplusplus
 }
 #endif
@@ -28,5 +30,9 @@ int stb_pr_predict(const stb_rest_view &r, const stb_cnts_ro &c, const stb_cust_
  * device word whose value goes into info->skipped */
 int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned samples, double *d_Hi, double *Hi_host,
                    double *total_host, stb_predict_info_t *info, const uint64_t *d_skipped, hipStream_t st, const char *who);
+/* k_gh_sum: the same sum over x_c = d_x[c] (d_A null: log densities; a value that is not finite is impossible), or over
+ * x_c = d_x[c] + log(d_A[c] / samples) (the log-domain accumulator pairs of gauss.hip's held-out points) */
+int stb_pr_heldout_log(const double *d_x, const double *d_A, unsigned samples, const uint64_t *d_hoff, int I, double *d_Hi,
+                       double *Hi_host, double *total_host, stb_predict_info_t *info, hipStream_t st, const char *who);
 #endif
 #endif

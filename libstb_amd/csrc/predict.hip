@@ -9,6 +9,7 @@
 //   k_predict      a wave a restaurant, grid-stride; restaurants are independent: nobody waits for anybody
 //   k_heldout_sum  k_logjoint's shape (logjoint.hip): blocks of 256 restaurants, a wave a restaurant, the block sums added
 //                  by the last workgroup to finish (a ticket); geometry and ticket from ticket.h
+//   k_gh_sum       the same body on log densities, or on log-domain accumulator pairs (gauss.hip's held-out points)
 //
 // The association (no contraction anywhere; FP64 throughout; u32 / u64 integers are exact) is the header's, word for
 // word; tests/pr_oracle.py replays it.  In short:
@@ -135,15 +136,28 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_predict(double a, const doubl
 
 // ctl: [0] ticket (u32); as u64 word 1: impossible customers -- zeroed on the stream ahead of the launch.
 // host: [0] total, as u64 [1] impossible, [2] customers, [3] skipped (copied from skipped_in, 0 without one)
-__global__ __launch_bounds__(PR_MAXTHREADS) void k_heldout_sum(const double *p, const uint64_t *hoff, uint64_t I,
-                                                               double samples, double *Hi, double *partial, unsigned nblk,
-                                                               unsigned *ctl, double *host,
-                                                               const unsigned long long *skipped_in) {
+//
+// The body serves two kernels that differ in what a customer's term x_c is taken from and in nothing else:
+//   PR_X_P       k_heldout_sum: p holds probabilities, x_c = log(p_c / samples)
+//   PR_X_LOG     k_gh_sum (stb_gauss_heldout_loglik): p holds log densities, x_c = p_c; not finite: impossible
+//   PR_X_LOGACC  k_gh_sum: (p, A) hold the log-domain accumulator pairs (M_c, A_c), x_c = M_c + log(A_c / samples);
+//                A_c / samples not positive and finite: impossible
+struct pr_sum_lds {  // a kernel's one copy, whichever forms of the body it holds
+  double sx[PR_BLOCK];  // H_i of the block's restaurants (the possible customers' sum)
+  unsigned sflag[PR_BLOCK];
+  double stage[PR_STAGE];
+  unsigned s_last;
+};
+#define PR_X_P 0
+#define PR_X_LOG 1
+#define PR_X_LOGACC 2
+template <int X>
+__device__ __forceinline__ void pr_heldout_sum(const double *p, const double *A, const uint64_t *hoff, uint64_t I,
+                                               double samples, double *Hi, double *partial, unsigned nblk, unsigned *ctl,
+                                               double *host, const unsigned long long *skipped_in, pr_sum_lds &lds) {
 #pragma clang fp contract(off)
-  __shared__ double sx[PR_BLOCK];  // H_i of the block's restaurants (the possible customers' sum)
-  __shared__ unsigned sflag[PR_BLOCK];
-  __shared__ double stage[PR_STAGE];
-  __shared__ unsigned s_last;
+  double *sx = lds.sx, *stage = lds.stage;
+  unsigned *sflag = lds.sflag;
   const unsigned nthr = blockDim.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = nthr >> 6;
   unsigned long long c_imp = 0;  // per lane, over everything the lane sees
   for (unsigned blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -157,10 +171,21 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_heldout_sum(const double *p, 
         const uint64_t c = base + lane;
         double x = 0.0;
         if (c < c1) {
-          const double pc = p[c], q = pc / samples;
-          if (q > 0.0 && isfinite(pc)) {
-            x = log(q);
+          bool ok;
+          if (X == PR_X_P) {
+            const double pc = p[c], q = pc / samples;
+            ok = q > 0.0 && isfinite(pc);
+            if (ok) x = log(q);
+          } else if (X == PR_X_LOG) {
+            const double l = p[c];
+            ok = isfinite(l);
+            if (ok) x = l;
           } else {
+            const double q = A[c] / samples;
+            ok = q > 0.0 && isfinite(q);
+            if (ok) x = p[c] + log(q);
+          }
+          if (!ok) {
             bad = 1;
             c_imp++;
           }
@@ -193,7 +218,7 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_heldout_sum(const double *p, 
   c_imp = stb_wave_sum(c_imp);
   unsigned long long *cnt = (unsigned long long *)ctl;
   if (lane == 0 && c_imp) __hip_atomic_fetch_add(&cnt[1], c_imp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (!stb_ticket_last(ctl, gridDim.x, &s_last)) return;  // (ticket.h: the block sums and the counter are published)
+  if (!stb_ticket_last(ctl, gridDim.x, &lds.s_last)) return;  // (ticket.h: the block sums and the counter are published)
   dd_t tot{0.0, 0.0};  // thread 0's
   for (unsigned b0 = 0; b0 < nblk; b0 += PR_STAGE) {
     const unsigned bn = nblk - b0 < PR_STAGE ? nblk - b0 : PR_STAGE;
@@ -211,6 +236,23 @@ __global__ __launch_bounds__(PR_MAXTHREADS) void k_heldout_sum(const double *p, 
     hc[2] = hoff[I] - hoff[0];
     hc[3] = skipped_in ? *skipped_in : 0ull;
   }
+}
+
+__global__ __launch_bounds__(PR_MAXTHREADS) void k_heldout_sum(const double *p, const uint64_t *hoff, uint64_t I,
+                                                               double samples, double *Hi, double *partial, unsigned nblk,
+                                                               unsigned *ctl, double *host,
+                                                               const unsigned long long *skipped_in) {
+  __shared__ pr_sum_lds lds;
+  pr_heldout_sum<PR_X_P>(p, nullptr, hoff, I, samples, Hi, partial, nblk, ctl, host, skipped_in, lds);
+}
+
+// A null: x holds log densities; else (x, A) the accumulator pairs of `samples` states
+__global__ __launch_bounds__(PR_MAXTHREADS) void k_gh_sum(const double *x, const double *A, const uint64_t *hoff, uint64_t I,
+                                                          double samples, double *Hi, double *partial, unsigned nblk,
+                                                          unsigned *ctl, double *host) {
+  __shared__ pr_sum_lds lds;
+  if (A) pr_heldout_sum<PR_X_LOGACC>(x, A, hoff, I, samples, Hi, partial, nblk, ctl, host, nullptr, lds);
+  else pr_heldout_sum<PR_X_LOG>(x, nullptr, hoff, I, samples, Hi, partial, nblk, ctl, host, nullptr, lds);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -248,8 +290,10 @@ int stb_pr_predict(const stb_rest_view &r, const stb_cnts_ro &c, const stb_cust_
   return 0;
 }
 
-int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned samples, double *d_Hi, double *Hi_host,
-                   double *total_host, stb_predict_info_t *info, const uint64_t *d_skipped, hipStream_t st, const char *who) {
+// log: k_gh_sum on (d_p, d_A) instead of k_heldout_sum on d_p
+static int pr_heldout(bool log, const double *d_p, const double *d_A, const uint64_t *d_hoff, int I, unsigned samples,
+                      double *d_Hi, double *Hi_host, double *total_host, stb_predict_info_t *info, const uint64_t *d_skipped,
+                      hipStream_t st, const char *who) {
   if (I == 0) {
     if (total_host) *total_host = 0.0;
     if (info) memset(info, 0, sizeof(*info));
@@ -261,8 +305,12 @@ int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned sa
     return stb_fail("%s: no launch geometry for I=%d", who, I);
   if (stb_tset_ready(pr, who) || stb_tset_room(pr, tg.need, STB_TG_CAP0_BLOCKS, sizeof(double), who)) return 1;
   HIPCHK(hipMemsetAsync(pr.d_ctl, 0, 64, st));
-  STB_LAUNCH(k_heldout_sum, dim3(tg.gx), dim3(64 * tg.waves), st, d_p, d_hoff, (uint64_t)I, (double)samples, d_Hi, (double *)pr.d_buf,
-             tg.nblk, pr.d_ctl, pr.h_out_dev, (const unsigned long long *)d_skipped);
+  if (log)
+    STB_LAUNCH(k_gh_sum, dim3(tg.gx), dim3(64 * tg.waves), st, d_p, d_A, d_hoff, (uint64_t)I, (double)samples, d_Hi,
+               (double *)pr.d_buf, tg.nblk, pr.d_ctl, pr.h_out_dev);
+  else
+    STB_LAUNCH(k_heldout_sum, dim3(tg.gx), dim3(64 * tg.waves), st, d_p, d_hoff, (uint64_t)I, (double)samples, d_Hi,
+               (double *)pr.d_buf, tg.nblk, pr.d_ctl, pr.h_out_dev, (const unsigned long long *)d_skipped);
   HIPCHK(hipGetLastError());
   if (d_Hi && Hi_host) HIPCHK(hipMemcpyAsync(Hi_host, d_Hi, sizeof(double) * (size_t)I, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -275,6 +323,16 @@ int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned sa
     info->skipped = hc[3];
   }
   return 0;
+}
+
+int stb_pr_heldout(const double *d_p, const uint64_t *d_hoff, int I, unsigned samples, double *d_Hi, double *Hi_host,
+                   double *total_host, stb_predict_info_t *info, const uint64_t *d_skipped, hipStream_t st, const char *who) {
+  return pr_heldout(false, d_p, nullptr, d_hoff, I, samples, d_Hi, Hi_host, total_host, info, d_skipped, st, who);
+}
+
+int stb_pr_heldout_log(const double *d_x, const double *d_A, unsigned samples, const uint64_t *d_hoff, int I, double *d_Hi,
+                       double *Hi_host, double *total_host, stb_predict_info_t *info, hipStream_t st, const char *who) {
+  return pr_heldout(true, d_x, d_A, d_hoff, I, samples, d_Hi, Hi_host, total_host, info, nullptr, st, who);
 }
 
 extern "C" int stb_predict_dishes(double a, const double *d_bpar, int I, const uint64_t *d_koff, const uint32_t *d_n,

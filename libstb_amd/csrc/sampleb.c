@@ -74,6 +74,7 @@ void stb_sampleb_cache_clear(void) {
   stb_hj_release();
   stb_lj_release();
   stb_pr_release();
+  stb_gh_release();
   stb_seat_release();
 }
 

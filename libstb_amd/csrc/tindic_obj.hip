@@ -54,6 +54,12 @@ struct stb_tindic {
   double *d_gpar;       // mu, tau [maxK x obs_D each], then the statistics' mean and Q [maxK x obs_D each]
   uint32_t *d_gn;       // [maxK] the statistics' counts
   bool g_have;          // mu and tau hold values (stb_tindic_set_gauss, or a stb_tindic_sample_gauss that succeeded)
+  // the observation held-out set (stb_tindic_set_heldout_obs): storage of its own, apart from d_hoff / d_hcls / d_pacc
+  uint64_t *d_ghoff;    // [I + 1] (null: no set)
+  double *d_gy;         // [gHc x obs_D]
+  double *d_gacc;       // M [gHc], then A [gHc]: the log-domain accumulator pairs
+  uint64_t gHc;
+  unsigned gsamples;    // states accumulated
   unsigned long long *d_info, *h_info;  // {skipped, stuck} on the device, and pinned
   void *d_cgs;          // the class draw's scratch (classgen.hip), from the buffer cache: kept while the matrix keeps its shape
   size_t cgs_bytes;
@@ -130,8 +136,20 @@ static int ti_not_obs(const stb_tindic_t *s, const char *who) {
                   "scaled by its own maximum, and its classes are the customers' indices", who);
 }
 
+// the observation held-out set, freed (the caller has waited for whatever reads it)
+static void ti_drop_gh(stb_tindic_t *s) {
+  void *dev[] = {s->d_ghoff, s->d_gy, s->d_gacc};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  s->d_ghoff = nullptr;
+  s->d_gy = s->d_gacc = nullptr;
+  s->gHc = 0;
+  s->gsamples = 0;
+}
+
 // the observations and what goes with them, freed (the caller has waited for whatever reads them)
 static void ti_drop_obs(stb_tindic_t *s) {
+  ti_drop_gh(s);
   void *dev[] = {s->d_x, s->d_gpar, s->d_gn};
   for (void *p : dev)
     if (p) (void)hipFree(p);
@@ -1819,7 +1837,24 @@ extern "C" int stb_tindic_set_obs(stb_tindic_t *s, const double *x_host, unsigne
       if (p) (void)hipFree(p);
     return 1;
   }
+  // (new observations of the same D keep the observation held-out set and its accumulator; another D drops them)
+  const bool keep_gh = s->d_ghoff && s->obs_D == D;
+  uint64_t *ghoff = s->d_ghoff;
+  double *gy = s->d_gy, *gacc = s->d_gacc;
+  const uint64_t gHc = s->gHc;
+  const unsigned gsamples = s->gsamples;
+  if (keep_gh) {
+    s->d_ghoff = nullptr;
+    s->d_gy = s->d_gacc = nullptr;
+  }
   ti_drop_obs(s);
+  if (keep_gh) {
+    s->d_ghoff = ghoff;
+    s->d_gy = gy;
+    s->d_gacc = gacc;
+    s->gHc = gHc;
+    s->gsamples = gsamples;
+  }
   ti_drop_cgs(s);
   if (s->d_cls) (void)hipFree(s->d_cls);
   if (s->d_lik) (void)hipFree(s->d_lik);
@@ -1901,4 +1936,116 @@ extern "C" int stb_tindic_gauss_logml(stb_tindic_t *s, const stb_gauss_prior_t *
   stb_device_scope dev(s->dev);
   if (stb_gs_stats(s->d_x, s->obs_D, s->d_cust, s->C, s->maxK, s->d_gn, ti_gmean(s), ti_gQ(s), nullptr, s->st, who)) return 1;
   return stb_gs_logml(s->d_gn, ti_gmean(s), ti_gQ(s), s->maxK, s->obs_D, prior, total, s->st, who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// held-out points under Gaussian observations (the kernels are gauss.hip's and predict.hip's k_gh_sum)
+
+extern "C" int stb_tindic_set_heldout_obs(stb_tindic_t *s, const uint64_t *hoff_host, const double *y_host) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_set_heldout_obs";
+  if (ti_obs_ready(s, false, who)) return 1;
+  uint64_t Hc = 0;
+  if (hoff_host) {
+    if (hoff_host[0] != 0) return stb_fail("%s: hoff[0]=%llu (must be 0)", who, (unsigned long long)hoff_host[0]);
+    for (int i = 0; i < s->I; i++)
+      if (hoff_host[i + 1] < hoff_host[i]) return stb_fail("%s: hoff[%d] < hoff[%d]", who, i + 1, i);
+    Hc = hoff_host[s->I];
+    if (Hc && !y_host) return stb_fail("%s: the held-out points are required", who);
+    for (uint64_t j = 0; j < Hc * s->obs_D; j++)
+      if (!std::isfinite(y_host[j])) return stb_fail("%s: y[%llu]=%g (must be finite)", who, (unsigned long long)j, y_host[j]);
+  }
+  stb_device_scope dev(s->dev);
+  int rc = 0;
+  uint64_t *d_hoff = nullptr;
+  double *d_y = nullptr, *d_acc = nullptr;
+  if (hipStreamSynchronize(s->st) != hipSuccess) rc = STB_STREAM_FAIL(who);
+  if (!rc && hoff_host) {
+    const size_t Hs = Hc ? Hc : 1;
+    if (hipMalloc((void **)&d_hoff, sizeof(uint64_t) * ((size_t)s->I + 1)) != hipSuccess ||
+        hipMalloc((void **)&d_y, sizeof(double) * Hs * s->obs_D) != hipSuccess || hipMalloc((void **)&d_acc, sizeof(double) * 2 * Hs) != hipSuccess)
+      rc = stb_fail("%s: out of device memory for %llu held-out points", who, (unsigned long long)Hc);
+    if (!rc && (hipMemcpy(d_hoff, hoff_host, sizeof(uint64_t) * ((size_t)s->I + 1), hipMemcpyHostToDevice) != hipSuccess ||
+                (Hc && hipMemcpy(d_y, y_host, sizeof(double) * Hc * s->obs_D, hipMemcpyHostToDevice) != hipSuccess)))
+      rc = STB_STREAM_FAIL(who);
+    if (!rc) rc = stb_gs_heldout_reset(d_acc, d_acc + Hs, Hs, s->st);
+    if (!rc && hipStreamSynchronize(s->st) != hipSuccess) rc = STB_STREAM_FAIL(who);
+  }
+  if (rc) {  // the set the object had stays
+    void *fresh[] = {d_hoff, d_y, d_acc};
+    for (void *p : fresh)
+      if (p) (void)hipFree(p);
+    return rc;
+  }
+  ti_drop_gh(s);
+  s->d_ghoff = d_hoff;
+  s->d_gy = d_y;
+  s->d_gacc = d_acc;
+  s->gHc = Hc;
+  s->gsamples = 0;
+  return 0;
+}
+
+// the accumulator's halves: M, then A (a set without points holds one pair)
+static double *ti_gaccM(const stb_tindic_t *s) { return s->d_gacc; }
+static double *ti_gaccA(const stb_tindic_t *s) { return s->d_gacc + (s->gHc ? s->gHc : 1); }
+
+static int ti_gh_ready(stb_tindic_t *s, const char *who) {
+  if (ti_obs_ready(s, false, who)) return 1;
+  if (!s->d_ghoff) return stb_fail("%s: no held-out points are set (stb_tindic_set_heldout_obs)", who);
+  return 0;
+}
+
+extern "C" int stb_tindic_gauss_heldout(stb_tindic_t *s, double a, const double *bpar, unsigned flags, double *total,
+                                        double *Hi_host, double *resp_host, stb_predict_info_t *info) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_gauss_heldout";
+  if (ti_obs_ready(s, true, who)) return 1;
+  if (!total) return stb_fail("%s: total is required", who);
+  if (!s->d_ghoff) return stb_fail("%s: no held-out points are set (stb_tindic_set_heldout_obs)", who);
+  if (flags & ~STB_GH_ACCUMULATE) return stb_fail("%s: unknown flags 0x%x", who, flags);
+  if (ti_pr_ready(s, a, bpar, 0, false, who)) return 1;
+  const bool accumulate = (flags & STB_GH_ACCUMULATE) != 0;
+  if (accumulate && s->gsamples == 0xffffffffu) return stb_fail("%s: the sample count is full (stb_tindic_gauss_heldout_reset)", who);
+  stb_device_scope dev(s->dev);
+  if (stb_hb_obj_stage(&s->hb, s->I, s->d_bpar, bpar, s->st, who)) return 1;
+  const unsigned K = s->maxK;
+  const size_t Hs = s->gHc ? s->gHc : 1;
+  stb_pool_scratch sc(s->st);
+  double *d_theta = nullptr, *d_ell = nullptr, *d_Hi = nullptr, *d_resp = nullptr;
+  if (sc.take(&d_theta, sizeof(double) * (size_t)(s->I ? s->I : 1) * K) != hipSuccess ||
+      (!accumulate && sc.take(&d_ell, sizeof(double) * Hs) != hipSuccess) ||
+      (Hi_host && sc.take(&d_Hi, sizeof(double) * (size_t)(s->I ? s->I : 1)) != hipSuccess) ||
+      (resp_host && sc.take(&d_resp, sizeof(double) * Hs * K) != hipSuccess))
+    return stb_fail("%s: out of device memory for %llu held-out points", who, (unsigned long long)s->gHc);
+  if (stb_pr_predict(ti_rest(s, a), ti_counts(s), stb_cust_ro{}, stb_lik_view{}, {d_theta, K}, 0, s->st, who)) return 1;
+  if (stb_gs_heldout(d_theta, K, s->I, s->d_ghoff, s->d_gy, s->obs_D, ti_gmu(s), ti_gtau(s), K, d_ell, d_resp, d_resp ? K : 0,
+                     accumulate ? ti_gaccM(s) : nullptr, accumulate ? ti_gaccA(s) : nullptr, s->st, who))
+    return 1;
+  if (d_resp && s->gHc &&
+      hipMemcpyAsync(resp_host, d_resp, sizeof(double) * s->gHc * K, hipMemcpyDeviceToHost, s->st) != hipSuccess)
+    return STB_STREAM_FAIL(who);
+  const unsigned samples = accumulate ? ++s->gsamples : 1u;
+  return sc.last(stb_pr_heldout_log(accumulate ? ti_gaccM(s) : d_ell, accumulate ? ti_gaccA(s) : nullptr, samples, s->d_ghoff, s->I,
+                                    d_Hi, Hi_host, total, info, s->st, who));
+}
+
+extern "C" int stb_tindic_gauss_heldout_reset(stb_tindic_t *s) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_gauss_heldout_reset";
+  if (ti_gh_ready(s, who)) return 1;
+  stb_device_scope dev(s->dev);
+  if (stb_gs_heldout_reset(ti_gaccM(s), ti_gaccA(s), s->gHc ? s->gHc : 1, s->st)) return 1;
+  s->gsamples = 0;
+  return 0;
+}
+
+extern "C" int stb_tindic_gauss_heldout_get(stb_tindic_t *s, double *M_out, double *A_out, unsigned *samples) {
+  STB_ENTRY;
+  const char *who = "stb_tindic_gauss_heldout_get";
+  if (ti_gh_ready(s, who)) return 1;
+  stb_device_scope dev(s->dev);
+  if (ti_fetch(s, {{M_out, ti_gaccM(s), sizeof(double) * s->gHc}, {A_out, ti_gaccA(s), sizeof(double) * s->gHc}}, who)) return 1;
+  if (samples) *samples = s->gsamples;
+  return 0;
 }
